@@ -1,10 +1,21 @@
 #!/usr/bin/env python3
 """Headline benchmark: persons/s of the ViTPose hot path on N MI355X (BASELINE.json).
 
-    python bench.py [--gpus N --steps K --warmup W] [--dtype fp16|bf16] [--batch 256]
+    python bench.py [--gpus N --steps K --warmup W] [--dtype fp16|bf16] [--batch 256] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 (`python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches those N ranks itself.)
+
+A plain run sets up, warms up (W steps), times EXACTLY K steps, writes the keypoints of the last timed step when --dump-outputs is
+given and prints the headline line: `metric` / `value` (persons/s over the timed steps) / `unit` / `higher_is_better` / `dtype` /
+`ms_per_step` (wall time of one timed step).  Nothing else runs unless asked for: no event records, no checks, no extra passes.
+
+--full adds everything described below, as every run did before the option existed (each leg can still be dropped with its --no-*
+option); --breakdown and --strong stay separate opt-ins.
+
+--dump-outputs DIR writes DIR/keypoints.npy: the float32 [B, K, 3] (y, x, conf) keypoints the timed path left in HBM after its last
+step (N > 1: the all-gathered [N*B, K, 3] of rank 0).  Weights and crops are seeded, so the same arguments give the same inputs on
+every run and two builds can be compared output for output.
 
 One "step" = one pass of the whole hot path (crop batch resident in HBM -> patch embed
 -> ViT encoder -> deconv head -> heatmaps -> arg-max/DARK-UDP decode -> keypoints in
@@ -13,7 +24,7 @@ HBM, + the RCCL all-gather of keypoints when N > 1) over one batch of 256 synthe
 Workload = BASELINE.json configs[1]: ViTPose-B COCO-17, batch 256, seeded random
 weights of that architecture, synthetic uniform-noise crops.
 
-Prints ONE JSON line on rank 0 with `roofline` (the GEMM family with the largest share of the step, timed live
+With --full, prints ONE JSON line on rank 0 with `roofline` (the GEMM family with the largest share of the step, timed live
 with HIP events on the library's stream inside the timed region; `kernel` = what the library says it launched, `traffic` read
 from the committed PMC passes as `traffic_source` states), `clock_under_load` (N=1: shader clock and board power sampled with rocm-smi during an
 untimed replay of the step -- the chip runs these GEMMs at its power limit, well below the 2.4 GHz behind `roofline.peak`), `step_ms` percentiles, `host_persons_per_sec` (N=1: pinned host
@@ -429,7 +440,14 @@ def main():
     ap.add_argument('--breakdown', action='store_true', help='extra untimed pass with every kernel family timed (stderr)')
     ap.add_argument('--strong', action='store_true', help='also measure the strong-scaled frame of BASELINE configs[3] (default when WORLD_SIZE > 1)')
     ap.add_argument('--force-dist', action='store_true', help='run the RCCL code path (process group, all-gather, barrier) even with one rank')
+    ap.add_argument('--full', action='store_true',
+                    help='beyond the headline: roofline + per-family GEMM timing (HIP events), step-time percentiles, the all-gather check and '
+                         'share, host-visible rate, clock / power under load, CPU baselines, the strong-scaled frame when WORLD_SIZE > 1')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the keypoints of the last timed step to DIR/keypoints.npy (float32)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:   # started plainly (as the driver starts N = 1): spawn the ranks ourselves
         rc = self_launch(args.gpus, sys.argv[1:], json_fd)
@@ -486,48 +504,55 @@ def main():
     step, fence = H.step, H.fence
 
     fams = list(FAMILIES)
-    eng.set_profiling(fams)      # warm-up pass with all four encoder GEMM families timed: picks the dominant one
-    eng.reset_profile()
+    if args.full:
+        eng.set_profiling(fams)      # warm-up pass with all four encoder GEMM families timed: picks the dominant one
+        eng.reset_profile()
     for _ in range(args.warmup):
         step()
     fence()
-    wprof = eng.profile()
-    dom = max(fams, key=lambda f: wprof[f]['ms']) if args.warmup > 0 else 'gemm_fc1'
-    # the four encoder GEMM families are timed live (HIP events around every launch, on the library's stream); the one with
+    if args.full:
+        wprof = eng.profile()
+        dom = max(fams, key=lambda f: wprof[f]['ms']) if args.warmup > 0 else 'gemm_fc1'
+    # --full: the four encoder GEMM families are timed live (HIP events around every launch, on the library's stream); the one with
     # the largest share of the step is reported as the dominant kernel (rocprofv3 --stats of the same command: profiles/)
     # batches of <= 16 crops replay a captured hipGraph, which event records inside the chunk would switch off: there the timed
     # region runs unprofiled and the dominant kernel's launch time is the warm-up pass's (roofline.timed = 'warm-up pass')
-    live = B > 16 and not args.no_live_events
-    eng.set_profiling([dom] if live else False)     # timed region: only the dominant family carries event records (2 per launch)
-    eng.reset_profile()
-    if not live:
+    graph_path = B <= 16 or args.no_live_events
+    live = args.full and not graph_path
+    if args.full:
+        eng.set_profiling([dom] if live else False)     # timed region: only the dominant family carries event records (2 per launch)
+        eng.reset_profile()
+    if graph_path:
         for _ in range(3):       # first sighting runs eagerly, the second captures the graph
             step()
     dt, per_rank = H.timed(args.steps)              # EXACTLY --steps steps between two fences, max over ranks
-    prof = eng.profile() if live else wprof
-    kernels = {f: eng.profile_kernel(f) for f in fams}   # the library's own record of what each family ran on
-    eng.set_profiling(False)
-    H.check_gathered(B)
-    ag_ms = H.allgather_ms()
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        kp = d_all if use_dist else d_out           # what the caller of the timed step receives, as of its last step
+        np.save(os.path.join(args.dump_outputs, 'keypoints.npy'), kp.detach().cpu().numpy().astype(np.float32))
+    if args.full:
+        prof = eng.profile() if live else wprof
+        kernels = {f: eng.profile_kernel(f) for f in fams}   # the library's own record of what each family ran on
+        eng.set_profiling(False)
+        H.check_gathered(B)
+        ag_ms = H.allgather_ms()
 
-    # per-step distribution (separate, untimed-for-`value` pass with a host synchronisation after every step)
-    step_ms = []
-    for _ in range(min(args.steps, 50)):
-        fence()
-        t1 = time.perf_counter()
-        step()
-        fence()
-        step_ms.append((time.perf_counter() - t1) * 1e3)
-    host_rate = None
-    if rank == 0 and world == 1 and not args.no_host_path and not hook:
-        host_rate = host_path_rate(eng, crops_u8, K)
-
-    clock = None
-    if rank == 0 and world == 1 and not args.no_clock and not hook:
-        clock = clock_power_under_load(step, fence)
+    step_ms, host_rate, clock = [], None, None
+    if args.full:
+        # per-step distribution (separate, untimed-for-`value` pass with a host synchronisation after every step)
+        for _ in range(min(args.steps, 50)):
+            fence()
+            t1 = time.perf_counter()
+            step()
+            fence()
+            step_ms.append((time.perf_counter() - t1) * 1e3)
+        if rank == 0 and world == 1 and not args.no_host_path and not hook:
+            host_rate = host_path_rate(eng, crops_u8, K)
+        if rank == 0 and world == 1 and not args.no_clock and not hook:
+            clock = clock_power_under_load(step, fence)
 
     strong = None
-    if use_dist and (world > 1 or args.strong):
+    if use_dist and (args.strong or (args.full and world > 1)):
         if hook:
             strong = strong_scaling_config4(world, rank, dev, args.dtype, steps=3, warmup=1, n_total=7, engine_factory=strong_factory, dist=dist)
         else:
@@ -546,23 +571,6 @@ def main():
 
     if rank == 0:
         persons_s = world * B * args.steps / dt
-        d = prof[dom]
-        ach = d['flops'] / (d['ms'] * 1e-3) if d['ms'] > 0 else 0.0
-        peak = PEAK_MFMA_FP8 if 'gemm8f_kernel' in kernels[dom] else PEAK_MFMA_16BIT     # the pipe the dominant kernel runs on
-        traffic, traffic_source = pmc_traffic(args, kernels[dom])
-        # one number per kernel in the line: the dominant family from the TIMED region (the same events `roofline` uses), the other three
-        # from the warm-up pass (all four families event-timed there, which perturbs the step slightly) -- each entry says which
-        def fam_entry(f):
-            src = prof if (live and f == dom) else wprof
-            steps_ = args.steps if (live and f == dom) else max(args.warmup, 1)
-            what = FAMILIES[f]
-            if kernels[f].startswith('qkvattn_kernel'):   # the fused kernel is accounted under the qkv family: its flops and time include the attention core,
-                what = 'attn.qkv (+LayerNorm fold +bias) + attention core (softmax, P.V) as ONE kernel; flops = both; the `attention` family is empty'
-            return {'what': what, 'kernel': kernels[f], 'timed': 'timed region' if (live and f == dom) else 'warm-up pass',
-                    'ms_per_step': round(src[f]['ms'] / steps_, 4), 'avg_launch_us': round(1e3 * src[f]['ms'] / max(src[f]['launches'], 1), 2),
-                    'tflops': round(src[f]['flops'] / max(src[f]['ms'], 1e-9) / 1e9, 1),
-                    'algorithmic_gbps': round(src[f]['bytes'] / max(src[f]['ms'], 1e-9) / 1e6, 1)}
-        per_family = {f: fam_entry(f) for f in fams}
         line = {
             'metric': 'persons_per_sec', 'value': round(persons_s, 1), 'unit': 'persons/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -575,23 +583,44 @@ def main():
                        'gflop_per_person': round(shp.gflop_per_person(), 3)},
             'model_tflops': round(persons_s * shp.gflop_per_person() / 1e3, 1),
             'model_frac_of_mfma_peak': round(persons_s * shp.gflop_per_person() * 1e9 / PEAK_MFMA_16BIT, 4),
-            'roofline': {'bound': 'mfma', 'kernel': kernels[dom], 'kernel_source': 'vp_profile_kernel (written by the launch code)',
-                         'what': FAMILIES[dom],
-                         'achieved': round(ach / 1e12, 2), 'peak': peak / 1e12, 'unit': 'TFLOP/s',
-                         'frac': round(ach / peak, 4), 'traffic': traffic, 'traffic_source': traffic_source,
-                         'timed': 'live, HIP events around every launch of the timed region' if live else 'warm-up pass (no event records in the timed region)',
-                         'launches': d['launches'], 'avg_launch_ms': round(d['ms'] / max(d['launches'], 1), 5),
-                         'flops_per_launch': d['flops'] / max(d['launches'], 1),
-                         'algorithmic_bytes_per_launch': d['bytes'] / max(d['launches'], 1)},
-            'clock_under_load': clock,
-            'encoder_gemms': per_family,
-            'step_ms': {'p10': round(float(np.percentile(step_ms, 10)), 4), 'p50': round(float(np.percentile(step_ms, 50)), 4),
-                        'p90': round(float(np.percentile(step_ms, 90)), 4), 'n': len(step_ms), 'note': 'one host synchronisation per step'},
-            'host_persons_per_sec': None if host_rate is None else round(host_rate, 1),
-            # diagnosis of a multi-GPU run: every rank's own time for the same steps, and the exchange alone
+            # diagnosis of a multi-GPU run: every rank's own time for the same steps
             'per_rank_ms_per_step': [round(v / args.steps * 1e3, 4) for v in per_rank],
-            'allgather_ms': None if ag_ms is None else round(ag_ms, 4),
+            'full': args.full,
         }
+        if args.full:
+            d = prof[dom]
+            ach = d['flops'] / (d['ms'] * 1e-3) if d['ms'] > 0 else 0.0
+            peak = PEAK_MFMA_FP8 if 'gemm8f_kernel' in kernels[dom] else PEAK_MFMA_16BIT     # the pipe the dominant kernel runs on
+            traffic, traffic_source = pmc_traffic(args, kernels[dom])
+            # one number per kernel in the line: the dominant family from the TIMED region (the same events `roofline` uses), the other three
+            # from the warm-up pass (all four families event-timed there, which perturbs the step slightly) -- each entry says which
+            def fam_entry(f):
+                src = prof if (live and f == dom) else wprof
+                steps_ = args.steps if (live and f == dom) else max(args.warmup, 1)
+                what = FAMILIES[f]
+                if kernels[f].startswith('qkvattn_kernel'):   # the fused kernel is accounted under the qkv family: its flops and time include the attention core,
+                    what = 'attn.qkv (+LayerNorm fold +bias) + attention core (softmax, P.V) as ONE kernel; flops = both; the `attention` family is empty'
+                return {'what': what, 'kernel': kernels[f], 'timed': 'timed region' if (live and f == dom) else 'warm-up pass',
+                        'ms_per_step': round(src[f]['ms'] / steps_, 4), 'avg_launch_us': round(1e3 * src[f]['ms'] / max(src[f]['launches'], 1), 2),
+                        'tflops': round(src[f]['flops'] / max(src[f]['ms'], 1e-9) / 1e9, 1),
+                        'algorithmic_gbps': round(src[f]['bytes'] / max(src[f]['ms'], 1e-9) / 1e6, 1)}
+            per_family = {f: fam_entry(f) for f in fams}
+            line.update({
+                'roofline': {'bound': 'mfma', 'kernel': kernels[dom], 'kernel_source': 'vp_profile_kernel (written by the launch code)',
+                             'what': FAMILIES[dom],
+                             'achieved': round(ach / 1e12, 2), 'peak': peak / 1e12, 'unit': 'TFLOP/s',
+                             'frac': round(ach / peak, 4), 'traffic': traffic, 'traffic_source': traffic_source,
+                             'timed': 'live, HIP events around every launch of the timed region' if live else 'warm-up pass (no event records in the timed region)',
+                             'launches': d['launches'], 'avg_launch_ms': round(d['ms'] / max(d['launches'], 1), 5),
+                             'flops_per_launch': d['flops'] / max(d['launches'], 1),
+                             'algorithmic_bytes_per_launch': d['bytes'] / max(d['launches'], 1)},
+                'clock_under_load': clock,
+                'encoder_gemms': per_family,
+                'step_ms': {'p10': round(float(np.percentile(step_ms, 10)), 4), 'p50': round(float(np.percentile(step_ms, 50)), 4),
+                            'p90': round(float(np.percentile(step_ms, 90)), 4), 'n': len(step_ms), 'note': 'one host synchronisation per step'},
+                'host_persons_per_sec': None if host_rate is None else round(host_rate, 1),
+                'allgather_ms': None if ag_ms is None else round(ag_ms, 4),   # the exchange alone
+            })
         if hook:   # the engine was swapped by VP_BENCH_ENGINE (CPU tests of the launcher): the numbers above are NOT a measurement of the HIP path
             line['engine'] = 'hook:' + hook
             line['valid'] = False
@@ -602,10 +631,10 @@ def main():
         if strong is not None:
             strong.pop('keypoints', None)
             line['strong_scaling_config4'] = strong
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(args.variant, args.dataset)
             line['cpu_baseline_batched'] = cpu_baseline_batched(args.variant, args.dataset, line['cpu_baseline']['cores'])
-        else:
+        elif args.full:
             line['cpu_baseline'] = None
             line['cpu_baseline_batched'] = None
         os.write(json_fd, (json.dumps(line) + '\n').encode())

@@ -194,7 +194,8 @@ def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with WORLD_SIZE unset -- the form the driver uses for N = 1 -- must spawn its two ranks itself
     (torch.distributed.run on 127.0.0.1) and still print exactly ONE JSON line on stdout, from rank 0 (it
     used to die on an assert).  The ranks run bench.main() end to end over gloo with the fake engine (VP_BENCH_ENGINE hook): argument
-    hand-through, process-group set-up, weak-scaling Harness, the strong-scaled frame, the JSON assembly."""
+    hand-through, process-group set-up, weak-scaling Harness, the strong-scaled frame, the JSON assembly (--full: the all-gather
+    share and the strong-scaled frame are not part of a plain run)."""
     import json
     import subprocess
     import sys
@@ -202,7 +203,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env['VP_BENCH_ENGINE'] = 'fake_bench_engine:make'
     env['PYTHONPATH'] = os.path.join(root, 'tests') + os.pathsep + root + os.pathsep + env.get('PYTHONPATH', '')
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full'],
                        capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -214,3 +215,35 @@ def test_bench_launches_its_own_ranks(tmp_path):
     sc = j['strong_scaling_config4']
     assert sc['scaling'] == 'strong' and sc['crops_per_rank'] == 4 and len(sc['per_rank_ms_per_frame']) == 2
     assert 'launching' in r.stderr      # the launcher path ran (not an externally provided WORLD_SIZE)
+
+
+@pytest.mark.parametrize('gpus', [1, 2])
+def test_bench_plain_run_is_lean_and_dumps_what_the_timed_path_computed(tmp_path, gpus):
+    """A plain `bench.py --gpus N --steps K --warmup W --dump-outputs DIR` (fake engine, gloo for N = 2): ONE JSON line with the
+    headline fields, none of the --full legs, and DIR/keypoints.npy = the float32 keypoints a caller of the timed step receives
+    (N = 2: the all-gathered batch of every rank), equal to what the engine computes from the seeded crops."""
+    import json
+    import subprocess
+    import sys
+    from fake_bench_engine import rank_crops
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    env['VP_BENCH_ENGINE'] = 'fake_bench_engine:make'
+    env['PYTHONPATH'] = os.path.join(root, 'tests') + os.pathsep + root + os.pathsep + env.get('PYTHONPATH', '')
+    out = tmp_path / 'outputs'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(gpus), '--steps', '4', '--warmup', '2',
+                        '--dump-outputs', str(out)], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, f'stdout must hold exactly one JSON line, got {len(lines)}: {r.stdout[:500]}'
+    j = json.loads(lines[0])
+    assert j['metric'] == 'persons_per_sec' and j['unit'] == 'persons/s' and j['higher_is_better'] is True and j['dtype'] == 'fp16'
+    assert j['value'] > 0 and j['ms_per_step'] > 0 and j['steps'] == 4 and j['warmup'] == 2 and j['n_gpus'] == gpus
+    assert abs(j['value'] - gpus * 3 * 1e3 / j['ms_per_step']) <= 0.01 * j['value']
+    assert j['full'] is False
+    for k in ('roofline', 'encoder_gemms', 'step_ms', 'clock_under_load', 'host_persons_per_sec', 'allgather_ms', 'cpu_baseline',
+              'strong_scaling_config4'):
+        assert k not in j, k
+    kp = np.load(out / 'keypoints.npy')
+    ref = torch.cat([FakeEngine.expected(rank_crops(rank)) for rank in range(gpus)]).numpy()
+    assert kp.dtype == np.float32 and np.array_equal(kp, ref)
