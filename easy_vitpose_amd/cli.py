@@ -47,7 +47,8 @@ def main(argv=None) -> int:
     ap.add_argument('--synthetic', default=None, choices=['s', 'b', 'l', 'h'], help='seeded peaked synthetic checkpoint of this size instead of --model')
     ap.add_argument('--yolo', default=None, help='ultralytics detector weights')
     ap.add_argument('--boxes', default=None, help='JSON file with detector boxes (replaces --yolo)')
-    ap.add_argument('--dataset', default=None)
+    ap.add_argument('--dataset', default=None, help='dataset of the checkpoint (default: from the --model file name); required for a ViTPose+ '
+                    'checkpoint, whose six datasets are coco, aic, mpii, ap10k, apt36k, wholebody')
     ap.add_argument('--det-class', default=None)
     ap.add_argument('--model-name', default=None, choices=['s', 'b', 'l', 'h'])
     ap.add_argument('--yolo-size', type=int, default=320)
@@ -66,10 +67,10 @@ def main(argv=None) -> int:
     assert (args.model is None) != (args.synthetic is None), 'give exactly one of --model / --synthetic'
 
     from easy_vitpose_amd import VitInference
-    from easy_vitpose_amd.configs import infer_dataset_by_path, model_shape
+    from easy_vitpose_amd.configs import model_shape
     from easy_vitpose_amd.jsonio import COCO17_JOINTS, save_json
     frames, is_video = _read_frames(args.input, args.rotate)
-    dataset = args.dataset or (infer_dataset_by_path(args.model) if args.model else 'coco')
+    dataset = args.dataset or ('coco' if not args.model else None)   # --model: VitInference reads it from the file name (a ViTPose+ file needs --dataset)
 
     detector = args.yolo
     if args.boxes is not None:
@@ -109,7 +110,7 @@ def main(argv=None) -> int:
         stem = base[:base.rfind('.')] if '.' in base else base
         path = os.path.join(out_dir, stem + '_result.json')
         print('>>> Saving output json')
-        save_json(path, keypoints, COCO17_JOINTS if model._vit_pose.K == 17 and dataset == 'coco' else None)
+        save_json(path, keypoints, COCO17_JOINTS if model._vit_pose.K == 17 and model.dataset == 'coco' else None)
     return 0
 
 

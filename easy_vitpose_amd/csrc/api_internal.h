@@ -100,7 +100,8 @@ struct vp_ctx {
     int next_slot = 0;
     // small batches: the whole forward + decode of a chunk captured once per (n, input format, source pointer) into a hipGraph and
     // replayed (170+ launches of a few microseconds each are launch-bound below ~16 crops); VP_GRAPH=0 disables
-    struct GraphEntry { hipGraphExec_t exec = nullptr; int n = 0, fmt = -1, seen = 0; bool no_graph = false; const void* src = nullptr; const int32_t* wh = nullptr; float* out = nullptr; };
+    struct GraphEntry { hipGraphExec_t exec = nullptr; int n = 0, fmt = -1, seen = 0; bool no_graph = false; const void* src = nullptr; const int32_t* wh = nullptr; float* out = nullptr;
+                        int expert = 0; };   // expert: a ViTPose+ handle's active expert is baked into the captured launches (fc2 weights, head, K)
     GraphEntry graphs[4];
     int graph_victim = 0;
     bool fuse_head = true;            // VP_FUSE_HEAD=0: deconv2 and the final 1x1 conv as two launches at every batch size
@@ -132,6 +133,22 @@ struct vp_ctx {
     uint8_t* frame_stage = nullptr;   // device copy of the current video frame (vp_infer_frame)
     size_t frame_cap = 0;
     int32_t* cparams = nullptr;       // per-crop geometry [max_batch, 8]
+    // ViTPose+ (multi-dataset "mixture of experts") handle, vp_load_weights on a state dict with backbone.blocks.*.mlp.experts.*: mlp.fc2 of block l is one full
+    // [D, 4D] matrix + [D] bias per expert (the split model's: shared rows then the expert's P rows), blocks[l].w_fc2 / b_fc2 point at expert 0 and expert e lies
+    // e * fc2_w_stride / fc2_b_stride elements behind; one keypoint head per expert.  `expert` = the active one (vp_set_expert): its fc2 slice, its head and its
+    // K (= Kp) serve every existing entry point.  Kmax sizes every buffer indexed by keypoint (== Kp on a plain handle).
+    struct Head { uint16_t *w_d1 = nullptr, *w_d2 = nullptr, *w_fin = nullptr; float *b_d1 = nullptr, *b_d2 = nullptr, *b_fin = nullptr; size_t fin_rows = 0; int K = 0; };
+    int Kmax = 0;
+    int n_experts = 0, part_features = 0, expert = 0;
+    size_t fc2_w_stride = 0, fc2_b_stride = 0;
+    std::vector<Head> ex_heads;
+    // vp_infer_experts, a chunk that mixes experts: the expert of every encoder crop (device [B], padding crops repeat the last one) and the crop index of
+    // every expert change; while set, mlp.fc2 runs all experts in one launch (GemmArgs::expert) on a tile whose rows never span two experts
+    int32_t* expert_ids = nullptr;    // [2 B]: the experts, then the gather order of the chunk's crops (gather_crops_launch)
+    void* mix_stage = nullptr;        // the chunk's crops in the caller's order, before the gather
+    size_t mix_stage_cap = 0;
+    const int32_t* mix_expert = nullptr;
+    std::vector<int> mix_bounds;
     // profiling
     uint32_t prof = 0;   // bit f = time kernel family f
     int gemm_variant[VP_PROF_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // tile cfg per GEMM family, -1 = default rule
@@ -190,9 +207,12 @@ struct Lookup {
         *out = it->second->data;
         return VP_OK;
     }
+    bool has(const std::string& name) const { return map.count(name) != 0; }
+    int64_t numel(const std::string& name) const { auto it = map.find(name); return it == map.end() ? -1 : it->second->numel; }
 };
 
-int pack_deconv(vp_ctx* c, Lookup& lk, int idx, int Cin, uint16_t** w_out, float** b_out);
+int pack_deconv(vp_ctx* c, Lookup& lk, int idx, int Cin, uint16_t** w_out, float** b_out, const std::string& head = "keypoint_head");
+void use_expert(vp_ctx* c, int e);   // make expert e of a ViTPose+ handle the active one (head pointers, Kp)
 
 // ---- vitpose_api.hip
 bool prof_begin(vp_ctx* c, int fam, double flops, double bytes);
@@ -228,7 +248,12 @@ Tile2Pick pick_gemm2_tile(int epi, int M, int N, int K);
 // split-K of a residual GEMM (attn.proj, mlp.fc2) at small batches: S k ranges on tile configuration `variant` (S = 1: no split)
 struct SplitKPick { int S, variant; };
 SplitKPick pick_splitk(int M, int N, int K);
-int pick_run_batch(int n, int D, int limit, int bm192_mask, bool extended, int gemm8_mask);   // the batch the encoder runs for a chunk of n crops (>= n, a multiple of 4 when padded)
+int pick_run_batch(int n, int D, int limit, int bm192_mask, bool extended, int gemm8_mask);
+// ViTPose+ mixed batch: may mlp.fc2 run on a tile of bm rows when the experts change at crops `bounds`?  (no m-tile may span two experts)
+bool expert_tile_ok(int bm, const std::vector<int>& bounds);
+// the crop-aligned tile mlp.fc2 of a mixed batch takes where the rule's tile is not (gemm8_ok: the 8-phase kernel's 192 x 256 tile may run it)
+int expert_fallback_variant(int M, int N, bool gemm8_ok, int* group_m);
+int tile_bm(int variant);   // rows of a tile configuration (0: unknown)   // the batch the encoder runs for a chunk of n crops (>= n, a multiple of 4 when padded)
 constexpr int SPLITK_MAX_S = 8, SPLITK_MAX_CROPS = 32;
 
 // ---- vitpose_api.hip: one GEMM of the path through the tile rules (also what the vp_dbg_gemm* taps launch)

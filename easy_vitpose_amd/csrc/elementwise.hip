@@ -120,6 +120,19 @@ hipError_t flip_merge_launch(float* hm, const float* hm_flipped, const int32_t* 
     return hipGetLastError();
 }
 
+// ViTPose+ mixed batch: dst crop i = src crop idx[i] (crops in expert order).  16-byte pieces; blockIdx.y = destination crop
+__global__ void gather_crops_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, const int32_t* __restrict__ idx, size_t pieces) {
+    const uint4* s = src + (size_t)idx[blockIdx.y] * pieces;
+    uint4* d = dst + (size_t)blockIdx.y * pieces;
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < pieces; j += (size_t)gridDim.x * blockDim.x) d[j] = s[j];
+}
+
+hipError_t gather_crops_launch(const void* src, void* dst, const int32_t* idx, int n, size_t crop_bytes, hipStream_t s) {
+    if (crop_bytes % 16 || n < 0 || n > 65535) return hipErrorInvalidValue;
+    if (n) hipLaunchKernelGGL(gather_crops_kernel, dim3(36, n), dim3(256), 0, s, (const uint4*)src, (uint4*)dst, idx, crop_bytes / 16);
+    return hipGetLastError();
+}
+
 // --------------------------------------------------------------- LayerNorm
 // nn.LayerNorm(eps=1e-6) (vit.py:274) over the fp32 residual stream, one wave per
 // token row, row held in registers (D <= 1280 -> <= 5 float4 per lane), two-pass

@@ -147,7 +147,7 @@ __device__ __forceinline__ void pipe5_half1(f32x4 (&acc)[C::TI][C::TJ], u32x4* f
     }
 }
 
-template <class T, int EPI_, int AMODE, class C>
+template <class T, int EPI_, int AMODE, class C, bool EXPERT = false>
 __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(GemmArgs g) {
     constexpr bool LN_PROD = (EPI_ == EPI_BIAS_RESID_LN || EPI_ == EPI_POS_LN);   // fused-LayerNorm producer variant
     constexpr int EPI = LN_PROD ? EPI_ - 4 : EPI_;                                // arithmetic of the base epilogue
@@ -187,6 +187,11 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(GemmArgs g) {
         tn = bid - tm * tiles_n;
     }
     const int n0 = tn * C::BN, m0 = tm * C::BM;
+    if constexpr (EXPERT) {   // ViTPose+ mlp.fc2 of a mixed batch: this m-tile's crop picks the expert's weight matrix and bias (GemmArgs::expert)
+        const int e = g.expert[m0 / 192];
+        g.W += (size_t)e * g.w_rows * g.K;
+        g.bias += (size_t)e * g.w_rows;
+    }
     const int K = g.K;
     const int klen = (EPI_ == EPI_PARTIAL) ? K / g.splitk : K;   // this workgroup's k range: [kbase, kbase + klen)
     const int kbase = (EPI_ == EPI_PARTIAL) ? split * klen : 0;
@@ -1253,6 +1258,9 @@ template <class T, int EPI, int AMODE, class C>
 static hipError_t launch(const GemmArgs& a, hipStream_t s) {
     if constexpr ((EPI == EPI_BIAS_RESID_LN || EPI == EPI_POS_LN) && C::DIRECT) return hipErrorInvalidValue;
     auto kern = gemm_kernel<T, EPI, AMODE, C>;
+    int ex = 0;   // the residual epilogues' per-crop expert instantiation (ViTPose+, GemmArgs::expert)
+    if constexpr (EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_RESID_LN)
+        if (a.expert) { kern = gemm_kernel<T, EPI, AMODE, C, true>; ex = 1; }
     // fused head: the staged 16-bit tile [BM][BN + 8] may be larger than the operand ring
     constexpr int LDS_BYTES = (EPI == EPI_DECONV_FINAL && C::BM * (C::BN * 2 + 16) > C::LDS) ? C::BM * (C::BN * 2 + 16) : C::LDS;
     constexpr int LN_STAT_BYTES = C::BM * 8;   // (mean, rstd) per tile row behind the ring: used when GemmArgs::ln_part is set
@@ -1260,13 +1268,13 @@ static hipError_t launch(const GemmArgs& a, hipStream_t s) {
     if (a.ln_part && (C::PIPE == 2 || C::PIPE == 3 || C::DIRECT)) return hipErrorInvalidValue;   // the prologue merge lives in the generic loop
     if (C::PIPE == 6 && a.K % 128 != 0) return hipErrorInvalidValue;                                      // two k-blocks per barrier
     if (a.ln_part && (a.ln_tiles & 1)) return hipErrorInvalidValue;   // a row's partial statistics are fetched as 16-byte pieces: ln_tiles * 8 bytes must be a multiple of 16
-    static bool attr_done[64] = {};   // the > 64 KiB LDS opt-in is a per-device function attribute
+    static bool attr_done[2][64] = {};   // the > 64 KiB LDS opt-in is a per-device function attribute
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_done[dev]) {
+    if (dev < 0 || dev >= 64 || !attr_done[ex][dev]) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES + LN_STAT_BYTES);
         if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) attr_done[dev] = true;
+        if (dev >= 0 && dev < 64) attr_done[ex][dev] = true;
     }
     GemmArgs g = a;
     const int tiles_n = (a.N + C::BN - 1) / C::BN;
@@ -1278,8 +1286,8 @@ static hipError_t launch(const GemmArgs& a, hipStream_t s) {
     }
     dim3 grid(AMODE == A_DECONV && a.parity_fast ? tiles * 4 : (EPI == EPI_PARTIAL ? tiles * a.splitk : tiles), AMODE == A_DECONV && !a.parity_fast ? 4 : 1);
     if (a.desc)
-        snprintf(a.desc, a.desc_cap, "gemm_kernel<%s, %d, %d, TileCfg<%d, %d, %d, %d, %d, %d, %d, %d>>", std::is_same<T, F16>::value ? "F16" : "BF16", EPI,
-                 AMODE, C::BM, C::BN, C::BK, C::WM, C::WN, C::STAGES, C::PIPE, C::DIRECT);
+        snprintf(a.desc, a.desc_cap, "gemm_kernel<%s, %d, %d, TileCfg<%d, %d, %d, %d, %d, %d, %d, %d>%s>", std::is_same<T, F16>::value ? "F16" : "BF16", EPI,
+                 AMODE, C::BM, C::BN, C::BK, C::WM, C::WN, C::STAGES, C::PIPE, C::DIRECT, ex ? ", true" : "");
     hipLaunchKernelGGL(kern, grid, dim3(C::NT), LDS_BYTES + (a.ln_part ? LN_STAT_BYTES : 0), s, g);
     return hipGetLastError();
 }
@@ -1375,6 +1383,7 @@ int gemm_tile_bn(int variant) {
 
 hipError_t gemm_launch(int dtype, int epi, const GemmArgs& a, hipStream_t s) {
     if (a.K % 64 != 0 || a.M <= 0 || a.N <= 0) return hipErrorInvalidValue;
+    if (a.expert && ((epi != EPI_BIAS_RESID && epi != EPI_BIAS_RESID_LN) || a.persist || a.M % 192)) return hipErrorInvalidValue;   // per-crop experts: the residual GEMM only
     if (a.variant >= 16 && a.variant <= 18) {   // 16: 256 x 256, 17: 256 x 192, 18: 192 x 256
 #ifdef VP_TOOLS
         static const int stagger_env = [] { const char* e = getenv("VP_G8_STAGGER"); return e ? atoi(e) : -1; }();

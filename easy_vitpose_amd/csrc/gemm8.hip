@@ -73,7 +73,7 @@ __device__ __forceinline__ u32x2 lds_tr16(const char* p) {   // ds_read_b64_tr_b
 
 // EPI: EPI_BIAS / EPI_BIAS_GELU (16-bit output straight from registers, optional LayerNorm-consumer fold, optional
 // 64x64-blocked output) or EPI_BIAS_RESID_LN (two-plane residual stream + row statistics, staged through LDS).
-template <class T, int EPI, class C>
+template <class T, int EPI, class C, bool EXPERT = false>
 __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
     constexpr bool RESID = (EPI == EPI_BIAS_RESID_LN);
     // residual epilogue: 256-wide tiles take it straight from registers (a lane's 16 accumulator columns of a row are 16 consecutive
@@ -117,7 +117,10 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
         const int w8 = C::BM == 256 ? wave * 8 : 0;   // 192-row tiles form the row offset of every piece in issue()
         xb = g.a_blocked ? (const char*)(g.A + ((size_t)(m0 >> 6) * (K >> 6) << 12)) + (size_t)w8 * 128
                          : (const char*)(g.A + (size_t)(m0 + w8) * K);
-        wb = (const char*)(g.W + (size_t)n0 * K);
+        if constexpr (EXPERT)   // ViTPose+ mlp.fc2 of a mixed batch: the tile's expert (GemmArgs::expert) -- also for the NEXT tile the ring prefetches across the boundary
+            wb = (const char*)(g.W + ((size_t)g.expert[m0 / 192] * g.w_rows + n0) * K);
+        else
+            wb = (const char*)(g.W + (size_t)n0 * K);
     };
     // DMA of one slot of K-tile kt (of the issue tile) into ring buffer B
     auto issue = [&](int which, int B, int kt, bool force = false) {
@@ -311,6 +314,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
 
     for (;;) {
         zero_acc();
+        const float* tbias = g.bias;   // the bias of this tile (its expert's: GemmArgs::expert)
+        if constexpr (EXPERT) tbias += (size_t)g.expert[m0 / 192] * g.w_rows;
         const bool has_next = t + tw.nloc < tw.cnt;
         int nm0 = m0, nn0 = n0;   // no next tile: the ring keeps fetching (valid, unused) K-tiles 0 / 1 of this tile
         if (has_next) tw.origin(t + tw.nloc, g.reverse, C::BM, C::BN, nm0, nn0);
@@ -530,7 +535,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
             const uint16_t* aux_lo = aux_hi + g.plane;
             f32x4 bias4[4];
 #pragma unroll
-            for (int f = 0; f < 4; ++f) bias4[f] = *(const f32x4*)(g.bias + nb + f * 4);
+            for (int f = 0; f < 4; ++f) bias4[f] = *(const f32x4*)(tbias + nb + f * 4);
             const bool store = !(VP_ABLATE(g) & 8);
             const int gran = g.N >> 6;
             constexpr int RD = C::BM == 192 ? VP_G8_RESD192 : VP_G8_RESD;   // residual of row group J: hi cols 0-7, hi 8-15, lo 0-7, lo 8-15; fetched RD row groups ahead
@@ -607,7 +612,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
                 f32x4 bias4[C::TI], s4[LN ? C::TI : 1];
                 float2 st[LN ? TJ : 1];
 #pragma unroll
-                for (int f = 0; f < C::TI; ++f) bias4[f] = *(const f32x4*)(g.bias + nb + fcol(f));
+                for (int f = 0; f < C::TI; ++f) bias4[f] = *(const f32x4*)(tbias + nb + fcol(f));
                 if constexpr (LN) {
 #pragma unroll
                     for (int f = 0; f < C::TI; ++f) s4[f] = *(const f32x4*)(g.ln_s + nb + fcol(f));
@@ -707,7 +712,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
             const int nl = wc * 16 * C::TI + fg_e * 4 * C::TI;   // first tile column of this lane
             f32x4 bias4[C::TI];
 #pragma unroll
-            for (int f = 0; f < C::TI; ++f) bias4[f] = *(const f32x4*)(g.bias + n0 + nl + f * 4);
+            for (int f = 0; f < C::TI; ++f) bias4[f] = *(const f32x4*)(tbias + n0 + nl + f * 4);
             unsigned long long rs[6] = {ts0, ts1, 0, 0, 0, 0};   // tools/gemm8_timeline.py --resid: drain, passes, statistics, restart
             // staged row lr of pass p  <->  tile row (p / (4/JPP)) 128 + (lr / (16 JPP)) 64 + ((p % (4/JPP)) JPP + (lr / 16) % JPP) 16 + lr % 16
             auto tile_row = [&](int p, int lr) {
@@ -809,14 +814,17 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
 template <class T, int EPI, class C>
 static hipError_t launch8(const GemmArgs& a, hipStream_t s) {
     auto kern = gemm8_kernel<T, EPI, C>;
+    int ex = 0;   // the residual epilogue's per-crop expert instantiation (ViTPose+, GemmArgs::expert)
+    if constexpr (EPI == EPI_BIAS_RESID_LN)
+        if (a.expert) { kern = gemm8_kernel<T, EPI, C, true>; ex = 1; }
     constexpr int LDS = (EPI == EPI_QKV_ATTN) ? 160 * 1024 : (EPI == EPI_BIAS_RESID_LN && C::BN != 256) ? ((128 * (C::BN * 4 + 16) + C::BM * (C::BN / 64) * 8) > C::RING ? (128 * (C::BN * 4 + 16) + C::BM * (C::BN / 64) * 8) : C::RING) : C::RING;
-    static bool attr_done[64] = {};   // per device: the LDS opt-in is a per-device function attribute
+    static bool attr_done[2][64] = {};   // per device: the LDS opt-in is a per-device function attribute
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_done[dev]) {
+    if (dev < 0 || dev >= 64 || !attr_done[ex][dev]) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) attr_done[dev] = true;
+        if (dev >= 0 && dev < 64) attr_done[ex][dev] = true;
     }
     const int tiles = (a.M / C::BM) * (a.N / C::BN);
     int grid = tiles < 256 ? tiles : 256;
@@ -827,7 +835,7 @@ static hipError_t launch8(const GemmArgs& a, hipStream_t s) {
     if (grid >= 256) grid &= ~7;   // (only the tools override can make it a smaller non-multiple; below 256 tiles: one workgroup per tile)
     if (grid < 8) return hipErrorInvalidValue;
     // (the name rocprofv3 prints for this instantiation: G8<BN, BM>)
-    if (a.desc) snprintf(a.desc, a.desc_cap, "gemm8_kernel<%s, %d, G8<%d, %d>>", std::is_same<T, F16>::value ? "F16" : "BF16", EPI, C::BN, C::BM);
+    if (a.desc) snprintf(a.desc, a.desc_cap, "gemm8_kernel<%s, %d, G8<%d, %d>%s>", std::is_same<T, F16>::value ? "F16" : "BF16", EPI, C::BN, C::BM, ex ? ", true" : "");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), LDS, s, a);
     return hipGetLastError();
 }

@@ -97,7 +97,13 @@ struct GemmArgs {
     float attn_scale_log2e;   // EPI_QKV_ATTN: head_dim^-0.5 * log2(e)
     int splitk;        // EPI_PARTIAL: number of k ranges S (K % (S * BK) == 0; grid = tiles * S)
     int parity_fast;   // deconv: 1 = the four output parities of a tile are consecutive logical blocks (same XCD, shared input rows); 0 = parity on blockIdx.y
-    const uint8_t* a_scales;
+    union {
+        const uint8_t* a_scales;   // fp8 mode (gemm8f.hip)
+        // ViTPose+ mlp.fc2 of a batch that mixes experts (the residual epilogues' EXPERT instantiations of gemm.hip / gemm8.hip): the m-tile at row m0 belongs
+        // to expert expert[m0 / 192] (one int32 per crop, device memory) and reads its weights expert * w_rows * K elements behind W, its bias
+        // expert * w_rows floats behind bias.  The host never hands a tile that spans two experts (tile_rules.hip expert_tile_ok).
+        const int32_t* expert;
+    };
     const float* w_scale;
     uint8_t* out_scales;
 };
@@ -184,6 +190,8 @@ hipError_t layernorm_launch(int dtype, const float* x, const float* gamma, const
                             uint16_t* out16, float* out32, int M, int D, hipStream_t s, size_t plane = 0);
 // crops -> im2col patch matrix [B*192, 768] 16-bit (k = c*256 + ky*16 + kx, zero border of 2 px)
 hipError_t im2col_launch(int dtype, const void* crops, int input_format, uint16_t* out, int B, hipStream_t s, bool flip = false, int n_src = 0);   // n_src < B: output crops n_src .. B - 1 repeat source crop n_src - 1
+// ViTPose+ mixed batch: dst crop i = src crop idx[i] (idx: device int32 [n], each in [0, n_src)); crop_bytes % 16 == 0
+hipError_t gather_crops_launch(const void* src, void* dst, const int32_t* idx, int n, size_t crop_bytes, hipStream_t s);
 // flip-test: hm = 0.5 (hm + flip_back(hm_flipped)); partner[k] = mirror joint of k (k itself if unpaired)
 hipError_t flip_merge_launch(float* hm, const float* hm_flipped, const int32_t* partner, int N, int K, int shift, hipStream_t s);
 

@@ -192,9 +192,45 @@ int pick_run_batch(int n, int D, int limit, int bm192_mask, bool extended, int g
     return (c0 > 0.0 && c1 > 0.0 && c1 < 0.95 * c0) ? n4 : n;
 }
 
+int tile_bm(int variant) {
+    if (variant == 16 || variant == 17) return 256;
+    if (variant == 18) return 192;
+    int bm = 0, bn = 0, slots = 0;
+    return tile2_dims(variant, bm, bn, slots) ? bm : 0;
+}
+
+// ViTPose+ mlp.fc2 of a batch that mixes experts (vp_infer_experts): the host orders the crops by expert, so the experts change only at the crops in `bounds`,
+// and a tile reads ONE expert's weights -- it may not span such a change.  Tiles of 32 / 64 / 96 / 192 rows divide a crop (192 token rows) and always qualify;
+// 128- and 256-row tiles only where every change falls on a multiple of their height (2 / 4 crops).  The rules above stay as they are: a single-expert batch
+// never gets here, and a mixed one keeps the rule's tile wherever it qualifies.  Every fallback is in the one-launch family (same k order, same bits).
+bool expert_tile_ok(int bm, const std::vector<int>& bounds) {
+    if (bm <= 0) return false;
+    for (int b : bounds)
+        if (((long)b * 192) % bm) return false;
+    return true;
+}
+
+// The crop-aligned tile a mixed batch's mlp.fc2 takes where the rule's 128- or 256-row tile spans an expert change: the 8-phase kernel's 192 x 256 tile where the
+// 8-phase kernel would have run it (gemm8_ok: N % 256 == 0 and >= 1.75 tiles per CU, ViTPose-B / -L / -H at large batches), else the residual default 192 x 128.
+int expert_fallback_variant(int M, int N, bool gemm8_ok, int* group_m) {
+    if (gemm8_ok && N % 256 == 0 && (long)(M / 192) * (N / 256) >= 448) { *group_m = 2; return 18; }
+    *group_m = 0;
+    return 11;
+}
+
 }  // namespace vpi
 
 extern "C" {
+
+// HOST ONLY: the tile mlp.fc2 of a mixed-expert batch runs (n crops, the experts change at the n_bounds crops in bounds, embed dim D): `variant` = what the rules picked
+// for the row count, gemm8_ok = the 8-phase kernel may run it; returns the variant kept or the crop-aligned fallback
+VP_API int vp_dbg_expert_tile(int32_t variant, int32_t M, int32_t N, int32_t gemm8_ok, const int32_t* bounds, int32_t n_bounds) {
+    if (M <= 0 || N <= 0 || n_bounds < 0 || (n_bounds > 0 && !bounds)) return VP_ERR_INVALID;
+    const std::vector<int> b(bounds, bounds + n_bounds);
+    if (expert_tile_ok(tile_bm(variant), b)) return variant;
+    int gm = 0;
+    return expert_fallback_variant(M, N, gemm8_ok != 0, &gm);
+}
 
 // HOST ONLY: the batch the encoder runs for a chunk of n crops of a model of embed dim D (pick_run_batch with the default switches; limit = the handle's padded workspace batch)
 VP_API int vp_dbg_run_batch(int32_t n, int32_t D, int32_t limit) {

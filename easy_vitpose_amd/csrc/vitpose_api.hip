@@ -77,6 +77,8 @@ int gemm(vp_ctx* c, int fam, int epi, const uint16_t* A, const uint16_t* W, cons
     g.group_m = c->gemm_group_m[fam];
     g.ablate = c->gemm_ablate | c->fam_ablate[fam];
     g.parity_fast = c->deconv_parity_fast;
+    const bool mixed = c->mix_expert && fam == VP_PROF_GEMM_FC2;   // ViTPose+ mixed batch: every crop's m-tiles read its own expert's fc2
+    if (mixed) g.expert = c->mix_expert;   // expert e's fc2 lies e * w_rows * K / e * w_rows behind (weights.hip upload_fc2_experts: w_rows = pad128(D))
     if (g.variant < 0) {
         const Tile2Pick tp = pick_gemm2_tile(epi, M, N, K);   // the 2-phase kernels' tile (the 8-phase kernel may take the GEMM over below)
         g.variant = tp.variant; g.group_m = tp.group_m;
@@ -122,6 +124,13 @@ int gemm(vp_ctx* c, int fam, int epi, const uint16_t* A, const uint16_t* W, cons
         g.persist = 0;
         if (g.variant >= 16 && g.variant <= 18) { g.variant = 8; g.group_m = 8; }
     }
+    if (mixed && !expert_tile_ok(tile_bm(g.variant), c->mix_bounds)) {   // a tile would span two experts: the crop-aligned tile instead (tile_rules.hip)
+        vp::GemmArgs t = g;
+        const bool g8 = (c->gemm8_mask & 1) && vp::gemm8_supported(epi, t, 256, 192);
+        g.variant = expert_fallback_variant(M, N, g8, &g.group_m);
+        g.persist = 0;
+        g.stagger = g.variant == 18 ? c->g8_stagger : 0;
+    }
     const bool deconv = epi == vp::EPI_DECONV || epi == vp::EPI_DECONV_FINAL;
     const double par = deconv ? 4.0 : 1.0;
     const double Nalg = (epi == vp::EPI_HEATMAP) ? (double)c->Kp : (double)N;   // heatmap: N counts the hi + lo weight rows
@@ -141,7 +150,7 @@ int gemm(vp_ctx* c, int fam, int epi, const uint16_t* A, const uint16_t* W, cons
     desc[0] = 0;
     g.desc = desc; g.desc_cap = (int)sizeof(desc);   // the launch code names the kernel it resolved to (one snprintf per GEMM launch: vp_profile_kernel reports the LAST launch)
     // small batches: a residual GEMM as S partial products over k ranges + a fixed-order reduction (tile_rules.hip pick_splitk)
-    if (epi == vp::EPI_BIAS_RESID_LN && c->splitk_ws && (size_t)M <= c->splitk_rows && c->gemm_variant[fam] < 0 && !(g.variant >= 16 && g.variant <= 18) &&
+    if (epi == vp::EPI_BIAS_RESID_LN && !mixed && c->splitk_ws && (size_t)M <= c->splitk_rows && c->gemm_variant[fam] < 0 && !(g.variant >= 16 && g.variant <= 18) &&
         out == (void*)aux && (fam == VP_PROF_GEMM_FC2 || fam == VP_PROF_GEMM_PROJ)) {
         const int which = fam == VP_PROF_GEMM_FC2 ? 1 : 0;
         SplitKPick sk = pick_splitk(M, N, K);
@@ -209,8 +218,14 @@ int gemm_fp8(vp_ctx* c, int fam, int epi, const uint8_t* A8, const uint8_t* a_sc
 
 namespace {
 
-// forward of one chunk (n <= max_batch) with device-resident crops; heatmaps land in c->hm
-int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, bool want_tokens, bool flip = false) {
+int head_chunk(vp_ctx* c, const uint16_t* y, int nh, float* hm);
+
+// fc2 weights / bias of block b for the active expert (a ViTPose+ handle outside a mixed batch; expert 0 = the only one of a plain handle)
+const uint16_t* fc2_w(const vp_ctx* c, const vpi::Block& b) { return c->mix_expert ? b.w_fc2 : b.w_fc2 + (size_t)c->expert * c->fc2_w_stride; }
+const float* fc2_b(const vp_ctx* c, const vpi::Block& b) { return c->mix_expert ? b.b_fc2 : b.b_fc2 + (size_t)c->expert * c->fc2_b_stride; }
+
+// forward of one chunk (n <= max_batch) with device-resident crops; heatmaps land in c->hm (head = false: the encoder and last_norm only, tokens in c->y)
+int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, bool want_tokens, bool flip = false, bool head = true) {
     const int D = c->D;
     // the ENCODER's batch: n_in crops, or the next multiple of 4 where that buys the MLP GEMMs an 8-phase tile (tile_rules.hip pick_run_batch; rows n_in .. n - 1 repeat the
     // last crop and are never read by the head); the fp8 mode pads its rows itself
@@ -352,7 +367,7 @@ int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, bool want_t
             if (fold2) { c1.rowstat = nullptr; c1.ln_part = c->ln_part; c1.ln_tiles = D / 64; }
             if ((rc = gemm(c, VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, xh, b.w_fc1, b.b_fc1, c->hid, nullptr, M, 4 * D, D, 4 * D, 0, 0, 0, &c1))) return rc;
             LnFuse p2 = prod; p2.a_blocked = c->blocked_hid; p2.reverse = (c->order_mask & 8) != 0;
-            if ((rc = gemm(c, VP_PROF_GEMM_FC2, vp::EPI_BIAS_RESID_LN, c->hid, b.w_fc2, b.b_fc2, c->x, c->x, M, D, 4 * D, D, 0, 0, 0, &p2))) return rc;
+            if ((rc = gemm(c, VP_PROF_GEMM_FC2, vp::EPI_BIAS_RESID_LN, c->hid, fc2_w(c, b), fc2_b(c, b), c->x, c->x, M, D, 4 * D, D, 0, 0, 0, &p2))) return rc;
             if (l + 1 < c->L && (rc = finalize(fold1))) return rc;   // last block: last_norm below is a standalone pass
         }
     } else {
@@ -369,21 +384,33 @@ int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, bool want_t
         LAUNCH(c, VP_PROF_LAYERNORM, 0.0, 6.0 * M * D,
                vp::layernorm_launch(c->dtype, c->x, b.ln2_g, b.ln2_b, c->y, nullptr, M, D, c->stream));
         if ((rc = gemm(c, VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, c->y, b.w_fc1, b.b_fc1, c->hid, nullptr, M, 4 * D, D, 4 * D))) return rc;
-        if ((rc = gemm(c, VP_PROF_GEMM_FC2, vp::EPI_BIAS_RESID, c->hid, b.w_fc2, b.b_fc2, c->x, c->x, M, D, 4 * D, D))) return rc;
+        if ((rc = gemm(c, VP_PROF_GEMM_FC2, vp::EPI_BIAS_RESID, c->hid, fc2_w(c, b), fc2_b(c, b), c->x, c->x, M, D, 4 * D, D))) return rc;
     }
     }
     // last_norm, head and decode: the caller's n_in crops (the planes are laid out for the encoder's row count)
     const int nh = n_in, Mh = nh * 192;
     LAUNCH(c, VP_PROF_LAYERNORM, 0.0, 6.0 * Mh * D,
            vp::layernorm_launch(c->dtype, c->x, c->lnf_g, c->lnf_b, c->y, want_tokens ? c->tok : nullptr, Mh, D, c->stream, plane));
+    return head ? head_chunk(c, c->y, nh, c->hm) : VP_OK;
+}
+
+// head of nh crops whose last_norm tokens start at y, with the active head weights (c->w_d1 .. c->w_fin, c->Kp) -> heatmaps [nh, Kp, 64, 48] at hm
+int head_chunk(vp_ctx* c, const uint16_t* y, int nh, float* hm) {
+    const int D = c->D;
+    int rc;
     // head: tokens [n,16,12,D] (NHWC view of [n*192, D]) -> [n,32,24,256] -> [n,64,48,256] -> heatmaps [n,Kp,64,48]
-    if ((rc = gemm(c, VP_PROF_GEMM_DECONV, vp::EPI_DECONV, c->y, c->w_d1, c->b_d1, c->d1, nullptr, nh * 192, 256, 4 * D, 256, 16, 12, D))) return rc;
+    if ((rc = gemm(c, VP_PROF_GEMM_DECONV, vp::EPI_DECONV, y, c->w_d1, c->b_d1, c->d1, nullptr, nh * 192, 256, 4 * D, 256, 16, 12, D))) return rc;
     // large batches: the final 1x1 conv rides in deconv2's epilogue (gemm.hip EPI_DECONV_FINAL, bit-identical heatmaps) and the
     // [n,64,48,256] tensor is never written; small batches keep the two launches on tiles that still fill 256 CUs
-    if (c->fuse_head && c->gemm_variant[VP_PROF_GEMM_DECONV] < 0 && (long)nh * 12 >= 512)
-        return gemm(c, VP_PROF_GEMM_DECONV, vp::EPI_DECONV_FINAL, c->d1, c->w_d2, c->b_d2, nullptr, nullptr, nh * 768, 256, 1024, 256, 32, 24, 256);
+    if (c->fuse_head && c->gemm_variant[VP_PROF_GEMM_DECONV] < 0 && (long)nh * 12 >= 512) {
+        float* keep = c->hm;   // gemm() hands EPI_DECONV_FINAL c->hm as its heatmap output
+        c->hm = hm;
+        rc = gemm(c, VP_PROF_GEMM_DECONV, vp::EPI_DECONV_FINAL, c->d1, c->w_d2, c->b_d2, nullptr, nullptr, nh * 768, 256, 1024, 256, 32, 24, 256);
+        c->hm = keep;
+        return rc;
+    }
     if ((rc = gemm(c, VP_PROF_GEMM_DECONV, vp::EPI_DECONV, c->d1, c->w_d2, c->b_d2, c->d2, nullptr, nh * 768, 256, 1024, 256, 32, 24, 256))) return rc;
-    if ((rc = gemm(c, VP_PROF_GEMM_FINAL, vp::EPI_HEATMAP, c->d2, c->w_fin, c->b_fin, c->hm, nullptr, nh * 3072, (int)c->fin_rows, 256, 0))) return rc;
+    if ((rc = gemm(c, VP_PROF_GEMM_FINAL, vp::EPI_HEATMAP, c->d2, c->w_fin, c->b_fin, hm, nullptr, nh * 3072, (int)c->fin_rows, 256, 0))) return rc;
     return VP_OK;
 }
 
@@ -408,7 +435,7 @@ int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh
     if (nb > c->graph_max_n || c->prof != 0 || (c->stream == nullptr && !graph_null)) return eager();
     vp_ctx::GraphEntry* ge = nullptr;
     for (auto& g : c->graphs)
-        if (g.n == nb && g.fmt == fmt && g.src == d_src && g.wh == d_wh && g.out == d_out) { ge = &g; break; }
+        if (g.n == nb && g.fmt == fmt && g.src == d_src && g.wh == d_wh && g.out == d_out && g.expert == c->expert) { ge = &g; break; }
     if (ge && ge->exec) {
         const hipError_t el = hipGraphLaunch(ge->exec, c->stream);
         if (el == hipSuccess) return VP_OK;
@@ -426,7 +453,7 @@ int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh
             hipGraphExecDestroy(ge->exec);
             ge->exec = nullptr;
         }
-        ge->n = nb; ge->fmt = fmt; ge->src = d_src; ge->wh = d_wh; ge->out = d_out; ge->seen = 1; ge->no_graph = false;
+        ge->n = nb; ge->fmt = fmt; ge->src = d_src; ge->wh = d_wh; ge->out = d_out; ge->expert = c->expert; ge->seen = 1; ge->no_graph = false;
         return eager();
     }
     // second sighting: capture.  Any failure of the capture machinery (not of the launches themselves) marks the key "do not
@@ -520,7 +547,7 @@ int vp_create(vp_handle* out, const vp_config* cfg) {
     if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(nullptr, VP_ERR_INVALID, "device_id out of range");
     vp_ctx* c = new vp_ctx();
     c->cfg = *cfg;
-    c->D = D; c->L = cfg->depth; c->heads = h; c->Kp = cfg->num_keypoints;
+    c->D = D; c->L = cfg->depth; c->heads = h; c->Kp = cfg->num_keypoints; c->Kmax = c->Kp;
     c->dtype = cfg->dtype == VP_DTYPE_BF16 ? vp::DT_BF16 : vp::DT_F16;   // fp8 mode: everything that is not one of the three MXFP8 GEMMs runs as fp16
     c->fp8 = cfg->dtype == VP_DTYPE_FP8;
     c->maxb = cfg->max_batch;
@@ -729,7 +756,7 @@ static int submit_impl(vp_handle c, const void* crops, int32_t fmt, int32_t n, c
         sl.in = q;
     }
     if (!sl.wh && (rc = dalloc(c, &sl.wh, (size_t)c->maxb * 2))) return rc;
-    if (!sl.kp && (rc = dalloc(c, &sl.kp, (size_t)c->maxb * c->Kp * 3))) return rc;
+    if (!sl.kp && (rc = dalloc(c, &sl.kp, (size_t)c->maxb * c->Kmax * 3))) return rc;
     if (!sl.h2d) HIPCHK(c, hipEventCreateWithFlags(&sl.h2d, hipEventDisableTiming));
     if (!sl.done) HIPCHK(c, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     if (!sl.out) HIPCHK(c, hipEventCreateWithFlags(&sl.out, hipEventDisableTiming));
@@ -766,7 +793,7 @@ static int submit_impl(vp_handle c, const void* crops, int32_t fmt, int32_t n, c
     if (stage_out) {
         if (!sl.host_kp) {
             void* q = nullptr;
-            HIPCHK(c, hipHostMalloc(&q, (size_t)c->maxb * c->Kp * 12, hipHostMallocDefault));
+            HIPCHK(c, hipHostMalloc(&q, (size_t)c->maxb * c->Kmax * 12, hipHostMallocDefault));
             sl.host_kp = (float*)q;
         }
         dst = sl.host_kp;
@@ -810,9 +837,9 @@ int vp_infer_flip(vp_handle c, const void* crops, int32_t fmt, int32_t n, const 
         partner[a] = b;
         partner[b] = a;
     }
-    const size_t hm_elems = (size_t)c->maxb * c->Kp * 3072;
+    const size_t hm_elems = (size_t)c->maxb * c->Kmax * 3072;
     if (!c->hm_keep && (rc = dalloc(c, &c->hm_keep, hm_elems))) return rc;
-    if (!c->partner && (rc = dalloc(c, &c->partner, (size_t)c->Kp))) return rc;
+    if (!c->partner && (rc = dalloc(c, &c->partner, (size_t)c->Kmax))) return rc;
     HIPCHK(c, hipMemcpy(c->partner, partner.data(), (size_t)c->Kp * 4, hipMemcpyHostToDevice));   // synchronous: `partner` is a local
     for (int off = 0; off < n; off += c->maxb) {
         const int nb = (n - off < c->maxb) ? n - off : c->maxb;
@@ -859,6 +886,126 @@ int vp_infer_tokens(vp_handle c, const void* crops, int32_t fmt, int32_t n, floa
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return VP_OK;
+}
+
+// ---- ViTPose+ (expert) handles --------------------------------------------------------------------------------------------
+int vp_expert_info(vp_handle c, int32_t* n_experts, int32_t* part_features, int32_t* k_per_expert) {
+    if (!c) return VP_ERR_INVALID;
+    if (!c->loaded) return fail(c, VP_ERR_STATE, "weights not loaded: call vp_load_weights first");
+    if (n_experts) *n_experts = c->n_experts;
+    if (part_features) *part_features = c->part_features;
+    if (k_per_expert)
+        for (int e = 0; e < c->n_experts && e < 8; ++e) k_per_expert[e] = c->ex_heads[e].K;
+    return VP_OK;
+}
+
+int vp_set_expert(vp_handle c, int32_t e) {
+    if (!c) return VP_ERR_INVALID;
+    if (!c->loaded) return fail(c, VP_ERR_STATE, "weights not loaded: call vp_load_weights first");
+    if (!c->n_experts) return fail(c, VP_ERR_STATE, "vp_set_expert: the handle holds a plain (single-dataset) checkpoint, not a ViTPose+ one");
+    if (e < 0 || e >= c->n_experts) return fail(c, VP_ERR_INVALID, "expert id " + std::to_string(e) + " outside [0, " + std::to_string(c->n_experts) + ")");
+    if (c->slots[0].busy || c->slots[1].busy) return fail(c, VP_ERR_STATE, "vp_set_expert with a vp_infer_submit in flight: call vp_infer_wait first");
+    use_expert(c, e);
+    return VP_OK;
+}
+
+int vp_infer_experts(vp_handle c, const void* crops, int32_t fmt, int32_t n, const int32_t* expert_ids, const int32_t* org_wh, float* out) {
+    int rc = check_ready(c, fmt, n, crops, out);
+    if (rc) return rc;
+    if (!c->n_experts) return fail(c, VP_ERR_STATE, "vp_infer_experts: the handle holds a plain (single-dataset) checkpoint, not a ViTPose+ one");
+    if (n > 0 && !expert_ids) return fail(c, VP_ERR_INVALID, "null expert_ids");
+    for (int i = 0; i < n; ++i)
+        if (expert_ids[i] < 0 || expert_ids[i] >= c->n_experts)
+            return fail(c, VP_ERR_INVALID, "expert id " + std::to_string(expert_ids[i]) + " of crop " + std::to_string(i) + " outside [0, " + std::to_string(c->n_experts) + ")");
+    if (c->slots[0].busy || c->slots[1].busy) return fail(c, VP_ERR_STATE, "vp_infer_experts with a vp_infer_submit in flight: call vp_infer_wait first");
+    // per chunk, the crops in expert order (stable): each expert is one contiguous segment, so that mlp.fc2's m-tiles see one expert and the head runs once per expert
+    const int saved = c->expert, D = c->D;
+    const size_t cb = crop_bytes(fmt), B = (size_t)((c->maxb + 3) / 4 * 4);
+    std::vector<int32_t> ids(2 * B), wh(2 * (size_t)c->maxb);
+    std::vector<int> order(c->maxb);
+    std::vector<float> kp((size_t)c->maxb * c->Kmax * 3);
+    auto run = [&]() -> int {
+        for (int off = 0; off < n; off += c->maxb) {
+            const int nb = (n - off < c->maxb) ? n - off : c->maxb;
+            for (int j = 0; j < nb; ++j) order[j] = off + j;
+            std::stable_sort(order.begin(), order.begin() + nb, [&](int a, int b) { return expert_ids[a] < expert_ids[b]; });
+            bool identity = true;
+            for (int j = 0; j < nb; ++j) identity = identity && order[j] == off + j;
+            if (identity) {
+                HIPCHK(c, hipMemcpyAsync(c->in_stage, (const char*)crops + (size_t)off * cb, (size_t)nb * cb, hipMemcpyHostToDevice, c->stream));
+            } else {   // one upload in the caller's order, then a device gather into expert order
+                if (c->mix_stage_cap < B * cb) {
+                    if (c->mix_stage) {
+                        HIPCHK(c, hipStreamSynchronize(c->stream));
+                        for (auto it = c->allocs.begin(); it != c->allocs.end(); ++it)
+                            if (*it == c->mix_stage) { c->allocs.erase(it); break; }
+                        HIPCHK(c, hipFree(c->mix_stage));
+                        c->mix_stage = nullptr; c->mix_stage_cap = 0;
+                    }
+                    char* q = nullptr;
+                    int arc = dalloc(c, &q, B * cb);
+                    if (arc) return arc;
+                    c->mix_stage = q; c->mix_stage_cap = B * cb;
+                }
+                HIPCHK(c, hipMemcpyAsync(c->mix_stage, (const char*)crops + (size_t)off * cb, (size_t)nb * cb, hipMemcpyHostToDevice, c->stream));
+            }
+            if (org_wh) {
+                for (int j = 0; j < nb; ++j) { wh[2 * j] = org_wh[2 * (size_t)order[j]]; wh[2 * j + 1] = org_wh[2 * (size_t)order[j] + 1]; }
+                HIPCHK(c, hipMemcpyAsync(c->wh_stage, wh.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
+            }
+            const int32_t* d_wh = org_wh ? c->wh_stage : nullptr;
+            // segments of the chunk: (expert, first crop, count); ids[B + j] = the gather order
+            std::vector<int> seg_e, seg_s;
+            for (int j = 0; j < nb; ++j) {
+                ids[j] = expert_ids[order[j]];
+                ids[B + j] = order[j] - off;
+                if (j == 0 || ids[j] != ids[j - 1]) { seg_e.push_back(ids[j]); seg_s.push_back(j); }
+            }
+            seg_s.push_back(nb);
+            for (size_t j = nb; j < B; ++j) ids[j] = ids[nb - 1];   // encoder padding crops repeat the last crop (pick_run_batch)
+            if (!identity) {
+                HIPCHK(c, hipMemcpyAsync(c->expert_ids, ids.data(), 2 * B * 4, hipMemcpyHostToDevice, c->stream));
+                HIPCHK(c, vp::gather_crops_launch(c->mix_stage, c->in_stage, c->expert_ids + B, nb, cb, c->stream));
+            }
+            if (seg_e.size() == 1) {   // one expert: the single-dataset path as it is (tile rules, split-K, hipGraph replay keyed on the expert)
+                use_expert(c, seg_e[0]);
+                if ((rc = run_chunk(c, c->in_stage, fmt, nb, d_wh, c->kp))) return rc;
+            } else {
+                // mixed: the encoder once (mlp.fc2 of every expert in one launch per layer: GemmArgs::expert), then head + decode per expert segment.
+                // Eager: the expert pattern shapes the head launches, so a captured graph would have to be keyed on it (the single-expert path above replays)
+                if (identity) HIPCHK(c, hipMemcpyAsync(c->expert_ids, ids.data(), B * 4, hipMemcpyHostToDevice, c->stream));
+                c->mix_expert = c->expert_ids;
+                c->mix_bounds.assign(seg_s.begin() + 1, seg_s.end() - 1);
+                rc = forward_chunk(c, c->in_stage, fmt, nb, false, false, false);
+                c->mix_expert = nullptr;
+                c->mix_bounds.clear();
+                if (rc) return rc;
+                for (size_t s = 0; s < seg_e.size(); ++s) {
+                    const int s0 = seg_s[s], cnt = seg_s[s + 1] - s0;
+                    use_expert(c, seg_e[s]);
+                    float* hm = c->hm + (size_t)s0 * c->Kmax * 3072;
+                    if ((rc = head_chunk(c, c->y + (size_t)s0 * 192 * D, cnt, hm))) return rc;
+                    LAUNCH(c, VP_PROF_DECODE, 0.0, 4.0 * cnt * c->Kp * 3072.0 + 12.0 * cnt * c->Kp,
+                           vp::decode_launch(hm, d_wh ? d_wh + 2 * (size_t)s0 : nullptr, c->kp + (size_t)s0 * c->Kmax * 3, cnt, c->Kp, c->stream));
+                }
+            }
+            HIPCHK(c, hipMemcpyAsync(kp.data(), c->kp, (size_t)nb * c->Kmax * 12, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));   // also keeps ids / wh (host vectors) alive until their uploads are done
+            // segment s's crops lie at [s0 Kmax + (j - s0) K_e] x 3 floats: back to the caller's order, joints beyond K_e = 0
+            for (size_t s = 0; s < seg_e.size(); ++s) {
+                const int K = c->ex_heads[seg_e[s]].K;
+                for (int j = seg_s[s]; j < seg_s[s + 1]; ++j) {
+                    float* dst = out + (size_t)order[j] * c->Kmax * 3;
+                    std::memcpy(dst, &kp[((size_t)seg_s[s] * c->Kmax + (size_t)(j - seg_s[s]) * K) * 3], (size_t)K * 12);
+                    std::memset(dst + (size_t)K * 3, 0, (size_t)(c->Kmax - K) * 12);
+                }
+            }
+        }
+        return VP_OK;
+    };
+    rc = run();
+    use_expert(c, saved);
+    return rc;
 }
 
 int vp_infer_frame(vp_handle c, const uint8_t* frame, int32_t fh, int32_t fw, const int32_t* crop_params, int32_t n, float* out) {

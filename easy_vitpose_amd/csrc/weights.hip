@@ -161,8 +161,8 @@ int upload_fp8_rows(vp_ctx* c, uint8_t** w_out, float** ws_out, float** c_out, c
 //   Wp[parity=(a,b)][o][t*Cin + c] = w[c][o][ky(a,ti)][kx(b,tj)] * gamma[o]/sqrt(var[o]+eps),  t = ti*2+tj
 //   a=0: ti=0 -> ky=1 (input row i), ti=1 -> ky=3 (row i-1);  a=1: ti=0 -> ky=0 (row i+1), ti=1 -> ky=2 (row i)
 //   bias[o] = beta[o] - mean[o]*scale[o]
-int pack_deconv(vp_ctx* c, Lookup& lk, int idx, int Cin, uint16_t** w_out, float** b_out) {
-    const std::string h = "keypoint_head.deconv_layers.";
+int pack_deconv(vp_ctx* c, Lookup& lk, int idx, int Cin, uint16_t** w_out, float** b_out, const std::string& head) {
+    const std::string h = head + ".deconv_layers.";
     const float *w, *g, *b, *mu, *var;
     int rc;
     if ((rc = lk.get(h + std::to_string(idx) + ".weight", (int64_t)Cin * 256 * 16, &w))) return rc;
@@ -192,6 +192,89 @@ int pack_deconv(vp_ctx* c, Lookup& lk, int idx, int Cin, uint16_t** w_out, float
     return upload_f32(c, b_out, bias.data(), 256);
 }
 
+// ViTPose+ checkpoints (the reference's model_split.py): expert 0 = coco with keypoint_head, expert i + 1 = these datasets with associate_keypoint_heads.i,
+// final layer sliced to its first K rows
+static const int kExpertK[6] = {17, 14, 16, 17, 17, 133};
+constexpr int kMaxExperts = 6;
+
+void use_expert(vp_ctx* c, int e) {
+    const vp_ctx::Head& h = c->ex_heads[e];
+    c->w_d1 = h.w_d1; c->b_d1 = h.b_d1; c->w_d2 = h.w_d2; c->b_d2 = h.b_d2; c->w_fin = h.w_fin; c->b_fin = h.b_fin;
+    c->fin_rows = h.fin_rows; c->Kp = h.K; c->expert = e;
+}
+
+// what a ViTPose+ state dict holds: E experts of P output features each (the last P rows of every block's mlp.fc2); 0 = not ViTPose+
+static int moe_layout(vp_ctx* c, Lookup& lk, int* E, int* P) {
+    const int D = c->D;
+    *E = 0; *P = 0;
+    if (!lk.has("backbone.blocks.0.mlp.experts.0.weight")) return VP_OK;
+    while (lk.has("backbone.blocks.0.mlp.experts." + std::to_string(*E) + ".weight")) ++*E;
+    if (*E > kMaxExperts) return fail(c, VP_ERR_INVALID, "ViTPose+ state dict with " + std::to_string(*E) + " experts: at most 6 (coco, aic, mpii, ap10k, apt36k, wholebody)");
+    const int64_t ne = lk.numel("backbone.blocks.0.mlp.experts.0.weight");
+    if (ne <= 0 || ne % (4 * (int64_t)D)) return fail(c, VP_ERR_SHAPE, "size mismatch for backbone.blocks.0.mlp.experts.0.weight: not [P, 4 * embed_dim]");
+    *P = (int)(ne / (4 * (int64_t)D));
+    if (*P % 64 != 0 || *P >= D)
+        return fail(c, VP_ERR_SHAPE, "ViTPose+ part_features " + std::to_string(*P) + " unsupported: must be a multiple of 64 and below embed_dim " + std::to_string(D));
+    return VP_OK;
+}
+
+// mlp.fc2 of every expert as the split model's full matrix: rows [0, D - P) shared, [D - P, D) the expert's; [E][pad(D)][4D] weights, [E][pad(D)] bias
+static int upload_fc2_experts(vp_ctx* c, Lookup& lk, const std::string& pre, int E, int P, vpi::Block& b) {
+    const int D = c->D;
+    const size_t K = 4 * (size_t)D, rows_pad = pad128(D), S = D - P;
+    const float *ws, *bs;
+    int rc;
+    if ((rc = lk.get(pre + "mlp.fc2.weight", (int64_t)(S * K), &ws)) || (rc = lk.get(pre + "mlp.fc2.bias", (int64_t)S, &bs))) return rc;
+    std::vector<uint16_t> w((size_t)E * rows_pad * K, 0);
+    std::vector<float> bias((size_t)E * rows_pad, 0.f);
+    for (int e = 0; e < E; ++e) {
+        const std::string ex = pre + "mlp.experts." + std::to_string(e) + ".";
+        const float *we, *be;
+        if ((rc = lk.get(ex + "weight", (int64_t)P * (int64_t)K, &we)) || (rc = lk.get(ex + "bias", P, &be))) return rc;
+        uint16_t* dst = &w[(size_t)e * rows_pad * K];
+        for (size_t i = 0; i < S * K; ++i) dst[i] = host_to_bits(ws[i], c->dtype);
+        for (size_t i = 0; i < (size_t)P * K; ++i) dst[S * K + i] = host_to_bits(we[i], c->dtype);
+        std::memcpy(&bias[(size_t)e * rows_pad], bs, S * 4);
+        std::memcpy(&bias[(size_t)e * rows_pad + S], be, (size_t)P * 4);
+    }
+    if ((rc = dalloc(c, &b.w_fc2, w.size()))) return rc;
+    HIPCHK(c, hipMemcpy(b.w_fc2, w.data(), w.size() * 2, hipMemcpyHostToDevice));
+    if ((rc = dalloc(c, &b.b_fc2, bias.size()))) return rc;
+    HIPCHK(c, hipMemcpy(b.b_fc2, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
+    c->fc2_w_stride = rows_pad * K;
+    c->fc2_b_stride = rows_pad;
+    return VP_OK;
+}
+
+// one keypoint head (deconvs + final layer sliced to its first K rows) -> c->ex_heads[e]
+static int upload_head(vp_ctx* c, Lookup& lk, const std::string& head, int K, vp_ctx::Head& h) {
+    int rc;
+    if ((rc = pack_deconv(c, lk, 0, c->D, &h.w_d1, &h.b_d1, head))) return rc;
+    if ((rc = pack_deconv(c, lk, 3, 256, &h.w_d2, &h.b_d2, head))) return rc;
+    const std::string fw = head + ".final_layer.weight", fb = head + ".final_layer.bias";
+    if (!lk.has(fw)) return fail(c, VP_ERR_MISSING_TENSOR, "missing key in state dict: " + fw);
+    if (!lk.has(fb)) return fail(c, VP_ERR_MISSING_TENSOR, "missing key in state dict: " + fb);
+    const int64_t nw = lk.numel(fw), nb = lk.numel(fb);
+    if (nw % 256 || nw < (int64_t)K * 256 || nb < K || nb * 256 != nw)
+        return fail(c, VP_ERR_SHAPE, "size mismatch for " + fw + ": expected at least " + std::to_string(K) + " rows of 256, got " + std::to_string(nw) + " elements");
+    const float *p;
+    if ((rc = lk.get(fw, nw, &p)) || (rc = upload_final(c, &h.w_fin, p, K, 256, &h.fin_rows))) return rc;
+    if ((rc = lk.get(fb, nb, &p)) || (rc = upload_f32(c, &h.b_fin, p, K, pad128(K)))) return rc;
+    h.K = K;
+    return VP_OK;
+}
+
+// replace a buffer made by dalloc with one of `count` elements
+template <class T> static int realloc_dev(vp_ctx* c, T** p, size_t count) {
+    if (*p) {
+        for (auto it = c->allocs.begin(); it != c->allocs.end(); ++it)
+            if (*it == (void*)*p) { c->allocs.erase(it); break; }
+        HIPCHK(c, hipFree(*p));
+        *p = nullptr;
+    }
+    return dalloc(c, p, count);
+}
+
 }  // namespace vpi
 
 extern "C" {
@@ -208,6 +291,11 @@ int vp_load_weights(vp_handle c, const vp_tensor_desc* tensors, int32_t n_tensor
     const size_t DD = (size_t)D * D;
     int rc;
     const float *p, *q;
+    int E = 0, P = 0;   // ViTPose+: E experts of P features (DESIGN.md "ViTPose+")
+    if ((rc = moe_layout(c, lk, &E, &P))) return rc;
+    if (E > 0 && c->fp8) return fail(c, VP_ERR_INVALID, "ViTPose+ (expert) checkpoints are not supported in the fp8 mode: create the handle with VP_DTYPE_F16 or VP_DTYPE_BF16");
+    if (E > 0 && c->Kp != kExpertK[0])
+        return fail(c, VP_ERR_INVALID, "a ViTPose+ checkpoint loads on a handle created with num_keypoints = 17 (its coco head); got " + std::to_string(c->Kp));
     // patch embed + positional embedding (vit.py:222, :382): aux[t] = pos[1+t] + pos[0] + conv bias
     if ((rc = lk.get("backbone.patch_embed.proj.weight", (int64_t)D * 768, &p))) return rc;
     if ((rc = upload_mat(c, &c->w_patch, p, D, 768, pad128(D)))) return rc;
@@ -253,6 +341,10 @@ int vp_load_weights(vp_handle c, const vp_tensor_desc* tensors, int32_t n_tensor
         if ((rc = lk.get(pre + "attn.proj.weight", (int64_t)DD, &p)) || (rc = upload_mat(c, &b.w_proj, p, D, D, pad128(D)))) return rc;
         if (c->y8 && (rc = upload_fp8_rows(c, &b.w_proj8, &b.ws_proj, nullptr, p, nullptr, nullptr, nullptr, D, D))) return rc;
         if ((rc = lk.get(pre + "attn.proj.bias", D, &p)) || (rc = upload_f32(c, &b.b_proj, p, D))) return rc;
+        if (E > 0) {
+            if ((rc = upload_fc2_experts(c, lk, pre, E, P, b))) return rc;
+            continue;
+        }
         if ((rc = lk.get(pre + "mlp.fc2.weight", (int64_t)4 * DD, &p))) return rc;
         if (c->fp8) { if ((rc = upload_fp8_rows(c, &b.w_fc28, &b.ws_fc2, nullptr, p, nullptr, nullptr, nullptr, D, 4 * (size_t)D))) return rc; }
         else if ((rc = upload_mat(c, &b.w_fc2, p, D, 4 * (size_t)D, pad128(D)))) return rc;
@@ -260,11 +352,31 @@ int vp_load_weights(vp_handle c, const vp_tensor_desc* tensors, int32_t n_tensor
     }
     if ((rc = lk.get("backbone.last_norm.weight", D, &p)) || (rc = upload_f32(c, &c->lnf_g, p, D))) return rc;
     if ((rc = lk.get("backbone.last_norm.bias", D, &p)) || (rc = upload_f32(c, &c->lnf_b, p, D))) return rc;
+    if (E > 0) {   // one head per expert; every buffer indexed by keypoint grows to the largest K
+        c->ex_heads.resize(E);
+        int kmax = 0;
+        for (int e = 0; e < E; ++e) {
+            const std::string head = e == 0 ? "keypoint_head" : "associate_keypoint_heads." + std::to_string(e - 1);
+            if (!lk.has(head + ".final_layer.weight"))
+                return fail(c, VP_ERR_MISSING_TENSOR, "ViTPose+ state dict: expert " + std::to_string(e) + " has no head (missing key " + head + ".final_layer.weight)");
+            if ((rc = upload_head(c, lk, head, kExpertK[e], c->ex_heads[e]))) return rc;
+            kmax = std::max(kmax, kExpertK[e]);
+        }
+        const size_t B = (size_t)((c->maxb + 3) / 4 * 4);
+        if (kmax > c->Kmax) {
+            if ((rc = realloc_dev(c, &c->hm, B * kmax * 3072)) || (rc = realloc_dev(c, &c->kp, B * kmax * 3))) return rc;
+            c->Kmax = kmax;
+        }
+        if ((rc = dalloc(c, &c->expert_ids, 2 * B))) return rc;
+        c->n_experts = E; c->part_features = P;
+        use_expert(c, 0);
+    } else {
     if ((rc = pack_deconv(c, lk, 0, D, &c->w_d1, &c->b_d1))) return rc;
     if ((rc = pack_deconv(c, lk, 3, 256, &c->w_d2, &c->b_d2))) return rc;
     if ((rc = lk.get("keypoint_head.final_layer.weight", (int64_t)c->Kp * 256, &p)) ||
         (rc = upload_final(c, &c->w_fin, p, c->Kp, 256, &c->fin_rows))) return rc;
     if ((rc = lk.get("keypoint_head.final_layer.bias", c->Kp, &p)) || (rc = upload_f32(c, &c->b_fin, p, c->Kp, pad128(c->Kp)))) return rc;
+    }
     {
         std::vector<float> z(pad128(4 * (size_t)D), 0.f);
         if ((rc = upload_f32(c, &c->b_zero, z.data(), z.size()))) return rc;

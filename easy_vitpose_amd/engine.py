@@ -9,7 +9,10 @@ import ctypes as C
 
 import numpy as np
 
+import dataclasses
+
 from . import _capi as capi
+from . import moe
 from .configs import HM_H, HM_W, IMG_H, IMG_W, ModelShape
 
 
@@ -58,10 +61,22 @@ class PinnedArray:
 
 
 class VitPoseHip:
-    """ViTPose (backbone + head + decode) on one MI355X through libvitpose_hip.so."""
+    """ViTPose (backbone + head + decode) on one MI355X through libvitpose_hip.so.
 
-    def __init__(self, shape: ModelShape, state_dict, dtype: str = 'fp16', device_id: int = 0, max_batch: int = 64):
+    A ViTPose+ state dict (easy_vitpose_amd/moe.py) loads as it is: ``.experts`` lists its ``(dataset, K)``, ``set_dataset``
+    picks the expert every method runs (``dataset=`` at construction does the same; default coco), and ``infer_mixed`` runs
+    a different dataset per crop in one call.  ``shape.num_keypoints`` is ignored for such a dict (its coco head has 17)."""
+
+    def __init__(self, shape: ModelShape, state_dict, dtype: str = 'fp16', device_id: int = 0, max_batch: int = 64,
+                 dataset: str | None = None):
         self.lib = capi.load_library()
+        self.experts = []
+        self._moe = moe.is_vitpose_plus(state_dict)
+        if self._moe:
+            moe.moe_info(state_dict)   # the loader's refusals, with the Python exception types
+            shape = dataclasses.replace(shape, num_keypoints=moe.NUM_KEYPOINTS[0])
+        elif dataset is not None:
+            raise ValueError('dataset= selects an expert of a ViTPose+ state dict; this one is a plain checkpoint')
         self.shape = shape
         self.dtype = dtype
         self.device_id = int(device_id)
@@ -74,6 +89,15 @@ class VitPoseHip:
         self._h = h
         try:
             self._load(state_dict)
+            if self._moe:
+                n, p, ks = C.c_int32(), C.c_int32(), (C.c_int32 * 8)()
+                capi.check(self.lib.vp_expert_info(self._h, C.byref(n), C.byref(p), ks), self._h)
+                self.part_features = p.value
+                self.experts = [(moe.DATASETS[e], int(ks[e])) for e in range(n.value)]
+                self.Kmax = max(k for _, k in self.experts)
+                self.dataset = 'coco'
+                if dataset is not None:
+                    self.set_dataset(dataset)
         except Exception:
             self.close()
             raise
@@ -87,6 +111,37 @@ class VitPoseHip:
         if code == capi.VP_ERR_SHAPE:
             raise RuntimeError(capi.last_error(self._h))  # load_state_dict's "size mismatch"
         capi.check(code, self._h)
+
+    # ------------------------------------------------------------ ViTPose+
+    def set_dataset(self, name: str):
+        """ViTPose+ handle: every method from now on runs this dataset's expert and head (vp_set_expert); K follows it."""
+        names = [d for d, _ in self.experts]
+        if not self._moe:
+            raise capi.VpError(capi.VP_ERR_STATE, 'set_dataset: a plain checkpoint has one dataset')
+        if name not in names:
+            raise ValueError(f'unknown dataset {name!r} for this ViTPose+ checkpoint: one of {", ".join(names)}')
+        e = names.index(name)
+        capi.check(self.lib.vp_set_expert(self._h, e), self._h)
+        self.dataset, self.K = name, self.experts[e][1]
+
+    def infer_mixed(self, crops: np.ndarray, datasets, org_wh=None):
+        """One call, a dataset per crop (vp_infer_experts): returns ``(out, k)`` -- ``out`` float32 [N, Kmax, 3] where crop i fills
+        its first ``k[i]`` joints (the rest are 0), ``k`` int32 [N].  `datasets`: names or expert indices."""
+        names = [d for d, _ in self.experts]
+        ids = np.ascontiguousarray([names.index(d) if isinstance(d, str) and d in names else (d if not isinstance(d, str) else -1)
+                                    for d in datasets], dtype=np.int32)
+        crops = np.ascontiguousarray(crops)
+        fmt = self._fmt(crops)
+        n = crops.shape[0]
+        assert len(ids) == n, 'one dataset per crop'
+        Kmax = getattr(self, 'Kmax', self.K)
+        out = np.empty((n, Kmax, 3), dtype=np.float32)
+        wh = None if org_wh is None else np.ascontiguousarray(org_wh, dtype=np.int32).reshape(n, 2)
+        if n:
+            capi.check(self.lib.vp_infer_experts(self._h, crops.ctypes.data, fmt, n, ids.ctypes.data,
+                                                 None if wh is None else wh.ctypes.data, out.ctypes.data), self._h)
+        ks = np.array([self.experts[i][1] if 0 <= i < len(self.experts) else 0 for i in ids], dtype=np.int32)
+        return out, ks
 
     # ------------------------------------------------------------ inference
     @staticmethod

@@ -24,6 +24,7 @@ import numpy as np
 from .configs import IMG_H, IMG_W, infer_dataset_by_path, infer_variant_from_state_dict, model_shape
 from .cropprep import crop_params, resize_linear_u8
 from .engine import VitPoseHip, decode_heatmaps
+from .moe import DATASETS as MOE_DATASETS, is_vitpose_plus
 
 __all__ = ['VitInference']
 
@@ -70,12 +71,19 @@ class VitInference:
                  yolo_step: Optional[int] = 1,
                  *, dtype: str = 'fp16', max_batch: int = 64, tracker=None):
         state_dict = None
+        dataset_given = dataset is not None
         if isinstance(model, (str, os.PathLike)):
             assert os.path.isfile(model), f'The model file {model} does not exist'
             assert not str(model).endswith(('.onnx', '.engine')), \
                 'the HIP backend loads .pth checkpoints only (no ONNX / TensorRT dispatch)'
             if dataset is None:
-                dataset = infer_dataset_by_path(str(model))
+                try:
+                    dataset = infer_dataset_by_path(str(model))
+                except ValueError:
+                    state_dict = self._load_pth(model)
+                    if is_vitpose_plus(state_dict):
+                        raise ValueError(self._moe_needs_dataset(model)) from None
+                    raise
         else:  # an in-memory state dict (extension; used by tests / benchmarks)
             state_dict = model
             assert dataset is not None, 'dataset must be given with an in-memory state dict'
@@ -117,9 +125,12 @@ class VitInference:
         assert model_name in [None, 's', 'b', 'l', 'h'], f'The model name {model_name} is not valid'
 
         if state_dict is None:
-            import torch
-            ckpt = torch.load(model, map_location='cpu', weights_only=True)
-            state_dict = ckpt['state_dict'] if 'state_dict' in ckpt else ckpt
+            state_dict = self._load_pth(model)
+        plus = is_vitpose_plus(state_dict)
+        if plus and not dataset_given:   # ViTPose+ (one file, six datasets): the filename cannot tell which head is wanted
+            raise ValueError(self._moe_needs_dataset(model))
+        if plus and dataset not in MOE_DATASETS:
+            raise ValueError(f'dataset {dataset!r} is not one of the ViTPose+ datasets: {", ".join(MOE_DATASETS)}')
         if model_name is None:
             model_name = infer_variant_from_state_dict(state_dict)
         nk = None
@@ -128,8 +139,19 @@ class VitInference:
         self.target_size = [IMG_W, IMG_H]  # data_cfg['image_size'], ViTPose_common.py:30
         dev_id = int(str(device).split(':')[1]) if ':' in str(device) else 0
         self._vit_pose = VitPoseHip(model_shape(model_name, None if nk else dataset, nk), state_dict,
-                                    dtype=dtype, device_id=dev_id, max_batch=max_batch)
+                                    dtype=dtype, device_id=dev_id, max_batch=max_batch, dataset=dataset if plus else None)
         self._inference = self._inference_hip
+
+    @staticmethod
+    def _load_pth(path):
+        import torch
+        ckpt = torch.load(path, map_location='cpu', weights_only=True)
+        return ckpt['state_dict'] if 'state_dict' in ckpt else ckpt
+
+    @staticmethod
+    def _moe_needs_dataset(model) -> str:
+        where = f' {model}' if isinstance(model, (str, os.PathLike)) else ''
+        return (f'the ViTPose+ checkpoint{where} holds six datasets: pass dataset= one of {", ".join(MOE_DATASETS)}')
 
     # ----------------------------------------------------------------- glue
     def _call_ultralytics(self, img_rgb):

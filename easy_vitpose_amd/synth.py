@@ -87,9 +87,22 @@ def synthetic_state_dict(shape: ModelShape, seed: int = 0, peaked: bool = False,
         sd[p + 'mlp.fc2.bias'] = normal((D,), 0.02)
     sd['backbone.last_norm.weight'] = normal((D,), 0.1, 1.0)
     sd['backbone.last_norm.bias'] = normal((D,), 0.05)
+    _random_head(sd, 'keypoint_head', rng, D, K)
+    if outliers:
+        _make_outliers(sd, shape, seed)
+    if peaked:
+        _make_peaked(sd, shape, seed, outliers)
+    return sd
+
+
+def _random_head(sd, prefix: str, rng, D: int, K: int) -> None:
+    """The random keypoint head (table above) under `prefix`, drawn from `rng` in key order."""
+    def normal(shp, std, mean=0.0):
+        return (rng.standard_normal(shp, dtype=np.float32) * np.float32(std) + np.float32(mean)).astype(np.float32)
+
     cin = D
-    for j, idx in enumerate((0, 3)):
-        h = 'keypoint_head.deconv_layers.'
+    for idx in (0, 3):
+        h = f'{prefix}.deconv_layers.'
         sd[f'{h}{idx}.weight'] = normal((cin, 256, 4, 4), float(np.sqrt(2.0 / (4 * cin))))
         sd[f'{h}{idx + 1}.weight'] = normal((256,), 0.1, 1.0)
         sd[f'{h}{idx + 1}.bias'] = normal((256,), 0.1)
@@ -97,13 +110,8 @@ def synthetic_state_dict(shape: ModelShape, seed: int = 0, peaked: bool = False,
         sd[f'{h}{idx + 1}.running_var'] = rng.uniform(0.5, 1.5, size=(256,)).astype(np.float32)
         sd[f'{h}{idx + 1}.num_batches_tracked'] = np.array(0, dtype=np.int64)
         cin = 256
-    sd['keypoint_head.final_layer.weight'] = normal((K, 256, 1, 1), 0.3 / 16.0)
-    sd['keypoint_head.final_layer.bias'] = normal((K,), 0.02)
-    if outliers:
-        _make_outliers(sd, shape, seed)
-    if peaked:
-        _make_peaked(sd, shape, seed, outliers)
-    return sd
+    sd[f'{prefix}.final_layer.weight'] = normal((K, 256, 1, 1), 0.3 / 16.0)
+    sd[f'{prefix}.final_layer.bias'] = normal((K,), 0.02)
 
 
 OUTLIER_BLOCK = 3          # the massive channels appear in the residual stream at the end of this block and stay
@@ -153,16 +161,21 @@ def _make_outliers(sd, shape: ModelShape, seed: int) -> None:
 
 
 def _make_peaked(sd, shape: ModelShape, seed: int, outliers: bool = False) -> None:
-    D, L, K = shape.embed_dim, shape.depth, shape.num_keypoints
-    rng = np.random.Generator(np.random.PCG64(seed + 7777))
+    D, L = shape.embed_dim, shape.depth
     code = (_CODE_NOMINAL_OUT if outliers else _CODE_NOMINAL).get((D, L), 0.8 * float(np.sqrt(D)))
     pos = sd['backbone.pos_embed']
     a = np.float32(2.5 * np.sqrt(D) * np.sqrt(L / 12.0))
     for t in range(192):
         pos[0, 1 + t, t] += a
+    _peak_head(sd, 'keypoint_head', np.random.Generator(np.random.PCG64(seed + 7777)), code, shape.num_keypoints)
+
+
+def _peak_head(sd, prefix: str, rng, code: float, K: int, rows: int = 0) -> None:
+    """The designed read-out of the peaked checkpoints on the head under `prefix` (K joints; `rows` > K: the final layer
+    carries rows - K more random rows, as an oversized ViTPose+ associate head does)."""
     bil = np.array([0.25, 0.75, 0.75, 0.25], dtype=np.float32)
     k2 = np.outer(bil, bil).astype(np.float32)
-    h = 'keypoint_head.deconv_layers.'
+    h = f'{prefix}.deconv_layers.'
     for idx in (0, 3):
         w = sd[f'{h}{idx}.weight'] * np.float32(0.35)
         w[:192] /= np.float32(code)
@@ -173,14 +186,50 @@ def _make_peaked(sd, shape: ModelShape, seed: int, outliers: bool = False) -> No
     s2 = sd[h + '4.weight'] / np.sqrt(sd[h + '4.running_var'] + np.float32(1e-5))
     gain = (code * s1[:192].astype(np.float64) * s2[:192].astype(np.float64)) * 0.67   # 0.67: peak of the interpolated blob / amp
     ty, tx = np.mgrid[0:16, 0:12].astype(np.float64)
-    w = (rng.standard_normal((K, 256)) * 0.02).astype(np.float32)
+    R = max(rows, K)
+    w = (rng.standard_normal((R, 256)) * 0.02).astype(np.float32)
     w[:, :192] /= np.float32(code)
     for k in range(K):
         cy, cx = rng.uniform(1.0, 14.0), rng.uniform(1.0, 10.0)
         sg, amp = rng.uniform(0.55, 0.8), rng.uniform(0.35, 0.95)
         g = amp * np.exp(-((ty - cy) ** 2 + (tx - cx) ** 2) / (2.0 * sg * sg))
         w[k, :192] += (g.reshape(-1) / gain).astype(np.float32)
-    sd['keypoint_head.final_layer.weight'] = np.ascontiguousarray(w.reshape(K, 256, 1, 1))
+    sd[f'{prefix}.final_layer.weight'] = np.ascontiguousarray(w.reshape(R, 256, 1, 1))
+
+
+def synthetic_moe_state_dict(shape: ModelShape, part_features: int, n_experts: int = 6, seed: int = 0,
+                             peaked: bool = False) -> "dict[str, np.ndarray]":
+    """A ViTPose+ state dict (easy_vitpose_amd/moe.py) with the reference's key names: ``synthetic_state_dict`` of the same
+    seed for everything shared (its coco head = ``keypoint_head``), every block's ``mlp.fc2`` cut to the first D - P output
+    features, and per expert e its own random ``mlp.experts.{e}`` rows (N(0, 0.02), seed + 1000 + e) and, for e > 0, its own
+    head ``associate_keypoint_heads.{e - 1}`` (seed + 100 + e; peaked: its own read-out, seed + 7777 + 100 + e).  The final
+    layers of the aic / mpii heads (K = 14 / 16) carry 17 rows, so that the split's ``[:K]`` cut matters.  Peaked heatmaps
+    survive because the read-out's code channels (0 .. 191) and the expert channels [D - P, D) do not overlap for P <= D - 192."""
+    from .moe import NUM_KEYPOINTS, head_prefix
+    D, L = shape.embed_dim, shape.depth
+    P = int(part_features)
+    assert 0 < P < D and n_experts <= len(NUM_KEYPOINTS)
+    base = ModelShape(shape.variant, D, L, shape.num_heads, NUM_KEYPOINTS[0])
+    sd = synthetic_state_dict(base, seed=seed, peaked=peaked)
+    for e in range(n_experts):
+        rng = np.random.Generator(np.random.PCG64(seed + 1000 + e))
+        for l in range(L):
+            p = f'backbone.blocks.{l}.mlp.'
+            sd[f'{p}experts.{e}.weight'] = (rng.standard_normal((P, 4 * D), dtype=np.float32) * np.float32(0.02)).astype(np.float32)
+            sd[f'{p}experts.{e}.bias'] = (rng.standard_normal((P,), dtype=np.float32) * np.float32(0.02)).astype(np.float32)
+    for l in range(L):
+        p = f'backbone.blocks.{l}.mlp.'
+        sd[p + 'fc2.weight'] = np.ascontiguousarray(sd[p + 'fc2.weight'][:D - P])
+        sd[p + 'fc2.bias'] = np.ascontiguousarray(sd[p + 'fc2.bias'][:D - P])
+    code = _CODE_NOMINAL.get((D, L), 0.8 * float(np.sqrt(D)))
+    for e in range(1, n_experts):
+        K = NUM_KEYPOINTS[e]
+        rows = max(K, 17)
+        pre = head_prefix(e)
+        _random_head(sd, pre, np.random.Generator(np.random.PCG64(seed + 100 + e)), D, rows)
+        if peaked:
+            _peak_head(sd, pre, np.random.Generator(np.random.PCG64(seed + 7777 + 100 + e)), code, K, rows)
+    return sd
 
 
 def synthetic_crops(n: int, seed: int = 0, kind: str = 'noise') -> np.ndarray:

@@ -211,6 +211,23 @@ VP_API int vp_infer_heatmaps(vp_handle h, const void* crops, int32_t input_forma
 /* Backbone output after last_norm (vit.py:387), float32 [N, 192, D]. */
 VP_API int vp_infer_tokens(vp_handle h, const void* crops, int32_t input_format, int32_t n, float* tokens);
 
+/* ViTPose+ checkpoints (multi-dataset "mixture of experts", the reference's model_split.py without the split).  vp_load_weights recognises a
+ * state dict with backbone.blocks.0.mlp.experts.0.weight: E experts (0 = coco with keypoint_head, e = 1..5 = aic / mpii / ap10k / apt36k /
+ * wholebody with associate_keypoint_heads.{e-1}, final layer cut to K = 14 / 16 / 17 / 17 / 133 rows), each the last P output features of every
+ * block's mlp.fc2.  The handle must have been created with num_keypoints = 17 and dtype fp16 / bf16 (fp8: VP_ERR_INVALID).
+ * vp_expert_info: *n_experts = E (0 on a plain handle), *part_features = P, k_per_expert[e] = K_e (cap 8; any pointer may be NULL). */
+VP_API int vp_expert_info(vp_handle h, int32_t* n_experts, int32_t* part_features, int32_t* k_per_expert);
+/* Make expert e the active one (default 0 = coco): every other entry point (vp_infer*, submit / wait, vp_infer_frame, vp_infer_flip,
+ * vp_infer_heatmaps, vp_infer_tokens) then runs expert e's mlp.fc2 and head, and K = K_e in every output shape -- bit for bit the handle of
+ * model_split.py's file for that dataset.  VP_ERR_INVALID for e outside [0, E), VP_ERR_STATE on a plain handle or with a vp_infer_submit in flight. */
+VP_API int vp_set_expert(vp_handle h, int32_t e);
+/* One call, one encoder pass, a different expert per crop: expert_ids[i] in [0, E).  out = float32 [n, Kmax, 3] (Kmax = the largest K_e of the
+ * checkpoint): crop i fills its first K_{e_i} joints, the rest are written as 0.  The crops are ordered by expert inside the call (mlp.fc2 of all
+ * experts in one launch per layer, one head + decode per expert present); crop i's result equals vp_set_expert(e_i) + vp_infer on that crop under
+ * the one-launch family (VP_SPLITK=0).  VP_ERR_STATE on a plain handle. */
+VP_API int vp_infer_experts(vp_handle h, const void* crops, int32_t input_format, int32_t n, const int32_t* expert_ids,
+                            const int32_t* org_wh, float* out);
+
 /* Decode alone: keypoints_from_heatmaps(unbiased=True, use_udp=True) + postprocess
  * (vit_utils/top_down_eval.py:493-641, easy_ViTPose/inference.py:187-205), one crop
  * at a time semantics.  heatmaps float32 [N, K, 64, 48] on the host. */
@@ -292,6 +309,11 @@ VP_API int vp_dbg_splitk_pick(int32_t M, int32_t N, int32_t K, int32_t* variant)
  * rows repeat the last crop, every kernel works row by row or crop by crop, so the real crops' keypoints are bit for bit those of the unpadded run; the head and the decode run
  * the real crops only.  VP_PAD_BATCH=0 switches the padding off. */
 VP_API int vp_dbg_run_batch(int32_t n, int32_t D, int32_t limit);
+/* HOST ONLY: the tile mlp.fc2 of a ViTPose+ batch that mixes experts runs -- `variant` = the tile the rules above picked for [M, N], gemm8_ok = the 8-phase
+ * kernel may run the GEMM, bounds[0 .. n_bounds) = the crops (in expert order) at which the expert changes.  Returns `variant` where no tile spans a change
+ * (32 / 64 / 96 / 192-row tiles always; 128 / 256-row tiles where every change is a multiple of 2 / 4 crops), else the crop-aligned fallback (18 = the 8-phase
+ * 192 x 256 tile, 11 = the 2-phase 192 x 128 residual tile). */
+VP_API int vp_dbg_expert_tile(int32_t variant, int32_t M, int32_t N, int32_t gemm8_ok, const int32_t* bounds, int32_t n_bounds);
 /* The two-phase schedule of a group call -- HOST ONLY, stub members: the order in which group_run would submit to (+ (member + 1)) and
  * wait for (- (member + 1)) its members for n crops on w devices of max_batch maxb.  Within every round all submissions precede the
  * first wait: no member's enqueue waits for another member's compute.  Returns the trace length (also beyond `cap`); < 0 on bad arguments. */
