@@ -28,7 +28,7 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_reset_profile', 'vp_get_profile', 'vp_profile_kernel', 'vp_group_peer_access_missing', 'vp_destroy', 'vp_last_error',
            'vp_dbg_gemm', 'vp_dbg_attention', 'vp_dbg_layernorm', 'vp_dbg_deconv', 'vp_dbg_gemm_case', 'vp_dbg_crop_prep',
            'vp_dbg_group_plan', 'vp_dbg_group_trace', 'vp_dbg_gemm8_pick', 'vp_dbg_gemm2_pick', 'vp_dbg_splitk_pick', 'vp_dbg_run_batch', 'vp_dbg_fp8_gemm', 'vp_dbg_mx_gemm', 'vp_dbg_host_e4m3', 'vp_dbg_gemm_fp8_case', 'vp_dbg_qkvattn',
-           'vp_expert_info', 'vp_set_expert', 'vp_infer_experts', 'vp_dbg_expert_tile']
+           'vp_expert_info', 'vp_set_expert', 'vp_infer_experts', 'vp_dbg_expert_tile', 'vp_infer_frames', 'vp_dbg_frame_plan']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -50,6 +50,10 @@ class vp_config(C.Structure):
 
 class vp_tensor_desc(C.Structure):
     _fields_ = [('name', C.c_char_p), ('data', C.POINTER(C.c_float)), ('numel', C.c_int64)]
+
+
+class vp_frame(C.Structure):
+    _fields_ = [('data', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32)]
 
 
 class vp_profile(C.Structure):
@@ -98,6 +102,8 @@ def load_library():
     lib.vp_group_last_error.argtypes = [H]
     lib.vp_group_last_error.restype = C.c_char_p
     lib.vp_infer_frame.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.vp_infer_frames.argtypes = [H, C.POINTER(vp_frame), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.vp_dbg_frame_plan.argtypes = [C.POINTER(vp_frame), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.vp_dbg_crop_prep.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.vp_infer_heatmaps.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.vp_infer_tokens.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]

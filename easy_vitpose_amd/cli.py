@@ -5,6 +5,7 @@ pose path, track across frames (``is_video``), report FPS and write the ``--save
 
     python -m easy_vitpose_amd.cli --input frame.png --model vitpose-b-coco.pth --yolo yolov8s.pt --output-path out --save-json
     python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --output-path out --save-json
+    python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --frame-batch 16   # 16 frames per pose call
 
 Not rebuilt (outside the hot path): drawing / preview windows (``--show``, ``--save-img``: OpenCV) and video
 decoding -- a video is accepted as a ``.npy`` stack ``[frames, H, W, 3]`` uint8 RGB, or as a directory of image files.
@@ -61,10 +62,12 @@ def main(argv=None) -> int:
     ap.add_argument('--save-img', action='store_true')
     ap.add_argument('--max-batch', type=int, default=64)
     ap.add_argument('--dtype', default='fp16', choices=['fp16', 'bf16'])
+    ap.add_argument('--frame-batch', type=int, default=1, help='frames per pose call: the crops of N frames run as one batch (VitInference.inference_frames)')
     args = ap.parse_args(argv)
     assert not (args.show or args.save_img), 'drawing / preview (OpenCV) is outside the HIP hot path: use --save-json'
     assert not args.save_json or args.output_path, 'Specify an output path if using save-img or save-json flags'
     assert (args.model is None) != (args.synthetic is None), 'give exactly one of --model / --synthetic'
+    assert args.frame_batch >= 1, '--frame-batch must be at least 1'
 
     from easy_vitpose_amd import VitInference
     from easy_vitpose_amd.configs import model_shape
@@ -94,10 +97,11 @@ def main(argv=None) -> int:
     print(f'>>> Model loaded: {args.model or "synthetic ViTPose-" + args.synthetic.upper()}')
     print(f'>>> Running inference on {args.input}')
     keypoints, dts = [], []
-    for img in frames:
+    for s in range(0, len(frames), args.frame_batch):
+        batch = frames[s:s + args.frame_batch]
         t0 = time.time()
-        keypoints.append(model.inference(img))
-        dts.append(time.time() - t0)
+        keypoints.extend(model.inference_frames(batch))
+        dts.extend([(time.time() - t0) / len(batch)] * len(batch))   # per frame: the batch's time over its frame count
     if is_video:
         tot = sum(len(k) for k in keypoints)
         print(f'>>> Mean inference FPS: {1 / np.mean(dts):.2f}')

@@ -75,6 +75,18 @@ def crop_params(bboxes: np.ndarray, frame_hw, pad_bbox: int = 10, aspect: float 
     return out
 
 
+def frames_crop_params(boxes_per_frame, frame_shapes, pad_bbox: int = 10) -> np.ndarray:
+    """The crops of several frames as one int32 [n, 9] table {frame, x0, y0, cw, ch, left_pad, top_pad, pw, ph} (vp_infer_frames):
+    `crop_params` of each frame's boxes with the frame index in front, frame by frame; a frame without boxes adds no row."""
+    rows = [np.zeros((0, 9), dtype=np.int32)]
+    for f, (boxes, shape) in enumerate(zip(boxes_per_frame, frame_shapes)):
+        if len(boxes) == 0:
+            continue
+        p = crop_params(boxes, tuple(shape)[:2], pad_bbox)
+        rows.append(np.concatenate([np.full((len(p), 1), f, dtype=np.int32), p], axis=1))
+    return np.concatenate(rows)
+
+
 def prepare_crops_host(frame: np.ndarray, params: np.ndarray) -> np.ndarray:
     """Host restatement of the crop path -> uint8 [n, 256, 192, 3] (what the HIP kernel must reproduce)."""
     out = np.empty((len(params), IMG_H, IMG_W, 3), dtype=np.uint8)

@@ -130,9 +130,9 @@ struct vp_ctx {
     bool foreign_pending = false;           // the last user was a caller's stream: ev_sw, recorded behind its launches, is what work on any other stream waits for
     hipEvent_t ev_sw = nullptr;
     int caller_stream_max_n = 16;           // batches up to this many crops take that path (VP_CALLER_STREAM=0: off)
-    uint8_t* frame_stage = nullptr;   // device copy of the current video frame (vp_infer_frame)
+    uint8_t* frame_stage = nullptr;   // staging arena of vp_infer_frames / vp_infer_frame: the row band of every host frame of the current call
     size_t frame_cap = 0;
-    int32_t* cparams = nullptr;       // per-crop geometry [max_batch, 8]
+    vp::CropRec* crecs = nullptr;     // per-crop source + geometry of the current chunk [max_batch]
     // ViTPose+ (multi-dataset "mixture of experts") handle, vp_load_weights on a state dict with backbone.blocks.*.mlp.experts.*: mlp.fc2 of block l is one full
     // [D, 4D] matrix + [D] bias per expert (the split model's: shared rows then the expert's P rows), blocks[l].w_fc2 / b_fc2 point at expert 0 and expert e lies
     // e * fc2_w_stride / fc2_b_stride elements behind; one keypoint head per expert.  `expert` = the active one (vp_set_expert): its fc2 slice, its head and its
@@ -219,6 +219,13 @@ bool prof_begin(vp_ctx* c, int fam, double flops, double bytes);
 void prof_end(vp_ctx* c, bool on);
 void prof_collect(vp_ctx* c);
 void apply_gemm_tuning(vp_ctx* c);
+// vp_infer_frames' plan (HOST ONLY): checks every crop of p9 [n, 9] against its frame, bands [n_frames, 2] = rows [row0, row1) its crops cover
+// ({0, 0}: no crop; may be NULL).  VP_OK or VP_ERR_INVALID with the reason in *why
+int frame_plan(const vp_frame* frames, int n_frames, const int32_t* p9, int n, int32_t* bands, std::string* why);
+// the crops of p9 from frames as crop-kernel records: host frames are uploaded band by band into c->frame_stage (one copy per frame with
+// crops), device frames are read in place (checked to be device memory of the handle's device first).  recs[n] (host), enqueued on c->stream
+int stage_frames(vp_ctx* c, const vp_frame* frames, int n_frames, bool on_device, const int32_t* p9, int n, const int32_t* bands,
+                 std::vector<vp::CropRec>& recs);
 
 #define LAUNCH(c, fam, flops, bytes, expr)   \
     do {                                     \

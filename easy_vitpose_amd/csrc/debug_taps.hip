@@ -606,19 +606,27 @@ VP_API int vp_dbg_gemm_compare(int32_t device, int32_t dtype, int32_t epi, int32
 }
 #endif  // VP_TOOLS
 
-// frame + crop geometry -> the uint8 [n,256,192,3] crops the model is fed (device crop/pad/resize kernel alone)
+// frame + crop geometry -> the uint8 [n,256,192,3] crops the model is fed (the device crop/pad/resize kernel alone, behind the staging of
+// vp_infer_frames: the one-frame case)
 VP_API int vp_dbg_crop_prep(int32_t device, const uint8_t* frame, int32_t fh, int32_t fw, const int32_t* crop_params, int32_t n, uint8_t* out) {
     if (!frame || !crop_params || !out || n <= 0 || fh <= 0 || fw <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
+    const vp_frame fr{frame, fh, fw};
+    std::vector<int32_t> p9((size_t)n * 9, 0);
+    for (int i = 0; i < n; ++i) std::memcpy(&p9[9 * (size_t)i + 1], crop_params + 8 * (size_t)i, 32);
+    int32_t band[2];
+    std::string why;
+    if (frame_plan(&fr, 1, p9.data(), n, band, &why)) return fail(nullptr, VP_ERR_INVALID, why);
     vp_ctx* c = dbg_ctx(device, VP_DTYPE_F16);
     if (!c) return VP_ERR_HIP;
-    uint8_t *df, *dout;
-    int32_t* dp;
+    std::vector<vp::CropRec> recs;
+    uint8_t* dout;
+    vp::CropRec* drec;
     int rc;
-    const size_t fb = (size_t)fh * fw * 3, ob = (size_t)n * 256 * 192 * 3;
-    if ((rc = dalloc(c, &df, fb)) || (rc = dalloc(c, &dout, ob)) || (rc = dalloc(c, &dp, (size_t)n * 8))) return dbg_finish(c, rc);
-    hipError_t e = hipMemcpy(df, frame, fb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dp, crop_params, (size_t)n * 32, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = vp::crop_resize_launch(df, fh, fw, dp, dout, n, nullptr);
+    const size_t ob = (size_t)n * 256 * 192 * 3;
+    if ((rc = stage_frames(c, &fr, 1, false, p9.data(), n, band, recs)) || (rc = dalloc(c, &dout, ob)) || (rc = dalloc(c, &drec, (size_t)n)))
+        return dbg_finish(c, rc);
+    hipError_t e = hipMemcpy(drec, recs.data(), (size_t)n * sizeof(vp::CropRec), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = vp::crop_resize_launch(drec, dout, n, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(c, VP_ERR_HIP, std::string("crop_prep: ") + hipGetErrorString(e));

@@ -813,15 +813,15 @@ __device__ __forceinline__ AxisCoef axis_coef(int d, int dsize, int ssize) {
     return c;
 }
 
-__global__ __launch_bounds__(192) void crop_resize_kernel(const uint8_t* __restrict__ frame, int FH, int FW,
-                                                          const int32_t* __restrict__ params, uint8_t* __restrict__ out) {
+__global__ __launch_bounds__(192) void crop_resize_kernel(const CropRec* __restrict__ recs, uint8_t* __restrict__ out) {
     const int crop = blockIdx.x >> 8, oy = blockIdx.x & 255, ox = threadIdx.x;
-    const int32_t* p = params + crop * 8;
-    const int x0 = p[0], y0 = p[1], cw = p[2], ch = p[3], left = p[4], top = p[5], pw = p[6], ph = p[7];
+    const CropRec r = recs[crop];   // each crop its own source (band or device frame) and pitch: one kernel for one or many frames
+    const uint8_t* __restrict__ src = r.src;
+    const int cw = r.cw, ch = r.ch, left = r.left, top = r.top, pw = r.pw, ph = r.ph;
     auto px = [&](int Y, int X, int c) -> int {   // padded-canvas pixel
         const int yy = Y - top, xx = X - left;
         if ((unsigned)yy >= (unsigned)ch || (unsigned)xx >= (unsigned)cw) return 0;
-        return frame[((size_t)(y0 + yy) * FW + (x0 + xx)) * 3 + c];
+        return src[(size_t)yy * r.pitch + (size_t)xx * 3 + c];
     };
     uint8_t* dst = out + (((size_t)crop * 256 + oy) * 192 + ox) * 3;
     if (pw == 384 && ph == 512) {                 // exactly 2x: OpenCV's INTER_LINEAR == fast INTER_AREA
@@ -840,8 +840,8 @@ __global__ __launch_bounds__(192) void crop_resize_kernel(const uint8_t* __restr
     }
 }
 
-hipError_t crop_resize_launch(const uint8_t* frame, int FH, int FW, const int32_t* params, uint8_t* out, int n, hipStream_t s) {
-    hipLaunchKernelGGL(crop_resize_kernel, dim3(n * 256), dim3(192), 0, s, frame, FH, FW, params, out);
+hipError_t crop_resize_launch(const CropRec* recs, uint8_t* out, int n, hipStream_t s) {
+    hipLaunchKernelGGL(crop_resize_kernel, dim3(n * 256), dim3(192), 0, s, recs, out);
     return hipGetLastError();
 }
 

@@ -195,8 +195,15 @@ hipError_t gather_crops_launch(const void* src, void* dst, const int32_t* idx, i
 // flip-test: hm = 0.5 (hm + flip_back(hm_flipped)); partner[k] = mirror joint of k (k itself if unpaired)
 hipError_t flip_merge_launch(float* hm, const float* hm_flipped, const int32_t* partner, int N, int K, int shift, hipStream_t s);
 
-// frame u8 [FH,FW,3] + params int32 [n,8] (x0,y0,cw,ch,left,top,pw,ph) -> crops u8 [n,256,192,3]
-hipError_t crop_resize_launch(const uint8_t* frame, int FH, int FW, const int32_t* params, uint8_t* out, int n, hipStream_t s);
+// one crop of a frame: src = the frame's pixel (y0, x0) (in a staged row band or in the caller's device frame), pitch = bytes per frame row;
+// the crop is [ch, cw] pixels, placed at (top, left) of a zero [ph, pw] canvas (vp_infer_frames builds these on the host)
+struct CropRec {
+    const uint8_t* src;
+    int64_t pitch;
+    int32_t cw, ch, left, top, pw, ph;
+};
+// recs: device CropRec [n] -> crops u8 [n,256,192,3]
+hipError_t crop_resize_launch(const CropRec* recs, uint8_t* out, int n, hipStream_t s);
 
 // --------------------------------------------------------------------- decode
 // heatmaps fp32 [N, K, 64, 48] -> out fp32 [N, K, 3] (y, x, conf); org_wh int32 [N,2] or null

@@ -519,6 +519,110 @@ int check_ready(vp_ctx* c, int fmt, int n, const void* p0, const void* p1, bool 
 
 }  // namespace
 
+namespace vpi {   // shared with debug_taps.hip (vp_dbg_crop_prep)
+
+int frame_plan(const vp_frame* frames, int n_frames, const int32_t* p9, int n, int32_t* bands, std::string* why) {
+    auto bad = [&](const std::string& m) { if (why) *why = m; return VP_ERR_INVALID; };
+    if (n < 0) return bad("negative crop count");
+    if (n > 0 && n_frames <= 0) return bad("crops given but no frames");
+    if (n > 0 && (!frames || !p9)) return bad("null frame or crop table");
+    const int nf = n_frames > 0 ? n_frames : 0;
+    std::vector<int64_t> lo(nf, INT64_MAX), hi(nf, -1);
+    for (int i = 0; i < n; ++i) {
+        const int32_t* p = p9 + 9 * (size_t)i;
+        const int f = p[0];
+        const std::string at = "crop " + std::to_string(i) + ": ";
+        if (f < 0 || f >= n_frames) return bad(at + "frame index " + std::to_string(f) + " outside [0, " + std::to_string(n_frames) + ")");
+        const vp_frame& fr = frames[f];
+        if (!fr.data) return bad(at + "frame " + std::to_string(f) + " has no data");
+        if (fr.h <= 0 || fr.w <= 0) return bad(at + "frame " + std::to_string(f) + " has a non-positive size");
+        const int64_t x0 = p[1], y0 = p[2], cw = p[3], ch = p[4], left = p[5], top = p[6], pw = p[7], ph = p[8];
+        if (cw <= 0 || ch <= 0 || pw <= 0 || ph <= 0) return bad(at + "non-positive crop or canvas size");
+        if (x0 < 0 || y0 < 0 || x0 + cw > fr.w || y0 + ch > fr.h || left < 0 || top < 0 || left + cw > pw || top + ch > ph)
+            return bad(at + "lies outside frame " + std::to_string(f) + " / its padded canvas");
+        lo[f] = std::min(lo[f], y0);
+        hi[f] = std::max(hi[f], y0 + ch);
+    }
+    if (bands)
+        for (int f = 0; f < nf; ++f) {
+            bands[2 * f] = hi[f] < 0 ? 0 : (int32_t)lo[f];
+            bands[2 * f + 1] = hi[f] < 0 ? 0 : (int32_t)hi[f];
+        }
+    return VP_OK;
+}
+
+int stage_frames(vp_ctx* c, const vp_frame* frames, int n_frames, bool on_device, const int32_t* p9, int n, const int32_t* bands,
+                 std::vector<vp::CropRec>& recs) {
+    std::vector<const uint8_t*> row0_ptr(n_frames, nullptr);   // row bands[2 f] of frame f, where the kernel reads it
+    if (on_device) {
+        for (int f = 0; f < n_frames; ++f) {
+            if (bands[2 * f] == bands[2 * f + 1]) continue;
+            const vp_frame& fr = frames[f];
+            const size_t fbytes = (size_t)fr.h * fr.w * 3;
+            hipPointerAttribute_t a;
+            std::memset(&a, 0, sizeof(a));
+            void* base = nullptr;
+            size_t size = 0;
+            bool ok = hipPointerGetAttributes(&a, fr.data) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->cfg.device_id;
+            ok = ok && hipMemGetAddressRange(&base, &size, (void*)fr.data) == hipSuccess && fr.data + fbytes <= (const uint8_t*)base + size;
+            if (!ok) {
+                (void)hipGetLastError();
+                return fail(c, VP_ERR_INVALID, "frame " + std::to_string(f) + " is not device memory of device " + std::to_string(c->cfg.device_id) +
+                                                   " (or runs past the end of its allocation)");
+            }
+            row0_ptr[f] = fr.data + (size_t)bands[2 * f] * fr.w * 3;
+        }
+    } else {
+        std::vector<size_t> off(n_frames, 0);
+        size_t total = 0;
+        for (int f = 0; f < n_frames; ++f) {
+            if (bands[2 * f] == bands[2 * f + 1]) continue;
+            off[f] = total;
+            total += ((size_t)(bands[2 * f + 1] - bands[2 * f]) * frames[f].w * 3 + 255) & ~(size_t)255;
+        }
+        if (total > c->frame_cap) {   // grow the arena and release the smaller one (never shrunk): growing resolutions must not grow device memory
+            void* q = nullptr;
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (hipMalloc(&q, total + 256) != hipSuccess) {   // the old arena stays: the handle remains usable
+                (void)hipGetLastError();
+                return fail(c, VP_ERR_HIP, "cannot allocate a " + std::to_string(total) + "-byte frame staging arena");
+            }
+            if (c->frame_stage) {
+                for (auto it = c->allocs.begin(); it != c->allocs.end(); ++it)
+                    if (*it == (void*)c->frame_stage) { c->allocs.erase(it); break; }
+                hipFree(c->frame_stage);
+            }
+            c->allocs.push_back(q);
+            c->frame_stage = (uint8_t*)q;
+            c->frame_cap = total;
+        }
+        for (int f = 0; f < n_frames; ++f) {   // ONE copy per frame with crops: its row band, full width
+            if (bands[2 * f] == bands[2 * f + 1]) continue;
+            const size_t pitch = (size_t)frames[f].w * 3;
+            HIPCHK(c, hipMemcpyAsync(c->frame_stage + off[f], frames[f].data + (size_t)bands[2 * f] * pitch,
+                                     (size_t)(bands[2 * f + 1] - bands[2 * f]) * pitch, hipMemcpyHostToDevice, c->stream));
+            row0_ptr[f] = c->frame_stage + off[f];
+        }
+    }
+    recs.resize(n);
+    for (int i = 0; i < n; ++i) {
+        const int32_t* p = p9 + 9 * (size_t)i;
+        const int f = p[0];
+        const int64_t pitch = (int64_t)frames[f].w * 3;
+        vp::CropRec& r = recs[i];
+        r.src = row0_ptr[f] + (size_t)(p[2] - bands[2 * f]) * pitch + (size_t)p[1] * 3;
+        r.pitch = pitch;
+        r.cw = p[3]; r.ch = p[4]; r.left = p[5]; r.top = p[6]; r.pw = p[7]; r.ph = p[8];
+    }
+    return VP_OK;
+}
+
+}  // namespace vpi
+
+namespace {
+
+}  // namespace
+
 extern "C" {
 
 int vp_abi_version(void) { return VP_ABI_VERSION; }
@@ -1008,47 +1112,51 @@ int vp_infer_experts(vp_handle c, const void* crops, int32_t fmt, int32_t n, con
     return rc;
 }
 
-int vp_infer_frame(vp_handle c, const uint8_t* frame, int32_t fh, int32_t fw, const int32_t* crop_params, int32_t n, float* out) {
-    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, frame, out);
-    if (rc) return rc;
-    if (fh <= 0 || fw <= 0 || (n > 0 && !crop_params)) return fail(c, VP_ERR_INVALID, "bad frame geometry");
-    const size_t fbytes = (size_t)fh * fw * 3;
-    if (fbytes > c->frame_cap) {
-        void* q = nullptr;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMalloc(&q, fbytes + 256));
-        if (c->frame_stage) {        // release the smaller staging buffer now: growing resolutions must not grow device memory
-            for (auto it = c->allocs.begin(); it != c->allocs.end(); ++it)
-                if (*it == (void*)c->frame_stage) { c->allocs.erase(it); break; }
-            hipFree(c->frame_stage);
-        }
-        c->allocs.push_back(q);
-        c->frame_stage = (uint8_t*)q;
-        c->frame_cap = fbytes;
-    }
-    if (!c->cparams && (rc = dalloc(c, &c->cparams, (size_t)c->maxb * 8))) return rc;
-    for (int i = 0; i < n; ++i) {
-        const int32_t* p = crop_params + 8 * (size_t)i;
-        if (p[0] < 0 || p[1] < 0 || p[2] <= 0 || p[3] <= 0 || p[0] + p[2] > fw || p[1] + p[3] > fh || p[4] < 0 || p[5] < 0 ||
-            p[4] + p[2] > p[6] || p[5] + p[3] > p[7])
-            return fail(c, VP_ERR_INVALID, "crop " + std::to_string(i) + " lies outside the frame / its padded canvas");
-    }
-    HIPCHK(c, hipMemcpyAsync(c->frame_stage, frame, fbytes, hipMemcpyHostToDevice, c->stream));
-    for (int off = 0; off < n; off += c->maxb) {
+int vp_infer_frames(vp_handle c, const vp_frame* frames, int32_t n_frames, int32_t on_device, const int32_t* p9, int32_t n, float* out) {
+    if (!c) return VP_ERR_INVALID;
+    std::vector<int32_t> bands((size_t)(n_frames > 0 ? n_frames : 0) * 2);
+    std::string why;
+    if (frame_plan(frames, n_frames, p9, n, bands.data(), &why)) return fail(c, VP_ERR_INVALID, why);   // before any copy or launch
+    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, p9, out);
+    if (rc || n == 0) return rc;
+    std::vector<vp::CropRec> recs;
+    if ((rc = stage_frames(c, frames, n_frames, on_device != 0, p9, n, bands.data(), recs))) return rc;
+    if (!c->crecs && (rc = dalloc(c, &c->crecs, (size_t)c->maxb))) return rc;
+    std::vector<int32_t> wh((size_t)c->maxb * 2);
+    for (int off = 0; off < n; off += c->maxb) {   // vp_infer's chunks: the same crops per chunk, so the same bits
         const int nb = (n - off < c->maxb) ? n - off : c->maxb;
-        HIPCHK(c, hipMemcpyAsync(c->cparams, crop_params + 8 * (size_t)off, (size_t)nb * 32, hipMemcpyHostToDevice, c->stream));
-        LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5,
-               vp::crop_resize_launch(c->frame_stage, fh, fw, c->cparams, (uint8_t*)c->in_stage, nb, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->crecs, recs.data() + off, (size_t)nb * sizeof(vp::CropRec), hipMemcpyHostToDevice, c->stream));
+        LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5, vp::crop_resize_launch(c->crecs, (uint8_t*)c->in_stage, nb, c->stream));
         // decode scales by the padded-canvas size (pw, ph) of each crop = the image pre_img receives
-        std::vector<int32_t> wh((size_t)nb * 2);
-        for (int i = 0; i < nb; ++i) { wh[2 * i] = crop_params[8 * (size_t)(off + i) + 6]; wh[2 * i + 1] = crop_params[8 * (size_t)(off + i) + 7]; }
+        for (int i = 0; i < nb; ++i) { wh[2 * i] = p9[9 * (size_t)(off + i) + 7]; wh[2 * i + 1] = p9[9 * (size_t)(off + i) + 8]; }
         HIPCHK(c, hipMemcpyAsync(c->wh_stage, wh.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // wh is a stack-lifetime host buffer
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // recs / wh are rewritten for the next chunk
         if ((rc = run_chunk(c, c->in_stage, VP_INPUT_U8_NHWC, nb, c->wh_stage, c->kp))) return rc;
         HIPCHK(c, hipMemcpyAsync(out + (size_t)off * c->Kp * 3, c->kp, (size_t)nb * c->Kp * 12, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return VP_OK;
+}
+
+// the one-frame case of vp_infer_frames
+int vp_infer_frame(vp_handle c, const uint8_t* frame, int32_t fh, int32_t fw, const int32_t* crop_params, int32_t n, float* out) {
+    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, frame, out);
+    if (rc) return rc;
+    if (fh <= 0 || fw <= 0 || (n > 0 && !crop_params)) return fail(c, VP_ERR_INVALID, "bad frame geometry");
+    const vp_frame fr{frame, fh, fw};
+    std::vector<int32_t> p9((size_t)n * 9);
+    for (int i = 0; i < n; ++i) {
+        p9[9 * (size_t)i] = 0;
+        std::memcpy(&p9[9 * (size_t)i + 1], crop_params + 8 * (size_t)i, 32);
+    }
+    return vp_infer_frames(c, &fr, 1, 0, p9.data(), n, out);
+}
+
+int vp_dbg_frame_plan(const vp_frame* frames, int32_t n_frames, const int32_t* params9, int32_t n, int32_t* bands) {
+    std::string why;
+    const int rc = frame_plan(frames, n_frames, params9, n, bands, &why);
+    if (rc) g_create_error = why;
+    return rc;
 }
 
 int vp_decode_only(int32_t device_id, const float* heatmaps, int32_t n, int32_t k, const int32_t* org_wh, float* out) {

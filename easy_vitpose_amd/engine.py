@@ -244,6 +244,46 @@ class VitPoseHip:
                                            params.ctypes.data, n, out.ctypes.data), self._h)
         return out
 
+    def infer_frames(self, frames, params: np.ndarray) -> np.ndarray:
+        """The crops of several frames in one call (vp_infer_frames): params [n, 9] (cropprep.frames_crop_params) -> [n, K, 3] in
+        padded-crop pixels.  `frames`: numpy uint8 [H, W, 3] arrays (host path: one upload of the row band each frame's crops cover),
+        or contiguous torch uint8 CUDA tensors [H, W, 3] on this handle's device (read in place, once torch's current stream on that
+        device has been synchronised).  A list that mixes the two raises TypeError."""
+        frames = list(frames)
+        params = np.ascontiguousarray(params, dtype=np.int32).reshape(-1, 9)
+        n = params.shape[0]
+        is_tensor = [hasattr(f, 'data_ptr') for f in frames]
+        if any(is_tensor) and not all(is_tensor):
+            raise TypeError('frames: all numpy arrays (host) or all torch CUDA tensors (device), not a mix')
+        on_device = bool(frames) and all(is_tensor)
+        table = (capi.vp_frame * max(len(frames), 1))()
+        keep = []
+        for i, f in enumerate(frames):
+            if on_device:
+                import torch
+                if not (f.is_cuda and f.dtype == torch.uint8 and f.is_contiguous()):
+                    raise TypeError('device frames must be contiguous torch uint8 CUDA tensors')
+                if f.device.index != self.device_id:
+                    raise ValueError(f'frame {i} lives on {f.device}, the handle on cuda:{self.device_id}')
+                ptr = f.data_ptr()
+            else:
+                f = np.ascontiguousarray(f)
+                if f.dtype != np.uint8:
+                    raise TypeError(f'frame {i}: uint8 expected, got {f.dtype}')
+                keep.append(f)
+                ptr = f.ctypes.data
+            if f.ndim != 3 or f.shape[2] != 3:
+                raise ValueError(f'frame {i}: [H, W, 3] expected, got {tuple(f.shape)}')
+            table[i] = capi.vp_frame(ptr, f.shape[0], f.shape[1])
+        out = np.empty((n, self.K, 3), dtype=np.float32)
+        if n == 0:
+            return out
+        if on_device:
+            import torch
+            torch.cuda.current_stream(torch.device('cuda', self.device_id)).synchronize()   # the frames are complete before the library reads them
+        capi.check(self.lib.vp_infer_frames(self._h, table, len(frames), int(on_device), params.ctypes.data, n, out.ctypes.data), self._h)
+        return out
+
     def heatmaps(self, crops: np.ndarray) -> np.ndarray:
         crops = np.ascontiguousarray(crops)
         n = crops.shape[0]

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from .configs import IMG_H, IMG_W, infer_dataset_by_path, infer_variant_from_state_dict, model_shape
-from .cropprep import crop_params, resize_linear_u8
+from .cropprep import frames_crop_params, resize_linear_u8
 from .engine import VitPoseHip, decode_heatmaps
 from .moe import DATASETS as MOE_DATASETS, is_vitpose_plus
 
@@ -206,42 +206,59 @@ class VitInference:
 
     # ------------------------------------------------------------ inference
     def inference(self, img: np.ndarray) -> "dict[typing.Any, typing.Any]":
-        """inference.py:221-281 with the crop loop batched."""
-        res_pd = np.empty((0, 5))
-        if (self.tracker is None or (self.frame_counter % self.yolo_step == 0 or self.frame_counter < 3)):
-            det = np.asarray(self.yolo(img), dtype=np.float64).reshape((-1, 5))
-            res_pd = det[det[:, 4] > 0.35].reshape((-1, 5))
-        self.frame_counter += 1
+        """inference.py:221-281 with the crop loop batched: the one-frame case of `inference_frames`."""
+        return self.inference_frames([img])[0]
 
-        ids = None
-        if self.tracker is not None:
-            res_pd = self.tracker.update(res_pd)
-            ids = res_pd[:, 5].astype(int).tolist()
-        bboxes = res_pd[:, :4].round().astype(int)
-        scores = res_pd[:, 4].tolist()
+    def inference_frames(self, imgs) -> "list[dict[typing.Any, typing.Any]]":
+        """`[self.inference(img) for img in imgs]` with ONE pose call for the crops of all frames (`vp_infer_frames`): the detector
+        runs on the same frames and the tracker is updated frame by frame, in order, as that loop would (neither depends on
+        keypoints); then every crop of every frame is cropped, padded, resized and run on device from one upload per frame, and the
+        offsets are added per crop.  `save_state` keeps the last frame's state."""
         pad_bbox = 10
-        if ids is None:
-            ids = range(len(bboxes))
+        dets = []
+        for img in imgs:
+            res_pd = np.empty((0, 5))
+            if (self.tracker is None or (self.frame_counter % self.yolo_step == 0 or self.frame_counter < 3)):
+                det = np.asarray(self.yolo(img), dtype=np.float64).reshape((-1, 5))
+                res_pd = det[det[:, 4] > 0.35].reshape((-1, 5))
+            self.frame_counter += 1
 
-        # crop + zero-pad to 3:4 + resize + normalise all happen on device from ONE copy of the frame
-        params = crop_params(bboxes, img.shape[:2], pad_bbox) if len(bboxes) else np.zeros((0, 8), np.int32)
-        for i in range(len(bboxes)):                       # keep the reference's in-place box update (:261-262)
-            bboxes[i] = (params[i, 0], params[i, 1], params[i, 0] + params[i, 2], params[i, 1] + params[i, 3])
-        offsets = [np.array([p[1] - p[5], p[0] - p[4]]) for p in params]   # bbox[:2][::-1] - [top_pad, left_pad]
-        kps = self._vit_pose.infer_frame(np.ascontiguousarray(img), params)
+            ids = None
+            if self.tracker is not None:
+                res_pd = self.tracker.update(res_pd)
+                ids = res_pd[:, 5].astype(int).tolist()
+            bboxes = res_pd[:, :4].round().astype(int)
+            scores = res_pd[:, 4].tolist()
+            if ids is None:
+                ids = range(len(bboxes))
+            dets.append((bboxes, ids, scores))
 
-        frame_keypoints, scores_bbox = {}, {}
-        for i, (id_, score) in enumerate(zip(ids, scores)):
-            k = kps[i]
-            k[:, :2] += offsets[i]
-            frame_keypoints[id_] = k
-            scores_bbox[id_] = score
-        if self.save_state:
-            self._img = img
+        # crop + zero-pad to 3:4 + resize + normalise all happen on device, each frame uploaded once
+        frames = [np.ascontiguousarray(img) for img in imgs]
+        p9 = frames_crop_params([d[0] for d in dets], [f.shape for f in frames], pad_bbox)
+        kps = self._vit_pose.infer_frames(frames, p9)
+
+        results, start = [], 0
+        for bboxes, ids, scores in dets:
+            params = p9[start:start + len(bboxes), 1:]
+            kps_f = kps[start:start + len(bboxes)]
+            start += len(bboxes)
+            for i in range(len(bboxes)):                       # keep the reference's in-place box update (:261-262)
+                bboxes[i] = (params[i, 0], params[i, 1], params[i, 0] + params[i, 2], params[i, 1] + params[i, 3])
+            offsets = [np.array([p[1] - p[5], p[0] - p[4]]) for p in params]   # bbox[:2][::-1] - [top_pad, left_pad]
+            frame_keypoints, scores_bbox = {}, {}
+            for i, (id_, score) in enumerate(zip(ids, scores)):
+                k = kps_f[i]
+                k[:, :2] += offsets[i]
+                frame_keypoints[id_] = k
+                scores_bbox[id_] = score
+            results.append((frame_keypoints, scores_bbox))
+        if self.save_state and len(imgs):
+            bboxes, ids, scores = dets[-1]
+            self._img = imgs[-1]
             self._tracker_res = (bboxes, ids, scores)
-            self._keypoints = frame_keypoints
-            self._scores_bbox = scores_bbox
-        return frame_keypoints
+            self._keypoints, self._scores_bbox = results[-1]
+        return [r[0] for r in results]
 
     def draw(self, show_yolo=True, show_raw_yolo=False, confidence_threshold=0.5):
         raise NotImplementedError('drawing (cv2/matplotlib) is outside the HIP hot path; use the keypoint dict')

@@ -197,6 +197,26 @@ VP_API const char* vp_group_last_error(vp_group_handle g);
 VP_API int vp_infer_frame(vp_handle h, const uint8_t* frame, int32_t fh, int32_t fw, const int32_t* crop_params,
                           int32_t n, float* out);
 
+/* Many frames, one call: the crops of several frames (a video chunk, several cameras) in one batch.
+ * frames[n_frames]: uint8 RGB [h, w, 3], C-contiguous.  crop_params = n x 9 int32 {frame, x0, y0, cw, ch, left_pad, top_pad, pw, ph}:
+ * the frame index, then vp_infer_frame's eight values.  Crops come in any order, any crop may name any frame, a frame may have none.
+ * The crops run in the caller's order in chunks of max_batch, exactly as vp_infer chunks them: the result has the bits of vp_infer on
+ * the host-prepared crops in the same order.  out = float32 [n, K, 3] in padded-crop pixels, as vp_infer_frame.
+ * frames_on_device = 0: every frame with at least one crop is uploaded as ONE copy of the row band its crops cover (rows [min y0,
+ * max(y0 + ch)), full width) into a device staging arena of the handle (grown, never shrunk; freed by vp_destroy); frames without
+ * crops are not copied.  frames_on_device = 1: the frames are device memory of the handle's device (checked with hipPointerGetAttributes
+ * before anything is launched) and are read in place; the caller guarantees they are complete when the call starts.
+ * Every crop is checked before any copy or launch (vp_dbg_frame_plan): VP_ERR_INVALID for a frame index outside [0, n_frames), a crop
+ * outside its frame or its padded canvas, a non-positive size, a NULL data pointer on a referenced frame, n > 0 with n_frames <= 0.
+ * n = 0: VP_OK, nothing is written.  A ViTPose+ handle runs its active expert (vp_set_expert). */
+typedef struct vp_frame {
+    const uint8_t* data;
+    int32_t h;
+    int32_t w;
+} vp_frame;
+VP_API int vp_infer_frames(vp_handle h, const vp_frame* frames, int32_t n_frames, int32_t frames_on_device,
+                           const int32_t* crop_params, int32_t n, float* out);
+
 /* Flip-test inference (the optional accuracy mode of the reference head, topdown_heatmap_simple_head.py:195-218 with
  * flip_back of vit_utils/post_processing/post_transforms.py:110-147; `flip_test=True, shift_heatmap=False` in
  * configs/ViTPose_common.py:91-93): the model runs on the crops and on their left-right mirror, the mirrored heatmaps are
@@ -292,6 +312,10 @@ VP_API int vp_dbg_gemm_case(int32_t device_id, int32_t dtype, int32_t epi, int32
  * per device (trailing devices short or empty).  Entry e = round * w + device: offs[e], cnts[e].  Returns the number of
  * entries (rounds * w), also when it exceeds `cap` (nothing is written beyond cap); < 0 on bad arguments. */
 VP_API int vp_dbg_group_plan(int32_t n, int32_t w, int32_t maxb, int32_t* offs, int32_t* cnts, int32_t cap);
+/* The plan of vp_infer_frames -- HOST ONLY, no device needed, the function vp_infer_frames runs first: checks every crop of params9 [n, 9]
+ * against frames[n_frames] (h, w and whether data is NULL; the pixels are never read) and writes bands [n_frames, 2] = the rows
+ * [row0, row1) of each frame its crops cover ({0, 0} for a frame without crops; bands may be NULL).  VP_OK or VP_ERR_INVALID. */
+VP_API int vp_dbg_frame_plan(const vp_frame* frames, int32_t n_frames, const int32_t* params9, int32_t n, int32_t* bands);
 /* HOST ONLY: which tile of the 8-phase GEMM kernel the selection rule picks for an [M, N] output -- 0 = none (2-phase kernels), 16 = 256 x 256,
  * 17 = 256 x 192, 18 = 192 x 256; wide != 0: 16-bit-output GEMMs (qkv, fc1), else the residual GEMMs; bm192_mask bits 1 / 2 as VP_G8_BM192, bit 4 = the
  * round-3 thresholds (as VP_G8_COST=0); *tiles (may be NULL) = its tile count */
