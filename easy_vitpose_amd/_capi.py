@@ -28,7 +28,8 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_reset_profile', 'vp_get_profile', 'vp_profile_kernel', 'vp_group_peer_access_missing', 'vp_destroy', 'vp_last_error',
            'vp_dbg_gemm', 'vp_dbg_attention', 'vp_dbg_layernorm', 'vp_dbg_deconv', 'vp_dbg_gemm_case', 'vp_dbg_crop_prep',
            'vp_dbg_group_plan', 'vp_dbg_group_trace', 'vp_dbg_gemm8_pick', 'vp_dbg_gemm2_pick', 'vp_dbg_splitk_pick', 'vp_dbg_run_batch', 'vp_dbg_fp8_gemm', 'vp_dbg_mx_gemm', 'vp_dbg_host_e4m3', 'vp_dbg_gemm_fp8_case', 'vp_dbg_qkvattn',
-           'vp_expert_info', 'vp_set_expert', 'vp_infer_experts', 'vp_dbg_expert_tile', 'vp_infer_frames', 'vp_dbg_frame_plan']
+           'vp_expert_info', 'vp_set_expert', 'vp_infer_experts', 'vp_dbg_expert_tile', 'vp_infer_frames', 'vp_dbg_frame_plan',
+           'vp_dbg_chunk_plan']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -150,6 +151,7 @@ def load_library():
     lib.vp_set_expert.argtypes = [H, C.c_int32]
     lib.vp_infer_experts.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vp_dbg_expert_tile.argtypes = [C.c_int32] * 4 + [C.c_void_p, C.c_int32]
+    lib.vp_dbg_chunk_plan.argtypes = [C.POINTER(vp_config), C.c_int32, C.c_void_p, C.c_int32]
     lib.vp_dbg_qkvattn.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 4
     for name in SYMBOLS:
         if name not in ('vp_stream', 'vp_last_error', 'vp_host_alloc', 'vp_host_free', 'vp_group_member', 'vp_group_last_error'):

@@ -37,10 +37,56 @@ struct Block {
     float *ws_qkv = nullptr, *ws_fc1 = nullptr, *ws_fc2 = nullptr, *ws_proj = nullptr;
 };
 
+// Every selection switch of a handle: read ONCE, at vp_create, by read_switches from the environment.  The chunk plan
+// (tile_rules.hip plan_chunk) and the orchestration read them here, never the environment.  The defaults are the shipped paths.
+struct Switches {
+    int g8_stagger = 0;               // gemm8: start delay per XCD in sleep quanta (VP_G8_STAGGER)
+    int gemm8_mask = 0x7;             // GEMMs on the 8-phase kernel at large batch: 1 fc2, 2 fc1, 4 qkv, 8 proj (VP_GEMM8; proj measured slower)
+    long g8_min_tiles = 448;          // the 8-phase tile qualifies from this many tiles (1.75 per CU; tools build: VP_G8_MIN_TILES)
+    bool persist_gemm = true;         // qkv / fc1 as persistent workgroups at large batch (VP_PERSIST=0: one tile per workgroup)
+    int order_mask = 8;               // tile walk last-to-first per GEMM: bit0 qkv, bit1 proj, bit2 fc1, bit3 fc2 (VP_ORDER)
+    bool blocked_hid = true;          // mlp hidden activations in the 64x64-blocked layout (VP_BLOCKED_HID=0: row-major)
+    bool blocked_qkv = true;          // qkv in the same blocked layout when the head dim is 64 (a (crop, head) slab = three contiguous 8 KiB blocks; VP_BLOCKED_QKV=0: row-major)
+    bool fuse_ln = true;              // LayerNorm folded into the GEMMs on both sides of it (VP_FUSE_LN=0: standalone passes)
+    bool fuse_qkv_attn = true;        // attn.qkv + attention core in one kernel where the chunk plan picks it (VP_FUSE_QKV_ATTN=0: two launches)
+    bool qa_min_set = false;          // VP_QA_MIN_TILES is given: it alone decides the head-dim-64 fused kernel (plan_chunk)
+    long qa_min_tiles = 108;          // head dim 64: the fused kernel from this many (pair, head) tiles (VP_QA_MIN_TILES)
+    long qa80_min_tiles = 192;        // head dim 80: the fused tile from this many (crop, head) tiles (VP_QA80_MIN_TILES; wins from 12 crops x 16 heads on, profiles/qkvattn80_r5.txt)
+    int qa80_group = 8;               // head dim 80 fused tile: crops per group of the tile order (VP_QA80_GROUP)
+    int attn_qsplit = 128;            // attention: three workgroups per (crop, head) up to this many (crop, head) pairs (VP_ATTN_QSPLIT; 0: never): B x 1 0.521 -> 0.495 ms,
+                                      // L x 1 1.215 -> 1.152, B x 8 0.949 -> 0.906; neutral at 128 pairs, slower from 192 on
+    int g8_bm192 = 3;                 // the 8-phase kernel's 192 x 256 tile is a candidate for: 1 = the residual GEMMs, 2 = the wide GEMMs (VP_G8_BM192)
+    bool pad_batch = true;            // the encoder runs the next multiple of 4 crops where that buys an 8-phase tile (tile_rules.hip pick_run_batch; VP_PAD_BATCH=0: never)
+    bool g8_cost_model = true;        // tile selection with the round-4 extensions (VP_G8_COST=0: the round-3 thresholds + the 192-row fallback)
+    bool deconv_parity_fast = true;   // head: the four output parities of a deconv tile run side by side on one XCD (VP_DECONV_PARITY_FAST=0: parity-major launch order)
+    bool fuse_head = true;            // VP_FUSE_HEAD=0: deconv2 and the final 1x1 conv as two launches at every batch size
+    bool fp8_proj16 = false;          // fp8 mode, head dim 64: attn.proj stays on the fp16 kernels (VP_FP8_PROJ16=1)
+    int graph_max_n = 16;             // chunks of up to this many crops are captured into a hipGraph and replayed (VP_GRAPH; 0 = off)
+    bool graph_null = true;           // ... on a caller's legacy default stream too (VP_GRAPH_NULL=0: plain launches there)
+    int caller_stream_max_n = 16;     // vp_infer_device_stream: batches up to this many crops launch on the caller's stream (VP_CALLER_STREAM=0: off)
+    bool fold_rule = true;            // beyond graph_max_n_stats crops: fold per consumer where its tile keeps its occupancy with the statistics area (plan_chunk; off when VP_FOLD_STATS is set)
+    int graph_max_n_stats = 8;        // batches of <= this many crops: the consumer GEMMs (qkv, fc1) merge the LayerNorm partial statistics of their tile rows
+                                      // themselves (once per row and tile, in the prologue: gemm.hip) and the 2 x depth ln_finalize launches disappear -- same
+                                      // ln_merge, bit-identical.  Measured (profiles/fold_stats_r3.txt): -7...-12 % per step at 1-8 crops, +0...+20 % at
+                                      // 16-48 (every column tile merges its rows again): threshold 8.  VP_FOLD_STATS=n moves it (0 = always ln_finalize).
+                                      // Round 6 (merge on a register copy, profiles/small_batch_r6.txt call 11): -2.6 ... -6.5 % against ln_finalize at 1-8 crops.
+                                      // Round 6, call 25: the '+0 ... +20 %' beyond 8 crops was the statistics area behind the default tile's 80 KiB ring (one workgroup per CU
+                                      // instead of two), not the merge: beyond this threshold each consumer folds on its own where its tile keeps its occupancy (fold_rule).
+                                      // Round 2 merged per LANE in the epilogue (16 x redundant): slower than ln_finalize even at 8 crops (3.89 vs 2.97 ms).
+    // split-K for the residual GEMMs of small batches (round 6; tile_rules.hip pick_splitk, gemm.hip EPI_PARTIAL, elementwise.hip splitk_reduce_kernel).
+    // VP_SPLITK=0 switches it off (the parity test flips it); VP_SPLITK="fc2:S:variant,proj:S:variant" overrides the rule.
+    bool splitk_on = true;
+    int splitk_force[2][2] = {{0, 0}, {0, 0}};   // [0 = proj, 1 = fc2][S, variant]; S = 0: the rule decides
+    int gemm_variant[VP_PROF_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // tile cfg per GEMM family, -1 = the rules (tools build: VP_GEMM_TUNE)
+    int gemm_group_m[VP_PROF_COUNT] = {0};
+    int fam_ablate[VP_PROF_COUNT] = {0};   // VP_TOOLS: per-family ablation / experiment bits in the forward pass (VP_ABLATE_FAM="fam:bits,...")
+};
+
 }  // namespace vpi
 
 struct vp_ctx {
     vp_config cfg;
+    vpi::Switches sw;
     int D, L, heads, Kp, dtype, maxb;
     hipStream_t stream = nullptr;
     std::string err;
@@ -63,18 +109,6 @@ struct vp_ctx {
     float *hm = nullptr, *kp = nullptr, *tok = nullptr;
     float* hm_keep = nullptr;         // flip-test: heatmaps of the un-flipped crops while the flipped pass runs
     int32_t* partner = nullptr;       // flip-test: mirror joint per joint
-    int g8_stagger = 0;               // gemm8: start delay per XCD in sleep quanta (VP_G8_STAGGER)
-    int gemm8_mask = 0x7;             // GEMMs on the 8-phase kernel at large batch: 1 fc2, 2 fc1, 4 qkv, 8 proj (VP_GEMM8; proj measured slower)
-    bool persist_gemm = true;         // qkv / fc1 as persistent workgroups at large batch (VP_PERSIST=0: one tile per workgroup)
-    int order_mask = 8;               // tile walk last-to-first per GEMM: bit0 qkv, bit1 proj, bit2 fc1, bit3 fc2 (VP_ORDER)
-    bool blocked_hid = true;          // mlp hidden activations in the 64x64-blocked layout (VP_BLOCKED_HID=0: row-major)
-    bool blocked_qkv = true;          // qkv in the same blocked layout when the head dim is 64 (a (crop, head) slab = three contiguous 8 KiB blocks; VP_BLOCKED_QKV=0: row-major)
-    bool fuse_ln = true;              // LayerNorm folded into the GEMMs on both sides of it (VP_FUSE_LN=0: standalone passes)
-    bool fuse_qkv_attn = true;        // head dim 64, even batches of >= 128 (pair, head) tiles: attn.qkv + attention core in one kernel (VP_FUSE_QKV_ATTN=0: two launches)
-    int g8_bm192 = 3;                 // the 8-phase kernel's 192 x 256 tile is a candidate for: 1 = the residual GEMMs, 2 = the wide GEMMs
-    bool pad_batch = true;            // the encoder runs the next multiple of 4 crops where that buys an 8-phase tile (tile_rules.hip pick_run_batch; VP_PAD_BATCH=0: never)
-    bool g8_cost_model = true;        // tile selection with the round-4 extensions (VP_G8_COST=0: the round-3 thresholds + the 192-row fallback)
-    bool deconv_parity_fast = true;   // head: the four output parities of a deconv tile run side by side on one XCD (VP_DECONV_PARITY_FAST=0: parity-major launch order)
     float *ln_part = nullptr, *rowstat = nullptr;   // partial row statistics [M][D/64][2], (mean, rstd) [M][2]
     // fp8 mode (vp_config.dtype = VP_DTYPE_FP8; csrc/mx8.h, gemm8f.hip, quant8.hip): qkv / fc1 / fc2 on MXFP8 operands.  Token rows are
     // padded to Mp (a multiple of the 256-row GEMM tile, >= 512); x8 / xs8 = LayerNorm(x) as MXFP8 codes / scales, hs8 = block scales of
@@ -104,23 +138,9 @@ struct vp_ctx {
                         int expert = 0; };   // expert: a ViTPose+ handle's active expert is baked into the captured launches (fc2 weights, head, K)
     GraphEntry graphs[4];
     int graph_victim = 0;
-    bool fuse_head = true;            // VP_FUSE_HEAD=0: deconv2 and the final 1x1 conv as two launches at every batch size
-    int graph_max_n = 16;
-    bool fold_rule = true;            // beyond graph_max_n_stats crops: fold per consumer where its tile keeps its occupancy with the statistics area (forward_chunk; off when VP_FOLD_STATS is set)
-    int graph_max_n_stats = 8;        // batches of <= this many crops: the consumer GEMMs (qkv, fc1) merge the LayerNorm partial statistics of their tile rows
-                                      // themselves (once per row and tile, in the prologue: gemm.hip) and the 2 x depth ln_finalize launches disappear -- same
-                                      // ln_merge, bit-identical.  Measured (profiles/fold_stats_r3.txt): -7...-12 % per step at 1-8 crops, +0...+20 % at
-                                      // 16-48 (every column tile merges its rows again): threshold 8.  VP_FOLD_STATS=n moves it (0 = always ln_finalize).
-                                      // Round 6 (merge on a register copy, profiles/small_batch_r6.txt call 11): -2.6 ... -6.5 % against ln_finalize at 1-8 crops.
-                                      // Round 6, call 25: the '+0 ... +20 %' beyond 8 crops was the statistics area behind the default tile's 80 KiB ring (one workgroup per CU
-                                      // instead of two), not the merge: beyond this threshold each consumer folds on its own where its tile keeps its occupancy (fold_rule).
-                                      // Round 2 merged per LANE in the epilogue (16 x redundant): slower than ln_finalize even at 8 crops (3.89 vs 2.97 ms).
-    // split-K for the residual GEMMs of small batches (round 6; tile_rules.hip pick_splitk, gemm.hip EPI_PARTIAL, elementwise.hip splitk_reduce_kernel): fp32 partial
-    // products [S][M][D] of up to splitk_rows token rows.  VP_SPLITK=0 switches it off (the parity test flips it); VP_SPLITK="fc2:S:variant,proj:S:variant" overrides the rule.
+    // split-K workspace of the residual GEMMs of small batches: fp32 partial products [S][M][D] of up to splitk_rows token rows (none when Switches::splitk_on is off)
     float* splitk_ws = nullptr;
     size_t splitk_rows = 0;
-    bool splitk_on = true;
-    int splitk_force[2][2] = {{0, 0}, {0, 0}};   // [0 = proj, 1 = fc2][S, variant]; S = 0: the rule decides
     hipEvent_t ev_in = nullptr, ev_out = nullptr;   // vp_infer_device_stream: ordering against the caller's stream
     // vp_infer_device_stream at small batches (round 5): the launches go onto the CALLER's stream (c->stream points at it for the duration of that call) instead of
     // being fenced against it with two cross-stream events per call (~0.1 ms at 1-16 crops).  The handle's workspaces are then used from more than one stream over
@@ -129,7 +149,6 @@ struct vp_ctx {
     const void* last_stream_id = nullptr;   // identity of the caller's stream the workspaces were last used on (compared, never dereferenced: the caller may have destroyed it)
     bool foreign_pending = false;           // the last user was a caller's stream: ev_sw, recorded behind its launches, is what work on any other stream waits for
     hipEvent_t ev_sw = nullptr;
-    int caller_stream_max_n = 16;           // batches up to this many crops take that path (VP_CALLER_STREAM=0: off)
     uint8_t* frame_stage = nullptr;   // staging arena of vp_infer_frames / vp_infer_frame: the row band of every host frame of the current call
     size_t frame_cap = 0;
     vp::CropRec* crecs = nullptr;     // per-crop source + geometry of the current chunk [max_batch]
@@ -151,10 +170,7 @@ struct vp_ctx {
     std::vector<int> mix_bounds;
     // profiling
     uint32_t prof = 0;   // bit f = time kernel family f
-    int gemm_variant[VP_PROF_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};   // tile cfg per GEMM family, -1 = default rule
-    int gemm_group_m[VP_PROF_COUNT] = {0};
     int gemm_ablate = 0;   // profiling only
-    int fam_ablate[VP_PROF_COUNT] = {0};   // VP_TOOLS: per-family ablation / experiment bits in the forward pass (VP_ABLATE_FAM="fam:bits,...")
     struct Ev { hipEvent_t a, b; int fam; double flops, bytes; };
     std::vector<Ev> evs;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
@@ -211,6 +227,7 @@ struct Lookup {
     int64_t numel(const std::string& name) const { auto it = map.find(name); return it == map.end() ? -1 : it->second->numel; }
 };
 
+size_t final_rows(size_t kp);   // physical (hi/lo interleaved) rows of the final conv's weights for kp keypoints
 int pack_deconv(vp_ctx* c, Lookup& lk, int idx, int Cin, uint16_t** w_out, float** b_out, const std::string& head = "keypoint_head");
 void use_expert(vp_ctx* c, int e);   // make expert e of a ViTPose+ handle the active one (head pointers, Kp)
 
@@ -218,7 +235,8 @@ void use_expert(vp_ctx* c, int e);   // make expert e of a ViTPose+ handle the a
 bool prof_begin(vp_ctx* c, int fam, double flops, double bytes);
 void prof_end(vp_ctx* c, bool on);
 void prof_collect(vp_ctx* c);
-void apply_gemm_tuning(vp_ctx* c);
+void read_switches(Switches& s);      // the environment's switches (vp_create, vp_dbg_chunk_plan)
+void apply_gemm_tuning(Switches& s);  // its VP_GEMM_TUNE part (tools build only): what the parity taps' contexts take
 // vp_infer_frames' plan (HOST ONLY): checks every crop of p9 [n, 9] against its frame, bands [n_frames, 2] = rows [row0, row1) its crops cover
 // ({0, 0}: no crop; may be NULL).  VP_OK or VP_ERR_INVALID with the reason in *why
 int frame_plan(const vp_frame* frames, int n_frames, const int32_t* p9, int n, int32_t* bands, std::string* why);
@@ -247,26 +265,38 @@ struct LnFuse {
     int* tiles_out = nullptr;         // producer: number of n-tiles written per row
 };
 
-// ---- tile_rules.hip
-struct G8Pick { int variant, bm, bn; long tiles; };
-G8Pick pick_gemm8_tile(int M, int N, bool wide, int bm192_mask, long min_tiles, bool extended);
-struct Tile2Pick { int variant, group_m; };
-Tile2Pick pick_gemm2_tile(int epi, int M, int N, int K);
-// split-K of a residual GEMM (attn.proj, mlp.fc2) at small batches: S k ranges on tile configuration `variant` (S = 1: no split)
-struct SplitKPick { int S, variant; };
-SplitKPick pick_splitk(int M, int N, int K);
-int pick_run_batch(int n, int D, int limit, int bm192_mask, bool extended, int gemm8_mask);
-// ViTPose+ mixed batch: may mlp.fc2 run on a tile of bm rows when the experts change at crops `bounds`?  (no m-tile may span two experts)
-bool expert_tile_ok(int bm, const std::vector<int>& bounds);
-// the crop-aligned tile mlp.fc2 of a mixed batch takes where the rule's tile is not (gemm8_ok: the 8-phase kernel's 192 x 256 tile may run it)
-int expert_fallback_variant(int M, int N, bool gemm8_ok, int* group_m);
-int tile_bm(int variant);   // rows of a tile configuration (0: unknown)   // the batch the encoder runs for a chunk of n crops (>= n, a multiple of 4 when padded)
+// ---- tile_rules.hip: which kernel runs each GEMM of a chunk (pure host code)
 constexpr int SPLITK_MAX_S = 8, SPLITK_MAX_CROPS = 32;
+// the complete choice for one GEMM: gemm.hip Cfg id (16 / 17 / 18 = the 8-phase kernel's 256 x 256 / 256 x 192 / 192 x 256 tile; on an fp8 GEMM 16 / 17 = the MXFP8
+// kernel's 256 x 256 / 256 x 192), tile-order group, persistent workgroups, start stagger; splitk > 1: that many partial products on Cfg splitk_variant + the reduction
+struct GemmPick { int variant = -1, group_m = 0, persist = 0, stagger = 0, splitk = 1, splitk_variant = 0; };
+// fam = VP_PROF_* family, epi = kernels.h GemmEpi, [M, N] x K with ldo = N; ln_part = a LayerNorm consumer that folds the partial statistics itself;
+// splitk_rows = the rows the split-K workspace holds (0: none); mix_bounds = a ViTPose+ mixed batch's expert changes (nullptr: one expert)
+GemmPick resolve_gemm(const Switches& s, int fam, int epi, int M, int N, int K, bool ln_part = false, size_t splitk_rows = 0,
+                      const std::vector<int>* mix_bounds = nullptr);
+GemmPick resolve_gemm_fp8(int fam, int epi, int Mp, int N);   // fp8 mode: qkv / fc1 / fc2 (and attn.proj at head dim 64) on the MXFP8 kernel
+enum QkvPath { QKV_GEMM = 0, QKV_ATTN64 = 1, QKV_ATTN80 = 2 };   // attn.qkv GEMM + attention kernel; fused: qkvattn.hip (head dim 64) / gemm8.hip EPI_QKV_ATTN (head dim 80)
+struct HeadPlan {
+    bool fused = false;               // deconv2 + the final 1x1 conv in one kernel (EPI_DECONV_FINAL)
+    GemmPick deconv1, deconv2, final;  // final: unused when fused
+};
+struct ChunkPlan {
+    int n = 0;                        // crops the encoder runs (>= the chunk's: padding crops repeat the last one)
+    bool fold1 = false, fold2 = false;   // LayerNorm-1 / -2: attn.qkv / mlp.fc1 merge the partial statistics themselves (no ln_finalize launch)
+    int qkv_path = QKV_GEMM;
+    bool attn_qsplit = false;         // the attention kernel on three workgroups per (crop, head)
+    bool proj_fp8 = false;            // fp8 mode: attn.proj on the MXFP8 kernel too (the attention kernel writes MXFP8)
+    GemmPick gemm[VP_PROF_COUNT];     // the encoder GEMMs by family: PATCH, QKV, PROJ, FC1, FC2
+    HeadPlan head;                    // the head of the chunk's crops
+};
+// fin_rows = physical rows of the final conv's weights (final_rows); mix_bounds as in resolve_gemm
+ChunkPlan plan_chunk(const Switches& s, int D, int heads, int max_batch, bool fp8, int n_in, size_t fin_rows, const std::vector<int>* mix_bounds = nullptr);
+HeadPlan plan_head(const Switches& s, int D, int nh, size_t fin_rows);
 
-// ---- vitpose_api.hip: one GEMM of the path through the tile rules (also what the vp_dbg_gemm* taps launch)
-int gemm(vp_ctx* c, int fam, int epi, const uint16_t* A, const uint16_t* W, const float* bias, void* out,
+// ---- vitpose_api.hip: one GEMM of the path as `pk` resolved it (also what the vp_dbg_gemm* taps launch)
+int gemm(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint16_t* A, const uint16_t* W, const float* bias, void* out,
          const float* aux, int M, int N, int K, int ldo, int Hin = 0, int Win = 0, int Cin = 0, const LnFuse* ln = nullptr);
-int gemm_fp8(vp_ctx* c, int fam, int epi, const uint8_t* A8, const uint8_t* a_scales, const uint8_t* W8, const float* w_scale, const float* bias,
+int gemm_fp8(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint8_t* A8, const uint8_t* a_scales, const uint8_t* W8, const float* w_scale, const float* bias,
              void* out, uint8_t* out_scales, const float* aux, int M, int N, int K, const LnFuse* ln);
 
 }  // namespace vpi

@@ -29,9 +29,6 @@
 namespace vp {
 
 static constexpr int T = 192;
-#ifndef VP_ATTN_QSPLIT_DEFAULT
-#define VP_ATTN_QSPLIT_DEFAULT 128   // (crop, head) pairs: B x 1 0.521 -> 0.495 ms, L x 1 1.215 -> 1.152, B x 8 0.949 -> 0.906; neutral at 128 pairs, slower from 192 on
-#endif
 
 template <int HD> struct AttnCfg {
     static constexpr int HDP = (HD + 31) / 32 * 32;   // head dim padded to the MFMA k step
@@ -268,7 +265,7 @@ __global__ __launch_bounds__(256, QT == 3 ? 2 : 3) void attention_kernel(const u
 }
 
 template <class Ty, int HD>
-static hipError_t launch(const uint16_t* qkv, uint16_t* out, int B, int D, int heads, hipStream_t s, int blocked) {
+static hipError_t launch(const uint16_t* qkv, uint16_t* out, int B, int D, int heads, hipStream_t s, bool qsplit, int blocked) {
 #ifdef VP_TOOLS   // measurement build: VP_ATTN_QT=3 runs the three-query-tiles-at-a-time variant (fewest LDS reads, 2 blocks per CU: measured slower)
     static const int qt = [] { const char* e = getenv("VP_ATTN_QT"); return e ? atoi(e) : 1; }();
     auto kern = qt == 1 ? attention_kernel<Ty, HD, 1> : attention_kernel<Ty, HD, 3>;
@@ -277,11 +274,8 @@ static hipError_t launch(const uint16_t* qkv, uint16_t* out, int B, int D, int h
 #endif
     const float scale = 1.0f / sqrtf((float)HD);   // head_dim ** -0.5, vit.py:156
     if (blocked && HD != 64) return hipErrorInvalidValue;
-    // small batches: three workgroups per (crop, head), one query tile per wave (QS = 3) while that still leaves CUs idle otherwise -- VP_ATTN_QSPLIT = the largest
-    // number of (crop, head) pairs that takes it (0: never; profiles/small_batch_r6.txt)
-    const char* qs_env = getenv("VP_ATTN_QSPLIT");   // read per launch (a parity test flips it inside one process; the hipGraph of a chunk keeps what it captured)
-    const int qsplit_max = qs_env ? atoi(qs_env) : VP_ATTN_QSPLIT_DEFAULT;
-    if (B * heads <= qsplit_max) {
+    // small batches: three workgroups per (crop, head), one query tile per wave (QS = 3) while that still leaves CUs idle otherwise (profiles/small_batch_r6.txt)
+    if (qsplit) {
         hipLaunchKernelGGL((attention_kernel<Ty, HD, 1, false, 3>), dim3(B * heads * 3), dim3(256), AttnCfg<HD>::LDS, s, qkv, out, D, heads,
                            scale * 1.4426950408889634f, blocked, (uint8_t*)nullptr);
         return hipGetLastError();
@@ -291,7 +285,7 @@ static hipError_t launch(const uint16_t* qkv, uint16_t* out, int B, int D, int h
     return hipGetLastError();
 }
 
-hipError_t attention_launch(int dtype, const uint16_t* qkv, uint16_t* out, int B, int D, int heads, hipStream_t s, int qkv_blocked, uint8_t* mx_scales) {
+hipError_t attention_launch(int dtype, const uint16_t* qkv, uint16_t* out, int B, int D, int heads, hipStream_t s, bool qsplit, int qkv_blocked, uint8_t* mx_scales) {
     const int hd = D / heads;
     if (hd * heads != D) return hipErrorInvalidValue;
     if (mx_scales) {   // fp8 mode: MXFP8 output (head dim 64, fp16 operands)
@@ -302,7 +296,7 @@ hipError_t attention_launch(int dtype, const uint16_t* qkv, uint16_t* out, int B
     }
 #define VP_ATT(HD)                                                                           \
     if (hd == HD)                                                                            \
-        return dtype == DT_F16 ? launch<F16, HD>(qkv, out, B, D, heads, s, qkv_blocked) : launch<BF16, HD>(qkv, out, B, D, heads, s, qkv_blocked);
+        return dtype == DT_F16 ? launch<F16, HD>(qkv, out, B, D, heads, s, qsplit, qkv_blocked) : launch<BF16, HD>(qkv, out, B, D, heads, s, qsplit, qkv_blocked);
     VP_ATT(32) VP_ATT(64) VP_ATT(80)
 #undef VP_ATT
     return hipErrorInvalidValue;

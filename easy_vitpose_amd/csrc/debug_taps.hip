@@ -18,7 +18,7 @@ vp_ctx* dbg_ctx(int device, int dtype) {
     vp_ctx* c = new vp_ctx();
     c->cfg.device_id = device;
     c->dtype = dtype == VP_DTYPE_F16 ? vp::DT_F16 : vp::DT_BF16;
-    apply_gemm_tuning(c);
+    apply_gemm_tuning(c->sw);
     return c;
 }
 int dbg_finish(vp_ctx* c, int rc) {
@@ -70,7 +70,7 @@ VP_API int vp_dbg_gemm(int32_t device, int32_t dtype, int32_t epi, int32_t M, in
         if ((rc = dalloc(c, &dO32, MN))) return dbg_finish(c, rc);
     } else if ((rc = dalloc(c, &dO16, MN))) return dbg_finish(c, rc);
     if ((rc = dalloc(c, &c->zero, (size_t)256))) return dbg_finish(c, rc);
-    rc = gemm(c, 0, epi, dA, dW, dB, epi >= 2 ? (void*)dO32 : (void*)dO16, dAux, M, N, K, N);
+    rc = gemm(c, 0, epi, resolve_gemm(c->sw, 0, epi, M, N, K), dA, dW, dB, epi >= 2 ? (void*)dO32 : (void*)dO16, dAux, M, N, K, N);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(c, VP_ERR_HIP, "gemm kernel failed");
     if (!rc) {
         if (epi >= 2) { if (hipMemcpy(out, dO32, MN * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(c, VP_ERR_HIP, "D2H"); }
@@ -88,7 +88,8 @@ VP_API int vp_dbg_attention(int32_t device, int32_t dtype, int32_t B, int32_t D,
     const size_t M = (size_t)B * 192;
     if ((rc = upload_mat(c, &dq, qkv, M, 3 * (size_t)D, M))) return dbg_finish(c, rc);
     if ((rc = dalloc(c, &dout, M * D))) return dbg_finish(c, rc);
-    hipError_t e = vp::attention_launch(c->dtype, dq, dout, B, D, heads, nullptr);
+    const char* qs = getenv("VP_ATTN_QSPLIT");   // read per call (a parity test flips it inside one process); handles read it once, at vp_create
+    hipError_t e = vp::attention_launch(c->dtype, dq, dout, B, D, heads, nullptr, (long)B * heads <= (qs ? atol(qs) : Switches{}.attn_qsplit));
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, std::string("attention: ") + hipGetErrorString(e)));
     return dbg_finish(c, download16(c, dout, out, M * D));
@@ -216,7 +217,7 @@ VP_API int vp_dbg_deconv(int32_t device, int32_t dtype, int32_t B, int32_t Hin, 
     if ((rc = dalloc(c, &dout, Min * 4 * 256))) return dbg_finish(c, rc);
     if ((rc = dalloc(c, &c->zero, (size_t)256))) return dbg_finish(c, rc);
     if (hipMemset(c->zero, 0, 512) != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, "memset"));
-    rc = gemm(c, 0, vp::EPI_DECONV, dx, dw, db, dout, nullptr, (int)Min, 256, 4 * Cin, 256, Hin, Win, Cin);
+    rc = gemm(c, 0, vp::EPI_DECONV, resolve_gemm(c->sw, 0, vp::EPI_DECONV, (int)Min, 256, 4 * Cin), dx, dw, db, dout, nullptr, (int)Min, 256, 4 * Cin, 256, Hin, Win, Cin);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(c, VP_ERR_HIP, "deconv kernel failed");
     if (!rc) rc = download16(c, dout, out, Min * 4 * 256);
     return dbg_finish(c, rc);
@@ -280,17 +281,18 @@ VP_API int vp_dbg_gemm_bench(int32_t device, int32_t dtype, int32_t epi, int32_t
     hipMemset(dB, 0, wrows * 4);
     if (dO32) hipMemset(dO32, 0, MN * 4);
     if (dAux) hipMemset(dAux, 0, (size_t)192 * N * 4);
-    c->gemm_variant[0] = variant & 0xff;
-    c->gemm_group_m[0] = group_m;
+    c->sw.gemm_variant[0] = variant & 0xff;
+    c->sw.gemm_group_m[0] = group_m;
     c->gemm_ablate = variant >> 8;   // tools only: ablation flags in the high bits
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     void* outp = epi >= 2 ? (void*)dO32 : (void*)dO16;
     const float* aux = epi == 2 ? dO32 : dAux;
-    for (int i = 0; i < 2 && !rc; ++i) rc = gemm(c, 0, epi, dA, dW, dB, outp, aux, M, N, K, N);
+    const GemmPick pk = resolve_gemm(c->sw, 0, epi, M, N, K);
+    for (int i = 0; i < 2 && !rc; ++i) rc = gemm(c, 0, epi, pk, dA, dW, dB, outp, aux, M, N, K, N);
     hipDeviceSynchronize();
     hipEventRecord(e0, nullptr);
-    for (int i = 0; i < iters && !rc; ++i) rc = gemm(c, 0, epi, dA, dW, dB, outp, aux, M, N, K, N);
+    for (int i = 0; i < iters && !rc; ++i) rc = gemm(c, 0, epi, pk, dA, dW, dB, outp, aux, M, N, K, N);
     hipEventRecord(e1, nullptr);
     if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(c, VP_ERR_HIP, "gemm bench kernel failed");
     float ms = 0.f;
@@ -719,8 +721,8 @@ VP_API int vp_dbg_gemm_fp8_case(int32_t device, int32_t epi, int32_t M, int32_t 
         if (hipMemcpy(dAux16, hp.data(), hp.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, "H2D"));
         ln.plane = MN; ln.stats_out = dStats;
     }
-    r = gemm_fp8(c, epi == 0 ? VP_PROF_GEMM_QKV : epi == 1 ? VP_PROF_GEMM_FC1 : VP_PROF_GEMM_FC2, epi, dA8, dAs, dW8, dWs, dB, dOut, dOs,
-                 (const float*)dAux16, M, N, K, &ln);
+    const int fam = epi == 0 ? VP_PROF_GEMM_QKV : epi == 1 ? VP_PROF_GEMM_FC1 : VP_PROF_GEMM_FC2;
+    r = gemm_fp8(c, fam, epi, resolve_gemm_fp8(fam, epi, M, N), dA8, dAs, dW8, dWs, dB, dOut, dOs, (const float*)dAux16, M, N, K, &ln);
     if (!r && hipDeviceSynchronize() != hipSuccess) r = fail(c, VP_ERR_HIP, "fp8 gemm kernel failed");
     if (r) return dbg_finish(c, r);
     // what the operands stand for

@@ -840,20 +840,26 @@ static hipError_t launch8(const GemmArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-bool gemm8_supported(int epi, const GemmArgs& a, int bn, int bm) {
+bool gemm8_shape_ok(int epi, int M, int N, int K, int ldo, int w_rows, int bn, int bm) {
     if (epi == EPI_QKV_ATTN)   // one crop x one head (head dim 80) per 192 x 256 tile: M = crops * 192, N = heads * 256 (head-major weights), y [M, K]
-        return bn == 256 && bm == 192 && a.M % 192 == 0 && a.N % 256 == 0 && (a.N >> 8) * 80 == a.K && a.K % 128 == 0 && a.K >= 256 && a.ldo == a.K &&
-               (size_t)a.M * a.K * 2 < (1ull << 32) && (size_t)a.w_rows * a.K * 2 < (1ull << 32) && (a.M / 192) * (a.N / 256) >= 8 && a.rowstat && a.ln_s &&
-               !a.a_blocked && !a.out_blocked && !a.reverse;
+        return bn == 256 && bm == 192 && M % 192 == 0 && N % 256 == 0 && (N >> 8) * 80 == K && K % 128 == 0 && K >= 256 && ldo == K &&
+               (size_t)M * K * 2 < (1ull << 32) && (size_t)w_rows * K * 2 < (1ull << 32) && (M / 192) * (N / 256) >= 8;
     if (epi != EPI_BIAS && epi != EPI_BIAS_GELU && epi != EPI_BIAS_RESID_LN) return false;
     if (bn != 256 && bn != 192) return false;
     if (bm != 256 && !(bm == 192 && bn == 256)) return false;   // 192-row tiles: 256 columns wide
-    if (a.M % bm || a.N % bn || a.K % 128 || a.K < 256) return false;
-    if ((size_t)a.M * a.K * 2 >= (1ull << 32) || (size_t)a.w_rows * a.K * 2 >= (1ull << 32)) return false;   // 32-bit per-lane offsets
-    if ((a.M / bm) * (a.N / bn) < 8) return false;
-    if (epi == EPI_BIAS_RESID_LN) return a.ldo == a.N && a.plane && a.stats_out && !a.out_blocked;
-    if ((size_t)a.M * a.N >= (1ull << 31)) return false;
-    return bn == 256 && a.ldo == a.N;   // wide 16-bit-output GEMMs: 256 x 256 tiles only
+    if (M % bm || N % bn || K % 128 || K < 256) return false;
+    if ((size_t)M * K * 2 >= (1ull << 32) || (size_t)w_rows * K * 2 >= (1ull << 32)) return false;   // 32-bit per-lane offsets
+    if ((M / bm) * (N / bn) < 8) return false;
+    if (epi == EPI_BIAS_RESID_LN) return ldo == N;
+    if ((size_t)M * N >= (1ull << 31)) return false;
+    return bn == 256 && ldo == N;   // wide 16-bit-output GEMMs: 256 x 256 tiles only
+}
+
+bool gemm8_supported(int epi, const GemmArgs& a, int bn, int bm) {
+    if (!gemm8_shape_ok(epi, a.M, a.N, a.K, a.ldo, a.w_rows, bn, bm)) return false;
+    if (epi == EPI_QKV_ATTN) return a.rowstat && a.ln_s && !a.a_blocked && !a.out_blocked && !a.reverse;
+    if (epi == EPI_BIAS_RESID_LN) return a.plane && a.stats_out && !a.out_blocked;
+    return true;
 }
 
 hipError_t gemm8_launch(int dtype, int epi, const GemmArgs& a, int bn, hipStream_t s, int bm) {

@@ -111,6 +111,8 @@ hipError_t gemm_launch(int dtype, int epi, const GemmArgs& a, hipStream_t s);
 // 8-phase persistent kernel (gemm8.hip): 256 x bn tiles (bn = 256 or 192), EPI_BIAS / EPI_BIAS_GELU / EPI_BIAS_RESID_LN.
 // Selected through GemmArgs::variant 16 (bn 256) / 17 (bn 192) in gemm_launch.
 bool gemm8_supported(int epi, const GemmArgs& a, int bn, int bm = 256);
+// the part of gemm8_supported that depends on the shape alone (w_rows = the weight rows behind W): what the selection rule (tile_rules.hip) asks before it picks the kernel
+bool gemm8_shape_ok(int epi, int M, int N, int K, int ldo, int w_rows, int bn, int bm);
 hipError_t gemm8_launch(int dtype, int epi, const GemmArgs& a, int bn, hipStream_t s, int bm = 256);
 // name of the kernel a launch resolves to, as the profiler prints it minus the namespace; written by the launch code when
 // GemmArgs::desc != nullptr (vp_profile_kernel)
@@ -157,8 +159,9 @@ hipError_t hwid_probe_launch(uint32_t* d_out, int blocks, int threads, int lds_b
 // qkv [B*192, 3*D] 16-bit (columns = [q | k | v] x heads x head_dim, vit.py:166-167)
 // out [B*192, D]   16-bit (columns = heads x head_dim, vit.py:176)
 // qkv_blocked (head dim 64 only): qkv in the 64 x 64-blocked layout the GEMMs write with GemmArgs::out_blocked
-// mx_scales != nullptr (fp8 mode, head dim 64): the output is written as MXFP8 (codes at `out`, 64 x 128-blocked; E8M0 scales at mx_scales)
-hipError_t attention_launch(int dtype, const uint16_t* qkv, uint16_t* out, int B, int D, int heads, hipStream_t s, int qkv_blocked = 0,
+// qsplit: three workgroups per (crop, head), one query tile per wave (small batches; the chunk plan decides, tile_rules.hip)
+// mx_scales != nullptr (fp8 mode, head dim 64): the output is written as MXFP8 (codes at `out`, 64 x 128-blocked; E8M0 scales at mx_scales; no query split)
+hipError_t attention_launch(int dtype, const uint16_t* qkv, uint16_t* out, int B, int D, int heads, hipStream_t s, bool qsplit, int qkv_blocked = 0,
                             uint8_t* mx_scales = nullptr);
 
 // attn.qkv + attention core in one kernel (qkvattn.hip; head dim 64): tile = (pair of crops, head); the qkv tensor never reaches HBM.

@@ -1,10 +1,15 @@
-// Tile rules: which kernel configuration runs one GEMM of the path -- pure host functions of the shape (no device, no handle), walked over
-// every batch size of every model by tests/test_host_logic.py through the host-only taps at the end of this file.
+// Tile rules: which kernel runs each GEMM of a chunk -- pure host functions of the switches and the shape (no device, no handle).  The single rules
+// (pick_*) feed one resolver per GEMM (resolve_gemm) and one plan per chunk (plan_chunk), which the orchestration (vitpose_api.hip) only executes.
+// tests/test_host_logic.py walks the rules and the plan over every batch size of every model through the host-only taps at the end of this file.
 #include "api_internal.h"
 
 using namespace vpi;
 
 namespace vpi {
+
+struct G8Pick { int variant, bm, bn; long tiles; };
+struct Tile2Pick { int variant, group_m; };
+struct SplitKPick { int S, variant; };   // split-K of a residual GEMM: S k ranges on tile configuration `variant` (S = 1: no split)
 
 // Tile of the 8-phase kernel for an [M, N] output (wide = 16-bit output, else residual epilogue); variant 0 = the 2-phase kernels run it.
 // A pure function of the shape: tests/test_host_logic.py walks it over every batch size through the host-only tap vp_dbg_gemm8_pick.
@@ -161,16 +166,17 @@ static bool tile2_dims(int variant, int& bm, int& bn, int& slots) {
     return false;
 }
 
-// Rounds x tile area x K of one MLP GEMM at M rows under the rules above: the persistent 8-phase kernel runs ceil(tiles / 256) full rounds (its 192-row tile priced x 1.08 as in
+// Rounds x tile area x K of one MLP GEMM on the tile resolve_gemm picked: the persistent 8-phase kernel runs ceil(tiles / 256) full rounds (its 192-row tile priced x 1.08 as in
 // pick_gemm8_tile); a 2-phase launch ceil(tiles / resident slots) rounds, priced x 1.15 (measured: the 2-phase 256 x 256 tile 33 us against 30 for the same one-round launch on
 // the 8-phase kernel, the default tile 110 against 80-90).
-static double mlp_gemm_cost(int epi, int M, int N, int K, bool wide, int bm192_mask, bool extended, bool gemm8) {
-    if (gemm8) {
-        const G8Pick pk = pick_gemm8_tile(M, N, wide, bm192_mask, 448, extended);
-        if (pk.variant) return (double)((pk.tiles + 255) / 256) * pk.bm * pk.bn * (pk.bm == 192 ? 1.08 : 1.0) * K;
-    }
+static double mlp_gemm_cost(const GemmPick& pk, int M, int N, int K) {
     int bm = 192, bn = 128, slots = 512;
-    if (!tile2_dims(pick_gemm2_tile(epi, M, N, K).variant, bm, bn, slots)) return 0.0;
+    if (pk.variant >= 16 && pk.variant <= 18) {
+        bm = pk.variant == 18 ? 192 : 256;
+        bn = pk.variant == 17 ? 192 : 256;
+        return (double)(((long)(M / bm) * (N / bn) + 255) / 256) * bm * bn * (bm == 192 ? 1.08 : 1.0) * K;
+    }
+    if (!tile2_dims(pk.variant, bm, bn, slots)) return 0.0;
     const long t = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn);
     return (double)((t + slots - 1) / slots) * bm * bn * (slots / 256) * 1.15 * K;
 }
@@ -181,12 +187,13 @@ static double mlp_gemm_cost(int epi, int M, int N, int K, bool wide, int bm192_m
 // or crop by crop, so the real crops' results are bit for bit those of the unpadded run: test_padded_encoder_batch_is_bit_identical) whenever the cost above of mlp.fc1 + mlp.fc2
 // drops by more than 5 % -- checked against the measured step times of every batch size in calls 17-20: 108 of the 112 padded sizes gain (2-9 %), 4 lose 1.0-4.2 %.  The head
 // and the decode run the real crops only.  A pure function of (n, D): tests/test_host_logic.py walks it through vp_dbg_run_batch.
-int pick_run_batch(int n, int D, int limit, int bm192_mask, bool extended, int gemm8_mask) {
+static int pick_run_batch(const Switches& s, int n, int D, int limit) {
     const int n4 = (n + 3) / 4 * 4;
     if (n < 33 || n4 == n || n4 > limit) return n;
     auto cost = [&](int m) {
-        return mlp_gemm_cost(vp::EPI_BIAS_GELU, 192 * m, 4 * D, D, true, bm192_mask, extended, (gemm8_mask & 2) != 0) +
-               mlp_gemm_cost(vp::EPI_BIAS_RESID_LN, 192 * m, D, 4 * D, false, bm192_mask, extended, (gemm8_mask & 1) != 0);
+        const int M = 192 * m;
+        return mlp_gemm_cost(resolve_gemm(s, VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, M, 4 * D, D), M, 4 * D, D) +
+               mlp_gemm_cost(resolve_gemm(s, VP_PROF_GEMM_FC2, vp::EPI_BIAS_RESID_LN, M, D, 4 * D), M, D, 4 * D);
     };
     const double c0 = cost(n), c1 = cost(n4);
     return (c0 > 0.0 && c1 > 0.0 && c1 < 0.95 * c0) ? n4 : n;
@@ -218,6 +225,157 @@ int expert_fallback_variant(int M, int N, bool gemm8_ok, int* group_m) {
     return 11;
 }
 
+static bool is_gemm8(int variant) { return variant >= 16 && variant <= 18; }
+static int gemm8_group_m(int fam) { return fam == VP_PROF_GEMM_QKV ? 4 : fam == VP_PROF_GEMM_FC2 ? 2 : 8; }   // measured sweep 0 / 2 / 4 / 8 / 16 / 32 (spread 2-3 %)
+
+// The complete choice for one GEMM, in the order the rules override each other: the tuned configuration (tools) or the 2-phase rule; the persistent variant of the
+// default wide tile; the 8-phase kernel at large batches; the fused deconv2 + final conv tile; a LayerNorm consumer that folds the statistics itself; a mixed-expert
+// batch's crop-aligned fc2 tile; split-K of a residual GEMM of a small batch.
+GemmPick resolve_gemm(const Switches& s, int fam, int epi, int M, int N, int K, bool ln_part, size_t splitk_rows, const std::vector<int>* mix_bounds) {
+    GemmPick p;
+    const bool tuned = s.gemm_variant[fam] >= 0;
+    const bool wide = epi == vp::EPI_BIAS || epi == vp::EPI_BIAS_GELU;
+    const int w_rows = (int)pad128((size_t)N);
+    if (tuned) {
+        p.variant = s.gemm_variant[fam]; p.group_m = s.gemm_group_m[fam];
+    } else {
+        const Tile2Pick tp = pick_gemm2_tile(epi, M, N, K);   // the 2-phase kernels' tile (the 8-phase kernel may take the GEMM over below)
+        p.variant = tp.variant; p.group_m = tp.group_m;
+    }
+    if (s.persist_gemm && p.variant == 8 && wide && K % 128 == 0 && M % 192 == 0 && N % 128 == 0 && (long)(M / 192) * (N / 128) >= 1024)   // >= 2 tiles per resident workgroup
+        p.persist = 1;
+    // large batches: the 8-phase persistent kernel (gemm8.hip), one 512-thread workgroup per CU on the tile pick_gemm8_tile picks, where the kernel takes the shape
+    // (attn.proj, K = N = D, is HBM-bound and stays on the 192 x 128 tile with two workgroups per CU: measured 105 vs 112 us; bit 3 of VP_GEMM8 moves it too)
+    const int g8bit = fam == VP_PROF_GEMM_FC2 ? 1 : fam == VP_PROF_GEMM_FC1 ? 2 : fam == VP_PROF_GEMM_QKV ? 4 : fam == VP_PROF_GEMM_PROJ ? 8 : 0;
+    if (!tuned && (s.gemm8_mask & g8bit) && (wide || epi == vp::EPI_BIAS_RESID_LN)) {
+        const G8Pick pk = pick_gemm8_tile(M, N, wide, s.g8_bm192, s.g8_min_tiles, s.g8_cost_model);
+        if (pk.variant && vp::gemm8_shape_ok(epi, M, N, K, N, w_rows, pk.bn, pk.bm)) {
+            p.variant = pk.variant; p.group_m = gemm8_group_m(fam); p.persist = 0; p.stagger = s.g8_stagger;
+        }
+    }
+    if (epi == vp::EPI_DECONV_FINAL) { p.variant = 3; p.group_m = 0; p.persist = 0; }   // deconv2 + final 1x1 conv: the 256 x 256 tile (all channels of a pixel)
+    if (ln_part) {   // only the one-tile-per-workgroup 2-phase kernel folds partial statistics itself
+        p.persist = 0;
+        if (is_gemm8(p.variant)) { p.variant = 8; p.group_m = 8; }
+    }
+    const bool mixed = mix_bounds && fam == VP_PROF_GEMM_FC2;   // ViTPose+ mixed batch: every crop's m-tiles read its own expert's fc2
+    if (mixed && !expert_tile_ok(tile_bm(p.variant), *mix_bounds)) {   // a tile would span two experts: the crop-aligned tile instead
+        const bool g8 = (s.gemm8_mask & 1) && vp::gemm8_shape_ok(epi, M, N, K, N, w_rows, 256, 192);
+        p.variant = expert_fallback_variant(M, N, g8, &p.group_m);
+        p.persist = 0;
+        p.stagger = p.variant == 18 ? s.g8_stagger : 0;
+    }
+    // small batches: a residual GEMM as S partial products over k ranges + a fixed-order reduction (pick_splitk); the path's residual GEMMs update x in place
+    if (epi == vp::EPI_BIAS_RESID_LN && !mixed && splitk_rows && (size_t)M <= splitk_rows && !tuned && !is_gemm8(p.variant) &&
+        (fam == VP_PROF_GEMM_FC2 || fam == VP_PROF_GEMM_PROJ)) {
+        const int which = fam == VP_PROF_GEMM_FC2 ? 1 : 0;
+        SplitKPick sk = pick_splitk(M, N, K);
+        if (s.splitk_force[which][0] > 0) sk = {s.splitk_force[which][0], s.splitk_force[which][1]};
+        if (sk.S > 1 && sk.S <= SPLITK_MAX_S && K % (sk.S * 128) == 0) { p.splitk = sk.S; p.splitk_variant = sk.variant; }
+    }
+    return p;
+}
+
+// fp8 mode: tile width 256 for the wide GEMMs; the residual GEMM takes the width whose tile count fills the rounds of 256 persistent workgroups best
+GemmPick resolve_gemm_fp8(int fam, int epi, int Mp, int N) {
+    int bn = 256;
+    if (epi == vp::EPI_BIAS_RESID_LN) {
+        double fill = -1.0;
+        for (int cand : {256, 192}) {
+            if (N % cand) continue;
+            const long t = (long)(Mp / 256) * (N / cand);
+            if (t < 8) continue;
+            const double f = (double)t / (double)((t + 255) / 256 * 256);
+            if (f > fill + 1e-9) { bn = cand; fill = f; }
+        }
+    }
+    GemmPick p;
+    p.variant = bn == 192 ? 17 : 16;
+    p.group_m = gemm8_group_m(fam);
+    return p;
+}
+
+// The head of nh crops: large batches run the final 1x1 conv in deconv2's epilogue (gemm.hip EPI_DECONV_FINAL, bit-identical heatmaps) and the [n,64,48,256] tensor is
+// never written; small batches keep the two launches on tiles that still fill 256 CUs
+HeadPlan plan_head(const Switches& s, int D, int nh, size_t fin_rows) {
+    HeadPlan h;
+    h.fused = s.fuse_head && s.gemm_variant[VP_PROF_GEMM_DECONV] < 0 && (long)nh * 12 >= 512;
+    h.deconv1 = resolve_gemm(s, VP_PROF_GEMM_DECONV, vp::EPI_DECONV, nh * 192, 256, 4 * D);
+    h.deconv2 = resolve_gemm(s, VP_PROF_GEMM_DECONV, h.fused ? vp::EPI_DECONV_FINAL : vp::EPI_DECONV, nh * 768, 256, 1024);
+    if (!h.fused) h.final = resolve_gemm(s, VP_PROF_GEMM_FINAL, vp::EPI_HEATMAP, nh * 3072, (int)fin_rows, 256);
+    return h;
+}
+
+ChunkPlan plan_chunk(const Switches& s, int D, int heads, int max_batch, bool fp8, int n_in, size_t fin_rows, const std::vector<int>* mix_bounds) {
+    ChunkPlan p;
+    // the ENCODER's batch: n_in crops, or the next multiple of 4 where that buys the MLP GEMMs an 8-phase tile (pick_run_batch; rows n_in .. n - 1 repeat the last crop and
+    // are never read by the head); the fp8 mode pads its rows itself
+    p.n = (s.pad_batch && s.fuse_ln && !fp8) ? pick_run_batch(s, n_in, D, (max_batch + 3) / 4 * 4) : n_in;
+    const int n = p.n, M = 192 * n, hd = D / heads;
+    const size_t splitk_rows = (s.fuse_ln && !fp8 && s.splitk_on) ? (size_t)std::min(max_batch, SPLITK_MAX_CROPS) * 192 : 0;   // vp_create's workspace
+    auto gemm = [&](int fam, int epi, int N, int K, bool ln_part) { return resolve_gemm(s, fam, epi, M, N, K, ln_part, splitk_rows, mix_bounds); };
+    p.attn_qsplit = (long)n * heads <= s.attn_qsplit;
+    p.head = plan_head(s, D, n_in, fin_rows);
+    const int resid = s.fuse_ln ? vp::EPI_BIAS_RESID_LN : vp::EPI_BIAS_RESID;   // without the fused LayerNorm: standalone passes, fp32 residual stream
+    p.gemm[VP_PROF_GEMM_PATCH] = gemm(VP_PROF_GEMM_PATCH, s.fuse_ln ? vp::EPI_POS_LN : vp::EPI_POS, D, 768, false);
+    p.gemm[VP_PROF_GEMM_PROJ] = gemm(VP_PROF_GEMM_PROJ, resid, D, D, false);
+    if (fp8) {   // qkv / fc1 / fc2 (and attn.proj at head dim 64) on MXFP8 operands, token rows padded to a multiple of 256 (>= 512)
+        const int Mp = std::max((M + 255) / 256 * 256, 512);
+        p.proj_fp8 = hd == 64 && !s.fp8_proj16;
+        p.gemm[VP_PROF_GEMM_QKV] = resolve_gemm_fp8(VP_PROF_GEMM_QKV, vp::EPI_BIAS, Mp, 3 * D);
+        if (p.proj_fp8) p.gemm[VP_PROF_GEMM_PROJ] = resolve_gemm_fp8(VP_PROF_GEMM_PROJ, vp::EPI_BIAS_RESID_LN, Mp, D);
+        p.gemm[VP_PROF_GEMM_FC1] = resolve_gemm_fp8(VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, Mp, 4 * D);
+        p.gemm[VP_PROF_GEMM_FC2] = resolve_gemm_fp8(VP_PROF_GEMM_FC2, vp::EPI_BIAS_RESID_LN, Mp, D);
+        return p;
+    }
+    p.gemm[VP_PROF_GEMM_FC2] = gemm(VP_PROF_GEMM_FC2, resid, D, 4 * D, false);
+    if (!s.fuse_ln) {
+        p.gemm[VP_PROF_GEMM_QKV] = gemm(VP_PROF_GEMM_QKV, vp::EPI_BIAS, 3 * D, D, false);
+        p.gemm[VP_PROF_GEMM_FC1] = gemm(VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, 4 * D, D, false);
+        return p;
+    }
+    // Small batches: the consumers fold the partial statistics themselves (same code, same bits) -- 2 x depth launches less
+    // (round 6: with the consumers' merge on a register copy of the row's statistics instead of a bank-conflicted LDS image -- gemm.hip, GemmArgs::ln_part -- the fold wins at
+    // every model and batch up to 8 crops, the one-round 192 x 128 tiles of ViTPose-L included: 8 crops 2.200 -> 2.143 ms against the ln_finalize launches, 4 crops 1.874 ->
+    // 1.800, 1 crop 1.172 -> 1.111; beyond 8 crops it still loses (every column tile merges its rows again; ViTPose-H's fused qkv + attention tile needs rowstat):
+    // profiles/small_batch_r6.txt call 11)
+    const bool fold_stats = n <= s.graph_max_n_stats;
+    // Round 6 (profiles/small_batch_r6.txt call 25): beyond 8 crops the fold did not lose because of the merge but because the (mean, rstd) area behind the ring pushes the
+    // 80 KiB ring of the default 192 x 128 tile over half the CU's LDS -- ONE workgroup per CU instead of two (+9 ... +12 % per step).  Per consumer (attn.qkv reads LayerNorm-1,
+    // mlp.fc1 LayerNorm-2): fold where its GEMM runs on a 2-phase tile that keeps its occupancy with the area (every configuration but the 80 KiB-ring ones), i.e. not on the
+    // 8-phase kernel, not in a fused qkv + attention kernel (they read rowstat): ViTPose-S 9-28 crops -6.5 ... -8 %, -B 9-14 -2 ... -6 %, -L 9-10 -2.3 %; same code, same bits.
+    auto folds = [&](int fam, int epi, int N) {
+        if (fold_stats) return true;
+        if (!s.fold_rule || n > 64 || s.gemm_variant[fam] >= 0) return false;
+        const int v = gemm(fam, epi, N, D, false).variant;
+        return v != 8 && v != 11 && !is_gemm8(v);
+    };
+    // attn.qkv + attention core as ONE kernel per (pair of crops, head) from 108 tiles on (qkvattn.hip; bit-identical y; an odd batch's last crop fills both halves of its pair)
+    // 128 - 1536 tiles: profiles/qkvattn_r4.txt.  Below (round 6, profiles/small_batch_r6.txt call 16): 108-120 tiles win or tie (ViTPose-B 17-20 crops -0.6 ... -6.5 %: at 19-20
+    // crops the unfused qkv is 540 tiles of 128 x 128 on 512 slots; ViTPose-L 13-14 crops equal); 96 tiles and fewer lose (-B 16 crops +-0, 12 crops +3 %, -L 9-12 crops +2 ... +7 %)
+    //   Call 26: with the per-consumer statistics fold the two-launch path saves its LayerNorm-1 ln_finalize launches wherever the qkv GEMM's tile folds, and wins back
+    //   108-127 tiles there (ViTPose-B 17-18 crops -1.8 / -2.2 %, -L 13-14 crops -2.9 / -3.4 %); where that GEMM would run on the default tile (-B 19-20) the fused kernel keeps them.
+    // Head dim 80: one crop x one head per 192 x 256 tile of the 8-phase kernel (gemm8.hip EPI_QKV_ATTN; bit-identical y), from qa80_min_tiles tiles on.
+    // The head-major weights both read exist where weights.hip made them (fused LayerNorm, VP_FUSE_QKV_ATTN).
+    const bool has_qkvh = s.fuse_qkv_attn && (hd == 64 || (heads * 80 == D && D % 128 == 0));
+    const bool qkv_can_fold = folds(VP_PROF_GEMM_QKV, vp::EPI_BIAS, 3 * D);
+    const long pair_tiles = (long)((n + 1) / 2) * heads;
+    const bool want80 = has_qkvh && heads * 80 == D && (long)n * heads >= s.qa80_min_tiles;
+    const bool want64 = has_qkvh && heads * 64 == D && pair_tiles >= s.qa_min_tiles && (s.qa_min_set || pair_tiles >= 128 || !qkv_can_fold);
+    p.fold1 = fold_stats || (!want80 && !want64 && qkv_can_fold);   // LayerNorm-1 -> attn.qkv
+    p.fold2 = folds(VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, 4 * D);     // LayerNorm-2 -> mlp.fc1
+    // (a shape the fused kernels reject -- a chunk beyond their 32-bit row offsets, fewer than 8 tiles under a lowered threshold -- takes the gemm + attention pair)
+    vp::QkvAttnArgs qa{};
+    qa.npairs = (n + 1) / 2; qa.ncrops = n; qa.heads = heads; qa.D = D;
+    if (s.gemm_variant[VP_PROF_GEMM_QKV] < 0 && !p.fold1) {
+        if (want80 && vp::gemm8_shape_ok(vp::EPI_QKV_ATTN, M, heads * 256, D, D, heads * 256, 256, 192)) p.qkv_path = QKV_ATTN80;
+        else if (want64 && vp::qkvattn_supported(qa)) p.qkv_path = QKV_ATTN64;
+    }
+    p.gemm[VP_PROF_GEMM_QKV] = gemm(VP_PROF_GEMM_QKV, vp::EPI_BIAS, 3 * D, D, p.fold1);
+    p.gemm[VP_PROF_GEMM_FC1] = gemm(VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, 4 * D, D, p.fold2);
+    return p;
+}
+
 }  // namespace vpi
 
 extern "C" {
@@ -235,7 +393,23 @@ VP_API int vp_dbg_expert_tile(int32_t variant, int32_t M, int32_t N, int32_t gem
 // HOST ONLY: the batch the encoder runs for a chunk of n crops of a model of embed dim D (pick_run_batch with the default switches; limit = the handle's padded workspace batch)
 VP_API int vp_dbg_run_batch(int32_t n, int32_t D, int32_t limit) {
     if (n <= 0 || D <= 0) return VP_ERR_INVALID;
-    return pick_run_batch(n, D, limit, 3, true, 0x7);
+    return pick_run_batch(Switches{}, n, D, limit);
+}
+
+// HOST ONLY: the plan of a chunk of n crops on a handle of *cfg, with the switches vp_create would read from the environment now; layout: include/vitpose_hip.h
+VP_API int vp_dbg_chunk_plan(const vp_config* cfg, int32_t n, int32_t* out, int32_t cap) {
+    if (!cfg || cfg->embed_dim <= 0 || cfg->num_heads <= 0 || cfg->embed_dim % cfg->num_heads || cfg->num_keypoints <= 0 || cfg->max_batch <= 0 ||
+        n <= 0 || n > cfg->max_batch || cap < 0 || (cap > 0 && !out))
+        return VP_ERR_INVALID;
+    Switches s;
+    read_switches(s);
+    const ChunkPlan p = plan_chunk(s, cfg->embed_dim, cfg->num_heads, cfg->max_batch, cfg->dtype == VP_DTYPE_FP8, n, final_rows((size_t)cfg->num_keypoints));
+    std::vector<int32_t> v = {p.n, p.fold1, p.fold2, p.qkv_path, p.attn_qsplit, p.head.fused, p.proj_fp8};
+    for (const GemmPick& g : {p.gemm[VP_PROF_GEMM_PATCH], p.gemm[VP_PROF_GEMM_QKV], p.gemm[VP_PROF_GEMM_PROJ], p.gemm[VP_PROF_GEMM_FC1], p.gemm[VP_PROF_GEMM_FC2],
+                              p.head.deconv1, p.head.deconv2, p.head.final})
+        v.insert(v.end(), {g.variant, g.group_m, g.persist, g.stagger, g.splitk, g.splitk_variant});
+    std::copy(v.begin(), v.begin() + std::min<size_t>(v.size(), (size_t)cap), out);
+    return (int)v.size();
 }
 
 

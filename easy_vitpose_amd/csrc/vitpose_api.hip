@@ -5,10 +5,6 @@
 
 using namespace vpi;
 
-#ifndef VP_GRAPH_NULL_DEFAULT
-#define VP_GRAPH_NULL_DEFAULT 1
-#endif
-
 namespace vpi {
 
 thread_local std::string g_create_error;
@@ -51,14 +47,14 @@ void prof_collect(vp_ctx* c) {
 
 // Tile configuration per GEMM family.  Defaults = best measured on MI355X (profiles/);
 // experiments override with VP_GEMM_TUNE="fam:variant:group_m,..." (fam = VP_PROF_* index).
-void apply_gemm_tuning(vp_ctx* c) {
+void apply_gemm_tuning(Switches& s) {
 #ifndef VP_TOOLS
-    (void)c;
+    (void)s;
 #else
     if (const char* t = getenv("VP_GEMM_TUNE")) {
         int f, v, gm, used = 0;
         while (sscanf(t, "%d:%d:%d%n", &f, &v, &gm, &used) == 3) {
-            if (f >= 0 && f < VP_PROF_COUNT) { c->gemm_variant[f] = v; c->gemm_group_m[f] = gm; }
+            if (f >= 0 && f < VP_PROF_COUNT) { s.gemm_variant[f] = v; s.gemm_group_m[f] = gm; }
             t += used;
             if (*t == ',') ++t; else break;
         }
@@ -66,71 +62,82 @@ void apply_gemm_tuning(vp_ctx* c) {
 #endif
 }
 
-int gemm(vp_ctx* c, int fam, int epi, const uint16_t* A, const uint16_t* W, const float* bias, void* out,
+// Every switch of a handle, read once (vp_create): switches between SHIPPED, tested code paths (each has a parity test that flips it) and the thresholds
+// of the measured rules; the measurement build adds its development switches (tools/)
+void read_switches(Switches& s) {
+    auto on = [](const char* name, bool& dst) { if (const char* f = getenv(name)) dst = atoi(f) != 0; };
+    auto num = [](const char* name, auto& dst) { if (const char* f = getenv(name)) dst = atol(f); };
+    on("VP_FUSE_LN", s.fuse_ln);
+    on("VP_PERSIST", s.persist_gemm);
+    if (const char* f = getenv("VP_GRAPH")) s.graph_max_n = atoi(f) == 1 ? 16 : atoi(f);   // 0 = off, 1 = default, n > 1: capture chunks of up to n crops
+    on("VP_GRAPH_NULL", s.graph_null);
+    if (const char* f = getenv("VP_CALLER_STREAM")) s.caller_stream_max_n = atoi(f) == 1 ? 16 : atoi(f);   // 0 = always fence against the caller's stream with events
+    on("VP_FUSE_HEAD", s.fuse_head);
+    if (const char* f = getenv("VP_FOLD_STATS")) { s.graph_max_n_stats = atoi(f); s.fold_rule = false; }   // an explicit threshold: fold up to that many crops, nowhere else
+    on("VP_BLOCKED_QKV", s.blocked_qkv);
+    on("VP_FUSE_QKV_ATTN", s.fuse_qkv_attn);
+    s.qa_min_set = getenv("VP_QA_MIN_TILES") != nullptr;
+    num("VP_QA_MIN_TILES", s.qa_min_tiles);
+    num("VP_QA80_MIN_TILES", s.qa80_min_tiles);
+    num("VP_QA80_GROUP", s.qa80_group);
+    num("VP_ATTN_QSPLIT", s.attn_qsplit);
+    on("VP_DECONV_PARITY_FAST", s.deconv_parity_fast);
+    on("VP_G8_COST", s.g8_cost_model);
+    on("VP_PAD_BATCH", s.pad_batch);
+    num("VP_G8_BM192", s.g8_bm192);   // mask: 1 = residual GEMMs, 2 = wide GEMMs may take the 192 x 256 tile of the 8-phase kernel (0: never)
+    if (const char* f = getenv("VP_SPLITK")) {   // 0 = off; "fc2:S:variant,proj:S:variant" = override the rule (measurement sweeps)
+        if (!strchr(f, ':')) s.splitk_on = atoi(f) != 0;
+        else {
+            const char* t = f;
+            while (*t) {
+                const int which = !strncmp(t, "fc2:", 4) ? 1 : !strncmp(t, "proj:", 5) ? 0 : -1;
+                if (which < 0) break;
+                t = strchr(t, ':') + 1;
+                int S = 0, v = 0, used = 0;
+                if (sscanf(t, "%d:%d%n", &S, &v, &used) != 2) break;
+                s.splitk_force[which][0] = S; s.splitk_force[which][1] = v;
+                t += used;
+                if (*t == ',') ++t;
+            }
+        }
+    }
+    num("VP_GEMM8", s.gemm8_mask);   // which GEMMs may take the 8-phase kernel (1 fc2, 2 fc1, 4 qkv, 8 proj; 0 = the 2-phase kernels everywhere)
+    s.fp8_proj16 = getenv("VP_FP8_PROJ16") != nullptr;
+#ifdef VP_TOOLS   // development switches of the measurement build (tools/, DESIGN.md section 8)
+    num("VP_G8_MIN_TILES", s.g8_min_tiles);
+    on("VP_BLOCKED_HID", s.blocked_hid);
+    num("VP_ORDER", s.order_mask);
+    num("VP_G8_STAGGER", s.g8_stagger);
+    if (const char* t = getenv("VP_ABLATE_FAM")) {   // e.g. "2:64,1:64" = non-temporal stores in the qkv and fc1 epilogues
+        int f, b, used = 0;
+        while (sscanf(t, "%d:%d%n", &f, &b, &used) == 2) {
+            if (f >= 0 && f < VP_PROF_COUNT) s.fam_ablate[f] = b;
+            t += used;
+            if (*t == ',') ++t; else break;
+        }
+    }
+#endif
+    apply_gemm_tuning(s);
+}
+
+int gemm(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint16_t* A, const uint16_t* W, const float* bias, void* out,
          const float* aux, int M, int N, int K, int ldo, int Hin, int Win, int Cin, const LnFuse* ln) {
     vp::GemmArgs g{};
     g.A = A; g.W = W; g.bias = bias; g.out = out; g.aux = aux;
     g.M = M; g.N = N; g.K = K; g.ldo = ldo;
     g.Hin = Hin; g.Win = Win; g.Cin = Cin; g.zero = c->zero; g.Kp = c->Kp;
     g.w_rows = (int)pad128((size_t)N);
-    g.variant = c->gemm_variant[fam];
-    g.group_m = c->gemm_group_m[fam];
-    g.ablate = c->gemm_ablate | c->fam_ablate[fam];
-    g.parity_fast = c->deconv_parity_fast;
-    const bool mixed = c->mix_expert && fam == VP_PROF_GEMM_FC2;   // ViTPose+ mixed batch: every crop's m-tiles read its own expert's fc2
-    if (mixed) g.expert = c->mix_expert;   // expert e's fc2 lies e * w_rows * K / e * w_rows behind (weights.hip upload_fc2_experts: w_rows = pad128(D))
-    if (g.variant < 0) {
-        const Tile2Pick tp = pick_gemm2_tile(epi, M, N, K);   // the 2-phase kernels' tile (the 8-phase kernel may take the GEMM over below)
-        g.variant = tp.variant; g.group_m = tp.group_m;
-    }
-    if (c->persist_gemm && g.variant == 8 && (epi == vp::EPI_BIAS || epi == vp::EPI_BIAS_GELU) && K % 128 == 0 && ldo == N &&
-        M % 192 == 0 && N % 128 == 0 && (long)(M / 192) * (N / 128) >= 1024)   // >= 2 tiles per resident workgroup
-        g.persist = 1;
+    g.variant = pk.variant; g.group_m = pk.group_m; g.persist = pk.persist; g.stagger = pk.stagger;
+    g.ablate = c->gemm_ablate | c->sw.fam_ablate[fam];
+    g.parity_fast = c->sw.deconv_parity_fast;
+    if (c->mix_expert && fam == VP_PROF_GEMM_FC2) g.expert = c->mix_expert;   // expert e's fc2 lies e * w_rows * K / e * w_rows behind (weights.hip upload_fc2_experts: w_rows = pad128(D))
     if (ln) {
         g.a_blocked = ln->a_blocked; g.out_blocked = ln->out_blocked; g.reverse = ln->reverse;
         g.plane = ln->plane; g.stats_out = ln->stats_out; g.rowstat = ln->rowstat; g.ln_s = ln->ln_s;
         g.ln_part = ln->ln_part; g.ln_tiles = ln->ln_tiles; g.ln_inv_d = 1.0f / (float)K;
         if (ln->tiles_out) *ln->tiles_out = N / 64;   // partial statistics are written per 64 columns, whatever the tile
     }
-    // large batches: the 8-phase persistent kernel (gemm8.hip), one 512-thread workgroup per CU on 256 x 256 (wide GEMMs) or
-    // 256 x 192 (N = D: 768 = 4 x 192, three full rounds of 256 workgroups at batch 256) tiles, when every CU gets >= 1.75 tiles
-    // (attn.proj, K = N = D, is HBM-bound and stays on the 192 x 128 tile with two workgroups per CU: measured 105 vs 112 us;
-    // bit 3 of VP_GEMM8 moves it too)
-    const bool is_proj = epi == vp::EPI_BIAS_RESID_LN && K <= N;
-    const int g8bit = fam == VP_PROF_GEMM_FC2 ? 1 : fam == VP_PROF_GEMM_FC1 ? 2 : fam == VP_PROF_GEMM_QKV ? 4 : fam == VP_PROF_GEMM_PROJ ? 8 : 0;
-    (void)is_proj;
-    if (c->gemm_variant[fam] < 0 && (c->gemm8_mask & g8bit) &&
-        (epi == vp::EPI_BIAS || epi == vp::EPI_BIAS_GELU || epi == vp::EPI_BIAS_RESID_LN)) {
-        const bool wide = epi != vp::EPI_BIAS_RESID_LN;
-        // tile shape: pick_gemm8_tile above (256 x 256; residual GEMMs also 256 x 192; 192 x 256 where the row count or the rounds ask for it)
-#ifdef VP_TOOLS
-        static const long min_tiles = [] { const char* e = getenv("VP_G8_MIN_TILES"); return e ? atol(e) : 448L; }();
-#else
-        const long min_tiles = 448;
-#endif
-        const G8Pick pk = pick_gemm8_tile(M, N, wide, c->g8_bm192, min_tiles, c->g8_cost_model);
-        if (pk.variant && vp::gemm8_supported(epi, g, pk.bn, pk.bm)) {
-            g.variant = pk.variant;
-            g.group_m = fam == VP_PROF_GEMM_QKV ? 4 : fam == VP_PROF_GEMM_FC2 ? 2 : 8;   // measured sweep 0 / 2 / 4 / 8 / 16 / 32 (spread 2-3 %)
-            g.persist = 0;
-            g.stagger = c->g8_stagger;
-        }
-    }
-    if (epi == vp::EPI_DECONV_FINAL) {   // deconv2 + final 1x1 conv in one kernel: the 256 x 256 tile (all channels of a pixel)
-        g.variant = 3; g.group_m = 0; g.persist = 0;
-        g.W2 = c->w_fin; g.bias2 = c->b_fin; g.out2 = c->hm;
-    }
-    if (g.ln_part) {   // only the one-tile-per-workgroup 2-phase kernel folds partial statistics itself
-        g.persist = 0;
-        if (g.variant >= 16 && g.variant <= 18) { g.variant = 8; g.group_m = 8; }
-    }
-    if (mixed && !expert_tile_ok(tile_bm(g.variant), c->mix_bounds)) {   // a tile would span two experts: the crop-aligned tile instead (tile_rules.hip)
-        vp::GemmArgs t = g;
-        const bool g8 = (c->gemm8_mask & 1) && vp::gemm8_supported(epi, t, 256, 192);
-        g.variant = expert_fallback_variant(M, N, g8, &g.group_m);
-        g.persist = 0;
-        g.stagger = g.variant == 18 ? c->g8_stagger : 0;
-    }
+    if (epi == vp::EPI_DECONV_FINAL) { g.W2 = c->w_fin; g.bias2 = c->b_fin; g.out2 = c->hm; }   // deconv2 + final 1x1 conv in one kernel
     const bool deconv = epi == vp::EPI_DECONV || epi == vp::EPI_DECONV_FINAL;
     const double par = deconv ? 4.0 : 1.0;
     const double Nalg = (epi == vp::EPI_HEATMAP) ? (double)c->Kp : (double)N;   // heatmap: N counts the hi + lo weight rows
@@ -149,25 +156,20 @@ int gemm(vp_ctx* c, int fam, int epi, const uint16_t* A, const uint16_t* W, cons
     char desc[192];
     desc[0] = 0;
     g.desc = desc; g.desc_cap = (int)sizeof(desc);   // the launch code names the kernel it resolved to (one snprintf per GEMM launch: vp_profile_kernel reports the LAST launch)
-    // small batches: a residual GEMM as S partial products over k ranges + a fixed-order reduction (tile_rules.hip pick_splitk)
-    if (epi == vp::EPI_BIAS_RESID_LN && !mixed && c->splitk_ws && (size_t)M <= c->splitk_rows && c->gemm_variant[fam] < 0 && !(g.variant >= 16 && g.variant <= 18) &&
-        out == (void*)aux && (fam == VP_PROF_GEMM_FC2 || fam == VP_PROF_GEMM_PROJ)) {
-        const int which = fam == VP_PROF_GEMM_FC2 ? 1 : 0;
-        SplitKPick sk = pick_splitk(M, N, K);
-        if (c->splitk_force[which][0] > 0) sk = {c->splitk_force[which][0], c->splitk_force[which][1]};
-        if (sk.S > 1 && sk.S <= SPLITK_MAX_S && K % (sk.S * 128) == 0) {
-            vp::GemmArgs p = g;
-            p.out = c->splitk_ws; p.aux = nullptr; p.bias = nullptr; p.stats_out = nullptr; p.plane = 0;
-            p.variant = sk.variant; p.group_m = 0; p.splitk = sk.S; p.ldo = N; p.persist = 0;
-            LAUNCH(c, fam, flops, bytes, vp::gemm_launch(c->dtype, vp::EPI_PARTIAL, p, c->stream));   // (flops / bytes stay the algorithmic figures of the GEMM; the partials' round trip is overhead)
-            if (desc[0]) {
-                char d2[224];
-                snprintf(d2, sizeof(d2), "%s x split-K %d + splitk_reduce_kernel", desc, sk.S);
-                if (c->kernel_desc[fam] != d2) c->kernel_desc[fam] = d2;
-            }
-            LAUNCH(c, fam, 0.0, 0.0, vp::splitk_reduce_launch(c->dtype, c->splitk_ws, sk.S, bias, (uint16_t*)out, g.plane, g.stats_out, M, N, c->stream));
-            return VP_OK;
+    // small batches: a residual GEMM as S partial products over k ranges + a fixed-order reduction (tile_rules.hip pick_splitk), x updated in place
+    if (pk.splitk > 1) {
+        if (out != (void*)aux || (size_t)M > c->splitk_rows || !c->splitk_ws) return fail(c, VP_ERR_INVALID, "split-K: a residual GEMM in place within the workspace only");
+        vp::GemmArgs p = g;
+        p.out = c->splitk_ws; p.aux = nullptr; p.bias = nullptr; p.stats_out = nullptr; p.plane = 0;
+        p.variant = pk.splitk_variant; p.group_m = 0; p.splitk = pk.splitk; p.ldo = N; p.persist = 0;
+        LAUNCH(c, fam, flops, bytes, vp::gemm_launch(c->dtype, vp::EPI_PARTIAL, p, c->stream));   // (flops / bytes stay the algorithmic figures of the GEMM; the partials' round trip is overhead)
+        if (desc[0]) {
+            char d2[224];
+            snprintf(d2, sizeof(d2), "%s x split-K %d + splitk_reduce_kernel", desc, pk.splitk);
+            if (c->kernel_desc[fam] != d2) c->kernel_desc[fam] = d2;
         }
+        LAUNCH(c, fam, 0.0, 0.0, vp::splitk_reduce_launch(c->dtype, c->splitk_ws, pk.splitk, bias, (uint16_t*)out, g.plane, g.stats_out, M, N, c->stream));
+        return VP_OK;
     }
     LAUNCH(c, fam, flops, bytes, vp::gemm_launch(c->dtype, epi, g, c->stream));
     if (desc[0] && c->kernel_desc[fam] != desc) c->kernel_desc[fam] = desc;
@@ -176,7 +178,7 @@ int gemm(vp_ctx* c, int fam, int epi, const uint16_t* A, const uint16_t* W, cons
 
 // fp8 mode: one encoder GEMM on MXFP8 operands (gemm8f.hip).  epi: EPI_BIAS (qkv -> 16-bit), EPI_BIAS_GELU (fc1 -> MXFP8 codes at `out`,
 // block scales at out_scales), EPI_BIAS_RESID_LN (fc2: two-plane residual + row statistics).  M = padded token rows (multiple of 256).
-int gemm_fp8(vp_ctx* c, int fam, int epi, const uint8_t* A8, const uint8_t* a_scales, const uint8_t* W8, const float* w_scale, const float* bias,
+int gemm_fp8(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint8_t* A8, const uint8_t* a_scales, const uint8_t* W8, const float* w_scale, const float* bias,
              void* out, uint8_t* out_scales, const float* aux, int M, int N, int K, const LnFuse* ln) {
     vp::GemmArgs g{};
     g.A = (const uint16_t*)A8; g.W = (const uint16_t*)W8; g.bias = bias; g.out = out; g.aux = aux;
@@ -188,19 +190,8 @@ int gemm_fp8(vp_ctx* c, int fam, int epi, const uint8_t* A8, const uint8_t* a_sc
         g.plane = ln->plane; g.stats_out = ln->stats_out;
         if (ln->tiles_out) *ln->tiles_out = N / 64;
     }
-    // tile width: 256 for the wide GEMMs; the residual GEMM takes the width whose tile count fills the rounds of 256 persistent workgroups best
-    int bn = 256;
-    if (epi == vp::EPI_BIAS_RESID_LN) {
-        double fill = -1.0;
-        for (int cand : {256, 192}) {
-            if (N % cand) continue;
-            const long t = (long)(M / 256) * (N / cand);
-            if (t < 8) continue;
-            const double f = (double)t / (double)((t + 255) / 256 * 256);
-            if (f > fill + 1e-9) { bn = cand; fill = f; }
-        }
-    }
-    g.group_m = fam == VP_PROF_GEMM_QKV ? 4 : fam == VP_PROF_GEMM_FC2 ? 2 : 8;
+    const int bn = pk.variant == 17 ? 192 : 256;   // tile_rules.hip resolve_gemm_fp8
+    g.group_m = pk.group_m;
     if (!vp::gemm8f_supported(epi, g, bn))
         return fail(c, VP_ERR_SHAPE, "fp8 mode: GEMM shape " + std::to_string(M) + " x " + std::to_string(N) + " x " + std::to_string(K) + " not supported by the MXFP8 kernel");
     const double flops = 2.0 * M * (double)N * K;
@@ -218,24 +209,30 @@ int gemm_fp8(vp_ctx* c, int fam, int epi, const uint8_t* A8, const uint8_t* a_sc
 
 namespace {
 
-int head_chunk(vp_ctx* c, const uint16_t* y, int nh, float* hm);
+int head_chunk(vp_ctx* c, const uint16_t* y, int nh, float* hm, const HeadPlan& hp);
 
 // fc2 weights / bias of block b for the active expert (a ViTPose+ handle outside a mixed batch; expert 0 = the only one of a plain handle)
 const uint16_t* fc2_w(const vp_ctx* c, const vpi::Block& b) { return c->mix_expert ? b.w_fc2 : b.w_fc2 + (size_t)c->expert * c->fc2_w_stride; }
 const float* fc2_b(const vp_ctx* c, const vpi::Block& b) { return c->mix_expert ? b.b_fc2 : b.b_fc2 + (size_t)c->expert * c->fc2_b_stride; }
 
-// forward of one chunk (n <= max_batch) with device-resident crops; heatmaps land in c->hm (head = false: the encoder and last_norm only, tokens in c->y)
+// forward of one chunk (n <= max_batch) with device-resident crops; heatmaps land in c->hm (head = false: the encoder and last_norm only, tokens in c->y).
+// Executes the chunk's plan (tile_rules.hip plan_chunk): which kernel runs each GEMM, the encoder batch, the LayerNorm folds, the qkv path.
 int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, bool want_tokens, bool flip = false, bool head = true) {
     const int D = c->D;
-    // the ENCODER's batch: n_in crops, or the next multiple of 4 where that buys the MLP GEMMs an 8-phase tile (tile_rules.hip pick_run_batch; rows n_in .. n - 1 repeat the
-    // last crop and are never read by the head); the fp8 mode pads its rows itself
-    const int n = (c->pad_batch && c->fuse_ln && !c->fp8) ? pick_run_batch(n_in, D, (c->maxb + 3) / 4 * 4, c->g8_bm192, c->g8_cost_model, c->gemm8_mask) : n_in;
+    const ChunkPlan pl = plan_chunk(c->sw, D, c->heads, c->maxb, c->fp8, n_in, c->fin_rows, c->mix_expert ? &c->mix_bounds : nullptr);
+    const GemmPick* pk = pl.gemm;
+    const int n = pl.n;   // rows n_in .. n - 1 of a padded encoder batch repeat the last crop and are never read by the head
     const int M = n * 192;
     const double in_b = (fmt == VP_INPUT_F32_NCHW ? 4.0 : 1.0) * n_in * 3.0 * 256 * 192;
     LAUNCH(c, VP_PROF_IM2COL, 0.0, in_b + 2.0 * M * 768, vp::im2col_launch(c->dtype, d_crops, fmt, c->hid, n, c->stream, flip, n_in));
     int rc;
     size_t plane = 0;   // != 0: the residual stream c->x is held as two 16-bit planes (fused-LayerNorm path)
-    const bool qkv_blocked = c->blocked_qkv && D / c->heads == 64;
+    const bool qkv_blocked = c->sw.blocked_qkv && D / c->heads == 64;
+    auto attention = [&](uint16_t* out, double bytes, uint8_t* mx_scales) -> int {
+        LAUNCH(c, VP_PROF_ATTN, 4.0 * 192 * 192 * (double)D * n, bytes,
+               vp::attention_launch(c->dtype, c->qkv, out, n, D, c->heads, c->stream, pl.attn_qsplit, qkv_blocked ? 1 : 0, mx_scales));
+        return VP_OK;
+    };
     if (c->fp8) {
         // fp8 mode.  The residual stream, the attention core, attn.proj, the head and the decode are the fp16 path's; qkv / fc1 / fc2 run
         // on MXFP8 operands.  Token rows are padded to Mp (multiple of the 256-row tile, >= 512): padding rows carry zeros into the
@@ -250,167 +247,123 @@ int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, bool want_t
                    vp::ln_quant_launch(c->dtype, xh, c->ln_part, tiles, c->x8, c->xs8, M, Mp, D, c->stream));
             return VP_OK;
         };
-        if ((rc = gemm(c, VP_PROF_GEMM_PATCH, vp::EPI_POS_LN, c->hid, c->w_patch, c->b_zero, c->x, c->pos, M, D, 768, D, 0, 0, 0, &prod))) return rc;
+        if ((rc = gemm(c, VP_PROF_GEMM_PATCH, vp::EPI_POS_LN, pk[VP_PROF_GEMM_PATCH], c->hid, c->w_patch, c->b_zero, c->x, c->pos, M, D, 768, D, 0, 0, 0, &prod))) return rc;
         for (int l = 0; l < c->L; ++l) {
             const Block& b = c->blocks[l];
             if ((rc = quant())) return rc;
             LnFuse cq; cq.out_blocked = qkv_blocked;
-            if ((rc = gemm_fp8(c, VP_PROF_GEMM_QKV, vp::EPI_BIAS, c->x8, c->xs8, b.w_qkv8, b.ws_qkv, b.b_qkv, c->qkv, nullptr, nullptr, Mp, 3 * D, D, &cq))) return rc;
+            if ((rc = gemm_fp8(c, VP_PROF_GEMM_QKV, vp::EPI_BIAS, pk[VP_PROF_GEMM_QKV], c->x8, c->xs8, b.w_qkv8, b.ws_qkv, b.b_qkv, c->qkv, nullptr, nullptr, Mp, 3 * D, D, &cq))) return rc;
             LnFuse pp = prod;
-            if (c->y8) {   // head dim 64: attention writes MXFP8, attn.proj runs on the fp8 kernel too
-                LAUNCH(c, VP_PROF_ATTN, 4.0 * 192 * 192 * (double)D * n, 7.0 * M * D,
-                       vp::attention_launch(c->dtype, c->qkv, (uint16_t*)c->y8, n, D, c->heads, c->stream, qkv_blocked ? 1 : 0, c->ys8));
-                if ((rc = gemm_fp8(c, VP_PROF_GEMM_PROJ, vp::EPI_BIAS_RESID_LN, c->y8, c->ys8, b.w_proj8, b.ws_proj, b.b_proj, c->x, nullptr, c->x, Mp, D, D, &pp))) return rc;
+            if (pl.proj_fp8) {   // head dim 64: attention writes MXFP8, attn.proj runs on the fp8 kernel too
+                if ((rc = attention((uint16_t*)c->y8, 7.0 * M * D, c->ys8))) return rc;
+                if ((rc = gemm_fp8(c, VP_PROF_GEMM_PROJ, vp::EPI_BIAS_RESID_LN, pk[VP_PROF_GEMM_PROJ], c->y8, c->ys8, b.w_proj8, b.ws_proj, b.b_proj, c->x, nullptr, c->x, Mp, D, D, &pp))) return rc;
             } else {
-                LAUNCH(c, VP_PROF_ATTN, 4.0 * 192 * 192 * (double)D * n, 8.0 * M * D,
-                       vp::attention_launch(c->dtype, c->qkv, c->y, n, D, c->heads, c->stream, qkv_blocked ? 1 : 0));
-                if ((rc = gemm(c, VP_PROF_GEMM_PROJ, vp::EPI_BIAS_RESID_LN, c->y, b.w_proj, b.b_proj, c->x, c->x, M, D, D, D, 0, 0, 0, &pp))) return rc;
+                if ((rc = attention(c->y, 8.0 * M * D, nullptr))) return rc;
+                if ((rc = gemm(c, VP_PROF_GEMM_PROJ, vp::EPI_BIAS_RESID_LN, pk[VP_PROF_GEMM_PROJ], c->y, b.w_proj, b.b_proj, c->x, c->x, M, D, D, D, 0, 0, 0, &pp))) return rc;
             }
             if ((rc = quant())) return rc;
-            if ((rc = gemm_fp8(c, VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, c->x8, c->xs8, b.w_fc18, b.ws_fc1, b.b_fc1, c->hid, c->hs8, nullptr, Mp, 4 * D, D, nullptr))) return rc;
+            if ((rc = gemm_fp8(c, VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, pk[VP_PROF_GEMM_FC1], c->x8, c->xs8, b.w_fc18, b.ws_fc1, b.b_fc1, c->hid, c->hs8, nullptr, Mp, 4 * D, D, nullptr))) return rc;
             LnFuse p2 = prod;
-            if ((rc = gemm_fp8(c, VP_PROF_GEMM_FC2, vp::EPI_BIAS_RESID_LN, (const uint8_t*)c->hid, c->hs8, b.w_fc28, b.ws_fc2, b.b_fc2, c->x, nullptr, c->x, Mp, D, 4 * D, &p2))) return rc;
+            if ((rc = gemm_fp8(c, VP_PROF_GEMM_FC2, vp::EPI_BIAS_RESID_LN, pk[VP_PROF_GEMM_FC2], (const uint8_t*)c->hid, c->hs8, b.w_fc28, b.ws_fc2, b.b_fc2, c->x, nullptr, c->x, Mp, D, 4 * D, &p2))) return rc;
         }
-    } else if (c->fuse_ln) {
+    } else if (c->sw.fuse_ln) {
         // LayerNorm folded into the GEMMs on both sides of it.  The residual stream is kept as two 16-bit planes
         // (x = hi + lo, same bytes as fp32, >= 22 significant bits): every producer (patch embed, attn.proj,
         // mlp.fc2) writes the planes + partial row statistics, a tiny kernel folds those into (mean, rstd), and
         // qkv / fc1 multiply the hi plane -- the UN-normalised rows -- by gamma-folded weights and normalise in
-        // their epilogue.  Saves the 151 MB read + 75 MB write of 24 of the 25 LayerNorm passes.
+        // their epilogue.  Saves the 151 MB read + 75 MB write of 24 of the 25 LayerNorm passes.  Where the plan folds (fold1 / fold2), the consumer
+        // merges the partial statistics itself and the ln_finalize launch disappears.
         plane = (size_t)M * D;
         uint16_t* xh = (uint16_t*)c->x;
         int tiles = 0;
         LnFuse prod; prod.plane = plane; prod.stats_out = c->ln_part; prod.tiles_out = &tiles;
-        // small batches: the consumers fold the partial statistics themselves (same code, same bits) -- 2 x depth launches less
-        // (round 6: with the consumers' merge on a register copy of the row's statistics instead of a bank-conflicted LDS image -- gemm.hip, GemmArgs::ln_part -- the fold wins at
-        // every model and batch up to 8 crops, the one-round 192 x 128 tiles of ViTPose-L included: 8 crops 2.200 -> 2.143 ms against the ln_finalize launches, 4 crops 1.874 ->
-        // 1.800, 1 crop 1.172 -> 1.111; beyond 8 crops it still loses (every column tile merges its rows again; ViTPose-H's fused qkv + attention tile needs rowstat):
-        // profiles/small_batch_r6.txt call 11)
-        const bool fold_stats = n <= c->graph_max_n_stats;
-        // Round 6 (profiles/small_batch_r6.txt call 25): beyond 8 crops the fold did not lose because of the merge but because the (mean, rstd) area behind the ring pushes the
-        // 80 KiB ring of the default 192 x 128 tile over half the CU's LDS -- ONE workgroup per CU instead of two (+9 ... +12 % per step).  Per consumer (attn.qkv reads LayerNorm-1,
-        // mlp.fc1 LayerNorm-2): fold where its GEMM runs on a 2-phase tile that keeps its occupancy with the area (every configuration but the 80 KiB-ring ones), i.e. not on the
-        // 8-phase kernel, not in a fused qkv + attention kernel (they read rowstat): ViTPose-S 9-28 crops -6.5 ... -8 %, -B 9-14 -2 ... -6 %, -L 9-10 -2.3 %; same code, same bits.
-        auto folds = [&](int fam, int epi, int N, int g8bit) {
-            if (fold_stats) return true;
-            if (!c->fold_rule || n > 64 || c->gemm_variant[fam] >= 0) return false;
-            if ((c->gemm8_mask & g8bit) && pick_gemm8_tile(M, N, true, c->g8_bm192, 448, c->g8_cost_model).variant) return false;
-            const int v = pick_gemm2_tile(epi, M, N, D).variant;
-            return v != 8 && v != 11;
-        };
-        // attn.qkv + attention core as ONE kernel per (pair of crops, head) from 108 tiles on (qkvattn.hip; bit-identical y; an odd batch's last crop fills both halves of its pair)
-        // 128 - 1536 tiles: profiles/qkvattn_r4.txt.  Below (round 6, profiles/small_batch_r6.txt call 16): 108-120 tiles win or tie (ViTPose-B 17-20 crops -0.6 ... -6.5 %: at 19-20
-        // crops the unfused qkv is 540 tiles of 128 x 128 on 512 slots; ViTPose-L 13-14 crops equal); 96 tiles and fewer lose (-B 16 crops +-0, 12 crops +3 %, -L 9-12 crops +2 ... +7 %)
-        //   Call 26: with the per-consumer statistics fold (below) the two-launch path saves its LayerNorm-1 ln_finalize launches wherever the qkv GEMM's tile folds, and wins back
-        //   108-127 tiles there (ViTPose-B 17-18 crops -1.8 / -2.2 %, -L 13-14 crops -2.9 / -3.4 %); where that GEMM would run on the default tile (-B 19-20) the fused kernel keeps them.
-        static const bool qa_min_set = getenv("VP_QA_MIN_TILES") != nullptr;
-        static const long qa_min_tiles = [] { const char* e = getenv("VP_QA_MIN_TILES"); return e ? atol(e) : 108L; }();
-        // head dim 80: one crop x one head per 192 x 256 tile of the 8-phase kernel (gemm8.hip EPI_QKV_ATTN; bit-identical y), from 192 tiles on
-        static const long qa80_min_tiles = [] { const char* e = getenv("VP_QA80_MIN_TILES"); return e ? atol(e) : 192L; }();   // wins from 12 crops x 16 heads on (profiles/qkvattn80_r5.txt)
-        const bool has_qkvh = c->L > 0 && c->blocks[0].w_qkvh != nullptr;
-        const bool qkv_can_fold = folds(VP_PROF_GEMM_QKV, vp::EPI_BIAS, 3 * D, 4);
-        const long pair_tiles = (long)((n + 1) / 2) * c->heads;
-        const bool want80 = has_qkvh && c->heads * 80 == D && (long)n * c->heads >= qa80_min_tiles;
-        const bool want64 = has_qkvh && c->heads * 64 == D && pair_tiles >= qa_min_tiles && (qa_min_set || pair_tiles >= 128 || !qkv_can_fold);
-        const bool fold1 = fold_stats || (!want80 && !want64 && qkv_can_fold);   // LayerNorm-1 -> attn.qkv
-        const bool fold2 = folds(VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, 4 * D, 2);                                       // LayerNorm-2 -> mlp.fc1
         auto finalize = [&](bool folded) -> int {
             if (folded) return VP_OK;
             LAUNCH(c, VP_PROF_LAYERNORM, 0.0, 8.0 * M * tiles + 8.0 * M, vp::ln_finalize_launch(c->ln_part, c->rowstat, M, tiles, D, c->stream));
             return VP_OK;
         };
-        if ((rc = gemm(c, VP_PROF_GEMM_PATCH, vp::EPI_POS_LN, c->hid, c->w_patch, c->b_zero, c->x, c->pos, M, D, 768, D, 0, 0, 0, &prod))) return rc;
-        if ((rc = finalize(fold1))) return rc;
+        const double qkv_attn_flops = 2.0 * M * 3.0 * D * D + 4.0 * 192 * 192 * (double)D * n, qkv_attn_bytes = 2.0 * M * D + 2.0 * 3 * D * (double)D + 2.0 * M * D;
+        if ((rc = gemm(c, VP_PROF_GEMM_PATCH, vp::EPI_POS_LN, pk[VP_PROF_GEMM_PATCH], c->hid, c->w_patch, c->b_zero, c->x, c->pos, M, D, 768, D, 0, 0, 0, &prod))) return rc;
+        if ((rc = finalize(pl.fold1))) return rc;
         for (int l = 0; l < c->L; ++l) {
             const Block& b = c->blocks[l];
-            LnFuse cq; cq.rowstat = c->rowstat; cq.ln_s = b.s_qkv; cq.reverse = (c->order_mask & 1) != 0; cq.out_blocked = qkv_blocked;
-            if (fold1) { cq.rowstat = nullptr; cq.ln_part = c->ln_part; cq.ln_tiles = D / 64; }
-            vp::QkvAttnArgs qa{};
-            qa.x_hi = xh; qa.wh = b.w_qkvh; qa.bh = b.b_qkvh; qa.sh = b.s_qkvh; qa.rowstat = c->rowstat; qa.y = c->y;
-            qa.npairs = (n + 1) / 2; qa.ncrops = n; qa.heads = c->heads; qa.D = D;   // odd n: the last crop fills both halves of its pair
-            qa.scale_log2e = (1.0f / sqrtf(64.0f)) * 1.4426950408889634f;
-            // (a shape the fused kernel rejects -- a chunk beyond its 32-bit row offsets, fewer than 8 tiles under a lowered VP_QA_MIN_TILES -- falls through
-            // to the gemm + attention pair below, the way gemm() falls back when gemm8_supported says no: ADVICE r4)
-            vp::GemmArgs g80{};
-            if (b.w_qkvh && c->heads * 80 == D) {
+            if (pl.qkv_path == QKV_ATTN80) {   // one crop x one head per 192 x 256 tile of the 8-phase kernel (gemm8.hip EPI_QKV_ATTN)
+                vp::GemmArgs g80{};
                 g80.A = xh; g80.W = b.w_qkvh; g80.bias = b.b_qkvh; g80.ln_s = b.s_qkvh; g80.rowstat = c->rowstat; g80.out = c->y;
                 g80.M = M; g80.N = c->heads * 256; g80.K = D; g80.ldo = D; g80.w_rows = c->heads * 256; g80.variant = 18;
                 // tile order: groups of 8 crops x all heads, crop fastest -- the 32 workgroups of an XCD then work on 8 crops x 4 heads at a time (12 operand K-slices
                 // fetched per K-tile for 32 tiles instead of 18 with the head-fastest order: PMC traffic 800 -> ~450 MB per launch, profiles/qkvattn80_r5.txt)
-                static const int qa80_group = [] { const char* e = getenv("VP_QA80_GROUP"); return e ? atoi(e) : 8; }();
-                g80.group_m = qa80_group;
+                g80.group_m = c->sw.qa80_group;
                 g80.attn_scale_log2e = (1.0f / sqrtf(80.0f)) * 1.4426950408889634f;
-                g80.ablate = c->gemm_ablate | c->fam_ablate[VP_PROF_GEMM_QKV];
-            }
-            if (g80.A && !fold1 && (long)n * c->heads >= qa80_min_tiles && c->gemm_variant[VP_PROF_GEMM_QKV] < 0 && vp::gemm8_supported(vp::EPI_QKV_ATTN, g80, 256, 192)) {
+                g80.ablate = c->gemm_ablate | c->sw.fam_ablate[VP_PROF_GEMM_QKV];
                 char desc[192];
                 desc[0] = 0;
                 g80.desc = desc; g80.desc_cap = (int)sizeof(desc);
-                LAUNCH(c, VP_PROF_GEMM_QKV, 2.0 * M * 3.0 * D * D + 4.0 * 192 * 192 * (double)D * n, 2.0 * M * D + 2.0 * 3 * D * (double)D + 2.0 * M * D,
-                       vp::gemm_launch(c->dtype, vp::EPI_QKV_ATTN, g80, c->stream));
+                LAUNCH(c, VP_PROF_GEMM_QKV, qkv_attn_flops, qkv_attn_bytes, vp::gemm_launch(c->dtype, vp::EPI_QKV_ATTN, g80, c->stream));
                 if (desc[0] && c->kernel_desc[VP_PROF_GEMM_QKV] != desc) c->kernel_desc[VP_PROF_GEMM_QKV] = desc;
-            } else if (want64 && b.w_qkvh && !fold1 && c->gemm_variant[VP_PROF_GEMM_QKV] < 0 && vp::qkvattn_supported(qa)) {
+            } else if (pl.qkv_path == QKV_ATTN64) {   // one pair of crops x one head per tile (qkvattn.hip; an odd batch's last crop fills both halves of its pair)
+                vp::QkvAttnArgs qa{};
+                qa.x_hi = xh; qa.wh = b.w_qkvh; qa.bh = b.b_qkvh; qa.sh = b.s_qkvh; qa.rowstat = c->rowstat; qa.y = c->y;
+                qa.npairs = (n + 1) / 2; qa.ncrops = n; qa.heads = c->heads; qa.D = D;
+                qa.scale_log2e = (1.0f / sqrtf(64.0f)) * 1.4426950408889634f;
                 char desc[96];
                 desc[0] = 0;
-                LAUNCH(c, VP_PROF_GEMM_QKV, 2.0 * M * 3.0 * D * D + 4.0 * 192 * 192 * (double)D * n, 2.0 * M * D + 2.0 * 3 * D * (double)D + 2.0 * M * D,
-                       vp::qkvattn_launch(c->dtype, qa, c->stream, desc, (int)sizeof(desc)));
+                LAUNCH(c, VP_PROF_GEMM_QKV, qkv_attn_flops, qkv_attn_bytes, vp::qkvattn_launch(c->dtype, qa, c->stream, desc, (int)sizeof(desc)));
                 if (desc[0] && c->kernel_desc[VP_PROF_GEMM_QKV] != desc) c->kernel_desc[VP_PROF_GEMM_QKV] = desc;
             } else {
-            if ((rc = gemm(c, VP_PROF_GEMM_QKV, vp::EPI_BIAS, xh, b.w_qkv, b.b_qkv, c->qkv, nullptr, M, 3 * D, D, 3 * D, 0, 0, 0, &cq))) return rc;
-            LAUNCH(c, VP_PROF_ATTN, 4.0 * 192 * 192 * (double)D * n, 8.0 * M * D,
-                   vp::attention_launch(c->dtype, c->qkv, c->y, n, D, c->heads, c->stream, qkv_blocked ? 1 : 0));
+                LnFuse cq; cq.rowstat = c->rowstat; cq.ln_s = b.s_qkv; cq.reverse = (c->sw.order_mask & 1) != 0; cq.out_blocked = qkv_blocked;
+                if (pl.fold1) { cq.rowstat = nullptr; cq.ln_part = c->ln_part; cq.ln_tiles = D / 64; }
+                if ((rc = gemm(c, VP_PROF_GEMM_QKV, vp::EPI_BIAS, pk[VP_PROF_GEMM_QKV], xh, b.w_qkv, b.b_qkv, c->qkv, nullptr, M, 3 * D, D, 3 * D, 0, 0, 0, &cq))) return rc;
+                if ((rc = attention(c->y, 8.0 * M * D, nullptr))) return rc;
             }
-            LnFuse pp = prod; pp.reverse = (c->order_mask & 2) != 0;
-            if ((rc = gemm(c, VP_PROF_GEMM_PROJ, vp::EPI_BIAS_RESID_LN, c->y, b.w_proj, b.b_proj, c->x, c->x, M, D, D, D, 0, 0, 0, &pp))) return rc;
-            if ((rc = finalize(fold2))) return rc;
-            LnFuse c1; c1.rowstat = c->rowstat; c1.ln_s = b.s_fc1; c1.out_blocked = c->blocked_hid; c1.reverse = (c->order_mask & 4) != 0;
-            if (fold2) { c1.rowstat = nullptr; c1.ln_part = c->ln_part; c1.ln_tiles = D / 64; }
-            if ((rc = gemm(c, VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, xh, b.w_fc1, b.b_fc1, c->hid, nullptr, M, 4 * D, D, 4 * D, 0, 0, 0, &c1))) return rc;
-            LnFuse p2 = prod; p2.a_blocked = c->blocked_hid; p2.reverse = (c->order_mask & 8) != 0;
-            if ((rc = gemm(c, VP_PROF_GEMM_FC2, vp::EPI_BIAS_RESID_LN, c->hid, fc2_w(c, b), fc2_b(c, b), c->x, c->x, M, D, 4 * D, D, 0, 0, 0, &p2))) return rc;
-            if (l + 1 < c->L && (rc = finalize(fold1))) return rc;   // last block: last_norm below is a standalone pass
+            LnFuse pp = prod; pp.reverse = (c->sw.order_mask & 2) != 0;
+            if ((rc = gemm(c, VP_PROF_GEMM_PROJ, vp::EPI_BIAS_RESID_LN, pk[VP_PROF_GEMM_PROJ], c->y, b.w_proj, b.b_proj, c->x, c->x, M, D, D, D, 0, 0, 0, &pp))) return rc;
+            if ((rc = finalize(pl.fold2))) return rc;
+            LnFuse c1; c1.rowstat = c->rowstat; c1.ln_s = b.s_fc1; c1.out_blocked = c->sw.blocked_hid; c1.reverse = (c->sw.order_mask & 4) != 0;
+            if (pl.fold2) { c1.rowstat = nullptr; c1.ln_part = c->ln_part; c1.ln_tiles = D / 64; }
+            if ((rc = gemm(c, VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, pk[VP_PROF_GEMM_FC1], xh, b.w_fc1, b.b_fc1, c->hid, nullptr, M, 4 * D, D, 4 * D, 0, 0, 0, &c1))) return rc;
+            LnFuse p2 = prod; p2.a_blocked = c->sw.blocked_hid; p2.reverse = (c->sw.order_mask & 8) != 0;
+            if ((rc = gemm(c, VP_PROF_GEMM_FC2, vp::EPI_BIAS_RESID_LN, pk[VP_PROF_GEMM_FC2], c->hid, fc2_w(c, b), fc2_b(c, b), c->x, c->x, M, D, 4 * D, D, 0, 0, 0, &p2))) return rc;
+            if (l + 1 < c->L && (rc = finalize(pl.fold1))) return rc;   // last block: last_norm below is a standalone pass
         }
     } else {
-    if ((rc = gemm(c, VP_PROF_GEMM_PATCH, vp::EPI_POS, c->hid, c->w_patch, c->b_zero, c->x, c->pos, M, D, 768, D))) return rc;
+    if ((rc = gemm(c, VP_PROF_GEMM_PATCH, vp::EPI_POS, pk[VP_PROF_GEMM_PATCH], c->hid, c->w_patch, c->b_zero, c->x, c->pos, M, D, 768, D))) return rc;
     for (int l = 0; l < c->L; ++l) {
         const Block& b = c->blocks[l];
         LAUNCH(c, VP_PROF_LAYERNORM, 0.0, 6.0 * M * D,
                vp::layernorm_launch(c->dtype, c->x, b.ln1_g, b.ln1_b, c->y, nullptr, M, D, c->stream));
         LnFuse q0; q0.out_blocked = qkv_blocked;
-        if ((rc = gemm(c, VP_PROF_GEMM_QKV, vp::EPI_BIAS, c->y, b.w_qkv, b.b_qkv, c->qkv, nullptr, M, 3 * D, D, 3 * D, 0, 0, 0, &q0))) return rc;
-        LAUNCH(c, VP_PROF_ATTN, 4.0 * 192 * 192 * (double)D * n, 8.0 * M * D,
-               vp::attention_launch(c->dtype, c->qkv, c->y, n, D, c->heads, c->stream, qkv_blocked ? 1 : 0));
-        if ((rc = gemm(c, VP_PROF_GEMM_PROJ, vp::EPI_BIAS_RESID, c->y, b.w_proj, b.b_proj, c->x, c->x, M, D, D, D))) return rc;
+        if ((rc = gemm(c, VP_PROF_GEMM_QKV, vp::EPI_BIAS, pk[VP_PROF_GEMM_QKV], c->y, b.w_qkv, b.b_qkv, c->qkv, nullptr, M, 3 * D, D, 3 * D, 0, 0, 0, &q0))) return rc;
+        if ((rc = attention(c->y, 8.0 * M * D, nullptr))) return rc;
+        if ((rc = gemm(c, VP_PROF_GEMM_PROJ, vp::EPI_BIAS_RESID, pk[VP_PROF_GEMM_PROJ], c->y, b.w_proj, b.b_proj, c->x, c->x, M, D, D, D))) return rc;
         LAUNCH(c, VP_PROF_LAYERNORM, 0.0, 6.0 * M * D,
                vp::layernorm_launch(c->dtype, c->x, b.ln2_g, b.ln2_b, c->y, nullptr, M, D, c->stream));
-        if ((rc = gemm(c, VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, c->y, b.w_fc1, b.b_fc1, c->hid, nullptr, M, 4 * D, D, 4 * D))) return rc;
-        if ((rc = gemm(c, VP_PROF_GEMM_FC2, vp::EPI_BIAS_RESID, c->hid, fc2_w(c, b), fc2_b(c, b), c->x, c->x, M, D, 4 * D, D))) return rc;
+        if ((rc = gemm(c, VP_PROF_GEMM_FC1, vp::EPI_BIAS_GELU, pk[VP_PROF_GEMM_FC1], c->y, b.w_fc1, b.b_fc1, c->hid, nullptr, M, 4 * D, D, 4 * D))) return rc;
+        if ((rc = gemm(c, VP_PROF_GEMM_FC2, vp::EPI_BIAS_RESID, pk[VP_PROF_GEMM_FC2], c->hid, fc2_w(c, b), fc2_b(c, b), c->x, c->x, M, D, 4 * D, D))) return rc;
     }
     }
     // last_norm, head and decode: the caller's n_in crops (the planes are laid out for the encoder's row count)
     const int nh = n_in, Mh = nh * 192;
     LAUNCH(c, VP_PROF_LAYERNORM, 0.0, 6.0 * Mh * D,
            vp::layernorm_launch(c->dtype, c->x, c->lnf_g, c->lnf_b, c->y, want_tokens ? c->tok : nullptr, Mh, D, c->stream, plane));
-    return head ? head_chunk(c, c->y, nh, c->hm) : VP_OK;
+    return head ? head_chunk(c, c->y, nh, c->hm, pl.head) : VP_OK;
 }
 
-// head of nh crops whose last_norm tokens start at y, with the active head weights (c->w_d1 .. c->w_fin, c->Kp) -> heatmaps [nh, Kp, 64, 48] at hm
-int head_chunk(vp_ctx* c, const uint16_t* y, int nh, float* hm) {
+// head of nh crops whose last_norm tokens start at y, with the active head weights (c->w_d1 .. c->w_fin, c->Kp) -> heatmaps [nh, Kp, 64, 48] at hm, as hp plans it
+int head_chunk(vp_ctx* c, const uint16_t* y, int nh, float* hm, const HeadPlan& hp) {
     const int D = c->D;
     int rc;
     // head: tokens [n,16,12,D] (NHWC view of [n*192, D]) -> [n,32,24,256] -> [n,64,48,256] -> heatmaps [n,Kp,64,48]
-    if ((rc = gemm(c, VP_PROF_GEMM_DECONV, vp::EPI_DECONV, y, c->w_d1, c->b_d1, c->d1, nullptr, nh * 192, 256, 4 * D, 256, 16, 12, D))) return rc;
-    // large batches: the final 1x1 conv rides in deconv2's epilogue (gemm.hip EPI_DECONV_FINAL, bit-identical heatmaps) and the
-    // [n,64,48,256] tensor is never written; small batches keep the two launches on tiles that still fill 256 CUs
-    if (c->fuse_head && c->gemm_variant[VP_PROF_GEMM_DECONV] < 0 && (long)nh * 12 >= 512) {
+    if ((rc = gemm(c, VP_PROF_GEMM_DECONV, vp::EPI_DECONV, hp.deconv1, y, c->w_d1, c->b_d1, c->d1, nullptr, nh * 192, 256, 4 * D, 256, 16, 12, D))) return rc;
+    if (hp.fused) {   // the final 1x1 conv rides in deconv2's epilogue: the [n,64,48,256] tensor is never written
         float* keep = c->hm;   // gemm() hands EPI_DECONV_FINAL c->hm as its heatmap output
         c->hm = hm;
-        rc = gemm(c, VP_PROF_GEMM_DECONV, vp::EPI_DECONV_FINAL, c->d1, c->w_d2, c->b_d2, nullptr, nullptr, nh * 768, 256, 1024, 256, 32, 24, 256);
+        rc = gemm(c, VP_PROF_GEMM_DECONV, vp::EPI_DECONV_FINAL, hp.deconv2, c->d1, c->w_d2, c->b_d2, nullptr, nullptr, nh * 768, 256, 1024, 256, 32, 24, 256);
         c->hm = keep;
         return rc;
     }
-    if ((rc = gemm(c, VP_PROF_GEMM_DECONV, vp::EPI_DECONV, c->d1, c->w_d2, c->b_d2, c->d2, nullptr, nh * 768, 256, 1024, 256, 32, 24, 256))) return rc;
-    if ((rc = gemm(c, VP_PROF_GEMM_FINAL, vp::EPI_HEATMAP, c->d2, c->w_fin, c->b_fin, hm, nullptr, nh * 3072, (int)c->fin_rows, 256, 0))) return rc;
+    if ((rc = gemm(c, VP_PROF_GEMM_DECONV, vp::EPI_DECONV, hp.deconv2, c->d1, c->w_d2, c->b_d2, c->d2, nullptr, nh * 768, 256, 1024, 256, 32, 24, 256))) return rc;
+    if ((rc = gemm(c, VP_PROF_GEMM_FINAL, vp::EPI_HEATMAP, hp.final, c->d2, c->w_fin, c->b_fin, hm, nullptr, nh * 3072, (int)c->fin_rows, 256, 0))) return rc;
     return VP_OK;
 }
 
@@ -431,8 +384,7 @@ int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh
     };
     // a caller's legacy default stream (torch's usual current stream): VP_GRAPH_NULL=1 replays the graph there too (a caller that synchronises after
     // every call pays the 110-290 eager launches' host time); 0 = plain launches (equal when calls are enqueued back to back)
-    static const bool graph_null = [] { const char* e = getenv("VP_GRAPH_NULL"); return e ? atoi(e) != 0 : VP_GRAPH_NULL_DEFAULT; }();
-    if (nb > c->graph_max_n || c->prof != 0 || (c->stream == nullptr && !graph_null)) return eager();
+    if (nb > c->sw.graph_max_n || c->prof != 0 || (c->stream == nullptr && !c->sw.graph_null)) return eager();
     vp_ctx::GraphEntry* ge = nullptr;
     for (auto& g : c->graphs)
         if (g.n == nb && g.fmt == fmt && g.src == d_src && g.wh == d_wh && g.out == d_out && g.expert == c->expert) { ge = &g; break; }
@@ -619,10 +571,6 @@ int stage_frames(vp_ctx* c, const vp_frame* frames, int n_frames, bool on_device
 
 }  // namespace vpi
 
-namespace {
-
-}  // namespace
-
 extern "C" {
 
 int vp_abi_version(void) { return VP_ABI_VERSION; }
@@ -655,12 +603,11 @@ int vp_create(vp_handle* out, const vp_config* cfg) {
     c->dtype = cfg->dtype == VP_DTYPE_BF16 ? vp::DT_BF16 : vp::DT_F16;   // fp8 mode: everything that is not one of the three MXFP8 GEMMs runs as fp16
     c->fp8 = cfg->dtype == VP_DTYPE_FP8;
     c->maxb = cfg->max_batch;
-    apply_gemm_tuning(c);
+    read_switches(c->sw);
     auto bail = [&](int rc) { g_create_error = c->err; vp_destroy(c); return rc; };
     if ((e = hipSetDevice(cfg->device_id)) != hipSuccess) { c->err = hipGetErrorString(e); return bail(VP_ERR_HIP); }
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) { c->err = hipGetErrorString(e); return bail(VP_ERR_HIP); }
     c->own_stream = c->stream;
-    if (const char* f = getenv("VP_CALLER_STREAM")) c->caller_stream_max_n = atoi(f) == 1 ? 16 : atoi(f);   // 0 = always fence against the caller's stream with events
     const size_t B = (size_t)((c->maxb + 3) / 4 * 4);   // workspaces: the encoder may run the next multiple of 4 crops (forward_chunk)
     // fp8 mode: workspaces indexed by token row are sized for the padded row count the MXFP8 GEMM tiles need
     c->Mp = std::max<size_t>((B * 192 + 255) / 256 * 256, 512);
@@ -672,58 +619,15 @@ int vp_create(vp_handle* out, const vp_config* cfg) {
     if ((rc = dalloc(c, &c->wh_stage, B * 2))) return bail(rc);
     if ((rc = dalloc(c, &c->x, M * D))) return bail(rc);
     if ((rc = dalloc(c, &c->y, M * D))) return bail(rc);
-    // switches between SHIPPED, tested code paths (each has a parity test that flips it): standalone LayerNorm passes, one-tile-per-
-    // workgroup wide GEMMs, eager small batches, un-fused head
-    if (const char* f = getenv("VP_FUSE_LN")) c->fuse_ln = atoi(f) != 0;
-    if (const char* f = getenv("VP_PERSIST")) c->persist_gemm = atoi(f) != 0;
-    if (const char* f = getenv("VP_GRAPH")) c->graph_max_n = atoi(f) == 1 ? 16 : atoi(f);   // 0 = off, 1 = default, n > 1: capture chunks of up to n crops
-    if (const char* f = getenv("VP_FUSE_HEAD")) c->fuse_head = atoi(f) != 0;
-    if (const char* f = getenv("VP_FOLD_STATS")) { c->graph_max_n_stats = atoi(f); c->fold_rule = false; }   // an explicit threshold: fold up to that many crops, nowhere else
-    if (const char* f = getenv("VP_BLOCKED_QKV")) c->blocked_qkv = atoi(f) != 0;
-    if (const char* f = getenv("VP_FUSE_QKV_ATTN")) c->fuse_qkv_attn = atoi(f) != 0;
-    if (const char* f = getenv("VP_DECONV_PARITY_FAST")) c->deconv_parity_fast = atoi(f) != 0;
-    if (const char* f = getenv("VP_G8_COST")) c->g8_cost_model = atoi(f) != 0;
-    if (const char* f = getenv("VP_PAD_BATCH")) c->pad_batch = atoi(f) != 0;
-    if (const char* f = getenv("VP_G8_BM192")) c->g8_bm192 = atoi(f);   // mask: 1 = residual GEMMs, 2 = wide GEMMs may take the 192 x 256 tile of the 8-phase kernel (0: never)
-    if (const char* f = getenv("VP_SPLITK")) {   // 0 = off; "fc2:S:variant,proj:S:variant" = override the rule (measurement sweeps)
-        if (!strchr(f, ':')) c->splitk_on = atoi(f) != 0;
-        else {
-            const char* t = f;
-            while (*t) {
-                const int which = !strncmp(t, "fc2:", 4) ? 1 : !strncmp(t, "proj:", 5) ? 0 : -1;
-                if (which < 0) break;
-                t = strchr(t, ':') + 1;
-                int S = 0, v = 0, used = 0;
-                if (sscanf(t, "%d:%d%n", &S, &v, &used) != 2) break;
-                c->splitk_force[which][0] = S; c->splitk_force[which][1] = v;
-                t += used;
-                if (*t == ',') ++t;
-            }
-        }
-    }
-    if (const char* f = getenv("VP_GEMM8")) c->gemm8_mask = atoi(f);   // which GEMMs may take the 8-phase kernel (1 fc2, 2 fc1, 4 qkv, 8 proj; 0 = the 2-phase kernels everywhere)
-#ifdef VP_TOOLS   // development switches of the measurement build (tools/, DESIGN.md section 8)
-    if (const char* f = getenv("VP_BLOCKED_HID")) c->blocked_hid = atoi(f) != 0;
-    if (const char* f = getenv("VP_ORDER")) c->order_mask = atoi(f);
-    if (const char* f = getenv("VP_G8_STAGGER")) c->g8_stagger = atoi(f);
-    if (const char* t = getenv("VP_ABLATE_FAM")) {   // e.g. "2:64,1:64" = non-temporal stores in the qkv and fc1 epilogues
-        int f, b, used = 0;
-        while (sscanf(t, "%d:%d%n", &f, &b, &used) == 2) {
-            if (f >= 0 && f < VP_PROF_COUNT) c->fam_ablate[f] = b;
-            t += used;
-            if (*t == ',') ++t; else break;
-        }
-    }
-#endif
-    if (c->fp8 && !c->fuse_ln) { c->err = "the fp8 mode is built on the fused-LayerNorm path (unset VP_FUSE_LN)"; return bail(VP_ERR_INVALID); }
-    if (c->fuse_ln) {
+    if (c->fp8 && !c->sw.fuse_ln) { c->err = "the fp8 mode is built on the fused-LayerNorm path (unset VP_FUSE_LN)"; return bail(VP_ERR_INVALID); }
+    if (c->sw.fuse_ln) {
         if ((rc = dalloc(c, &c->ln_part, M * (size_t)(D / 64) * 2))) return bail(rc);
         if ((rc = dalloc(c, &c->rowstat, M * 2))) return bail(rc);
     }
     if (c->fp8) {
         if ((rc = dalloc(c, &c->x8, M * D)) || (rc = dalloc(c, &c->xs8, M * (size_t)(D / 32))) || (rc = dalloc(c, &c->hs8, M * (size_t)(4 * D / 32)))) return bail(rc);
         if (hipMemset(c->x, 0, M * D * 4) != hipSuccess) { c->err = "hipMemset"; return bail(VP_ERR_HIP); }   // padding rows of the planes: read by fc2's residual epilogue
-        if (hd == 64 && !getenv("VP_FP8_PROJ16")) {   // VP_FP8_PROJ16=1: attn.proj stays on the fp16 kernels (parity test flips it)
+        if (hd == 64 && !c->sw.fp8_proj16) {   // VP_FP8_PROJ16=1: attn.proj stays on the fp16 kernels (parity test flips it; tile_rules.hip plan_chunk proj_fp8)
             if ((rc = dalloc(c, &c->y8, M * D)) || (rc = dalloc(c, &c->ys8, M * (size_t)(D / 32)))) return bail(rc);
             if (hipMemset(c->y8, 0, M * D) != hipSuccess || hipMemset(c->ys8, 0, M * (size_t)(D / 32)) != hipSuccess) { c->err = "hipMemset"; return bail(VP_ERR_HIP); }   // padding rows: zero codes
         }
@@ -734,7 +638,7 @@ int vp_create(vp_handle* out, const vp_config* cfg) {
     if ((rc = dalloc(c, &c->d2, B * 3072 * 256))) return bail(rc);
     if ((rc = dalloc(c, &c->hm, B * c->Kp * 3072))) return bail(rc);
     if ((rc = dalloc(c, &c->kp, B * c->Kp * 3))) return bail(rc);
-    if (c->fuse_ln && !c->fp8 && c->splitk_on) {
+    if (c->sw.fuse_ln && !c->fp8 && c->sw.splitk_on) {   // (the rows tile_rules.hip plan_chunk assumes)
         c->splitk_rows = (size_t)std::min<int>(c->maxb, SPLITK_MAX_CROPS) * 192;
         if ((rc = dalloc(c, &c->splitk_ws, (size_t)SPLITK_MAX_S * c->splitk_rows * D))) return bail(rc);
     }
@@ -759,7 +663,7 @@ int vp_infer_device_stream(vp_handle c, const void* d_crops, int32_t fmt, int32_
     int rc = check_ready(c, fmt, n, d_crops, d_out, false);
     if (rc) return rc;
     hipStream_t cs = (hipStream_t)caller_stream;
-    if (n > 0 && n <= c->caller_stream_max_n && n <= c->maxb && cs != c->own_stream) {
+    if (n > 0 && n <= c->sw.caller_stream_max_n && n <= c->maxb && cs != c->own_stream) {
         // Small batches: the chunk's launches (or its hipGraph) go onto the caller's stream itself -- in order with its producers and consumers by construction, no
         // cross-stream dependency per call (two of them cost ~0.1 ms of a 0.6-2.4 ms step: profiles/small_batch_r5.txt).  ev_sw, recorded behind the launches, is
         // what the next call on any other stream (and vp_synchronize / vp_destroy) waits for.
@@ -1088,7 +992,7 @@ int vp_infer_experts(vp_handle c, const void* crops, int32_t fmt, int32_t n, con
                     const int s0 = seg_s[s], cnt = seg_s[s + 1] - s0;
                     use_expert(c, seg_e[s]);
                     float* hm = c->hm + (size_t)s0 * c->Kmax * 3072;
-                    if ((rc = head_chunk(c, c->y + (size_t)s0 * 192 * D, cnt, hm))) return rc;
+                    if ((rc = head_chunk(c, c->y + (size_t)s0 * 192 * D, cnt, hm, plan_head(c->sw, D, cnt, c->fin_rows)))) return rc;
                     LAUNCH(c, VP_PROF_DECODE, 0.0, 4.0 * cnt * c->Kp * 3072.0 + 12.0 * cnt * c->Kp,
                            vp::decode_launch(hm, d_wh ? d_wh + 2 * (size_t)s0 : nullptr, c->kp + (size_t)s0 * c->Kmax * 3, cnt, c->Kp, c->stream));
                 }

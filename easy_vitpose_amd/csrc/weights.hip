@@ -83,8 +83,10 @@ size_t pad128(size_t n) { return (n + 255) / 256 * 256; }
 // the hi and lo products of the SAME output columns.  The GEMM is HBM-bound on its A operand, so the doubled MFMA
 // work is free, and the final layer's weight rounding (9 % of the heatmap error variance, tests/precision_budget.py)
 // disappears.  Physical rows: 32 * ceil(Kp / 16).
+size_t final_rows(size_t kp) { return (kp + 15) / 16 * 32; }
+
 int upload_final(vp_ctx* c, uint16_t** dst, const float* src, size_t kp, size_t cols, size_t* rows_phys) {
-    const size_t groups = (kp + 15) / 16, rows = groups * 32, rows_pad = pad128(rows);
+    const size_t rows = final_rows(kp), rows_pad = pad128(rows);
     std::vector<uint16_t> tmp(rows_pad * cols, 0);
     for (size_t n = 0; n < kp; ++n)
         for (size_t k = 0; k < cols; ++k) {
@@ -320,12 +322,12 @@ int vp_load_weights(vp_handle c, const vp_tensor_desc* tensors, int32_t n_tensor
         if (c->fp8) {
             if ((rc = upload_fp8_rows(c, &b.w_qkv8, &b.ws_qkv, &b.b_qkv, wq, bq, g1, be1, 3 * (size_t)D, D))) return rc;
             if ((rc = upload_fp8_rows(c, &b.w_fc18, &b.ws_fc1, &b.b_fc1, w1, b1, g2, be2, 4 * (size_t)D, D))) return rc;
-        } else if (c->fuse_ln) {
+        } else if (c->sw.fuse_ln) {
             if ((rc = upload_ln_folded(c, &b.w_qkv, &b.s_qkv, &b.b_qkv, wq, bq, g1, be1, 3 * (size_t)D, D))) return rc;
-            if (c->fuse_qkv_attn && D / c->heads == 64) {   // head-major copies for the fused qkv + attention kernel
+            if (c->sw.fuse_qkv_attn && D / c->heads == 64) {   // head-major copies for the fused qkv + attention kernel
                 if ((rc = dalloc(c, &b.w_qkvh, 3 * (size_t)D * D)) || (rc = dalloc(c, &b.b_qkvh, 3 * (size_t)D)) || (rc = dalloc(c, &b.s_qkvh, 3 * (size_t)D))) return rc;
                 HIPCHK(c, vp::qkv_head_major_launch(b.w_qkv, b.b_qkv, b.s_qkv, b.w_qkvh, b.b_qkvh, b.s_qkvh, D, D, nullptr));
-            } else if (c->fuse_qkv_attn && c->heads * 80 == D && D % 128 == 0) {   // head dim 80 (ViTPose-H): [q_h | k_h | v_h | 16 zero rows] per head (gemm8.hip EPI_QKV_ATTN)
+            } else if (c->sw.fuse_qkv_attn && c->heads * 80 == D && D % 128 == 0) {   // head dim 80 (ViTPose-H): [q_h | k_h | v_h | 16 zero rows] per head (gemm8.hip EPI_QKV_ATTN)
                 const size_t rows = (size_t)c->heads * 256;
                 if ((rc = dalloc(c, &b.w_qkvh, rows * D)) || (rc = dalloc(c, &b.b_qkvh, rows)) || (rc = dalloc(c, &b.s_qkvh, rows))) return rc;
                 HIPCHK(c, vp::qkv_head_major80_launch(b.w_qkv, b.b_qkv, b.s_qkv, b.w_qkvh, b.b_qkvh, b.s_qkvh, D, D, c->heads, nullptr));

@@ -338,6 +338,15 @@ VP_API int vp_dbg_run_batch(int32_t n, int32_t D, int32_t limit);
  * (32 / 64 / 96 / 192-row tiles always; 128 / 256-row tiles where every change is a multiple of 2 / 4 crops), else the crop-aligned fallback (18 = the 8-phase
  * 192 x 256 tile, 11 = the 2-phase 192 x 128 residual tile). */
 VP_API int vp_dbg_expert_tile(int32_t variant, int32_t M, int32_t N, int32_t gemm8_ok, const int32_t* bounds, int32_t n_bounds);
+/* HOST ONLY: the plan a handle of *cfg runs for a chunk of n crops (1 <= n <= max_batch; one expert), with the switches vp_create would read from the
+ * environment now.  Writes min(cap, 55) ints to out and returns 55 (VP_ERR_INVALID on bad arguments):
+ *   [0] crops the encoder runs (>= n: padding crops repeat the last one)   [1] / [2] attn.qkv / mlp.fc1 merge the LayerNorm statistics themselves
+ *   [3] qkv path: 0 = attn.qkv GEMM + attention kernel, 1 = fused kernel (head dim 64), 2 = fused 8-phase tile (head dim 80)
+ *   [4] attention on three workgroups per (crop, head)   [5] deconv2 + final conv fused   [6] fp8 mode: attn.proj on the MXFP8 kernel
+ *   then 8 GEMMs -- patch embed, attn.qkv, attn.proj, mlp.fc1, mlp.fc2, deconv1, deconv2, final conv (unused when [5]) -- of 6 ints each:
+ *   variant (gemm.hip Cfg id; 16 / 17 / 18 = the 8-phase 256 x 256 / 256 x 192 / 192 x 256 tile, on the MXFP8 kernel for the fp8 GEMMs), tile-order group,
+ *   persistent workgroups, start stagger, split-K ranges S (1 = one launch), Cfg id of the partial products. */
+VP_API int vp_dbg_chunk_plan(const vp_config* cfg, int32_t n, int32_t* out, int32_t cap);
 /* The two-phase schedule of a group call -- HOST ONLY, stub members: the order in which group_run would submit to (+ (member + 1)) and
  * wait for (- (member + 1)) its members for n crops on w devices of max_batch maxb.  Within every round all submissions precede the
  * first wait: no member's enqueue waits for another member's compute.  Returns the trace length (also beyond `cap`); < 0 on bad arguments. */

@@ -95,3 +95,45 @@ def dark_conditioned(heatmaps: np.ndarray, vmin: float = 0.05) -> np.ndarray:
             dxy = 0.5 * (l[5] - l[1] - l[3] + 2 * l[0] - l[2] - l[4] + l[6])
             out[i, j] = dxx < -0.02 and dyy < -0.02 and dxx * dyy - dxy * dxy > 0.25 * dxx * dyy
     return out
+
+
+# ------------------------------------------------------------------ the chunk plan (vp_dbg_chunk_plan, include/vitpose_hip.h)
+PLAN_GEMMS = ('patch', 'qkv', 'proj', 'fc1', 'fc2', 'deconv1', 'deconv2', 'final')
+PICK_FIELDS = ('variant', 'group_m', 'persist', 'stagger', 'splitk', 'splitk_variant')
+# gemm.hip Cfg id -> TileCfg parameters, as the launch code names the kernel (vp_profile_kernel)
+TILE_CFGS = {1: '128, 128, 64, 64, 64, 2, 1, 0', 3: '256, 256, 64, 128, 64, 2, 1, 0', 8: '192, 128, 64, 96, 64, 2, 1, 0', 9: '64, 64, 64, 32, 32, 2, 0, 0',
+             11: '192, 128, 64, 48, 64, 2, 1, 0', 12: '64, 64, 64, 32, 32, 4, 0, 0', 15: '128, 64, 64, 64, 32, 3, 0, 0', 20: '192, 128, 64, 48, 64, 3, 1, 0',
+             30: '64, 64, 64, 32, 32, 6, 6, 0', 31: '32, 64, 64, 16, 32, 6, 6, 0', 41: '96, 64, 64, 48, 32, 4, 0, 0'}
+
+
+def chunk_plan(shape, dtype: str, max_batch: int, n: int) -> dict:
+    """The plan a handle of `shape` runs for a chunk of n crops, decoded: top-level fields + one pick per GEMM."""
+    import ctypes as C
+    from easy_vitpose_amd import _capi as capi
+    lib = capi.load_library()
+    cfg = capi.vp_config(shape.embed_dim, shape.depth, shape.num_heads, shape.num_keypoints, capi.DTYPES[dtype], 0, max_batch)
+    out = (C.c_int32 * 64)()
+    count = lib.vp_dbg_chunk_plan(C.byref(cfg), n, out, 64)
+    assert count == 7 + 6 * len(PLAN_GEMMS), count
+    v = list(out[:count])
+    plan = dict(zip(('n', 'fold1', 'fold2', 'qkv_path', 'attn_qsplit', 'fused_head', 'proj_fp8'), v[:7]))
+    plan['gemm'] = {g: dict(zip(PICK_FIELDS, v[7 + 6 * i:13 + 6 * i])) for i, g in enumerate(PLAN_GEMMS)}
+    return plan
+
+
+def planned_kernels(plan: dict, fp8: bool = False) -> dict:
+    """vp_profile_kernel family -> a substring of the kernel name its LAST launch must carry under `plan`."""
+    def name(pick, on_fp8=False):
+        v = pick['variant']
+        if v in (16, 17, 18):
+            return f"{'gemm8f_kernel' if on_fp8 else 'gemm8_kernel'}<", f"G8<{192 if v == 17 else 256}, {192 if v == 18 else 256}>"
+        if pick['splitk'] > 1:
+            return 'gemm_kernel<', f"TileCfg<{TILE_CFGS[pick['splitk_variant']]}>> x split-K {pick['splitk']} + splitk_reduce_kernel"
+        return ('gemm_persist_kernel<' if pick['persist'] else 'gemm_kernel<'), f'TileCfg<{TILE_CFGS[v]}>'
+    g = plan['gemm']
+    out = {'gemm_patch': name(g['patch']), 'gemm_proj': name(g['proj'], fp8 and plan['proj_fp8']),
+           'gemm_fc1': name(g['fc1'], fp8), 'gemm_fc2': name(g['fc2'], fp8), 'gemm_deconv': name(g['deconv2'])}
+    out['gemm_qkv'] = {0: name(g['qkv'], fp8), 1: ('qkvattn_kernel<', ''), 2: ('gemm8_kernel<', ', 9, G8<256, 192>')}[plan['qkv_path']]
+    if not plan['fused_head']:
+        out['gemm_final'] = name(g['final'])
+    return out

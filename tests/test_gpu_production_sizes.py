@@ -25,7 +25,7 @@ from easy_vitpose_amd import VitPoseHip
 from easy_vitpose_amd import _capi as capi
 from easy_vitpose_amd.configs import model_shape
 from easy_vitpose_amd.synth import synthetic_crops, synthetic_state_dict
-from helpers import CONF_TOL, KP_TOL_PX, round_to
+from helpers import CONF_TOL, KP_TOL_PX, chunk_plan, planned_kernels, round_to
 from oracle import vitpose_cpu as O
 
 pytestmark = pytest.mark.gpu
@@ -99,6 +99,23 @@ def test_production_batch_under_assertion(golden_dir, variant, dataset, B, n_ora
           f'{d2.size} joints: coordinate max err {d2.max():.4f} px, confidence max err {c2.max():.3e}')
     assert err.max() < HM_MAX_ERR and np.sqrt((err ** 2).mean()) < HM_RMS_ERR
     assert d2.max() < KP_TOL_PX and c2.max() < CONF_TOL
+
+
+@pytest.mark.parametrize('variant,dataset', [('s', 'coco'), ('b', 'coco'), ('l', 'coco_25'), ('h', 'wholebody')])
+def test_every_family_runs_the_kernel_the_chunk_plan_names(variant, dataset):
+    """The chunk plan (tile_rules.hip plan_chunk through vp_dbg_chunk_plan) against what the handle launches: at the CASES batches and at 1, 2, 8, 9, 17, 33 and
+    65 crops, the last launch of every GEMM family ran on the kernel and tile the plan names."""
+    sizes = sorted({1, 2, 8, 9, 17, 33, 65} | {c[2] for c in CASES if c[0] == variant})
+    shp = model_shape(variant, dataset)
+    eng = VitPoseHip(shp, synthetic_state_dict(shp, 0), dtype='fp16', device_id=0, max_batch=sizes[-1])
+    crops = synthetic_crops(sizes[-1], 7, 'noise')
+    for n in sizes:
+        eng.infer(crops[:n])
+        plan = chunk_plan(shp, 'fp16', sizes[-1], n)
+        for fam, (kernel, tile) in planned_kernels(plan).items():
+            got = eng.profile_kernel(fam)
+            assert got.startswith(kernel) and tile in got, f'{variant} @ {n} crops: {fam} ran on {got!r}, the plan names {kernel}...{tile}'
+    eng.close()
 
 
 # ------------------------------------------------------------------ op level: GEMM configurations at D = 1024 / 1280

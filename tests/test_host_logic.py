@@ -350,6 +350,95 @@ def test_gemm8_tile_selection_over_every_batch_size():
     assert pick(12096, 1024, 0, 0)[0] == 0 and pick(12096, 1024, 0, 2)[0] == 0 and pick(12096, 4096, 1, 1)[0] == 0   # the mask bits: 1 = residual, 2 = wide
 
 
+def _plan_walk(variant, max_batch, dtype='fp16'):
+    from helpers import chunk_plan
+    shape = configs.model_shape(variant, 'coco')
+    return {n: chunk_plan(shape, dtype, max_batch, n) for n in range(1, max_batch + 1)}
+
+
+@pytest.mark.parametrize('max_batch', [256, 8])
+@pytest.mark.parametrize('variant', ['s', 'b', 'l', 'h'])
+def test_chunk_plan_over_every_batch_size(variant, max_batch, monkeypatch):
+    """The plan of a chunk (tile_rules.hip plan_chunk through the host-only tap vp_dbg_chunk_plan) walked over every batch size: it combines the single rules
+    the way the orchestration executes them.  A consumer that folds the LayerNorm statistics is never on an 80 KiB-ring tile (8, 11) or the 8-phase kernel;
+    the encoder batch is vp_dbg_run_batch's; every GEMM is on the tile its single rule names (the 8-phase pick where it qualifies, else the 2-phase rule);
+    split-K exactly where pick_splitk says; and VP_SPLITK=0, VP_PAD_BATCH=0, VP_GEMM8=0 change the plan as documented."""
+    lib = capi.load_library()
+    shape = configs.model_shape(variant, 'coco')
+    D, heads, kp = shape.embed_dim, shape.num_heads, shape.num_keypoints
+    fin_rows = -(-kp // 16) * 32
+    tiles, gm, sv = C.c_int32(), C.c_int32(), C.c_int32()
+    g8 = {16, 17, 18}
+    plans = _plan_walk(variant, max_batch)
+    for n_in, p in plans.items():
+        g = p['gemm']
+        n = p['n']
+        M = 192 * n
+        assert n == lib.vp_dbg_run_batch(n_in, D, -(-max_batch // 4) * 4), (n_in, n)
+        for fold, fam in ((p['fold1'], 'qkv'), (p['fold2'], 'fc1')):
+            if fold and not (fam == 'qkv' and p['qkv_path']):
+                assert g[fam]['variant'] not in {8, 11} | g8 and not g[fam]['persist'], (n_in, fam, g[fam])
+        assert not (p['fold1'] and p['qkv_path']), n_in                                # the fused qkv + attention kernels read rowstat
+        assert p['qkv_path'] in ((0, 1) if D // heads == 64 else (0, 2) if D // heads == 80 else (0,))
+        assert p['attn_qsplit'] == (n * heads <= 128) and p['proj_fp8'] == 0
+        for fam, epi, N, K, bit in (('qkv', 0, 3 * D, D, 4), ('fc1', 1, 4 * D, D, 2), ('proj', 6, D, D, 0), ('fc2', 6, D, 4 * D, 1), ('patch', 7, D, 768, 0)):
+            pick = g[fam]
+            v8 = lib.vp_dbg_gemm8_pick(M, N, int(epi < 2), 3, C.byref(tiles)) if bit else 0
+            v2 = lib.vp_dbg_gemm2_pick(epi, M, N, K, C.byref(gm))
+            folded = (fam == 'qkv' and p['fold1']) or (fam == 'fc1' and p['fold2'])
+            if v8 and folded:
+                assert (pick['variant'], pick['group_m']) == (8, 8), (n_in, fam, pick)
+            elif v8:
+                assert (pick['variant'], pick['group_m']) == (v8, {'qkv': 4, 'fc2': 2}.get(fam, 8)), (n_in, fam, pick, v8)
+            else:
+                assert (pick['variant'], pick['group_m']) == (v2, gm.value), (n_in, fam, pick, v2)
+                assert pick['persist'] == (epi < 2 and v2 == 8 and not folded and n * (N // 128) >= 1024), (n_in, fam, pick)
+            S = lib.vp_dbg_splitk_pick(M, N, K, C.byref(sv)) if fam in ('proj', 'fc2') and not v8 and n <= min(max_batch, 32) else 1
+            assert (pick['splitk'], pick['splitk_variant']) == ((S, sv.value) if S > 1 else (1, 0)), (n_in, fam, pick, S)
+        fused = n_in * 12 >= 512
+        assert p['fused_head'] == fused
+        assert g['deconv1']['variant'] == lib.vp_dbg_gemm2_pick(4, 192 * n_in, 256, 4 * D, None)
+        assert g['deconv2']['variant'] == (3 if fused else lib.vp_dbg_gemm2_pick(4, 768 * n_in, 256, 1024, None))
+        assert fused or g['final']['variant'] == lib.vp_dbg_gemm2_pick(5, 3072 * n_in, fin_rows, 256, None)
+    # the switches: VP_SPLITK=0 removes every split and nothing else; VP_PAD_BATCH=0 keeps the chunk's batch; VP_GEMM8=0 keeps every GEMM off the 8-phase kernel
+    monkeypatch.setenv('VP_SPLITK', '0')
+    assert _plan_walk(variant, max_batch) == {n: {**p, 'gemm': {k: {**v, 'splitk': 1, 'splitk_variant': 0} for k, v in p['gemm'].items()}} for n, p in plans.items()}
+    monkeypatch.delenv('VP_SPLITK')
+    monkeypatch.setenv('VP_PAD_BATCH', '0')
+    unpadded = _plan_walk(variant, max_batch)
+    for n_in, p in unpadded.items():
+        assert p['n'] == n_in
+        if plans[n_in]['n'] == n_in:
+            assert p == plans[n_in], n_in
+    monkeypatch.delenv('VP_PAD_BATCH')
+    monkeypatch.setenv('VP_GEMM8', '0')
+    for n_in, p in _plan_walk(variant, max_batch).items():
+        assert p['n'] == n_in and all(v['variant'] not in g8 for v in p['gemm'].values()), n_in
+        if not any(v['variant'] in g8 for v in plans[n_in]['gemm'].values()):
+            assert p == plans[n_in], n_in
+
+
+def test_chunk_plan_fp8_and_bad_arguments():
+    """fp8 handles: qkv / fc1 / fc2 (and attn.proj at head dim 64) on the MXFP8 kernel's 256-row tiles, no padded batch, no split-K; bad arguments are refused."""
+    from helpers import chunk_plan
+    for variant in ('b', 'l', 'h'):
+        shape = configs.model_shape(variant, 'coco')
+        for n in (1, 2, 7, 8, 33, 65, 128):
+            p = chunk_plan(shape, 'fp8', 128, n)
+            assert p['n'] == n and p['proj_fp8'] == (shape.embed_dim // shape.num_heads == 64) and p['qkv_path'] == 0
+            fams = ('qkv', 'fc1', 'fc2') + (('proj',) if p['proj_fp8'] else ())
+            for fam in fams:
+                assert p['gemm'][fam]['variant'] in (16, 17) and p['gemm'][fam]['splitk'] == 1
+            assert p['gemm']['qkv']['variant'] == 16 and p['gemm']['fc1']['variant'] == 16
+            assert all(v['splitk'] == 1 for v in p['gemm'].values())
+    lib = capi.load_library()
+    out = (C.c_int32 * 64)()
+    good = capi.vp_config(768, 12, 12, 17, 0, 0, 8)
+    assert lib.vp_dbg_chunk_plan(C.byref(good), 8, out, 64) == 55 and lib.vp_dbg_chunk_plan(C.byref(good), 8, None, 0) == 55
+    for cfg, n in ((good, 0), (good, 9), (capi.vp_config(768, 12, 7, 17, 0, 0, 8), 1), (capi.vp_config(768, 12, 12, 17, 0, 0, 0), 1)):
+        assert lib.vp_dbg_chunk_plan(C.byref(cfg), n, out, 64) == capi.VP_ERR_INVALID
+
+
 @pytest.mark.parametrize('n', [0, 1, 7, 64, 513])
 @pytest.mark.parametrize('w', [1, 2, 8])
 @pytest.mark.parametrize('maxb', [1, 8, 64])
