@@ -29,7 +29,7 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_dbg_gemm', 'vp_dbg_attention', 'vp_dbg_layernorm', 'vp_dbg_deconv', 'vp_dbg_gemm_case', 'vp_dbg_crop_prep',
            'vp_dbg_group_plan', 'vp_dbg_group_trace', 'vp_dbg_gemm8_pick', 'vp_dbg_gemm2_pick', 'vp_dbg_splitk_pick', 'vp_dbg_run_batch', 'vp_dbg_fp8_gemm', 'vp_dbg_mx_gemm', 'vp_dbg_host_e4m3', 'vp_dbg_gemm_fp8_case', 'vp_dbg_qkvattn',
            'vp_expert_info', 'vp_set_expert', 'vp_infer_experts', 'vp_dbg_expert_tile', 'vp_infer_frames', 'vp_dbg_frame_plan',
-           'vp_dbg_chunk_plan']
+           'vp_dbg_chunk_plan', 'vp_infer_boxes_stream', 'vp_dbg_box_geometry']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -105,6 +105,9 @@ def load_library():
     lib.vp_infer_frame.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.vp_infer_frames.argtypes = [H, C.POINTER(vp_frame), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.vp_dbg_frame_plan.argtypes = [C.POINTER(vp_frame), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.vp_infer_boxes_stream.argtypes = [H, C.POINTER(vp_frame), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vp_dbg_box_geometry.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.vp_dbg_crop_prep.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.vp_infer_heatmaps.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.vp_infer_tokens.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]

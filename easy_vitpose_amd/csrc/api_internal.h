@@ -135,7 +135,8 @@ struct vp_ctx {
     // small batches: the whole forward + decode of a chunk captured once per (n, input format, source pointer) into a hipGraph and
     // replayed (170+ launches of a few microseconds each are launch-bound below ~16 crops); VP_GRAPH=0 disables
     struct GraphEntry { hipGraphExec_t exec = nullptr; int n = 0, fmt = -1, seen = 0; bool no_graph = false; const void* src = nullptr; const int32_t* wh = nullptr; float* out = nullptr;
-                        int expert = 0; };   // expert: a ViTPose+ handle's active expert is baked into the captured launches (fc2 weights, head, K)
+                        int expert = 0;     // expert: a ViTPose+ handle's active expert is baked into the captured launches (fc2 weights, head, K)
+                        const int32_t* post = nullptr; };   // vp_infer_boxes_stream: the frame-offset kernel after the decode (its aux buffer; null: none)
     GraphEntry graphs[4];
     int graph_victim = 0;
     // split-K workspace of the residual GEMMs of small batches: fp32 partial products [S][M][D] of up to splitk_rows token rows (none when Switches::splitk_on is off)
@@ -152,6 +153,7 @@ struct vp_ctx {
     uint8_t* frame_stage = nullptr;   // staging arena of vp_infer_frames / vp_infer_frame: the row band of every host frame of the current call
     size_t frame_cap = 0;
     vp::CropRec* crecs = nullptr;     // per-crop source + geometry of the current chunk [max_batch]
+    int32_t* box_aux = nullptr;       // vp_infer_boxes_stream: per box of the current chunk (y0 - top_pad, x0 - left_pad, status, 0) [max_batch][4]
     // ViTPose+ (multi-dataset "mixture of experts") handle, vp_load_weights on a state dict with backbone.blocks.*.mlp.experts.*: mlp.fc2 of block l is one full
     // [D, 4D] matrix + [D] bias per expert (the split model's: shared rows then the expert's P rows), blocks[l].w_fc2 / b_fc2 point at expert 0 and expert e lies
     // e * fc2_w_stride / fc2_b_stride elements behind; one keypoint head per expert.  `expert` = the active one (vp_set_expert): its fc2 slice, its head and its
@@ -244,6 +246,9 @@ int frame_plan(const vp_frame* frames, int n_frames, const int32_t* p9, int n, i
 // crops), device frames are read in place (checked to be device memory of the handle's device first).  recs[n] (host), enqueued on c->stream
 int stage_frames(vp_ctx* c, const vp_frame* frames, int n_frames, bool on_device, const int32_t* p9, int n, const int32_t* bands,
                  std::vector<vp::CropRec>& recs);
+// vp_infer_boxes_stream / vp_dbg_box_geometry (HOST ONLY): the host arguments of a boxes call (sizes of every frame, row stride, pad, counts).
+// VP_OK or VP_ERR_INVALID with the reason in *why
+int box_args(int n_frames, const int32_t* frame_hw, int hw_stride, int row_stride, int n, int pad, std::string* why);
 
 #define LAUNCH(c, fam, flops, bytes, expr)   \
     do {                                     \

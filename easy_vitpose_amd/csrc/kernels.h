@@ -208,6 +208,20 @@ struct CropRec {
 // recs: device CropRec [n] -> crops u8 [n,256,192,3]
 hipError_t crop_resize_launch(const CropRec* recs, uint8_t* out, int n, hipStream_t s);
 
+// vp_infer_boxes_stream (boxes.hip): frames [f0, f0 + count) of the call's table, passed by kernel argument (2 KiB)
+constexpr int BOX_FRAMES_PER_LAUNCH = 128;
+struct BoxFrames {
+    const uint8_t* data[BOX_FRAMES_PER_LAUNCH];
+    int32_t h[BOX_FRAMES_PER_LAUNCH], w[BOX_FRAMES_PER_LAUNCH];
+    int32_t f0, count, n_frames;
+};
+// boxes xyxy (row i at xyxy + i * row_stride) + frame index [n] (NULL: frame 0) -> crop records, decode sizes wh [n, 2] = (pw, ph),
+// aux [n, 4] = (y0 - top_pad, x0 - left_pad, status, 0); optional p9_out [n, 9] (frames_crop_params rows) and status_out [n]
+hipError_t box_geometry_launch(const BoxFrames& fr, const float* xyxy, int row_stride, const int32_t* frame_idx, int n, int pad, const uint8_t* zero_px,
+                               CropRec* recs, int32_t* wh, int32_t* aux, int32_t* p9_out, int32_t* status_out, hipStream_t s);
+// decoded keypoints [n, K, 3] in padded-crop pixels -> frame pixels (aux as above; status != 0: all zero)
+hipError_t box_offsets_launch(const int32_t* aux, float* out, int n, int K, hipStream_t s);
+
 // --------------------------------------------------------------------- decode
 // heatmaps fp32 [N, K, 64, 48] -> out fp32 [N, K, 3] (y, x, conf); org_wh int32 [N,2] or null
 hipError_t decode_launch(const float* hm, const int32_t* org_wh, float* out, int N, int K, hipStream_t s);

@@ -2,6 +2,7 @@
 // context + weight packer + forward orchestration.  No CPU fallback anywhere:
 // every compute entry point needs a HIP device and fails with VP_ERR_HIP otherwise.
 #include "api_internal.h"
+#include "boxgeom.h"
 
 using namespace vpi;
 
@@ -373,21 +374,29 @@ int decode_chunk(vp_ctx* c, const int32_t* d_wh, float* d_out, int n) {
     return VP_OK;
 }
 
+// vp_infer_boxes_stream: keypoints in padded-crop pixels -> frame pixels, zero rows for invalid boxes (aux = c->box_aux)
+int offsets_chunk(vp_ctx* c, const int32_t* aux, float* d_out, int n) {
+    LAUNCH(c, VP_PROF_DECODE, 0.0, 24.0 * n * c->Kp + 16.0 * n, vp::box_offsets_launch(aux, d_out, n, c->Kp, c->stream));
+    return VP_OK;
+}
+
 // forward + decode of one chunk.  Small chunks (<= graph_max_n crops, profiling off) are launch-bound -- ~110-290 launches of a few
 // microseconds each -- so the second time the same (n, format, buffers) combination is seen the chunk is captured into a hipGraph
-// and from then on replayed with one hipGraphLaunch.
-int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh, float* d_out) {
+// and from then on replayed with one hipGraphLaunch.  post != null: the frame-offset kernel of vp_infer_boxes_stream follows the decode
+// (inside the graph; `post` is part of the key).
+int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh, float* d_out, const int32_t* post = nullptr) {
     int rc;
     auto eager = [&]() -> int {
         if ((rc = forward_chunk(c, d_src, fmt, nb, false))) return rc;
-        return decode_chunk(c, d_wh, d_out, nb);
+        if ((rc = decode_chunk(c, d_wh, d_out, nb))) return rc;
+        return post ? offsets_chunk(c, post, d_out, nb) : VP_OK;
     };
     // a caller's legacy default stream (torch's usual current stream): VP_GRAPH_NULL=1 replays the graph there too (a caller that synchronises after
     // every call pays the 110-290 eager launches' host time); 0 = plain launches (equal when calls are enqueued back to back)
     if (nb > c->sw.graph_max_n || c->prof != 0 || (c->stream == nullptr && !c->sw.graph_null)) return eager();
     vp_ctx::GraphEntry* ge = nullptr;
     for (auto& g : c->graphs)
-        if (g.n == nb && g.fmt == fmt && g.src == d_src && g.wh == d_wh && g.out == d_out && g.expert == c->expert) { ge = &g; break; }
+        if (g.n == nb && g.fmt == fmt && g.src == d_src && g.wh == d_wh && g.out == d_out && g.expert == c->expert && g.post == post) { ge = &g; break; }
     if (ge && ge->exec) {
         const hipError_t el = hipGraphLaunch(ge->exec, c->stream);
         if (el == hipSuccess) return VP_OK;
@@ -405,7 +414,7 @@ int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh
             hipGraphExecDestroy(ge->exec);
             ge->exec = nullptr;
         }
-        ge->n = nb; ge->fmt = fmt; ge->src = d_src; ge->wh = d_wh; ge->out = d_out; ge->expert = c->expert; ge->seen = 1; ge->no_graph = false;
+        ge->n = nb; ge->fmt = fmt; ge->src = d_src; ge->wh = d_wh; ge->out = d_out; ge->expert = c->expert; ge->post = post; ge->seen = 1; ge->no_graph = false;
         return eager();
     }
     // second sighting: capture.  Any failure of the capture machinery (not of the launches themselves) marks the key "do not
@@ -417,6 +426,7 @@ int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh
     if (e != hipSuccess) { c->stream = target; (void)hipGetLastError(); ge->no_graph = true; return eager(); }
     rc = forward_chunk(c, d_src, fmt, nb, false);
     if (!rc) rc = decode_chunk(c, d_wh, d_out, nb);
+    if (!rc && post) rc = offsets_chunk(c, post, d_out, nb);
     e = hipStreamEndCapture(c->stream, &graph);
     c->stream = target;
     if (rc) {   // a launch failed INSIDE the capture (e.g. a capture-illegal call): nothing has executed -- drop the graph, clear the sticky
@@ -467,6 +477,39 @@ int check_ready(vp_ctx* c, int fmt, int n, const void* p0, const void* p1, bool 
     hipError_t e = hipSetDevice(c->cfg.device_id);
     if (e != hipSuccess) return fail(c, VP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
     return adopt_own ? adopt_stream(c, c->own_stream) : VP_OK;   // every entry but the caller-stream path works on the handle's own stream
+}
+
+// The ordering of the caller-stream entries (vp_infer_device_stream, vp_infer_boxes_stream): `chunks` enqueues the call's work on c->stream.
+// Batches of 1 .. caller_stream_max_n crops (<= max_batch) run ON the caller's stream -- in order with its producers and consumers by construction,
+// no cross-stream dependency per call (two of them cost ~0.1 ms of a 0.6-2.4 ms step: profiles/small_batch_r5.txt); ev_sw, recorded behind the
+// launches, is what the next call on any other stream (and vp_synchronize / vp_destroy) waits for.  Larger batches run on the handle's own
+// stream, fenced against the caller's with ev_in / ev_out.
+template <class Chunks> int caller_ordered(vp_ctx* c, hipStream_t cs, int n, Chunks chunks) {
+    int rc;
+    if (n > 0 && n <= c->sw.caller_stream_max_n && n <= c->maxb && cs != c->own_stream) {
+        if ((rc = adopt_stream(c, cs))) return rc;
+        c->stream = cs;
+        rc = chunks();
+        c->stream = c->own_stream;
+        if (!c->ev_sw && hipEventCreateWithFlags(&c->ev_sw, hipEventDisableTiming) != hipSuccess) return fail(c, VP_ERR_HIP, "hipEventCreateWithFlags(ev_sw)");
+        const hipError_t er = hipEventRecord(c->ev_sw, cs);   // also when rc != 0: part of the chunk may be enqueued
+        c->foreign_pending = true;
+        c->last_stream_id = (const void*)cs;
+        if (rc) return rc;
+        if (er != hipSuccess) return fail(c, VP_ERR_HIP, std::string("hipEventRecord(ev_sw): ") + hipGetErrorString(er));
+        return VP_OK;
+    }
+    if ((rc = adopt_stream(c, c->own_stream))) return rc;
+    if (!c->ev_in) HIPCHK(c, hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
+    if (!c->ev_out) HIPCHK(c, hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));
+    // everything the caller enqueued on its stream so far (the producers of the inputs) happens before the library's kernels ...
+    HIPCHK(c, hipEventRecord(c->ev_in, cs));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in, 0));
+    if ((rc = chunks())) return rc;
+    // ... and whatever the caller enqueues afterwards (consumers of the outputs) happens after them
+    HIPCHK(c, hipEventRecord(c->ev_out, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(cs, c->ev_out, 0));
+    return VP_OK;
 }
 
 }  // namespace
@@ -569,6 +612,20 @@ int stage_frames(vp_ctx* c, const vp_frame* frames, int n_frames, bool on_device
     return VP_OK;
 }
 
+int box_args(int n_frames, const int32_t* frame_hw, int hw_stride, int row_stride, int n, int pad, std::string* why) {
+    auto bad = [&](const std::string& m) { if (why) *why = m; return VP_ERR_INVALID; };
+    if (n < 0) return bad("negative box count");
+    if (row_stride < 4) return bad("row_stride " + std::to_string(row_stride) + " < 4 (x1, y1, x2, y2 per row)");
+    if (pad < 0) return bad("negative pad");
+    if (n > 0 && n_frames <= 0) return bad("boxes given but no frames");
+    for (int f = 0; f < n_frames && n > 0; ++f) {   // every frame of the table: the frame indices live on the device
+        const int32_t h = frame_hw[(size_t)f * hw_stride], w = frame_hw[(size_t)f * hw_stride + 1];
+        if (h <= 0 || w <= 0 || h > vp::BOX_MAX_SIDE || w > vp::BOX_MAX_SIDE)
+            return bad("frame " + std::to_string(f) + " has a size outside [1, 2^24]");
+    }
+    return VP_OK;
+}
+
 }  // namespace vpi
 
 extern "C" {
@@ -662,34 +719,14 @@ int vp_infer_device(vp_handle c, const void* d_crops, int32_t fmt, int32_t n, co
 int vp_infer_device_stream(vp_handle c, const void* d_crops, int32_t fmt, int32_t n, const int32_t* d_org_wh, float* d_out, void* caller_stream) {
     int rc = check_ready(c, fmt, n, d_crops, d_out, false);
     if (rc) return rc;
-    hipStream_t cs = (hipStream_t)caller_stream;
-    if (n > 0 && n <= c->sw.caller_stream_max_n && n <= c->maxb && cs != c->own_stream) {
-        // Small batches: the chunk's launches (or its hipGraph) go onto the caller's stream itself -- in order with its producers and consumers by construction, no
-        // cross-stream dependency per call (two of them cost ~0.1 ms of a 0.6-2.4 ms step: profiles/small_batch_r5.txt).  ev_sw, recorded behind the launches, is
-        // what the next call on any other stream (and vp_synchronize / vp_destroy) waits for.
-        if ((rc = adopt_stream(c, cs))) return rc;
-        c->stream = cs;
-        rc = run_chunk(c, d_crops, fmt, n, d_org_wh, d_out);
-        c->stream = c->own_stream;
-        if (!c->ev_sw && hipEventCreateWithFlags(&c->ev_sw, hipEventDisableTiming) != hipSuccess) return fail(c, VP_ERR_HIP, "hipEventCreateWithFlags(ev_sw)");
-        const hipError_t er = hipEventRecord(c->ev_sw, cs);   // also when rc != 0: part of the chunk may be enqueued
-        c->foreign_pending = true;
-        c->last_stream_id = (const void*)cs;
-        if (rc) return rc;
-        if (er != hipSuccess) return fail(c, VP_ERR_HIP, std::string("hipEventRecord(ev_sw): ") + hipGetErrorString(er));
+    return caller_ordered(c, (hipStream_t)caller_stream, n, [&]() -> int {
+        for (int off = 0; off < n; off += c->maxb) {   // vp_infer_device's chunks
+            const int nb = (n - off < c->maxb) ? n - off : c->maxb;
+            const char* src = (const char*)d_crops + (size_t)off * crop_bytes(fmt);
+            if ((rc = run_chunk(c, src, fmt, nb, d_org_wh ? d_org_wh + 2 * (size_t)off : nullptr, d_out + (size_t)off * c->Kp * 3))) return rc;
+        }
         return VP_OK;
-    }
-    if ((rc = adopt_stream(c, c->own_stream))) return rc;
-    if (!c->ev_in) HIPCHK(c, hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
-    if (!c->ev_out) HIPCHK(c, hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));
-    // everything the caller enqueued on its stream so far (the producers of d_crops / d_org_wh) happens before the library's kernels ...
-    HIPCHK(c, hipEventRecord(c->ev_in, cs));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in, 0));
-    if ((rc = vp_infer_device(c, d_crops, fmt, n, d_org_wh, d_out, 0))) return rc;
-    // ... and whatever the caller enqueues afterwards (consumers of d_out) happens after them
-    HIPCHK(c, hipEventRecord(c->ev_out, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(cs, c->ev_out, 0));
-    return VP_OK;
+    });
 }
 
 int vp_infer(vp_handle c, const void* crops, int32_t fmt, int32_t n, const int32_t* org_wh, float* out) {
@@ -1061,6 +1098,79 @@ int vp_dbg_frame_plan(const vp_frame* frames, int32_t n_frames, const int32_t* p
     const int rc = frame_plan(frames, n_frames, params9, n, bands, &why);
     if (rc) g_create_error = why;
     return rc;
+}
+
+int vp_infer_boxes_stream(vp_handle c, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx,
+                          int32_t n, int32_t pad, float* d_out, int32_t* d_crop_params, int32_t* d_status, void* caller_stream) {
+    if (!c) return VP_ERR_INVALID;
+    // every host argument is checked before anything is enqueued
+    if (n > 0 && (!frames || !d_xyxy || !d_out)) return fail(c, VP_ERR_INVALID, "null frame table, box or output pointer");
+    std::vector<int32_t> hw((size_t)std::max(n > 0 ? n_frames : 0, 0) * 2);
+    for (size_t f = 0; f < hw.size() / 2; ++f) { hw[2 * f] = frames[f].h; hw[2 * f + 1] = frames[f].w; }
+    std::string why;
+    if (box_args(n_frames, hw.data(), 2, row_stride, n, pad, &why)) return fail(c, VP_ERR_INVALID, why);
+    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, d_xyxy, d_out, false);
+    if (rc || n == 0) return rc;
+    for (int f = 0; f < n_frames; ++f) {   // device memory of the handle's device, the whole frame inside one allocation (as stage_frames checks)
+        const vp_frame& fr = frames[f];
+        hipPointerAttribute_t a;
+        std::memset(&a, 0, sizeof(a));
+        void* base = nullptr;
+        size_t size = 0;
+        bool ok = fr.data && hipPointerGetAttributes(&a, fr.data) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->cfg.device_id;
+        ok = ok && hipMemGetAddressRange(&base, &size, (void*)fr.data) == hipSuccess && fr.data + (size_t)fr.h * fr.w * 3 <= (const uint8_t*)base + size;
+        if (!ok) {
+            (void)hipGetLastError();
+            return fail(c, VP_ERR_INVALID, "frame " + std::to_string(f) + " is not device memory of device " + std::to_string(c->cfg.device_id) +
+                                               " (or runs past the end of its allocation)");
+        }
+    }
+    // the chunk's crop records / decode sizes / offsets live in handle buffers sized by max_batch, allocated on the first call
+    if (!c->crecs && (rc = dalloc(c, &c->crecs, (size_t)c->maxb))) return rc;
+    if (!c->box_aux && (rc = dalloc(c, &c->box_aux, (size_t)c->maxb * 4))) return rc;
+    return caller_ordered(c, (hipStream_t)caller_stream, n, [&]() -> int {
+        for (int off = 0; off < n; off += c->maxb) {   // vp_infer_frames' chunks: the same crops per chunk, so the same plan and bits
+            const int nb = (n - off < c->maxb) ? n - off : c->maxb;
+            // geometry + crop run eagerly in front of the chunk's graph: the frame pointers change from call to call, the graph's buffers do not
+            for (int f0 = 0; f0 < n_frames; f0 += vp::BOX_FRAMES_PER_LAUNCH) {
+                vp::BoxFrames bf;
+                std::memset(&bf, 0, sizeof(bf));
+                bf.f0 = f0; bf.count = std::min(n_frames - f0, vp::BOX_FRAMES_PER_LAUNCH); bf.n_frames = n_frames;
+                for (int j = 0; j < bf.count; ++j) { bf.data[j] = frames[f0 + j].data; bf.h[j] = frames[f0 + j].h; bf.w[j] = frames[f0 + j].w; }
+                LAUNCH(c, VP_PROF_IM2COL, 0.0, 64.0 * nb,
+                       vp::box_geometry_launch(bf, d_xyxy + (size_t)off * row_stride, row_stride, d_frame_idx ? d_frame_idx + off : nullptr, nb, pad,
+                                               (const uint8_t*)c->zero, c->crecs, c->wh_stage, c->box_aux,
+                                               d_crop_params ? d_crop_params + (size_t)off * 9 : nullptr, d_status ? d_status + off : nullptr, c->stream));
+            }
+            LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5, vp::crop_resize_launch(c->crecs, (uint8_t*)c->in_stage, nb, c->stream));
+            if ((rc = run_chunk(c, c->in_stage, VP_INPUT_U8_NHWC, nb, c->wh_stage, d_out + (size_t)off * c->Kp * 3, c->box_aux))) return rc;
+        }
+        return VP_OK;
+    });
+}
+
+int vp_dbg_box_geometry(const float* xyxy, int32_t row_stride, const int32_t* frame_idx, const int32_t* frame_hw, int32_t n_frames, int32_t n, int32_t pad,
+                        int32_t* out9, int32_t* status) {
+    std::string why;
+    if (n > 0 && (!xyxy || (n_frames > 0 && !frame_hw))) why = "null box or frame table";
+    const int rc = why.empty() ? box_args(n_frames, frame_hw, 2, row_stride, n, pad, &why) : (int)VP_ERR_INVALID;
+    if (rc) { g_create_error = why; return rc; }
+    for (int i = 0; i < n; ++i) {   // what box_geometry_kernel computes for box i
+        const int32_t f = frame_idx ? frame_idx[i] : 0;
+        int32_t p8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        int st = vp::BOX_BAD_FRAME;
+        if (f >= 0 && f < n_frames) {
+            const float* b = xyxy + (size_t)i * row_stride;
+            st = vp::box_geometry(b[0], b[1], b[2], b[3], frame_hw[2 * (size_t)f], frame_hw[2 * (size_t)f + 1], pad, p8);
+            if (st != vp::BOX_OK) std::memset(p8, 0, sizeof(p8));
+        }
+        if (out9) {
+            out9[9 * (size_t)i] = st == vp::BOX_OK ? f : 0;
+            std::memcpy(out9 + 9 * (size_t)i + 1, p8, sizeof(p8));
+        }
+        if (status) status[i] = st;
+    }
+    return VP_OK;
 }
 
 int vp_decode_only(int32_t device_id, const float* heatmaps, int32_t n, int32_t k, const int32_t* org_wh, float* out) {

@@ -284,6 +284,55 @@ class VitPoseHip:
         capi.check(self.lib.vp_infer_frames(self._h, table, len(frames), int(on_device), params.ctypes.data, n, out.ctypes.data), self._h)
         return out
 
+    def infer_boxes(self, frames, boxes, frame_index=None, pad: int = 10, out=None, crop_params: bool = False, status: bool = False):
+        """Detector boxes on device frames -> keypoints in FRAME pixels, all on the device (vp_infer_boxes_stream, contract in
+        include/vitpose_hip.h).  `frames`: contiguous torch uint8 CUDA tensors [H, W, 3] on this handle's device; `boxes`: float32 CUDA
+        [n, >= 4] (x1, y1, x2, y2, ...) with unit column stride, e.g. a detector's [n, 6] output as it is; `frame_index`: int32 CUDA [n]
+        (None: every box on frame 0); `pad`: pixels added on every side before clipping.  Returns `out` float32 [n, K, 3] (allocated
+        when not given), plus int32 [n, 9] crop params (cropprep.frames_crop_params rows) and int32 [n] status (0 ok, 1 bad frame index,
+        2 non-finite box, 3 empty box; such rows are all zero) when asked for.  Everything is enqueued on torch's current stream without
+        a host synchronisation, under the ordering notes of `infer_device`: consume the results with torch ops on that stream."""
+        import torch
+        dev = torch.device('cuda', self.device_id)
+        frames = list(frames)
+        table = (capi.vp_frame * max(len(frames), 1))()
+        for i, f in enumerate(frames):
+            if not (isinstance(f, torch.Tensor) and f.is_cuda and f.dtype == torch.uint8 and f.is_contiguous()):
+                raise TypeError(f'frame {i}: a contiguous torch uint8 CUDA tensor expected')
+            if f.device != dev:
+                raise ValueError(f'frame {i} lives on {f.device}, the handle on {dev}')
+            if f.ndim != 3 or f.shape[2] != 3:
+                raise ValueError(f'frame {i}: [H, W, 3] expected, got {tuple(f.shape)}')
+            table[i] = capi.vp_frame(f.data_ptr(), f.shape[0], f.shape[1])
+        if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda and boxes.dtype == torch.float32):
+            raise TypeError('boxes: a float32 torch CUDA tensor expected')
+        if boxes.device != dev:
+            raise ValueError(f'boxes live on {boxes.device}, the handle on {dev}')
+        if boxes.ndim != 2 or boxes.shape[1] < 4 or (boxes.shape[0] > 0 and boxes.stride(1) != 1):
+            raise ValueError(f'boxes: [n, >= 4] with unit column stride expected, got {tuple(boxes.shape)} strides {boxes.stride()}')
+        n = boxes.shape[0]
+        row_stride = boxes.stride(0) if n > 1 else max(boxes.stride(0), 4)   # one row: its stride is never used
+        fip = None
+        if frame_index is not None:
+            if not (isinstance(frame_index, torch.Tensor) and frame_index.is_cuda and frame_index.dtype == torch.int32):
+                raise TypeError('frame_index: an int32 torch CUDA tensor expected')
+            if frame_index.device != dev or tuple(frame_index.shape) != (n,) or not frame_index.is_contiguous():
+                raise ValueError(f'frame_index: contiguous [{n}] on {dev} expected, got {tuple(frame_index.shape)} on {frame_index.device}')
+            fip = frame_index.data_ptr()
+        if out is None:
+            out = torch.empty((n, self.K, 3), dtype=torch.float32, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                  and out.device == dev and out.numel() == n * self.K * 3):
+            raise ValueError(f'out: a contiguous float32 tensor of {n} x {self.K} x 3 on {dev} expected')
+        cp = torch.empty((n, 9), dtype=torch.int32, device=dev) if crop_params else None
+        st = torch.empty((n,), dtype=torch.int32, device=dev) if status else None
+        cs = torch.cuda.current_stream(dev).cuda_stream
+        capi.check(self.lib.vp_infer_boxes_stream(self._h, table, len(frames), boxes.data_ptr(), row_stride, fip, n, int(pad), out.data_ptr(),
+                                                  None if cp is None else cp.data_ptr(), None if st is None else st.data_ptr(), cs), self._h)
+        if cp is None and st is None:
+            return out
+        return (out,) + tuple(t for t in (cp, st) if t is not None)
+
     def heatmaps(self, crops: np.ndarray) -> np.ndarray:
         crops = np.ascontiguousarray(crops)
         n = crops.shape[0]

@@ -217,6 +217,33 @@ typedef struct vp_frame {
 VP_API int vp_infer_frames(vp_handle h, const vp_frame* frames, int32_t n_frames, int32_t frames_on_device,
                            const int32_t* crop_params, int32_t n, float* out);
 
+/* Detector boxes to frame keypoints, all on the device, ordered on the CALLER's stream: the stream-ordered twin of vp_infer_frames.
+ * frames[n_frames] (host table): uint8 RGB [h, w, 3] frames in device memory of the handle's device, every entry checked before anything is
+ * enqueued (hipPointerGetAttributes + hipMemGetAddressRange: the whole frame inside one allocation); the caller's stream produces them.
+ * d_xyxy: device float32 boxes, row i = (x1, y1, x2, y2) at d_xyxy + i * row_stride (row_stride >= 4: a detector's [n, 6] tensor passes in place
+ * with 6).  d_frame_idx: device int32 [n], the frame of each box (NULL: frame 0).  pad: pixels added on every side before clipping (the
+ * reference's 10).  Per box, a kernel computes cropprep.crop_params (the padded, clipped box; pad_image's canvas) in double precision, bit for
+ * bit what the host computes on the float32 boxes widened to float64 (|coordinates| < 2^30; larger finite ones are clipped like any other).
+ * d_out: device float32 [n, K, 3] (y, x, conf) in FRAME pixels: row i has the bits of vp_infer_frames on those crop rows (same max_batch
+ * chunks, so the same plan, split-K included) followed by the offsets (y0 - top_pad, x0 - left_pad) added as VitInference.inference_frames
+ * adds them.  d_crop_params (may be NULL): device int32 [n, 9], each box's frames_crop_params row {frame, x0, y0, cw, ch, left_pad, top_pad,
+ * pw, ph}; (x0, y0, x0 + cw, y0 + ch) is the reference's in-place box update.  d_status (may be NULL): device int32 [n]: 0 ok, 1 frame index
+ * outside [0, n_frames), 2 a coordinate is not finite, 3 the box is empty after padding and clipping (the host path's 'empty box' assertion),
+ * checked in that order.  A row with a non-zero status reads no frame, gets all-zero keypoints and an all-zero d_crop_params row.
+ * Ordering as vp_infer_device_stream: batches of <= 16 crops (that fit max_batch) run on caller_stream itself, larger ones on the handle's
+ * stream fenced with two events; the next call on any stream, vp_synchronize and vp_destroy order themselves behind the work.  n > max_batch
+ * runs in max_batch chunks.  Per chunk: the box kernel (launched once per 128 frames of the table, which travels by kernel argument) and the crop
+ * kernel run eagerly, then the forward, decode and offset kernel (a replayed hipGraph for chunks of <= 16 crops).  The call never blocks the
+ * host: no stream / device / event synchronisation and no copy from host memory; its device buffers are sized by max_batch and allocated on the
+ * first call.  The one exception is vp_infer_device_stream's: when a fifth distinct small chunk (size, output pointer) evicts a cached graph,
+ * the handle's current stream is synchronised once before that graph is destroyed.
+ * VP_ERR_INVALID before anything is enqueued: a NULL pointer (frames, d_xyxy, d_out with n > 0), row_stride < 4, pad < 0, n > 0 with
+ * n_frames <= 0, a frame side outside [1, 2^24], a frame that is not device memory of the handle's device.  n = 0: VP_OK, nothing is
+ * written.  A ViTPose+ handle runs its active expert (vp_set_expert). */
+VP_API int vp_infer_boxes_stream(vp_handle h, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride,
+                                 const int32_t* d_frame_idx, int32_t n, int32_t pad, float* d_out, int32_t* d_crop_params,
+                                 int32_t* d_status, void* caller_stream);
+
 /* Flip-test inference (the optional accuracy mode of the reference head, topdown_heatmap_simple_head.py:195-218 with
  * flip_back of vit_utils/post_processing/post_transforms.py:110-147; `flip_test=True, shift_heatmap=False` in
  * configs/ViTPose_common.py:91-93): the model runs on the crops and on their left-right mirror, the mirrored heatmaps are
@@ -316,6 +343,12 @@ VP_API int vp_dbg_group_plan(int32_t n, int32_t w, int32_t maxb, int32_t* offs, 
  * against frames[n_frames] (h, w and whether data is NULL; the pixels are never read) and writes bands [n_frames, 2] = the rows
  * [row0, row1) of each frame its crops cover ({0, 0} for a frame without crops; bands may be NULL).  VP_OK or VP_ERR_INVALID. */
 VP_API int vp_dbg_frame_plan(const vp_frame* frames, int32_t n_frames, const int32_t* params9, int32_t n, int32_t* bands);
+/* The box geometry of vp_infer_boxes_stream -- HOST ONLY, no device needed, the same function its kernel runs: host float32 boxes xyxy
+ * (row i at xyxy + i * row_stride), frame_idx [n] (NULL: frame 0), frame_hw [n_frames, 2] = (h, w) -> out9 [n, 9] (the d_crop_params rows) and
+ * status [n] (either may be NULL).  VP_ERR_INVALID for the host-argument refusals of vp_infer_boxes_stream (a NULL box / frame table,
+ * row_stride < 4, pad < 0, n > 0 with n_frames <= 0, a frame side outside [1, 2^24]). */
+VP_API int vp_dbg_box_geometry(const float* xyxy, int32_t row_stride, const int32_t* frame_idx, const int32_t* frame_hw, int32_t n_frames,
+                               int32_t n, int32_t pad, int32_t* out9, int32_t* status);
 /* HOST ONLY: which tile of the 8-phase GEMM kernel the selection rule picks for an [M, N] output -- 0 = none (2-phase kernels), 16 = 256 x 256,
  * 17 = 256 x 192, 18 = 192 x 256; wide != 0: 16-bit-output GEMMs (qkv, fc1), else the residual GEMMs; bm192_mask bits 1 / 2 as VP_G8_BM192, bit 4 = the
  * round-3 thresholds (as VP_G8_COST=0); *tiles (may be NULL) = its tile count */
