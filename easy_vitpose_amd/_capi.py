@@ -29,7 +29,9 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_dbg_gemm', 'vp_dbg_attention', 'vp_dbg_layernorm', 'vp_dbg_deconv', 'vp_dbg_gemm_case', 'vp_dbg_crop_prep',
            'vp_dbg_group_plan', 'vp_dbg_group_trace', 'vp_dbg_gemm8_pick', 'vp_dbg_gemm2_pick', 'vp_dbg_splitk_pick', 'vp_dbg_run_batch', 'vp_dbg_fp8_gemm', 'vp_dbg_mx_gemm', 'vp_dbg_host_e4m3', 'vp_dbg_gemm_fp8_case', 'vp_dbg_qkvattn',
            'vp_expert_info', 'vp_set_expert', 'vp_infer_experts', 'vp_dbg_expert_tile', 'vp_infer_frames', 'vp_dbg_frame_plan',
-           'vp_dbg_chunk_plan', 'vp_infer_boxes_stream', 'vp_dbg_box_geometry']
+           'vp_dbg_chunk_plan', 'vp_infer_boxes_stream', 'vp_dbg_box_geometry',
+           'vp_set_flip_test', 'vp_clear_flip_test', 'vp_flip_test_enabled', 'vp_group_set_flip_test', 'vp_group_clear_flip_test',
+           'vp_dbg_flip_partner', 'vp_dbg_flip_layout', 'vp_dbg_decode_flip']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -156,6 +158,14 @@ def load_library():
     lib.vp_dbg_expert_tile.argtypes = [C.c_int32] * 4 + [C.c_void_p, C.c_int32]
     lib.vp_dbg_chunk_plan.argtypes = [C.POINTER(vp_config), C.c_int32, C.c_void_p, C.c_int32]
     lib.vp_dbg_qkvattn.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 4
+    lib.vp_set_flip_test.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32]
+    lib.vp_clear_flip_test.argtypes = [H]
+    lib.vp_flip_test_enabled.argtypes = [H]
+    lib.vp_group_set_flip_test.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32]
+    lib.vp_group_clear_flip_test.argtypes = [H]
+    lib.vp_dbg_flip_partner.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.vp_dbg_flip_layout.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.vp_dbg_decode_flip.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if name not in ('vp_stream', 'vp_last_error', 'vp_host_alloc', 'vp_host_free', 'vp_group_member', 'vp_group_last_error'):
             getattr(lib, name).restype = C.c_int

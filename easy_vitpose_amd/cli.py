@@ -6,6 +6,7 @@ pose path, track across frames (``is_video``), report FPS and write the ``--save
     python -m easy_vitpose_amd.cli --input frame.png --model vitpose-b-coco.pth --yolo yolov8s.pt --output-path out --save-json
     python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --output-path out --save-json
     python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --frame-batch 16   # 16 frames per pose call
+    python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --flip-test        # flip-test (COCO-17 pairs; else --flip-pairs FILE.json)
 
 Not rebuilt (outside the hot path): drawing / preview windows (``--show``, ``--save-img``: OpenCV) and video
 decoding -- a video is accepted as a ``.npy`` stack ``[frames, H, W, 3]`` uint8 RGB, or as a directory of image files.
@@ -40,7 +41,17 @@ def _read_frames(path: str, rotate: int):
     return [np.array(Image.open(path).convert('RGB').rotate(rotate))], False
 
 
-def main(argv=None) -> int:
+def flip_test_argument(args):
+    """--flip-test / --flip-pairs -> VitInference's flip_test=: None (off), True (the COCO-17 table) or the pair list of FILE.json."""
+    if args.flip_pairs is not None:
+        pairs = json.load(open(args.flip_pairs))
+        if not (isinstance(pairs, list) and all(isinstance(p, list) and len(p) == 2 and all(isinstance(v, int) for v in p) for p in pairs)):
+            raise ValueError(f'{args.flip_pairs}: a JSON list of [left, right] joint index pairs expected')
+        return pairs
+    return True if args.flip_test else None
+
+
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--input', required=True, help='image file, .npy frame stack, or directory of images')
     ap.add_argument('--output-path', default='', help='output directory (required by --save-json)')
@@ -63,7 +74,15 @@ def main(argv=None) -> int:
     ap.add_argument('--max-batch', type=int, default=64)
     ap.add_argument('--dtype', default='fp16', choices=['fp16', 'bf16'])
     ap.add_argument('--frame-batch', type=int, default=1, help='frames per pose call: the crops of N frames run as one batch (VitInference.inference_frames)')
-    args = ap.parse_args(argv)
+    ap.add_argument('--flip-test', action='store_true', help='flip-test: average each crop with its mirror image (the accuracy mode of the reference\'s test '
+                    'configs); on its own it stands for the COCO-17 mirror pairs, any other dataset needs --flip-pairs')
+    ap.add_argument('--flip-pairs', default=None, metavar='FILE.json', help='mirror joint pairs [[left, right], ...] of the dataset (implies --flip-test)')
+    ap.add_argument('--shift-heatmap', action='store_true', help='flip-test: shift the flipped-back heatmaps one pixel right (the reference\'s shift_heatmap)')
+    return ap
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
     assert not (args.show or args.save_img), 'drawing / preview (OpenCV) is outside the HIP hot path: use --save-json'
     assert not args.save_json or args.output_path, 'Specify an output path if using save-img or save-json flags'
     assert (args.model is None) != (args.synthetic is None), 'give exactly one of --model / --synthetic'
@@ -93,7 +112,8 @@ def main(argv=None) -> int:
         state_dict = synthetic_state_dict(model_shape(args.synthetic, dataset), 0, peaked=True)
     model = VitInference(state_dict if state_dict is not None else args.model, detector, args.model_name or args.synthetic,
                          args.det_class, dataset, args.yolo_size, is_video=is_video, single_pose=args.single_pose,
-                         yolo_step=args.yolo_step, dtype=args.dtype, max_batch=args.max_batch)
+                         yolo_step=args.yolo_step, dtype=args.dtype, max_batch=args.max_batch,
+                         flip_test=flip_test_argument(args), shift_heatmap=args.shift_heatmap)
     print(f'>>> Model loaded: {args.model or "synthetic ViTPose-" + args.synthetic.upper()}')
     print(f'>>> Running inference on {args.input}')
     keypoints, dts = [], []

@@ -100,3 +100,25 @@ def infer_variant_from_state_dict(sd) -> str:
         if d == D:
             return v
     raise ValueError(f'unknown embed_dim {D}')
+
+
+# mirror joint pairs of the 17-joint COCO layout (left / right eye, ear, shoulder, elbow, wrist, hip, knee, ankle): the one flip-pair table the
+# reference ships (datasets/COCO.py); every other dataset's pairs come from the user
+COCO17_FLIP_PAIRS = [[1, 2], [3, 4], [5, 6], [7, 8], [9, 10], [11, 12], [13, 14], [15, 16]]
+
+
+def resolve_flip_pairs(flip_test, dataset, num_keypoints):
+    """`flip_test` of VitInference / the CLI -> the pair list to hand the handle, or None for "mode off".  True stands for the COCO-17
+    table and is accepted for that layout only; any other dataset needs its pairs spelled out."""
+    if flip_test is None or flip_test is False:
+        return None
+    if flip_test is True:
+        if dataset != 'coco' or num_keypoints != 17:
+            raise ValueError(f'flip_test=True stands for the mirror pairs of the 17-joint COCO layout; dataset {dataset!r} with {num_keypoints} '
+                             'joints needs its pairs given explicitly: flip_test=[[left, right], ...]')
+        return [list(p) for p in COCO17_FLIP_PAIRS]
+    pairs = [[int(a), int(b)] for a, b in flip_test]
+    for a, b in pairs:
+        if not (0 <= a < num_keypoints and 0 <= b < num_keypoints):
+            raise ValueError(f'flip pair ({a}, {b}) outside the {num_keypoints} joints of dataset {dataset!r}')
+    return pairs

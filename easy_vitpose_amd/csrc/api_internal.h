@@ -109,6 +109,15 @@ struct vp_ctx {
     float *hm = nullptr, *kp = nullptr, *tok = nullptr;
     float* hm_keep = nullptr;         // flip-test: heatmaps of the un-flipped crops while the flipped pass runs
     int32_t* partner = nullptr;       // flip-test: mirror joint per joint
+    // flip-test MODE (vp_set_flip_test): every chunk of run_chunk / vp_infer_heatmaps runs its crops and their mirror images as one interleaved batch of twice
+    // the rows (elementwise.hip im2col_twin_kernel) and decodes the average without materialising it (decode.hip decode_kernel<true>).  A chunk then holds
+    // max_batch / 2 of the caller's crops (chunk_cap).  flip_gen = 0 while off, a fresh value per vp_set_flip_test: part of the hipGraph key, since the table
+    // and the shift are baked into a captured decode launch.  flip_table = the mode's own partner table (vp_infer_flip rewrites `partner` per call).
+    bool flip_on = false;
+    int flip_shift = 0;
+    uint32_t flip_gen = 0, flip_counter = 0;
+    int32_t* flip_table = nullptr;    // device [Kmax]
+    std::vector<int32_t> flip_pairs;  // the pairs as given (a group compares its members' modes)
     float *ln_part = nullptr, *rowstat = nullptr;   // partial row statistics [M][D/64][2], (mean, rstd) [M][2]
     // fp8 mode (vp_config.dtype = VP_DTYPE_FP8; csrc/mx8.h, gemm8f.hip, quant8.hip): qkv / fc1 / fc2 on MXFP8 operands.  Token rows are
     // padded to Mp (a multiple of the 256-row GEMM tile, >= 512); x8 / xs8 = LayerNorm(x) as MXFP8 codes / scales, hs8 = block scales of
@@ -136,7 +145,8 @@ struct vp_ctx {
     // replayed (170+ launches of a few microseconds each are launch-bound below ~16 crops); VP_GRAPH=0 disables
     struct GraphEntry { hipGraphExec_t exec = nullptr; int n = 0, fmt = -1, seen = 0; bool no_graph = false; const void* src = nullptr; const int32_t* wh = nullptr; float* out = nullptr;
                         int expert = 0;     // expert: a ViTPose+ handle's active expert is baked into the captured launches (fc2 weights, head, K)
-                        const int32_t* post = nullptr; };   // vp_infer_boxes_stream: the frame-offset kernel after the decode (its aux buffer; null: none)
+                        const int32_t* post = nullptr;   // vp_infer_boxes_stream: the frame-offset kernel after the decode (its aux buffer; null: none)
+                        uint32_t flip = 0; };            // the flip-test mode's generation the launches were captured under (flip_gen; 0: mode off)
     GraphEntry graphs[4];
     int graph_victim = 0;
     // split-K workspace of the residual GEMMs of small batches: fp32 partial products [S][M][D] of up to splitk_rows token rows (none when Switches::splitk_on is off)
@@ -234,6 +244,8 @@ int pack_deconv(vp_ctx* c, Lookup& lk, int idx, int Cin, uint16_t** w_out, float
 void use_expert(vp_ctx* c, int e);   // make expert e of a ViTPose+ handle the active one (head pointers, Kp)
 
 // ---- vitpose_api.hip
+// flip-test mode (HOST ONLY): partner[k] = the mirror joint of k among K joints (k itself when unpaired) from n_pairs x 2 indices; VP_OK or VP_ERR_INVALID with the reason in *why
+int flip_partner_table(int K, const int32_t* pairs, int n_pairs, int32_t* partner, std::string* why);
 bool prof_begin(vp_ctx* c, int fam, double flops, double bytes);
 void prof_end(vp_ctx* c, bool on);
 void prof_collect(vp_ctx* c);

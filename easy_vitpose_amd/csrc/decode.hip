@@ -28,15 +28,22 @@ __device__ __forceinline__ int reflect101(int i, int n) {
 
 struct GaussK { float w[11]; };
 
+// FLIP (flip-test mode, vp_set_flip_test): hm is the interleaved batch [2 N, K, 64, 48] -- crop n at 2 n, its mirror image at 2 n + 1 -- and the map the block
+// decodes is 0.5 (crop's map k + flip_back(mirror's map partner[k])), formed in registers wherever the plain kernel loads a value: the same fp32 add and exact
+// multiply as flip_merge_kernel and the same summation orders below, so the result equals flip_merge + decode bit for bit while the merged tensor is never
+// written.  flip_back = x reversed (column x reads 47 - x; with `shift`, column x > 0 reads 48 - x and column 0 keeps 47): a reversed 192-byte row is the same
+// one or two cache lines, read as one aligned 16-byte load (+ one scalar under `shift`) and swizzled in registers.
+template <bool FLIP>
 __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ hm, const int32_t* __restrict__ org_wh,
-                                                     float* __restrict__ out, int K, GaussK gk) {
+                                                     float* __restrict__ out, int K, GaussK gk, const int32_t* __restrict__ partner, int shift) {
     __shared__ float s_val[4];
     __shared__ int s_idx[4];
     __shared__ float s_part[7][11];
     __shared__ float s_samp[7];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = blockIdx.x / K, k = blockIdx.x % K;
-    const float* map = hm + (size_t)blockIdx.x * HW;
+    const float* map = hm + (FLIP ? (size_t)2 * n * K + k : (size_t)blockIdx.x) * HW;
+    const float* mir = FLIP ? hm + ((size_t)(2 * n + 1) * K + partner[k]) * HW : nullptr;
 
     // ---- arg-max / max over 3072 values, first index on ties (_get_max_preds, :82-114)
     float best = -INFINITY;
@@ -44,7 +51,16 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const int v4 = tid + 256 * i;
-        const f32x4 v = ((const f32x4*)map)[v4];
+        f32x4 v = ((const f32x4*)map)[v4];
+        if (FLIP) {   // columns x0 .. x0 + 3 of row y average with the mirror's columns 47 - x0 .. 44 - x0 (shift: 48 - x0 .. 45 - x0, column 0 with 47)
+            const int y = v4 / 12, x0 = (v4 - y * 12) * 4;
+            const float* mrow = mir + y * WW;
+            const f32x4 r = *(const f32x4*)(mrow + 44 - x0);
+            f32x4 b = f32x4{r[3], r[2], r[1], r[0]};
+            if (shift) b = f32x4{x0 ? mrow[48 - x0] : r[3], r[3], r[2], r[1]};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = 0.5f * (v[e] + b[e]);
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (v[e] > best || bidx == 0x7fffffff) { best = v[e]; bidx = v4 * 4 + e; }
@@ -81,10 +97,17 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
         int py = rem / (WW + 2) - 1, px = rem % (WW + 2) - 1;
         py = min(max(py, 0), HH - 1);                 // np.pad(mode='edge')
         px = min(max(px, 0), WW - 1);
-        const float* src = hm + ((size_t)n * K + kk) * HW + reflect101(py + ty - 5, HH) * WW;
+        const int ry = reflect101(py + ty - 5, HH) * WW;
+        const float* src = hm + ((size_t)(FLIP ? 2 * n : n) * K + kk) * HW + ry;
+        const float* msrc = FLIP ? hm + ((size_t)(2 * n + 1) * K + partner[kk]) * HW + ry : nullptr;   // the neighbour map the samples wrap into, and ITS partner
         float acc = 0.f;
 #pragma unroll
-        for (int tx = 0; tx < 11; ++tx) acc += gk.w[tx] * src[reflect101(px + tx - 5, WW)];
+        for (int tx = 0; tx < 11; ++tx) {
+            const int x = reflect101(px + tx - 5, WW);
+            float v = src[x];
+            if (FLIP) v = 0.5f * (v + msrc[47 - ((shift && x > 0) ? x - 1 : x)]);
+            acc += gk.w[tx] * v;
+        }
         s_part[s][ty] = acc;
     }
     __syncthreads();
@@ -118,20 +141,30 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
         if (org_wh) { ow = org_wh[2 * n]; oh = org_wh[2 * n + 1]; }
         const double fx = (double)rx * ((double)ow / (WW - 1.0)) + (double)(ow / 2) - (double)ow * 0.5;
         const double fy = (double)ry * ((double)oh / (HH - 1.0)) + (double)(oh / 2) - (double)oh * 0.5;
-        float* o = out + (size_t)blockIdx.x * 3;
+        float* o = out + (size_t)blockIdx.x * 3;             // [n, K, 3] of the caller's crops in both modes
         o[0] = (float)fy;                            // (y, x, conf)  inference.py:205
         o[1] = (float)fx;
         o[2] = maxval;
     }
 }
 
-hipError_t decode_launch(const float* hm, const int32_t* org_wh, float* out, int N, int K, hipStream_t s) {
+static GaussK gauss11() {
     // OpenCV getGaussianKernel(11, sigma<=0): sigma = 0.3*((11-1)*0.5-1)+0.8 = 2.0, float32 weights, sum 1
     GaussK gk;
     double w[11], sum = 0.0;
     for (int i = 0; i < 11; ++i) { w[i] = exp(-((i - 5.0) * (i - 5.0)) / (2.0 * 2.0 * 2.0)); sum += w[i]; }
     for (int i = 0; i < 11; ++i) gk.w[i] = (float)(w[i] / sum);
-    hipLaunchKernelGGL(decode_kernel, dim3(N * K), dim3(256), 0, s, hm, org_wh, out, K, gk);
+    return gk;
+}
+
+hipError_t decode_launch(const float* hm, const int32_t* org_wh, float* out, int N, int K, hipStream_t s) {
+    hipLaunchKernelGGL(decode_kernel<false>, dim3(N * K), dim3(256), 0, s, hm, org_wh, out, K, gauss11(), (const int32_t*)nullptr, 0);
+    return hipGetLastError();
+}
+
+hipError_t decode_flip_launch(const float* hm, const int32_t* partner, int shift, const int32_t* org_wh, float* out, int N, int K, hipStream_t s) {
+    if (!partner) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(decode_kernel<true>, dim3(N * K), dim3(256), 0, s, hm, org_wh, out, K, gauss11(), partner, shift);
     return hipGetLastError();
 }
 

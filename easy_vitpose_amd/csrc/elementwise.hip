@@ -92,12 +92,111 @@ hipError_t im2col_launch(int dtype, const void* crops, int fmt, uint16_t* out, i
     return hipGetLastError();
 }
 
+// ------------------------------------------------------- flip-test twin gather
+// Flip-test mode (vp_set_flip_test): the patch rows of n crops AND of their mirror images in one launch, interleaved -- output crop 2i is
+// crop i, output crop 2i + 1 its mirror (bit for bit the FLIP path above).  One block = one patch row (py) of one PAIR: the 3 x 16 source
+// rows are read from HBM once, converted once and laid into LDS the straight way; the straight output reads them as im2col_kernel does,
+// the mirrored output reads the same tile backwards (output column xo = source column 191 - xo; the conv's zero border of the mirror
+// image lies at source columns 192, 193).  Output rows beyond 2 n_src (a padded encoder batch) repeat the last one, 2 n_src - 1.
+__host__ __device__ inline void flip_twin_source(int bo, int n_src, int* src, int* mirror) {   // output crop bo of the interleaved batch
+    const int r = bo < 2 * n_src - 1 ? bo : 2 * n_src - 1;
+    *src = r >> 1;
+    *mirror = r & 1;
+}
+
+template <class Ty, int FMT>
+__global__ __launch_bounds__(256) void im2col_twin_kernel(const void* __restrict__ in, uint16_t* __restrict__ out, int B, int n_src) {
+    constexpr int XS = 208;                                  // LDS row: x = -2 .. 205 (index x + 2)
+    __shared__ __attribute__((aligned(16))) uint16_t tile[3 * 16 * XS];
+    const int tid = threadIdx.x;
+    const int pair = blockIdx.x >> 4, py = blockIdx.x & 15;
+    int b, m0, b1, m1;
+    flip_twin_source(2 * pair, n_src, &b, &m0);              // both output crops of a pair read the same source crop
+    flip_twin_source(2 * pair + 1, n_src, &b1, &m1);
+    const int ytop = 16 * py - 2;
+    if (FMT == VP_INPUT_F32_NCHW) {
+        for (int id = tid; id < 3 * 16 * 48; id += 256) {
+            const int x4 = id % 48, ky = (id / 48) & 15, c = id / (48 * 16);
+            const int y = ytop + ky;
+            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+            if ((unsigned)y < 256u) v = *(const f32x4*)((const float*)in + (((size_t)b * 3 + c) * 256 + y) * 192 + x4 * 4);
+            uint32_t* dst = (uint32_t*)(tile + (c * 16 + ky) * XS + x4 * 4 + 2);
+            dst[0] = pack2<Ty>(v[0], v[1]);
+            dst[1] = pack2<Ty>(v[2], v[3]);
+        }
+    } else {
+        for (int id = tid; id < 16 * 36; id += 256) {
+            const int q = id % 36, ky = id / 36;
+            const int y = ytop + ky;
+            u32x4 raw = u32x4{0, 0, 0, 0};
+            const bool inside = (unsigned)y < 256u;
+            if (inside) raw = *(const u32x4*)((const uint8_t*)in + ((size_t)b * 256 + y) * 576 + q * 16);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int off = q * 16 + e, x = off / 3, c = off - x * 3;
+                const double mean = c == 0 ? 0.485 : (c == 1 ? 0.456 : 0.406);   // pre_img, as im2col_kernel
+                const double stdv = c == 0 ? 0.229 : (c == 1 ? 0.224 : 0.225);
+                const uint8_t u = (uint8_t)(raw[e >> 2] >> ((e & 3) * 8));
+                const float f = inside ? (float)(((double)u / 255.0 - mean) / stdv) : 0.f;
+                tile[(c * 16 + ky) * XS + x + 2] = to_bits<Ty>(f);
+            }
+        }
+    }
+    if (tid < 192) {   // zero border of every (c, ky) row: x = -2, -1 (the straight crop's left) and x = 192, 193 (the mirror's left)
+        const int r = tid >> 2, j = tid & 3;
+        tile[r * XS + (j < 2 ? j : 192 + j)] = 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int bo = 2 * pair + half;
+        if (bo >= B) break;
+        const bool mirror = half ? m1 != 0 : m0 != 0;
+        uint16_t* orow = out + ((size_t)bo * 192 + py * 12) * 768;
+        for (int id = tid; id < 12 * 96; id += 256) {
+            const int px = id / 96, kc = id - px * 96;
+            const int c = kc >> 5, ky = (kc & 31) >> 1, kx0 = (kc & 1) * 8;
+            const uint16_t* row = tile + (c * 16 + ky) * XS;
+            u32x4 v;
+            if (!mirror) {
+                v = *(const u32x4*)(row + 16 * px + kx0);
+            } else {   // output columns xo .. xo + 7 = LDS elements 195 - xo' .. 188 - xo' (xo' = 16 px + kx0), an 8-byte aligned run read upwards and reversed
+                const uint32_t* q = (const uint32_t*)(row + 188 - 16 * px - kx0);
+                const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3];
+                v = u32x4{(w3 >> 16) | (w3 << 16), (w2 >> 16) | (w2 << 16), (w1 >> 16) | (w1 << 16), (w0 >> 16) | (w0 << 16)};
+            }
+            *(u32x4*)(orow + (size_t)id * 8) = v;
+        }
+    }
+}
+
+hipError_t im2col_twin_launch(int dtype, const void* crops, int fmt, uint16_t* out, int B, int n_src, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    if (n_src <= 0 || 2 * n_src > B) return hipErrorInvalidValue;   // B output crops: 2 n_src interleaved + padding
+    const int grid = (B + 1) / 2 * 16;   // one block per patch row of a pair
+#define VP_I2T(TY, F) hipLaunchKernelGGL((im2col_twin_kernel<TY, F>), dim3(grid), dim3(256), 0, s, crops, out, B, n_src)
+    if (fmt == VP_INPUT_F32_NCHW) {
+        if (dtype == DT_F16) VP_I2T(F16, VP_INPUT_F32_NCHW); else VP_I2T(BF16, VP_INPUT_F32_NCHW);
+    } else if (fmt == VP_INPUT_U8_NHWC) {
+        if (dtype == DT_F16) VP_I2T(F16, VP_INPUT_U8_NHWC); else VP_I2T(BF16, VP_INPUT_U8_NHWC);
+    } else {
+        return hipErrorInvalidValue;
+    }
+#undef VP_I2T
+    return hipGetLastError();
+}
+
+void flip_twin_layout(int bo, int n_src, int* src, int* mirror) { flip_twin_source(bo, n_src, src, mirror); }
+
 // ------------------------------------------------------------- flip-test merge
 // hm[n][k][y][x] = 0.5 (hm[n][k][y][x] + back[n][k][y][x]),  back = flip_back(hm_flipped) (post_transforms.py:110-147:
 // channels swapped by the mirror pairs, then reversed in x), optionally shifted right by one pixel
 // (topdown_heatmap_simple_head.py:213-215, `shift_heatmap`); the average is what the flip-test consumer takes.
+// crop n's maps start n * a_stride / n * b_stride floats behind hm / hm_flipped: K * 3072 for two tensors of their own (vp_infer_flip), 2 K * 3072 for the
+// interleaved batch of the flip-test mode (hm_flipped = hm + K * 3072: the merged maps land in the straight crop's slot)
 __global__ __launch_bounds__(256) void flip_merge_kernel(float* __restrict__ hm, const float* __restrict__ hm_flipped,
-                                                         const int32_t* __restrict__ partner, int K, int shift, size_t total) {
+                                                         const int32_t* __restrict__ partner, int K, int shift, size_t total,
+                                                         size_t a_stride, size_t b_stride) {
     for (size_t id = (size_t)blockIdx.x * 256 + threadIdx.x; id < total; id += (size_t)gridDim.x * 256) {
         const int x = (int)(id % 48);
         const size_t row = id / 48;                    // (n*K + k)*64 + y
@@ -107,16 +206,17 @@ __global__ __launch_bounds__(256) void flip_merge_kernel(float* __restrict__ hm,
         const size_t n = nk / K;
         int xs = x;                                    // column of the flipped-back map before the shift
         if (shift && x > 0) xs = x - 1;
-        const float b = hm_flipped[((n * K + partner[k]) * 64 + y) * 48 + (47 - xs)];
-        hm[id] = 0.5f * (hm[id] + b);
+        const float b = hm_flipped[n * b_stride + ((size_t)partner[k] * 64 + y) * 48 + (47 - xs)];
+        float* a = hm + n * a_stride + ((size_t)k * 64 + y) * 48 + x;
+        *a = 0.5f * (*a + b);
     }
 }
 
-hipError_t flip_merge_launch(float* hm, const float* hm_flipped, const int32_t* partner, int N, int K, int shift, hipStream_t s) {
-    const size_t total = (size_t)N * K * 3072;
+hipError_t flip_merge_launch(float* hm, const float* hm_flipped, const int32_t* partner, int N, int K, int shift, hipStream_t s, int interleaved) {
+    const size_t total = (size_t)N * K * 3072, stride = (size_t)K * 3072 * (interleaved ? 2 : 1);
     int grid = (int)((total + 255) / 256);
     if (grid > 16384) grid = 16384;
-    if (total) hipLaunchKernelGGL(flip_merge_kernel, dim3(grid), dim3(256), 0, s, hm, hm_flipped, partner, K, shift, total);
+    if (total) hipLaunchKernelGGL(flip_merge_kernel, dim3(grid), dim3(256), 0, s, hm, hm_flipped, partner, K, shift, total, stride, stride);
     return hipGetLastError();
 }
 

@@ -196,7 +196,10 @@ hipError_t im2col_launch(int dtype, const void* crops, int input_format, uint16_
 // ViTPose+ mixed batch: dst crop i = src crop idx[i] (idx: device int32 [n], each in [0, n_src)); crop_bytes % 16 == 0
 hipError_t gather_crops_launch(const void* src, void* dst, const int32_t* idx, int n, size_t crop_bytes, hipStream_t s);
 // flip-test: hm = 0.5 (hm + flip_back(hm_flipped)); partner[k] = mirror joint of k (k itself if unpaired)
-hipError_t flip_merge_launch(float* hm, const float* hm_flipped, const int32_t* partner, int N, int K, int shift, hipStream_t s);
+hipError_t flip_merge_launch(float* hm, const float* hm_flipped, const int32_t* partner, int N, int K, int shift, hipStream_t s, int interleaved = 0);   // interleaved: crop n's maps lie 2 n K 3072 floats behind both pointers
+// flip-test mode: B output crops = the n_src crops and their mirror images interleaved (2 i = crop i, 2 i + 1 = its mirror), rows beyond 2 n_src repeat the last one
+hipError_t im2col_twin_launch(int dtype, const void* crops, int input_format, uint16_t* out, int B, int n_src, hipStream_t s);
+void flip_twin_layout(int bo, int n_src, int* src, int* mirror);   // HOST: the source crop of output crop bo and whether it is mirrored (the kernel's own index function)
 
 // one crop of a frame: src = the frame's pixel (y0, x0) (in a staged row band or in the caller's device frame), pitch = bytes per frame row;
 // the crop is [ch, cw] pixels, placed at (top, left) of a zero [ph, pw] canvas (vp_infer_frames builds these on the host)
@@ -225,5 +228,8 @@ hipError_t box_offsets_launch(const int32_t* aux, float* out, int n, int K, hipS
 // --------------------------------------------------------------------- decode
 // heatmaps fp32 [N, K, 64, 48] -> out fp32 [N, K, 3] (y, x, conf); org_wh int32 [N,2] or null
 hipError_t decode_launch(const float* hm, const int32_t* org_wh, float* out, int N, int K, hipStream_t s);
+// flip-test mode: hm = the interleaved batch [2 N, K, 64, 48] (crop, mirror, crop, mirror, ...); decodes 0.5 (crop + flip_back(mirror)) without materialising it,
+// bit for bit flip_merge_launch + decode_launch
+hipError_t decode_flip_launch(const float* hm, const int32_t* partner, int shift, const int32_t* org_wh, float* out, int N, int K, hipStream_t s);
 
 }  // namespace vp

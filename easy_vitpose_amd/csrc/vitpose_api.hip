@@ -218,14 +218,17 @@ const float* fc2_b(const vp_ctx* c, const vpi::Block& b) { return c->mix_expert 
 
 // forward of one chunk (n <= max_batch) with device-resident crops; heatmaps land in c->hm (head = false: the encoder and last_norm only, tokens in c->y).
 // Executes the chunk's plan (tile_rules.hip plan_chunk): which kernel runs each GEMM, the encoder batch, the LayerNorm folds, the qkv path.
-int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, bool want_tokens, bool flip = false, bool head = true) {
+// twin_src > 0 (flip-test mode): n_in = 2 * twin_src rows, the twin_src crops at d_crops interleaved with their mirror images (crop, mirror, crop, mirror, ...);
+// everything behind the patch gather is the plain forward of an n_in-crop batch.
+int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, bool want_tokens, bool flip = false, bool head = true, int twin_src = 0) {
     const int D = c->D;
     const ChunkPlan pl = plan_chunk(c->sw, D, c->heads, c->maxb, c->fp8, n_in, c->fin_rows, c->mix_expert ? &c->mix_bounds : nullptr);
     const GemmPick* pk = pl.gemm;
     const int n = pl.n;   // rows n_in .. n - 1 of a padded encoder batch repeat the last crop and are never read by the head
     const int M = n * 192;
     const double in_b = (fmt == VP_INPUT_F32_NCHW ? 4.0 : 1.0) * n_in * 3.0 * 256 * 192;
-    LAUNCH(c, VP_PROF_IM2COL, 0.0, in_b + 2.0 * M * 768, vp::im2col_launch(c->dtype, d_crops, fmt, c->hid, n, c->stream, flip, n_in));
+    if (twin_src) LAUNCH(c, VP_PROF_IM2COL, 0.0, 0.5 * in_b + 2.0 * M * 768, vp::im2col_twin_launch(c->dtype, d_crops, fmt, c->hid, n, twin_src, c->stream));
+    else LAUNCH(c, VP_PROF_IM2COL, 0.0, in_b + 2.0 * M * 768, vp::im2col_launch(c->dtype, d_crops, fmt, c->hid, n, c->stream, flip, n_in));
     int rc;
     size_t plane = 0;   // != 0: the residual stream c->x is held as two 16-bit planes (fused-LayerNorm path)
     const bool qkv_blocked = c->sw.blocked_qkv && D / c->heads == 64;
@@ -368,10 +371,26 @@ int head_chunk(vp_ctx* c, const uint16_t* y, int nh, float* hm, const HeadPlan& 
     return VP_OK;
 }
 
-int decode_chunk(vp_ctx* c, const int32_t* d_wh, float* d_out, int n) {
-    LAUNCH(c, VP_PROF_DECODE, 0.0, 4.0 * n * c->Kp * 3072.0 + 12.0 * n * c->Kp,
-           vp::decode_launch(c->hm, d_wh, d_out, n, c->Kp, c->stream));
+// twin: c->hm holds the 2 n interleaved maps forward_mode_chunk leaves under the flip-test mode (never vp_infer_flip's own two passes, whatever the mode)
+int decode_chunk(vp_ctx* c, const int32_t* d_wh, float* d_out, int n, bool twin) {
+    if (twin)
+        LAUNCH(c, VP_PROF_DECODE, 0.0, 8.0 * n * c->Kp * 3072.0 + 12.0 * n * c->Kp,
+               vp::decode_flip_launch(c->hm, c->flip_table, c->flip_shift, d_wh, d_out, n, c->Kp, c->stream));
+    else
+        LAUNCH(c, VP_PROF_DECODE, 0.0, 4.0 * n * c->Kp * 3072.0 + 12.0 * n * c->Kp,
+               vp::decode_launch(c->hm, d_wh, d_out, n, c->Kp, c->stream));
     return VP_OK;
+}
+
+// crops of the caller a chunk holds: with the flip-test mode on, every crop brings its mirror image into the batch
+int chunk_cap(const vp_ctx* c) { return c->flip_on ? c->maxb / 2 : c->maxb; }
+// rows the forward of nb caller crops runs (before the plan's encoder padding): what the small-batch thresholds (hipGraph replay, caller's stream) are about
+int chunk_rows(const vp_ctx* c, int nb) { return c->flip_on ? 2 * nb : nb; }
+
+// the forward of a chunk of nb <= chunk_cap crops as the handle's mode asks: heatmaps [nb, Kp, 64, 48] in c->hm, or with the flip-test mode on the
+// interleaved [2 nb, Kp, 64, 48] of the crops and their mirror images (decode_chunk averages them on the fly)
+int forward_mode_chunk(vp_ctx* c, const void* d_src, int fmt, int nb) {
+    return c->flip_on ? forward_chunk(c, d_src, fmt, 2 * nb, false, false, true, nb) : forward_chunk(c, d_src, fmt, nb, false);
 }
 
 // vp_infer_boxes_stream: keypoints in padded-crop pixels -> frame pixels, zero rows for invalid boxes (aux = c->box_aux)
@@ -386,17 +405,18 @@ int offsets_chunk(vp_ctx* c, const int32_t* aux, float* d_out, int n) {
 // (inside the graph; `post` is part of the key).
 int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh, float* d_out, const int32_t* post = nullptr) {
     int rc;
+    if (nb > chunk_cap(c)) return fail(c, VP_ERR_INVALID, "a chunk of " + std::to_string(nb) + " crops exceeds what the handle's workspaces hold in this mode");
     auto eager = [&]() -> int {
-        if ((rc = forward_chunk(c, d_src, fmt, nb, false))) return rc;
-        if ((rc = decode_chunk(c, d_wh, d_out, nb))) return rc;
+        if ((rc = forward_mode_chunk(c, d_src, fmt, nb))) return rc;
+        if ((rc = decode_chunk(c, d_wh, d_out, nb, c->flip_on))) return rc;
         return post ? offsets_chunk(c, post, d_out, nb) : VP_OK;
     };
     // a caller's legacy default stream (torch's usual current stream): VP_GRAPH_NULL=1 replays the graph there too (a caller that synchronises after
     // every call pays the 110-290 eager launches' host time); 0 = plain launches (equal when calls are enqueued back to back)
-    if (nb > c->sw.graph_max_n || c->prof != 0 || (c->stream == nullptr && !c->sw.graph_null)) return eager();
+    if (chunk_rows(c, nb) > c->sw.graph_max_n || c->prof != 0 || (c->stream == nullptr && !c->sw.graph_null)) return eager();
     vp_ctx::GraphEntry* ge = nullptr;
     for (auto& g : c->graphs)
-        if (g.n == nb && g.fmt == fmt && g.src == d_src && g.wh == d_wh && g.out == d_out && g.expert == c->expert && g.post == post) { ge = &g; break; }
+        if (g.n == nb && g.fmt == fmt && g.src == d_src && g.wh == d_wh && g.out == d_out && g.expert == c->expert && g.post == post && g.flip == c->flip_gen) { ge = &g; break; }
     if (ge && ge->exec) {
         const hipError_t el = hipGraphLaunch(ge->exec, c->stream);
         if (el == hipSuccess) return VP_OK;
@@ -414,7 +434,7 @@ int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh
             hipGraphExecDestroy(ge->exec);
             ge->exec = nullptr;
         }
-        ge->n = nb; ge->fmt = fmt; ge->src = d_src; ge->wh = d_wh; ge->out = d_out; ge->expert = c->expert; ge->post = post; ge->seen = 1; ge->no_graph = false;
+        ge->n = nb; ge->fmt = fmt; ge->src = d_src; ge->wh = d_wh; ge->out = d_out; ge->expert = c->expert; ge->post = post; ge->flip = c->flip_gen; ge->seen = 1; ge->no_graph = false;
         return eager();
     }
     // second sighting: capture.  Any failure of the capture machinery (not of the launches themselves) marks the key "do not
@@ -424,8 +444,8 @@ int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh
     c->stream = c->own_stream;
     hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
     if (e != hipSuccess) { c->stream = target; (void)hipGetLastError(); ge->no_graph = true; return eager(); }
-    rc = forward_chunk(c, d_src, fmt, nb, false);
-    if (!rc) rc = decode_chunk(c, d_wh, d_out, nb);
+    rc = forward_mode_chunk(c, d_src, fmt, nb);
+    if (!rc) rc = decode_chunk(c, d_wh, d_out, nb, c->flip_on);
     if (!rc && post) rc = offsets_chunk(c, post, d_out, nb);
     e = hipStreamEndCapture(c->stream, &graph);
     c->stream = target;
@@ -486,7 +506,7 @@ int check_ready(vp_ctx* c, int fmt, int n, const void* p0, const void* p1, bool 
 // stream, fenced against the caller's with ev_in / ev_out.
 template <class Chunks> int caller_ordered(vp_ctx* c, hipStream_t cs, int n, Chunks chunks) {
     int rc;
-    if (n > 0 && n <= c->sw.caller_stream_max_n && n <= c->maxb && cs != c->own_stream) {
+    if (n > 0 && chunk_rows(c, n) <= c->sw.caller_stream_max_n && n <= chunk_cap(c) && cs != c->own_stream) {
         if ((rc = adopt_stream(c, cs))) return rc;
         c->stream = cs;
         rc = chunks();
@@ -626,6 +646,22 @@ int box_args(int n_frames, const int32_t* frame_hw, int hw_stride, int row_strid
     return VP_OK;
 }
 
+int flip_partner_table(int K, const int32_t* pairs, int n_pairs, int32_t* partner, std::string* why) {
+    auto bad = [&](const std::string& m) { if (why) *why = m; return VP_ERR_INVALID; };
+    if (K <= 0 || !partner) return bad("no joints");
+    if (n_pairs < 0) return bad("negative n_pairs");
+    if (n_pairs > 0 && !pairs) return bad("null flip_pairs with n_pairs > 0");
+    for (int k = 0; k < K; ++k) partner[k] = k;
+    for (int i = 0; i < n_pairs; ++i) {
+        const int a = pairs[2 * i], b = pairs[2 * i + 1];
+        if (a < 0 || b < 0 || a >= K || b >= K)
+            return bad("flip pair " + std::to_string(i) + " = (" + std::to_string(a) + ", " + std::to_string(b) + ") outside the head's " + std::to_string(K) + " joints");
+        partner[a] = b;
+        partner[b] = a;
+    }
+    return VP_OK;
+}
+
 }  // namespace vpi
 
 extern "C" {
@@ -707,8 +743,9 @@ int vp_create(vp_handle* out, const vp_config* cfg) {
 int vp_infer_device(vp_handle c, const void* d_crops, int32_t fmt, int32_t n, const int32_t* d_org_wh, float* d_out, int32_t sync) {
     int rc = check_ready(c, fmt, n, d_crops, d_out);
     if (rc) return rc;
-    for (int off = 0; off < n; off += c->maxb) {
-        const int nb = (n - off < c->maxb) ? n - off : c->maxb;
+    const int cap = chunk_cap(c);
+    for (int off = 0; off < n; off += cap) {
+        const int nb = (n - off < cap) ? n - off : cap;
         const char* src = (const char*)d_crops + (size_t)off * crop_bytes(fmt);
         if ((rc = run_chunk(c, src, fmt, nb, d_org_wh ? d_org_wh + 2 * (size_t)off : nullptr, d_out + (size_t)off * c->Kp * 3))) return rc;
     }
@@ -719,9 +756,10 @@ int vp_infer_device(vp_handle c, const void* d_crops, int32_t fmt, int32_t n, co
 int vp_infer_device_stream(vp_handle c, const void* d_crops, int32_t fmt, int32_t n, const int32_t* d_org_wh, float* d_out, void* caller_stream) {
     int rc = check_ready(c, fmt, n, d_crops, d_out, false);
     if (rc) return rc;
+    const int cap = chunk_cap(c);
     return caller_ordered(c, (hipStream_t)caller_stream, n, [&]() -> int {
-        for (int off = 0; off < n; off += c->maxb) {   // vp_infer_device's chunks
-            const int nb = (n - off < c->maxb) ? n - off : c->maxb;
+        for (int off = 0; off < n; off += cap) {   // vp_infer_device's chunks
+            const int nb = (n - off < cap) ? n - off : cap;
             const char* src = (const char*)d_crops + (size_t)off * crop_bytes(fmt);
             if ((rc = run_chunk(c, src, fmt, nb, d_org_wh ? d_org_wh + 2 * (size_t)off : nullptr, d_out + (size_t)off * c->Kp * 3))) return rc;
         }
@@ -732,13 +770,14 @@ int vp_infer_device_stream(vp_handle c, const void* d_crops, int32_t fmt, int32_
 int vp_infer(vp_handle c, const void* crops, int32_t fmt, int32_t n, const int32_t* org_wh, float* out) {
     int rc = check_ready(c, fmt, n, crops, out);
     if (rc) return rc;
-    if (n > c->maxb && !c->slots[0].busy && !c->slots[1].busy) {
+    const int cap = chunk_cap(c);
+    if (n > cap && !c->slots[0].busy && !c->slots[1].busy) {
         // more than one chunk: through the two asynchronous slots, so that the upload of chunk i+1 and the download of chunk i-1
         // run under the compute of chunk i (fully overlapped when the caller's buffers are pinned; pageable buffers still work,
         // the runtime stages them synchronously)
         int pending[2], np = 0;
-        for (int off = 0; off < n; off += c->maxb) {
-            const int nb = (n - off < c->maxb) ? n - off : c->maxb;
+        for (int off = 0; off < n; off += cap) {
+            const int nb = (n - off < cap) ? n - off : cap;
             int32_t slot = -1;
             rc = vp_infer_submit(c, (const char*)crops + (size_t)off * crop_bytes(fmt), fmt, nb, org_wh ? org_wh + 2 * (size_t)off : nullptr,
                                  out + (size_t)off * c->Kp * 3, &slot);
@@ -753,8 +792,8 @@ int vp_infer(vp_handle c, const void* crops, int32_t fmt, int32_t n, const int32
             if ((rc = vp_infer_wait(c, pending[i]))) return rc;
         return VP_OK;
     }
-    for (int off = 0; off < n; off += c->maxb) {
-        const int nb = (n - off < c->maxb) ? n - off : c->maxb;
+    for (int off = 0; off < n; off += cap) {
+        const int nb = (n - off < cap) ? n - off : cap;
         const char* src = (const char*)crops + (size_t)off * crop_bytes(fmt);
         HIPCHK(c, hipMemcpyAsync(c->in_stage, src, (size_t)nb * crop_bytes(fmt), hipMemcpyHostToDevice, c->stream));
         if (org_wh) HIPCHK(c, hipMemcpyAsync(c->wh_stage, org_wh + 2 * (size_t)off, (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
@@ -789,7 +828,8 @@ static int submit_impl(vp_handle c, const void* crops, int32_t fmt, int32_t n, c
     int rc = check_ready(c, fmt, n, crops, out);
     if (rc) return rc;
     if (!slot_out) return fail(c, VP_ERR_INVALID, "null slot pointer");
-    if (n <= 0 || n > c->maxb) return fail(c, VP_ERR_INVALID, "vp_infer_submit takes 1 .. max_batch crops per call");
+    if (n <= 0 || n > chunk_cap(c))
+        return fail(c, VP_ERR_INVALID, c->flip_on ? "vp_infer_submit takes 1 .. max_batch / 2 crops per call while the flip-test mode is on" : "vp_infer_submit takes 1 .. max_batch crops per call");
     if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     if (!c->d2h_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking));
     const int si = c->next_slot;
@@ -898,7 +938,7 @@ int vp_infer_flip(vp_handle c, const void* crops, int32_t fmt, int32_t n, const 
         HIPCHK(c, hipMemcpyAsync(c->hm, c->hm_keep, (size_t)nb * c->Kp * 3072 * 4, hipMemcpyDeviceToDevice, c->stream));
         if (heatmaps) HIPCHK(c, hipMemcpyAsync(heatmaps + (size_t)off * c->Kp * 3072, c->hm, (size_t)nb * c->Kp * 3072 * 4, hipMemcpyDeviceToHost, c->stream));
         if (out) {
-            if ((rc = decode_chunk(c, org_wh ? c->wh_stage : nullptr, c->kp, nb))) return rc;
+            if ((rc = decode_chunk(c, org_wh ? c->wh_stage : nullptr, c->kp, nb, false))) return rc;
             HIPCHK(c, hipMemcpyAsync(out + (size_t)off * c->Kp * 3, c->kp, (size_t)nb * c->Kp * 12, hipMemcpyDeviceToHost, c->stream));
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -906,14 +946,72 @@ int vp_infer_flip(vp_handle c, const void* crops, int32_t fmt, int32_t n, const 
     return VP_OK;
 }
 
+// ---- flip-test mode ------------------------------------------------------------------------------------------------------
+int vp_set_flip_test(vp_handle c, const int32_t* flip_pairs, int32_t n_pairs, int32_t shift_heatmap) {
+    if (!c) return VP_ERR_INVALID;
+    if (!c->loaded) return fail(c, VP_ERR_STATE, "weights not loaded: call vp_load_weights first");
+    std::vector<int32_t> partner((size_t)c->Kmax);
+    std::string why;
+    if (flip_partner_table(c->Kp, flip_pairs, n_pairs, partner.data(), &why)) return fail(c, VP_ERR_INVALID, "vp_set_flip_test: " + why);
+    for (int k = c->Kp; k < c->Kmax; ++k) partner[k] = k;
+    if (c->maxb < 2)
+        return fail(c, VP_ERR_STATE, "vp_set_flip_test: a crop and its mirror image share the forward batch, which needs max_batch >= 2 (this handle has 1)");
+    if (c->slots[0].busy || c->slots[1].busy) return fail(c, VP_ERR_STATE, "vp_set_flip_test with a vp_infer_submit in flight: call vp_infer_wait first");
+    int rc = vp_synchronize(c);   // a previous table may still be read by enqueued work (also on a caller's stream)
+    if (rc) return rc;
+    if (!c->flip_table && (rc = dalloc(c, &c->flip_table, (size_t)c->Kmax))) return rc;
+    HIPCHK(c, hipMemcpy(c->flip_table, partner.data(), (size_t)c->Kmax * 4, hipMemcpyHostToDevice));   // synchronous: `partner` is a local
+    c->flip_pairs.assign(flip_pairs, flip_pairs + 2 * (size_t)n_pairs);
+    c->flip_shift = shift_heatmap ? 1 : 0;
+    c->flip_on = true;
+    c->flip_gen = ++c->flip_counter;   // never the value of an earlier set: a graph captured under another table or shift is not replayed
+    return VP_OK;
+}
+
+int vp_clear_flip_test(vp_handle c) {
+    if (!c) return VP_ERR_INVALID;
+    if (c->slots[0].busy || c->slots[1].busy) return fail(c, VP_ERR_STATE, "vp_clear_flip_test with a vp_infer_submit in flight: call vp_infer_wait first");
+    c->flip_on = false;
+    c->flip_gen = 0;   // the graphs of the plain mode are valid again
+    c->flip_pairs.clear();
+    return VP_OK;
+}
+
+int vp_flip_test_enabled(vp_handle c) { return c && c->flip_on ? 1 : 0; }
+
+int vp_dbg_flip_partner(int32_t k, const int32_t* flip_pairs, int32_t n_pairs, int32_t* partner) {
+    std::string why;
+    std::vector<int32_t> tmp((size_t)(k > 0 ? k : 0));
+    const int rc = flip_partner_table(k, flip_pairs, n_pairs, partner ? partner : tmp.data(), &why);
+    if (rc) g_create_error = why;
+    return rc;
+}
+
+int vp_dbg_flip_layout(int32_t n, int32_t rows, int32_t* src, int32_t* mirror) {
+    if (n <= 0 || rows < 2 * n || !src || !mirror) return VP_ERR_INVALID;
+    for (int bo = 0; bo < rows; ++bo) {
+        int s_, m_;
+        vp::flip_twin_layout(bo, n, &s_, &m_);
+        src[bo] = s_; mirror[bo] = m_;
+    }
+    return VP_OK;
+}
+
 int vp_infer_heatmaps(vp_handle c, const void* crops, int32_t fmt, int32_t n, float* heatmaps) {
     int rc = check_ready(c, fmt, n, crops, heatmaps);
     if (rc) return rc;
-    for (int off = 0; off < n; off += c->maxb) {
-        const int nb = (n - off < c->maxb) ? n - off : c->maxb;
+    const int cap = chunk_cap(c);
+    const size_t map_bytes = (size_t)c->Kp * 3072 * 4;
+    for (int off = 0; off < n; off += cap) {
+        const int nb = (n - off < cap) ? n - off : cap;
         HIPCHK(c, hipMemcpyAsync(c->in_stage, (const char*)crops + (size_t)off * crop_bytes(fmt), (size_t)nb * crop_bytes(fmt), hipMemcpyHostToDevice, c->stream));
-        if ((rc = forward_chunk(c, c->in_stage, fmt, nb, false))) return rc;
-        HIPCHK(c, hipMemcpyAsync(heatmaps + (size_t)off * c->Kp * 3072, c->hm, (size_t)nb * c->Kp * 3072 * 4, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = forward_mode_chunk(c, c->in_stage, fmt, nb))) return rc;
+        if (c->flip_on) {   // the averaged maps, materialised in the straight crops' slots (every second one of the interleaved batch)
+            HIPCHK(c, vp::flip_merge_launch(c->hm, c->hm + (size_t)c->Kp * 3072, c->flip_table, nb, c->Kp, c->flip_shift, c->stream, 1));
+            HIPCHK(c, hipMemcpy2DAsync(heatmaps + (size_t)off * c->Kp * 3072, map_bytes, c->hm, 2 * map_bytes, map_bytes, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+        } else {
+            HIPCHK(c, hipMemcpyAsync(heatmaps + (size_t)off * c->Kp * 3072, c->hm, (size_t)nb * map_bytes, hipMemcpyDeviceToHost, c->stream));
+        }
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return VP_OK;
@@ -950,7 +1048,13 @@ int vp_set_expert(vp_handle c, int32_t e) {
     if (!c->n_experts) return fail(c, VP_ERR_STATE, "vp_set_expert: the handle holds a plain (single-dataset) checkpoint, not a ViTPose+ one");
     if (e < 0 || e >= c->n_experts) return fail(c, VP_ERR_INVALID, "expert id " + std::to_string(e) + " outside [0, " + std::to_string(c->n_experts) + ")");
     if (c->slots[0].busy || c->slots[1].busy) return fail(c, VP_ERR_STATE, "vp_set_expert with a vp_infer_submit in flight: call vp_infer_wait first");
+    const int k_before = c->Kp;
     use_expert(c, e);
+    if (c->flip_on && c->Kp != k_before) {   // the pairs were validated against the previous head's joints and say nothing about this one's
+        vp_clear_flip_test(c);
+        return fail(c, VP_ERR_STATE, "vp_set_expert: expert " + std::to_string(e) + " is active, but its head has " + std::to_string(c->Kp) + " joints, not " +
+                                         std::to_string(k_before) + ": the flip-test mode was cleared -- call vp_set_flip_test with this dataset's pairs");
+    }
     return VP_OK;
 }
 
@@ -963,6 +1067,7 @@ int vp_infer_experts(vp_handle c, const void* crops, int32_t fmt, int32_t n, con
         if (expert_ids[i] < 0 || expert_ids[i] >= c->n_experts)
             return fail(c, VP_ERR_INVALID, "expert id " + std::to_string(expert_ids[i]) + " of crop " + std::to_string(i) + " outside [0, " + std::to_string(c->n_experts) + ")");
     if (c->slots[0].busy || c->slots[1].busy) return fail(c, VP_ERR_STATE, "vp_infer_experts with a vp_infer_submit in flight: call vp_infer_wait first");
+    if (c->flip_on) return fail(c, VP_ERR_STATE, "vp_infer_experts does not run under the flip-test mode (one partner table per handle, not per crop): call vp_clear_flip_test first");
     // per chunk, the crops in expert order (stable): each expert is one contiguous segment, so that mlp.fc2's m-tiles see one expert and the head runs once per expert
     const int saved = c->expert, D = c->D;
     const size_t cb = crop_bytes(fmt), B = (size_t)((c->maxb + 3) / 4 * 4);
@@ -1064,8 +1169,9 @@ int vp_infer_frames(vp_handle c, const vp_frame* frames, int32_t n_frames, int32
     if ((rc = stage_frames(c, frames, n_frames, on_device != 0, p9, n, bands.data(), recs))) return rc;
     if (!c->crecs && (rc = dalloc(c, &c->crecs, (size_t)c->maxb))) return rc;
     std::vector<int32_t> wh((size_t)c->maxb * 2);
-    for (int off = 0; off < n; off += c->maxb) {   // vp_infer's chunks: the same crops per chunk, so the same bits
-        const int nb = (n - off < c->maxb) ? n - off : c->maxb;
+    const int cap = chunk_cap(c);
+    for (int off = 0; off < n; off += cap) {   // vp_infer's chunks: the same crops per chunk, so the same bits
+        const int nb = (n - off < cap) ? n - off : cap;
         HIPCHK(c, hipMemcpyAsync(c->crecs, recs.data() + off, (size_t)nb * sizeof(vp::CropRec), hipMemcpyHostToDevice, c->stream));
         LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5, vp::crop_resize_launch(c->crecs, (uint8_t*)c->in_stage, nb, c->stream));
         // decode scales by the padded-canvas size (pw, ph) of each crop = the image pre_img receives
@@ -1128,9 +1234,10 @@ int vp_infer_boxes_stream(vp_handle c, const vp_frame* frames, int32_t n_frames,
     // the chunk's crop records / decode sizes / offsets live in handle buffers sized by max_batch, allocated on the first call
     if (!c->crecs && (rc = dalloc(c, &c->crecs, (size_t)c->maxb))) return rc;
     if (!c->box_aux && (rc = dalloc(c, &c->box_aux, (size_t)c->maxb * 4))) return rc;
+    const int cap = chunk_cap(c);
     return caller_ordered(c, (hipStream_t)caller_stream, n, [&]() -> int {
-        for (int off = 0; off < n; off += c->maxb) {   // vp_infer_frames' chunks: the same crops per chunk, so the same plan and bits
-            const int nb = (n - off < c->maxb) ? n - off : c->maxb;
+        for (int off = 0; off < n; off += cap) {   // vp_infer_frames' chunks: the same crops per chunk, so the same plan and bits
+            const int nb = (n - off < cap) ? n - off : cap;
             // geometry + crop run eagerly in front of the chunk's graph: the frame pointers change from call to call, the graph's buffers do not
             for (int f0 = 0; f0 < n_frames; f0 += vp::BOX_FRAMES_PER_LAUNCH) {
                 vp::BoxFrames bf;
@@ -1173,7 +1280,8 @@ int vp_dbg_box_geometry(const float* xyxy, int32_t row_stride, const int32_t* fr
     return VP_OK;
 }
 
-int vp_decode_only(int32_t device_id, const float* heatmaps, int32_t n, int32_t k, const int32_t* org_wh, float* out) {
+// decode of host heatmaps on device `device_id`: partner == null: [n, k, 64, 48] as they are; else the interleaved [2 n, k, 64, 48] of the flip-test mode
+static int decode_host(int32_t device_id, const float* heatmaps, int32_t n, int32_t k, const int32_t* partner, int32_t shift, const int32_t* org_wh, float* out) {
     if (!heatmaps || !out || n <= 0 || k <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, VP_ERR_HIP, "no HIP device available (no CPU fallback)");
@@ -1181,8 +1289,8 @@ int vp_decode_only(int32_t device_id, const float* heatmaps, int32_t n, int32_t 
     vp_ctx* c = nullptr;   // errors below are reported through the create-error slot
     HIPCHK(c, hipSetDevice(device_id));
     float *d_hm = nullptr, *d_out = nullptr;
-    int32_t* d_wh = nullptr;
-    const size_t hb = (size_t)n * k * 3072 * 4, ob = (size_t)n * k * 12;
+    int32_t *d_wh = nullptr, *d_partner = nullptr;
+    const size_t hb = (size_t)n * k * 3072 * 4 * (partner ? 2 : 1), ob = (size_t)n * k * 12;
     int rc = VP_OK;
     hipError_t e = hipMalloc((void**)&d_hm, hb);
     if (e == hipSuccess) e = hipMalloc((void**)&d_out, ob);
@@ -1191,14 +1299,32 @@ int vp_decode_only(int32_t device_id, const float* heatmaps, int32_t n, int32_t 
         e = hipMalloc((void**)&d_wh, (size_t)n * 8);
         if (e == hipSuccess) e = hipMemcpy(d_wh, org_wh, (size_t)n * 8, hipMemcpyHostToDevice);
     }
-    if (e == hipSuccess) e = vp::decode_launch(d_hm, d_wh, d_out, n, k, nullptr);
+    if (e == hipSuccess && partner) {
+        e = hipMalloc((void**)&d_partner, (size_t)k * 4);
+        if (e == hipSuccess) e = hipMemcpy(d_partner, partner, (size_t)k * 4, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = partner ? vp::decode_flip_launch(d_hm, d_partner, shift ? 1 : 0, d_wh, d_out, n, k, nullptr) : vp::decode_launch(d_hm, d_wh, d_out, n, k, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(nullptr, VP_ERR_HIP, std::string("vp_decode_only: ") + hipGetErrorString(e));
+    if (e != hipSuccess) rc = fail(nullptr, VP_ERR_HIP, std::string(partner ? "vp_dbg_decode_flip: " : "vp_decode_only: ") + hipGetErrorString(e));
     if (d_hm) hipFree(d_hm);
     if (d_out) hipFree(d_out);
     if (d_wh) hipFree(d_wh);
+    if (d_partner) hipFree(d_partner);
     return rc;
+}
+
+int vp_decode_only(int32_t device_id, const float* heatmaps, int32_t n, int32_t k, const int32_t* org_wh, float* out) {
+    return decode_host(device_id, heatmaps, n, k, nullptr, 0, org_wh, out);
+}
+
+int vp_dbg_decode_flip(int32_t device_id, const float* heatmaps2, int32_t n, int32_t k, const int32_t* flip_pairs, int32_t n_pairs, int32_t shift_heatmap,
+                       const int32_t* org_wh, float* out) {
+    if (k <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
+    std::vector<int32_t> partner((size_t)k);
+    std::string why;
+    if (flip_partner_table(k, flip_pairs, n_pairs, partner.data(), &why)) return fail(nullptr, VP_ERR_INVALID, why);
+    return decode_host(device_id, heatmaps2, n, k, partner.data(), shift_heatmap, org_wh, out);
 }
 
 // ---- multi-GPU group (one process, N devices): crops sharded contiguously, weights replicated ------------------------------
@@ -1330,7 +1456,12 @@ static int group_run(vp_group* g, const void* crops, int32_t fmt, int32_t n, con
     std::vector<float> scratch;
     if (!out) { scratch.resize((size_t)n * K * 3); out = scratch.data(); }
     std::vector<int> offs, cnts;
-    if (group_plan(n, w, g->h[0]->maxb, offs, cnts) < 0) return VP_ERR_INVALID;
+    for (int i = 1; i < w; ++i)   // one plan for all members: they must agree on the flip-test mode (vp_group_set_flip_test sets them alike)
+        if (g->h[i]->flip_on != g->h[0]->flip_on || (g->h[0]->flip_on && (g->h[i]->flip_shift != g->h[0]->flip_shift || g->h[i]->flip_pairs != g->h[0]->flip_pairs))) {
+            g->err = "the members of the group disagree on the flip-test mode (member " + std::to_string(i) + " against member 0): set it with vp_group_set_flip_test";
+            return VP_ERR_STATE;
+        }
+    if (group_plan(n, w, chunk_cap(g->h[0]), offs, cnts) < 0) return VP_ERR_INVALID;
     std::vector<int> slot(w, -1);
     // phase 1 per member: upload (pinned caller memory as it is, pageable memory through the member's pinned staging buffer), model,
     // decode, download into the member's pinned staging buffer, and the peer copies of the device-side all-gather -- all enqueued, none
@@ -1374,6 +1505,24 @@ int vp_group_infer_allgather(vp_group_handle g, const void* crops, int32_t fmt, 
 }
 
 vp_handle vp_group_member(vp_group_handle g, int32_t i) { return (g && i >= 0 && i < (int)g->h.size()) ? g->h[i] : nullptr; }
+
+int vp_group_set_flip_test(vp_group_handle g, const int32_t* flip_pairs, int32_t n_pairs, int32_t shift_heatmap) {
+    if (!g) return VP_ERR_INVALID;
+    for (auto* h : g->h) {
+        const int rc = vp_set_flip_test(h, flip_pairs, n_pairs, shift_heatmap);
+        if (rc) { g->err = h->err; for (auto* q : g->h) vp_clear_flip_test(q); return rc; }   // all or none
+    }
+    return VP_OK;
+}
+
+int vp_group_clear_flip_test(vp_group_handle g) {
+    if (!g) return VP_ERR_INVALID;
+    for (auto* h : g->h) {
+        const int rc = vp_clear_flip_test(h);
+        if (rc) { g->err = h->err; return rc; }
+    }
+    return VP_OK;
+}
 
 int vp_group_destroy(vp_group_handle g) {
     if (!g) return VP_OK;

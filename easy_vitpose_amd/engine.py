@@ -35,6 +35,13 @@ def _tensor_descs(state_dict):
     return (capi.vp_tensor_desc * len(descs))(*descs), keep
 
 
+def _flip_pairs_array(pairs) -> np.ndarray:
+    a = np.asarray(list(pairs) if pairs is not None else [], dtype=np.int64)
+    if a.size and (a.ndim != 2 or a.shape[1] != 2):
+        raise ValueError(f'flip pairs: [[left, right], ...] expected, got shape {a.shape}')
+    return np.ascontiguousarray(a.reshape(-1, 2), dtype=np.int32)
+
+
 class PinnedArray:
     """numpy view of page-locked host memory (vp_host_alloc): the buffers vp_infer_submit can copy from / to asynchronously."""
 
@@ -121,8 +128,11 @@ class VitPoseHip:
         if name not in names:
             raise ValueError(f'unknown dataset {name!r} for this ViTPose+ checkpoint: one of {", ".join(names)}')
         e = names.index(name)
-        capi.check(self.lib.vp_set_expert(self._h, e), self._h)
-        self.dataset, self.K = name, self.experts[e][1]
+        drops_mode = self.flip_test and self.experts[e][1] != self.K   # another K: the switch takes place, the flip-test mode is cleared, VP_ERR_STATE says so
+        code = self.lib.vp_set_expert(self._h, e)
+        if code == capi.VP_OK or (drops_mode and code == capi.VP_ERR_STATE and not self.flip_test):
+            self.dataset, self.K = name, self.experts[e][1]
+        capi.check(code, self._h)
 
     def infer_mixed(self, crops: np.ndarray, datasets, org_wh=None):
         """One call, a dataset per crop (vp_infer_experts): returns ``(out, k)`` -- ``out`` float32 [N, Kmax, 3] where crop i fills
@@ -230,6 +240,24 @@ class VitPoseHip:
                                               len(pairs), int(bool(shift_heatmap)), out.ctypes.data,
                                               None if hm is None else hm.ctypes.data), self._h)
         return (out, hm) if return_heatmaps else out
+
+    def set_flip_test(self, pairs, shift_heatmap: bool = False):
+        """Flip-test as a mode of the handle (vp_set_flip_test, contract in include/vitpose_hip.h): from now on `infer`, `infer_device`,
+        `submit` / `wait`, `infer_frame`, `infer_frames` and `infer_boxes` return the keypoints of the average of each crop's heatmaps and
+        the flipped-back heatmaps of its mirror image, and `heatmaps` returns that average.  The mirror images ride in the same forward,
+        so a chunk holds ``max_batch // 2`` crops (`submit` takes that many at most).  `pairs`: the dataset's mirror joint pairs
+        [[l, r], ...], validated against the active head's K.  `tokens`, `infer_flip` are not affected; `infer_mixed` refuses while
+        the mode is on.  A ViTPose+ handle: `set_dataset` to a head with another K clears the mode and raises."""
+        pairs = _flip_pairs_array(pairs)
+        capi.check(self.lib.vp_set_flip_test(self._h, pairs.ctypes.data if len(pairs) else None, len(pairs), int(bool(shift_heatmap))), self._h)
+
+    def clear_flip_test(self):
+        """Back to the default mode (vp_clear_flip_test)."""
+        capi.check(self.lib.vp_clear_flip_test(self._h), self._h)
+
+    @property
+    def flip_test(self) -> bool:
+        return bool(self.lib.vp_flip_test_enabled(self._h))
 
     def infer_frame(self, frame: np.ndarray, params: np.ndarray) -> np.ndarray:
         """Whole frame + crop geometry (cropprep.crop_params) -> [n, K, 3] in padded-crop pixels (vp_infer_frame)."""
@@ -402,6 +430,21 @@ def decode_heatmaps(heatmaps: np.ndarray, org_wh=None, device_id: int = 0) -> np
     return out
 
 
+def decode_flip_heatmaps(heatmaps2: np.ndarray, pairs, shift_heatmap: bool = False, org_wh=None, device_id: int = 0) -> np.ndarray:
+    """The flip-test mode's fused decode alone (vp_dbg_decode_flip): host heatmaps [2 N, K, 64, 48], crop i's maps at 2 i and its mirror
+    image's at 2 i + 1 -> [N, K, 3] of their flip-test average, which is never formed."""
+    lib = capi.load_library()
+    hm = np.ascontiguousarray(heatmaps2, dtype=np.float32)
+    n2, k, h, w = hm.shape
+    assert (h, w) == (HM_H, HM_W) and n2 % 2 == 0
+    pairs = _flip_pairs_array(pairs)
+    out = np.empty((n2 // 2, k, 3), dtype=np.float32)
+    wh = None if org_wh is None else np.ascontiguousarray(org_wh, dtype=np.int32).reshape(n2 // 2, 2)
+    capi.check(lib.vp_dbg_decode_flip(device_id, hm.ctypes.data, n2 // 2, k, pairs.ctypes.data if len(pairs) else None, len(pairs),
+                                      int(bool(shift_heatmap)), None if wh is None else wh.ctypes.data, out.ctypes.data))
+    return out
+
+
 def crop_prep_device(frame: np.ndarray, params: np.ndarray, device_id: int = 0) -> np.ndarray:
     """The device crop/pad/resize kernel alone (vp_dbg_crop_prep): uint8 [n, 256, 192, 3]."""
     lib = capi.load_library()
@@ -444,6 +487,14 @@ class VitPoseGroup:
         self._check(self.lib.vp_group_infer(self._g, crops.ctypes.data, VitPoseHip._fmt(crops), n,
                                             None if wh is None else wh.ctypes.data, out.ctypes.data))
         return out
+
+    def set_flip_test(self, pairs, shift_heatmap: bool = False):
+        """The flip-test mode on every member (vp_group_set_flip_test; VitPoseHip.set_flip_test): a round then takes max_batch // 2 crops per device."""
+        pairs = _flip_pairs_array(pairs)
+        self._check(self.lib.vp_group_set_flip_test(self._g, pairs.ctypes.data if len(pairs) else None, len(pairs), int(bool(shift_heatmap))))
+
+    def clear_flip_test(self):
+        self._check(self.lib.vp_group_clear_flip_test(self._g))
 
     def infer_allgather(self, crops: np.ndarray, d_all, org_wh=None):
         """`d_all`: one torch float32 tensor [n, K, 3] per device of the group; every one receives ALL keypoints (peer copies)."""

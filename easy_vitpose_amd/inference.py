@@ -4,7 +4,8 @@ with its backend slot filled by the MI355X-native HIP path.
 Kept from the reference: constructor signature (:81-90), ``reset`` (:174-185),
 ``postprocess`` (:187-205), ``inference(img) -> {id: (K,3) (y,x,score)}`` (:221-281),
 ``pre_img`` (:314-318), the state attributes (:112-116, :274-279) and the exception
-types.  Changed on purpose: the per-box Python loop that ran the model once per
+types.  Added: ``flip_test=`` (keyword): the reference's test-time flip averaging as a mode
+of the engine handle (a pair list, or True for the COCO-17 table).  Changed on purpose: the per-box Python loop that ran the model once per
 crop (:259-272) becomes ONE batched call into the C ABI (``_inference_batch``);
 ``_inference`` (single crop, :207-219) is still there and returns ``[1, K, 3]``.
 
@@ -21,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .configs import IMG_H, IMG_W, infer_dataset_by_path, infer_variant_from_state_dict, model_shape
+from .configs import IMG_H, IMG_W, infer_dataset_by_path, infer_variant_from_state_dict, model_shape, resolve_flip_pairs
 from .cropprep import frames_crop_params, resize_linear_u8
 from .engine import VitPoseHip, decode_heatmaps
 from .moe import DATASETS as MOE_DATASETS, is_vitpose_plus
@@ -69,7 +70,7 @@ class VitInference:
                  is_video: Optional[bool] = False,
                  single_pose: Optional[bool] = False,
                  yolo_step: Optional[int] = 1,
-                 *, dtype: str = 'fp16', max_batch: int = 64, tracker=None):
+                 *, dtype: str = 'fp16', max_batch: int = 64, tracker=None, flip_test=None, shift_heatmap: bool = False):
         state_dict = None
         dataset_given = dataset is not None
         if isinstance(model, (str, os.PathLike)):
@@ -138,8 +139,13 @@ class VitInference:
             nk = int(np.asarray(state_dict['keypoint_head.final_layer.bias']).shape[0])
         self.target_size = [IMG_W, IMG_H]  # data_cfg['image_size'], ViTPose_common.py:30
         dev_id = int(str(device).split(':')[1]) if ':' in str(device) else 0
-        self._vit_pose = VitPoseHip(model_shape(model_name, None if nk else dataset, nk), state_dict,
+        shape = model_shape(model_name, None if nk else dataset, nk)
+        # flip_test (the reference's test configs: flip_test=True): a pair list, or True for the COCO-17 table; refused before anything is loaded
+        flip_pairs = resolve_flip_pairs(flip_test, dataset, shape.num_keypoints)
+        self._vit_pose = VitPoseHip(shape, state_dict,
                                     dtype=dtype, device_id=dev_id, max_batch=max_batch, dataset=dataset if plus else None)
+        if flip_pairs is not None:   # a mode of the handle: every call below (inference, inference_frames, the boxes route) inherits it
+            self._vit_pose.set_flip_test(flip_pairs, shift_heatmap)
         self._inference = self._inference_hip
 
     @staticmethod

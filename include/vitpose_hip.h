@@ -253,7 +253,43 @@ VP_API int vp_infer_boxes_stream(vp_handle h, const vp_frame* frames, int32_t n_
 VP_API int vp_infer_flip(vp_handle h, const void* crops, int32_t input_format, int32_t n, const int32_t* org_wh,
                          const int32_t* flip_pairs, int32_t n_pairs, int32_t shift_heatmap, float* out, float* heatmaps);
 
-/* Parity/debug taps.  Heatmaps = ViTPose.forward output, float32 [N, K, 64, 48]. */
+/* Flip-test as a MODE of the handle (how the reference's test configs quote accuracy: flip_test=True).  After vp_set_flip_test every entry that
+ * decodes keypoints -- vp_infer, vp_infer_device, vp_infer_device_stream, vp_infer_submit / vp_infer_wait, vp_infer_frame, vp_infer_frames,
+ * vp_infer_boxes_stream, vp_group_infer / vp_group_infer_allgather (set on every member: vp_group_set_flip_test) -- returns the keypoints of
+ * 0.5 (heatmaps(crop) + flip_back(heatmaps(mirrored crop))), in that entry's own output layout and coordinate frame, and vp_infer_heatmaps returns
+ * those averaged maps.  flip_pairs / shift_heatmap as in vp_infer_flip; the pairs are validated against the ACTIVE head's K and uploaded once.
+ *   How it runs: the crops and their mirror images form ONE forward batch of twice the rows (crop, mirror, crop, mirror, ...), planned, padded and
+ *   replayed from a hipGraph like any batch of that size, and the decode averages the two maps of a joint on the fly.  A chunk therefore holds
+ *   max_batch / 2 of the caller's crops (vp_infer_submit: 1 .. max_batch / 2 per call), the small-batch thresholds (VP_GRAPH, VP_CALLER_STREAM)
+ *   count the rows that run (2 n), and n crops under the mode are a 2 n batch: bit identity with another batch size or with vp_infer_flip (two
+ *   passes of n) is NOT promised -- equal within the rounding of the 16-bit GEMMs, run-to-run identical.
+ *   Not under the mode: vp_infer_tokens and vp_infer_flip (unchanged, whatever the mode); vp_infer_experts returns VP_ERR_STATE while it is on.
+ *   ViTPose+ handles: the mode belongs to the active expert's joints.  vp_set_expert to a head with the same K keeps it; to a head with another K the
+ *   switch takes place, the mode is CLEARED and the call returns VP_ERR_STATE saying so (set it again with that dataset's pairs).
+ *   fp8 handles: the mode sits above the encoder and runs as it does on fp16 (exactness of the fused decode and run-to-run identity are tested, parity figures are not).
+ * VP_ERR_INVALID: n_pairs < 0, NULL pairs with n_pairs > 0, a joint index outside [0, K).  VP_ERR_STATE: weights not loaded, a vp_infer_submit in
+ * flight, or max_batch == 1 (a crop and its mirror share the batch; there is no hidden two-pass fallback).  The set waits for the handle's
+ * enqueued work (the table may still be read).  vp_clear_flip_test: back to the default; a handle whose mode was never set, or was cleared, runs exactly the launches it ran before.
+ * vp_flip_test_enabled: 1 while the mode is on.  Library builds that carry the mode define VP_HAS_FLIP_TEST_MODE. */
+#define VP_HAS_FLIP_TEST_MODE 1
+VP_API int vp_set_flip_test(vp_handle h, const int32_t* flip_pairs, int32_t n_pairs, int32_t shift_heatmap);
+VP_API int vp_clear_flip_test(vp_handle h);
+VP_API int vp_flip_test_enabled(vp_handle h);
+/* the same on every member of a group (all or none: a member's refusal clears the mode on all of them).  vp_group_infer* return VP_ERR_STATE
+ * when the members disagree on the mode (set through vp_group_member one by one). */
+VP_API int vp_group_set_flip_test(vp_group_handle g, const int32_t* flip_pairs, int32_t n_pairs, int32_t shift_heatmap);
+VP_API int vp_group_clear_flip_test(vp_group_handle g);
+/* HOST ONLY taps of the mode's pure functions: the partner table of k joints (partner may be NULL: validation only; the reason of a refusal is in
+ * vp_last_error(NULL)), and the interleaved batch's index function -- src[r] / mirror[r] = the source crop of output row r in [0, rows) and whether
+ * it is mirrored, for n crops in a forward of rows >= 2 n crops (rows beyond 2 n repeat the last one). */
+VP_API int vp_dbg_flip_partner(int32_t k, const int32_t* flip_pairs, int32_t n_pairs, int32_t* partner);
+VP_API int vp_dbg_flip_layout(int32_t n, int32_t rows, int32_t* src, int32_t* mirror);
+/* The mode's decode kernel alone, on host data (as vp_decode_only): heatmaps2 = float32 [2 n, k, 64, 48], crop i's maps at 2 i and its mirror
+ * image's at 2 i + 1 -> out [n, k, 3] = vp_decode_only of 0.5 (crop + flip_back(mirror)), bit for bit, without forming that tensor. */
+VP_API int vp_dbg_decode_flip(int32_t device_id, const float* heatmaps2, int32_t n, int32_t k, const int32_t* flip_pairs, int32_t n_pairs,
+                              int32_t shift_heatmap, const int32_t* org_wh, float* out);
+
+/* Parity/debug taps.  Heatmaps = ViTPose.forward output, float32 [N, K, 64, 48] (under the flip-test mode: the averaged maps). */
 VP_API int vp_infer_heatmaps(vp_handle h, const void* crops, int32_t input_format, int32_t n, float* heatmaps);
 /* Backbone output after last_norm (vit.py:387), float32 [N, 192, D]. */
 VP_API int vp_infer_tokens(vp_handle h, const void* crops, int32_t input_format, int32_t n, float* tokens);
