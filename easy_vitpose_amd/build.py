@@ -27,7 +27,7 @@ LIBDIR = os.path.join(HERE, '_lib')
 LIB = os.path.join(LIBDIR, 'libvitpose_hip.so')
 TOOLS_LIB = os.path.join(LIBDIR, 'libvitpose_hip_tools.so')
 SOURCES = ['gemm.hip', 'gemm8.hip', 'gemm8f.hip', 'qkvattn.hip', 'quant8.hip', 'attention.hip', 'elementwise.hip', 'decode.hip', 'boxes.hip', 'fp8_probe.hip',
-           'vitpose_api.hip', 'weights.hip', 'tile_rules.hip', 'debug_taps.hip']
+           'handle.hip', 'forward.hip', 'infer.hip', 'group.hip', 'weights.hip', 'tile_rules.hip', 'debug_taps.hip']
 TOOLS_SOURCES = SOURCES
 HEADERS = ['common.h', 'kernels.h', 'gemm8_common.h', 'mx8.h', 'api_internal.h', 'boxgeom.h', os.path.join('..', '..', 'include', 'vitpose_hip.h'),
            os.path.join('..', '..', 'include', 'vitpose_hip_tools.h')]

@@ -1,5 +1,8 @@
 // Internal header shared by the translation units behind the C ABI (include/vitpose_hip.h):
-//   vitpose_api.hip  -- handle, streams, forward orchestration, the ABI entry points, the multi-device group
+//   handle.hip       -- the handle: vp_create / vp_destroy, the switches, the guards of every entry, its modes (expert, flip-test), profiling, vp_synchronize
+//   forward.hip      -- the forward of a chunk: gemm / gemm_fp8, forward_chunk, head_chunk, decode_chunk, run_chunk and its hipGraph cache
+//   infer.hip        -- the inference entries and their staging (vp_infer*: host / device crops, the two slots, frames, boxes, experts, flip), stream adoption
+//   group.hip        -- the multi-device group (vp_group*)
 //   weights.hip      -- the weight packer (vp_load_weights: BN / LayerNorm folding, 16-bit / e4m3 conversion, deconv re-tiling)
 //   tile_rules.hip   -- which GEMM tile runs a shape (pure host functions + their host-only taps)
 //   debug_taps.hip   -- vp_dbg_*: one kernel on host data (parity tests), and the measurement build's timing taps
@@ -107,8 +110,8 @@ struct vp_ctx {
     float* x = nullptr;
     uint16_t *y = nullptr, *qkv = nullptr, *hid = nullptr, *d1 = nullptr, *d2 = nullptr;
     float *hm = nullptr, *kp = nullptr, *tok = nullptr;
-    float* hm_keep = nullptr;         // flip-test: heatmaps of the un-flipped crops while the flipped pass runs
-    int32_t* partner = nullptr;       // flip-test: mirror joint per joint
+    float* hm_keep = nullptr;         // vp_infer_flip only: heatmaps of the un-flipped crops while the flipped pass runs
+    int32_t* partner = nullptr;       // vp_infer_flip only: mirror joint per joint, rewritten per call (the MODE below has its own flip_table)
     // flip-test MODE (vp_set_flip_test): every chunk of run_chunk / vp_infer_heatmaps runs its crops and their mirror images as one interleaved batch of twice
     // the rows (elementwise.hip im2col_twin_kernel) and decodes the average without materialising it (decode.hip decode_kernel<true>).  A chunk then holds
     // max_batch / 2 of the caller's crops (chunk_cap).  flip_gen = 0 while off, a fresh value per vp_set_flip_test: part of the hipGraph key, since the table
@@ -141,12 +144,20 @@ struct vp_ctx {
     hipStream_t copy_stream = nullptr;   // H2D of the asynchronous path
     hipStream_t d2h_stream = nullptr;    // D2H on its own stream: an in-order copy stream would hold the next upload behind `wait compute; download`
     int next_slot = 0;
-    // small batches: the whole forward + decode of a chunk captured once per (n, input format, source pointer) into a hipGraph and
-    // replayed (170+ launches of a few microseconds each are launch-bound below ~16 crops); VP_GRAPH=0 disables
-    struct GraphEntry { hipGraphExec_t exec = nullptr; int n = 0, fmt = -1, seen = 0; bool no_graph = false; const void* src = nullptr; const int32_t* wh = nullptr; float* out = nullptr;
-                        int expert = 0;     // expert: a ViTPose+ handle's active expert is baked into the captured launches (fc2 weights, head, K)
-                        const int32_t* post = nullptr;   // vp_infer_boxes_stream: the frame-offset kernel after the decode (its aux buffer; null: none)
-                        uint32_t flip = 0; };            // the flip-test mode's generation the launches were captured under (flip_gen; 0: mode off)
+    // small batches: the whole forward + decode of a chunk captured once per key into a hipGraph and replayed (170+ launches of a few microseconds
+    // each are launch-bound below ~16 crops); VP_GRAPH=0 disables.  The key = everything baked into the captured launches: a new field is one edit here
+    // (run_chunk builds the key once per call, compares it on lookup and stores it on first sighting)
+    struct GraphKey {
+        int n = 0, fmt = -1;
+        const void* src = nullptr; const int32_t* wh = nullptr; float* out = nullptr;
+        int expert = 0;                  // a ViTPose+ handle's active expert (fc2 weights, head, K)
+        const int32_t* post = nullptr;   // vp_infer_boxes_stream: the frame-offset kernel after the decode (its aux buffer; null: none)
+        uint32_t flip = 0;               // the flip-test mode's generation the launches were captured under (flip_gen; 0: mode off)
+        bool operator==(const GraphKey& o) const {
+            return n == o.n && fmt == o.fmt && src == o.src && wh == o.wh && out == o.out && expert == o.expert && post == o.post && flip == o.flip;
+        }
+    };
+    struct GraphEntry { GraphKey key; hipGraphExec_t exec = nullptr; bool no_graph = false; };   // no_graph: capture or launch failed once, the key stays eager
     GraphEntry graphs[4];
     int graph_victim = 0;
     // split-K workspace of the residual GEMMs of small batches: fp32 partial products [S][M][D] of up to splitk_rows token rows (none when Switches::splitk_on is off)
@@ -192,9 +203,17 @@ struct vp_ctx {
 
 namespace vpi {
 
+// ---- handle.hip
 extern thread_local std::string g_create_error;
 
 int fail(vp_ctx* c, int code, const std::string& msg);
+// the guards the entries share.  need_weights: VP_ERR_INVALID without a handle, VP_ERR_STATE before vp_load_weights.  slots_idle: VP_ERR_STATE
+// "<who> with a vp_infer_submit in flight ..." while a slot is busy.  quiesce: wait for everything enqueued on the handle's buffers, on a caller's stream too
+int need_weights(vp_ctx* c);
+bool slots_busy(const vp_ctx* c);
+int slots_idle(vp_ctx* c, const char* who);
+int quiesce(vp_ctx* c);
+inline size_t crop_bytes(int fmt) { return (size_t)3 * 256 * 192 * (fmt == VP_INPUT_F32_NCHW ? 4 : 1); }
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \
@@ -243,7 +262,7 @@ size_t final_rows(size_t kp);   // physical (hi/lo interleaved) rows of the fina
 int pack_deconv(vp_ctx* c, Lookup& lk, int idx, int Cin, uint16_t** w_out, float** b_out, const std::string& head = "keypoint_head");
 void use_expert(vp_ctx* c, int e);   // make expert e of a ViTPose+ handle the active one (head pointers, Kp)
 
-// ---- vitpose_api.hip
+// ---- handle.hip
 // flip-test mode (HOST ONLY): partner[k] = the mirror joint of k among K joints (k itself when unpaired) from n_pairs x 2 indices; VP_OK or VP_ERR_INVALID with the reason in *why
 int flip_partner_table(int K, const int32_t* pairs, int n_pairs, int32_t* partner, std::string* why);
 bool prof_begin(vp_ctx* c, int fam, double flops, double bytes);
@@ -251,6 +270,8 @@ void prof_end(vp_ctx* c, bool on);
 void prof_collect(vp_ctx* c);
 void read_switches(Switches& s);      // the environment's switches (vp_create, vp_dbg_chunk_plan)
 void apply_gemm_tuning(Switches& s);  // its VP_GEMM_TUNE part (tools build only): what the parity taps' contexts take
+
+// ---- infer.hip
 // vp_infer_frames' plan (HOST ONLY): checks every crop of p9 [n, 9] against its frame, bands [n_frames, 2] = rows [row0, row1) its crops cover
 // ({0, 0}: no crop; may be NULL).  VP_OK or VP_ERR_INVALID with the reason in *why
 int frame_plan(const vp_frame* frames, int n_frames, const int32_t* p9, int n, int32_t* bands, std::string* why);
@@ -261,6 +282,8 @@ int stage_frames(vp_ctx* c, const vp_frame* frames, int n_frames, bool on_device
 // vp_infer_boxes_stream / vp_dbg_box_geometry (HOST ONLY): the host arguments of a boxes call (sizes of every frame, row stride, pad, counts).
 // VP_OK or VP_ERR_INVALID with the reason in *why
 int box_args(int n_frames, const int32_t* frame_hw, int hw_stride, int row_stride, int n, int pad, std::string* why);
+// vp_infer_submit; stage_out (the group path): the download lands in the slot's pinned buffer and vp_infer_wait copies it to `out`
+int submit_impl(vp_ctx* c, const void* crops, int32_t fmt, int32_t n, const int32_t* org_wh, float* out, int32_t* slot_out, bool stage_out);
 
 #define LAUNCH(c, fam, flops, bytes, expr)   \
     do {                                     \
@@ -310,10 +333,24 @@ struct ChunkPlan {
 ChunkPlan plan_chunk(const Switches& s, int D, int heads, int max_batch, bool fp8, int n_in, size_t fin_rows, const std::vector<int>* mix_bounds = nullptr);
 HeadPlan plan_head(const Switches& s, int D, int nh, size_t fin_rows);
 
-// ---- vitpose_api.hip: one GEMM of the path as `pk` resolved it (also what the vp_dbg_gemm* taps launch)
+// ---- forward.hip: one GEMM of the path as `pk` resolved it (also what the vp_dbg_gemm* taps launch).  EPI_DECONV_FINAL: `out` = the fp32 heatmaps
 int gemm(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint16_t* A, const uint16_t* W, const float* bias, void* out,
          const float* aux, int M, int N, int K, int ldo, int Hin = 0, int Win = 0, int Cin = 0, const LnFuse* ln = nullptr);
 int gemm_fp8(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint8_t* A8, const uint8_t* a_scales, const uint8_t* W8, const float* w_scale, const float* bias,
              void* out, uint8_t* out_scales, const float* aux, int M, int N, int K, const LnFuse* ln);
+// what a forward_chunk call asks for beyond the plain forward to heatmaps in c->hm
+struct FwdOpts {
+    bool tokens = false;   // also keep last_norm's fp32 tokens in c->tok (vp_infer_tokens)
+    bool mirror = false;   // the crops are read mirrored left-right (vp_infer_flip's second pass)
+    bool head = true;      // false: the encoder and last_norm only, tokens in c->y (vp_infer_experts runs the head per expert segment)
+    int twin_src = 0;      // > 0 (flip-test mode): n_in = 2 * twin_src rows, the twin_src crops at d_crops interleaved with their mirror images (crop, mirror, crop, mirror, ...)
+};
+int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, const FwdOpts& o = FwdOpts());
+int head_chunk(vp_ctx* c, const uint16_t* y, int nh, float* hm, const HeadPlan& hp);
+int decode_chunk(vp_ctx* c, const int32_t* d_wh, float* d_out, int n, bool twin);
+int chunk_cap(const vp_ctx* c);
+int chunk_rows(const vp_ctx* c, int nb);
+int forward_mode_chunk(vp_ctx* c, const void* d_src, int fmt, int nb);
+int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh, float* d_out, const int32_t* post = nullptr);
 
 }  // namespace vpi

@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void im2col_kernel(const void* __restrict__ in
     constexpr int XS = 208;                                  // LDS row: x = -2 .. 205 (index x + 2)
     __shared__ __attribute__((aligned(16))) uint16_t tile[3 * 16 * XS];
     const int tid = threadIdx.x;
-    const int bo = blockIdx.x >> 4, py = blockIdx.x & 15;    // output crop bo reads source crop min(bo, n_src - 1): the rows of a padded encoder batch (vitpose_api.hip forward_chunk) repeat the last crop
+    const int bo = blockIdx.x >> 4, py = blockIdx.x & 15;    // output crop bo reads source crop min(bo, n_src - 1): the rows of a padded encoder batch (forward.hip forward_chunk) repeat the last crop
     const int b = min(bo, n_src - 1);
     const int ytop = 16 * py - 2;
     if (FMT == VP_INPUT_F32_NCHW) {

@@ -1,0 +1,662 @@
+// The inference entries of the C ABI (include/vitpose_hip.h) and their staging: host crops, device crops on the handle's or a caller's stream,
+// the two asynchronous slots, frames, device boxes, ViTPose+ mixed batches, vp_infer_flip.  Each walks its crops in chunks (for_chunks) and hands
+// a chunk to forward.hip.
+#include "api_internal.h"
+#include "boxgeom.h"
+
+using namespace vpi;
+
+namespace {
+
+// The one walk over n crops in chunks of at most cap: body(off, nb) for crops [off, off + nb), stopping at the first error
+template <class Body> int for_chunks(int n, int cap, Body body) {
+    for (int off = 0; off < n; off += cap)
+        if (const int rc = body(off, std::min(n - off, cap))) return rc;
+    return VP_OK;
+}
+
+// The host-staged chunk: crops [off, off + nb) of a host batch into in_stage and, where given, their sizes into wh_stage, on c->stream ...
+int stage_in(vp_ctx* c, const void* crops, int fmt, const int32_t* org_wh, int off, int nb) {
+    HIPCHK(c, hipMemcpyAsync(c->in_stage, (const char*)crops + (size_t)off * crop_bytes(fmt), (size_t)nb * crop_bytes(fmt), hipMemcpyHostToDevice, c->stream));
+    if (org_wh) HIPCHK(c, hipMemcpyAsync(c->wh_stage, org_wh + 2 * (size_t)off, (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
+    return VP_OK;
+}
+// ... and nb results of `elem` floats each from d_res back to rows [off, off + nb) of the caller's `out`; copy_out_sync also waits for the chunk:
+// the staging buffers are rewritten by the next one
+int copy_out(vp_ctx* c, float* out, const float* d_res, size_t elem, int off, int nb) {
+    HIPCHK(c, hipMemcpyAsync(out + (size_t)off * elem, d_res, (size_t)nb * elem * 4, hipMemcpyDeviceToHost, c->stream));
+    return VP_OK;
+}
+int copy_out_sync(vp_ctx* c, float* out, const float* d_res, size_t elem, int off, int nb) {
+    if (const int rc = copy_out(c, out, d_res, elem, off, nb)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VP_OK;
+}
+
+// vp_infer_device / vp_infer_device_stream: n device-resident crops through run_chunk on c->stream (the entries differ in the ordering around this)
+int device_chunks(vp_ctx* c, const void* d_crops, int fmt, int n, const int32_t* d_wh, float* d_out) {
+    return for_chunks(n, chunk_cap(c), [&](int off, int nb) {
+        return run_chunk(c, (const char*)d_crops + (size_t)off * crop_bytes(fmt), fmt, nb, d_wh ? d_wh + 2 * (size_t)off : nullptr, d_out + (size_t)off * c->Kp * 3);
+    });
+}
+
+// frame f of a call that reads its frames in place: device memory of the handle's device, the whole frame inside one allocation.  A null frame
+// fails here too: vp_infer_boxes_stream relies on it (vp_infer_frames has refused one in frame_plan, with the crop that names it)
+int check_device_frame(vp_ctx* c, const vp_frame& fr, int f) {
+    hipPointerAttribute_t a;
+    std::memset(&a, 0, sizeof(a));
+    void* base = nullptr;
+    size_t size = 0;
+    bool ok = fr.data && hipPointerGetAttributes(&a, fr.data) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->cfg.device_id;
+    ok = ok && hipMemGetAddressRange(&base, &size, (void*)fr.data) == hipSuccess && fr.data + (size_t)fr.h * fr.w * 3 <= (const uint8_t*)base + size;
+    if (ok) return VP_OK;
+    (void)hipGetLastError();
+    return fail(c, VP_ERR_INVALID, "frame " + std::to_string(f) + " is not device memory of device " + std::to_string(c->cfg.device_id) +
+                                       " (or runs past the end of its allocation)");
+}
+
+// A grow-only device buffer of the handle (*buf, *cap bytes) holds at least `bytes`: the larger one is allocated first, then the smaller one is
+// released (never shrunk: growing inputs must not grow device memory without bound), so a failed allocation leaves the handle usable
+template <class T> int grow_buffer(vp_ctx* c, T** buf, size_t* cap, size_t bytes, const char* what) {
+    if (bytes <= *cap) return VP_OK;
+    void* q = nullptr;
+    if (*buf) HIPCHK(c, hipStreamSynchronize(c->stream));   // enqueued work may still read the old one
+    if (hipMalloc(&q, bytes + 256) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, VP_ERR_HIP, "cannot allocate a " + std::to_string(bytes) + "-byte " + what);
+    }
+    if (*buf) {
+        const auto it = std::find(c->allocs.begin(), c->allocs.end(), (void*)*buf);
+        if (it != c->allocs.end()) c->allocs.erase(it);
+        hipFree(*buf);
+    }
+    c->allocs.push_back(q);
+    *buf = (T*)q;
+    *cap = bytes;
+    return VP_OK;
+}
+
+// Work on the handle's buffers is about to be enqueued on stream s: order it behind whatever the previous call left on ANOTHER stream.
+//   own -> own, caller A -> caller A: nothing (in-order streams);  own -> caller: record on own, caller waits;  caller -> own / another caller: wait for ev_sw,
+//   which vp_infer_device_stream recorded on the caller's stream behind its launches (that stream itself is never touched again: it may be gone).
+int adopt_stream(vp_ctx* c, hipStream_t s) {
+    if (!c->foreign_pending && s == c->own_stream) return VP_OK;
+    if (c->foreign_pending && (const void*)s == c->last_stream_id && s != c->own_stream) return VP_OK;
+    if (!c->ev_sw) HIPCHK(c, hipEventCreateWithFlags(&c->ev_sw, hipEventDisableTiming));
+    if (!c->foreign_pending) HIPCHK(c, hipEventRecord(c->ev_sw, c->own_stream));
+    HIPCHK(c, hipStreamWaitEvent(s, c->ev_sw, 0));
+    if (s == c->own_stream) c->foreign_pending = false;
+    return VP_OK;
+}
+
+int check_ready(vp_ctx* c, int fmt, int n, const void* p0, const void* p1, bool adopt_own = true) {
+    if (const int rc = need_weights(c)) return rc;
+    if (fmt != VP_INPUT_F32_NCHW && fmt != VP_INPUT_U8_NHWC) return fail(c, VP_ERR_INVALID, "unknown input_format");
+    if (n < 0 || (n > 0 && (!p0 || !p1))) return fail(c, VP_ERR_INVALID, "null buffer or negative batch");
+    hipError_t e = hipSetDevice(c->cfg.device_id);
+    if (e != hipSuccess) return fail(c, VP_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
+    return adopt_own ? adopt_stream(c, c->own_stream) : VP_OK;   // every entry but the caller-stream path works on the handle's own stream
+}
+
+// The ordering of the caller-stream entries (vp_infer_device_stream, vp_infer_boxes_stream): `chunks` enqueues the call's work on c->stream.
+// Batches of 1 .. caller_stream_max_n crops (<= max_batch) run ON the caller's stream -- in order with its producers and consumers by construction,
+// no cross-stream dependency per call (two of them cost ~0.1 ms of a 0.6-2.4 ms step: profiles/small_batch_r5.txt); ev_sw, recorded behind the
+// launches, is what the next call on any other stream (and vp_synchronize / vp_destroy) waits for.  Larger batches run on the handle's own
+// stream, fenced against the caller's with ev_in / ev_out.
+template <class Chunks> int caller_ordered(vp_ctx* c, hipStream_t cs, int n, Chunks chunks) {
+    int rc;
+    if (n > 0 && chunk_rows(c, n) <= c->sw.caller_stream_max_n && n <= chunk_cap(c) && cs != c->own_stream) {
+        if ((rc = adopt_stream(c, cs))) return rc;
+        c->stream = cs;
+        rc = chunks();
+        c->stream = c->own_stream;
+        if (!c->ev_sw && hipEventCreateWithFlags(&c->ev_sw, hipEventDisableTiming) != hipSuccess) return fail(c, VP_ERR_HIP, "hipEventCreateWithFlags(ev_sw)");
+        const hipError_t er = hipEventRecord(c->ev_sw, cs);   // also when rc != 0: part of the chunk may be enqueued
+        c->foreign_pending = true;
+        c->last_stream_id = (const void*)cs;
+        if (rc) return rc;
+        if (er != hipSuccess) return fail(c, VP_ERR_HIP, std::string("hipEventRecord(ev_sw): ") + hipGetErrorString(er));
+        return VP_OK;
+    }
+    if ((rc = adopt_stream(c, c->own_stream))) return rc;
+    if (!c->ev_in) HIPCHK(c, hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
+    if (!c->ev_out) HIPCHK(c, hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming));
+    // everything the caller enqueued on its stream so far (the producers of the inputs) happens before the library's kernels ...
+    HIPCHK(c, hipEventRecord(c->ev_in, cs));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_in, 0));
+    if ((rc = chunks())) return rc;
+    // ... and whatever the caller enqueues afterwards (consumers of the outputs) happens after them
+    HIPCHK(c, hipEventRecord(c->ev_out, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(cs, c->ev_out, 0));
+    return VP_OK;
+}
+
+}  // namespace
+
+namespace vpi {   // shared with debug_taps.hip (vp_dbg_crop_prep) and group.hip (submit_impl)
+
+int frame_plan(const vp_frame* frames, int n_frames, const int32_t* p9, int n, int32_t* bands, std::string* why) {
+    auto bad = [&](const std::string& m) { if (why) *why = m; return VP_ERR_INVALID; };
+    if (n < 0) return bad("negative crop count");
+    if (n > 0 && n_frames <= 0) return bad("crops given but no frames");
+    if (n > 0 && (!frames || !p9)) return bad("null frame or crop table");
+    const int nf = n_frames > 0 ? n_frames : 0;
+    std::vector<int64_t> lo(nf, INT64_MAX), hi(nf, -1);
+    for (int i = 0; i < n; ++i) {
+        const int32_t* p = p9 + 9 * (size_t)i;
+        const int f = p[0];
+        const std::string at = "crop " + std::to_string(i) + ": ";
+        if (f < 0 || f >= n_frames) return bad(at + "frame index " + std::to_string(f) + " outside [0, " + std::to_string(n_frames) + ")");
+        const vp_frame& fr = frames[f];
+        if (!fr.data) return bad(at + "frame " + std::to_string(f) + " has no data");
+        if (fr.h <= 0 || fr.w <= 0) return bad(at + "frame " + std::to_string(f) + " has a non-positive size");
+        const int64_t x0 = p[1], y0 = p[2], cw = p[3], ch = p[4], left = p[5], top = p[6], pw = p[7], ph = p[8];
+        if (cw <= 0 || ch <= 0 || pw <= 0 || ph <= 0) return bad(at + "non-positive crop or canvas size");
+        if (x0 < 0 || y0 < 0 || x0 + cw > fr.w || y0 + ch > fr.h || left < 0 || top < 0 || left + cw > pw || top + ch > ph)
+            return bad(at + "lies outside frame " + std::to_string(f) + " / its padded canvas");
+        lo[f] = std::min(lo[f], y0);
+        hi[f] = std::max(hi[f], y0 + ch);
+    }
+    if (bands)
+        for (int f = 0; f < nf; ++f) {
+            bands[2 * f] = hi[f] < 0 ? 0 : (int32_t)lo[f];
+            bands[2 * f + 1] = hi[f] < 0 ? 0 : (int32_t)hi[f];
+        }
+    return VP_OK;
+}
+
+int stage_frames(vp_ctx* c, const vp_frame* frames, int n_frames, bool on_device, const int32_t* p9, int n, const int32_t* bands,
+                 std::vector<vp::CropRec>& recs) {
+    std::vector<const uint8_t*> row0_ptr(n_frames, nullptr);   // row bands[2 f] of frame f, where the kernel reads it
+    if (on_device) {
+        for (int f = 0; f < n_frames; ++f) {
+            if (bands[2 * f] == bands[2 * f + 1]) continue;
+            if (const int rc = check_device_frame(c, frames[f], f)) return rc;
+            row0_ptr[f] = frames[f].data + (size_t)bands[2 * f] * frames[f].w * 3;
+        }
+    } else {
+        std::vector<size_t> off(n_frames, 0);
+        size_t total = 0;
+        for (int f = 0; f < n_frames; ++f) {
+            if (bands[2 * f] == bands[2 * f + 1]) continue;
+            off[f] = total;
+            total += ((size_t)(bands[2 * f + 1] - bands[2 * f]) * frames[f].w * 3 + 255) & ~(size_t)255;
+        }
+        if (const int rc = grow_buffer(c, &c->frame_stage, &c->frame_cap, total, "frame staging arena")) return rc;
+        for (int f = 0; f < n_frames; ++f) {   // ONE copy per frame with crops: its row band, full width
+            if (bands[2 * f] == bands[2 * f + 1]) continue;
+            const size_t pitch = (size_t)frames[f].w * 3;
+            HIPCHK(c, hipMemcpyAsync(c->frame_stage + off[f], frames[f].data + (size_t)bands[2 * f] * pitch,
+                                     (size_t)(bands[2 * f + 1] - bands[2 * f]) * pitch, hipMemcpyHostToDevice, c->stream));
+            row0_ptr[f] = c->frame_stage + off[f];
+        }
+    }
+    recs.resize(n);
+    for (int i = 0; i < n; ++i) {
+        const int32_t* p = p9 + 9 * (size_t)i;
+        const int f = p[0];
+        const int64_t pitch = (int64_t)frames[f].w * 3;
+        vp::CropRec& r = recs[i];
+        r.src = row0_ptr[f] + (size_t)(p[2] - bands[2 * f]) * pitch + (size_t)p[1] * 3;
+        r.pitch = pitch;
+        r.cw = p[3]; r.ch = p[4]; r.left = p[5]; r.top = p[6]; r.pw = p[7]; r.ph = p[8];
+    }
+    return VP_OK;
+}
+
+int box_args(int n_frames, const int32_t* frame_hw, int hw_stride, int row_stride, int n, int pad, std::string* why) {
+    auto bad = [&](const std::string& m) { if (why) *why = m; return VP_ERR_INVALID; };
+    if (n < 0) return bad("negative box count");
+    if (row_stride < 4) return bad("row_stride " + std::to_string(row_stride) + " < 4 (x1, y1, x2, y2 per row)");
+    if (pad < 0) return bad("negative pad");
+    if (n > 0 && n_frames <= 0) return bad("boxes given but no frames");
+    for (int f = 0; f < n_frames && n > 0; ++f) {   // every frame of the table: the frame indices live on the device
+        const int32_t h = frame_hw[(size_t)f * hw_stride], w = frame_hw[(size_t)f * hw_stride + 1];
+        if (h <= 0 || w <= 0 || h > vp::BOX_MAX_SIDE || w > vp::BOX_MAX_SIDE)
+            return bad("frame " + std::to_string(f) + " has a size outside [1, 2^24]");
+    }
+    return VP_OK;
+}
+
+// ---- asynchronous host path ----------------------------------------------------------------------------------------------
+// true when `p` is page-locked host memory the runtime knows (hipHostMalloc / vp_host_alloc / hipHostRegister): only such memory is
+// copied asynchronously as it is
+static bool host_ptr_is_pinned(const void* p) {
+    hipPointerAttribute_t a;
+    std::memset(&a, 0, sizeof(a));
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // unknown to the runtime = pageable
+    return a.type == hipMemoryTypeHost;
+}
+
+// stage_out: the D2H targets the slot's own pinned buffer and vp_infer_wait copies it to `out` (the group path: the caller's
+// memory may be pageable, and an asynchronous copy to pageable memory is host-synchronous -- it would hold the submission until the
+// compute is over and serialise the devices of a group)
+int submit_impl(vp_ctx* c, const void* crops, int32_t fmt, int32_t n, const int32_t* org_wh, float* out, int32_t* slot_out, bool stage_out) {
+    int rc = check_ready(c, fmt, n, crops, out);
+    if (rc) return rc;
+    if (!slot_out) return fail(c, VP_ERR_INVALID, "null slot pointer");
+    if (n <= 0 || n > chunk_cap(c))
+        return fail(c, VP_ERR_INVALID, c->flip_on ? "vp_infer_submit takes 1 .. max_batch / 2 crops per call while the flip-test mode is on" : "vp_infer_submit takes 1 .. max_batch crops per call");
+    if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    if (!c->d2h_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking));
+    const int si = c->next_slot;
+    vp_ctx::Slot& sl = c->slots[si];
+    if (sl.busy) return fail(c, VP_ERR_STATE, "both slots in flight: call vp_infer_wait first");
+    if (!sl.in) {
+        char* q;
+        if ((rc = dalloc(c, &q, (size_t)c->maxb * crop_bytes(VP_INPUT_F32_NCHW)))) return rc;
+        sl.in = q;
+    }
+    if (!sl.wh && (rc = dalloc(c, &sl.wh, (size_t)c->maxb * 2))) return rc;
+    if (!sl.kp && (rc = dalloc(c, &sl.kp, (size_t)c->maxb * c->Kmax * 3))) return rc;
+    if (!sl.h2d) HIPCHK(c, hipEventCreateWithFlags(&sl.h2d, hipEventDisableTiming));
+    if (!sl.done) HIPCHK(c, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    if (!sl.out) HIPCHK(c, hipEventCreateWithFlags(&sl.out, hipEventDisableTiming));
+    // copy stream: H2D of this call (the slot's previous D2H finished: vp_infer_wait was called on it)
+    const size_t in_bytes = (size_t)n * crop_bytes(fmt);
+    if (stage_out && !host_ptr_is_pinned(crops)) {
+        // the group path with pageable caller memory: staged through the slot's pinned buffer in 4 MiB pieces, so that this call never
+        // waits for a device (hipMemcpyAsync from pageable memory held member i + 1's submission behind member i's staging)
+        if (sl.host_in_cap < in_bytes) {
+            if (sl.host_in) { HIPCHK(c, hipStreamSynchronize(c->copy_stream)); hipHostFree(sl.host_in); sl.host_in = nullptr; sl.host_in_cap = 0; }
+            void* q = nullptr;
+            HIPCHK(c, hipHostMalloc(&q, in_bytes, hipHostMallocDefault));
+            sl.host_in = (char*)q; sl.host_in_cap = in_bytes;
+        }
+        const size_t piece = (size_t)4 << 20;
+        for (size_t off = 0; off < in_bytes; off += piece) {
+            const size_t len = in_bytes - off < piece ? in_bytes - off : piece;
+            std::memcpy(sl.host_in + off, (const char*)crops + off, len);
+            HIPCHK(c, hipMemcpyAsync((char*)sl.in + off, sl.host_in + off, len, hipMemcpyHostToDevice, c->copy_stream));
+        }
+    } else {
+        HIPCHK(c, hipMemcpyAsync(sl.in, crops, in_bytes, hipMemcpyHostToDevice, c->copy_stream));
+    }
+    if (org_wh) HIPCHK(c, hipMemcpyAsync(sl.wh, org_wh, (size_t)n * 8, hipMemcpyHostToDevice, c->copy_stream));
+    HIPCHK(c, hipEventRecord(sl.h2d, c->copy_stream));
+    // compute stream: after the upload
+    HIPCHK(c, hipStreamWaitEvent(c->stream, sl.h2d, 0));
+    if ((rc = run_chunk(c, sl.in, fmt, n, org_wh ? sl.wh : nullptr, sl.kp))) return rc;
+    HIPCHK(c, hipEventRecord(sl.done, c->stream));
+    // download stream: D2H of the keypoints after the compute
+    HIPCHK(c, hipStreamWaitEvent(c->d2h_stream, sl.done, 0));
+    float* dst = out;
+    sl.user_out = nullptr;
+    if (stage_out) {
+        if (!sl.host_kp) {
+            void* q = nullptr;
+            HIPCHK(c, hipHostMalloc(&q, (size_t)c->maxb * c->Kmax * 12, hipHostMallocDefault));
+            sl.host_kp = (float*)q;
+        }
+        dst = sl.host_kp;
+        sl.user_out = out;
+        sl.out_bytes = (size_t)n * c->Kp * 12;
+    }
+    HIPCHK(c, hipMemcpyAsync(dst, sl.kp, (size_t)n * c->Kp * 12, hipMemcpyDeviceToHost, c->d2h_stream));
+    HIPCHK(c, hipEventRecord(sl.out, c->d2h_stream));
+    sl.busy = true;
+    *slot_out = si;
+    c->next_slot = si ^ 1;
+    return VP_OK;
+}
+
+}  // namespace vpi
+
+extern "C" {
+
+int vp_infer_device(vp_handle c, const void* d_crops, int32_t fmt, int32_t n, const int32_t* d_org_wh, float* d_out, int32_t sync) {
+    int rc = check_ready(c, fmt, n, d_crops, d_out);
+    if (rc || (rc = device_chunks(c, d_crops, fmt, n, d_org_wh, d_out))) return rc;
+    if (sync) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VP_OK;
+}
+
+int vp_infer_device_stream(vp_handle c, const void* d_crops, int32_t fmt, int32_t n, const int32_t* d_org_wh, float* d_out, void* caller_stream) {
+    const int rc = check_ready(c, fmt, n, d_crops, d_out, false);
+    if (rc) return rc;
+    return caller_ordered(c, (hipStream_t)caller_stream, n, [&]() { return device_chunks(c, d_crops, fmt, n, d_org_wh, d_out); });
+}
+
+int vp_infer(vp_handle c, const void* crops, int32_t fmt, int32_t n, const int32_t* org_wh, float* out) {
+    int rc = check_ready(c, fmt, n, crops, out);
+    if (rc) return rc;
+    const int cap = chunk_cap(c);
+    if (n > cap && !slots_busy(c)) {
+        // more than one chunk: through the two asynchronous slots, so that the upload of chunk i+1 and the download of chunk i-1
+        // run under the compute of chunk i (fully overlapped when the caller's buffers are pinned; pageable buffers still work,
+        // the runtime stages them synchronously)
+        int pending[2], np = 0;
+        rc = for_chunks(n, cap, [&](int off, int nb) -> int {
+            int32_t slot = -1;
+            int r = vp_infer_submit(c, (const char*)crops + (size_t)off * crop_bytes(fmt), fmt, nb, org_wh ? org_wh + 2 * (size_t)off : nullptr,
+                                    out + (size_t)off * c->Kp * 3, &slot);
+            if (r) return r;
+            pending[np++] = slot;
+            if (np < 2) return VP_OK;
+            r = vp_infer_wait(c, pending[0]);
+            pending[0] = pending[1]; np = 1;
+            return r;
+        });
+        for (int i = 0; i < np; ++i) {   // whatever is still in flight, after an error too; the first error is the call's
+            const int r = vp_infer_wait(c, pending[i]);
+            if (!rc) rc = r;
+        }
+        return rc;
+    }
+    return for_chunks(n, cap, [&](int off, int nb) -> int {
+        int r = stage_in(c, crops, fmt, org_wh, off, nb);
+        if (r || (r = run_chunk(c, c->in_stage, fmt, nb, org_wh ? c->wh_stage : nullptr, c->kp))) return r;
+        return copy_out_sync(c, out, c->kp, (size_t)c->Kp * 3, off, nb);
+    });
+}
+
+int vp_infer_submit(vp_handle c, const void* crops, int32_t fmt, int32_t n, const int32_t* org_wh, float* out, int32_t* slot_out) {
+    return submit_impl(c, crops, fmt, n, org_wh, out, slot_out, false);
+}
+
+int vp_infer_wait(vp_handle c, int32_t slot) {
+    if (!c || slot < 0 || slot > 1) return VP_ERR_INVALID;
+    vp_ctx::Slot& sl = c->slots[slot];
+    if (!sl.busy) return fail(c, VP_ERR_STATE, "slot not in flight");
+    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HIPCHK(c, hipEventSynchronize(sl.out));
+    if (sl.user_out) { std::memcpy(sl.user_out, sl.host_kp, sl.out_bytes); sl.user_out = nullptr; }
+    sl.busy = false;
+    return VP_OK;
+}
+
+int vp_infer_flip(vp_handle c, const void* crops, int32_t fmt, int32_t n, const int32_t* org_wh, const int32_t* flip_pairs,
+                  int32_t n_pairs, int32_t shift_heatmap, float* out, float* heatmaps) {
+    int rc = check_ready(c, fmt, n, crops, out ? (const void*)out : (const void*)heatmaps);
+    if (rc) return rc;
+    if (n_pairs < 0 || (n_pairs > 0 && !flip_pairs)) return fail(c, VP_ERR_INVALID, "bad flip_pairs");
+    if (n == 0) return VP_OK;   // nothing to do (and no async upload of the stack-lifetime partner table left in flight)
+    std::vector<int32_t> partner(c->Kp);
+    std::string why;
+    if (flip_partner_table(c->Kp, flip_pairs, n_pairs, partner.data(), &why)) return fail(c, VP_ERR_INVALID, "vp_infer_flip: " + why);
+    const size_t hm_elems = (size_t)c->maxb * c->Kmax * 3072;
+    if (!c->hm_keep && (rc = dalloc(c, &c->hm_keep, hm_elems))) return rc;
+    if (!c->partner && (rc = dalloc(c, &c->partner, (size_t)c->Kmax))) return rc;
+    HIPCHK(c, hipMemcpy(c->partner, partner.data(), (size_t)c->Kp * 4, hipMemcpyHostToDevice));   // synchronous: `partner` is a local
+    FwdOpts mirrored;
+    mirrored.mirror = true;
+    return for_chunks(n, c->maxb, [&](int off, int nb) -> int {   // its own two passes of up to max_batch crops, whatever the handle's mode
+        int rc = stage_in(c, crops, fmt, org_wh, off, nb);
+        if (rc || (rc = forward_chunk(c, c->in_stage, fmt, nb))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->hm_keep, c->hm, (size_t)nb * c->Kp * 3072 * 4, hipMemcpyDeviceToDevice, c->stream));
+        if ((rc = forward_chunk(c, c->in_stage, fmt, nb, mirrored))) return rc;   // mirrored crops -> c->hm
+        HIPCHK(c, vp::flip_merge_launch(c->hm_keep, c->hm, c->partner, nb, c->Kp, shift_heatmap ? 1 : 0, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->hm, c->hm_keep, (size_t)nb * c->Kp * 3072 * 4, hipMemcpyDeviceToDevice, c->stream));
+        if (heatmaps && (rc = copy_out(c, heatmaps, c->hm, (size_t)c->Kp * 3072, off, nb))) return rc;
+        if (out && ((rc = decode_chunk(c, org_wh ? c->wh_stage : nullptr, c->kp, nb, false)) || (rc = copy_out(c, out, c->kp, (size_t)c->Kp * 3, off, nb)))) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return VP_OK;
+    });
+}
+
+int vp_infer_heatmaps(vp_handle c, const void* crops, int32_t fmt, int32_t n, float* heatmaps) {
+    int rc = check_ready(c, fmt, n, crops, heatmaps);
+    if (rc) return rc;
+    const size_t map_elems = (size_t)c->Kp * 3072, map_bytes = map_elems * 4;
+    return for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {
+        int rc = stage_in(c, crops, fmt, nullptr, off, nb);
+        if (rc || (rc = forward_mode_chunk(c, c->in_stage, fmt, nb))) return rc;
+        if (!c->flip_on) return copy_out_sync(c, heatmaps, c->hm, map_elems, off, nb);
+        // the averaged maps, materialised in the straight crops' slots (every second one of the interleaved batch)
+        HIPCHK(c, vp::flip_merge_launch(c->hm, c->hm + map_elems, c->flip_table, nb, c->Kp, c->flip_shift, c->stream, 1));
+        HIPCHK(c, hipMemcpy2DAsync(heatmaps + (size_t)off * map_elems, map_bytes, c->hm, 2 * map_bytes, map_bytes, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return VP_OK;
+    });
+}
+
+int vp_infer_tokens(vp_handle c, const void* crops, int32_t fmt, int32_t n, float* tokens) {
+    int rc = check_ready(c, fmt, n, crops, tokens);
+    if (rc) return rc;
+    if (!c->tok && (rc = dalloc(c, &c->tok, (size_t)c->maxb * 192 * c->D))) return rc;
+    FwdOpts with_tokens;
+    with_tokens.tokens = true;
+    return for_chunks(n, c->maxb, [&](int off, int nb) -> int {
+        int rc = stage_in(c, crops, fmt, nullptr, off, nb);
+        if (rc || (rc = forward_chunk(c, c->in_stage, fmt, nb, with_tokens))) return rc;
+        return copy_out_sync(c, tokens, c->tok, (size_t)192 * c->D, off, nb);
+    });
+}
+
+int vp_infer_experts(vp_handle c, const void* crops, int32_t fmt, int32_t n, const int32_t* expert_ids, const int32_t* org_wh, float* out) {
+    int rc = check_ready(c, fmt, n, crops, out);
+    if (rc) return rc;
+    if (!c->n_experts) return fail(c, VP_ERR_STATE, "vp_infer_experts: the handle holds a plain (single-dataset) checkpoint, not a ViTPose+ one");
+    if (n > 0 && !expert_ids) return fail(c, VP_ERR_INVALID, "null expert_ids");
+    for (int i = 0; i < n; ++i)
+        if (expert_ids[i] < 0 || expert_ids[i] >= c->n_experts)
+            return fail(c, VP_ERR_INVALID, "expert id " + std::to_string(expert_ids[i]) + " of crop " + std::to_string(i) + " outside [0, " + std::to_string(c->n_experts) + ")");
+    if ((rc = slots_idle(c, "vp_infer_experts"))) return rc;
+    if (c->flip_on) return fail(c, VP_ERR_STATE, "vp_infer_experts does not run under the flip-test mode (one partner table per handle, not per crop): call vp_clear_flip_test first");
+    // per chunk, the crops in expert order (stable): each expert is one contiguous segment, so that mlp.fc2's m-tiles see one expert and the head runs once per expert
+    const int saved = c->expert, D = c->D;
+    const size_t cb = crop_bytes(fmt), B = (size_t)((c->maxb + 3) / 4 * 4);
+    std::vector<int32_t> ids(2 * B), wh(2 * (size_t)c->maxb);
+    std::vector<int> order(c->maxb);
+    std::vector<float> kp((size_t)c->maxb * c->Kmax * 3);
+    FwdOpts encoder_only;
+    encoder_only.head = false;
+    rc = for_chunks(n, c->maxb, [&](int off, int nb) -> int {
+        int rc;
+        for (int j = 0; j < nb; ++j) order[j] = off + j;
+        std::stable_sort(order.begin(), order.begin() + nb, [&](int a, int b) { return expert_ids[a] < expert_ids[b]; });
+        bool identity = true;
+        for (int j = 0; j < nb; ++j) identity = identity && order[j] == off + j;
+        if (identity) {
+            if ((rc = stage_in(c, crops, fmt, nullptr, off, nb))) return rc;   // (the sizes follow in expert order)
+        } else {   // one upload in the caller's order, then a device gather into expert order
+            if ((rc = grow_buffer(c, &c->mix_stage, &c->mix_stage_cap, B * cb, "mixed-batch staging buffer"))) return rc;
+            HIPCHK(c, hipMemcpyAsync(c->mix_stage, (const char*)crops + (size_t)off * cb, (size_t)nb * cb, hipMemcpyHostToDevice, c->stream));
+        }
+        if (org_wh) {
+            for (int j = 0; j < nb; ++j) { wh[2 * j] = org_wh[2 * (size_t)order[j]]; wh[2 * j + 1] = org_wh[2 * (size_t)order[j] + 1]; }
+            HIPCHK(c, hipMemcpyAsync(c->wh_stage, wh.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
+        }
+        const int32_t* d_wh = org_wh ? c->wh_stage : nullptr;
+        // segments of the chunk: (expert, first crop, count); ids[B + j] = the gather order
+        std::vector<int> seg_e, seg_s;
+        for (int j = 0; j < nb; ++j) {
+            ids[j] = expert_ids[order[j]];
+            ids[B + j] = order[j] - off;
+            if (j == 0 || ids[j] != ids[j - 1]) { seg_e.push_back(ids[j]); seg_s.push_back(j); }
+        }
+        seg_s.push_back(nb);
+        for (size_t j = nb; j < B; ++j) ids[j] = ids[nb - 1];   // encoder padding crops repeat the last crop (pick_run_batch)
+        if (!identity) {
+            HIPCHK(c, hipMemcpyAsync(c->expert_ids, ids.data(), 2 * B * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, vp::gather_crops_launch(c->mix_stage, c->in_stage, c->expert_ids + B, nb, cb, c->stream));
+        }
+        if (seg_e.size() == 1) {   // one expert: the single-dataset path as it is (tile rules, split-K, hipGraph replay keyed on the expert)
+            use_expert(c, seg_e[0]);
+            if ((rc = run_chunk(c, c->in_stage, fmt, nb, d_wh, c->kp))) return rc;
+        } else {
+            // mixed: the encoder once (mlp.fc2 of every expert in one launch per layer: GemmArgs::expert), then head + decode per expert segment.
+            // Eager: the expert pattern shapes the head launches, so a captured graph would have to be keyed on it (the single-expert path above replays)
+            if (identity) HIPCHK(c, hipMemcpyAsync(c->expert_ids, ids.data(), B * 4, hipMemcpyHostToDevice, c->stream));
+            c->mix_expert = c->expert_ids;
+            c->mix_bounds.assign(seg_s.begin() + 1, seg_s.end() - 1);
+            rc = forward_chunk(c, c->in_stage, fmt, nb, encoder_only);
+            c->mix_expert = nullptr;
+            c->mix_bounds.clear();
+            if (rc) return rc;
+            for (size_t s = 0; s < seg_e.size(); ++s) {
+                const int s0 = seg_s[s], cnt = seg_s[s + 1] - s0;
+                use_expert(c, seg_e[s]);
+                float* hm = c->hm + (size_t)s0 * c->Kmax * 3072;
+                if ((rc = head_chunk(c, c->y + (size_t)s0 * 192 * D, cnt, hm, plan_head(c->sw, D, cnt, c->fin_rows)))) return rc;
+                LAUNCH(c, VP_PROF_DECODE, 0.0, 4.0 * cnt * c->Kp * 3072.0 + 12.0 * cnt * c->Kp,
+                       vp::decode_launch(hm, d_wh ? d_wh + 2 * (size_t)s0 : nullptr, c->kp + (size_t)s0 * c->Kmax * 3, cnt, c->Kp, c->stream));
+            }
+        }
+        if ((rc = copy_out_sync(c, kp.data(), c->kp, (size_t)c->Kmax * 3, 0, nb))) return rc;   // the wait also keeps ids / wh (host vectors) alive until their uploads are done
+        // segment s's crops lie at [s0 Kmax + (j - s0) K_e] x 3 floats: back to the caller's order, joints beyond K_e = 0
+        for (size_t s = 0; s < seg_e.size(); ++s) {
+            const int K = c->ex_heads[seg_e[s]].K;
+            for (int j = seg_s[s]; j < seg_s[s + 1]; ++j) {
+                float* dst = out + (size_t)order[j] * c->Kmax * 3;
+                std::memcpy(dst, &kp[((size_t)seg_s[s] * c->Kmax + (size_t)(j - seg_s[s]) * K) * 3], (size_t)K * 12);
+                std::memset(dst + (size_t)K * 3, 0, (size_t)(c->Kmax - K) * 12);
+            }
+        }
+        return VP_OK;
+    });
+    use_expert(c, saved);
+    return rc;
+}
+
+int vp_infer_frames(vp_handle c, const vp_frame* frames, int32_t n_frames, int32_t on_device, const int32_t* p9, int32_t n, float* out) {
+    if (!c) return VP_ERR_INVALID;
+    std::vector<int32_t> bands((size_t)(n_frames > 0 ? n_frames : 0) * 2);
+    std::string why;
+    if (frame_plan(frames, n_frames, p9, n, bands.data(), &why)) return fail(c, VP_ERR_INVALID, why);   // before any copy or launch
+    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, p9, out);
+    if (rc || n == 0) return rc;
+    std::vector<vp::CropRec> recs;
+    if ((rc = stage_frames(c, frames, n_frames, on_device != 0, p9, n, bands.data(), recs))) return rc;
+    if (!c->crecs && (rc = dalloc(c, &c->crecs, (size_t)c->maxb))) return rc;
+    std::vector<int32_t> wh((size_t)c->maxb * 2);
+    return for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // vp_infer's chunks: the same crops per chunk, so the same bits
+        HIPCHK(c, hipMemcpyAsync(c->crecs, recs.data() + off, (size_t)nb * sizeof(vp::CropRec), hipMemcpyHostToDevice, c->stream));
+        LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5, vp::crop_resize_launch(c->crecs, (uint8_t*)c->in_stage, nb, c->stream));
+        // decode scales by the padded-canvas size (pw, ph) of each crop = the image pre_img receives
+        for (int i = 0; i < nb; ++i) { wh[2 * i] = p9[9 * (size_t)(off + i) + 7]; wh[2 * i + 1] = p9[9 * (size_t)(off + i) + 8]; }
+        HIPCHK(c, hipMemcpyAsync(c->wh_stage, wh.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // recs / wh are rewritten for the next chunk
+        if (const int rc = run_chunk(c, c->in_stage, VP_INPUT_U8_NHWC, nb, c->wh_stage, c->kp)) return rc;
+        return copy_out_sync(c, out, c->kp, (size_t)c->Kp * 3, off, nb);
+    });
+}
+
+// the one-frame case of vp_infer_frames
+int vp_infer_frame(vp_handle c, const uint8_t* frame, int32_t fh, int32_t fw, const int32_t* crop_params, int32_t n, float* out) {
+    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, frame, out);
+    if (rc) return rc;
+    if (fh <= 0 || fw <= 0 || (n > 0 && !crop_params)) return fail(c, VP_ERR_INVALID, "bad frame geometry");
+    const vp_frame fr{frame, fh, fw};
+    std::vector<int32_t> p9((size_t)n * 9);
+    for (int i = 0; i < n; ++i) {
+        p9[9 * (size_t)i] = 0;
+        std::memcpy(&p9[9 * (size_t)i + 1], crop_params + 8 * (size_t)i, 32);
+    }
+    return vp_infer_frames(c, &fr, 1, 0, p9.data(), n, out);
+}
+
+int vp_dbg_frame_plan(const vp_frame* frames, int32_t n_frames, const int32_t* params9, int32_t n, int32_t* bands) {
+    std::string why;
+    const int rc = frame_plan(frames, n_frames, params9, n, bands, &why);
+    if (rc) g_create_error = why;
+    return rc;
+}
+
+int vp_infer_boxes_stream(vp_handle c, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx,
+                          int32_t n, int32_t pad, float* d_out, int32_t* d_crop_params, int32_t* d_status, void* caller_stream) {
+    if (!c) return VP_ERR_INVALID;
+    // every host argument is checked before anything is enqueued
+    if (n > 0 && (!frames || !d_xyxy || !d_out)) return fail(c, VP_ERR_INVALID, "null frame table, box or output pointer");
+    std::vector<int32_t> hw((size_t)std::max(n > 0 ? n_frames : 0, 0) * 2);
+    for (size_t f = 0; f < hw.size() / 2; ++f) { hw[2 * f] = frames[f].h; hw[2 * f + 1] = frames[f].w; }
+    std::string why;
+    if (box_args(n_frames, hw.data(), 2, row_stride, n, pad, &why)) return fail(c, VP_ERR_INVALID, why);
+    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, d_xyxy, d_out, false);
+    if (rc || n == 0) return rc;
+    for (int f = 0; f < n_frames; ++f)   // every frame of the table: which ones the boxes name is on the device
+        if ((rc = check_device_frame(c, frames[f], f))) return rc;
+    // the chunk's crop records / decode sizes / offsets live in handle buffers sized by max_batch, allocated on the first call
+    if (!c->crecs && (rc = dalloc(c, &c->crecs, (size_t)c->maxb))) return rc;
+    if (!c->box_aux && (rc = dalloc(c, &c->box_aux, (size_t)c->maxb * 4))) return rc;
+    return caller_ordered(c, (hipStream_t)caller_stream, n, [&]() {
+        return for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // vp_infer_frames' chunks: the same crops per chunk, so the same plan and bits
+            // geometry + crop run eagerly in front of the chunk's graph: the frame pointers change from call to call, the graph's buffers do not
+            for (int f0 = 0; f0 < n_frames; f0 += vp::BOX_FRAMES_PER_LAUNCH) {
+                vp::BoxFrames bf;
+                std::memset(&bf, 0, sizeof(bf));
+                bf.f0 = f0; bf.count = std::min(n_frames - f0, vp::BOX_FRAMES_PER_LAUNCH); bf.n_frames = n_frames;
+                for (int j = 0; j < bf.count; ++j) { bf.data[j] = frames[f0 + j].data; bf.h[j] = frames[f0 + j].h; bf.w[j] = frames[f0 + j].w; }
+                LAUNCH(c, VP_PROF_IM2COL, 0.0, 64.0 * nb,
+                       vp::box_geometry_launch(bf, d_xyxy + (size_t)off * row_stride, row_stride, d_frame_idx ? d_frame_idx + off : nullptr, nb, pad,
+                                               (const uint8_t*)c->zero, c->crecs, c->wh_stage, c->box_aux,
+                                               d_crop_params ? d_crop_params + (size_t)off * 9 : nullptr, d_status ? d_status + off : nullptr, c->stream));
+            }
+            LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5, vp::crop_resize_launch(c->crecs, (uint8_t*)c->in_stage, nb, c->stream));
+            return run_chunk(c, c->in_stage, VP_INPUT_U8_NHWC, nb, c->wh_stage, d_out + (size_t)off * c->Kp * 3, c->box_aux);
+        });
+    });
+}
+
+int vp_dbg_box_geometry(const float* xyxy, int32_t row_stride, const int32_t* frame_idx, const int32_t* frame_hw, int32_t n_frames, int32_t n, int32_t pad,
+                        int32_t* out9, int32_t* status) {
+    std::string why;
+    if (n > 0 && (!xyxy || (n_frames > 0 && !frame_hw))) why = "null box or frame table";
+    const int rc = why.empty() ? box_args(n_frames, frame_hw, 2, row_stride, n, pad, &why) : (int)VP_ERR_INVALID;
+    if (rc) { g_create_error = why; return rc; }
+    for (int i = 0; i < n; ++i) {   // what box_geometry_kernel computes for box i
+        const int32_t f = frame_idx ? frame_idx[i] : 0;
+        int32_t p8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        int st = vp::BOX_BAD_FRAME;
+        if (f >= 0 && f < n_frames) {
+            const float* b = xyxy + (size_t)i * row_stride;
+            st = vp::box_geometry(b[0], b[1], b[2], b[3], frame_hw[2 * (size_t)f], frame_hw[2 * (size_t)f + 1], pad, p8);
+            if (st != vp::BOX_OK) std::memset(p8, 0, sizeof(p8));
+        }
+        if (out9) {
+            out9[9 * (size_t)i] = st == vp::BOX_OK ? f : 0;
+            std::memcpy(out9 + 9 * (size_t)i + 1, p8, sizeof(p8));
+        }
+        if (status) status[i] = st;
+    }
+    return VP_OK;
+}
+
+// decode of host heatmaps on device `device_id`: partner == null: [n, k, 64, 48] as they are; else the interleaved [2 n, k, 64, 48] of the flip-test mode
+static int decode_host(int32_t device_id, const float* heatmaps, int32_t n, int32_t k, const int32_t* partner, int32_t shift, const int32_t* org_wh, float* out) {
+    if (!heatmaps || !out || n <= 0 || k <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, VP_ERR_HIP, "no HIP device available (no CPU fallback)");
+    if (device_id < 0 || device_id >= ndev) return fail(nullptr, VP_ERR_INVALID, "device_id out of range");
+    vp_ctx* c = nullptr;   // errors below are reported through the create-error slot
+    HIPCHK(c, hipSetDevice(device_id));
+    float *d_hm = nullptr, *d_out = nullptr;
+    int32_t *d_wh = nullptr, *d_partner = nullptr;
+    const size_t hb = (size_t)n * k * 3072 * 4 * (partner ? 2 : 1), ob = (size_t)n * k * 12;
+    int rc = VP_OK;
+    hipError_t e = hipMalloc((void**)&d_hm, hb);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_out, ob);
+    if (e == hipSuccess) e = hipMemcpy(d_hm, heatmaps, hb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && org_wh) {
+        e = hipMalloc((void**)&d_wh, (size_t)n * 8);
+        if (e == hipSuccess) e = hipMemcpy(d_wh, org_wh, (size_t)n * 8, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess && partner) {
+        e = hipMalloc((void**)&d_partner, (size_t)k * 4);
+        if (e == hipSuccess) e = hipMemcpy(d_partner, partner, (size_t)k * 4, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = partner ? vp::decode_flip_launch(d_hm, d_partner, shift ? 1 : 0, d_wh, d_out, n, k, nullptr) : vp::decode_launch(d_hm, d_wh, d_out, n, k, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(nullptr, VP_ERR_HIP, std::string(partner ? "vp_dbg_decode_flip: " : "vp_decode_only: ") + hipGetErrorString(e));
+    if (d_hm) hipFree(d_hm);
+    if (d_out) hipFree(d_out);
+    if (d_wh) hipFree(d_wh);
+    if (d_partner) hipFree(d_partner);
+    return rc;
+}
+
+int vp_decode_only(int32_t device_id, const float* heatmaps, int32_t n, int32_t k, const int32_t* org_wh, float* out) {
+    return decode_host(device_id, heatmaps, n, k, nullptr, 0, org_wh, out);
+}
+
+int vp_dbg_decode_flip(int32_t device_id, const float* heatmaps2, int32_t n, int32_t k, const int32_t* flip_pairs, int32_t n_pairs, int32_t shift_heatmap,
+                       const int32_t* org_wh, float* out) {
+    if (k <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
+    std::vector<int32_t> partner((size_t)k);
+    std::string why;
+    if (flip_partner_table(k, flip_pairs, n_pairs, partner.data(), &why)) return fail(nullptr, VP_ERR_INVALID, why);
+    return decode_host(device_id, heatmaps2, n, k, partner.data(), shift_heatmap, org_wh, out);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // Tile rules: which kernel runs each GEMM of a chunk -- pure host functions of the switches and the shape (no device, no handle).  The single rules
-// (pick_*) feed one resolver per GEMM (resolve_gemm) and one plan per chunk (plan_chunk), which the orchestration (vitpose_api.hip) only executes.
+// (pick_*) feed one resolver per GEMM (resolve_gemm) and one plan per chunk (plan_chunk), which the orchestration (forward.hip) only executes.
 // tests/test_host_logic.py walks the rules and the plan over every batch size of every model through the host-only taps at the end of this file.
 #include "api_internal.h"
 

@@ -204,7 +204,7 @@ def test_small_batch_statistics_fold_is_bit_identical(monkeypatch, variant, data
 @pytest.mark.parametrize('variant,dataset,n,folded', [('s', 'coco', 12, 'both'), ('s', 'coco', 28, 'both'), ('b', 'coco', 12, 'both'), ('b', 'coco', 16, 'ln1'), ('l', 'coco_25', 12, 'ln1'),
                                                        ('h', 'wholebody', 10, 'ln1'), ('b', 'coco', 18, 'ln1'), ('l', 'coco_25', 14, 'ln1'), ('b', 'coco', 20, 'none')])
 def test_statistics_fold_rule_beyond_8_crops(monkeypatch, variant, dataset, n, folded):
-    """Round 6: beyond 8 crops the consumers' statistics merge is chosen PER CONSUMER (vitpose_api.hip forward_chunk): attn.qkv (LayerNorm-1) / mlp.fc1 (LayerNorm-2) fold where
+    """Round 6: beyond 8 crops the consumers' statistics merge is chosen PER CONSUMER (forward.hip forward_chunk): attn.qkv (LayerNorm-1) / mlp.fc1 (LayerNorm-2) fold where
     their GEMM runs on a 2-phase tile that keeps its occupancy with the (mean, rstd) area behind its ring -- not the 80 KiB ring of the default 192 x 128 tile (one workgroup
     per CU instead of two), not the 8-phase kernel, not a fused qkv + attention kernel.  Same ln_merge: heatmaps and keypoints equal the ln_finalize path (VP_FOLD_STATS=0)
     bit for bit, and exactly the expected ln_finalize launches disappear.  At 108-127 (pair, head) tiles (ViTPose-B 17-18 crops, -L 13-14) the two-launch qkv + attention path
@@ -260,7 +260,7 @@ def test_fused_head_is_bit_identical(monkeypatch, variant, dataset, dtype, n):
 @pytest.mark.parametrize('n', [36, 96])
 def test_mid_batch_gemm8_selection_is_bit_identical(monkeypatch, n):
     """Between ~32 and ~128 crops the 8-phase kernel takes a GEMM when its tiles fill the last round of 256 persistent workgroups
-    (vitpose_api.hip gemm()): 36 crops -> qkv on 243 tiles over 240 workgroups (uneven XCD shares, some workgroups take two tiles),
+    (forward.hip gemm()): 36 crops -> qkv on 243 tiles over 240 workgroups (uneven XCD shares, some workgroups take two tiles),
     96 crops -> fc2 on 216 tiles of 256 x 256 with the residual epilogue.  Same arithmetic order as the 2-phase kernels: the whole
     path must not change by a bit against VP_GEMM8=0."""
     shp, sd, _ = weights('b', 'coco')

@@ -33,7 +33,7 @@ pytestmark = pytest.mark.gpu
 HM_MAX_ERR, HM_RMS_ERR = 4e-3, 6e-4     # fp16 budgets of tests/test_gpu_parity.py
 
 
-# expected kernel families per case (substring of vp_profile_kernel): the selection rules of tile_rules.hip (applied by vitpose_api.hip gemm()) at these sizes
+# expected kernel families per case (substring of vp_profile_kernel): the selection rules of tile_rules.hip (applied by forward.hip gemm()) at these sizes
 CASES = [
     # variant, dataset, batch, oracle crops, {family: substring}
     ('h', 'wholebody', 128, 2, {'gemm_qkv': 'gemm8_kernel<F16, 9, G8<256, 192>>', 'gemm_fc1': 'gemm8_kernel<F16, 1, G8<256, 256>>',   # qkv + attention fused (head dim 80, round 5): 128 crops x 16 heads = 2048 one-crop tiles of 192 x 256

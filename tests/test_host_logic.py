@@ -443,7 +443,7 @@ def test_chunk_plan_fp8_and_bad_arguments():
 @pytest.mark.parametrize('w', [1, 2, 8])
 @pytest.mark.parametrize('maxb', [1, 8, 64])
 def test_group_sharding_plan(n, w, maxb):
-    """vp_group_infer's sharding (vitpose_api.hip group_plan, the function group_run executes) through the host-only tap
+    """vp_group_infer's sharding (group.hip group_plan, the function group_run executes) through the host-only tap
     vp_dbg_group_plan: rounds of w * maxb crops, contiguous shards of ceil(nr / w) crops, no crop lost or duplicated, no shard
     above max_batch, trailing devices short or empty -- for uneven tails, more devices than crops and multi-round calls.
     No device needed: the multi-GPU path is checked before 8-GPU hardware shows up."""
@@ -481,7 +481,7 @@ def test_group_sharding_plan(n, w, maxb):
 
 @pytest.mark.parametrize('n,w,maxb', [(64, 8, 8), (513, 8, 64), (7, 8, 64), (2048, 8, 256), (5, 2, 1), (1, 8, 8)])
 def test_group_call_enqueues_every_member_before_it_waits_for_any(n, w, maxb):
-    """The two-phase schedule of vp_group_infer (vitpose_api.hip group_rounds, the function group_run executes) with stub members,
+    """The two-phase schedule of vp_group_infer (group.hip group_rounds, the function group_run executes) with stub members,
     host only: inside every round ALL submissions precede the first wait, each member that got work is waited for exactly once, in
     member order, and the submissions of round r + 1 start only after round r has been collected (the members' two slots are then
     free again).  Phase 1 of the real path contains no wait either: downloads land in pinned staging, uploads are asynchronous from

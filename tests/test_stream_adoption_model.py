@@ -1,4 +1,4 @@
-"""CPU model of the cross-call stream ordering of a handle (easy_vitpose_amd/csrc/vitpose_api.hip: adopt_stream, check_ready, vp_infer_device_stream, vp_synchronize;
+"""CPU model of the cross-call stream ordering of a handle (easy_vitpose_amd/csrc/infer.hip: adopt_stream, check_ready, caller_ordered behind vp_infer_device_stream; handle.hip: quiesce behind vp_synchronize;
 round 5).  At <= 16 crops the stream-ordered entry enqueues its chunk on the CALLER's stream, so the handle's workspaces are used from several streams over time and the
 library alone must order consecutive calls.  The model replays random sequences of calls -- own-stream entries (vp_infer, vp_infer_device, ...), the stream-ordered entry
 on the legacy default stream / on two caller streams at small and at large batches, vp_synchronize -- as operations on in-order streams with event records and waits, and
@@ -38,7 +38,7 @@ class Handle:
     def wait(self, stream, name):
         self.op(stream, 'wait', self.ev[name])          # a wait captures the event's latest record at the time of the call
 
-    # --- vitpose_api.hip adopt_stream
+    # --- infer.hip adopt_stream
     def adopt(self, s, call):
         if not self.foreign_pending and s == OWN:
             return
