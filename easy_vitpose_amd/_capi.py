@@ -31,7 +31,8 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_expert_info', 'vp_set_expert', 'vp_infer_experts', 'vp_dbg_expert_tile', 'vp_infer_frames', 'vp_dbg_frame_plan',
            'vp_dbg_chunk_plan', 'vp_infer_boxes_stream', 'vp_dbg_box_geometry',
            'vp_set_flip_test', 'vp_clear_flip_test', 'vp_flip_test_enabled', 'vp_group_set_flip_test', 'vp_group_clear_flip_test',
-           'vp_dbg_flip_partner', 'vp_dbg_flip_layout', 'vp_dbg_decode_flip']
+           'vp_dbg_flip_partner', 'vp_dbg_flip_layout', 'vp_dbg_decode_flip',
+           'vp_infer_experts_device_stream', 'vp_infer_frames_experts', 'vp_infer_boxes_experts_stream', 'vp_dbg_mix_plan', 'vp_dbg_decode_mix']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -156,6 +157,12 @@ def load_library():
     lib.vp_set_expert.argtypes = [H, C.c_int32]
     lib.vp_infer_experts.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vp_dbg_expert_tile.argtypes = [C.c_int32] * 4 + [C.c_void_p, C.c_int32]
+    lib.vp_infer_experts_device_stream.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vp_infer_frames_experts.argtypes = [H, C.POINTER(vp_frame), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.vp_infer_boxes_experts_stream.argtypes = [H, C.POINTER(vp_frame), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vp_dbg_mix_plan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    lib.vp_dbg_decode_mix.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vp_dbg_chunk_plan.argtypes = [C.POINTER(vp_config), C.c_int32, C.c_void_p, C.c_int32]
     lib.vp_dbg_qkvattn.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 4
     lib.vp_set_flip_test.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32]

@@ -1,7 +1,7 @@
 // Internal header shared by the translation units behind the C ABI (include/vitpose_hip.h):
 //   handle.hip       -- the handle: vp_create / vp_destroy, the switches, the guards of every entry, its modes (expert, flip-test), profiling, vp_synchronize
 //   forward.hip      -- the forward of a chunk: gemm / gemm_fp8, forward_chunk, head_chunk, decode_chunk, run_chunk and its hipGraph cache
-//   infer.hip        -- the inference entries and their staging (vp_infer*: host / device crops, the two slots, frames, boxes, experts, flip), stream adoption
+//   infer.hip        -- the inference entries and their staging (vp_infer*: host / device crops, the two slots, frames, boxes, experts and their per-crop plan, flip), stream adoption
 //   group.hip        -- the multi-device group (vp_group*)
 //   weights.hip      -- the weight packer (vp_load_weights: BN / LayerNorm folding, 16-bit / e4m3 conversion, deconv re-tiling)
 //   tile_rules.hip   -- which GEMM tile runs a shape (pure host functions + their host-only taps)
@@ -87,6 +87,18 @@ struct Switches {
 
 }  // namespace vpi
 
+namespace vpi {
+// The plan of one chunk with per-crop experts (HOST ONLY, a pure function of the chunk's ids: mix_plan): the crops in stable expert order -- position j holds caller
+// row order[j] (chunk-local) of expert ids[j] -- and the run-length segments of that order: segment s = expert seg_e[s] at positions [seg_s[s], seg_s[s + 1]).
+// pattern = GraphKey::mix (mix_pattern): 0 for one segment.
+struct MixPlan {
+    int nb = 0;
+    std::vector<int32_t> order, ids;
+    std::vector<int> seg_e, seg_s;
+    uint64_t pattern = 0;
+};
+}  // namespace vpi
+
 struct vp_ctx {
     vp_config cfg;
     vpi::Switches sw;
@@ -153,8 +165,15 @@ struct vp_ctx {
         int expert = 0;                  // a ViTPose+ handle's active expert (fc2 weights, head, K)
         const int32_t* post = nullptr;   // vp_infer_boxes_stream: the frame-offset kernel after the decode (its aux buffer; null: none)
         uint32_t flip = 0;               // the flip-test mode's generation the launches were captured under (flip_gen; 0: mode off)
+        // the per-crop expert entries (vp_infer_experts_device_stream, ...).  mix = the chunk's expert pattern, the count per expert in an exact encoding
+        // (mix_pattern): with the crops in stable expert order the counts determine every launch -- the gather, the encoder's tile bounds, each head's rows -- and
+        // the permutation lives in table buffers the launches only point at.  0 for every chunk that runs one expert.  wide: the decode goes the record route
+        // into rows of Kmax joints (a one-expert chunk of those entries: the plain forward under key.expert, then that decode).  Both 0 / false on every other entry.
+        uint64_t mix = 0;
+        bool wide = false;
         bool operator==(const GraphKey& o) const {
-            return n == o.n && fmt == o.fmt && src == o.src && wh == o.wh && out == o.out && expert == o.expert && post == o.post && flip == o.flip;
+            return n == o.n && fmt == o.fmt && src == o.src && wh == o.wh && out == o.out && expert == o.expert && post == o.post && flip == o.flip &&
+                   mix == o.mix && wide == o.wide;
         }
     };
     struct GraphEntry { GraphKey key; hipGraphExec_t exec = nullptr; bool no_graph = false; };   // no_graph: capture or launch failed once, the key stays eager
@@ -191,6 +210,14 @@ struct vp_ctx {
     size_t mix_stage_cap = 0;
     const int32_t* mix_expert = nullptr;
     std::vector<int> mix_bounds;
+    // the per-crop expert entries: the chunk's tables on the device, written by mix_tables_launch from kernel arguments in front of the chunk -- expert_ids [0, B) the
+    // experts in expert order and [B, 2 B) the caller row of every position (as vp_infer_experts lays them out), mix_slot = the position of every caller row,
+    // mix_recs = the decode's records.  mix = the host plan of the chunk run_chunk is running (null on every other entry): it shapes the launches of chunk_body
+    int32_t* mix_slot = nullptr;
+    vp::MixRec* mix_recs = nullptr;
+    const vpi::MixPlan* mix = nullptr;
+    vpi::MixPlan mix_host;                         // the plan of the current chunk and the scratch of its tables: host memory that lives with the handle
+    std::vector<int32_t> mix_ks, mix_first, mix_k;
     // profiling
     uint32_t prof = 0;   // bit f = time kernel family f
     int gemm_ablate = 0;   // profiling only
@@ -282,6 +309,16 @@ int stage_frames(vp_ctx* c, const vp_frame* frames, int n_frames, bool on_device
 // vp_infer_boxes_stream / vp_dbg_box_geometry (HOST ONLY): the host arguments of a boxes call (sizes of every frame, row stride, pad, counts).
 // VP_OK or VP_ERR_INVALID with the reason in *why
 int box_args(int n_frames, const int32_t* frame_hw, int hw_stride, int row_stride, int n, int pad, std::string* why);
+// the per-crop expert entries (HOST ONLY).  mix_check_ids: VP_ERR_INVALID with the reason in *why for null ids or an id outside [0, n_experts), naming the crop
+// (every entry checks the whole call with it before anything is enqueued).  mix_plan: checked ids [nb] of one chunk -> p (reused from chunk to chunk).
+// mix_pattern: the exact code of the counts per expert -- 8 bits each for up to 8 experts of up to 254 crops, 0 for a chunk of one expert, MIX_NO_GRAPH where the
+// counts do not fit (such a chunk runs eagerly).  mix_records: MixRec's first / K of every position [nb] -- the head of segment s writes its maps [cnt, K_e, 64, 48]
+// from map seg_s[s] * Kmax on (k_per_expert [n_experts])
+constexpr uint64_t MIX_NO_GRAPH = ~(uint64_t)0;
+int mix_check_ids(const int32_t* ids, int n, int n_experts, std::string* why);
+void mix_plan(const int32_t* ids, int nb, int n_experts, MixPlan& p);
+uint64_t mix_pattern(const std::vector<int>& seg_e, const std::vector<int>& seg_s, int n_experts);
+void mix_records(const MixPlan& p, const int32_t* k_per_expert, int Kmax, int32_t* first, int32_t* K);
 // vp_infer_submit; stage_out (the group path): the download lands in the slot's pinned buffer and vp_infer_wait copies it to `out`
 int submit_impl(vp_ctx* c, const void* crops, int32_t fmt, int32_t n, const int32_t* org_wh, float* out, int32_t* slot_out, bool stage_out);
 

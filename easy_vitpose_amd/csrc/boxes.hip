@@ -12,7 +12,7 @@ namespace vp {
 __global__ __launch_bounds__(64) void box_geometry_kernel(BoxFrames fr, const float* __restrict__ xyxy, int row_stride, const int32_t* __restrict__ frame_idx,
                                                           int n, int pad, const uint8_t* __restrict__ zero_px, CropRec* __restrict__ recs,
                                                           int32_t* __restrict__ wh, int32_t* __restrict__ aux, int32_t* __restrict__ p9_out,
-                                                          int32_t* __restrict__ status_out) {
+                                                          int32_t* __restrict__ status_out, const int32_t* __restrict__ slot) {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
     const int32_t f = frame_idx ? frame_idx[i] : 0;
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(64) void box_geometry_kernel(BoxFrames fr, const fl
         r.src = zero_px; r.pitch = 3;
         r.cw = r.ch = r.pw = r.ph = 1; r.left = r.top = 0;
     }
-    recs[i] = r;
+    recs[slot ? slot[i] : i] = r;   // a chunk with per-crop experts: straight into its place in the expert order
     wh[2 * i] = r.pw;   // decode scales by the padded canvas, as vp_infer_frames passes it
     wh[2 * i + 1] = r.ph;
     aux[4 * i] = p8[1] - p8[5];       // y0 - top_pad
@@ -53,16 +53,18 @@ __global__ __launch_bounds__(64) void box_geometry_kernel(BoxFrames fr, const fl
 }
 
 hipError_t box_geometry_launch(const BoxFrames& fr, const float* xyxy, int row_stride, const int32_t* frame_idx, int n, int pad, const uint8_t* zero_px,
-                               CropRec* recs, int32_t* wh, int32_t* aux, int32_t* p9_out, int32_t* status_out, hipStream_t s) {
+                               CropRec* recs, int32_t* wh, int32_t* aux, int32_t* p9_out, int32_t* status_out, hipStream_t s, const int32_t* slot) {
     hipLaunchKernelGGL(box_geometry_kernel, dim3((n + 63) / 64), dim3(64), 0, s, fr, xyxy, row_stride, frame_idx, n, pad, zero_px, recs, wh, aux, p9_out,
-                       status_out);
+                       status_out, slot);
     return hipGetLastError();
 }
 
 // out [n, K, 3] (y, x, conf) in padded-crop pixels -> frame pixels: + (y0 - top_pad, x0 - left_pad) in float32, as VitInference.inference_frames
 // adds them (numpy's float64 add of an integer below 2^24 followed by the float32 store rounds the exact sum once, as this add does);
-// rows with a non-zero status become all zero.
-__global__ __launch_bounds__(256) void box_offsets_kernel(const int32_t* __restrict__ aux, float* __restrict__ out, int n, int K) {
+// rows with a non-zero status become all zero.  slot / recs (null: every row has K joints): a ViTPose+ chunk with per-crop experts, rows of K = Kmax joints --
+// row i's expert has recs[slot[i]].K of them, the zeros the decode wrote behind those stay zeros.
+__global__ __launch_bounds__(256) void box_offsets_kernel(const int32_t* __restrict__ aux, float* __restrict__ out, int n, int K, const int32_t* __restrict__ slot,
+                                                          const MixRec* __restrict__ recs) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n * K) return;
     const int i = j / K;
@@ -71,12 +73,14 @@ __global__ __launch_bounds__(256) void box_offsets_kernel(const int32_t* __restr
         o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;
         return;
     }
+    if (slot && j - i * K >= recs[slot[i]].K) return;
     o[0] = o[0] + (float)aux[4 * i];
     o[1] = o[1] + (float)aux[4 * i + 1];
 }
 
-hipError_t box_offsets_launch(const int32_t* aux, float* out, int n, int K, hipStream_t s) {
-    hipLaunchKernelGGL(box_offsets_kernel, dim3((n * K + 255) / 256), dim3(256), 0, s, aux, out, n, K);
+hipError_t box_offsets_launch(const int32_t* aux, float* out, int n, int K, hipStream_t s, const int32_t* slot, const MixRec* recs) {
+    if ((slot != nullptr) != (recs != nullptr)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(box_offsets_kernel, dim3((n * K + 255) / 256), dim3(256), 0, s, aux, out, n, K, slot, recs);
     return hipGetLastError();
 }
 

@@ -33,16 +33,34 @@ struct GaussK { float w[11]; };
 // multiply as flip_merge_kernel and the same summation orders below, so the result equals flip_merge + decode bit for bit while the merged tensor is never
 // written.  flip_back = x reversed (column x reads 47 - x; with `shift`, column x > 0 reads 48 - x and column 0 keeps 47): a reversed 192-byte row is the same
 // one or two cache lines, read as one aligned 16-byte load (+ one scalar under `shift`) and swizzled in registers.
-template <bool FLIP>
+//
+// MIX (a ViTPose+ chunk with per-crop experts, decode_mix_launch): the grid is [N, Kmax] and the crop at position n of the chunk's expert order brings its own
+// record -- where its maps start, how many joints its expert has, which row of the caller's order it is.  Blocks k < K_e run the code below on exactly the values the
+// plain kernel sees for that crop as a [1, K_e, 64, 48] batch (the record only replaces the three index expressions n K + k, n and blockIdx.x), so the bits are the plain
+// kernel's; blocks k >= K_e write the zeros of the padded row.  FLIP and MIX are compile-time: decode_kernel<false, false> keeps the instruction stream it had.
+template <bool FLIP, bool MIX>
 __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ hm, const int32_t* __restrict__ org_wh,
-                                                     float* __restrict__ out, int K, GaussK gk, const int32_t* __restrict__ partner, int shift) {
+                                                     float* __restrict__ out, int K, GaussK gk, const int32_t* __restrict__ partner, int shift,
+                                                     const MixRec* __restrict__ recs) {
     __shared__ float s_val[4];
     __shared__ int s_idx[4];
     __shared__ float s_part[7][11];
     __shared__ float s_samp[7];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = blockIdx.x / K, k = blockIdx.x % K;
-    const float* map = hm + (FLIP ? (size_t)2 * n * K + k : (size_t)blockIdx.x) * HW;
+    int first = 0, row = n;   // MIX: the crop's first map, and its row in org_wh / out
+    if (MIX) {
+        const MixRec r = recs[n];
+        row = r.dst;
+        if (k >= r.K) {   // a joint this crop's expert does not have (the whole block leaves: no barrier was reached yet)
+            if (tid < 3) out[((size_t)row * K + k) * 3 + tid] = 0.f;
+            return;
+        }
+        out += ((size_t)row * K + k) * 3;   // K is still Kmax here: the output rows' stride
+        first = r.first;
+        K = r.K;
+    }
+    const float* map = hm + (MIX ? (size_t)first + k : FLIP ? (size_t)2 * n * K + k : (size_t)blockIdx.x) * HW;
     const float* mir = FLIP ? hm + ((size_t)(2 * n + 1) * K + partner[k]) * HW : nullptr;
 
     // ---- arg-max / max over 3072 values, first index on ties (_get_max_preds, :82-114)
@@ -98,7 +116,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
         py = min(max(py, 0), HH - 1);                 // np.pad(mode='edge')
         px = min(max(px, 0), WW - 1);
         const int ry = reflect101(py + ty - 5, HH) * WW;
-        const float* src = hm + ((size_t)(FLIP ? 2 * n : n) * K + kk) * HW + ry;
+        const float* src = hm + (MIX ? (size_t)first + kk : (size_t)(FLIP ? 2 * n : n) * K + kk) * HW + ry;
         const float* msrc = FLIP ? hm + ((size_t)(2 * n + 1) * K + partner[kk]) * HW + ry : nullptr;   // the neighbour map the samples wrap into, and ITS partner
         float acc = 0.f;
 #pragma unroll
@@ -138,10 +156,10 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
         // transform_preds(use_udp=True) with center = (w//2, h//2), scale = (w, h)
         // (post_transforms.py:183-192, inference.py:200-204), float64 then float32
         int ow = 192, oh = 256;
-        if (org_wh) { ow = org_wh[2 * n]; oh = org_wh[2 * n + 1]; }
+        if (org_wh) { ow = org_wh[2 * (MIX ? row : n)]; oh = org_wh[2 * (MIX ? row : n) + 1]; }
         const double fx = (double)rx * ((double)ow / (WW - 1.0)) + (double)(ow / 2) - (double)ow * 0.5;
         const double fy = (double)ry * ((double)oh / (HH - 1.0)) + (double)(oh / 2) - (double)oh * 0.5;
-        float* o = out + (size_t)blockIdx.x * 3;             // [n, K, 3] of the caller's crops in both modes
+        float* o = MIX ? out : out + (size_t)blockIdx.x * 3;   // [n, K, 3] of the caller's crops in every mode
         o[0] = (float)fy;                            // (y, x, conf)  inference.py:205
         o[1] = (float)fx;
         o[2] = maxval;
@@ -158,13 +176,19 @@ static GaussK gauss11() {
 }
 
 hipError_t decode_launch(const float* hm, const int32_t* org_wh, float* out, int N, int K, hipStream_t s) {
-    hipLaunchKernelGGL(decode_kernel<false>, dim3(N * K), dim3(256), 0, s, hm, org_wh, out, K, gauss11(), (const int32_t*)nullptr, 0);
+    hipLaunchKernelGGL((decode_kernel<false, false>), dim3(N * K), dim3(256), 0, s, hm, org_wh, out, K, gauss11(), (const int32_t*)nullptr, 0, (const MixRec*)nullptr);
     return hipGetLastError();
 }
 
 hipError_t decode_flip_launch(const float* hm, const int32_t* partner, int shift, const int32_t* org_wh, float* out, int N, int K, hipStream_t s) {
     if (!partner) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(decode_kernel<true>, dim3(N * K), dim3(256), 0, s, hm, org_wh, out, K, gauss11(), partner, shift);
+    hipLaunchKernelGGL((decode_kernel<true, false>), dim3(N * K), dim3(256), 0, s, hm, org_wh, out, K, gauss11(), partner, shift, (const MixRec*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t decode_mix_launch(const float* hm, const MixRec* recs, const int32_t* org_wh, float* out, int N, int Kmax, hipStream_t s) {
+    if (!recs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((decode_kernel<false, true>), dim3(N * Kmax), dim3(256), 0, s, hm, org_wh, out, Kmax, gauss11(), (const int32_t*)nullptr, 0, recs);
     return hipGetLastError();
 }
 

@@ -233,6 +233,30 @@ hipError_t gather_crops_launch(const void* src, void* dst, const int32_t* idx, i
     return hipGetLastError();
 }
 
+// ViTPose+ chunk with per-crop experts: the call's tables from the kernel argument into the handle's device buffers (kernels.h MixTable).  One thread owns
+// every value it writes; the launches of a chunk write disjoint positions, so the order among them does not matter.
+__global__ __launch_bounds__(MIX_CROPS_PER_LAUNCH) void mix_tables_kernel(MixTable t, int32_t* __restrict__ ids, int32_t* __restrict__ order,
+                                                                        int32_t* __restrict__ slot, MixRec* __restrict__ recs) {
+    const int i = threadIdx.x;
+    if (i < t.count) {
+        const int j = t.base + i;
+        ids[j] = t.id[i];
+        order[j] = t.order[i];
+        slot[t.order[i]] = j;
+        MixRec r;
+        r.first = t.first[i]; r.K = t.K[i]; r.dst = t.order[i];
+        recs[j] = r;
+    }
+    if (t.count > 0)
+        for (int j = t.base + t.count + i; j < t.pad_to; j += MIX_CROPS_PER_LAUNCH) ids[j] = t.id[t.count - 1];
+}
+
+hipError_t mix_tables_launch(const MixTable& t, int32_t* ids, int32_t* order, int32_t* slot, MixRec* recs, hipStream_t s) {
+    if (t.count < 0 || t.count > MIX_CROPS_PER_LAUNCH || t.base < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mix_tables_kernel, dim3(1), dim3(MIX_CROPS_PER_LAUNCH), 0, s, t, ids, order, slot, recs);
+    return hipGetLastError();
+}
+
 // --------------------------------------------------------------- LayerNorm
 // nn.LayerNorm(eps=1e-6) (vit.py:274) over the fp32 residual stream, one wave per
 // token row, row held in registers (D <= 1280 -> <= 5 float4 per lane), two-pass

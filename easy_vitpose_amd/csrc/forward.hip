@@ -283,9 +283,48 @@ static int offsets_chunk(vp_ctx* c, const int32_t* aux, float* d_out, int n) {
     return VP_OK;
 }
 
+// The chunk of a per-crop expert entry (k.wide; c->mix = its plan, the tables are on the device).  Mixed (k.mix != 0): the crops into expert order (device crops:
+// one gather; frames and boxes were cropped straight into it), the encoder once with every expert's mlp.fc2 in one launch per layer on tiles that never span two
+// experts, one head per expert present on its segment's rows.  One expert: the plain forward under that expert.  Then ONE decode launch by records into rows of
+// Kmax joints in the caller's order, and the frame offsets on those rows.  Leaves the last segment's expert active: the entry restores the handle's own.
+static int mix_chunk_body(vp_ctx* c, const GraphKey& k) {
+    const MixPlan& m = *c->mix;
+    const int nseg = (int)m.seg_e.size(), D = c->D;
+    int rc;
+    if (nseg == 1) {
+        use_expert(c, m.seg_e[0]);
+        if ((rc = forward_chunk(c, k.src, k.fmt, k.n))) return rc;
+    } else {
+        const void* src = k.src;
+        if (src != c->in_stage) {
+            const size_t B = (size_t)((c->maxb + 3) / 4 * 4);
+            HIPCHK(c, vp::gather_crops_launch(src, c->in_stage, c->expert_ids + B, k.n, crop_bytes(k.fmt), c->stream));
+            src = c->in_stage;
+        }
+        FwdOpts encoder_only;
+        encoder_only.head = false;
+        c->mix_expert = c->expert_ids;
+        c->mix_bounds.assign(m.seg_s.begin() + 1, m.seg_s.end() - 1);
+        rc = forward_chunk(c, src, k.fmt, k.n, encoder_only);
+        c->mix_expert = nullptr;
+        c->mix_bounds.clear();
+        if (rc) return rc;
+        for (int s = 0; s < nseg; ++s) {
+            const int s0 = m.seg_s[s], cnt = m.seg_s[s + 1] - s0;
+            use_expert(c, m.seg_e[s]);
+            if ((rc = head_chunk(c, c->y + (size_t)s0 * 192 * D, cnt, c->hm + (size_t)s0 * c->Kmax * 3072, plan_head(c->sw, D, cnt, c->fin_rows)))) return rc;
+        }
+    }
+    LAUNCH(c, VP_PROF_DECODE, 0.0, 4.0 * k.n * c->Kmax * 3072.0 + 12.0 * k.n * c->Kmax,
+           vp::decode_mix_launch(c->hm, c->mix_recs, k.wh, k.out, k.n, c->Kmax, c->stream));
+    if (k.post) LAUNCH(c, VP_PROF_DECODE, 0.0, 24.0 * k.n * c->Kmax + 16.0 * k.n, vp::box_offsets_launch(k.post, k.out, k.n, c->Kmax, c->stream, c->mix_slot, c->mix_recs));
+    return VP_OK;
+}
+
 // forward + decode (+ frame offsets, key.post != null) of the chunk a key names, on c->stream: what the eager path launches and what a capture records
 static int chunk_body(vp_ctx* c, const GraphKey& k) {
     int rc;
+    if (k.wide) return mix_chunk_body(c, k);
     if ((rc = forward_mode_chunk(c, k.src, k.fmt, k.n))) return rc;
     if ((rc = decode_chunk(c, k.wh, k.out, k.n, c->flip_on))) return rc;
     return k.post ? offsets_chunk(c, k.post, k.out, k.n) : VP_OK;
@@ -345,7 +384,14 @@ static int graph_give_up(vp_ctx* c, GraphEntry* ge) {
 // and from then on replayed with one hipGraphLaunch.
 int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh, float* d_out, const int32_t* post) {
     if (nb > chunk_cap(c)) return fail(c, VP_ERR_INVALID, "a chunk of " + std::to_string(nb) + " crops exceeds what the handle's workspaces hold in this mode");
-    const GraphKey key{nb, fmt, d_src, d_wh, d_out, c->expert, post, c->flip_gen};
+    GraphKey key{nb, fmt, d_src, d_wh, d_out, c->expert, post, c->flip_gen};
+    if (c->mix) {   // a per-crop expert entry: its chunk's pattern, or the one expert the whole chunk runs
+        if (c->flip_on || c->mix->nb != nb) return fail(c, VP_ERR_STATE, "a chunk with per-crop experts under the flip-test mode, or a plan of another chunk");
+        key.wide = true;
+        key.mix = c->mix->pattern;
+        key.expert = key.mix ? 0 : c->mix->seg_e[0];
+        if (key.mix == MIX_NO_GRAPH) return chunk_body(c, key);   // a pattern the key cannot hold exactly
+    }
     // a caller's legacy default stream (torch's usual current stream): VP_GRAPH_NULL=1 replays the graph there too (a caller that synchronises after
     // every call pays the 110-290 eager launches' host time); 0 = plain launches (equal when calls are enqueued back to back)
     if (chunk_rows(c, nb) > c->sw.graph_max_n || c->prof != 0 || (c->stream == nullptr && !c->sw.graph_null)) return chunk_body(c, key);

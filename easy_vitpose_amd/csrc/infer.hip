@@ -1,6 +1,6 @@
 // The inference entries of the C ABI (include/vitpose_hip.h) and their staging: host crops, device crops on the handle's or a caller's stream,
-// the two asynchronous slots, frames, device boxes, ViTPose+ mixed batches, vp_infer_flip.  Each walks its crops in chunks (for_chunks) and hands
-// a chunk to forward.hip.
+// the two asynchronous slots, frames, device boxes, ViTPose+ mixed batches (vp_infer_experts; per-crop experts on the device, frames and boxes entries with
+// their host-side plan, mix_plan), vp_infer_flip.  Each walks its crops in chunks (for_chunks) and hands a chunk to forward.hip.
 #include "api_internal.h"
 #include "boxgeom.h"
 
@@ -131,6 +131,45 @@ template <class Chunks> int caller_ordered(vp_ctx* c, hipStream_t cs, int n, Chu
     return VP_OK;
 }
 
+// ---- per-crop expert entries: what vp_infer_experts_device_stream, vp_infer_frames_experts and vp_infer_boxes_experts_stream share
+// every refusal of such a call, before anything is enqueued (the entry's own argument checks and check_ready come first)
+int mix_ready(vp_ctx* c, const char* who, int n, const int32_t* expert_ids) {
+    if (!c->n_experts) return fail(c, VP_ERR_STATE, std::string(who) + ": the handle holds a plain (single-dataset) checkpoint, not a ViTPose+ one");
+    std::string why;
+    if (mix_check_ids(expert_ids, n, c->n_experts, &why)) return fail(c, VP_ERR_INVALID, why);
+    if (c->flip_on)
+        return fail(c, VP_ERR_STATE, std::string(who) + " does not run under the flip-test mode (one partner table per handle, not per crop): call vp_clear_flip_test first");
+    return slots_idle(c, who);
+}
+
+// the plan of chunk [off, off + nb) and its tables onto the device: kernel arguments only, MIX_CROPS_PER_LAUNCH positions per launch, on c->stream
+// (the ids were checked for the whole call by mix_ready; the plan and its scratch live in the handle: no allocation per chunk once they have grown)
+int mix_chunk_tables(vp_ctx* c, const int32_t* expert_ids, int off, int nb, MixPlan& p) {
+    mix_plan(expert_ids + off, nb, c->n_experts, p);
+    const int B = (c->maxb + 3) / 4 * 4;
+    std::vector<int32_t>&ks = c->mix_ks, &first = c->mix_first, &K = c->mix_k;
+    ks.resize(c->n_experts); first.resize(nb); K.resize(nb);
+    for (int e = 0; e < c->n_experts; ++e) ks[e] = c->ex_heads[e].K;
+    mix_records(p, ks.data(), c->Kmax, first.data(), K.data());
+    for (int base = 0; base < nb; base += vp::MIX_CROPS_PER_LAUNCH) {
+        vp::MixTable t;
+        std::memset(&t, 0, sizeof(t));
+        t.base = base; t.count = std::min(nb - base, vp::MIX_CROPS_PER_LAUNCH);
+        t.pad_to = base + t.count == nb ? B : 0;   // encoder padding crops repeat the last crop (pick_run_batch)
+        for (int i = 0; i < t.count; ++i) { t.id[i] = p.ids[base + i]; t.order[i] = p.order[base + i]; t.first[i] = first[base + i]; t.K[i] = K[base + i]; }
+        LAUNCH(c, VP_PROF_IM2COL, 0.0, 28.0 * t.count, vp::mix_tables_launch(t, c->expert_ids, c->expert_ids + B, c->mix_slot, c->mix_recs, c->stream));
+    }
+    return VP_OK;
+}
+
+// run_chunk under plan p, whatever it returns
+int run_mix_chunk(vp_ctx* c, const MixPlan& p, const void* d_src, int fmt, int nb, const int32_t* d_wh, float* d_out, const int32_t* post = nullptr) {
+    c->mix = &p;
+    const int rc = run_chunk(c, d_src, fmt, nb, d_wh, d_out, post);
+    c->mix = nullptr;
+    return rc;
+}
+
 }  // namespace
 
 namespace vpi {   // shared with debug_taps.hip (vp_dbg_crop_prep) and group.hip (submit_impl)
@@ -216,6 +255,52 @@ int box_args(int n_frames, const int32_t* frame_hw, int hw_stride, int row_strid
             return bad("frame " + std::to_string(f) + " has a size outside [1, 2^24]");
     }
     return VP_OK;
+}
+
+// ---- per-crop experts: the plan of a chunk (HOST ONLY) ------------------------------------------------------------------------
+int mix_check_ids(const int32_t* ids, int n, int n_experts, std::string* why) {
+    auto bad = [&](const std::string& m) { if (why) *why = m; return VP_ERR_INVALID; };
+    if (n > 0 && !ids) return bad("null expert_ids");
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= n_experts)
+            return bad("expert id " + std::to_string(ids[i]) + " of crop " + std::to_string(i) + " outside [0, " + std::to_string(n_experts) + ")");
+    return VP_OK;
+}
+
+void mix_plan(const int32_t* ids, int nb, int n_experts, MixPlan& p) {
+    p.nb = nb;
+    p.order.resize(nb > 0 ? nb : 0);   // (p is reused from chunk to chunk: its vectors keep their capacity)
+    p.ids.resize(nb > 0 ? nb : 0);
+    p.seg_e.clear();
+    p.seg_s.clear();
+    for (int i = 0; i < nb; ++i) p.order[i] = i;
+    std::stable_sort(p.order.begin(), p.order.end(), [&](int32_t a, int32_t b) { return ids[a] < ids[b]; });
+    for (int j = 0; j < nb; ++j) {
+        p.ids[j] = ids[p.order[j]];
+        if (j == 0 || p.ids[j] != p.ids[j - 1]) { p.seg_e.push_back(p.ids[j]); p.seg_s.push_back(j); }
+    }
+    p.seg_s.push_back(nb);
+    p.pattern = mix_pattern(p.seg_e, p.seg_s, n_experts);
+}
+
+uint64_t mix_pattern(const std::vector<int>& seg_e, const std::vector<int>& seg_s, int n_experts) {
+    if (seg_e.size() <= 1) return 0;
+    if (n_experts > 8) return MIX_NO_GRAPH;
+    uint64_t code = 0;
+    for (size_t s = 0; s < seg_e.size(); ++s) {
+        const int cnt = seg_s[s + 1] - seg_s[s];
+        if (cnt > 254) return MIX_NO_GRAPH;
+        code |= (uint64_t)cnt << (8 * seg_e[s]);   // one byte per expert: two count vectors share a code only if they are equal
+    }
+    return code;
+}
+
+void mix_records(const MixPlan& p, const int32_t* k_per_expert, int Kmax, int32_t* first, int32_t* K) {
+    for (size_t s = 0; s < p.seg_e.size(); ++s)
+        for (int j = p.seg_s[s]; j < p.seg_s[s + 1]; ++j) {
+            K[j] = k_per_expert[p.seg_e[s]];
+            first[j] = p.seg_s[s] * Kmax + (j - p.seg_s[s]) * K[j];
+        }
 }
 
 // ---- asynchronous host path ----------------------------------------------------------------------------------------------
@@ -427,26 +512,24 @@ int vp_infer_experts(vp_handle c, const void* crops, int32_t fmt, int32_t n, con
     int rc = check_ready(c, fmt, n, crops, out);
     if (rc) return rc;
     if (!c->n_experts) return fail(c, VP_ERR_STATE, "vp_infer_experts: the handle holds a plain (single-dataset) checkpoint, not a ViTPose+ one");
-    if (n > 0 && !expert_ids) return fail(c, VP_ERR_INVALID, "null expert_ids");
-    for (int i = 0; i < n; ++i)
-        if (expert_ids[i] < 0 || expert_ids[i] >= c->n_experts)
-            return fail(c, VP_ERR_INVALID, "expert id " + std::to_string(expert_ids[i]) + " of crop " + std::to_string(i) + " outside [0, " + std::to_string(c->n_experts) + ")");
+    std::string why;
+    if (mix_check_ids(expert_ids, n, c->n_experts, &why)) return fail(c, VP_ERR_INVALID, why);
     if ((rc = slots_idle(c, "vp_infer_experts"))) return rc;
     if (c->flip_on) return fail(c, VP_ERR_STATE, "vp_infer_experts does not run under the flip-test mode (one partner table per handle, not per crop): call vp_clear_flip_test first");
     // per chunk, the crops in expert order (stable): each expert is one contiguous segment, so that mlp.fc2's m-tiles see one expert and the head runs once per expert
     const int saved = c->expert, D = c->D;
     const size_t cb = crop_bytes(fmt), B = (size_t)((c->maxb + 3) / 4 * 4);
     std::vector<int32_t> ids(2 * B), wh(2 * (size_t)c->maxb);
-    std::vector<int> order(c->maxb);
+    MixPlan& p = c->mix_host;   // the chunk's plan (mix_plan): the one the device, frames and boxes entries run
     std::vector<float> kp((size_t)c->maxb * c->Kmax * 3);
     FwdOpts encoder_only;
     encoder_only.head = false;
     rc = for_chunks(n, c->maxb, [&](int off, int nb) -> int {
         int rc;
-        for (int j = 0; j < nb; ++j) order[j] = off + j;
-        std::stable_sort(order.begin(), order.begin() + nb, [&](int a, int b) { return expert_ids[a] < expert_ids[b]; });
+        mix_plan(expert_ids + off, nb, c->n_experts, p);
+        const std::vector<int>&seg_e = p.seg_e, &seg_s = p.seg_s;
         bool identity = true;
-        for (int j = 0; j < nb; ++j) identity = identity && order[j] == off + j;
+        for (int j = 0; j < nb; ++j) identity = identity && p.order[j] == j;
         if (identity) {
             if ((rc = stage_in(c, crops, fmt, nullptr, off, nb))) return rc;   // (the sizes follow in expert order)
         } else {   // one upload in the caller's order, then a device gather into expert order
@@ -454,18 +537,15 @@ int vp_infer_experts(vp_handle c, const void* crops, int32_t fmt, int32_t n, con
             HIPCHK(c, hipMemcpyAsync(c->mix_stage, (const char*)crops + (size_t)off * cb, (size_t)nb * cb, hipMemcpyHostToDevice, c->stream));
         }
         if (org_wh) {
-            for (int j = 0; j < nb; ++j) { wh[2 * j] = org_wh[2 * (size_t)order[j]]; wh[2 * j + 1] = org_wh[2 * (size_t)order[j] + 1]; }
+            for (int j = 0; j < nb; ++j) { wh[2 * j] = org_wh[2 * (size_t)(off + p.order[j])]; wh[2 * j + 1] = org_wh[2 * (size_t)(off + p.order[j]) + 1]; }
             HIPCHK(c, hipMemcpyAsync(c->wh_stage, wh.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
         }
         const int32_t* d_wh = org_wh ? c->wh_stage : nullptr;
-        // segments of the chunk: (expert, first crop, count); ids[B + j] = the gather order
-        std::vector<int> seg_e, seg_s;
+        // ids[j] = the experts in expert order, ids[B + j] = the gather order
         for (int j = 0; j < nb; ++j) {
-            ids[j] = expert_ids[order[j]];
-            ids[B + j] = order[j] - off;
-            if (j == 0 || ids[j] != ids[j - 1]) { seg_e.push_back(ids[j]); seg_s.push_back(j); }
+            ids[j] = p.ids[j];
+            ids[B + j] = p.order[j];
         }
-        seg_s.push_back(nb);
         for (size_t j = nb; j < B; ++j) ids[j] = ids[nb - 1];   // encoder padding crops repeat the last crop (pick_run_batch)
         if (!identity) {
             HIPCHK(c, hipMemcpyAsync(c->expert_ids, ids.data(), 2 * B * 4, hipMemcpyHostToDevice, c->stream));
@@ -498,12 +578,61 @@ int vp_infer_experts(vp_handle c, const void* crops, int32_t fmt, int32_t n, con
         for (size_t s = 0; s < seg_e.size(); ++s) {
             const int K = c->ex_heads[seg_e[s]].K;
             for (int j = seg_s[s]; j < seg_s[s + 1]; ++j) {
-                float* dst = out + (size_t)order[j] * c->Kmax * 3;
+                float* dst = out + (size_t)(off + p.order[j]) * c->Kmax * 3;
                 std::memcpy(dst, &kp[((size_t)seg_s[s] * c->Kmax + (size_t)(j - seg_s[s]) * K) * 3], (size_t)K * 12);
                 std::memset(dst + (size_t)K * 3, 0, (size_t)(c->Kmax - K) * 12);
             }
         }
         return VP_OK;
+    });
+    use_expert(c, saved);
+    return rc;
+}
+
+int vp_infer_experts_device_stream(vp_handle c, const void* d_crops, int32_t fmt, int32_t n, const int32_t* expert_ids, const int32_t* d_org_wh, float* d_out,
+                                   void* caller_stream) {
+    int rc = check_ready(c, fmt, n, d_crops, d_out, false);
+    if (rc || (rc = mix_ready(c, "vp_infer_experts_device_stream", n, expert_ids))) return rc;
+    const int saved = c->expert;
+    rc = caller_ordered(c, (hipStream_t)caller_stream, n, [&]() {
+        return for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // vp_infer_experts' chunks: the same crops per chunk, so the same plan and bits
+            MixPlan& p = c->mix_host;
+            if (const int rc = mix_chunk_tables(c, expert_ids, off, nb, p)) return rc;
+            return run_mix_chunk(c, p, (const char*)d_crops + (size_t)off * crop_bytes(fmt), fmt, nb, d_org_wh ? d_org_wh + 2 * (size_t)off : nullptr,
+                                 d_out + (size_t)off * c->Kmax * 3);
+        });
+    });
+    use_expert(c, saved);
+    return rc;
+}
+
+int vp_infer_frames_experts(vp_handle c, const vp_frame* frames, int32_t n_frames, int32_t on_device, const int32_t* p9, int32_t n, const int32_t* expert_ids,
+                            float* out) {
+    if (!c) return VP_ERR_INVALID;
+    std::vector<int32_t> bands((size_t)(n_frames > 0 ? n_frames : 0) * 2);
+    std::string why;
+    if (frame_plan(frames, n_frames, p9, n, bands.data(), &why)) return fail(c, VP_ERR_INVALID, why);   // before any copy or launch
+    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, p9, out);
+    if (rc || (rc = mix_ready(c, "vp_infer_frames_experts", n, expert_ids)) || n == 0) return rc;
+    std::vector<vp::CropRec> recs;
+    if ((rc = stage_frames(c, frames, n_frames, on_device != 0, p9, n, bands.data(), recs))) return rc;
+    if (!c->crecs && (rc = dalloc(c, &c->crecs, (size_t)c->maxb))) return rc;
+    std::vector<int32_t> wh((size_t)c->maxb * 2);
+    std::vector<vp::CropRec> sorted((size_t)c->maxb);
+    const int saved = c->expert;
+    rc = for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // vp_infer_frames' staging per chunk; the records go to their place in the expert order
+        MixPlan& p = c->mix_host;
+        int rc = mix_chunk_tables(c, expert_ids, off, nb, p);
+        if (rc) return rc;
+        for (int j = 0; j < nb; ++j) sorted[j] = recs[(size_t)off + p.order[j]];
+        HIPCHK(c, hipMemcpyAsync(c->crecs, sorted.data(), (size_t)nb * sizeof(vp::CropRec), hipMemcpyHostToDevice, c->stream));
+        LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5, vp::crop_resize_launch(c->crecs, (uint8_t*)c->in_stage, nb, c->stream));
+        // the decode sizes stay in the caller's order: the record route reads the row it writes
+        for (int i = 0; i < nb; ++i) { wh[2 * i] = p9[9 * (size_t)(off + i) + 7]; wh[2 * i + 1] = p9[9 * (size_t)(off + i) + 8]; }
+        HIPCHK(c, hipMemcpyAsync(c->wh_stage, wh.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // sorted / wh are rewritten for the next chunk
+        if ((rc = run_mix_chunk(c, p, c->in_stage, VP_INPUT_U8_NHWC, nb, c->wh_stage, c->kp))) return rc;
+        return copy_out_sync(c, out, c->kp, (size_t)c->Kmax * 3, off, nb);
     });
     use_expert(c, saved);
     return rc;
@@ -553,8 +682,9 @@ int vp_dbg_frame_plan(const vp_frame* frames, int32_t n_frames, const int32_t* p
     return rc;
 }
 
-int vp_infer_boxes_stream(vp_handle c, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx,
-                          int32_t n, int32_t pad, float* d_out, int32_t* d_crop_params, int32_t* d_status, void* caller_stream) {
+// vp_infer_boxes_stream (expert_ids == null) and vp_infer_boxes_experts_stream
+static int boxes_impl(vp_ctx* c, const char* who, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx,
+                      int32_t n, int32_t pad, const int32_t* expert_ids, bool mixed, float* d_out, int32_t* d_crop_params, int32_t* d_status, void* caller_stream) {
     if (!c) return VP_ERR_INVALID;
     // every host argument is checked before anything is enqueued
     if (n > 0 && (!frames || !d_xyxy || !d_out)) return fail(c, VP_ERR_INVALID, "null frame table, box or output pointer");
@@ -563,14 +693,18 @@ int vp_infer_boxes_stream(vp_handle c, const vp_frame* frames, int32_t n_frames,
     std::string why;
     if (box_args(n_frames, hw.data(), 2, row_stride, n, pad, &why)) return fail(c, VP_ERR_INVALID, why);
     int rc = check_ready(c, VP_INPUT_U8_NHWC, n, d_xyxy, d_out, false);
-    if (rc || n == 0) return rc;
+    if (rc || (mixed && (rc = mix_ready(c, who, n, expert_ids))) || n == 0) return rc;
     for (int f = 0; f < n_frames; ++f)   // every frame of the table: which ones the boxes name is on the device
         if ((rc = check_device_frame(c, frames[f], f))) return rc;
     // the chunk's crop records / decode sizes / offsets live in handle buffers sized by max_batch, allocated on the first call
     if (!c->crecs && (rc = dalloc(c, &c->crecs, (size_t)c->maxb))) return rc;
     if (!c->box_aux && (rc = dalloc(c, &c->box_aux, (size_t)c->maxb * 4))) return rc;
-    return caller_ordered(c, (hipStream_t)caller_stream, n, [&]() {
+    const int saved = c->expert;
+    rc = caller_ordered(c, (hipStream_t)caller_stream, n, [&]() {
         return for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // vp_infer_frames' chunks: the same crops per chunk, so the same plan and bits
+            MixPlan& p = c->mix_host;
+            if (mixed)   // the tables first: the box kernel writes each crop record to its place in the expert order (sizes, offsets, params and status stay in the caller's)
+                if (const int rc = mix_chunk_tables(c, expert_ids, off, nb, p)) return rc;
             // geometry + crop run eagerly in front of the chunk's graph: the frame pointers change from call to call, the graph's buffers do not
             for (int f0 = 0; f0 < n_frames; f0 += vp::BOX_FRAMES_PER_LAUNCH) {
                 vp::BoxFrames bf;
@@ -580,12 +714,27 @@ int vp_infer_boxes_stream(vp_handle c, const vp_frame* frames, int32_t n_frames,
                 LAUNCH(c, VP_PROF_IM2COL, 0.0, 64.0 * nb,
                        vp::box_geometry_launch(bf, d_xyxy + (size_t)off * row_stride, row_stride, d_frame_idx ? d_frame_idx + off : nullptr, nb, pad,
                                                (const uint8_t*)c->zero, c->crecs, c->wh_stage, c->box_aux,
-                                               d_crop_params ? d_crop_params + (size_t)off * 9 : nullptr, d_status ? d_status + off : nullptr, c->stream));
+                                               d_crop_params ? d_crop_params + (size_t)off * 9 : nullptr, d_status ? d_status + off : nullptr, c->stream,
+                                               mixed ? c->mix_slot : nullptr));
             }
             LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5, vp::crop_resize_launch(c->crecs, (uint8_t*)c->in_stage, nb, c->stream));
+            if (mixed) return run_mix_chunk(c, p, c->in_stage, VP_INPUT_U8_NHWC, nb, c->wh_stage, d_out + (size_t)off * c->Kmax * 3, c->box_aux);
             return run_chunk(c, c->in_stage, VP_INPUT_U8_NHWC, nb, c->wh_stage, d_out + (size_t)off * c->Kp * 3, c->box_aux);
         });
     });
+    if (mixed) use_expert(c, saved);
+    return rc;
+}
+
+int vp_infer_boxes_stream(vp_handle c, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx,
+                          int32_t n, int32_t pad, float* d_out, int32_t* d_crop_params, int32_t* d_status, void* caller_stream) {
+    return boxes_impl(c, "vp_infer_boxes_stream", frames, n_frames, d_xyxy, row_stride, d_frame_idx, n, pad, nullptr, false, d_out, d_crop_params, d_status, caller_stream);
+}
+
+int vp_infer_boxes_experts_stream(vp_handle c, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx,
+                                  int32_t n, int32_t pad, const int32_t* expert_ids, float* d_out, int32_t* d_crop_params, int32_t* d_status, void* caller_stream) {
+    return boxes_impl(c, "vp_infer_boxes_experts_stream", frames, n_frames, d_xyxy, row_stride, d_frame_idx, n, pad, expert_ids, true, d_out, d_crop_params, d_status,
+                      caller_stream);
 }
 
 int vp_dbg_box_geometry(const float* xyxy, int32_t row_stride, const int32_t* frame_idx, const int32_t* frame_hw, int32_t n_frames, int32_t n, int32_t pad,
@@ -657,6 +806,76 @@ int vp_dbg_decode_flip(int32_t device_id, const float* heatmaps2, int32_t n, int
     std::string why;
     if (flip_partner_table(k, flip_pairs, n_pairs, partner.data(), &why)) return fail(nullptr, VP_ERR_INVALID, why);
     return decode_host(device_id, heatmaps2, n, k, partner.data(), shift_heatmap, org_wh, out);
+}
+
+int vp_dbg_mix_plan(const int32_t* expert_ids, int32_t n, int32_t n_experts, int32_t max_batch, const int32_t* k_per_expert, int32_t* order, int32_t* ids_padded,
+                    int32_t* counts, int32_t* records, uint64_t* pattern) {
+    if (n < 0 || n_experts <= 0 || max_batch <= 0 || (n > 0 && !expert_ids)) return fail(nullptr, VP_ERR_INVALID, "bad argument");
+    std::string why;
+    if (mix_check_ids(expert_ids, n, n_experts, &why)) return fail(nullptr, VP_ERR_INVALID, why);
+    const int B = (max_batch + 3) / 4 * 4;
+    int kmax = 0;
+    for (int e = 0; e < n_experts && k_per_expert; ++e) kmax = std::max(kmax, k_per_expert[e]);
+    int ci = 0;
+    const int rc = for_chunks(n, max_batch, [&](int off, int nb) -> int {   // the entries' own walk
+        MixPlan p;
+        mix_plan(expert_ids + off, nb, n_experts, p);
+        if (order) std::memcpy(order + off, p.order.data(), (size_t)nb * 4);
+        if (ids_padded)   // what mix_tables_kernel leaves in the handle's id buffer
+            for (int j = 0; j < B; ++j) ids_padded[(size_t)ci * B + j] = p.ids[std::min(j, nb - 1)];
+        if (counts) {
+            std::memset(counts + (size_t)ci * n_experts, 0, (size_t)n_experts * 4);
+            for (size_t s = 0; s < p.seg_e.size(); ++s) counts[(size_t)ci * n_experts + p.seg_e[s]] = p.seg_s[s + 1] - p.seg_s[s];
+        }
+        if (records && k_per_expert) {
+            std::vector<int32_t> first(nb), K(nb);
+            mix_records(p, k_per_expert, kmax, first.data(), K.data());
+            for (int j = 0; j < nb; ++j) { int32_t* r = records + 3 * (size_t)(off + j); r[0] = first[j]; r[1] = K[j]; r[2] = p.order[j]; }
+        }
+        if (pattern) pattern[ci] = p.pattern;
+        ++ci;
+        return VP_OK;
+    });
+    return rc ? rc : ci;
+}
+
+int vp_dbg_decode_mix(int32_t device_id, const float* heatmaps, int32_t n_maps, int32_t n, int32_t kmax, const int32_t* records, const int32_t* org_wh, float* out) {
+    if (!heatmaps || !out || !records || n <= 0 || kmax <= 0 || n_maps <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
+    std::vector<uint8_t> seen((size_t)n, 0);
+    for (int j = 0; j < n; ++j) {   // every record inside the maps and the output, every output row written once
+        const int32_t* r = records + 3 * (size_t)j;
+        if (r[0] < 0 || r[1] <= 0 || r[1] > kmax || (int64_t)r[0] + r[1] > n_maps || r[2] < 0 || r[2] >= n || seen[r[2]]++)
+            return fail(nullptr, VP_ERR_INVALID, "record " + std::to_string(j) + " lies outside the maps or the output, or repeats a row");
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, VP_ERR_HIP, "no HIP device available (no CPU fallback)");
+    if (device_id < 0 || device_id >= ndev) return fail(nullptr, VP_ERR_INVALID, "device_id out of range");
+    vp_ctx* c = nullptr;
+    HIPCHK(c, hipSetDevice(device_id));
+    float *d_hm = nullptr, *d_out = nullptr;
+    int32_t* d_wh = nullptr;
+    vp::MixRec* d_rec = nullptr;
+    const size_t hb = (size_t)n_maps * 3072 * 4, ob = (size_t)n * kmax * 12;
+    hipError_t e = hipMalloc((void**)&d_hm, hb);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_out, ob);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_rec, (size_t)n * sizeof(vp::MixRec));
+    if (e == hipSuccess) e = hipMemcpy(d_hm, heatmaps, hb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rec, records, (size_t)n * sizeof(vp::MixRec), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_out, 0xff, ob);   // NaN: every value of the output must be written
+    if (e == hipSuccess && org_wh) {
+        e = hipMalloc((void**)&d_wh, (size_t)n * 8);
+        if (e == hipSuccess) e = hipMemcpy(d_wh, org_wh, (size_t)n * 8, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = vp::decode_mix_launch(d_hm, d_rec, d_wh, d_out, n, kmax, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost);
+    int rc = VP_OK;
+    if (e != hipSuccess) rc = fail(nullptr, VP_ERR_HIP, std::string("vp_dbg_decode_mix: ") + hipGetErrorString(e));
+    if (d_hm) hipFree(d_hm);
+    if (d_out) hipFree(d_out);
+    if (d_rec) hipFree(d_rec);
+    if (d_wh) hipFree(d_wh);
+    return rc;
 }
 
 }  // extern "C"

@@ -219,11 +219,10 @@ struct BoxFrames {
     int32_t f0, count, n_frames;
 };
 // boxes xyxy (row i at xyxy + i * row_stride) + frame index [n] (NULL: frame 0) -> crop records, decode sizes wh [n, 2] = (pw, ph),
-// aux [n, 4] = (y0 - top_pad, x0 - left_pad, status, 0); optional p9_out [n, 9] (frames_crop_params rows) and status_out [n]
+// aux [n, 4] = (y0 - top_pad, x0 - left_pad, status, 0); optional p9_out [n, 9] (frames_crop_params rows) and status_out [n].  slot (null: the identity):
+// box i's crop record goes to recs[slot[i]] -- a ViTPose+ chunk with per-crop experts crops straight into its expert order; every other row stays at i
 hipError_t box_geometry_launch(const BoxFrames& fr, const float* xyxy, int row_stride, const int32_t* frame_idx, int n, int pad, const uint8_t* zero_px,
-                               CropRec* recs, int32_t* wh, int32_t* aux, int32_t* p9_out, int32_t* status_out, hipStream_t s);
-// decoded keypoints [n, K, 3] in padded-crop pixels -> frame pixels (aux as above; status != 0: all zero)
-hipError_t box_offsets_launch(const int32_t* aux, float* out, int n, int K, hipStream_t s);
+                               CropRec* recs, int32_t* wh, int32_t* aux, int32_t* p9_out, int32_t* status_out, hipStream_t s, const int32_t* slot = nullptr);
 
 // --------------------------------------------------------------------- decode
 // heatmaps fp32 [N, K, 64, 48] -> out fp32 [N, K, 3] (y, x, conf); org_wh int32 [N,2] or null
@@ -231,5 +230,27 @@ hipError_t decode_launch(const float* hm, const int32_t* org_wh, float* out, int
 // flip-test mode: hm = the interleaved batch [2 N, K, 64, 48] (crop, mirror, crop, mirror, ...); decodes 0.5 (crop + flip_back(mirror)) without materialising it,
 // bit for bit flip_merge_launch + decode_launch
 hipError_t decode_flip_launch(const float* hm, const int32_t* partner, int shift, const int32_t* org_wh, float* out, int N, int K, hipStream_t s);
+
+// ViTPose+ chunk with per-crop experts: the crop at position j of the chunk's expert order.  `first` = index of its first 64 x 48 map in the chunk's heatmap
+// buffer, K = its expert's joint count, dst = its row in the caller's order (output row, and row of org_wh)
+struct MixRec {
+    int32_t first, K, dst;
+};
+// the record route of the decode: ONE launch for the whole chunk.  Block (j, k): k < recs[j].K decodes map recs[j].first + k as decode_launch does on a
+// [1, K, 64, 48] crop (same arithmetic, same summation orders, same bits) into out[recs[j].dst][k]; k >= K writes zeros.  out fp32 [N, Kmax, 3], org_wh [N, 2] or null
+hipError_t decode_mix_launch(const float* hm, const MixRec* recs, const int32_t* org_wh, float* out, int N, int Kmax, hipStream_t s);
+// vp_infer_boxes_stream: decoded keypoints [n, K, 3] in padded-crop pixels -> frame pixels (aux as box_geometry_launch writes it; status != 0: all zero).  slot + recs
+// (both or neither): rows of K = Kmax joints of a chunk with per-crop experts -- row i keeps the zeros behind its expert's recs[slot[i]].K joints
+hipError_t box_offsets_launch(const int32_t* aux, float* out, int n, int K, hipStream_t s, const int32_t* slot = nullptr, const MixRec* recs = nullptr);
+
+// The per-call tables of such a chunk travel by kernel argument (no copy from host memory): positions [base, base + count) of the expert order per launch --
+// id = the expert, order = the caller row (gather_crops_launch's index, MixRec::dst), first / K as MixRec.  The launch with pad_to > 0 (the chunk's last)
+// also writes ids[base + count .. pad_to) = its last id: the encoder's padding crops repeat the last crop.  slot[order[j]] = j: the caller row's position.
+constexpr int MIX_CROPS_PER_LAUNCH = 128;
+struct MixTable {
+    int32_t id[MIX_CROPS_PER_LAUNCH], order[MIX_CROPS_PER_LAUNCH], first[MIX_CROPS_PER_LAUNCH], K[MIX_CROPS_PER_LAUNCH];
+    int32_t base, count, pad_to;
+};
+hipError_t mix_tables_launch(const MixTable& t, int32_t* ids, int32_t* order, int32_t* slot, MixRec* recs, hipStream_t s);
 
 }  // namespace vp

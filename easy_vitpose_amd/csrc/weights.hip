@@ -369,7 +369,7 @@ int vp_load_weights(vp_handle c, const vp_tensor_desc* tensors, int32_t n_tensor
             if ((rc = realloc_dev(c, &c->hm, B * kmax * 3072)) || (rc = realloc_dev(c, &c->kp, B * kmax * 3))) return rc;
             c->Kmax = kmax;
         }
-        if ((rc = dalloc(c, &c->expert_ids, 2 * B))) return rc;
+        if ((rc = dalloc(c, &c->expert_ids, 2 * B)) || (rc = dalloc(c, &c->mix_slot, B)) || (rc = dalloc(c, &c->mix_recs, B))) return rc;
         c->n_experts = E; c->part_features = P;
         use_expert(c, 0);
     } else {

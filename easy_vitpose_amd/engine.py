@@ -153,6 +153,44 @@ class VitPoseHip:
         ks = np.array([self.experts[i][1] if 0 <= i < len(self.experts) else 0 for i in ids], dtype=np.int32)
         return out, ks
 
+    def _dataset_ids(self, datasets, n: int) -> np.ndarray:
+        """`datasets` (names or expert indices, one per crop) -> int32 [n] expert ids (an unknown name becomes -1: the library refuses it, naming the crop)"""
+        if not self._moe:
+            raise capi.VpError(capi.VP_ERR_STATE, 'datasets=: the handle holds a plain (single-dataset) checkpoint, not a ViTPose+ one')
+        names = [d for d, _ in self.experts]
+        ids = np.ascontiguousarray([names.index(d) if isinstance(d, str) and d in names else (d if not isinstance(d, str) else -1)
+                                    for d in datasets], dtype=np.int32)
+        if len(ids) != n:   # the library reads n ids
+            raise ValueError(f'datasets: one per crop expected ({n}), got {len(ids)}')
+        return ids
+
+    def dataset_k(self, datasets) -> np.ndarray:
+        """int32 [n]: the joints each row of a per-crop dataset call fills (the rest of its Kmax joints are 0)"""
+        datasets = list(datasets)
+        return np.array([self.experts[i][1] for i in self._dataset_ids(datasets, len(datasets))], dtype=np.int32)
+
+    def infer_mixed_device(self, d_crops, datasets, d_out, org_wh=None, stream=None):
+        """`infer_mixed` on device-resident torch tensors, stream-ordered (vp_infer_experts_device_stream, contract in include/vitpose_hip.h):
+        `d_crops` as in `infer_device`, `datasets` one name or expert index per crop (host), `d_out` float32 CUDA with n x Kmax x 3 elements --
+        row i fills its first K of its dataset's joints (`dataset_k`), the rest are 0, rows in the caller's order, bit for bit `infer_mixed`'s.
+        `org_wh`: int32 CUDA [n, 2] or None.  `stream`: a torch stream or a raw hipStream_t value (None: torch's current stream); ordering and host
+        behaviour as `infer_device(ordered=True)` -- nothing blocks the host, consume `d_out` on that stream.  The active dataset is unchanged."""
+        import torch
+        assert d_crops.is_cuda and d_out.is_cuda and d_crops.is_contiguous() and d_out.is_contiguous()
+        fmt = capi.VP_INPUT_U8_NHWC if d_crops.dtype == torch.uint8 else capi.VP_INPUT_F32_NCHW
+        n = d_crops.shape[0]
+        ids = self._dataset_ids(datasets, n)
+        assert d_out.dtype == torch.float32 and d_out.numel() == n * self.Kmax * 3
+        whp = None
+        if org_wh is not None:
+            assert org_wh.is_cuda and org_wh.dtype == torch.int32 and org_wh.numel() == 2 * n
+            whp = org_wh.data_ptr()
+        if stream is None:
+            stream = torch.cuda.current_stream(d_crops.device)
+        cs = stream.cuda_stream if hasattr(stream, 'cuda_stream') else int(stream)
+        capi.check(self.lib.vp_infer_experts_device_stream(self._h, d_crops.data_ptr(), fmt, n, ids.ctypes.data, whp, d_out.data_ptr(), cs), self._h)
+        return d_out
+
     # ------------------------------------------------------------ inference
     @staticmethod
     def _fmt(crops: np.ndarray):
@@ -272,9 +310,11 @@ class VitPoseHip:
                                            params.ctypes.data, n, out.ctypes.data), self._h)
         return out
 
-    def infer_frames(self, frames, params: np.ndarray) -> np.ndarray:
+    def infer_frames(self, frames, params: np.ndarray, datasets=None):
         """The crops of several frames in one call (vp_infer_frames): params [n, 9] (cropprep.frames_crop_params) -> [n, K, 3] in
-        padded-crop pixels.  `frames`: numpy uint8 [H, W, 3] arrays (host path: one upload of the row band each frame's crops cover),
+        padded-crop pixels.  `datasets` (a ViTPose+ handle: one name or expert index per crop, as in `infer_mixed`): a dataset per crop in the
+        same call (vp_infer_frames_experts) -- returns ``(out, k)`` as `infer_mixed` does, ``out`` [n, Kmax, 3] with row i's first ``k[i]``
+        joints filled, bit for bit `infer_mixed` on the host-prepared crops.  `frames`: numpy uint8 [H, W, 3] arrays (host path: one upload of the row band each frame's crops cover),
         or contiguous torch uint8 CUDA tensors [H, W, 3] on this handle's device (read in place, once torch's current stream on that
         device has been synchronised).  A list that mixes the two raises TypeError."""
         frames = list(frames)
@@ -303,23 +343,31 @@ class VitPoseHip:
             if f.ndim != 3 or f.shape[2] != 3:
                 raise ValueError(f'frame {i}: [H, W, 3] expected, got {tuple(f.shape)}')
             table[i] = capi.vp_frame(ptr, f.shape[0], f.shape[1])
-        out = np.empty((n, self.K, 3), dtype=np.float32)
-        if n == 0:
-            return out
-        if on_device:
+        ids = None if datasets is None else self._dataset_ids(datasets, n)
+        out = np.empty((n, self.K if ids is None else self.Kmax, 3), dtype=np.float32)
+        if n and on_device:
             import torch
             torch.cuda.current_stream(torch.device('cuda', self.device_id)).synchronize()   # the frames are complete before the library reads them
-        capi.check(self.lib.vp_infer_frames(self._h, table, len(frames), int(on_device), params.ctypes.data, n, out.ctypes.data), self._h)
+        if ids is not None:
+            if n:
+                capi.check(self.lib.vp_infer_frames_experts(self._h, table, len(frames), int(on_device), params.ctypes.data, n, ids.ctypes.data,
+                                                            out.ctypes.data), self._h)
+            return out, self.dataset_k(ids)
+        if n:
+            capi.check(self.lib.vp_infer_frames(self._h, table, len(frames), int(on_device), params.ctypes.data, n, out.ctypes.data), self._h)
         return out
 
-    def infer_boxes(self, frames, boxes, frame_index=None, pad: int = 10, out=None, crop_params: bool = False, status: bool = False):
+    def infer_boxes(self, frames, boxes, frame_index=None, pad: int = 10, out=None, crop_params: bool = False, status: bool = False, datasets=None):
         """Detector boxes on device frames -> keypoints in FRAME pixels, all on the device (vp_infer_boxes_stream, contract in
         include/vitpose_hip.h).  `frames`: contiguous torch uint8 CUDA tensors [H, W, 3] on this handle's device; `boxes`: float32 CUDA
         [n, >= 4] (x1, y1, x2, y2, ...) with unit column stride, e.g. a detector's [n, 6] output as it is; `frame_index`: int32 CUDA [n]
         (None: every box on frame 0); `pad`: pixels added on every side before clipping.  Returns `out` float32 [n, K, 3] (allocated
         when not given), plus int32 [n, 9] crop params (cropprep.frames_crop_params rows) and int32 [n] status (0 ok, 1 bad frame index,
         2 non-finite box, 3 empty box; such rows are all zero) when asked for.  Everything is enqueued on torch's current stream without
-        a host synchronisation, under the ordering notes of `infer_device`: consume the results with torch ops on that stream."""
+        a host synchronisation, under the ordering notes of `infer_device`: consume the results with torch ops on that stream.
+        `datasets` (a ViTPose+ handle: one name or expert index per box, on the host, as in `infer_mixed`): a dataset per box in the same call
+        (vp_infer_boxes_experts_stream) -- `out` is then [n, Kmax, 3], row i's first `dataset_k(datasets)[i]` joints filled and the rest 0;
+        crop params and status are the plain call's."""
         import torch
         dev = torch.device('cuda', self.device_id)
         frames = list(frames)
@@ -347,16 +395,23 @@ class VitPoseHip:
             if frame_index.device != dev or tuple(frame_index.shape) != (n,) or not frame_index.is_contiguous():
                 raise ValueError(f'frame_index: contiguous [{n}] on {dev} expected, got {tuple(frame_index.shape)} on {frame_index.device}')
             fip = frame_index.data_ptr()
+        ids = None if datasets is None else self._dataset_ids(datasets, n)
+        K = self.K if ids is None else self.Kmax
         if out is None:
-            out = torch.empty((n, self.K, 3), dtype=torch.float32, device=dev)
+            out = torch.empty((n, K, 3), dtype=torch.float32, device=dev)
         elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-                  and out.device == dev and out.numel() == n * self.K * 3):
-            raise ValueError(f'out: a contiguous float32 tensor of {n} x {self.K} x 3 on {dev} expected')
+                  and out.device == dev and out.numel() == n * K * 3):
+            raise ValueError(f'out: a contiguous float32 tensor of {n} x {K} x 3 on {dev} expected')
         cp = torch.empty((n, 9), dtype=torch.int32, device=dev) if crop_params else None
         st = torch.empty((n,), dtype=torch.int32, device=dev) if status else None
         cs = torch.cuda.current_stream(dev).cuda_stream
-        capi.check(self.lib.vp_infer_boxes_stream(self._h, table, len(frames), boxes.data_ptr(), row_stride, fip, n, int(pad), out.data_ptr(),
-                                                  None if cp is None else cp.data_ptr(), None if st is None else st.data_ptr(), cs), self._h)
+        if ids is not None:
+            capi.check(self.lib.vp_infer_boxes_experts_stream(self._h, table, len(frames), boxes.data_ptr(), row_stride, fip, n, int(pad), ids.ctypes.data,
+                                                              out.data_ptr(), None if cp is None else cp.data_ptr(), None if st is None else st.data_ptr(),
+                                                              cs), self._h)
+        else:
+            capi.check(self.lib.vp_infer_boxes_stream(self._h, table, len(frames), boxes.data_ptr(), row_stride, fip, n, int(pad), out.data_ptr(),
+                                                      None if cp is None else cp.data_ptr(), None if st is None else st.data_ptr(), cs), self._h)
         if cp is None and st is None:
             return out
         return (out,) + tuple(t for t in (cp, st) if t is not None)

@@ -311,6 +311,49 @@ VP_API int vp_set_expert(vp_handle h, int32_t e);
 VP_API int vp_infer_experts(vp_handle h, const void* crops, int32_t input_format, int32_t n, const int32_t* expert_ids,
                             const int32_t* org_wh, float* out);
 
+/* Per-crop experts on the production entries: the twins of vp_infer_device_stream, vp_infer_frames and vp_infer_boxes_stream that take expert_ids -- HOST
+ * int32 [n], expert_ids[i] in [0, E) the dataset of crop / box i (the caller knows n, and which detector or class group produced which rows, on the host).
+ * Everything else -- arguments, staging, chunks of max_batch, ordering, what blocks the host and what does not -- is the plain entry's; the outputs are
+ * [n, Kmax, 3] rows in the CALLER's order with the joints beyond K_{e_i} written as 0, as vp_infer_experts returns them, on the device where the plain entry
+ * writes to the device.  Row i has the bits of vp_infer_experts on the same crops, ids and max_batch.
+ *   How a chunk runs: its crops in stable expert order (device crops: one gather; frames and boxes are cropped straight into that order), the encoder once
+ *   with every expert's mlp.fc2 in one launch per layer, one head per expert present, ONE decode launch for the whole chunk that writes each crop's row in the
+ *   caller's order, the boxes entry's offsets on those rows.  The chunk's tables (ids, order, decode records) reach the device as kernel arguments of a small
+ *   kernel in front of the chunk: no copy from host memory, no synchronisation.  Chunks of <= 16 crops replay a hipGraph keyed on the count per expert: two
+ *   calls with the same counts in another permutation replay the same graph.  A chunk whose crops share one expert runs the plain forward of that expert.
+ * vp_infer_experts_device_stream: ordering and host behaviour of vp_infer_device_stream (<= 16 crops on caller_stream itself, larger batches on the handle's
+ *   stream between two events; never blocks the host but for the graph eviction documented there).  d_org_wh: device int32 [n, 2] in the caller's order, or NULL.
+ * vp_infer_frames_experts: vp_infer_frames' staging and host waits; out = host float32 [n, Kmax, 3] in padded-crop pixels.
+ * vp_infer_boxes_experts_stream: vp_infer_boxes_stream plus expert_ids; d_out = device float32 [n, Kmax, 3] in frame pixels, d_crop_params and d_status in
+ *   the caller's order with the plain entry's values; a row with a non-zero status reads no frame and is all zero.
+ * Refusals, before anything is enqueued: the plain entry's own, then VP_ERR_STATE on a plain (single-dataset) handle, VP_ERR_INVALID for NULL expert_ids or an
+ * id outside [0, E) (the message names the crop), VP_ERR_STATE while the flip-test mode is on (its partner table belongs to one head) or a vp_infer_submit is in
+ * flight.  The active expert (vp_set_expert) is the same after the call as before.  Library builds that carry these entries define VP_HAS_EXPERT_ENTRIES. */
+#define VP_HAS_EXPERT_ENTRIES 1
+VP_API int vp_infer_experts_device_stream(vp_handle h, const void* d_crops, int32_t input_format, int32_t n, const int32_t* expert_ids,
+                                          const int32_t* d_org_wh, float* d_out, void* caller_stream);
+VP_API int vp_infer_frames_experts(vp_handle h, const vp_frame* frames, int32_t n_frames, int32_t frames_on_device, const int32_t* crop_params,
+                                   int32_t n, const int32_t* expert_ids, float* out);
+VP_API int vp_infer_boxes_experts_stream(vp_handle h, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride,
+                                         const int32_t* d_frame_idx, int32_t n, int32_t pad, const int32_t* expert_ids, float* d_out,
+                                         int32_t* d_crop_params, int32_t* d_status, void* caller_stream);
+/* HOST ONLY, no device needed: the plan those entries run for expert_ids [n] on a handle of n_experts experts and max_batch crops per chunk -- the pure function
+ * ids -> order, segments that shapes their launches.  Per chunk c (crops [c max_batch, ...)), with B = max_batch rounded up to a multiple of 4:
+ *   order [n]: position j of chunk c holds the chunk-local caller row order[c max_batch + j] (stable expert order)
+ *   ids_padded [chunks, B]: the experts in that order; the rows beyond the chunk repeat the last id (the encoder's padding crops)
+ *   counts [chunks, n_experts]: crops per expert = the run-length segments of the sorted ids
+ *   records [n, 3]: the decode's record per position {first heatmap of the crop, K_e, destination row}, given k_per_expert [n_experts]
+ *   pattern [chunks]: the expert pattern in the hipGraph key -- an exact code of `counts` (one byte per expert), 0 for a chunk of one expert, all ones where
+ *   the counts do not fit (more than 8 experts or 254 crops of one: such a chunk runs eagerly)
+ * Any output may be NULL.  Returns the number of chunks, or VP_ERR_INVALID (< 0) for an id outside [0, n_experts) (vp_last_error(NULL) names the crop). */
+VP_API int vp_dbg_mix_plan(const int32_t* expert_ids, int32_t n, int32_t n_experts, int32_t max_batch, const int32_t* k_per_expert, int32_t* order,
+                           int32_t* ids_padded, int32_t* counts, int32_t* records, uint64_t* pattern);
+/* The record route of the decode kernel alone, on host data (as vp_decode_only): heatmaps = float32 [n_maps, 64, 48]; records [n, 3] as above, crop j's K_j
+ * maps start at map first_j -> out [n, kmax, 3]: row dst_j = vp_decode_only of those K_j maps as one crop (org_wh [n, 2] by destination row, or NULL), bit for
+ * bit, joints beyond K_j zero.  VP_ERR_INVALID for a record outside the maps or the output, or two records with one destination. */
+VP_API int vp_dbg_decode_mix(int32_t device_id, const float* heatmaps, int32_t n_maps, int32_t n, int32_t kmax, const int32_t* records,
+                             const int32_t* org_wh, float* out);
+
 /* Decode alone: keypoints_from_heatmaps(unbiased=True, use_udp=True) + postprocess
  * (vit_utils/top_down_eval.py:493-641, easy_ViTPose/inference.py:187-205), one crop
  * at a time semantics.  heatmaps float32 [N, K, 64, 48] on the host. */
