@@ -203,16 +203,15 @@ struct vp_ctx {
     int n_experts = 0, part_features = 0, expert = 0;
     size_t fc2_w_stride = 0, fc2_b_stride = 0;
     std::vector<Head> ex_heads;
-    // vp_infer_experts, a chunk that mixes experts: the expert of every encoder crop (device [B], padding crops repeat the last one) and the crop index of
-    // every expert change; while set, mlp.fc2 runs all experts in one launch (GemmArgs::expert) on a tile whose rows never span two experts
-    int32_t* expert_ids = nullptr;    // [2 B]: the experts, then the gather order of the chunk's crops (gather_crops_launch)
-    void* mix_stage = nullptr;        // the chunk's crops in the caller's order, before the gather
+    // the per-crop expert entries (vp_infer_experts and its device, frames and boxes twins): the chunk's tables on the device, written by mix_tables_launch from kernel
+    // arguments in front of the chunk -- expert_ids [0, B) the expert of every encoder crop in expert order (padding crops repeat the last one) and [B, 2 B) the caller row of
+    // every position (gather_crops_launch), mix_slot = the position of every caller row, mix_recs = the decode's records.  mix = the host plan of the chunk run_chunk is
+    // running (null on every other entry): it shapes the launches of chunk_body
+    int32_t* expert_ids = nullptr;
+    void* mix_stage = nullptr;        // vp_infer_experts: the chunk's crops in the caller's order, before the gather
     size_t mix_stage_cap = 0;
-    const int32_t* mix_expert = nullptr;
-    std::vector<int> mix_bounds;
-    // the per-crop expert entries: the chunk's tables on the device, written by mix_tables_launch from kernel arguments in front of the chunk -- expert_ids [0, B) the
-    // experts in expert order and [B, 2 B) the caller row of every position (as vp_infer_experts lays them out), mix_slot = the position of every caller row,
-    // mix_recs = the decode's records.  mix = the host plan of the chunk run_chunk is running (null on every other entry): it shapes the launches of chunk_body
+    const int32_t* mix_expert = nullptr;   // set by mix_chunk_body around a mixed chunk's encoder, null otherwise: mlp.fc2 runs all experts in one launch (GemmArgs::expert) ...
+    std::vector<int> mix_bounds;           // ... on tiles that never span two experts: the crop index of every expert change
     int32_t* mix_slot = nullptr;
     vp::MixRec* mix_recs = nullptr;
     const vpi::MixPlan* mix = nullptr;
@@ -379,7 +378,7 @@ int gemm_fp8(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint8_t* A8,
 struct FwdOpts {
     bool tokens = false;   // also keep last_norm's fp32 tokens in c->tok (vp_infer_tokens)
     bool mirror = false;   // the crops are read mirrored left-right (vp_infer_flip's second pass)
-    bool head = true;      // false: the encoder and last_norm only, tokens in c->y (vp_infer_experts runs the head per expert segment)
+    bool head = true;      // false: the encoder and last_norm only, tokens in c->y (mix_chunk_body runs the head per expert segment)
     int twin_src = 0;      // > 0 (flip-test mode): n_in = 2 * twin_src rows, the twin_src crops at d_crops interleaved with their mirror images (crop, mirror, crop, mirror, ...)
 };
 int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, const FwdOpts& o = FwdOpts());

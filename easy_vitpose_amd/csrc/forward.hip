@@ -283,10 +283,10 @@ static int offsets_chunk(vp_ctx* c, const int32_t* aux, float* d_out, int n) {
     return VP_OK;
 }
 
-// The chunk of a per-crop expert entry (k.wide; c->mix = its plan, the tables are on the device).  Mixed (k.mix != 0): the crops into expert order (device crops:
-// one gather; frames and boxes were cropped straight into it), the encoder once with every expert's mlp.fc2 in one launch per layer on tiles that never span two
+// The chunk of a per-crop expert entry (k.wide; c->mix = its plan, the tables are on the device).  Mixed (k.mix != 0): the crops into expert order (crops in the
+// caller's order: one gather; frames and boxes were cropped straight into it), the encoder once with every expert's mlp.fc2 in one launch per layer on tiles that never span two
 // experts, one head per expert present on its segment's rows.  One expert: the plain forward under that expert.  Then ONE decode launch by records into rows of
-// Kmax joints in the caller's order, and the frame offsets on those rows.  Leaves the last segment's expert active: the entry restores the handle's own.
+// Kmax joints in the caller's order, and the frame offsets on those rows.  The only writer of c->mix_expert / c->mix_bounds.
 static int mix_chunk_body(vp_ctx* c, const GraphKey& k) {
     const MixPlan& m = *c->mix;
     const int nseg = (int)m.seg_e.size(), D = c->D;

@@ -15,9 +15,9 @@ template <class Body> int for_chunks(int n, int cap, Body body) {
     return VP_OK;
 }
 
-// The host-staged chunk: crops [off, off + nb) of a host batch into in_stage and, where given, their sizes into wh_stage, on c->stream ...
-int stage_in(vp_ctx* c, const void* crops, int fmt, const int32_t* org_wh, int off, int nb) {
-    HIPCHK(c, hipMemcpyAsync(c->in_stage, (const char*)crops + (size_t)off * crop_bytes(fmt), (size_t)nb * crop_bytes(fmt), hipMemcpyHostToDevice, c->stream));
+// The host-staged chunk: crops [off, off + nb) of a host batch into in_stage (or dst) and, where given, their sizes into wh_stage, on c->stream ...
+int stage_in(vp_ctx* c, const void* crops, int fmt, const int32_t* org_wh, int off, int nb, void* dst = nullptr) {
+    HIPCHK(c, hipMemcpyAsync(dst ? dst : c->in_stage, (const char*)crops + (size_t)off * crop_bytes(fmt), (size_t)nb * crop_bytes(fmt), hipMemcpyHostToDevice, c->stream));
     if (org_wh) HIPCHK(c, hipMemcpyAsync(c->wh_stage, org_wh + 2 * (size_t)off, (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
     return VP_OK;
 }
@@ -162,11 +162,13 @@ int mix_chunk_tables(vp_ctx* c, const int32_t* expert_ids, int off, int nb, MixP
     return VP_OK;
 }
 
-// run_chunk under plan p, whatever it returns
+// run_chunk under plan p; whatever it returns, the handle's own expert is the active one again (an eager chunk leaves its last segment's)
 int run_mix_chunk(vp_ctx* c, const MixPlan& p, const void* d_src, int fmt, int nb, const int32_t* d_wh, float* d_out, const int32_t* post = nullptr) {
+    const int own = c->expert;
     c->mix = &p;
     const int rc = run_chunk(c, d_src, fmt, nb, d_wh, d_out, post);
     c->mix = nullptr;
+    use_expert(c, own);
     return rc;
 }
 
@@ -510,91 +512,29 @@ int vp_infer_tokens(vp_handle c, const void* crops, int32_t fmt, int32_t n, floa
 
 int vp_infer_experts(vp_handle c, const void* crops, int32_t fmt, int32_t n, const int32_t* expert_ids, const int32_t* org_wh, float* out) {
     int rc = check_ready(c, fmt, n, crops, out);
-    if (rc) return rc;
-    if (!c->n_experts) return fail(c, VP_ERR_STATE, "vp_infer_experts: the handle holds a plain (single-dataset) checkpoint, not a ViTPose+ one");
-    std::string why;
-    if (mix_check_ids(expert_ids, n, c->n_experts, &why)) return fail(c, VP_ERR_INVALID, why);
-    if ((rc = slots_idle(c, "vp_infer_experts"))) return rc;
-    if (c->flip_on) return fail(c, VP_ERR_STATE, "vp_infer_experts does not run under the flip-test mode (one partner table per handle, not per crop): call vp_clear_flip_test first");
-    // per chunk, the crops in expert order (stable): each expert is one contiguous segment, so that mlp.fc2's m-tiles see one expert and the head runs once per expert
-    const int saved = c->expert, D = c->D;
-    const size_t cb = crop_bytes(fmt), B = (size_t)((c->maxb + 3) / 4 * 4);
-    std::vector<int32_t> ids(2 * B), wh(2 * (size_t)c->maxb);
-    MixPlan& p = c->mix_host;   // the chunk's plan (mix_plan): the one the device, frames and boxes entries run
-    std::vector<float> kp((size_t)c->maxb * c->Kmax * 3);
-    FwdOpts encoder_only;
-    encoder_only.head = false;
-    rc = for_chunks(n, c->maxb, [&](int off, int nb) -> int {
-        int rc;
-        mix_plan(expert_ids + off, nb, c->n_experts, p);
-        const std::vector<int>&seg_e = p.seg_e, &seg_s = p.seg_s;
-        bool identity = true;
-        for (int j = 0; j < nb; ++j) identity = identity && p.order[j] == j;
-        if (identity) {
-            if ((rc = stage_in(c, crops, fmt, nullptr, off, nb))) return rc;   // (the sizes follow in expert order)
-        } else {   // one upload in the caller's order, then a device gather into expert order
-            if ((rc = grow_buffer(c, &c->mix_stage, &c->mix_stage_cap, B * cb, "mixed-batch staging buffer"))) return rc;
-            HIPCHK(c, hipMemcpyAsync(c->mix_stage, (const char*)crops + (size_t)off * cb, (size_t)nb * cb, hipMemcpyHostToDevice, c->stream));
+    if (rc || (rc = mix_ready(c, "vp_infer_experts", n, expert_ids))) return rc;
+    return for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // the host-staged caller of the per-crop chunk: its twins' plan, tables, body and replay
+        MixPlan& p = c->mix_host;
+        int rc = mix_chunk_tables(c, expert_ids, off, nb, p);
+        if (rc) return rc;
+        // The crops go up in the caller's order.  Ids that never decrease (one expert among them) are the expert order already: straight into in_stage.
+        // Any other chunk goes into mix_stage, and the chunk body gathers: it does so exactly when its source is not in_stage
+        void* src = c->in_stage;
+        if (!std::is_sorted(expert_ids + off, expert_ids + off + nb)) {
+            if ((rc = grow_buffer(c, &c->mix_stage, &c->mix_stage_cap, (size_t)((c->maxb + 3) / 4 * 4) * crop_bytes(fmt), "mixed-batch staging buffer"))) return rc;
+            src = c->mix_stage;
         }
-        if (org_wh) {
-            for (int j = 0; j < nb; ++j) { wh[2 * j] = org_wh[2 * (size_t)(off + p.order[j])]; wh[2 * j + 1] = org_wh[2 * (size_t)(off + p.order[j]) + 1]; }
-            HIPCHK(c, hipMemcpyAsync(c->wh_stage, wh.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
-        }
-        const int32_t* d_wh = org_wh ? c->wh_stage : nullptr;
-        // ids[j] = the experts in expert order, ids[B + j] = the gather order
-        for (int j = 0; j < nb; ++j) {
-            ids[j] = p.ids[j];
-            ids[B + j] = p.order[j];
-        }
-        for (size_t j = nb; j < B; ++j) ids[j] = ids[nb - 1];   // encoder padding crops repeat the last crop (pick_run_batch)
-        if (!identity) {
-            HIPCHK(c, hipMemcpyAsync(c->expert_ids, ids.data(), 2 * B * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, vp::gather_crops_launch(c->mix_stage, c->in_stage, c->expert_ids + B, nb, cb, c->stream));
-        }
-        if (seg_e.size() == 1) {   // one expert: the single-dataset path as it is (tile rules, split-K, hipGraph replay keyed on the expert)
-            use_expert(c, seg_e[0]);
-            if ((rc = run_chunk(c, c->in_stage, fmt, nb, d_wh, c->kp))) return rc;
-        } else {
-            // mixed: the encoder once (mlp.fc2 of every expert in one launch per layer: GemmArgs::expert), then head + decode per expert segment.
-            // Eager: the expert pattern shapes the head launches, so a captured graph would have to be keyed on it (the single-expert path above replays)
-            if (identity) HIPCHK(c, hipMemcpyAsync(c->expert_ids, ids.data(), B * 4, hipMemcpyHostToDevice, c->stream));
-            c->mix_expert = c->expert_ids;
-            c->mix_bounds.assign(seg_s.begin() + 1, seg_s.end() - 1);
-            rc = forward_chunk(c, c->in_stage, fmt, nb, encoder_only);
-            c->mix_expert = nullptr;
-            c->mix_bounds.clear();
-            if (rc) return rc;
-            for (size_t s = 0; s < seg_e.size(); ++s) {
-                const int s0 = seg_s[s], cnt = seg_s[s + 1] - s0;
-                use_expert(c, seg_e[s]);
-                float* hm = c->hm + (size_t)s0 * c->Kmax * 3072;
-                if ((rc = head_chunk(c, c->y + (size_t)s0 * 192 * D, cnt, hm, plan_head(c->sw, D, cnt, c->fin_rows)))) return rc;
-                LAUNCH(c, VP_PROF_DECODE, 0.0, 4.0 * cnt * c->Kp * 3072.0 + 12.0 * cnt * c->Kp,
-                       vp::decode_launch(hm, d_wh ? d_wh + 2 * (size_t)s0 : nullptr, c->kp + (size_t)s0 * c->Kmax * 3, cnt, c->Kp, c->stream));
-            }
-        }
-        if ((rc = copy_out_sync(c, kp.data(), c->kp, (size_t)c->Kmax * 3, 0, nb))) return rc;   // the wait also keeps ids / wh (host vectors) alive until their uploads are done
-        // segment s's crops lie at [s0 Kmax + (j - s0) K_e] x 3 floats: back to the caller's order, joints beyond K_e = 0
-        for (size_t s = 0; s < seg_e.size(); ++s) {
-            const int K = c->ex_heads[seg_e[s]].K;
-            for (int j = seg_s[s]; j < seg_s[s + 1]; ++j) {
-                float* dst = out + (size_t)(off + p.order[j]) * c->Kmax * 3;
-                std::memcpy(dst, &kp[((size_t)seg_s[s] * c->Kmax + (size_t)(j - seg_s[s]) * K) * 3], (size_t)K * 12);
-                std::memset(dst + (size_t)K * 3, 0, (size_t)(c->Kmax - K) * 12);
-            }
-        }
-        return VP_OK;
+        // the sizes stay in the caller's order too: the record route reads the row it writes
+        if ((rc = stage_in(c, crops, fmt, org_wh, off, nb, src)) || (rc = run_mix_chunk(c, p, src, fmt, nb, org_wh ? c->wh_stage : nullptr, c->kp))) return rc;
+        return copy_out_sync(c, out, c->kp, (size_t)c->Kmax * 3, off, nb);
     });
-    use_expert(c, saved);
-    return rc;
 }
 
 int vp_infer_experts_device_stream(vp_handle c, const void* d_crops, int32_t fmt, int32_t n, const int32_t* expert_ids, const int32_t* d_org_wh, float* d_out,
                                    void* caller_stream) {
     int rc = check_ready(c, fmt, n, d_crops, d_out, false);
     if (rc || (rc = mix_ready(c, "vp_infer_experts_device_stream", n, expert_ids))) return rc;
-    const int saved = c->expert;
-    rc = caller_ordered(c, (hipStream_t)caller_stream, n, [&]() {
+    return caller_ordered(c, (hipStream_t)caller_stream, n, [&]() {
         return for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // vp_infer_experts' chunks: the same crops per chunk, so the same plan and bits
             MixPlan& p = c->mix_host;
             if (const int rc = mix_chunk_tables(c, expert_ids, off, nb, p)) return rc;
@@ -602,63 +542,49 @@ int vp_infer_experts_device_stream(vp_handle c, const void* d_crops, int32_t fmt
                                  d_out + (size_t)off * c->Kmax * 3);
         });
     });
-    use_expert(c, saved);
-    return rc;
+}
+
+// vp_infer_frames (mixed == false) and vp_infer_frames_experts (a flag, not a null test: null ids are an error of the latter)
+static int frames_impl(vp_ctx* c, const char* who, const vp_frame* frames, int32_t n_frames, int32_t on_device, const int32_t* p9, int32_t n, const int32_t* expert_ids,
+                       bool mixed, float* out) {
+    if (!c) return VP_ERR_INVALID;
+    std::vector<int32_t> bands((size_t)(n_frames > 0 ? n_frames : 0) * 2);
+    std::string why;
+    if (frame_plan(frames, n_frames, p9, n, bands.data(), &why)) return fail(c, VP_ERR_INVALID, why);   // before any copy or launch
+    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, p9, out);
+    if (rc || (mixed && (rc = mix_ready(c, who, n, expert_ids))) || n == 0) return rc;
+    std::vector<vp::CropRec> recs;
+    if ((rc = stage_frames(c, frames, n_frames, on_device != 0, p9, n, bands.data(), recs))) return rc;
+    if (!c->crecs && (rc = dalloc(c, &c->crecs, (size_t)c->maxb))) return rc;
+    std::vector<int32_t> wh((size_t)c->maxb * 2);
+    std::vector<vp::CropRec> sorted(mixed ? (size_t)c->maxb : 0);
+    return for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // vp_infer's chunks: the same crops per chunk, so the same (plan and) bits
+        MixPlan& p = c->mix_host;
+        const vp::CropRec* src = recs.data() + off;
+        if (mixed) {   // the tables first; the records go to their place in the expert order
+            if (const int rc = mix_chunk_tables(c, expert_ids, off, nb, p)) return rc;
+            for (int j = 0; j < nb; ++j) sorted[j] = recs[(size_t)off + p.order[j]];
+            src = sorted.data();
+        }
+        HIPCHK(c, hipMemcpyAsync(c->crecs, src, (size_t)nb * sizeof(vp::CropRec), hipMemcpyHostToDevice, c->stream));
+        LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5, vp::crop_resize_launch(c->crecs, (uint8_t*)c->in_stage, nb, c->stream));
+        // decode scales by the padded-canvas size (pw, ph) of each crop = the image pre_img receives; in the caller's order (the record route reads the row it writes)
+        for (int i = 0; i < nb; ++i) { wh[2 * i] = p9[9 * (size_t)(off + i) + 7]; wh[2 * i + 1] = p9[9 * (size_t)(off + i) + 8]; }
+        HIPCHK(c, hipMemcpyAsync(c->wh_stage, wh.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // recs / sorted / wh are rewritten for the next chunk
+        if (const int rc = mixed ? run_mix_chunk(c, p, c->in_stage, VP_INPUT_U8_NHWC, nb, c->wh_stage, c->kp) : run_chunk(c, c->in_stage, VP_INPUT_U8_NHWC, nb, c->wh_stage, c->kp))
+            return rc;
+        return copy_out_sync(c, out, c->kp, (size_t)(mixed ? c->Kmax : c->Kp) * 3, off, nb);
+    });
 }
 
 int vp_infer_frames_experts(vp_handle c, const vp_frame* frames, int32_t n_frames, int32_t on_device, const int32_t* p9, int32_t n, const int32_t* expert_ids,
                             float* out) {
-    if (!c) return VP_ERR_INVALID;
-    std::vector<int32_t> bands((size_t)(n_frames > 0 ? n_frames : 0) * 2);
-    std::string why;
-    if (frame_plan(frames, n_frames, p9, n, bands.data(), &why)) return fail(c, VP_ERR_INVALID, why);   // before any copy or launch
-    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, p9, out);
-    if (rc || (rc = mix_ready(c, "vp_infer_frames_experts", n, expert_ids)) || n == 0) return rc;
-    std::vector<vp::CropRec> recs;
-    if ((rc = stage_frames(c, frames, n_frames, on_device != 0, p9, n, bands.data(), recs))) return rc;
-    if (!c->crecs && (rc = dalloc(c, &c->crecs, (size_t)c->maxb))) return rc;
-    std::vector<int32_t> wh((size_t)c->maxb * 2);
-    std::vector<vp::CropRec> sorted((size_t)c->maxb);
-    const int saved = c->expert;
-    rc = for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // vp_infer_frames' staging per chunk; the records go to their place in the expert order
-        MixPlan& p = c->mix_host;
-        int rc = mix_chunk_tables(c, expert_ids, off, nb, p);
-        if (rc) return rc;
-        for (int j = 0; j < nb; ++j) sorted[j] = recs[(size_t)off + p.order[j]];
-        HIPCHK(c, hipMemcpyAsync(c->crecs, sorted.data(), (size_t)nb * sizeof(vp::CropRec), hipMemcpyHostToDevice, c->stream));
-        LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5, vp::crop_resize_launch(c->crecs, (uint8_t*)c->in_stage, nb, c->stream));
-        // the decode sizes stay in the caller's order: the record route reads the row it writes
-        for (int i = 0; i < nb; ++i) { wh[2 * i] = p9[9 * (size_t)(off + i) + 7]; wh[2 * i + 1] = p9[9 * (size_t)(off + i) + 8]; }
-        HIPCHK(c, hipMemcpyAsync(c->wh_stage, wh.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // sorted / wh are rewritten for the next chunk
-        if ((rc = run_mix_chunk(c, p, c->in_stage, VP_INPUT_U8_NHWC, nb, c->wh_stage, c->kp))) return rc;
-        return copy_out_sync(c, out, c->kp, (size_t)c->Kmax * 3, off, nb);
-    });
-    use_expert(c, saved);
-    return rc;
+    return frames_impl(c, "vp_infer_frames_experts", frames, n_frames, on_device, p9, n, expert_ids, true, out);
 }
 
 int vp_infer_frames(vp_handle c, const vp_frame* frames, int32_t n_frames, int32_t on_device, const int32_t* p9, int32_t n, float* out) {
-    if (!c) return VP_ERR_INVALID;
-    std::vector<int32_t> bands((size_t)(n_frames > 0 ? n_frames : 0) * 2);
-    std::string why;
-    if (frame_plan(frames, n_frames, p9, n, bands.data(), &why)) return fail(c, VP_ERR_INVALID, why);   // before any copy or launch
-    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, p9, out);
-    if (rc || n == 0) return rc;
-    std::vector<vp::CropRec> recs;
-    if ((rc = stage_frames(c, frames, n_frames, on_device != 0, p9, n, bands.data(), recs))) return rc;
-    if (!c->crecs && (rc = dalloc(c, &c->crecs, (size_t)c->maxb))) return rc;
-    std::vector<int32_t> wh((size_t)c->maxb * 2);
-    return for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // vp_infer's chunks: the same crops per chunk, so the same bits
-        HIPCHK(c, hipMemcpyAsync(c->crecs, recs.data() + off, (size_t)nb * sizeof(vp::CropRec), hipMemcpyHostToDevice, c->stream));
-        LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5, vp::crop_resize_launch(c->crecs, (uint8_t*)c->in_stage, nb, c->stream));
-        // decode scales by the padded-canvas size (pw, ph) of each crop = the image pre_img receives
-        for (int i = 0; i < nb; ++i) { wh[2 * i] = p9[9 * (size_t)(off + i) + 7]; wh[2 * i + 1] = p9[9 * (size_t)(off + i) + 8]; }
-        HIPCHK(c, hipMemcpyAsync(c->wh_stage, wh.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // recs / wh are rewritten for the next chunk
-        if (const int rc = run_chunk(c, c->in_stage, VP_INPUT_U8_NHWC, nb, c->wh_stage, c->kp)) return rc;
-        return copy_out_sync(c, out, c->kp, (size_t)c->Kp * 3, off, nb);
-    });
+    return frames_impl(c, "vp_infer_frames", frames, n_frames, on_device, p9, n, nullptr, false, out);
 }
 
 // the one-frame case of vp_infer_frames
@@ -699,8 +625,7 @@ static int boxes_impl(vp_ctx* c, const char* who, const vp_frame* frames, int32_
     // the chunk's crop records / decode sizes / offsets live in handle buffers sized by max_batch, allocated on the first call
     if (!c->crecs && (rc = dalloc(c, &c->crecs, (size_t)c->maxb))) return rc;
     if (!c->box_aux && (rc = dalloc(c, &c->box_aux, (size_t)c->maxb * 4))) return rc;
-    const int saved = c->expert;
-    rc = caller_ordered(c, (hipStream_t)caller_stream, n, [&]() {
+    return caller_ordered(c, (hipStream_t)caller_stream, n, [&]() {
         return for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // vp_infer_frames' chunks: the same crops per chunk, so the same plan and bits
             MixPlan& p = c->mix_host;
             if (mixed)   // the tables first: the box kernel writes each crop record to its place in the expert order (sizes, offsets, params and status stay in the caller's)
@@ -722,8 +647,6 @@ static int boxes_impl(vp_ctx* c, const char* who, const vp_frame* frames, int32_
             return run_chunk(c, c->in_stage, VP_INPUT_U8_NHWC, nb, c->wh_stage, d_out + (size_t)off * c->Kp * 3, c->box_aux);
         });
     });
-    if (mixed) use_expert(c, saved);
-    return rc;
 }
 
 int vp_infer_boxes_stream(vp_handle c, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx,
@@ -761,42 +684,42 @@ int vp_dbg_box_geometry(const float* xyxy, int32_t row_stride, const int32_t* fr
     return VP_OK;
 }
 
-// decode of host heatmaps on device `device_id`: partner == null: [n, k, 64, 48] as they are; else the interleaved [2 n, k, 64, 48] of the flip-test mode
-static int decode_host(int32_t device_id, const float* heatmaps, int32_t n, int32_t k, const int32_t* partner, int32_t shift, const int32_t* org_wh, float* out) {
+// One decode launch on host data, on device `device_id`: the scratch, the uploads, the launch, the download (into NaN: every value must be written), the frees.
+// records != null: n_maps maps by records into [n, k] rows;  partner != null: the interleaved [n_maps = 2 n, k, 64, 48] of the flip-test mode;  neither: [n, k, 64, 48]
+static int decode_host(const char* who, int32_t device_id, const float* heatmaps, size_t n_maps, int32_t n, int32_t k, const int32_t* partner, int32_t shift,
+                       const int32_t* records, const int32_t* org_wh, float* out) {
     if (!heatmaps || !out || n <= 0 || k <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, VP_ERR_HIP, "no HIP device available (no CPU fallback)");
     if (device_id < 0 || device_id >= ndev) return fail(nullptr, VP_ERR_INVALID, "device_id out of range");
     vp_ctx* c = nullptr;   // errors below are reported through the create-error slot
     HIPCHK(c, hipSetDevice(device_id));
-    float *d_hm = nullptr, *d_out = nullptr;
-    int32_t *d_wh = nullptr, *d_partner = nullptr;
-    const size_t hb = (size_t)n * k * 3072 * 4 * (partner ? 2 : 1), ob = (size_t)n * k * 12;
-    int rc = VP_OK;
-    hipError_t e = hipMalloc((void**)&d_hm, hb);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, ob);
-    if (e == hipSuccess) e = hipMemcpy(d_hm, heatmaps, hb, hipMemcpyHostToDevice);
-    if (e == hipSuccess && org_wh) {
-        e = hipMalloc((void**)&d_wh, (size_t)n * 8);
-        if (e == hipSuccess) e = hipMemcpy(d_wh, org_wh, (size_t)n * 8, hipMemcpyHostToDevice);
+    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the maps, the sizes, the partner table, the records (each where given), the output
+    const void* h[4] = {heatmaps, org_wh, partner, records};
+    const size_t bytes[5] = {n_maps * 3072 * 4, (size_t)n * 8, (size_t)k * 4, (size_t)n * sizeof(vp::MixRec), (size_t)n * k * 12};
+    hipError_t e = hipMalloc(&d[4], bytes[4]);
+    if (e == hipSuccess) e = hipMemset(d[4], 0xff, bytes[4]);
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) {
+        if (!h[i]) continue;
+        e = hipMalloc(&d[i], bytes[i]);
+        if (e == hipSuccess) e = hipMemcpy(d[i], h[i], bytes[i], hipMemcpyHostToDevice);
     }
-    if (e == hipSuccess && partner) {
-        e = hipMalloc((void**)&d_partner, (size_t)k * 4);
-        if (e == hipSuccess) e = hipMemcpy(d_partner, partner, (size_t)k * 4, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = partner ? vp::decode_flip_launch(d_hm, d_partner, shift ? 1 : 0, d_wh, d_out, n, k, nullptr) : vp::decode_launch(d_hm, d_wh, d_out, n, k, nullptr);
+    const float* d_hm = (const float*)d[0];
+    const int32_t* d_wh = (const int32_t*)d[1];
+    if (e == hipSuccess)
+        e = records   ? vp::decode_mix_launch(d_hm, (const vp::MixRec*)d[3], d_wh, (float*)d[4], n, k, nullptr)
+            : partner ? vp::decode_flip_launch(d_hm, (const int32_t*)d[2], shift ? 1 : 0, d_wh, (float*)d[4], n, k, nullptr)
+                      : vp::decode_launch(d_hm, d_wh, (float*)d[4], n, k, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(nullptr, VP_ERR_HIP, std::string(partner ? "vp_dbg_decode_flip: " : "vp_decode_only: ") + hipGetErrorString(e));
-    if (d_hm) hipFree(d_hm);
-    if (d_out) hipFree(d_out);
-    if (d_wh) hipFree(d_wh);
-    if (d_partner) hipFree(d_partner);
+    if (e == hipSuccess) e = hipMemcpy(out, d[4], bytes[4], hipMemcpyDeviceToHost);
+    const int rc = e == hipSuccess ? (int)VP_OK : fail(nullptr, VP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    for (void* q : d)
+        if (q) hipFree(q);
     return rc;
 }
 
 int vp_decode_only(int32_t device_id, const float* heatmaps, int32_t n, int32_t k, const int32_t* org_wh, float* out) {
-    return decode_host(device_id, heatmaps, n, k, nullptr, 0, org_wh, out);
+    return decode_host("vp_decode_only", device_id, heatmaps, (size_t)n * k, n, k, nullptr, 0, nullptr, org_wh, out);
 }
 
 int vp_dbg_decode_flip(int32_t device_id, const float* heatmaps2, int32_t n, int32_t k, const int32_t* flip_pairs, int32_t n_pairs, int32_t shift_heatmap,
@@ -805,7 +728,7 @@ int vp_dbg_decode_flip(int32_t device_id, const float* heatmaps2, int32_t n, int
     std::vector<int32_t> partner((size_t)k);
     std::string why;
     if (flip_partner_table(k, flip_pairs, n_pairs, partner.data(), &why)) return fail(nullptr, VP_ERR_INVALID, why);
-    return decode_host(device_id, heatmaps2, n, k, partner.data(), shift_heatmap, org_wh, out);
+    return decode_host("vp_dbg_decode_flip", device_id, heatmaps2, (size_t)n * k * 2, n, k, partner.data(), shift_heatmap, nullptr, org_wh, out);
 }
 
 int vp_dbg_mix_plan(const int32_t* expert_ids, int32_t n, int32_t n_experts, int32_t max_batch, const int32_t* k_per_expert, int32_t* order, int32_t* ids_padded,
@@ -847,35 +770,7 @@ int vp_dbg_decode_mix(int32_t device_id, const float* heatmaps, int32_t n_maps, 
         if (r[0] < 0 || r[1] <= 0 || r[1] > kmax || (int64_t)r[0] + r[1] > n_maps || r[2] < 0 || r[2] >= n || seen[r[2]]++)
             return fail(nullptr, VP_ERR_INVALID, "record " + std::to_string(j) + " lies outside the maps or the output, or repeats a row");
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, VP_ERR_HIP, "no HIP device available (no CPU fallback)");
-    if (device_id < 0 || device_id >= ndev) return fail(nullptr, VP_ERR_INVALID, "device_id out of range");
-    vp_ctx* c = nullptr;
-    HIPCHK(c, hipSetDevice(device_id));
-    float *d_hm = nullptr, *d_out = nullptr;
-    int32_t* d_wh = nullptr;
-    vp::MixRec* d_rec = nullptr;
-    const size_t hb = (size_t)n_maps * 3072 * 4, ob = (size_t)n * kmax * 12;
-    hipError_t e = hipMalloc((void**)&d_hm, hb);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, ob);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_rec, (size_t)n * sizeof(vp::MixRec));
-    if (e == hipSuccess) e = hipMemcpy(d_hm, heatmaps, hb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_rec, records, (size_t)n * sizeof(vp::MixRec), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_out, 0xff, ob);   // NaN: every value of the output must be written
-    if (e == hipSuccess && org_wh) {
-        e = hipMalloc((void**)&d_wh, (size_t)n * 8);
-        if (e == hipSuccess) e = hipMemcpy(d_wh, org_wh, (size_t)n * 8, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = vp::decode_mix_launch(d_hm, d_rec, d_wh, d_out, n, kmax, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost);
-    int rc = VP_OK;
-    if (e != hipSuccess) rc = fail(nullptr, VP_ERR_HIP, std::string("vp_dbg_decode_mix: ") + hipGetErrorString(e));
-    if (d_hm) hipFree(d_hm);
-    if (d_out) hipFree(d_out);
-    if (d_rec) hipFree(d_rec);
-    if (d_wh) hipFree(d_wh);
-    return rc;
+    return decode_host("vp_dbg_decode_mix", device_id, heatmaps, (size_t)n_maps, n, kmax, nullptr, 0, records, org_wh, out);
 }
 
 }  // extern "C"

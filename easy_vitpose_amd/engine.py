@@ -137,15 +137,13 @@ class VitPoseHip:
     def infer_mixed(self, crops: np.ndarray, datasets, org_wh=None):
         """One call, a dataset per crop (vp_infer_experts): returns ``(out, k)`` -- ``out`` float32 [N, Kmax, 3] where crop i fills
         its first ``k[i]`` joints (the rest are 0), ``k`` int32 [N].  `datasets`: names or expert indices."""
-        names = [d for d, _ in self.experts]
-        ids = np.ascontiguousarray([names.index(d) if isinstance(d, str) and d in names else (d if not isinstance(d, str) else -1)
-                                    for d in datasets], dtype=np.int32)
         crops = np.ascontiguousarray(crops)
         fmt = self._fmt(crops)
         n = crops.shape[0]
-        assert len(ids) == n, 'one dataset per crop'
-        Kmax = getattr(self, 'Kmax', self.K)
-        out = np.empty((n, Kmax, 3), dtype=np.float32)
+        datasets = list(datasets)
+        assert len(datasets) == n, 'one dataset per crop'
+        ids = self._dataset_ids(datasets, n)
+        out = np.empty((n, self.Kmax, 3), dtype=np.float32)
         wh = None if org_wh is None else np.ascontiguousarray(org_wh, dtype=np.int32).reshape(n, 2)
         if n:
             capi.check(self.lib.vp_infer_experts(self._h, crops.ctypes.data, fmt, n, ids.ctypes.data,

@@ -306,7 +306,8 @@ VP_API int vp_expert_info(vp_handle h, int32_t* n_experts, int32_t* part_feature
 VP_API int vp_set_expert(vp_handle h, int32_t e);
 /* One call, one encoder pass, a different expert per crop: expert_ids[i] in [0, E).  out = float32 [n, Kmax, 3] (Kmax = the largest K_e of the
  * checkpoint): crop i fills its first K_{e_i} joints, the rest are written as 0.  The crops are ordered by expert inside the call (mlp.fc2 of all
- * experts in one launch per layer, one head + decode per expert present); crop i's result equals vp_set_expert(e_i) + vp_infer on that crop under
+ * experts in one launch per layer, one head per expert present, ONE decode launch for the chunk; chunks of up to VP_GRAPH crops are replayed from a
+ * hipGraph keyed on the count per expert, as for its twins below); crop i's result equals vp_set_expert(e_i) + vp_infer on that crop under
  * the one-launch family (VP_SPLITK=0).  VP_ERR_STATE on a plain handle. */
 VP_API int vp_infer_experts(vp_handle h, const void* crops, int32_t input_format, int32_t n, const int32_t* expert_ids,
                             const int32_t* org_wh, float* out);

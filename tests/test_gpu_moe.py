@@ -179,7 +179,9 @@ def test_graph_replay_never_crosses_expert_patterns(one_launch_family, n):
     C = np.full(n, 5, np.int32)                                # single expert (wholebody): same (n, buffers), another graph
     B = np.array([0, 5, 3, 5, 1, 2, 4, 0][:n], np.int32)       # mixed
     eng = expert_handle('s', 'fp16', 16)
-    seq = [A, A, C, C, C, B, B, B, A, C, A]
+    # B: eager, captured, replayed.  Its reverse holds the same counts in another permutation: B's graph with new tables, twice, then B's own again.
+    # np.sort(B) holds them in expert order already: no gather, the crops staged where the forward reads them -- another source, another graph
+    seq = [A, A, C, C, C, B, B, B, B[::-1].copy(), B[::-1].copy(), B, np.sort(B), np.sort(B), B, A, C, A]
     res = [eng.infer_mixed(crops, ids)[0] for ids in seq]
     eng.close()
     ref = {}

@@ -2,7 +2,11 @@
 vp_infer_frames_experts (infer_frames(datasets=)) and vp_infer_boxes_experts_stream (infer_boxes(datasets=)).  Every comparison is bit for bit, fp16:
 against infer_mixed on the same crops, ids and max_batch (same chunks, same plan), across eager run, graph capture and replay, on three streams; a new
 permutation under a captured graph; the fused decode's record route alone against vp_decode_only; datasets=None against the plain entries; refusals;
-and the reference's keypoints within the suite's tolerance.  The plan itself is pinned on the CPU (tests/test_mix_plan_host.py)."""
+and the reference's keypoints within the suite's tolerance.  The plan itself is pinned on the CPU (tests/test_mix_plan_host.py).
+
+vp_infer_experts (infer_mixed) is the host-staged caller of the same chunk body as these entries, so "entry == infer_mixed" compares one body under two
+stagings.  The anchor of every per-crop entry is tests/test_gpu_moe.py's comparison of infer_mixed with the six split handles (and, for the device-stream
+entry directly, test_device_stream_entry_is_bit_identical_to_split_handles below)."""
 from __future__ import annotations
 
 import os
@@ -15,7 +19,7 @@ from easy_vitpose_amd.cropprep import frames_crop_params
 from easy_vitpose_amd.engine import PinnedArray, decode_heatmaps
 from easy_vitpose_amd.moe import DATASETS, NUM_KEYPOINTS
 from helpers import CONF_TOL, KP_TOL_PX
-from test_gpu_moe import expert_handle, patterns, pool, split_handle
+from test_gpu_moe import check_mixed, expert_handle, patterns, pool, split_handle
 
 pytestmark = pytest.mark.gpu
 KMAX = max(NUM_KEYPOINTS)
@@ -67,6 +71,32 @@ def test_device_stream_entry_equals_infer_mixed(variant, sizes, max_batch):
                     assert np.array_equal(got, want), f'{variant} n={n} {name} stream={sname} call {rep}: {(got != want).sum()} differing values'
             assert np.array_equal(ks, eng.dataset_k(ids))
     eng.close()
+
+
+def test_device_stream_entry_is_bit_identical_to_split_handles(one_launch_family):
+    """the device-stream entry against the split model's six handles, not against its host-staged twin: 3 and 13 crops (one mixed chunk), 37 (two full
+    chunks of 16 and a ragged 5) at max_batch 16, every pattern, three calls each on torch's default stream (eager, capture, replay)"""
+    torch = _torch()
+    crops = pool()
+    rng = np.random.default_rng(11)
+    eng = expert_handle('s', 'fp16', 16)
+    results = []
+    for n in (3, 13, 37):
+        d_out = torch.empty((n, KMAX, 3), device='cuda')
+        for name, ids in patterns(n):
+            idx = rng.choice(len(crops), size=n, replace=False)
+            d_crops = torch.from_numpy(crops[idx]).cuda()
+            ks = eng.dataset_k(ids)
+            results += [(n, name, rep, ids, idx, run_device(eng, d_crops, ids, d_out, None), ks) for rep in range(3)]
+    eng.close()
+    ref = {}
+    for e, ds in enumerate(DATASETS):
+        h = split_handle('s', ds, 'fp16', 16)
+        ref[e] = h.infer(crops)
+        h.close()
+    for n, name, rep, ids, idx, out, ks in results:
+        assert out.shape == (n, KMAX, 3), (n, name, rep)
+        check_mixed(out, ks, ids, idx, ref)
 
 
 # ---- 2. same counts, another permutation: the captured graph with new tables ------------------------------------------------------------
