@@ -32,7 +32,8 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_dbg_chunk_plan', 'vp_infer_boxes_stream', 'vp_dbg_box_geometry',
            'vp_set_flip_test', 'vp_clear_flip_test', 'vp_flip_test_enabled', 'vp_group_set_flip_test', 'vp_group_clear_flip_test',
            'vp_dbg_flip_partner', 'vp_dbg_flip_layout', 'vp_dbg_decode_flip',
-           'vp_infer_experts_device_stream', 'vp_infer_frames_experts', 'vp_infer_boxes_experts_stream', 'vp_dbg_mix_plan', 'vp_dbg_decode_mix']
+           'vp_infer_experts_device_stream', 'vp_infer_frames_experts', 'vp_infer_boxes_experts_stream', 'vp_dbg_mix_plan', 'vp_dbg_decode_mix',
+           'vp_set_flip_test_experts', 'vp_dbg_mix_plan_flip', 'vp_dbg_decode_flip_mix']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -170,6 +171,9 @@ def load_library():
     lib.vp_flip_test_enabled.argtypes = [H]
     lib.vp_group_set_flip_test.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32]
     lib.vp_group_clear_flip_test.argtypes = [H]
+    lib.vp_set_flip_test_experts.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.vp_dbg_mix_plan_flip.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    lib.vp_dbg_decode_flip_mix.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.vp_dbg_flip_partner.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.vp_dbg_flip_layout.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.vp_dbg_decode_flip.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]

@@ -133,6 +133,11 @@ struct vp_ctx {
     uint32_t flip_gen = 0, flip_counter = 0;
     int32_t* flip_table = nullptr;    // device [Kmax]
     std::vector<int32_t> flip_pairs;  // the pairs as given (a group compares its members' modes)
+    // ... with one table per expert (vp_set_flip_test_experts, a ViTPose+ handle): flip_ex on top of flip_on, flip_tables = device [n_experts, Kmax], row e validated
+    // against expert e's K (identity beyond it).  Every entry of the single-table mode reads the active expert's row (flip_table_now), vp_set_expert keeps the mode,
+    // and the per-crop expert entries run under it: mix_chunk_body doubles the rows of the chunk's plan, the decode reads row e of each crop's record
+    bool flip_ex = false;
+    int32_t* flip_tables = nullptr;
     float *ln_part = nullptr, *rowstat = nullptr;   // partial row statistics [M][D/64][2], (mean, rstd) [M][2]
     // fp8 mode (vp_config.dtype = VP_DTYPE_FP8; csrc/mx8.h, gemm8f.hip, quant8.hip): qkv / fc1 / fc2 on MXFP8 operands.  Token rows are
     // padded to Mp (a multiple of the 256-row GEMM tile, >= 512); x8 / xs8 = LayerNorm(x) as MXFP8 codes / scales, hs8 = block scales of
@@ -214,6 +219,7 @@ struct vp_ctx {
     std::vector<int> mix_bounds;           // ... on tiles that never span two experts: the crop index of every expert change
     int32_t* mix_slot = nullptr;
     vp::MixRec* mix_recs = nullptr;
+    vp::MixRecFlip* mix_recs_flip = nullptr;   // the decode's records under the per-expert flip-test mode (allocated by vp_set_flip_test_experts)
     const vpi::MixPlan* mix = nullptr;
     vpi::MixPlan mix_host;                         // the plan of the current chunk and the scratch of its tables: host memory that lives with the handle
     std::vector<int32_t> mix_ks, mix_first, mix_k;
@@ -291,6 +297,8 @@ void use_expert(vp_ctx* c, int e);   // make expert e of a ViTPose+ handle the a
 // ---- handle.hip
 // flip-test mode (HOST ONLY): partner[k] = the mirror joint of k among K joints (k itself when unpaired) from n_pairs x 2 indices; VP_OK or VP_ERR_INVALID with the reason in *why
 int flip_partner_table(int K, const int32_t* pairs, int n_pairs, int32_t* partner, std::string* why);
+// the partner table the flip-test mode reads now: the handle's one table, or the active expert's row of the per-expert tables
+inline const int32_t* flip_table_now(const vp_ctx* c) { return c->flip_ex ? c->flip_tables + (size_t)c->expert * c->Kmax : c->flip_table; }
 bool prof_begin(vp_ctx* c, int fam, double flops, double bytes);
 void prof_end(vp_ctx* c, bool on);
 void prof_collect(vp_ctx* c);
@@ -318,6 +326,9 @@ int mix_check_ids(const int32_t* ids, int n, int n_experts, std::string* why);
 void mix_plan(const int32_t* ids, int nb, int n_experts, MixPlan& p);
 uint64_t mix_pattern(const std::vector<int>& seg_e, const std::vector<int>& seg_s, int n_experts);
 void mix_records(const MixPlan& p, const int32_t* k_per_expert, int Kmax, int32_t* first, int32_t* K);
+// ... under the per-expert flip-test mode: position j is forward rows 2 j (the crop) and 2 j + 1 (its mirror), the head of segment s writes [2 cnt, K_e, 64, 48] from map
+// 2 seg_s[s] * Kmax on, so first = 2 seg_s[s] * Kmax + 2 (j - seg_s[s]) * K_e (the mirror's maps start K_e behind)
+void mix_records_flip(const MixPlan& p, const int32_t* k_per_expert, int Kmax, int32_t* first, int32_t* K);
 // vp_infer_submit; stage_out (the group path): the download lands in the slot's pinned buffer and vp_infer_wait copies it to `out`
 int submit_impl(vp_ctx* c, const void* crops, int32_t fmt, int32_t n, const int32_t* org_wh, float* out, int32_t* slot_out, bool stage_out);
 

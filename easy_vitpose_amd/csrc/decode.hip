@@ -38,6 +38,10 @@ struct GaussK { float w[11]; };
 // record -- where its maps start, how many joints its expert has, which row of the caller's order it is.  Blocks k < K_e run the code below on exactly the values the
 // plain kernel sees for that crop as a [1, K_e, 64, 48] batch (the record only replaces the three index expressions n K + k, n and blockIdx.x), so the bits are the plain
 // kernel's; blocks k >= K_e write the zeros of the padded row.  FLIP and MIX are compile-time: decode_kernel<false, false> keeps the instruction stream it had.
+//
+// FLIP and MIX (the per-expert flip-test mode, decode_flip_mix_launch): `recs` holds MixRecFlip records, `partner` the [n_experts, Kmax] table.  The crop's K_e maps
+// start at `first`, its mirror's at first + K_e (a [2, K_e, 64, 48] pair), and the mirror is read through row e of the table: the FLIP body on the values it sees
+// for that pair under expert e's table, so the bits are decode_kernel<true, false>'s.  The three other instantiations keep their instruction streams.
 template <bool FLIP, bool MIX>
 __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ hm, const int32_t* __restrict__ org_wh,
                                                      float* __restrict__ out, int K, GaussK gk, const int32_t* __restrict__ partner, int shift,
@@ -49,7 +53,18 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = blockIdx.x / K, k = blockIdx.x % K;
     int first = 0, row = n;   // MIX: the crop's first map, and its row in org_wh / out
-    if (MIX) {
+    if (MIX && FLIP) {
+        const MixRecFlip r = ((const MixRecFlip*)recs)[n];
+        row = r.dst;
+        if (k >= r.K) {
+            if (tid < 3) out[((size_t)row * K + k) * 3 + tid] = 0.f;
+            return;
+        }
+        out += ((size_t)row * K + k) * 3;
+        partner += (size_t)r.e * K;   // the expert's row of the [n_experts, Kmax] table
+        first = r.first;
+        K = r.K;
+    } else if (MIX) {
         const MixRec r = recs[n];
         row = r.dst;
         if (k >= r.K) {   // a joint this crop's expert does not have (the whole block leaves: no barrier was reached yet)
@@ -61,7 +76,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
         K = r.K;
     }
     const float* map = hm + (MIX ? (size_t)first + k : FLIP ? (size_t)2 * n * K + k : (size_t)blockIdx.x) * HW;
-    const float* mir = FLIP ? hm + ((size_t)(2 * n + 1) * K + partner[k]) * HW : nullptr;
+    const float* mir = FLIP ? hm + (MIX ? (size_t)first + K + partner[k] : (size_t)(2 * n + 1) * K + partner[k]) * HW : nullptr;
 
     // ---- arg-max / max over 3072 values, first index on ties (_get_max_preds, :82-114)
     float best = -INFINITY;
@@ -117,7 +132,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
         px = min(max(px, 0), WW - 1);
         const int ry = reflect101(py + ty - 5, HH) * WW;
         const float* src = hm + (MIX ? (size_t)first + kk : (size_t)(FLIP ? 2 * n : n) * K + kk) * HW + ry;
-        const float* msrc = FLIP ? hm + ((size_t)(2 * n + 1) * K + partner[kk]) * HW + ry : nullptr;   // the neighbour map the samples wrap into, and ITS partner
+        const float* msrc = FLIP ? hm + (MIX ? (size_t)first + K + partner[kk] : (size_t)(2 * n + 1) * K + partner[kk]) * HW + ry : nullptr;   // the neighbour map the samples wrap into, and ITS partner
         float acc = 0.f;
 #pragma unroll
         for (int tx = 0; tx < 11; ++tx) {
@@ -189,6 +204,13 @@ hipError_t decode_flip_launch(const float* hm, const int32_t* partner, int shift
 hipError_t decode_mix_launch(const float* hm, const MixRec* recs, const int32_t* org_wh, float* out, int N, int Kmax, hipStream_t s) {
     if (!recs) return hipErrorInvalidValue;
     hipLaunchKernelGGL((decode_kernel<false, true>), dim3(N * Kmax), dim3(256), 0, s, hm, org_wh, out, Kmax, gauss11(), (const int32_t*)nullptr, 0, recs);
+    return hipGetLastError();
+}
+
+hipError_t decode_flip_mix_launch(const float* hm, const MixRecFlip* recs, const int32_t* partners, int shift, const int32_t* org_wh, float* out, int N, int Kmax,
+                                  hipStream_t s) {
+    if (!recs || !partners) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((decode_kernel<true, true>), dim3(N * Kmax), dim3(256), 0, s, hm, org_wh, out, Kmax, gauss11(), partners, shift, (const MixRec*)recs);
     return hipGetLastError();
 }
 

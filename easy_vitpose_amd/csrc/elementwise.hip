@@ -235,25 +235,40 @@ hipError_t gather_crops_launch(const void* src, void* dst, const int32_t* idx, i
 
 // ViTPose+ chunk with per-crop experts: the call's tables from the kernel argument into the handle's device buffers (kernels.h MixTable).  One thread owns
 // every value it writes; the launches of a chunk write disjoint positions, so the order among them does not matter.
+// TWIN (the per-expert flip-test mode, mix_tables_flip_launch): position j is forward rows 2 j and 2 j + 1 -- the ids are written per ROW (pad_to counts rows), the
+// decode's four-field record goes to recs_flip, everything else stays per crop.
+template <bool TWIN>
 __global__ __launch_bounds__(MIX_CROPS_PER_LAUNCH) void mix_tables_kernel(MixTable t, int32_t* __restrict__ ids, int32_t* __restrict__ order,
-                                                                        int32_t* __restrict__ slot, MixRec* __restrict__ recs) {
+                                                                        int32_t* __restrict__ slot, MixRec* __restrict__ recs, MixRecFlip* __restrict__ recs_flip) {
     const int i = threadIdx.x;
     if (i < t.count) {
         const int j = t.base + i;
-        ids[j] = t.id[i];
+        if (TWIN) { ids[2 * j] = t.id[i]; ids[2 * j + 1] = t.id[i]; }
+        else ids[j] = t.id[i];
         order[j] = t.order[i];
         slot[t.order[i]] = j;
         MixRec r;
         r.first = t.first[i]; r.K = t.K[i]; r.dst = t.order[i];
         recs[j] = r;
+        if (TWIN) {
+            MixRecFlip f;
+            f.first = t.first[i]; f.K = t.K[i]; f.dst = t.order[i]; f.e = t.id[i];
+            recs_flip[j] = f;
+        }
     }
     if (t.count > 0)
-        for (int j = t.base + t.count + i; j < t.pad_to; j += MIX_CROPS_PER_LAUNCH) ids[j] = t.id[t.count - 1];
+        for (int j = (TWIN ? 2 : 1) * (t.base + t.count) + i; j < t.pad_to; j += MIX_CROPS_PER_LAUNCH) ids[j] = t.id[t.count - 1];
 }
 
 hipError_t mix_tables_launch(const MixTable& t, int32_t* ids, int32_t* order, int32_t* slot, MixRec* recs, hipStream_t s) {
     if (t.count < 0 || t.count > MIX_CROPS_PER_LAUNCH || t.base < 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mix_tables_kernel, dim3(1), dim3(MIX_CROPS_PER_LAUNCH), 0, s, t, ids, order, slot, recs);
+    hipLaunchKernelGGL(mix_tables_kernel<false>, dim3(1), dim3(MIX_CROPS_PER_LAUNCH), 0, s, t, ids, order, slot, recs, (MixRecFlip*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t mix_tables_flip_launch(const MixTable& t, int32_t* ids, int32_t* order, int32_t* slot, MixRec* recs, MixRecFlip* recs_flip, hipStream_t s) {
+    if (t.count < 0 || t.count > MIX_CROPS_PER_LAUNCH || t.base < 0 || !recs_flip) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mix_tables_kernel<true>, dim3(1), dim3(MIX_CROPS_PER_LAUNCH), 0, s, t, ids, order, slot, recs, recs_flip);
     return hipGetLastError();
 }
 

@@ -254,7 +254,7 @@ int head_chunk(vp_ctx* c, const uint16_t* y, int nh, float* hm, const HeadPlan& 
 int decode_chunk(vp_ctx* c, const int32_t* d_wh, float* d_out, int n, bool twin) {
     if (twin)
         LAUNCH(c, VP_PROF_DECODE, 0.0, 8.0 * n * c->Kp * 3072.0 + 12.0 * n * c->Kp,
-               vp::decode_flip_launch(c->hm, c->flip_table, c->flip_shift, d_wh, d_out, n, c->Kp, c->stream));
+               vp::decode_flip_launch(c->hm, flip_table_now(c), c->flip_shift, d_wh, d_out, n, c->Kp, c->stream));
     else
         LAUNCH(c, VP_PROF_DECODE, 0.0, 4.0 * n * c->Kp * 3072.0 + 12.0 * n * c->Kp,
                vp::decode_launch(c->hm, d_wh, d_out, n, c->Kp, c->stream));
@@ -287,13 +287,17 @@ static int offsets_chunk(vp_ctx* c, const int32_t* aux, float* d_out, int n) {
 // caller's order: one gather; frames and boxes were cropped straight into it), the encoder once with every expert's mlp.fc2 in one launch per layer on tiles that never span two
 // experts, one head per expert present on its segment's rows.  One expert: the plain forward under that expert.  Then ONE decode launch by records into rows of
 // Kmax joints in the caller's order, and the frame offsets on those rows.  The only writer of c->mix_expert / c->mix_bounds.
+// Under the per-expert flip-test mode (c->flip_ex; tw = 2): the twin patch gather on the ordered crops puts position j at rows 2 j (the crop) and 2 j + 1 (its mirror),
+// so the encoder runs 2 n rows with doubled bounds -- every expert change at an even row -- each head its segment's 2 cnt rows, writing at 2 s0 * Kmax maps, and the
+// decode averages a crop's two maps of a joint under its expert's table (mix_recs_flip).  One expert: that expert's plain forward under the mode.
 static int mix_chunk_body(vp_ctx* c, const GraphKey& k) {
     const MixPlan& m = *c->mix;
     const int nseg = (int)m.seg_e.size(), D = c->D;
+    const int tw = c->flip_ex ? 2 : 1;
     int rc;
     if (nseg == 1) {
         use_expert(c, m.seg_e[0]);
-        if ((rc = forward_chunk(c, k.src, k.fmt, k.n))) return rc;
+        if ((rc = forward_mode_chunk(c, k.src, k.fmt, k.n))) return rc;
     } else {
         const void* src = k.src;
         if (src != c->in_stage) {
@@ -303,20 +307,26 @@ static int mix_chunk_body(vp_ctx* c, const GraphKey& k) {
         }
         FwdOpts encoder_only;
         encoder_only.head = false;
+        if (tw == 2) encoder_only.twin_src = k.n;
         c->mix_expert = c->expert_ids;
-        c->mix_bounds.assign(m.seg_s.begin() + 1, m.seg_s.end() - 1);
-        rc = forward_chunk(c, src, k.fmt, k.n, encoder_only);
+        c->mix_bounds.clear();
+        for (int s = 1; s < nseg; ++s) c->mix_bounds.push_back(tw * m.seg_s[s]);
+        rc = forward_chunk(c, src, k.fmt, tw * k.n, encoder_only);
         c->mix_expert = nullptr;
         c->mix_bounds.clear();
         if (rc) return rc;
         for (int s = 0; s < nseg; ++s) {
-            const int s0 = m.seg_s[s], cnt = m.seg_s[s + 1] - s0;
+            const int s0 = tw * m.seg_s[s], cnt = tw * (m.seg_s[s + 1] - m.seg_s[s]);
             use_expert(c, m.seg_e[s]);
             if ((rc = head_chunk(c, c->y + (size_t)s0 * 192 * D, cnt, c->hm + (size_t)s0 * c->Kmax * 3072, plan_head(c->sw, D, cnt, c->fin_rows)))) return rc;
         }
     }
-    LAUNCH(c, VP_PROF_DECODE, 0.0, 4.0 * k.n * c->Kmax * 3072.0 + 12.0 * k.n * c->Kmax,
-           vp::decode_mix_launch(c->hm, c->mix_recs, k.wh, k.out, k.n, c->Kmax, c->stream));
+    if (tw == 2)
+        LAUNCH(c, VP_PROF_DECODE, 0.0, 8.0 * k.n * c->Kmax * 3072.0 + 12.0 * k.n * c->Kmax,
+               vp::decode_flip_mix_launch(c->hm, c->mix_recs_flip, c->flip_tables, c->flip_shift, k.wh, k.out, k.n, c->Kmax, c->stream));
+    else
+        LAUNCH(c, VP_PROF_DECODE, 0.0, 4.0 * k.n * c->Kmax * 3072.0 + 12.0 * k.n * c->Kmax,
+               vp::decode_mix_launch(c->hm, c->mix_recs, k.wh, k.out, k.n, c->Kmax, c->stream));
     if (k.post) LAUNCH(c, VP_PROF_DECODE, 0.0, 24.0 * k.n * c->Kmax + 16.0 * k.n, vp::box_offsets_launch(k.post, k.out, k.n, c->Kmax, c->stream, c->mix_slot, c->mix_recs));
     return VP_OK;
 }
@@ -386,7 +396,7 @@ int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh
     if (nb > chunk_cap(c)) return fail(c, VP_ERR_INVALID, "a chunk of " + std::to_string(nb) + " crops exceeds what the handle's workspaces hold in this mode");
     GraphKey key{nb, fmt, d_src, d_wh, d_out, c->expert, post, c->flip_gen};
     if (c->mix) {   // a per-crop expert entry: its chunk's pattern, or the one expert the whole chunk runs
-        if (c->flip_on || c->mix->nb != nb) return fail(c, VP_ERR_STATE, "a chunk with per-crop experts under the flip-test mode, or a plan of another chunk");
+        if ((c->flip_on && !c->flip_ex) || c->mix->nb != nb) return fail(c, VP_ERR_STATE, "a chunk with per-crop experts under the single-table flip-test mode, or a plan of another chunk");
         key.wide = true;
         key.mix = c->mix->pattern;
         key.expert = key.mix ? 0 : c->mix->seg_e[0];

@@ -135,7 +135,7 @@ static int group_run(vp_group* g, const void* crops, int32_t fmt, int32_t n, con
     if (!out) { scratch.resize((size_t)n * K * 3); out = scratch.data(); }
     std::vector<int> offs, cnts;
     for (int i = 1; i < w; ++i)   // one plan for all members: they must agree on the flip-test mode (vp_group_set_flip_test sets them alike)
-        if (g->h[i]->flip_on != g->h[0]->flip_on || (g->h[0]->flip_on && (g->h[i]->flip_shift != g->h[0]->flip_shift || g->h[i]->flip_pairs != g->h[0]->flip_pairs))) {
+        if (g->h[i]->flip_on != g->h[0]->flip_on || g->h[i]->flip_ex != g->h[0]->flip_ex || (g->h[0]->flip_on && (g->h[i]->flip_shift != g->h[0]->flip_shift || g->h[i]->flip_pairs != g->h[0]->flip_pairs))) {
             g->err = "the members of the group disagree on the flip-test mode (member " + std::to_string(i) + " against member 0): set it with vp_group_set_flip_test";
             return VP_ERR_STATE;
         }

@@ -257,7 +257,47 @@ int vp_set_flip_test(vp_handle c, const int32_t* flip_pairs, int32_t n_pairs, in
     c->flip_pairs.assign(flip_pairs, flip_pairs + 2 * (size_t)n_pairs);
     c->flip_shift = shift_heatmap ? 1 : 0;
     c->flip_on = true;
+    c->flip_ex = false;                // (replaces the per-expert form)
     c->flip_gen = ++c->flip_counter;   // never the value of an earlier set: a graph captured under another table or shift is not replayed
+    return VP_OK;
+}
+
+// one table per expert: everything is validated and every refusal returned before the handle changes
+int vp_set_flip_test_experts(vp_handle c, const int32_t* flip_pairs, const int32_t* n_pairs, int32_t shift_heatmap) {
+    int rc = need_weights(c);
+    if (rc) return rc;
+    if (!c->n_experts) return fail(c, VP_ERR_STATE, "vp_set_flip_test_experts: the handle holds a plain (single-dataset) checkpoint, not a ViTPose+ one (vp_set_flip_test is its mode)");
+    if (!n_pairs) return fail(c, VP_ERR_INVALID, "vp_set_flip_test_experts: null n_pairs");
+    const int E = c->n_experts;
+    size_t total = 0;
+    for (int e = 0; e < E; ++e) {
+        if (n_pairs[e] < 0) return fail(c, VP_ERR_INVALID, "vp_set_flip_test_experts: expert " + std::to_string(e) + ": negative n_pairs");
+        total += (size_t)n_pairs[e];
+    }
+    if (total > 0 && !flip_pairs) return fail(c, VP_ERR_INVALID, "vp_set_flip_test_experts: null flip_pairs with a positive pair count");
+    std::vector<int32_t> tables((size_t)E * c->Kmax);
+    size_t at = 0;
+    for (int e = 0; e < E; ++e) {
+        int32_t* row = tables.data() + (size_t)e * c->Kmax;
+        std::string why;
+        if (flip_partner_table(c->ex_heads[e].K, n_pairs[e] ? flip_pairs + 2 * at : nullptr, n_pairs[e], row, &why))
+            return fail(c, VP_ERR_INVALID, "vp_set_flip_test_experts: expert " + std::to_string(e) + ": " + why);
+        for (int k = c->ex_heads[e].K; k < c->Kmax; ++k) row[k] = k;
+        at += (size_t)n_pairs[e];
+    }
+    if (c->maxb < 2)
+        return fail(c, VP_ERR_STATE, "vp_set_flip_test_experts: a crop and its mirror image share the forward batch, which needs max_batch >= 2 (this handle has 1)");
+    if ((rc = slots_idle(c, "vp_set_flip_test_experts"))) return rc;
+    if ((rc = vp_synchronize(c))) return rc;   // a previous table may still be read by enqueued work (also on a caller's stream)
+    if (!c->flip_tables && (rc = dalloc(c, &c->flip_tables, tables.size()))) return rc;
+    if (!c->mix_recs_flip && (rc = dalloc(c, &c->mix_recs_flip, (size_t)((c->maxb + 3) / 4 * 4)))) return rc;
+    HIPCHK(c, hipMemcpy(c->flip_tables, tables.data(), tables.size() * 4, hipMemcpyHostToDevice));   // synchronous: `tables` is a local
+    c->flip_pairs.assign(flip_pairs, flip_pairs + 2 * total);
+    c->flip_pairs.insert(c->flip_pairs.end(), n_pairs, n_pairs + E);   // (the counts too: two handles' modes compare equal only with the same split)
+    c->flip_shift = shift_heatmap ? 1 : 0;
+    c->flip_on = true;
+    c->flip_ex = true;
+    c->flip_gen = ++c->flip_counter;
     return VP_OK;
 }
 
@@ -265,12 +305,13 @@ int vp_clear_flip_test(vp_handle c) {
     if (!c) return VP_ERR_INVALID;
     if (int rc = slots_idle(c, "vp_clear_flip_test")) return rc;
     c->flip_on = false;
+    c->flip_ex = false;
     c->flip_gen = 0;   // the graphs of the plain mode are valid again
     c->flip_pairs.clear();
     return VP_OK;
 }
 
-int vp_flip_test_enabled(vp_handle c) { return c && c->flip_on ? 1 : 0; }
+int vp_flip_test_enabled(vp_handle c) { return c && c->flip_on ? (c->flip_ex ? 2 : 1) : 0; }   // 2: one table per expert (vp_set_flip_test_experts)
 
 int vp_dbg_flip_partner(int32_t k, const int32_t* flip_pairs, int32_t n_pairs, int32_t* partner) {
     std::string why;
@@ -307,7 +348,7 @@ int vp_set_expert(vp_handle c, int32_t e) {
     if (int rc = slots_idle(c, "vp_set_expert")) return rc;
     const int k_before = c->Kp;
     use_expert(c, e);
-    if (c->flip_on && c->Kp != k_before) {   // the pairs were validated against the previous head's joints and say nothing about this one's
+    if (c->flip_on && !c->flip_ex && c->Kp != k_before) {   // the pairs were validated against the previous head's joints and say nothing about this one's
         vp_clear_flip_test(c);
         return fail(c, VP_ERR_STATE, "vp_set_expert: expert " + std::to_string(e) + " is active, but its head has " + std::to_string(c->Kp) + " joints, not " +
                                          std::to_string(k_before) + ": the flip-test mode was cleared -- call vp_set_flip_test with this dataset's pairs");

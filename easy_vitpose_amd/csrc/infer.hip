@@ -1,6 +1,6 @@
 // The inference entries of the C ABI (include/vitpose_hip.h) and their staging: host crops, device crops on the handle's or a caller's stream,
 // the two asynchronous slots, frames, device boxes, ViTPose+ mixed batches (vp_infer_experts; per-crop experts on the device, frames and boxes entries with
-// their host-side plan, mix_plan), vp_infer_flip.  Each walks its crops in chunks (for_chunks) and hands a chunk to forward.hip.
+// their host-side plan, mix_plan, and its doubled form under the per-expert flip-test mode, mix_records_flip), vp_infer_flip.  Each walks its crops in chunks (for_chunks) and hands a chunk to forward.hip.
 #include "api_internal.h"
 #include "boxgeom.h"
 
@@ -137,7 +137,7 @@ int mix_ready(vp_ctx* c, const char* who, int n, const int32_t* expert_ids) {
     if (!c->n_experts) return fail(c, VP_ERR_STATE, std::string(who) + ": the handle holds a plain (single-dataset) checkpoint, not a ViTPose+ one");
     std::string why;
     if (mix_check_ids(expert_ids, n, c->n_experts, &why)) return fail(c, VP_ERR_INVALID, why);
-    if (c->flip_on)
+    if (c->flip_on && !c->flip_ex)
         return fail(c, VP_ERR_STATE, std::string(who) + " does not run under the flip-test mode (one partner table per handle, not per crop): call vp_clear_flip_test first");
     return slots_idle(c, who);
 }
@@ -150,14 +150,18 @@ int mix_chunk_tables(vp_ctx* c, const int32_t* expert_ids, int off, int nb, MixP
     std::vector<int32_t>&ks = c->mix_ks, &first = c->mix_first, &K = c->mix_k;
     ks.resize(c->n_experts); first.resize(nb); K.resize(nb);
     for (int e = 0; e < c->n_experts; ++e) ks[e] = c->ex_heads[e].K;
-    mix_records(p, ks.data(), c->Kmax, first.data(), K.data());
+    if (c->flip_ex) mix_records_flip(p, ks.data(), c->Kmax, first.data(), K.data());   // the per-expert flip-test mode: nb <= max_batch / 2 crops, two forward rows each
+    else mix_records(p, ks.data(), c->Kmax, first.data(), K.data());
     for (int base = 0; base < nb; base += vp::MIX_CROPS_PER_LAUNCH) {
         vp::MixTable t;
         std::memset(&t, 0, sizeof(t));
         t.base = base; t.count = std::min(nb - base, vp::MIX_CROPS_PER_LAUNCH);
         t.pad_to = base + t.count == nb ? B : 0;   // encoder padding crops repeat the last crop (pick_run_batch)
         for (int i = 0; i < t.count; ++i) { t.id[i] = p.ids[base + i]; t.order[i] = p.order[base + i]; t.first[i] = first[base + i]; t.K[i] = K[base + i]; }
-        LAUNCH(c, VP_PROF_IM2COL, 0.0, 28.0 * t.count, vp::mix_tables_launch(t, c->expert_ids, c->expert_ids + B, c->mix_slot, c->mix_recs, c->stream));
+        if (c->flip_ex)
+            LAUNCH(c, VP_PROF_IM2COL, 0.0, 48.0 * t.count, vp::mix_tables_flip_launch(t, c->expert_ids, c->expert_ids + B, c->mix_slot, c->mix_recs, c->mix_recs_flip, c->stream));
+        else
+            LAUNCH(c, VP_PROF_IM2COL, 0.0, 28.0 * t.count, vp::mix_tables_launch(t, c->expert_ids, c->expert_ids + B, c->mix_slot, c->mix_recs, c->stream));
     }
     return VP_OK;
 }
@@ -302,6 +306,14 @@ void mix_records(const MixPlan& p, const int32_t* k_per_expert, int Kmax, int32_
         for (int j = p.seg_s[s]; j < p.seg_s[s + 1]; ++j) {
             K[j] = k_per_expert[p.seg_e[s]];
             first[j] = p.seg_s[s] * Kmax + (j - p.seg_s[s]) * K[j];
+        }
+}
+
+void mix_records_flip(const MixPlan& p, const int32_t* k_per_expert, int Kmax, int32_t* first, int32_t* K) {
+    for (size_t s = 0; s < p.seg_e.size(); ++s)
+        for (int j = p.seg_s[s]; j < p.seg_s[s + 1]; ++j) {
+            K[j] = k_per_expert[p.seg_e[s]];
+            first[j] = 2 * p.seg_s[s] * Kmax + 2 * (j - p.seg_s[s]) * K[j];
         }
 }
 
@@ -490,7 +502,7 @@ int vp_infer_heatmaps(vp_handle c, const void* crops, int32_t fmt, int32_t n, fl
         if (rc || (rc = forward_mode_chunk(c, c->in_stage, fmt, nb))) return rc;
         if (!c->flip_on) return copy_out_sync(c, heatmaps, c->hm, map_elems, off, nb);
         // the averaged maps, materialised in the straight crops' slots (every second one of the interleaved batch)
-        HIPCHK(c, vp::flip_merge_launch(c->hm, c->hm + map_elems, c->flip_table, nb, c->Kp, c->flip_shift, c->stream, 1));
+        HIPCHK(c, vp::flip_merge_launch(c->hm, c->hm + map_elems, flip_table_now(c), nb, c->Kp, c->flip_shift, c->stream, 1));
         HIPCHK(c, hipMemcpy2DAsync(heatmaps + (size_t)off * map_elems, map_bytes, c->hm, 2 * map_bytes, map_bytes, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return VP_OK;
@@ -685,9 +697,10 @@ int vp_dbg_box_geometry(const float* xyxy, int32_t row_stride, const int32_t* fr
 }
 
 // One decode launch on host data, on device `device_id`: the scratch, the uploads, the launch, the download (into NaN: every value must be written), the frees.
-// records != null: n_maps maps by records into [n, k] rows;  partner != null: the interleaved [n_maps = 2 n, k, 64, 48] of the flip-test mode;  neither: [n, k, 64, 48]
+// records != null: n_maps maps by records into [n, k] rows;  partner != null: the interleaved [n_maps = 2 n, k, 64, 48] of the flip-test mode;  neither: [n, k, 64, 48];
+// both (n_tables > 0): four-field records and a [n_tables, k] partner table, the per-expert flip-test mode
 static int decode_host(const char* who, int32_t device_id, const float* heatmaps, size_t n_maps, int32_t n, int32_t k, const int32_t* partner, int32_t shift,
-                       const int32_t* records, const int32_t* org_wh, float* out) {
+                       const int32_t* records, const int32_t* org_wh, float* out, int32_t n_tables = 0) {
     if (!heatmaps || !out || n <= 0 || k <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, VP_ERR_HIP, "no HIP device available (no CPU fallback)");
@@ -696,7 +709,8 @@ static int decode_host(const char* who, int32_t device_id, const float* heatmaps
     HIPCHK(c, hipSetDevice(device_id));
     void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the maps, the sizes, the partner table, the records (each where given), the output
     const void* h[4] = {heatmaps, org_wh, partner, records};
-    const size_t bytes[5] = {n_maps * 3072 * 4, (size_t)n * 8, (size_t)k * 4, (size_t)n * sizeof(vp::MixRec), (size_t)n * k * 12};
+    const size_t bytes[5] = {n_maps * 3072 * 4, (size_t)n * 8, (size_t)k * 4 * (n_tables ? n_tables : 1), (size_t)n * (n_tables ? sizeof(vp::MixRecFlip) : sizeof(vp::MixRec)),
+                             (size_t)n * k * 12};
     hipError_t e = hipMalloc(&d[4], bytes[4]);
     if (e == hipSuccess) e = hipMemset(d[4], 0xff, bytes[4]);
     for (int i = 0; i < 4 && e == hipSuccess; ++i) {
@@ -707,9 +721,10 @@ static int decode_host(const char* who, int32_t device_id, const float* heatmaps
     const float* d_hm = (const float*)d[0];
     const int32_t* d_wh = (const int32_t*)d[1];
     if (e == hipSuccess)
-        e = records   ? vp::decode_mix_launch(d_hm, (const vp::MixRec*)d[3], d_wh, (float*)d[4], n, k, nullptr)
-            : partner ? vp::decode_flip_launch(d_hm, (const int32_t*)d[2], shift ? 1 : 0, d_wh, (float*)d[4], n, k, nullptr)
-                      : vp::decode_launch(d_hm, d_wh, (float*)d[4], n, k, nullptr);
+        e = n_tables  ? vp::decode_flip_mix_launch(d_hm, (const vp::MixRecFlip*)d[3], (const int32_t*)d[2], shift ? 1 : 0, d_wh, (float*)d[4], n, k, nullptr)
+            : records ? vp::decode_mix_launch(d_hm, (const vp::MixRec*)d[3], d_wh, (float*)d[4], n, k, nullptr)
+            : partner   ? vp::decode_flip_launch(d_hm, (const int32_t*)d[2], shift ? 1 : 0, d_wh, (float*)d[4], n, k, nullptr)
+                        : vp::decode_launch(d_hm, d_wh, (float*)d[4], n, k, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, d[4], bytes[4], hipMemcpyDeviceToHost);
     const int rc = e == hipSuccess ? (int)VP_OK : fail(nullptr, VP_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
@@ -771,6 +786,55 @@ int vp_dbg_decode_mix(int32_t device_id, const float* heatmaps, int32_t n_maps, 
             return fail(nullptr, VP_ERR_INVALID, "record " + std::to_string(j) + " lies outside the maps or the output, or repeats a row");
     }
     return decode_host("vp_dbg_decode_mix", device_id, heatmaps, (size_t)n_maps, n, kmax, nullptr, 0, records, org_wh, out);
+}
+
+int vp_dbg_mix_plan_flip(const int32_t* expert_ids, int32_t n, int32_t n_experts, int32_t max_batch, const int32_t* k_per_expert, int32_t* order, int32_t* row_ids,
+                         int32_t* counts, int32_t* records, uint64_t* pattern) {
+    if (n < 0 || n_experts <= 0 || max_batch <= 0 || (n > 0 && !expert_ids)) return fail(nullptr, VP_ERR_INVALID, "bad argument");
+    if (max_batch < 2) return fail(nullptr, VP_ERR_INVALID, "max_batch < 2: a crop and its mirror image share the forward batch");
+    std::string why;
+    if (mix_check_ids(expert_ids, n, n_experts, &why)) return fail(nullptr, VP_ERR_INVALID, why);
+    const int B = (max_batch + 3) / 4 * 4;
+    int kmax = 0;
+    for (int e = 0; e < n_experts && k_per_expert; ++e) kmax = std::max(kmax, k_per_expert[e]);
+    int ci = 0;
+    const int rc = for_chunks(n, max_batch / 2, [&](int off, int nb) -> int {   // the entries' own walk under the mode (chunk_cap)
+        MixPlan p;
+        mix_plan(expert_ids + off, nb, n_experts, p);
+        if (order) std::memcpy(order + off, p.order.data(), (size_t)nb * 4);
+        if (row_ids)   // what mix_tables_kernel<true> leaves in the handle's id buffer
+            for (int r = 0; r < B; ++r) row_ids[(size_t)ci * B + r] = p.ids[std::min(r >> 1, nb - 1)];
+        if (counts) {
+            std::memset(counts + (size_t)ci * n_experts, 0, (size_t)n_experts * 4);
+            for (size_t s = 0; s < p.seg_e.size(); ++s) counts[(size_t)ci * n_experts + p.seg_e[s]] = p.seg_s[s + 1] - p.seg_s[s];
+        }
+        if (records && k_per_expert) {
+            std::vector<int32_t> first(nb), K(nb);
+            mix_records_flip(p, k_per_expert, kmax, first.data(), K.data());
+            for (int j = 0; j < nb; ++j) { int32_t* r = records + 4 * (size_t)(off + j); r[0] = first[j]; r[1] = K[j]; r[2] = p.order[j]; r[3] = p.ids[j]; }
+        }
+        if (pattern) pattern[ci] = p.pattern;
+        ++ci;
+        return VP_OK;
+    });
+    return rc ? rc : ci;
+}
+
+int vp_dbg_decode_flip_mix(int32_t device_id, const float* heatmaps, int32_t n_maps, int32_t n, int32_t kmax, const int32_t* records4, const int32_t* partners,
+                           int32_t n_experts, int32_t shift_heatmap, const int32_t* org_wh, float* out) {
+    if (!heatmaps || !out || !records4 || !partners || n <= 0 || kmax <= 0 || n_maps <= 0 || n_experts <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n_experts * kmax; ++i)   // the kernel indexes maps with it
+        if (partners[i] < 0 || partners[i] >= kmax) return fail(nullptr, VP_ERR_INVALID, "partner table entry " + std::to_string(i) + " outside [0, kmax)");
+    std::vector<uint8_t> seen((size_t)n, 0);
+    for (int j = 0; j < n; ++j) {   // every record's 2 K maps inside the maps, its row inside the output and written once, its expert inside the table
+        const int32_t* r = records4 + 4 * (size_t)j;
+        if (r[0] < 0 || r[1] <= 0 || r[1] > kmax || (int64_t)r[0] + 2 * (int64_t)r[1] > n_maps || r[2] < 0 || r[2] >= n || seen[r[2]]++ || r[3] < 0 || r[3] >= n_experts)
+            return fail(nullptr, VP_ERR_INVALID, "record " + std::to_string(j) + " lies outside the maps, the output or the partner table, or repeats a row");
+        for (int k = 0; k < r[1]; ++k)   // a mirror joint of this crop must be one of ITS K maps
+            if (partners[(size_t)r[3] * kmax + k] >= r[1])
+                return fail(nullptr, VP_ERR_INVALID, "record " + std::to_string(j) + ": expert " + std::to_string(r[3]) + "'s partner of joint " + std::to_string(k) + " is outside its " + std::to_string(r[1]) + " joints");
+    }
+    return decode_host("vp_dbg_decode_flip_mix", device_id, heatmaps, (size_t)n_maps, n, kmax, partners, shift_heatmap, records4, org_wh, out, n_experts);
 }
 
 }  // extern "C"

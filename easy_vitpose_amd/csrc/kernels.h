@@ -239,6 +239,15 @@ struct MixRec {
 // the record route of the decode: ONE launch for the whole chunk.  Block (j, k): k < recs[j].K decodes map recs[j].first + k as decode_launch does on a
 // [1, K, 64, 48] crop (same arithmetic, same summation orders, same bits) into out[recs[j].dst][k]; k >= K writes zeros.  out fp32 [N, Kmax, 3], org_wh [N, 2] or null
 hipError_t decode_mix_launch(const float* hm, const MixRec* recs, const int32_t* org_wh, float* out, int N, int Kmax, hipStream_t s);
+// The same chunk under the per-expert flip-test mode (vp_set_flip_test_experts): the forward ran every crop and its mirror image as rows 2 j, 2 j + 1 of the expert
+// order, so the crop's K maps start at `first` and its mirror's at first + K; e = its expert, the row of the [n_experts, Kmax] partner table its mirror is read by
+struct MixRecFlip {
+    int32_t first, K, dst, e;
+};
+// Block (j, k): k < recs[j].K decodes 0.5 (map first + k + flip_back(map first + K + partners[e][k])) as decode_flip_launch does on a [2, K, 64, 48] pair (same fp32
+// add, exact multiply and summation orders: same bits) into out[recs[j].dst][k]; k >= K writes zeros.  partners: device int32 [n_experts, Kmax]
+hipError_t decode_flip_mix_launch(const float* hm, const MixRecFlip* recs, const int32_t* partners, int shift, const int32_t* org_wh, float* out, int N, int Kmax,
+                                  hipStream_t s);
 // vp_infer_boxes_stream: decoded keypoints [n, K, 3] in padded-crop pixels -> frame pixels (aux as box_geometry_launch writes it; status != 0: all zero).  slot + recs
 // (both or neither): rows of K = Kmax joints of a chunk with per-crop experts -- row i keeps the zeros behind its expert's recs[slot[i]].K joints
 hipError_t box_offsets_launch(const int32_t* aux, float* out, int n, int K, hipStream_t s, const int32_t* slot = nullptr, const MixRec* recs = nullptr);
@@ -252,5 +261,9 @@ struct MixTable {
     int32_t base, count, pad_to;
 };
 hipError_t mix_tables_launch(const MixTable& t, int32_t* ids, int32_t* order, int32_t* slot, MixRec* recs, hipStream_t s);
+// ... under the per-expert flip-test mode: position j of the expert order is forward rows 2 j and 2 j + 1, so ids[2 j] = ids[2 j + 1] = id (pad_to counts ROWS:
+// ids[2 (base + count) .. pad_to) repeat the last id), order / slot stay per crop, and the decode's record is recs_flip[j] = {first, K, order, id}
+// (recs[j] keeps {first, K, order} for box_offsets_launch, which reads K alone)
+hipError_t mix_tables_flip_launch(const MixTable& t, int32_t* ids, int32_t* order, int32_t* slot, MixRec* recs, MixRecFlip* recs_flip, hipStream_t s);
 
 }  // namespace vp

@@ -128,7 +128,7 @@ class VitPoseHip:
         if name not in names:
             raise ValueError(f'unknown dataset {name!r} for this ViTPose+ checkpoint: one of {", ".join(names)}')
         e = names.index(name)
-        drops_mode = self.flip_test and self.experts[e][1] != self.K   # another K: the switch takes place, the flip-test mode is cleared, VP_ERR_STATE says so
+        drops_mode = self.flip_test and not self.flip_test_per_dataset and self.experts[e][1] != self.K   # another K: the switch takes place, the flip-test mode is cleared, VP_ERR_STATE says so
         code = self.lib.vp_set_expert(self._h, e)
         if code == capi.VP_OK or (drops_mode and code == capi.VP_ERR_STATE and not self.flip_test):
             self.dataset, self.K = name, self.experts[e][1]
@@ -283,9 +283,40 @@ class VitPoseHip:
         the flipped-back heatmaps of its mirror image, and `heatmaps` returns that average.  The mirror images ride in the same forward,
         so a chunk holds ``max_batch // 2`` crops (`submit` takes that many at most).  `pairs`: the dataset's mirror joint pairs
         [[l, r], ...], validated against the active head's K.  `tokens`, `infer_flip` are not affected; `infer_mixed` refuses while
-        the mode is on.  A ViTPose+ handle: `set_dataset` to a head with another K clears the mode and raises."""
+        the mode is on (`set_flip_test_datasets` is the form it runs under).  A ViTPose+ handle: `set_dataset` to a head with another K clears the mode and raises."""
         pairs = _flip_pairs_array(pairs)
         capi.check(self.lib.vp_set_flip_test(self._h, pairs.ctypes.data if len(pairs) else None, len(pairs), int(bool(shift_heatmap))), self._h)
+
+    def set_flip_test_datasets(self, pairs_by_dataset, shift_heatmap: bool = False):
+        """The flip-test mode of a ViTPose+ handle with one pair table per dataset (vp_set_flip_test_experts, contract in include/vitpose_hip.h):
+        `pairs_by_dataset` maps every dataset of the checkpoint -- by name or expert index -- to its mirror joint pairs [[l, r], ...], each validated
+        against that dataset's K.  A dataset that is missing, named twice or unknown raises ValueError naming it before the library is called (it would
+        silently mirror every joint onto itself).  While it is on, every method `set_flip_test` covers runs under the active dataset's table,
+        `set_dataset` keeps the mode whatever the K, and `infer_mixed`, `infer_mixed_device`, `infer_frames(datasets=)` and `infer_boxes(datasets=)`
+        return each crop's flip-test keypoints under its own dataset's table (a chunk holds ``max_batch // 2`` crops).  `clear_flip_test`
+        switches it off, `set_flip_test` replaces it by the single-table mode."""
+        if not self._moe:
+            raise capi.VpError(capi.VP_ERR_STATE, 'set_flip_test_datasets: the handle holds a plain (single-dataset) checkpoint, not a ViTPose+ one')
+        names = [d for d, _ in self.experts]
+        by_expert = {}
+        for key, pairs in dict(pairs_by_dataset).items():
+            if isinstance(key, str):
+                if key not in names:
+                    raise ValueError(f'unknown dataset {key!r} for this ViTPose+ checkpoint: one of {", ".join(names)}')
+                e = names.index(key)
+            else:
+                e = int(key)
+                if not 0 <= e < len(names):
+                    raise ValueError(f'unknown expert index {key!r} for this ViTPose+ checkpoint: 0 .. {len(names) - 1}')
+            if e in by_expert:
+                raise ValueError(f'dataset {names[e]!r} is given twice (by name and by expert index)')
+            by_expert[e] = _flip_pairs_array(pairs)
+        missing = [names[e] for e in range(len(names)) if e not in by_expert]
+        if missing:
+            raise ValueError(f'set_flip_test_datasets: no pairs for {", ".join(missing)} (give [] for a dataset without mirror pairs)')
+        counts = np.ascontiguousarray([len(by_expert[e]) for e in range(len(names))], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([by_expert[e].reshape(-1, 2) for e in range(len(names))]), dtype=np.int32)
+        capi.check(self.lib.vp_set_flip_test_experts(self._h, flat.ctypes.data if len(flat) else None, counts.ctypes.data, int(bool(shift_heatmap))), self._h)
 
     def clear_flip_test(self):
         """Back to the default mode (vp_clear_flip_test)."""
@@ -294,6 +325,11 @@ class VitPoseHip:
     @property
     def flip_test(self) -> bool:
         return bool(self.lib.vp_flip_test_enabled(self._h))
+
+    @property
+    def flip_test_per_dataset(self) -> bool:
+        """the mode is on with one pair table per dataset (`set_flip_test_datasets`)"""
+        return self.lib.vp_flip_test_enabled(self._h) == 2
 
     def infer_frame(self, frame: np.ndarray, params: np.ndarray) -> np.ndarray:
         """Whole frame + crop geometry (cropprep.crop_params) -> [n, K, 3] in padded-crop pixels (vp_infer_frame)."""

@@ -263,7 +263,8 @@ VP_API int vp_infer_flip(vp_handle h, const void* crops, int32_t input_format, i
  *   max_batch / 2 of the caller's crops (vp_infer_submit: 1 .. max_batch / 2 per call), the small-batch thresholds (VP_GRAPH, VP_CALLER_STREAM)
  *   count the rows that run (2 n), and n crops under the mode are a 2 n batch: bit identity with another batch size or with vp_infer_flip (two
  *   passes of n) is NOT promised -- equal within the rounding of the 16-bit GEMMs, run-to-run identical.
- *   Not under the mode: vp_infer_tokens and vp_infer_flip (unchanged, whatever the mode); vp_infer_experts returns VP_ERR_STATE while it is on.
+ *   Not under the mode: vp_infer_tokens and vp_infer_flip (unchanged, whatever the mode); vp_infer_experts and its twins return VP_ERR_STATE while it is on
+ *   (they run under the per-expert form below, vp_set_flip_test_experts).
  *   ViTPose+ handles: the mode belongs to the active expert's joints.  vp_set_expert to a head with the same K keeps it; to a head with another K the
  *   switch takes place, the mode is CLEARED and the call returns VP_ERR_STATE saying so (set it again with that dataset's pairs).
  *   fp8 handles: the mode sits above the encoder and runs as it does on fp16 (exactness of the fused decode and run-to-run identity are tested, parity figures are not).
@@ -279,6 +280,22 @@ VP_API int vp_flip_test_enabled(vp_handle h);
  * when the members disagree on the mode (set through vp_group_member one by one). */
 VP_API int vp_group_set_flip_test(vp_group_handle g, const int32_t* flip_pairs, int32_t n_pairs, int32_t shift_heatmap);
 VP_API int vp_group_clear_flip_test(vp_group_handle g);
+/* The mode with ONE PARTNER TABLE PER EXPERT, for ViTPose+ handles: what lets the per-crop expert entries run under it.  n_pairs = host int32 [E] (E from
+ * vp_expert_info), flip_pairs = expert 0's pairs, then expert 1's, ...: (sum of n_pairs) x 2 joint indices, each expert's validated against ITS K_e (a refusal
+ * names the expert and the pair).  One device table [E, Kmax] is uploaded; the set waits for the handle's enqueued work as vp_set_flip_test does.  While this form is on:
+ *   - every entry that honours the single-table mode honours this one with the ACTIVE expert's table, and vp_set_expert to any expert keeps the mode on and
+ *     returns VP_OK (every expert has its own validated table: nothing is cleared);
+ *   - vp_infer_experts, vp_infer_experts_device_stream, vp_infer_frames_experts and vp_infer_boxes_experts_stream run under it: row i = the flip-test keypoints of
+ *     crop i under expert e_i's table, in the entry's own layout and coordinate frame, joints beyond K_{e_i} zero.  A chunk holds max_batch / 2 crops: they go into
+ *     stable expert order, position j as forward rows 2 j (the crop) and 2 j + 1 (its mirror), so every expert's rows start at an even row; one encoder pass of
+ *     2 nb rows, one head per expert present on its 2 cnt rows, ONE decode launch that averages each crop's two maps of a joint on the fly.  A chunk of one
+ *     expert runs the launches of vp_set_expert + the mode.  The hipGraph pattern counts crops per expert; VP_GRAPH / VP_CALLER_STREAM count the 2 nb rows;
+ *   - vp_flip_test_enabled returns 2 (1 for the single-table mode); vp_clear_flip_test switches it off; vp_set_flip_test replaces it by the single-table mode.
+ * The single-table mode is unchanged: it refuses the per-crop entries and clears on a change of K.  No group, submit / wait or fp8 form (ViTPose+ refuses fp8).
+ * VP_ERR_INVALID: NULL n_pairs, a negative count, NULL pairs with a positive total, an index outside [0, K_e).  VP_ERR_STATE: a plain (single-dataset) handle,
+ * weights not loaded, a vp_infer_submit in flight, max_batch == 1.  A refused call leaves the handle as it was. */
+#define VP_HAS_FLIP_TEST_EXPERTS 1
+VP_API int vp_set_flip_test_experts(vp_handle h, const int32_t* flip_pairs, const int32_t* n_pairs, int32_t shift_heatmap);
 /* HOST ONLY taps of the mode's pure functions: the partner table of k joints (partner may be NULL: validation only; the reason of a refusal is in
  * vp_last_error(NULL)), and the interleaved batch's index function -- src[r] / mirror[r] = the source crop of output row r in [0, rows) and whether
  * it is mirrored, for n crops in a forward of rows >= 2 n crops (rows beyond 2 n repeat the last one). */
@@ -354,6 +371,20 @@ VP_API int vp_dbg_mix_plan(const int32_t* expert_ids, int32_t n, int32_t n_exper
  * bit, joints beyond K_j zero.  VP_ERR_INVALID for a record outside the maps or the output, or two records with one destination. */
 VP_API int vp_dbg_decode_mix(int32_t device_id, const float* heatmaps, int32_t n_maps, int32_t n, int32_t kmax, const int32_t* records,
                              const int32_t* org_wh, float* out);
+/* HOST ONLY: the plan of the same chunks under the per-expert flip-test mode (vp_set_flip_test_experts).  Arguments as vp_dbg_mix_plan; a chunk holds
+ * max_batch / 2 crops and its forward 2 nb rows -- position j of the order is rows 2 j (the crop) and 2 j + 1 (its mirror):
+ *   order [n], counts [chunks, n_experts], pattern [chunks]: per CROP, as vp_dbg_mix_plan gives them for chunks of max_batch / 2
+ *   row_ids [chunks, B]: the expert of every forward row, ids[order[r >> 1]]; the rows beyond 2 nb repeat the last one
+ *   records [n, 4]: {first, K_e, destination row, e} with first = 2 seg_start Kmax + 2 (j - seg_start) K_e; the mirror's K_e maps start at first + K_e
+ * Returns the number of chunks, or VP_ERR_INVALID as vp_dbg_mix_plan does, and for max_batch < 2. */
+VP_API int vp_dbg_mix_plan_flip(const int32_t* expert_ids, int32_t n, int32_t n_experts, int32_t max_batch, const int32_t* k_per_expert, int32_t* order,
+                                int32_t* row_ids, int32_t* counts, int32_t* records, uint64_t* pattern);
+/* That mode's decode kernel alone, on host data: heatmaps = float32 [n_maps, 64, 48]; records4 [n, 4] as above; partners = int32 [n_experts, kmax], row e the
+ * mirror joint of every joint of expert e (vp_dbg_flip_partner, the identity beyond K_e) -> out [n, kmax, 3]: row dst_j = vp_dbg_decode_flip of the
+ * [2, K_j, 64, 48] maps from first_j on under expert e_j's table, bit for bit, joints beyond K_j zero.  VP_ERR_INVALID for a record whose 2 K maps leave
+ * [0, n_maps), a destination outside [0, n), two records with one destination, an expert outside [0, n_experts). */
+VP_API int vp_dbg_decode_flip_mix(int32_t device_id, const float* heatmaps, int32_t n_maps, int32_t n, int32_t kmax, const int32_t* records4,
+                                  const int32_t* partners, int32_t n_experts, int32_t shift_heatmap, const int32_t* org_wh, float* out);
 
 /* Decode alone: keypoints_from_heatmaps(unbiased=True, use_udp=True) + postprocess
  * (vit_utils/top_down_eval.py:493-641, easy_ViTPose/inference.py:187-205), one crop
