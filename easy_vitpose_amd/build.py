@@ -6,12 +6,13 @@ The shared object is written to ``easy_vitpose_amd/_lib/`` (git-ignored, but it
 travels to the GPU box with the gpurun snapshot).  hipcc cross-compiles for
 gfx950 without a GPU, so this also runs in the CPU-only build container.
 
-Two libraries from the same sources:
+Two libraries:
 
 * ``libvitpose_hip.so`` -- the PRODUCT: what ``_capi.load_library`` loads, what tests / bench / smoke run.
 * ``libvitpose_hip_tools.so`` (``--tools``, ``-DVP_TOOLS``) -- the measurement build ``tools/`` load through ``VP_HIP_LIB``:
-  ablation flags, start stagger and cycle stamps inside the GEMM kernels, the experimental tile configurations, the
-  development environment switches (``include/vitpose_hip_tools.h``).
+  the same sources with ablation flags, start stagger and cycle stamps inside the GEMM kernels, every row of the tile table
+  (``csrc/tiles.h``) and the development environment switches, plus the two tools-only translation units ``probes.hip``
+  (calibration and issue / store / placement probes) and ``tools_taps.hip`` (timing taps; ``include/vitpose_hip_tools.h``).
 """
 from __future__ import annotations
 
@@ -28,8 +29,8 @@ LIB = os.path.join(LIBDIR, 'libvitpose_hip.so')
 TOOLS_LIB = os.path.join(LIBDIR, 'libvitpose_hip_tools.so')
 SOURCES = ['gemm.hip', 'gemm8.hip', 'gemm8f.hip', 'qkvattn.hip', 'quant8.hip', 'attention.hip', 'elementwise.hip', 'decode.hip', 'boxes.hip', 'fp8_probe.hip',
            'handle.hip', 'forward.hip', 'infer.hip', 'group.hip', 'weights.hip', 'tile_rules.hip', 'debug_taps.hip']
-TOOLS_SOURCES = SOURCES
-HEADERS = ['common.h', 'kernels.h', 'gemm8_common.h', 'mx8.h', 'api_internal.h', 'boxgeom.h', os.path.join('..', '..', 'include', 'vitpose_hip.h'),
+TOOLS_SOURCES = SOURCES + ['probes.hip', 'tools_taps.hip']   # measurement code no plan can launch: probes, timing taps
+HEADERS = ['common.h', 'kernels.h', 'tiles.h', 'dbg_util.h', 'gemm8_common.h', 'mx8.h', 'api_internal.h', 'boxgeom.h', os.path.join('..', '..', 'include', 'vitpose_hip.h'),
            os.path.join('..', '..', 'include', 'vitpose_hip_tools.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden',
          '-ffp-contract=fast', '-Wno-unused-result']
@@ -72,7 +73,7 @@ def build_library(force: bool = False, verbose: bool = False, tools: bool = Fals
         return r
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1, 16)) as ex:
             list(ex.map(run, jobs))
     if jobs or force or _stale(lib, objs):
         run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', *objs, '-o', lib])

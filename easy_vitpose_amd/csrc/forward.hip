@@ -1,6 +1,7 @@
 // The forward of one chunk behind the C ABI (include/vitpose_hip.h): the GEMM launchers, the encoder + head + decode of up to max_batch crops as the
 // chunk's plan (tile_rules.hip plan_chunk) picked them, and the hipGraph cache that replays small chunks (run_chunk).
 #include "api_internal.h"
+#include "tiles.h"
 
 using namespace vpi;
 
@@ -81,7 +82,7 @@ int gemm_fp8(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint8_t* A8,
         g.plane = ln->plane; g.stats_out = ln->stats_out;
         if (ln->tiles_out) *ln->tiles_out = N / 64;
     }
-    const int bn = pk.variant == 17 ? 192 : 256;   // tile_rules.hip resolve_gemm_fp8
+    const int bn = vp::tile8_bn(pk.variant);   // tile_rules.hip resolve_gemm_fp8 (0 = not an 8-phase tile: refused below)
     g.group_m = pk.group_m;
     if (!vp::gemm8f_supported(epi, g, bn))
         return fail(c, VP_ERR_SHAPE, "fp8 mode: GEMM shape " + std::to_string(M) + " x " + std::to_string(N) + " x " + std::to_string(K) + " not supported by the MXFP8 kernel");

@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "tiles.h"
 
 namespace vp {
 
@@ -1200,59 +1201,18 @@ static hipError_t launch_persist(const GemmArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Tile configurations (id = GemmArgs::variant).  Measured on MI355X at M = 49152 (tools/gemm_tune.py,
-// profiles/gemm_tune_r1.txt).  Default = Cfg8: one 192-token crop per m-tile, so the tile count divides
-// evenly over 256 CUs x 2 resident blocks for every encoder GEMM (no tail wave), and the epilogue of one
-// block overlaps the main loop of its CU partner.  The others are kept as measured alternatives:
-// 256x256 halves the L2->LDS operand traffic but runs 1 block / CU (epilogue exposed, tail wave at N = D);
-// Cfg6 is the staggered two-group (anti-phase wave pairs) schedule; Cfg5 the fragment-store A/B reference;
-// Cfg10 = Cfg8 with hand-scheduled inline-asm ds_reads and counted lgkmcnt (bare loop +7 %, end to end +0-2 %:
-// the operand stream, not the intra-wave schedule, is what bounds these GEMMs).  Cfg11 = the Cfg8 block tile cut
-// into 8 wave tiles of 48x64: same main-loop rate (LDS reads are at 18 % utilisation, so the smaller wave tile
-// costs nothing), but twice the threads for the VALU-heavy residual epilogue (plane split + LayerNorm statistics):
-// proj+fc2 4.54 -> 4.30 ms per step; no gain for qkv / fc1, slower for the deconvs (96x32 wave tiles: -25 %).
-//                    BM   BN  BK   WM  WN  STAGES PIPE DIRECT      LDS   waves
-using Cfg0 = TileCfg<128, 128, 64, 64, 64, 2, 0, 0>;    //  64 KiB   4   (2 blocks / CU)
-using Cfg1 = TileCfg<128, 128, 64, 64, 64, 2, 1, 0>;    //  same + pipelined fragment reads
-using Cfg2 = TileCfg<256, 256, 64, 128, 64, 2, 0, 0>;   // 128 KiB   8   (1 block / CU)
-using Cfg3 = TileCfg<256, 256, 64, 128, 64, 2, 1, 0>;   //  same + pipelined fragment reads
-using Cfg4 = TileCfg<256, 256, 32, 128, 64, 4, 2, 0>;   // 128 KiB   8   4-stage ring, register double-buffered fragments
-using Cfg5 = TileCfg<128, 128, 64, 64, 64, 2, 0, 1>;    //  Cfg0 with fragment-shaped epilogue stores (A/B reference)
-using Cfg6 = TileCfg<256, 256, 32, 128, 64, 4, 3, 0>;   // 128 KiB   8   staggered two-group schedule
-using Cfg7 = TileCfg<192, 256, 64, 96, 64, 2, 1, 0>;    // 112 KiB   8   (1 block / CU)
-using Cfg8 = TileCfg<192, 128, 64, 96, 64, 2, 1, 0>;    //  80 KiB   4   (2 blocks / CU)  <- default
-using Cfg9 = TileCfg<64, 64, 64, 32, 32, 2, 0, 0>;      //  32 KiB   4   (5 blocks / CU)  small batches: enough tiles to fill 256 CUs
-using Cfg10 = TileCfg<192, 128, 64, 96, 64, 2, 5, 0>;   //  Cfg8 with the hand-scheduled (inline-asm ds_read, counted lgkmcnt) fragment pipeline
-using Cfg11 = TileCfg<192, 128, 64, 48, 64, 2, 1, 0>;  //  80 KiB   8   Cfg8 tile as 8 waves of 48x64 (4 waves / SIMD, 122 VGPRs)  <- default for the residual GEMMs
-// small batches (a few crops per GPU): the 2-stage ring waits for every k-block's full L2 latency; deeper rings keep 2-3 blocks in flight
-using Cfg12 = TileCfg<64, 64, 64, 32, 32, 4, 0, 0>;     //  64 KiB   4   (2 blocks / CU)  Cfg9 with a 4-stage ring
-using Cfg13 = TileCfg<128, 128, 64, 64, 64, 3, 1, 0>;   //  96 KiB   4   (1 block / CU)   Cfg1 with a 3-stage ring
-using Cfg14 = TileCfg<64, 64, 64, 32, 32, 3, 0, 0>;     //  48 KiB   4   (3 blocks / CU)  Cfg9 with a 3-stage ring
-using Cfg15 = TileCfg<128, 64, 64, 64, 32, 3, 0, 0>;    //  72 KiB   4   (2 blocks / CU)  128(m) x 64(n), 3-stage ring
-static constexpr int NUM_TILE_CFGS = 16;
-// (16-18 = the 8-phase kernel of gemm8.hip.)  Round 5, small batches IN SITU: every layer's weights are first touched from HBM (ViTPose-L: 25 MB per layer,
-// 600 MB per forward -- more than L2 + the memory-side cache hold), so a k-block costs an HBM round trip, not the L2 hit the isolated sweeps of rounds 2-3 saw:
-// a workgroup retires STAGES - 1 k-blocks per round trip whatever its tile, and one full round of workgroups with a deep ring beats more, smaller tiles.
-using Cfg19 = TileCfg<192, 128, 64, 96, 64, 3, 1, 0>;   // 120 KiB   4   (1 block / CU)   Cfg8 with a 3-stage ring
-using Cfg20 = TileCfg<192, 128, 64, 48, 64, 3, 1, 0>;   // 120 KiB   8   (1 block / CU)   Cfg11 with a 3-stage ring
-using Cfg21 = TileCfg<64, 64, 64, 32, 32, 5, 0, 0>;     //  80 KiB   4   (2 blocks / CU)  Cfg9 with a 5-stage ring
-using Cfg22 = TileCfg<128, 64, 64, 64, 32, 6, 0, 0>;    // 144 KiB   4   (1 block / CU)   128(m) x 64(n), 6-stage ring
-using Cfg23 = TileCfg<64, 64, 64, 32, 32, 8, 0, 0>;     // 128 KiB   4   (1 block / CU)   Cfg9 with an 8-stage ring
-using Cfg24 = TileCfg<128, 128, 64, 64, 64, 4, 1, 0>;   // 128 KiB   4   (1 block / CU)   Cfg1 with a 4-stage ring
-using Cfg25 = TileCfg<128, 128, 32, 64, 64, 4, 0, 0>;   //  64 KiB   4   (2 blocks / CU)  128 x 128 with k-blocks of 32: 4-stage ring in Cfg1's LDS
-using Cfg26 = TileCfg<128, 128, 32, 64, 64, 5, 0, 0>;   //  80 KiB   4   (2 blocks / CU)  ... 5-stage
-using Cfg27 = TileCfg<64, 64, 64, 32, 32, 4, 1, 0>;     //  64 KiB   4   (2 blocks / CU)  Cfg12 with pipelined fragment reads
-using Cfg28 = TileCfg<64, 64, 64, 32, 32, 5, 6, 0>;     //  80 KiB   4   (2 blocks / CU)  64 x 64, two k-blocks per barrier, 5-stage ring (3 k-blocks in flight)
-using Cfg29 = TileCfg<64, 64, 64, 32, 32, 4, 6, 0>;     //  64 KiB   4   (2 blocks / CU)  ... 4-stage ring (2 in flight)
-using Cfg30 = TileCfg<64, 64, 64, 32, 32, 6, 6, 0>;     //  96 KiB   4   (1 block / CU)   ... 6-stage ring (4 in flight)
-using Cfg31 = TileCfg<32, 64, 64, 16, 32, 6, 6, 0>;     //  72 KiB   4   (2 blocks / CU)  32(m) x 64(n): twice the workgroups of a 1-2 crop GEMM, half the MFMAs per wave and k-block
-using Cfg32 = TileCfg<32, 64, 64, 16, 32, 8, 6, 0>;     //  96 KiB   4   (1 block / CU)   ... 8-stage ring (6 in flight)
-using Cfg41 = TileCfg<96, 64, 64, 48, 32, 4, 0, 0>;     //  80 KiB   4   (2 blocks / CU)  96(m) x 64(n), 4-stage ring: the residual GEMMs between the 64 x 64 and 128 x 64 regimes (round 6: <= 448 tiles;
-                                                        //                                 ViTPose-L 11-14 crops, -B 15-18, -H 9-11: profiles/small_batch_r6.txt call 18)
-// (round 6: the staggered two-group schedule -- PIPE 3, waves 0-3 / 4-7 one barrier apart -- on 256 x 128 / 128 x 128 / 128 x 256 tiles with k-blocks of 32 was measured for the
-// 8-crop wide GEMMs and lost everywhere, +8 ... +25 % per step, as did register double-buffered fragments -- PIPE 2 -- on 192 x 128 / 128 x 128 / 128 x 64 / 64 x 64 tiles with k-blocks of 32,
-// +3 ... +20 %: profiles/small_batch_r6.txt calls 9-10; the configurations are not kept.  Also measured and not kept (calls 13, 15): a 4-stage ring on the one-round
-// 192 x 128 tile (+1 %), the 96 x 64 tile with a 6-stage ring / two k-blocks per barrier (loses wherever the 4-stage one wins).)
+// Tile configurations (id = GemmArgs::variant): the rows of tiles.h.  CfgAt<i> is row i as the kernels' template argument.
+template <int I>
+using CfgAt = TileCfg<TILES[I].BM, TILES[I].BN, TILES[I].BK, TILES[I].WM, TILES[I].WN, TILES[I].STAGES, TILES[I].PIPE, TILES[I].DIRECT>;
+constexpr int tile_index(int id) { return (int)(find_tile(id) - TILES); }
+using Cfg3 = CfgAt<tile_index(3)>;   // 256 x 256: the fused deconv2 + final conv tile (EPI_DECONV_FINAL)
+using Cfg8 = CfgAt<tile_index(8)>;   // the default tile: the persistent variant
+// the table's derived values against the kernel's own, for every row
+template <int... I>
+constexpr bool table_matches_kernels(std::integer_sequence<int, I...>) {
+    return ((tile_ring_bytes(TILES[I]) == CfgAt<I>::LDS && tile_threads(TILES[I]) == CfgAt<I>::NT) && ...);
+}
+static_assert(table_matches_kernels(std::make_integer_sequence<int, NUM_TILES>{}), "tiles.h: ring bytes / thread count differ from TileCfg");
 
 template <class T, int EPI, int AMODE, class C>
 static hipError_t launch(const GemmArgs& a, hipStream_t s) {
@@ -1292,64 +1252,29 @@ static hipError_t launch(const GemmArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// the product library carries the configurations the selection rule of tile_rules.hip can pick (1, 3, 8, 9, 11, 12, 15, 20, 30, 31, 41);
-// the measured alternatives are instantiated in the VP_TOOLS build only
+// One compile-time walk over the tile table: row I is instantiated for this epilogue where the table says so -- the product library carries the rows marked
+// `product` (the ids the rules of tile_rules.hip can pick), the measurement build every row; EPI_PARTIAL (split-K partial products) the rows marked `partial`.
 #ifdef VP_TOOLS
-#define VP_TOOLS_CASE(v) case v: return launch<T, EPI, AMODE, Cfg##v>(a, s);
+constexpr bool ALL_TILES = true;
 #else
-#define VP_TOOLS_CASE(v)
+constexpr bool ALL_TILES = false;
 #endif
+template <class T, int EPI, int AMODE, int I>
+static bool launch_row(const GemmArgs& a, hipStream_t s, hipError_t& e) {
+    constexpr bool instantiated = EPI == EPI_PARTIAL ? TILES[I].partial : (TILES[I].product || ALL_TILES);
+    if constexpr (instantiated)
+        if (a.variant == TILES[I].id) { e = launch<T, EPI, AMODE, CfgAt<I>>(a, s); return true; }
+    return false;
+}
+template <class T, int EPI, int AMODE, int... I>
+static hipError_t by_variant(const GemmArgs& a, hipStream_t s, std::integer_sequence<int, I...>) {
+    hipError_t e = hipErrorInvalidValue;   // an id without an instantiated row
+    (void)(... || launch_row<T, EPI, AMODE, I>(a, s, e));   // a LEFT fold: the rows, and so the kernels in the code object, are instantiated in table order
+    return e;
+}
 template <class T, int EPI, int AMODE>
 static hipError_t by_variant(const GemmArgs& a, hipStream_t s) {
-    switch (a.variant) {
-        VP_TOOLS_CASE(0)
-        case 1: return launch<T, EPI, AMODE, Cfg1>(a, s);
-        VP_TOOLS_CASE(2)
-        case 3: return launch<T, EPI, AMODE, Cfg3>(a, s);
-        VP_TOOLS_CASE(4)
-        VP_TOOLS_CASE(5)
-        VP_TOOLS_CASE(6)
-        VP_TOOLS_CASE(7)
-        case 8: return launch<T, EPI, AMODE, Cfg8>(a, s);
-        case 9: return launch<T, EPI, AMODE, Cfg9>(a, s);
-        VP_TOOLS_CASE(10)
-        case 11: return launch<T, EPI, AMODE, Cfg11>(a, s);
-        case 12: return launch<T, EPI, AMODE, Cfg12>(a, s);
-        VP_TOOLS_CASE(13)
-        VP_TOOLS_CASE(14)
-        case 15: return launch<T, EPI, AMODE, Cfg15>(a, s);
-        VP_TOOLS_CASE(19)
-        case 20: return launch<T, EPI, AMODE, Cfg20>(a, s);
-        VP_TOOLS_CASE(21)
-        VP_TOOLS_CASE(22)
-        VP_TOOLS_CASE(23)
-        VP_TOOLS_CASE(24)
-        VP_TOOLS_CASE(25)
-        VP_TOOLS_CASE(26)
-        VP_TOOLS_CASE(27)
-        VP_TOOLS_CASE(28)
-        VP_TOOLS_CASE(29)
-        case 30: return launch<T, EPI, AMODE, Cfg30>(a, s);
-        case 31: return launch<T, EPI, AMODE, Cfg31>(a, s);
-        VP_TOOLS_CASE(32)
-        case 41: return launch<T, EPI, AMODE, Cfg41>(a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-// split-K partial products (EPI_PARTIAL): the tiles the small-batch rule of tile_rules.hip may pick for them
-template <class T>
-static hipError_t by_variant_partial(const GemmArgs& a, hipStream_t s) {
-    switch (a.variant) {
-        case 1: return launch<T, EPI_PARTIAL, A_DENSE, Cfg1>(a, s);
-        case 11: return launch<T, EPI_PARTIAL, A_DENSE, Cfg11>(a, s);
-        case 12: return launch<T, EPI_PARTIAL, A_DENSE, Cfg12>(a, s);
-        case 15: return launch<T, EPI_PARTIAL, A_DENSE, Cfg15>(a, s);
-        case 20: return launch<T, EPI_PARTIAL, A_DENSE, Cfg20>(a, s);
-        case 30: return launch<T, EPI_PARTIAL, A_DENSE, Cfg30>(a, s);
-        case 31: return launch<T, EPI_PARTIAL, A_DENSE, Cfg31>(a, s);
-    }
-    return hipErrorInvalidValue;
+    return by_variant<T, EPI, AMODE>(a, s, std::make_integer_sequence<int, NUM_TILES>{});
 }
 
 template <class T>
@@ -1363,7 +1288,7 @@ static hipError_t dispatch(int epi, const GemmArgs& a, hipStream_t s) {
         case EPI_HEATMAP: return by_variant<T, EPI_HEATMAP, A_DENSE>(a, s);
         case EPI_BIAS_RESID_LN: return by_variant<T, EPI_BIAS_RESID_LN, A_DENSE>(a, s);
         case EPI_POS_LN: return by_variant<T, EPI_POS_LN, A_DENSE>(a, s);
-        case EPI_PARTIAL: return by_variant_partial<T>(a, s);
+        case EPI_PARTIAL: return by_variant<T, EPI_PARTIAL, A_DENSE>(a, s);
         case EPI_DECONV_FINAL:   // one tile configuration: 256 x 256 (all channels of a pixel in one tile)
             if (a.variant != 3 || a.N != Cfg3::BN || !a.W2 || !a.bias2 || !a.out2 || a.Kp <= 0) return hipErrorInvalidValue;
             return launch<T, EPI_DECONV_FINAL, A_DECONV, Cfg3>(a, s);
@@ -1371,29 +1296,19 @@ static hipError_t dispatch(int epi, const GemmArgs& a, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
-int gemm_tile_bn(int variant) {
-    static const int bn[NUM_TILE_CFGS] = {Cfg0::BN, Cfg1::BN, Cfg2::BN, Cfg3::BN, Cfg4::BN, Cfg5::BN, Cfg6::BN, Cfg7::BN, Cfg8::BN, Cfg9::BN, Cfg10::BN, Cfg11::BN,
-                                          Cfg12::BN, Cfg13::BN, Cfg14::BN, Cfg15::BN};
-    if (variant == 16 || variant == 18) return 256;
-    if (variant == 17) return 192;
-    if (variant == 19 || variant == 20 || (variant >= 24 && variant <= 26)) return 128;
-    if ((variant >= 21 && variant <= 23) || (variant >= 27 && variant <= 32) || variant == 41) return 64;
-    return (variant >= 0 && variant < NUM_TILE_CFGS) ? bn[variant] : 0;
-}
-
 hipError_t gemm_launch(int dtype, int epi, const GemmArgs& a, hipStream_t s) {
     if (a.K % 64 != 0 || a.M <= 0 || a.N <= 0) return hipErrorInvalidValue;
     if (a.expert && ((epi != EPI_BIAS_RESID && epi != EPI_BIAS_RESID_LN) || a.persist || a.M % 192)) return hipErrorInvalidValue;   // per-crop experts: the residual GEMM only
-    if (a.variant >= 16 && a.variant <= 18) {   // 16: 256 x 256, 17: 256 x 192, 18: 192 x 256
+    if (const Tile8Row* t8 = find_tile8(a.variant)) {   // the 8-phase kernel's tiles
 #ifdef VP_TOOLS
         static const int stagger_env = [] { const char* e = getenv("VP_G8_STAGGER"); return e ? atoi(e) : -1; }();
         if (stagger_env >= 0) {
             GemmArgs b = a;   // experiments: override the start stagger
             b.stagger = stagger_env;
-            return gemm8_launch(dtype, epi, b, a.variant == 17 ? 192 : 256, s, a.variant == 18 ? 192 : 256);
+            return gemm8_launch(dtype, epi, b, t8->BN, s, t8->BM);
         }
 #endif
-        return gemm8_launch(dtype, epi, a, a.variant == 17 ? 192 : 256, s, a.variant == 18 ? 192 : 256);
+        return gemm8_launch(dtype, epi, a, t8->BN, s, t8->BM);
     }
 #ifdef VP_TOOLS
     static const int proj_stagger_env = [] { const char* e = getenv("VP_PROJ_STAGGER"); return e ? atoi(e) : 0; }();
@@ -1404,7 +1319,8 @@ hipError_t gemm_launch(int dtype, int epi, const GemmArgs& a, hipStream_t s) {
     }
 #endif
     if (a.persist) {   // persistent variant: wide 16-bit-output GEMMs on the default tile (a 256x256 instantiation spilled and was slower)
-        if ((epi != EPI_BIAS && epi != EPI_BIAS_GELU) || a.variant != 8 || a.K % 128 || a.N % 8 || a.ldo != a.N || a.reverse ||
+        // (launch_persist allocates no statistics area behind the ring: a consumer that folds partial statistics itself, ln_part, is refused here, not only by resolve_gemm)
+        if ((epi != EPI_BIAS && epi != EPI_BIAS_GELU) || a.variant != 8 || a.ln_part || a.K % 128 || a.N % 8 || a.ldo != a.N || a.reverse ||
             a.M % Cfg8::BM || (size_t)a.M * a.K * 2 >= (1ull << 32) ||
             (size_t)((a.N + Cfg8::BN - 1) / Cfg8::BN) * Cfg8::BN > (size_t)a.w_rows)
             return hipErrorInvalidValue;

@@ -6,11 +6,18 @@
 
 // Two builds of the same sources (easy_vitpose_amd/build.py): the PRODUCT library (libvitpose_hip.so) and, with -DVP_TOOLS, the
 // measurement library tools/ loads (libvitpose_hip_tools.so): ablation flags and start stagger inside the GEMM loops, cycle
-// stamps, the experimental tile configurations and kernel variants, the development environment switches.  In the product
-// build GemmArgs::ablate / ::stagger read as the constant 0, so none of those branches exists in its kernels.
+// stamps, the experimental tile configurations and kernel variants, the development environment switches -- and two translation
+// units of its own, probes.hip and tools_taps.hip.  In the product build GemmArgs::ablate / ::stagger read as the constant 0, so
+// none of those branches exists in its kernels.
 #ifdef VP_TOOLS
 #define VP_ABLATE(g) ((g).ablate)
 #define VP_STAGGER(g) ((g).stagger)
+namespace vp {   // probes.hip: compiled into the measurement library only
+// calibration micro-benchmarks (tools/): kind 0/1 = MFMA 16x16x32 / 32x32x16 f16 TFLOP/s, 2 = float4 copy TB/s
+hipError_t peak_bench(int kind, double* result);
+// tools/hwid_probe.py: every workgroup of a launch records (HW_REG_HW_ID, HW_REG_XCC_ID, start cycle lo, hi) -> d_out[blocks][4]
+hipError_t hwid_probe_launch(uint32_t* d_out, int blocks, int threads, int lds_bytes, int spin, hipStream_t s);
+}  // namespace vp
 #else
 #define VP_ABLATE(g) 0
 #define VP_STAGGER(g) 0
@@ -56,7 +63,7 @@ struct GemmArgs {
     const float* bias2;
     float* out2;
     int w_rows;           // rows W is padded to at upload (multiple of 256); deconv parity slab = w_rows * K
-    int variant;          // tile configuration (gemm.hip Cfg0..)
+    int variant;          // tile configuration (an id of tiles.h)
     int group_m;          // grouped tile order: m-tiles per group (<= 1: plain n-fastest order)
     size_t w_parity_stride;  // filled by gemm_launch
     // ---- fused LayerNorm ----
@@ -128,7 +135,6 @@ hipError_t ln_quant_launch(int dtype, const uint16_t* x_hi, const float* ln_part
 // fp32 rows [M, K] -> MXFP8 in the same layouts (parity taps)
 hipError_t mx_quantize_launch(const float* src, uint8_t* codes, uint8_t* scales, int M, int K, hipStream_t s);
 
-int gemm_tile_bn(int variant);   // BN of a tile configuration (number of n-tiles = ceil(N / BN))
 // fill a 16-bit buffer with pseudo-random values in [-1, 1) (benchmark operands)
 hipError_t fill_random16(int dtype, uint16_t* p, size_t n, uint32_t seed, hipStream_t s);
 
@@ -149,11 +155,6 @@ hipError_t fp8_probe_launch(const float* dA, const float* dW, const float* dAs, 
 // v_mfma_scale_f32_16x16x128_f8f6f4 with the operand roles and the packed scale dwords of the fp8 mode's GEMM.  M % 64 == 0, N % 16 == 0, K % 128 == 0
 hipError_t mx_probe_launch(const float* dA, const float* dW, const float* dWs, uint8_t* dA8, uint8_t* dAs, uint8_t* dW8, float* dOut,
                            int M, int N, int K, hipStream_t s);
-
-// calibration micro-benchmarks (tools/): kind 0/1 = MFMA 16x16x32 / 32x32x16 f16 TFLOP/s, 2 = float4 copy TB/s
-hipError_t peak_bench(int kind, double* result);
-// tools/hwid_probe.py: every workgroup of a launch records (HW_REG_HW_ID, HW_REG_XCC_ID, start cycle lo, hi) -> d_out[blocks][4]
-hipError_t hwid_probe_launch(uint32_t* d_out, int blocks, int threads, int lds_bytes, int spin, hipStream_t s);
 
 // ------------------------------------------------------------------ attention
 // qkv [B*192, 3*D] 16-bit (columns = [q | k | v] x heads x head_dim, vit.py:166-167)

@@ -2,6 +2,7 @@
 // (pick_*) feed one resolver per GEMM (resolve_gemm) and one plan per chunk (plan_chunk), which the orchestration (forward.hip) only executes.
 // tests/test_host_logic.py walks the rules and the plan over every batch size of every model through the host-only taps at the end of this file.
 #include "api_internal.h"
+#include "tiles.h"
 
 using namespace vpi;
 
@@ -9,6 +10,7 @@ namespace vpi {
 
 struct G8Pick { int variant, bm, bn; long tiles; };
 struct Tile2Pick { int variant, group_m; };
+using vp::is_gemm8;
 struct SplitKPick { int S, variant; };   // split-K of a residual GEMM: S k ranges on tile configuration `variant` (S = 1: no split)
 
 // Tile of the 8-phase kernel for an [M, N] output (wide = 16-bit output, else residual epilogue); variant 0 = the 2-phase kernels run it.
@@ -24,29 +26,26 @@ struct SplitKPick { int S, variant; };   // split-K of a residual GEMM: S k rang
 // `extended` the 192 x 256 tile is only the fallback when no 256-row tile qualifies.  Where isolated and in-situ timings disagreed (fc2 at 52 / 128
 // crops, ViTPose-L at 40, -S at 256: the 2-phase kernel finds `hid` in the caches and wins by 2 - 7 % in situ) the rule follows the in-situ result.
 G8Pick pick_gemm8_tile(int M, int N, bool wide, int bm192_mask, long min_tiles, bool extended) {
-    struct Cand { int bm, bn, variant; };
-    static const Cand cands[3] = {{256, 256, 16}, {256, 192, 17}, {192, 256, 18}};
     const bool ext = extended && M >= 7680;
     const long t2 = (long)((M + 191) / 192) * ((N + 127) / 128);
     const double cost2 = t2 <= 256 ? 24576.0 : (double)((t2 + 511) / 512) * 49152.0;
     G8Pick pk{0, 0, 0, 0};
     double best = 0.0;
     bool have256 = false;
-    for (int i = 0; i < 3; ++i) {
-        const Cand& cd = cands[i];
-        if (M % cd.bm || N % cd.bn || (wide && cd.variant == 17)) continue;
-        if (cd.variant == 18 && (!(bm192_mask & (wide ? 2 : 1)) || (!ext && have256))) continue;   // round-3 behaviour: only when no 256-row tile qualifies
-        const long t = (long)(M / cd.bm) * (N / cd.bn);
+    for (const vp::Tile8Row& cd : vp::TILES8) {   // in table order: 256 x 256, 256 x 192, 192 x 256
+        if (M % cd.BM || N % cd.BN || (wide && cd.id == 17)) continue;
+        if (cd.id == 18 && (!(bm192_mask & (wide ? 2 : 1)) || (!ext && have256))) continue;   // round-3 behaviour: only when no 256-row tile qualifies
+        const long t = (long)(M / cd.BM) * (N / cd.BN);
         if (t < 8) continue;
         const long rounds = (t + 255) / 256;
         const double f = (double)t / (double)(rounds * 256);   // share of 256 CUs x rounds that computes a tile (below 256 tiles: one workgroup per tile)
-        const double cost = (double)rounds * cd.bm * cd.bn * (cd.variant == 18 ? 1.08 : 1.0);
+        const double cost = (double)rounds * cd.BM * cd.BN * (cd.id == 18 ? 1.08 : 1.0);
         bool q = t >= min_tiles || (f >= 0.8 && t >= 192);
         if (ext) q = q || (rounds == 1 && t >= 192) || cost < 0.95 * cost2;
         if (!q) continue;
-        if (cd.bm == 256) have256 = true;
+        if (cd.BM == 256) have256 = true;
         if (!pk.variant || (ext ? cost < 0.98 * best : f > (double)pk.tiles / (double)((pk.tiles + 255) / 256 * 256) + 1e-9)) {
-            pk = {cd.variant, cd.bm, cd.bn, t};
+            pk = {cd.id, cd.BM, cd.BN, t};
             best = cost;
         }
     }
@@ -149,21 +148,12 @@ SplitKPick pick_splitk(int M, int N, int K) {
     return {1, 0};
 }
 
-// (BM, BN, workgroups resident on 256 CUs) of a 2-phase tile configuration the rule above can return
+// (BM, BN, workgroups resident on 256 CUs) of a 2-phase tile configuration the rules above can return: the product rows of tiles.h
 static bool tile2_dims(int variant, int& bm, int& bn, int& slots) {
-    switch (variant) {
-        case 8: case 11: bm = 192; bn = 128; slots = 512; return true;
-        case 1: bm = 128; bn = 128; slots = 512; return true;
-        case 3: bm = 256; bn = 256; slots = 256; return true;
-        case 9: bm = 64; bn = 64; slots = 1280; return true;
-        case 12: bm = 64; bn = 64; slots = 512; return true;
-        case 15: bm = 128; bn = 64; slots = 512; return true;
-        case 20: bm = 192; bn = 128; slots = 256; return true;
-        case 30: bm = 64; bn = 64; slots = 256; return true;
-        case 31: bm = 32; bn = 64; slots = 512; return true;
-        case 41: bm = 96; bn = 64; slots = 512; return true;
-    }
-    return false;
+    const vp::TileRow* r = vp::find_tile(variant);
+    if (!r || !r->product) return false;
+    bm = r->BM; bn = r->BN; slots = vp::tile_slots(*r);
+    return true;
 }
 
 // Rounds x tile area x K of one MLP GEMM on the tile resolve_gemm picked: the persistent 8-phase kernel runs ceil(tiles / 256) full rounds (its 192-row tile priced x 1.08 as in
@@ -171,9 +161,8 @@ static bool tile2_dims(int variant, int& bm, int& bn, int& slots) {
 // the 8-phase kernel, the default tile 110 against 80-90).
 static double mlp_gemm_cost(const GemmPick& pk, int M, int N, int K) {
     int bm = 192, bn = 128, slots = 512;
-    if (pk.variant >= 16 && pk.variant <= 18) {
-        bm = pk.variant == 18 ? 192 : 256;
-        bn = pk.variant == 17 ? 192 : 256;
+    if (const vp::Tile8Row* t8 = vp::find_tile8(pk.variant)) {
+        bm = t8->BM; bn = t8->BN;
         return (double)(((long)(M / bm) * (N / bn) + 255) / 256) * bm * bn * (bm == 192 ? 1.08 : 1.0) * K;
     }
     if (!tile2_dims(pk.variant, bm, bn, slots)) return 0.0;
@@ -200,8 +189,7 @@ static int pick_run_batch(const Switches& s, int n, int D, int limit) {
 }
 
 int tile_bm(int variant) {
-    if (variant == 16 || variant == 17) return 256;
-    if (variant == 18) return 192;
+    if (const int bm8 = vp::tile8_bm(variant)) return bm8;
     int bm = 0, bn = 0, slots = 0;
     return tile2_dims(variant, bm, bn, slots) ? bm : 0;
 }
@@ -220,12 +208,12 @@ bool expert_tile_ok(int bm, const std::vector<int>& bounds) {
 // The crop-aligned tile a mixed batch's mlp.fc2 takes where the rule's 128- or 256-row tile spans an expert change: the 8-phase kernel's 192 x 256 tile where the
 // 8-phase kernel would have run it (gemm8_ok: N % 256 == 0 and >= 1.75 tiles per CU, ViTPose-B / -L / -H at large batches), else the residual default 192 x 128.
 int expert_fallback_variant(int M, int N, bool gemm8_ok, int* group_m) {
-    if (gemm8_ok && N % 256 == 0 && (long)(M / 192) * (N / 256) >= 448) { *group_m = 2; return 18; }
+    constexpr vp::Tile8Row t8 = *vp::find_tile8(18);   // 192 x 256: the 8-phase tile of one crop's rows
+    if (gemm8_ok && N % t8.BN == 0 && (long)(M / t8.BM) * (N / t8.BN) >= 448) { *group_m = 2; return t8.id; }
     *group_m = 0;
     return 11;
 }
 
-static bool is_gemm8(int variant) { return variant >= 16 && variant <= 18; }
 static int gemm8_group_m(int fam) { return fam == VP_PROF_GEMM_QKV ? 4 : fam == VP_PROF_GEMM_FC2 ? 2 : 8; }   // measured sweep 0 / 2 / 4 / 8 / 16 / 32 (spread 2-3 %)
 
 // The complete choice for one GEMM, in the order the rules override each other: the tuned configuration (tools) or the 2-phase rule; the persistent variant of the
@@ -260,7 +248,7 @@ GemmPick resolve_gemm(const Switches& s, int fam, int epi, int M, int N, int K, 
     }
     const bool mixed = mix_bounds && fam == VP_PROF_GEMM_FC2;   // ViTPose+ mixed batch: every crop's m-tiles read its own expert's fc2
     if (mixed && !expert_tile_ok(tile_bm(p.variant), *mix_bounds)) {   // a tile would span two experts: the crop-aligned tile instead
-        const bool g8 = (s.gemm8_mask & 1) && vp::gemm8_shape_ok(epi, M, N, K, N, w_rows, 256, 192);
+        const bool g8 = (s.gemm8_mask & 1) && vp::gemm8_shape_ok(epi, M, N, K, N, w_rows, vp::tile8_bn(18), vp::tile8_bm(18));
         p.variant = expert_fallback_variant(M, N, g8, &p.group_m);
         p.persist = 0;
         p.stagger = p.variant == 18 ? s.g8_stagger : 0;
@@ -348,7 +336,7 @@ ChunkPlan plan_chunk(const Switches& s, int D, int heads, int max_batch, bool fp
         if (fold_stats) return true;
         if (!s.fold_rule || n > 64 || s.gemm_variant[fam] >= 0) return false;
         const int v = gemm(fam, epi, N, D, false).variant;
-        return v != 8 && v != 11 && !is_gemm8(v);
+        return vp::tile_folds_stats(v);
     };
     // attn.qkv + attention core as ONE kernel per (pair of crops, head) from 108 tiles on (qkvattn.hip; bit-identical y; an odd batch's last crop fills both halves of its pair)
     // 128 - 1536 tiles: profiles/qkvattn_r4.txt.  Below (round 6, profiles/small_batch_r6.txt call 16): 108-120 tiles win or tie (ViTPose-B 17-20 crops -0.6 ... -6.5 %: at 19-20

@@ -2,7 +2,7 @@
  * vitpose_hip_tools.h -- entry points of the MEASUREMENT build only (libvitpose_hip_tools.so = the sources of
  * libvitpose_hip.so compiled with -DVP_TOOLS, easy_vitpose_amd/build.py): cycle-stamp timelines of the GEMM kernels.  The
  * measurement build additionally honours GemmArgs::ablate / ::stagger inside the kernels, instantiates the experimental tile
- * configurations (gemm.hip Cfg0/2/4/5/6/7/10/13/14/15) and reads the
+ * configurations (the rows of csrc/tiles.h not marked `product`) and reads the
  * development environment switches.  tools/ loads it; the product path and tests/ never do.
  */
 #ifndef VITPOSE_HIP_TOOLS_H
@@ -37,7 +37,7 @@ VP_API int vp_dbg_gemm_bench(int32_t device_id, int32_t dtype, int32_t epi, int3
                              int32_t M, int32_t N, int32_t K, int32_t iters, float* ms_out);
 /* production GEMM configurations on RANDOM device operands (tools/gemm8_check.py, tests/test_gpu_gemm_cfgs.py):
  * epi = 0 bias, 1 bias+gelu, 2 bias+residual (fp32), 3 pos (fp32), 6 bias + two-plane residual + LayerNorm row statistics;
- * variant = tile configuration (gemm.hip Cfg0-11; 16 / 17 = the 8-phase kernel of gemm8.hip with 256x256 / 256x192 tiles);
+ * variant = tile configuration (an id of csrc/tiles.h; 16 / 17 = the 8-phase kernel of gemm8.hip with 256x256 / 256x192 tiles);
  * flags: 1 persistent workgroups, 2 64x64-blocked output, 4 64x64-blocked A operand, 8 reversed tile walk, 16 LayerNorm-consumer fold.
  * bench2: average milliseconds per launch.  compare: both configurations on the same operands, `reps` times; counts every
  * differing output element / statistic (two kernels with the same accumulation order must agree bit for bit). */
