@@ -6,6 +6,7 @@ Importing the package never touches the GPU; the first use of the engine loads
 ``_lib/libvitpose_hip.so`` and raises loudly if it is missing (no CPU fallback).
 """
 from .configs import ModelShape, model_shape  # noqa: F401
+from .cropprep import Frame  # noqa: F401
 
 
 def __getattr__(name):
@@ -18,4 +19,4 @@ def __getattr__(name):
     raise AttributeError(name)
 
 
-__all__ = ['VitInference', 'VitPoseHip', 'VitPoseGroup', 'PinnedArray', 'decode_heatmaps', 'ModelShape', 'model_shape']
+__all__ = ['VitInference', 'VitPoseHip', 'VitPoseGroup', 'PinnedArray', 'decode_heatmaps', 'ModelShape', 'model_shape', 'Frame']

@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), '_lib', 'lib
 VP_OK, VP_ERR_INVALID, VP_ERR_HIP, VP_ERR_STATE, VP_ERR_MISSING_TENSOR, VP_ERR_SHAPE = range(6)
 VP_DTYPE_F16, VP_DTYPE_BF16, VP_DTYPE_FP8 = 0, 1, 2
 VP_INPUT_F32_NCHW, VP_INPUT_U8_NHWC = 0, 1
+VP_PIX_RGB24, VP_PIX_BGR24, VP_PIX_NV12 = 0, 1, 2
+VP_YUV_BT601, VP_YUV_BT709, VP_YUV_BT601_FULL = 0, 1, 2
 VP_PROF_NAMES = ['gemm_proj', 'gemm_fc1', 'gemm_qkv', 'gemm_patch', 'gemm_deconv', 'gemm_final',
                  'attention', 'layernorm', 'im2col', 'decode', 'gemm_fc2']
 VP_PROF_COUNT = len(VP_PROF_NAMES)
@@ -33,7 +35,8 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_set_flip_test', 'vp_clear_flip_test', 'vp_flip_test_enabled', 'vp_group_set_flip_test', 'vp_group_clear_flip_test',
            'vp_dbg_flip_partner', 'vp_dbg_flip_layout', 'vp_dbg_decode_flip',
            'vp_infer_experts_device_stream', 'vp_infer_frames_experts', 'vp_infer_boxes_experts_stream', 'vp_dbg_mix_plan', 'vp_dbg_decode_mix',
-           'vp_set_flip_test_experts', 'vp_dbg_mix_plan_flip', 'vp_dbg_decode_flip_mix']
+           'vp_set_flip_test_experts', 'vp_dbg_mix_plan_flip', 'vp_dbg_decode_flip_mix',
+           'vp_infer_images', 'vp_infer_boxes_images_stream', 'vp_dbg_image_plan', 'vp_dbg_crop_prep_image']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -59,6 +62,10 @@ class vp_tensor_desc(C.Structure):
 
 class vp_frame(C.Structure):
     _fields_ = [('data', C.c_void_p), ('h', C.c_int32), ('w', C.c_int32)]
+
+
+class vp_image(C.Structure):
+    _fields_ = [('plane', C.c_void_p * 2), ('pitch', C.c_int64 * 2), ('h', C.c_int32), ('w', C.c_int32), ('format', C.c_int32), ('matrix', C.c_int32)]
 
 
 class vp_profile(C.Structure):
@@ -174,6 +181,11 @@ def load_library():
     lib.vp_set_flip_test_experts.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int32]
     lib.vp_dbg_mix_plan_flip.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     lib.vp_dbg_decode_flip_mix.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.vp_infer_images.argtypes = [H, C.POINTER(vp_image), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.vp_infer_boxes_images_stream.argtypes = [H, C.POINTER(vp_image), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vp_dbg_image_plan.argtypes = [C.POINTER(vp_image), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.vp_dbg_crop_prep_image.argtypes = [C.c_int32, C.POINTER(vp_image), C.c_void_p, C.c_int32, C.c_void_p]
     lib.vp_dbg_flip_partner.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.vp_dbg_flip_layout.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.vp_dbg_decode_flip.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]

@@ -95,3 +95,164 @@ def prepare_crops_host(frame: np.ndarray, params: np.ndarray) -> np.ndarray:
         canvas[top:top + ch, left:left + cw] = frame[y0:y0 + ch, x0:x0 + cw]
         out[i] = resize_linear_u8(canvas, (IMG_W, IMG_H))
     return out
+
+
+# ---- pixel formats of the frames and boxes entries (include/vitpose_hip.h vp_image; the one device definition is csrc/pixfmt.h) ----------------
+PIX_FORMATS = {'rgb': 0, 'bgr': 1, 'nv12': 2}                      # VP_PIX_*
+YUV_MATRIX_IDS = {'bt601': 0, 'bt709': 1, 'bt601_full': 2}         # VP_YUV_*
+# (yoff, cy, crv, cgu, cgv, cbu) at shift 20.  bt601: the integers of 1.164 / 1.596 / 0.391 / 0.813 / 2.018, the constants of OpenCV's
+# cvtColor(COLOR_YUV2RGB_NV12) -- against that binary PARITY UNPINNED (cv2 is not installed here); the others round(x * 2^20) of the standard matrices
+YUV_COEFS = {
+    'bt601': (16, 1220542, 1673527, -409993, -852492, 2116026),
+    'bt709': (16, 1220945, 1879825, -223607, -558796, 2215014),
+    'bt601_full': (0, 1048576, 1470104, -360853, -748826, 1858077),
+}
+YUV_SHIFT = 20
+
+
+def _matrix_name(matrix) -> str:
+    if isinstance(matrix, str):
+        if matrix not in YUV_COEFS:
+            raise ValueError(f'unknown YUV matrix {matrix!r}: one of {sorted(YUV_COEFS)}')
+        return matrix
+    for name, i in YUV_MATRIX_IDS.items():
+        if i == matrix:
+            return name
+    raise ValueError(f'unknown YUV matrix {matrix!r}')
+
+
+def _is_tensor(a) -> bool:
+    return hasattr(a, 'data_ptr')
+
+
+def _host(a) -> np.ndarray:
+    return a.detach().cpu().numpy() if _is_tensor(a) else np.asarray(a)
+
+
+def nv12_to_rgb(y, uv, matrix='bt601') -> np.ndarray:
+    """NV12 planes (y uint8 [h, w], uv uint8 [ceil(h/2), ceil(w/2), 2] = U, V pairs) -> uint8 [h, w, 3] RGB: the host restatement of the crop
+    kernel's pixel fetch.  int32, arithmetic shifts; chroma replicated (pixel (r, c) reads the pair (r >> 1, c >> 1))."""
+    y, uv = _host(y), _host(uv)
+    h, w = y.shape
+    assert uv.shape == ((h + 1) // 2, (w + 1) // 2, 2), f'uv {uv.shape} for y {y.shape}'
+    yoff, cy, crv, cgu, cgv, cbu = (np.int32(v) for v in YUV_COEFS[_matrix_name(matrix)])
+    yy = np.maximum(y.astype(np.int32) - yoff, 0) * cy + np.int32(1 << (YUV_SHIFT - 1))
+    c = uv[np.arange(h)[:, None] >> 1, np.arange(w)[None, :] >> 1].astype(np.int32) - np.int32(128)
+    u, v = c[..., 0], c[..., 1]
+    rgb = np.stack([(yy + crv * v) >> YUV_SHIFT, (yy + cgu * u + cgv * v) >> YUV_SHIFT, (yy + cbu * u) >> YUV_SHIFT], -1)
+    return np.clip(rgb, 0, 255).astype(np.uint8)
+
+
+_RGB2YUV = {   # (yoff, rows of Y, U, V over R, G, B): the forward matrices the tables above invert
+    'bt601': (16, ((0.256788, 0.504129, 0.097906), (-0.148223, -0.290993, 0.439216), (0.439216, -0.367788, -0.071427))),
+    'bt709': (16, ((0.182586, 0.614231, 0.062007), (-0.100644, -0.338572, 0.439216), (0.439216, -0.398942, -0.040274))),
+    'bt601_full': (0, ((0.299, 0.587, 0.114), (-0.168736, -0.331264, 0.5), (0.5, -0.418688, -0.081312))),
+}
+
+
+def rgb_to_nv12(rgb, matrix='bt601'):
+    """uint8 [h, w, 3] RGB -> (y [h, w], uv [ceil(h/2), ceil(w/2), 2]) uint8.  Makes NV12 content for tests and benchmarks from seeded RGB frames:
+    deterministic (float64, round half to even, chroma = the mean of each 2 x 2 block with the last row / column repeated on odd sizes), NOT an oracle."""
+    rgb = _host(rgb).astype(np.float64)
+    h, w = rgb.shape[:2]
+    yoff, (my, mu, mv) = _RGB2YUV[_matrix_name(matrix)]
+    y = np.clip(np.rint(rgb @ np.array(my) + yoff), 0, 255).astype(np.uint8)
+    pad = np.pad(rgb, ((0, h & 1), (0, w & 1), (0, 0)), mode='edge')
+    blk = (pad[0::2, 0::2] + pad[0::2, 1::2] + pad[1::2, 0::2] + pad[1::2, 1::2]) / 4.0
+    uv = np.stack([blk @ np.array(mu), blk @ np.array(mv)], -1) + 128.0
+    return y, np.clip(np.rint(uv), 0, 255).astype(np.uint8)
+
+
+class Frame:
+    """One frame of `VitPoseHip.infer_frames` / `infer_boxes` in the layout its producer holds it (vp_image): `Frame.rgb(a)`, `Frame.bgr(a)` for
+    packed uint8 [H, W, 3], `Frame.nv12(y, uv, matrix)` for a decoder surface (y uint8 [H, W]; uv uint8 [ceil(H/2), ceil(W/2), 2], U then V).  The
+    planes are numpy arrays (host) or torch CUDA tensors (device); rows may be pitched -- the strides are read from the array, nothing is
+    copied, and the Frame keeps its planes alive.  Within a row the bytes must be dense (strides (pitch, 3, 1) / (pitch, 1) / (pitch, 2, 1))."""
+    __slots__ = ('format', 'matrix', 'planes', 'h', 'w', 'pitch')
+
+    def __init__(self, fmt: str, planes, matrix='bt601'):
+        if fmt not in PIX_FORMATS:
+            raise ValueError(f'unknown pixel format {fmt!r}: one of {sorted(PIX_FORMATS)}')
+        self.format, self.matrix, self.planes = fmt, _matrix_name(matrix), tuple(planes)
+        tens = [_is_tensor(p) for p in self.planes]
+        if any(tens) and not all(tens):
+            raise TypeError('the planes of a frame are all numpy arrays (host) or all torch CUDA tensors (device)')
+        for p in self.planes:
+            if _is_tensor(p):
+                if not p.is_cuda:
+                    raise TypeError('a tensor plane must be a torch CUDA tensor (host planes are numpy arrays)')
+                if str(p.dtype) != 'torch.uint8':
+                    raise TypeError(f'uint8 expected, got {p.dtype}')
+            elif not isinstance(p, np.ndarray):
+                raise TypeError(f'a numpy array or a torch CUDA tensor expected, got {type(p).__name__}')
+            elif p.dtype != np.uint8:
+                raise TypeError(f'uint8 expected, got {p.dtype}')
+        a = self.planes[0]
+        if fmt == 'nv12':
+            if len(self.planes) != 2 or a.ndim != 2:
+                raise ValueError(f'NV12: y [H, W] and uv [ceil(H/2), ceil(W/2), 2] expected, got y {tuple(a.shape)}')
+            self.h, self.w = int(a.shape[0]), int(a.shape[1])
+            uv = self.planes[1]
+            if tuple(uv.shape) != ((self.h + 1) // 2, (self.w + 1) // 2, 2):
+                raise ValueError(f'NV12: uv [{(self.h + 1) // 2}, {(self.w + 1) // 2}, 2] expected for y [{self.h}, {self.w}], got {tuple(uv.shape)}')
+            self.pitch = (self._pitch(a, (1,), self.w), self._pitch(uv, (2, 1), 2 * ((self.w + 1) // 2)))
+        else:
+            if len(self.planes) != 1 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f'[H, W, 3] expected, got {tuple(a.shape)}')
+            self.h, self.w = int(a.shape[0]), int(a.shape[1])
+            self.pitch = (self._pitch(a, (3, 1), 3 * self.w), 0)
+
+    @staticmethod
+    def _strides(a):
+        return tuple(int(s) for s in (a.stride() if _is_tensor(a) else a.strides))   # uint8: elements are bytes
+
+    @classmethod
+    def _pitch(cls, a, inner, row_bytes: int) -> int:
+        """bytes per row of plane `a` whose strides behind the row axis must be `inner` (a dimension of one element has no stride to speak of)"""
+        st = cls._strides(a)
+        for dim, want in zip(range(1, a.ndim), inner):
+            if a.shape[dim] > 1 and st[dim] != want:
+                raise ValueError(f'strides {st} of a {tuple(a.shape)} plane: the bytes of a row must be dense (strides (pitch,) + {inner}); the last dimension has stride 1')
+        if a.shape[0] <= 1:
+            return row_bytes
+        if st[0] < row_bytes:
+            raise ValueError(f'row stride {st[0]} of a {tuple(a.shape)} plane is below its {row_bytes} row bytes (overlapping or reversed rows)')
+        return st[0]
+
+    @classmethod
+    def rgb(cls, a):
+        return cls('rgb', (a,))
+
+    @classmethod
+    def bgr(cls, a):
+        return cls('bgr', (a,))
+
+    @classmethod
+    def nv12(cls, y, uv, matrix='bt601'):
+        return cls('nv12', (y, uv), matrix)
+
+    @property
+    def on_device(self) -> bool:
+        return _is_tensor(self.planes[0])
+
+    @property
+    def shape(self):
+        return (self.h, self.w, 3)
+
+    def pointers(self):
+        """(plane 0, plane 1 or None) as integers"""
+        ptr = [p.data_ptr() if _is_tensor(p) else p.ctypes.data for p in self.planes]
+        return ptr[0], (ptr[1] if len(ptr) > 1 else None)
+
+    def __repr__(self):
+        return f'Frame.{self.format}({self.h} x {self.w}, pitch {self.pitch}, {"device" if self.on_device else "host"})'
+
+
+def to_rgb(frame) -> np.ndarray:
+    """Any frame the frames / boxes entries accept -> contiguous host uint8 [H, W, 3] RGB: what those entries see.  A bare array or tensor is RGB."""
+    if not isinstance(frame, Frame):
+        return np.ascontiguousarray(_host(frame))
+    if frame.format == 'nv12':
+        return nv12_to_rgb(frame.planes[0], frame.planes[1], frame.matrix)
+    a = _host(frame.planes[0])
+    return np.ascontiguousarray(a[..., ::-1] if frame.format == 'bgr' else a)

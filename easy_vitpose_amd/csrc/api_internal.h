@@ -306,12 +306,16 @@ void read_switches(Switches& s);      // the environment's switches (vp_create, 
 void apply_gemm_tuning(Switches& s);  // its VP_GEMM_TUNE part (tools build only): what the parity taps' contexts take
 
 // ---- infer.hip
-// vp_infer_frames' plan (HOST ONLY): checks every crop of p9 [n, 9] against its frame, bands [n_frames, 2] = rows [row0, row1) its crops cover
-// ({0, 0}: no crop; may be NULL).  VP_OK or VP_ERR_INVALID with the reason in *why
-int frame_plan(const vp_frame* frames, int n_frames, const int32_t* p9, int n, int32_t* bands, std::string* why);
-// the crops of p9 from frames as crop-kernel records: host frames are uploaded band by band into c->frame_stage (one copy per frame with
-// crops), device frames are read in place (checked to be device memory of the handle's device first).  recs[n] (host), enqueued on c->stream
-int stage_frames(vp_ctx* c, const vp_frame* frames, int n_frames, bool on_device, const int32_t* p9, int n, const int32_t* bands,
+// the layout of one frame (HOST ONLY): VP_ERR_INVALID with "frame f ..." in *why for an unknown format, an unknown matrix or a null UV plane of an NV12 frame, a negative
+// pitch, a pitch below the plane's row bytes (csrc/pixfmt.h plane_row_bytes).  Sizes and plane[0] are the callers' checks
+int image_check(const vp_image& im, int f, std::string* why);
+// vp_infer_images' plan (HOST ONLY): checks every crop of p9 [n, 9] against its frame (and, at the first crop that names it, the frame's layout: image_check),
+// bands [n_frames, 2] = frame rows [row0, row1) its crops cover ({0, 0}: no crop; may be NULL).  VP_OK or VP_ERR_INVALID with the reason in *why
+int image_plan(const vp_image* frames, int n_frames, const int32_t* p9, int n, int32_t* bands, std::string* why);
+// the crops of p9 from frames as crop-kernel records: host frames are uploaded band by band into c->frame_stage (one copy per plane of a frame with
+// crops: Y / RGB rows [row0, row1), UV rows [row0 >> 1, (row1 + 1) >> 1), at the caller's pitch), device frames are read in place (every plane checked to be device
+// memory of the handle's device first).  recs[n] (host), enqueued on c->stream
+int stage_frames(vp_ctx* c, const vp_image* frames, int n_frames, bool on_device, const int32_t* p9, int n, const int32_t* bands,
                  std::vector<vp::CropRec>& recs);
 // vp_infer_boxes_stream / vp_dbg_box_geometry (HOST ONLY): the host arguments of a boxes call (sizes of every frame, row stride, pad, counts).
 // VP_OK or VP_ERR_INVALID with the reason in *why

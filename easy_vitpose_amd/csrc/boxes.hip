@@ -2,6 +2,7 @@
 // Neither uses atomics (one thread owns every value it writes), so a call is bit-identical from run to run.
 #include "boxgeom.h"
 #include "kernels.h"
+#include "pixfmt.h"
 
 namespace vp {
 
@@ -23,19 +24,25 @@ __global__ __launch_bounds__(64) void box_geometry_kernel(BoxFrames fr, const fl
     int st = BOX_BAD_FRAME;
     if (in_window) {
         const float* b = xyxy + (size_t)i * row_stride;
-        st = box_geometry(b[0], b[1], b[2], b[3], fr.h[f - fr.f0], fr.w[f - fr.f0], pad, p8);
+        st = box_geometry(b[0], b[1], b[2], b[3], fr.fr[f - fr.f0].h, fr.fr[f - fr.f0].w, pad, p8);
         if (st != BOX_OK)
             for (int j = 0; j < 8; ++j) p8[j] = 0;
     }
     CropRec r;
     if (st == BOX_OK) {
-        const int64_t pitch = (int64_t)fr.w[f - fr.f0] * 3;
-        r.src = fr.data[f - fr.f0] + (size_t)p8[1] * pitch + (size_t)p8[0] * 3;
-        r.pitch = pitch;
+        const BoxFrame& im = fr.fr[f - fr.f0];
+        const bool nv12 = im.format == PIX_NV12;
+        r.src = im.plane[0] + (size_t)p8[1] * im.pitch[0] + (size_t)p8[0] * (nv12 ? 1 : 3);
+        r.pitch = im.pitch[0];
         r.cw = p8[2]; r.ch = p8[3]; r.left = p8[4]; r.top = p8[5]; r.pw = p8[6]; r.ph = p8[7];
+        r.src1 = nv12 ? im.plane[1] + (size_t)(p8[1] >> 1) * im.pitch[1] + (size_t)(p8[0] >> 1) * 2 : nullptr;
+        r.pitch1 = nv12 ? im.pitch[1] : 0;
+        r.format = im.format; r.matrix = im.matrix; r.oy = p8[1] & 1; r.ox = p8[0] & 1;
     } else {
         r.src = zero_px; r.pitch = 3;
         r.cw = r.ch = r.pw = r.ph = 1; r.left = r.top = 0;
+        r.src1 = nullptr; r.pitch1 = 0;
+        r.format = PIX_RGB24; r.matrix = 0; r.oy = r.ox = 0;
     }
     recs[slot ? slot[i] : i] = r;   // a chunk with per-crop experts: straight into its place in the expert order
     wh[2 * i] = r.pw;   // decode scales by the padded canvas, as vp_infer_frames passes it

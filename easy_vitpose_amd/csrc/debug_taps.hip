@@ -256,16 +256,15 @@ VP_API int vp_dbg_gemm_case(int32_t device, int32_t dtype, int32_t epi, int32_t 
     return dbg_finish(c, VP_OK);
 }
 
-// frame + crop geometry -> the uint8 [n,256,192,3] crops the model is fed (the device crop/pad/resize kernel alone, behind the staging of
-// vp_infer_frames: the one-frame case)
-VP_API int vp_dbg_crop_prep(int32_t device, const uint8_t* frame, int32_t fh, int32_t fw, const int32_t* crop_params, int32_t n, uint8_t* out) {
-    if (!frame || !crop_params || !out || n <= 0 || fh <= 0 || fw <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
-    const vp_frame fr{frame, fh, fw};
+// image + crop geometry -> the uint8 [n,256,192,3] RGB crops the model is fed (the device crop/pad/resize kernel alone, behind the staging of
+// vp_infer_images: the one-frame case)
+VP_API int vp_dbg_crop_prep_image(int32_t device, const vp_image* image, const int32_t* crop_params, int32_t n, uint8_t* out) {
+    if (!image || !crop_params || !out || n <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
     std::vector<int32_t> p9((size_t)n * 9, 0);
     for (int i = 0; i < n; ++i) std::memcpy(&p9[9 * (size_t)i + 1], crop_params + 8 * (size_t)i, 32);
     int32_t band[2];
     std::string why;
-    if (frame_plan(&fr, 1, p9.data(), n, band, &why)) return fail(nullptr, VP_ERR_INVALID, why);
+    if (image_plan(image, 1, p9.data(), n, band, &why)) return fail(nullptr, VP_ERR_INVALID, why);
     vp_ctx* c = dbg_ctx(device, VP_DTYPE_F16);
     if (!c) return VP_ERR_HIP;
     std::vector<vp::CropRec> recs;
@@ -273,7 +272,7 @@ VP_API int vp_dbg_crop_prep(int32_t device, const uint8_t* frame, int32_t fh, in
     vp::CropRec* drec;
     int rc;
     const size_t ob = (size_t)n * 256 * 192 * 3;
-    if ((rc = stage_frames(c, &fr, 1, false, p9.data(), n, band, recs)) || (rc = dalloc(c, &dout, ob)) || (rc = dalloc(c, &drec, (size_t)n)))
+    if ((rc = stage_frames(c, image, 1, false, p9.data(), n, band, recs)) || (rc = dalloc(c, &dout, ob)) || (rc = dalloc(c, &drec, (size_t)n)))
         return dbg_finish(c, rc);
     hipError_t e = hipMemcpy(drec, recs.data(), (size_t)n * sizeof(vp::CropRec), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = vp::crop_resize_launch(drec, dout, n, nullptr);
@@ -281,6 +280,13 @@ VP_API int vp_dbg_crop_prep(int32_t device, const uint8_t* frame, int32_t fh, in
     if (e == hipSuccess) e = hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = fail(c, VP_ERR_HIP, std::string("crop_prep: ") + hipGetErrorString(e));
     return dbg_finish(c, rc);
+}
+
+// ... on a packed RGB frame
+VP_API int vp_dbg_crop_prep(int32_t device, const uint8_t* frame, int32_t fh, int32_t fw, const int32_t* crop_params, int32_t n, uint8_t* out) {
+    if (!frame || fh <= 0 || fw <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
+    const vp_image im{{frame, nullptr}, {(int64_t)fw * 3, 0}, fh, fw, VP_PIX_RGB24, 0};
+    return vp_dbg_crop_prep_image(device, &im, crop_params, n, out);
 }
 
 // BASELINE config 5 probe: rows quantised to OCP e4m3 on device + one GEMM through v_mfma_f32_16x16x128_f8f6f4 (fp8_probe.hip)

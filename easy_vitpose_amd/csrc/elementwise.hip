@@ -1,6 +1,7 @@
 // HBM-bound helpers of the ViTPose path: patch gather (im2col) and LayerNorm.
 #include "common.h"
 #include "kernels.h"
+#include "pixfmt.h"
 #include "../../include/vitpose_hip.h"
 
 namespace vp {
@@ -520,31 +521,48 @@ __device__ __forceinline__ AxisCoef axis_coef(int d, int dsize, int ssize) {
     return c;
 }
 
-__global__ __launch_bounds__(192) void crop_resize_kernel(const CropRec* __restrict__ recs, uint8_t* __restrict__ out) {
-    const int crop = blockIdx.x >> 8, oy = blockIdx.x & 255, ox = threadIdx.x;
-    const CropRec r = recs[crop];   // each crop its own source (band or device frame) and pitch: one kernel for one or many frames
+// One output pixel of crop record r whose frame is in format FMT.  fetch = the RGB8 value of a padded-canvas pixel: the SOURCE pixel converted once
+// (pixfmt.h), zero outside the crop; both interpolation branches then run on RGB exactly as they did when RGB24 was the only format.
+template <int FMT> __device__ __forceinline__ void crop_pixel(const CropRec& r, int oy, int ox, uint8_t* __restrict__ dst) {
     const uint8_t* __restrict__ src = r.src;
+    const uint8_t* __restrict__ src1 = r.src1;
     const int cw = r.cw, ch = r.ch, left = r.left, top = r.top, pw = r.pw, ph = r.ph;
-    auto px = [&](int Y, int X, int c) -> int {   // padded-canvas pixel
+    const YuvCoef k = yuv_coef(FMT == PIX_NV12 ? r.matrix : 0);
+    auto fetch = [&](int Y, int X, int* rgb) {   // padded-canvas pixel
         const int yy = Y - top, xx = X - left;
-        if ((unsigned)yy >= (unsigned)ch || (unsigned)xx >= (unsigned)cw) return 0;
-        return src[(size_t)yy * r.pitch + (size_t)xx * 3 + c];
+        if ((unsigned)yy >= (unsigned)ch || (unsigned)xx >= (unsigned)cw) { rgb[0] = rgb[1] = rgb[2] = 0; return; }
+        if (FMT == PIX_NV12) {
+            const uint8_t* uv = src1 + (size_t)((r.oy + yy) >> 1) * r.pitch1 + (size_t)((r.ox + xx) >> 1) * 2;
+            yuv_to_rgb(k, src[(size_t)yy * r.pitch + (size_t)xx], uv[0], uv[1], rgb);
+            return;
+        }
+        const uint8_t* p = src + (size_t)yy * r.pitch + (size_t)xx * 3;
+        rgb[0] = p[FMT == PIX_BGR24 ? 2 : 0]; rgb[1] = p[1]; rgb[2] = p[FMT == PIX_BGR24 ? 0 : 2];
     };
-    uint8_t* dst = out + (((size_t)crop * 256 + oy) * 192 + ox) * 3;
+    int p00[3], p01[3], p10[3], p11[3];
     if (pw == 384 && ph == 512) {                 // exactly 2x: OpenCV's INTER_LINEAR == fast INTER_AREA
+        fetch(2 * oy, 2 * ox, p00); fetch(2 * oy, 2 * ox + 1, p01); fetch(2 * oy + 1, 2 * ox, p10); fetch(2 * oy + 1, 2 * ox + 1, p11);
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-            dst[c] = (uint8_t)((px(2 * oy, 2 * ox, c) + px(2 * oy, 2 * ox + 1, c) + px(2 * oy + 1, 2 * ox, c) +
-                                px(2 * oy + 1, 2 * ox + 1, c) + 2) >> 2);
+        for (int c = 0; c < 3; ++c) dst[c] = (uint8_t)((p00[c] + p01[c] + p10[c] + p11[c] + 2) >> 2);
         return;
     }
     const AxisCoef cx = axis_coef(ox, 192, pw), cy = axis_coef(oy, 256, ph);
+    fetch(cy.s0, cx.s0, p00); fetch(cy.s0, cx.s1, p01); fetch(cy.s1, cx.s0, p10); fetch(cy.s1, cx.s1, p11);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const int r0 = px(cy.s0, cx.s0, c) * cx.a0 + px(cy.s0, cx.s1, c) * cx.a1;
-        const int r1 = px(cy.s1, cx.s0, c) * cx.a0 + px(cy.s1, cx.s1, c) * cx.a1;
+        const int r0 = p00[c] * cx.a0 + p01[c] * cx.a1;
+        const int r1 = p10[c] * cx.a0 + p11[c] * cx.a1;
         dst[c] = (uint8_t)((((cy.a0 * (r0 >> 4)) >> 16) + ((cy.a1 * (r1 >> 4)) >> 16) + 2) >> 2);
     }
+}
+
+__global__ __launch_bounds__(192) void crop_resize_kernel(const CropRec* __restrict__ recs, uint8_t* __restrict__ out) {
+    const int crop = blockIdx.x >> 8, oy = blockIdx.x & 255, ox = threadIdx.x;
+    const CropRec r = recs[crop];   // each crop its own source (band or device frame), pitch and format: one kernel for one or many frames
+    uint8_t* dst = out + (((size_t)crop * 256 + oy) * 192 + ox) * 3;
+    if (r.format == PIX_RGB24) crop_pixel<PIX_RGB24>(r, oy, ox, dst);   // block-uniform: a launch may hold records of several formats
+    else if (r.format == PIX_NV12) crop_pixel<PIX_NV12>(r, oy, ox, dst);
+    else crop_pixel<PIX_BGR24>(r, oy, ox, dst);
 }
 
 hipError_t crop_resize_launch(const CropRec* recs, uint8_t* out, int n, hipStream_t s) {

@@ -3,6 +3,7 @@
 // their host-side plan, mix_plan, and its doubled form under the per-expert flip-test mode, mix_records_flip), vp_infer_flip.  Each walks its crops in chunks (for_chunks) and hands a chunk to forward.hip.
 #include "api_internal.h"
 #include "boxgeom.h"
+#include "pixfmt.h"
 
 using namespace vpi;
 
@@ -40,20 +41,34 @@ int device_chunks(vp_ctx* c, const void* d_crops, int fmt, int n, const int32_t*
     });
 }
 
-// frame f of a call that reads its frames in place: device memory of the handle's device, the whole frame inside one allocation.  A null frame
-// fails here too: vp_infer_boxes_stream relies on it (vp_infer_frames has refused one in frame_plan, with the crop that names it)
-int check_device_frame(vp_ctx* c, const vp_frame& fr, int f) {
-    hipPointerAttribute_t a;
-    std::memset(&a, 0, sizeof(a));
-    void* base = nullptr;
-    size_t size = 0;
-    bool ok = fr.data && hipPointerGetAttributes(&a, fr.data) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->cfg.device_id;
-    ok = ok && hipMemGetAddressRange(&base, &size, (void*)fr.data) == hipSuccess && fr.data + (size_t)fr.h * fr.w * 3 <= (const uint8_t*)base + size;
+// frame f of a call that reads its frames in place: every plane device memory of the handle's device, (plane rows - 1) * pitch + row bytes of it inside one
+// allocation (the planes may share one or not).  A null plane fails here too: vp_infer_boxes_stream relies on it (vp_infer_frames has refused one in
+// image_plan, with the crop that names it).  The format and the pitches have passed image_check
+int check_device_frame(vp_ctx* c, const vp_image& im, int f) {
+    bool ok = true;
+    for (int p = 0; p < (im.format == vp::PIX_NV12 ? 2 : 1) && ok; ++p) {
+        hipPointerAttribute_t a;
+        std::memset(&a, 0, sizeof(a));
+        void* base = nullptr;
+        size_t size = 0;
+        const uint8_t* q = im.plane[p];
+        const size_t bytes = (size_t)(vp::plane_rows(im.format, p, im.h) - 1) * (size_t)im.pitch[p] + (size_t)vp::plane_row_bytes(im.format, p, im.w);
+        ok = q && hipPointerGetAttributes(&a, q) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->cfg.device_id;
+        ok = ok && hipMemGetAddressRange(&base, &size, (void*)q) == hipSuccess && q + bytes <= (const uint8_t*)base + size;
+    }
     if (ok) return VP_OK;
     (void)hipGetLastError();
     return fail(c, VP_ERR_INVALID, "frame " + std::to_string(f) + " is not device memory of device " + std::to_string(c->cfg.device_id) +
                                        " (or runs past the end of its allocation)");
 }
+
+// the RGB24 frames of the entries that came before vp_image: {{data, NULL}, {3 w, 0}, h, w, RGB24, 0}
+std::vector<vp_image> rgb_images(const vp_frame* frames, int n_frames) {
+    std::vector<vp_image> v(frames && n_frames > 0 ? (size_t)n_frames : 0);
+    for (size_t f = 0; f < v.size(); ++f) v[f] = vp_image{{frames[f].data, nullptr}, {(int64_t)frames[f].w * 3, 0}, frames[f].h, frames[f].w, VP_PIX_RGB24, 0};
+    return v;
+}
+const vp_image* table_ptr(const std::vector<vp_image>& v) { return v.empty() ? nullptr : v.data(); }   // (a temporary lives to the end of the call it is passed to)
 
 // A grow-only device buffer of the handle (*buf, *cap bytes) holds at least `bytes`: the larger one is allocated first, then the smaller one is
 // released (never shrunk: growing inputs must not grow device memory without bound), so a failed allocation leaves the handle usable
@@ -180,7 +195,21 @@ int run_mix_chunk(vp_ctx* c, const MixPlan& p, const void* d_src, int fmt, int n
 
 namespace vpi {   // shared with debug_taps.hip (vp_dbg_crop_prep) and group.hip (submit_impl)
 
-int frame_plan(const vp_frame* frames, int n_frames, const int32_t* p9, int n, int32_t* bands, std::string* why) {
+int image_check(const vp_image& im, int f, std::string* why) {
+    auto bad = [&](const std::string& m) { if (why) *why = "frame " + std::to_string(f) + " " + m; return VP_ERR_INVALID; };
+    if (im.format < 0 || im.format >= vp::PIX_FORMATS) return bad("has an unknown pixel format " + std::to_string(im.format));
+    const bool nv12 = im.format == vp::PIX_NV12;
+    if (nv12 && (im.matrix < 0 || im.matrix >= vp::YUV_MATRICES)) return bad("has an unknown YUV matrix " + std::to_string(im.matrix));
+    if (im.pitch[0] < 0 || (nv12 && im.pitch[1] < 0)) return bad("has a negative pitch");
+    if (im.w > 0 && im.pitch[0] < vp::plane_row_bytes(im.format, 0, im.w))
+        return bad("has pitch[0] " + std::to_string(im.pitch[0]) + " below its " + std::to_string(vp::plane_row_bytes(im.format, 0, im.w)) + " row bytes");
+    if (nv12 && !im.plane[1]) return bad("is NV12 without a UV plane (plane[1] is null)");
+    if (nv12 && im.w > 0 && im.pitch[1] < vp::plane_row_bytes(im.format, 1, im.w))
+        return bad("has pitch[1] " + std::to_string(im.pitch[1]) + " below the " + std::to_string(vp::plane_row_bytes(im.format, 1, im.w)) + " bytes of a UV row (2 ceil(w / 2))");
+    return VP_OK;
+}
+
+int image_plan(const vp_image* frames, int n_frames, const int32_t* p9, int n, int32_t* bands, std::string* why) {
     auto bad = [&](const std::string& m) { if (why) *why = m; return VP_ERR_INVALID; };
     if (n < 0) return bad("negative crop count");
     if (n > 0 && n_frames <= 0) return bad("crops given but no frames");
@@ -192,9 +221,13 @@ int frame_plan(const vp_frame* frames, int n_frames, const int32_t* p9, int n, i
         const int f = p[0];
         const std::string at = "crop " + std::to_string(i) + ": ";
         if (f < 0 || f >= n_frames) return bad(at + "frame index " + std::to_string(f) + " outside [0, " + std::to_string(n_frames) + ")");
-        const vp_frame& fr = frames[f];
-        if (!fr.data) return bad(at + "frame " + std::to_string(f) + " has no data");
+        const vp_image& fr = frames[f];
+        if (!fr.plane[0]) return bad(at + "frame " + std::to_string(f) + " has no data");
         if (fr.h <= 0 || fr.w <= 0) return bad(at + "frame " + std::to_string(f) + " has a non-positive size");
+        if (hi[f] < 0) {   // the first crop that names the frame: its layout
+            std::string w;
+            if (image_check(fr, f, &w)) return bad(at + w);
+        }
         const int64_t x0 = p[1], y0 = p[2], cw = p[3], ch = p[4], left = p[5], top = p[6], pw = p[7], ph = p[8];
         if (cw <= 0 || ch <= 0 || pw <= 0 || ph <= 0) return bad(at + "non-positive crop or canvas size");
         if (x0 < 0 || y0 < 0 || x0 + cw > fr.w || y0 + ch > fr.h || left < 0 || top < 0 || left + cw > pw || top + ch > ph)
@@ -210,41 +243,66 @@ int frame_plan(const vp_frame* frames, int n_frames, const int32_t* p9, int n, i
     return VP_OK;
 }
 
-int stage_frames(vp_ctx* c, const vp_frame* frames, int n_frames, bool on_device, const int32_t* p9, int n, const int32_t* bands,
+int stage_frames(vp_ctx* c, const vp_image* frames, int n_frames, bool on_device, const int32_t* p9, int n, const int32_t* bands,
                  std::vector<vp::CropRec>& recs) {
-    std::vector<const uint8_t*> row0_ptr(n_frames, nullptr);   // row bands[2 f] of frame f, where the kernel reads it
+    // plane p of frame f at the first row of its band, where the kernel reads it: Y / RGB row bands[2 f], UV row bands[2 f] >> 1
+    std::vector<const uint8_t*> row0_ptr((size_t)n_frames * 2, nullptr);
+    auto band_rows = [&](int f, int p, int64_t* r0, int64_t* r1) {   // rows [*r0, *r1) of plane p the band covers
+        *r0 = p ? bands[2 * f] >> 1 : bands[2 * f];
+        *r1 = p ? ((int64_t)bands[2 * f + 1] + 1) >> 1 : bands[2 * f + 1];
+    };
+    auto planes = [&](int f) { return frames[f].format == vp::PIX_NV12 ? 2 : 1; };
     if (on_device) {
         for (int f = 0; f < n_frames; ++f) {
             if (bands[2 * f] == bands[2 * f + 1]) continue;
             if (const int rc = check_device_frame(c, frames[f], f)) return rc;
-            row0_ptr[f] = frames[f].data + (size_t)bands[2 * f] * frames[f].w * 3;
+            for (int p = 0; p < planes(f); ++p) {
+                int64_t r0, r1;
+                band_rows(f, p, &r0, &r1);
+                row0_ptr[2 * f + p] = frames[f].plane[p] + (size_t)r0 * frames[f].pitch[p];
+            }
         }
     } else {
-        std::vector<size_t> off(n_frames, 0);
+        // the band of a plane keeps the caller's pitch: (rows - 1) * pitch + row bytes, never a byte past the last pixel
+        auto band_bytes = [&](int f, int p) {
+            int64_t r0, r1;
+            band_rows(f, p, &r0, &r1);
+            return (size_t)(r1 - r0 - 1) * (size_t)frames[f].pitch[p] + (size_t)vp::plane_row_bytes(frames[f].format, p, frames[f].w);
+        };
+        std::vector<size_t> off((size_t)n_frames * 2, 0);
         size_t total = 0;
         for (int f = 0; f < n_frames; ++f) {
             if (bands[2 * f] == bands[2 * f + 1]) continue;
-            off[f] = total;
-            total += ((size_t)(bands[2 * f + 1] - bands[2 * f]) * frames[f].w * 3 + 255) & ~(size_t)255;
+            for (int p = 0; p < planes(f); ++p) {
+                off[2 * f + p] = total;
+                total += (band_bytes(f, p) + 255) & ~(size_t)255;
+            }
         }
         if (const int rc = grow_buffer(c, &c->frame_stage, &c->frame_cap, total, "frame staging arena")) return rc;
-        for (int f = 0; f < n_frames; ++f) {   // ONE copy per frame with crops: its row band, full width
+        for (int f = 0; f < n_frames; ++f) {   // ONE copy per plane of a frame with crops: its row band, full width
             if (bands[2 * f] == bands[2 * f + 1]) continue;
-            const size_t pitch = (size_t)frames[f].w * 3;
-            HIPCHK(c, hipMemcpyAsync(c->frame_stage + off[f], frames[f].data + (size_t)bands[2 * f] * pitch,
-                                     (size_t)(bands[2 * f + 1] - bands[2 * f]) * pitch, hipMemcpyHostToDevice, c->stream));
-            row0_ptr[f] = c->frame_stage + off[f];
+            for (int p = 0; p < planes(f); ++p) {
+                int64_t r0, r1;
+                band_rows(f, p, &r0, &r1);
+                HIPCHK(c, hipMemcpyAsync(c->frame_stage + off[2 * f + p], frames[f].plane[p] + (size_t)r0 * frames[f].pitch[p], band_bytes(f, p), hipMemcpyHostToDevice,
+                                         c->stream));
+                row0_ptr[2 * f + p] = c->frame_stage + off[2 * f + p];
+            }
         }
     }
     recs.resize(n);
     for (int i = 0; i < n; ++i) {
         const int32_t* p = p9 + 9 * (size_t)i;
         const int f = p[0];
-        const int64_t pitch = (int64_t)frames[f].w * 3;
+        const vp_image& im = frames[f];
+        const bool nv12 = im.format == vp::PIX_NV12;
         vp::CropRec& r = recs[i];
-        r.src = row0_ptr[f] + (size_t)(p[2] - bands[2 * f]) * pitch + (size_t)p[1] * 3;
-        r.pitch = pitch;
+        r.src = row0_ptr[2 * f] + (size_t)(p[2] - bands[2 * f]) * im.pitch[0] + (size_t)p[1] * (nv12 ? 1 : 3);
+        r.pitch = im.pitch[0];
         r.cw = p[3]; r.ch = p[4]; r.left = p[5]; r.top = p[6]; r.pw = p[7]; r.ph = p[8];
+        r.src1 = nv12 ? row0_ptr[2 * f + 1] + (size_t)((p[2] >> 1) - (bands[2 * f] >> 1)) * im.pitch[1] + (size_t)(p[1] >> 1) * 2 : nullptr;
+        r.pitch1 = nv12 ? im.pitch[1] : 0;
+        r.format = im.format; r.matrix = im.matrix; r.oy = p[2] & 1; r.ox = p[1] & 1;
     }
     return VP_OK;
 }
@@ -557,12 +615,12 @@ int vp_infer_experts_device_stream(vp_handle c, const void* d_crops, int32_t fmt
 }
 
 // vp_infer_frames (mixed == false) and vp_infer_frames_experts (a flag, not a null test: null ids are an error of the latter)
-static int frames_impl(vp_ctx* c, const char* who, const vp_frame* frames, int32_t n_frames, int32_t on_device, const int32_t* p9, int32_t n, const int32_t* expert_ids,
+static int frames_impl(vp_ctx* c, const char* who, const vp_image* frames, int32_t n_frames, int32_t on_device, const int32_t* p9, int32_t n, const int32_t* expert_ids,
                        bool mixed, float* out) {
     if (!c) return VP_ERR_INVALID;
     std::vector<int32_t> bands((size_t)(n_frames > 0 ? n_frames : 0) * 2);
     std::string why;
-    if (frame_plan(frames, n_frames, p9, n, bands.data(), &why)) return fail(c, VP_ERR_INVALID, why);   // before any copy or launch
+    if (image_plan(frames, n_frames, p9, n, bands.data(), &why)) return fail(c, VP_ERR_INVALID, why);   // before any copy or launch
     int rc = check_ready(c, VP_INPUT_U8_NHWC, n, p9, out);
     if (rc || (mixed && (rc = mix_ready(c, who, n, expert_ids))) || n == 0) return rc;
     std::vector<vp::CropRec> recs;
@@ -592,11 +650,15 @@ static int frames_impl(vp_ctx* c, const char* who, const vp_frame* frames, int32
 
 int vp_infer_frames_experts(vp_handle c, const vp_frame* frames, int32_t n_frames, int32_t on_device, const int32_t* p9, int32_t n, const int32_t* expert_ids,
                             float* out) {
-    return frames_impl(c, "vp_infer_frames_experts", frames, n_frames, on_device, p9, n, expert_ids, true, out);
+    return frames_impl(c, "vp_infer_frames_experts", table_ptr(rgb_images(frames, n_frames)), n_frames, on_device, p9, n, expert_ids, true, out);
 }
 
 int vp_infer_frames(vp_handle c, const vp_frame* frames, int32_t n_frames, int32_t on_device, const int32_t* p9, int32_t n, float* out) {
-    return frames_impl(c, "vp_infer_frames", frames, n_frames, on_device, p9, n, nullptr, false, out);
+    return frames_impl(c, "vp_infer_frames", table_ptr(rgb_images(frames, n_frames)), n_frames, on_device, p9, n, nullptr, false, out);
+}
+
+int vp_infer_images(vp_handle c, const vp_image* images, int32_t n_images, int32_t on_device, const int32_t* p9, int32_t n, const int32_t* expert_ids, float* out) {
+    return frames_impl(c, "vp_infer_images", images, n_images, on_device, p9, n, expert_ids, expert_ids != nullptr, out);
 }
 
 // the one-frame case of vp_infer_frames
@@ -615,13 +677,20 @@ int vp_infer_frame(vp_handle c, const uint8_t* frame, int32_t fh, int32_t fw, co
 
 int vp_dbg_frame_plan(const vp_frame* frames, int32_t n_frames, const int32_t* params9, int32_t n, int32_t* bands) {
     std::string why;
-    const int rc = frame_plan(frames, n_frames, params9, n, bands, &why);
+    const int rc = image_plan(table_ptr(rgb_images(frames, n_frames)), n_frames, params9, n, bands, &why);
+    if (rc) g_create_error = why;
+    return rc;
+}
+
+int vp_dbg_image_plan(const vp_image* images, int32_t n_images, const int32_t* params9, int32_t n, int32_t* bands) {
+    std::string why;
+    const int rc = image_plan(images, n_images, params9, n, bands, &why);
     if (rc) g_create_error = why;
     return rc;
 }
 
 // vp_infer_boxes_stream (expert_ids == null) and vp_infer_boxes_experts_stream
-static int boxes_impl(vp_ctx* c, const char* who, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx,
+static int boxes_impl(vp_ctx* c, const char* who, const vp_image* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx,
                       int32_t n, int32_t pad, const int32_t* expert_ids, bool mixed, float* d_out, int32_t* d_crop_params, int32_t* d_status, void* caller_stream) {
     if (!c) return VP_ERR_INVALID;
     // every host argument is checked before anything is enqueued
@@ -630,6 +699,8 @@ static int boxes_impl(vp_ctx* c, const char* who, const vp_frame* frames, int32_
     for (size_t f = 0; f < hw.size() / 2; ++f) { hw[2 * f] = frames[f].h; hw[2 * f + 1] = frames[f].w; }
     std::string why;
     if (box_args(n_frames, hw.data(), 2, row_stride, n, pad, &why)) return fail(c, VP_ERR_INVALID, why);
+    for (int f = 0; f < n_frames && n > 0; ++f)   // the layout of every frame of the table
+        if (image_check(frames[f], f, &why)) return fail(c, VP_ERR_INVALID, why);
     int rc = check_ready(c, VP_INPUT_U8_NHWC, n, d_xyxy, d_out, false);
     if (rc || (mixed && (rc = mix_ready(c, who, n, expert_ids))) || n == 0) return rc;
     for (int f = 0; f < n_frames; ++f)   // every frame of the table: which ones the boxes name is on the device
@@ -647,7 +718,10 @@ static int boxes_impl(vp_ctx* c, const char* who, const vp_frame* frames, int32_
                 vp::BoxFrames bf;
                 std::memset(&bf, 0, sizeof(bf));
                 bf.f0 = f0; bf.count = std::min(n_frames - f0, vp::BOX_FRAMES_PER_LAUNCH); bf.n_frames = n_frames;
-                for (int j = 0; j < bf.count; ++j) { bf.data[j] = frames[f0 + j].data; bf.h[j] = frames[f0 + j].h; bf.w[j] = frames[f0 + j].w; }
+                for (int j = 0; j < bf.count; ++j) {
+                    const vp_image& im = frames[f0 + j];
+                    bf.fr[j] = vp::BoxFrame{{im.plane[0], im.plane[1]}, {im.pitch[0], im.pitch[1]}, im.h, im.w, im.format, im.matrix};
+                }
                 LAUNCH(c, VP_PROF_IM2COL, 0.0, 64.0 * nb,
                        vp::box_geometry_launch(bf, d_xyxy + (size_t)off * row_stride, row_stride, d_frame_idx ? d_frame_idx + off : nullptr, nb, pad,
                                                (const uint8_t*)c->zero, c->crecs, c->wh_stage, c->box_aux,
@@ -663,13 +737,19 @@ static int boxes_impl(vp_ctx* c, const char* who, const vp_frame* frames, int32_
 
 int vp_infer_boxes_stream(vp_handle c, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx,
                           int32_t n, int32_t pad, float* d_out, int32_t* d_crop_params, int32_t* d_status, void* caller_stream) {
-    return boxes_impl(c, "vp_infer_boxes_stream", frames, n_frames, d_xyxy, row_stride, d_frame_idx, n, pad, nullptr, false, d_out, d_crop_params, d_status, caller_stream);
+    return boxes_impl(c, "vp_infer_boxes_stream", table_ptr(rgb_images(frames, n_frames)), n_frames, d_xyxy, row_stride, d_frame_idx, n, pad, nullptr, false, d_out, d_crop_params, d_status, caller_stream);
 }
 
 int vp_infer_boxes_experts_stream(vp_handle c, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx,
                                   int32_t n, int32_t pad, const int32_t* expert_ids, float* d_out, int32_t* d_crop_params, int32_t* d_status, void* caller_stream) {
-    return boxes_impl(c, "vp_infer_boxes_experts_stream", frames, n_frames, d_xyxy, row_stride, d_frame_idx, n, pad, expert_ids, true, d_out, d_crop_params, d_status,
-                      caller_stream);
+    return boxes_impl(c, "vp_infer_boxes_experts_stream", table_ptr(rgb_images(frames, n_frames)), n_frames, d_xyxy, row_stride, d_frame_idx, n, pad, expert_ids, true, d_out,
+                      d_crop_params, d_status, caller_stream);
+}
+
+int vp_infer_boxes_images_stream(vp_handle c, const vp_image* images, int32_t n_images, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx, int32_t n,
+                                 int32_t pad, const int32_t* expert_ids, float* d_out, int32_t* d_crop_params, int32_t* d_status, void* caller_stream) {
+    return boxes_impl(c, "vp_infer_boxes_images_stream", images, n_images, d_xyxy, row_stride, d_frame_idx, n, pad, expert_ids, expert_ids != nullptr, d_out, d_crop_params,
+                      d_status, caller_stream);
 }
 
 int vp_dbg_box_geometry(const float* xyxy, int32_t row_stride, const int32_t* frame_idx, const int32_t* frame_hw, int32_t n_frames, int32_t n, int32_t pad,

@@ -202,21 +202,30 @@ hipError_t flip_merge_launch(float* hm, const float* hm_flipped, const int32_t* 
 hipError_t im2col_twin_launch(int dtype, const void* crops, int input_format, uint16_t* out, int B, int n_src, hipStream_t s);
 void flip_twin_layout(int bo, int n_src, int* src, int* mirror);   // HOST: the source crop of output crop bo and whether it is mirrored (the kernel's own index function)
 
-// one crop of a frame: src = the frame's pixel (y0, x0) (in a staged row band or in the caller's device frame), pitch = bytes per frame row;
-// the crop is [ch, cw] pixels, placed at (top, left) of a zero [ph, pw] canvas (vp_infer_frames builds these on the host)
+// one crop of a frame: src = plane 0 at the frame's pixel (y0, x0) (in a staged row band or in the caller's device frame), pitch = bytes per row of that plane;
+// the crop is [ch, cw] pixels, placed at (top, left) of a zero [ph, pw] canvas (vp_infer_frames builds these on the host).  format / matrix (pixfmt.h) say how a
+// source pixel becomes RGB8.  NV12: src1 = the UV pair of pixel (y0, x0), i.e. plane 1 at chroma (y0 >> 1, x0 >> 1), pitch1 its row bytes, and (oy, ox) = the
+// parities of (y0, x0): crop pixel (yy, xx) reads the pair ((oy + yy) >> 1, (ox + xx) >> 1) behind src1 = the frame's ((y0 + yy) >> 1, (x0 + xx) >> 1)
 struct CropRec {
     const uint8_t* src;
     int64_t pitch;
     int32_t cw, ch, left, top, pw, ph;
+    const uint8_t* src1;
+    int64_t pitch1;
+    int32_t format, matrix, oy, ox;
 };
-// recs: device CropRec [n] -> crops u8 [n,256,192,3]
+// recs: device CropRec [n] -> crops u8 [n,256,192,3] RGB
 hipError_t crop_resize_launch(const CropRec* recs, uint8_t* out, int n, hipStream_t s);
 
-// vp_infer_boxes_stream (boxes.hip): frames [f0, f0 + count) of the call's table, passed by kernel argument (2 KiB)
-constexpr int BOX_FRAMES_PER_LAUNCH = 128;
+// vp_infer_boxes_stream (boxes.hip): frames [f0, f0 + count) of the call's table, passed by kernel argument (3 KiB: 64 entries of 48 bytes; 128 would pass the 4 KiB of a launch)
+constexpr int BOX_FRAMES_PER_LAUNCH = 64;
+struct BoxFrame {   // vp_image's fields
+    const uint8_t* plane[2];
+    int64_t pitch[2];
+    int32_t h, w, format, matrix;
+};
 struct BoxFrames {
-    const uint8_t* data[BOX_FRAMES_PER_LAUNCH];
-    int32_t h[BOX_FRAMES_PER_LAUNCH], w[BOX_FRAMES_PER_LAUNCH];
+    BoxFrame fr[BOX_FRAMES_PER_LAUNCH];
     int32_t f0, count, n_frames;
 };
 // boxes xyxy (row i at xyxy + i * row_stride) + frame index [n] (NULL: frame 0) -> crop records, decode sizes wh [n, 2] = (pw, ph),

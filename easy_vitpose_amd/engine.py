@@ -14,6 +14,7 @@ import dataclasses
 from . import _capi as capi
 from . import moe
 from .configs import HM_H, HM_W, IMG_H, IMG_W, ModelShape
+from .cropprep import PIX_FORMATS, YUV_MATRIX_IDS, Frame
 
 
 def _as_f32_numpy(v) -> np.ndarray:
@@ -349,51 +350,69 @@ class VitPoseHip:
         padded-crop pixels.  `datasets` (a ViTPose+ handle: one name or expert index per crop, as in `infer_mixed`): a dataset per crop in the
         same call (vp_infer_frames_experts) -- returns ``(out, k)`` as `infer_mixed` does, ``out`` [n, Kmax, 3] with row i's first ``k[i]``
         joints filled, bit for bit `infer_mixed` on the host-prepared crops.  `frames`: numpy uint8 [H, W, 3] arrays (host path: one upload of the row band each frame's crops cover),
-        or contiguous torch uint8 CUDA tensors [H, W, 3] on this handle's device (read in place, once torch's current stream on that
-        device has been synchronised).  A list that mixes the two raises TypeError."""
-        frames = list(frames)
+        or torch uint8 CUDA tensors [H, W, 3] on this handle's device (read in place, once torch's current stream on that
+        device has been synchronised), or `Frame` objects (`Frame.rgb / bgr / nv12`: BGR, NV12 surfaces, pitched planes; vp_infer_images) -- formats may differ
+        within a call, and the result has the bits of the call on `cropprep.to_rgb` of every frame.  A bare array or tensor is RGB; rows at a pitch (strides
+        (pitch, 3, 1)) pass in place.  A list that mixes host and device frames raises TypeError."""
         params = np.ascontiguousarray(params, dtype=np.int32).reshape(-1, 9)
         n = params.shape[0]
-        is_tensor = [hasattr(f, 'data_ptr') for f in frames]
-        if any(is_tensor) and not all(is_tensor):
+        frames = [self._as_frame(f, i) for i, f in enumerate(frames)]
+        on_dev = [f.on_device for f in frames]
+        if any(on_dev) and not all(on_dev):
             raise TypeError('frames: all numpy arrays (host) or all torch CUDA tensors (device), not a mix')
-        on_device = bool(frames) and all(is_tensor)
-        table = (capi.vp_frame * max(len(frames), 1))()
-        keep = []
-        for i, f in enumerate(frames):
-            if on_device:
-                import torch
-                if not (f.is_cuda and f.dtype == torch.uint8 and f.is_contiguous()):
-                    raise TypeError('device frames must be contiguous torch uint8 CUDA tensors')
-                if f.device.index != self.device_id:
-                    raise ValueError(f'frame {i} lives on {f.device}, the handle on cuda:{self.device_id}')
-                ptr = f.data_ptr()
-            else:
-                f = np.ascontiguousarray(f)
-                if f.dtype != np.uint8:
-                    raise TypeError(f'frame {i}: uint8 expected, got {f.dtype}')
-                keep.append(f)
-                ptr = f.ctypes.data
-            if f.ndim != 3 or f.shape[2] != 3:
-                raise ValueError(f'frame {i}: [H, W, 3] expected, got {tuple(f.shape)}')
-            table[i] = capi.vp_frame(ptr, f.shape[0], f.shape[1])
+        on_device = bool(frames) and all(on_dev)
+        table = self._image_table(frames)
         ids = None if datasets is None else self._dataset_ids(datasets, n)
         out = np.empty((n, self.K if ids is None else self.Kmax, 3), dtype=np.float32)
         if n and on_device:
             import torch
             torch.cuda.current_stream(torch.device('cuda', self.device_id)).synchronize()   # the frames are complete before the library reads them
-        if ids is not None:
-            if n:
-                capi.check(self.lib.vp_infer_frames_experts(self._h, table, len(frames), int(on_device), params.ctypes.data, n, ids.ctypes.data,
-                                                            out.ctypes.data), self._h)
-            return out, self.dataset_k(ids)
         if n:
-            capi.check(self.lib.vp_infer_frames(self._h, table, len(frames), int(on_device), params.ctypes.data, n, out.ctypes.data), self._h)
-        return out
+            capi.check(self.lib.vp_infer_images(self._h, table, len(frames), int(on_device), params.ctypes.data, n, None if ids is None else ids.ctypes.data,
+                                                out.ctypes.data), self._h)
+        return out if ids is None else (out, self.dataset_k(ids))
+
+    @staticmethod
+    def _as_frame(f, i: int) -> Frame:
+        """entry i of a frame list as a `Frame`: a bare [H, W, 3] array or tensor means RGB.  Rows at a pitch (strides (pitch, 3, 1)) pass in place; any other
+        host layout is copied, any other device layout refused."""
+        if isinstance(f, Frame):
+            return f
+        try:
+            if hasattr(f, 'data_ptr'):
+                if not f.is_cuda:
+                    raise TypeError('device frames must be torch uint8 CUDA tensors')
+                return Frame.rgb(f)
+            f = np.asarray(f)
+            if f.dtype != np.uint8:
+                raise TypeError(f'uint8 expected, got {f.dtype}')
+            if f.ndim == 3 and f.shape[2] == 3:
+                try:
+                    return Frame.rgb(f)
+                except ValueError:
+                    return Frame.rgb(np.ascontiguousarray(f))   # reversed channels, a column step, ...: not a vp_image
+            return Frame.rgb(f)
+        except (TypeError, ValueError) as e:
+            raise type(e)(f'frame {i}: {e}') from None
+
+    def _image_table(self, frames, device_only: bool = False):
+        """the vp_image table of `frames` (Frame objects; they keep the planes alive)"""
+        table = (capi.vp_image * max(len(frames), 1))()
+        for i, f in enumerate(frames):
+            if device_only and not f.on_device:
+                raise TypeError(f'frame {i}: torch uint8 CUDA tensors expected')
+            if f.on_device:
+                for p in f.planes:
+                    if p.device.index != self.device_id:
+                        raise ValueError(f'frame {i} lives on {p.device}, the handle on cuda:{self.device_id}')
+            p0, p1 = f.pointers()
+            table[i] = capi.vp_image((C.c_void_p * 2)(p0, p1), (C.c_int64 * 2)(*f.pitch), f.h, f.w, PIX_FORMATS[f.format], YUV_MATRIX_IDS[f.matrix])
+        return table
 
     def infer_boxes(self, frames, boxes, frame_index=None, pad: int = 10, out=None, crop_params: bool = False, status: bool = False, datasets=None):
         """Detector boxes on device frames -> keypoints in FRAME pixels, all on the device (vp_infer_boxes_stream, contract in
-        include/vitpose_hip.h).  `frames`: contiguous torch uint8 CUDA tensors [H, W, 3] on this handle's device; `boxes`: float32 CUDA
+        include/vitpose_hip.h).  `frames`: torch uint8 CUDA tensors [H, W, 3] on this handle's device (RGB; rows may be pitched: a view of a wider buffer),
+        or `Frame` objects over device planes (`Frame.bgr`, `Frame.nv12`: vp_infer_boxes_images_stream), read in place; `boxes`: float32 CUDA
         [n, >= 4] (x1, y1, x2, y2, ...) with unit column stride, e.g. a detector's [n, 6] output as it is; `frame_index`: int32 CUDA [n]
         (None: every box on frame 0); `pad`: pixels added on every side before clipping.  Returns `out` float32 [n, K, 3] (allocated
         when not given), plus int32 [n, 9] crop params (cropprep.frames_crop_params rows) and int32 [n] status (0 ok, 1 bad frame index,
@@ -404,16 +423,8 @@ class VitPoseHip:
         crop params and status are the plain call's."""
         import torch
         dev = torch.device('cuda', self.device_id)
-        frames = list(frames)
-        table = (capi.vp_frame * max(len(frames), 1))()
-        for i, f in enumerate(frames):
-            if not (isinstance(f, torch.Tensor) and f.is_cuda and f.dtype == torch.uint8 and f.is_contiguous()):
-                raise TypeError(f'frame {i}: a contiguous torch uint8 CUDA tensor expected')
-            if f.device != dev:
-                raise ValueError(f'frame {i} lives on {f.device}, the handle on {dev}')
-            if f.ndim != 3 or f.shape[2] != 3:
-                raise ValueError(f'frame {i}: [H, W, 3] expected, got {tuple(f.shape)}')
-            table[i] = capi.vp_frame(f.data_ptr(), f.shape[0], f.shape[1])
+        frames = [self._as_frame(f, i) for i, f in enumerate(frames)]
+        table = self._image_table(frames, device_only=True)
         if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda and boxes.dtype == torch.float32):
             raise TypeError('boxes: a float32 torch CUDA tensor expected')
         if boxes.device != dev:
@@ -439,13 +450,9 @@ class VitPoseHip:
         cp = torch.empty((n, 9), dtype=torch.int32, device=dev) if crop_params else None
         st = torch.empty((n,), dtype=torch.int32, device=dev) if status else None
         cs = torch.cuda.current_stream(dev).cuda_stream
-        if ids is not None:
-            capi.check(self.lib.vp_infer_boxes_experts_stream(self._h, table, len(frames), boxes.data_ptr(), row_stride, fip, n, int(pad), ids.ctypes.data,
-                                                              out.data_ptr(), None if cp is None else cp.data_ptr(), None if st is None else st.data_ptr(),
-                                                              cs), self._h)
-        else:
-            capi.check(self.lib.vp_infer_boxes_stream(self._h, table, len(frames), boxes.data_ptr(), row_stride, fip, n, int(pad), out.data_ptr(),
-                                                      None if cp is None else cp.data_ptr(), None if st is None else st.data_ptr(), cs), self._h)
+        capi.check(self.lib.vp_infer_boxes_images_stream(self._h, table, len(frames), boxes.data_ptr(), row_stride, fip, n, int(pad),
+                                                         None if ids is None else ids.ctypes.data, out.data_ptr(), None if cp is None else cp.data_ptr(),
+                                                         None if st is None else st.data_ptr(), cs), self._h)
         if cp is None and st is None:
             return out
         return (out,) + tuple(t for t in (cp, st) if t is not None)
@@ -542,6 +549,19 @@ def crop_prep_device(frame: np.ndarray, params: np.ndarray, device_id: int = 0) 
     out = np.empty((len(params), IMG_H, IMG_W, 3), dtype=np.uint8)
     capi.check(lib.vp_dbg_crop_prep(device_id, frame.ctypes.data, frame.shape[0], frame.shape[1], params.ctypes.data,
                                     len(params), out.ctypes.data))
+    return out
+
+
+def crop_prep_image(frame: Frame, params: np.ndarray, device_id: int = 0) -> np.ndarray:
+    """The device crop/pad/resize kernel alone on one host `Frame` of any layout (vp_dbg_crop_prep_image): uint8 RGB [n, 256, 192, 3]."""
+    lib = capi.load_library()
+    if frame.on_device:
+        raise TypeError('crop_prep_image takes a frame whose planes are on the host')
+    params = np.ascontiguousarray(params, dtype=np.int32).reshape(-1, 8)
+    out = np.empty((len(params), IMG_H, IMG_W, 3), dtype=np.uint8)
+    p0, p1 = frame.pointers()
+    im = capi.vp_image((C.c_void_p * 2)(p0, p1), (C.c_int64 * 2)(*frame.pitch), frame.h, frame.w, PIX_FORMATS[frame.format], YUV_MATRIX_IDS[frame.matrix])
+    capi.check(lib.vp_dbg_crop_prep_image(device_id, C.byref(im), params.ctypes.data, len(params), out.ctypes.data))
     return out
 
 

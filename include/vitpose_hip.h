@@ -232,7 +232,7 @@ VP_API int vp_infer_frames(vp_handle h, const vp_frame* frames, int32_t n_frames
  * checked in that order.  A row with a non-zero status reads no frame, gets all-zero keypoints and an all-zero d_crop_params row.
  * Ordering as vp_infer_device_stream: batches of <= 16 crops (that fit max_batch) run on caller_stream itself, larger ones on the handle's
  * stream fenced with two events; the next call on any stream, vp_synchronize and vp_destroy order themselves behind the work.  n > max_batch
- * runs in max_batch chunks.  Per chunk: the box kernel (launched once per 128 frames of the table, which travels by kernel argument) and the crop
+ * runs in max_batch chunks.  Per chunk: the box kernel (launched once per 64 frames of the table, which travels by kernel argument) and the crop
  * kernel run eagerly, then the forward, decode and offset kernel (a replayed hipGraph for chunks of <= 16 crops).  The call never blocks the
  * host: no stream / device / event synchronisation and no copy from host memory; its device buffers are sized by max_batch and allocated on the
  * first call.  The one exception is vp_infer_device_stream's: when a fifth distinct small chunk (size, output pointer) evicts a cached graph,
@@ -355,6 +355,56 @@ VP_API int vp_infer_frames_experts(vp_handle h, const vp_frame* frames, int32_t 
 VP_API int vp_infer_boxes_experts_stream(vp_handle h, const vp_frame* frames, int32_t n_frames, const float* d_xyxy, int32_t row_stride,
                                          const int32_t* d_frame_idx, int32_t n, int32_t pad, const int32_t* expert_ids, float* d_out,
                                          int32_t* d_crop_params, int32_t* d_status, void* caller_stream);
+/* Frames as a video pipeline holds them: NV12 decoder surfaces, BGR capture buffers, pitched views (an ROI, one frame of a batch buffer).  vp_image describes
+ * one frame by plane pointers and row pitches, and the pixel fetch of the crop kernel converts each SOURCE pixel to RGB8 before any interpolation -- the
+ * interpolation arithmetic is the RGB route's.  The result of either entry below is therefore, bit for bit, what vp_infer_frames / vp_infer_boxes_stream
+ * return on the same frame converted on the host (easy_vitpose_amd/cropprep.py to_rgb), without the full-frame conversion pass: only the pixels under the
+ * boxes are read.
+ *   NV12 -> RGB (int32, arithmetic shifts; one definition in csrc/pixfmt.h):  y' = max(Y - yoff, 0), u' = U - 128, v' = V - 128,
+ *     R = clip255((cy y' + crv v' + 2^19) >> 20),  G = clip255((cy y' + cgu u' + cgv v' + 2^19) >> 20),  B = clip255((cy y' + cbu u' + 2^19) >> 20)
+ *     matrix            yoff  cy       crv      cgu      cgv      cbu
+ *     VP_YUV_BT601      16    1220542  1673527  -409993  -852492  2116026    (OpenCV's COLOR_YUV2RGB_NV12 constants; parity against that binary is unpinned)
+ *     VP_YUV_BT709      16    1220945  1879825  -223607  -558796  2215014
+ *     VP_YUV_BT601_FULL 0     1048576  1470104  -360853  -748826  1858077
+ *   Chroma is replicated, not interpolated: pixel (y, x) reads the UV pair (y >> 1, x >> 1).  Odd h or w is legal (the ceil sizes keep that index valid).
+ *   The two planes are separate pointers: one allocation (a decoder surface, UV at base + pitch * aligned_h) or two.  Not supported: 10-bit P010 / P016,
+ *   planar I420, RGBA, interpolated chroma.
+ * vp_infer_images: the contract of vp_infer_frames (expert_ids == NULL: the handle's active expert) or of vp_infer_frames_experts (expert_ids != NULL) --
+ *   chunks of max_batch, the staging (host frames: ONE upload per plane per frame of the row band its crops cover, Y rows [lo, hi) and UV rows
+ *   [lo >> 1, (hi + 1) >> 1), (rows - 1) * pitch + row bytes each, never a byte past the last pixel), the host waits, the refusals.
+ * vp_infer_boxes_images_stream: the contract of vp_infer_boxes_stream (expert_ids == NULL) or of vp_infer_boxes_experts_stream: no host synchronisation,
+ *   the stream ordering, the status codes; the box kernel is launched once per 64 frames of the table.
+ * Frames of one call may differ in format and matrix.  Device planes are checked one by one before anything is enqueued: (plane rows - 1) * pitch + row
+ * bytes inside one allocation of the handle's device.  VP_ERR_INVALID on top of the plain entries' refusals (vp_dbg_image_plan; the message names the crop
+ * or the frame): an unknown format or matrix, a negative pitch, pitch[0] below the row bytes, NV12 with a NULL plane[1] or pitch[1] < 2 ceil(w / 2).
+ * vp_infer_frame, vp_infer_frames, vp_infer_frames_experts, vp_infer_boxes_stream and vp_infer_boxes_experts_stream are these entries on
+ * vp_image{{data, NULL}, {3 w, 0}, h, w, VP_PIX_RGB24, 0}.  Library builds that carry them define VP_HAS_IMAGE_ENTRIES. */
+#define VP_HAS_IMAGE_ENTRIES 1
+#define VP_PIX_RGB24 0   /* plane[0]: R,G,B bytes, pitch[0] >= 3 w                      */
+#define VP_PIX_BGR24 1   /* plane[0]: B,G,R bytes, pitch[0] >= 3 w                      */
+#define VP_PIX_NV12  2   /* plane[0]: Y [h, w], pitch[0] >= w; plane[1]: U,V pairs
+                            [ceil(h/2), ceil(w/2)], pitch[1] >= 2 ceil(w/2)            */
+#define VP_YUV_BT601      0   /* limited range (Y 16..235) */
+#define VP_YUV_BT709      1   /* limited range             */
+#define VP_YUV_BT601_FULL 2   /* full range (JPEG / MJPEG) */
+typedef struct vp_image {
+    const uint8_t* plane[2];
+    int64_t pitch[2];      /* bytes per row of each plane */
+    int32_t h, w;
+    int32_t format;        /* VP_PIX_*  */
+    int32_t matrix;        /* VP_YUV_*, read for NV12 only */
+} vp_image;   /* 48 bytes */
+VP_API int vp_infer_images(vp_handle h, const vp_image* images, int32_t n_images, int32_t images_on_device, const int32_t* crop_params, int32_t n,
+                           const int32_t* expert_ids, float* out);
+VP_API int vp_infer_boxes_images_stream(vp_handle h, const vp_image* images, int32_t n_images, const float* d_xyxy, int32_t row_stride,
+                                        const int32_t* d_frame_idx, int32_t n, int32_t pad, const int32_t* expert_ids, float* d_out,
+                                        int32_t* d_crop_params, int32_t* d_status, void* caller_stream);
+/* HOST ONLY, no device needed: vp_dbg_frame_plan over vp_image, the function vp_infer_images runs first (bands [n_images, 2] in frame rows, may be NULL).
+ * VP_ERR_INVALID, the crop or frame named in vp_last_error(NULL), for everything vp_dbg_frame_plan refuses and for the image refusals listed above. */
+VP_API int vp_dbg_image_plan(const vp_image* images, int32_t n_images, const int32_t* params9, int32_t n, int32_t* bands);
+/* the device crop / zero-pad / resize kernel alone on ONE image whose planes are on the host (vp_dbg_crop_prep over vp_image): uint8 RGB crops [n, 256, 192, 3] */
+VP_API int vp_dbg_crop_prep_image(int32_t device_id, const vp_image* image, const int32_t* crop_params, int32_t n, uint8_t* out);
+
 /* HOST ONLY, no device needed: the plan those entries run for expert_ids [n] on a handle of n_experts experts and max_batch crops per chunk -- the pure function
  * ids -> order, segments that shapes their launches.  Per chunk c (crops [c max_batch, ...)), with B = max_batch rounded up to a multiple of 4:
  *   order [n]: position j of chunk c holds the chunk-local caller row order[c max_batch + j] (stable expert order)
