@@ -11,7 +11,7 @@ Two libraries:
 * ``libvitpose_hip.so`` -- the PRODUCT: what ``_capi.load_library`` loads, what tests / bench / smoke run.
 * ``libvitpose_hip_tools.so`` (``--tools``, ``-DVP_TOOLS``) -- the measurement build ``tools/`` load through ``VP_HIP_LIB``:
   the same sources with ablation flags, start stagger and cycle stamps inside the GEMM kernels, every row of the tile table
-  (``csrc/tiles.h``) and the development environment switches, plus the two tools-only translation units ``probes.hip``
+  (``csrc/tiles.h``: the product rows plus the candidate rows the sweeps of ``tools/`` measure) and the development environment switches, plus the two tools-only translation units ``probes.hip``
   (calibration and issue / store / placement probes) and ``tools_taps.hip`` (timing taps; ``include/vitpose_hip_tools.h``).
 """
 from __future__ import annotations

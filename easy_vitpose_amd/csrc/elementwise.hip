@@ -353,15 +353,6 @@ hipError_t layernorm_launch(int dtype, const float* x, const float* gamma, const
     return hipGetLastError();
 }
 
-
-// sum over the 8 lanes of a DPP half-row (every lane receives it): quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror -- the sequence of gemm.hip::row8_sum
-__device__ __forceinline__ float row8_sum_dpp(float x) {
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));
-    return x;
-}
-
 // Fused-LayerNorm helper: the residual GEMMs leave, per token row and 64-column granule, (sum, M2 about the
 // granule mean).  Fold them in a FIXED order (deterministic, unlike atomics) into (mean, rstd) per row with the
 // pairwise-merge identity  M2 = sum_g [M2_g + 64 (mean_g - mean)^2]  -- no E[x^2] - mean^2 cancellation.
@@ -438,7 +429,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
         *(u32x4*)(x_hi + plane + off) = ol;
     }
     float s1 = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    s1 = row8_sum_dpp(s1);
+    s1 = row8_sum(s1);
     const float mg = s1 * (1.0f / 64.0f);
     float s2 = 0.f;
 #pragma unroll
@@ -446,7 +437,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
         const float d = v[e] - mg;
         s2 = fmaf(d, d, s2);
     }
-    s2 = row8_sum_dpp(s2);
+    s2 = row8_sum(s2);
     if (ok && (ch & 7) == 0) *(float2*)(stats_out + ((size_t)m * (N >> 6) + (ch >> 3)) * 2) = float2{s1, s2};
 }
 

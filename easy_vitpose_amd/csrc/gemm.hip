@@ -35,11 +35,11 @@
 
 namespace vp {
 
-template <int BM_, int BN_, int BK_, int WM_, int WN_, int STAGES_, int PIPE_ = 0, int DIRECT_ = 0>
+template <int BM_, int BN_, int BK_, int WM_, int WN_, int STAGES_, int PIPE_ = 0>
 struct TileCfg {
-    static constexpr int DIRECT = DIRECT_;   // 1: fragment-shaped epilogue stores straight from registers (A/B reference)
     static constexpr int BM = BM_, BN = BN_, BK = BK_, WM = WM_, WN = WN_, STAGES = STAGES_;
-    static constexpr int PIPE = PIPE_;   // 1: issue the fragment reads of both k-halves before the first MFMA block
+    static constexpr int PIPE = PIPE_;   // 0: plain k-step; 1: the fragment reads of k-half 1 issued inside the MFMAs of k-half 0; 6: two k-blocks per barrier
+    static_assert(PIPE == 0 || PIPE == 1 || PIPE == 6, "PIPE");
     static constexpr int NWM = BM / WM, NWN = BN / WN, NWAVES = NWM * NWN, NT = NWAVES * 64;
     static constexpr int ROWB = BK * 2;            // bytes per tile row
     static constexpr int SLOTS = ROWB / 16;        // 16-B slots per row (8 or 4)
@@ -69,83 +69,11 @@ template <class C, int ES> constexpr int epi_rows_per_pass() {
     return jp;
 }
 
-// sum over the 16 lanes of a DPP row (every lane receives it): quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror
-__device__ __forceinline__ float row16_sum(float x) {
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));
-    return x;
-}
-
-// sum over the 8 lanes of a DPP half-row (every lane receives it): quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror
-__device__ __forceinline__ float row8_sum(float x) {
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));
-    return x;
-}
-
 // fused-LayerNorm producer: as epi_rows_per_pass<C, 4>, leaving room for the tile's row statistics behind the staged rows
 template <class C> constexpr int epi_rows_per_pass_ln() {
     int jp = C::TJ;
     while (jp > 1 && C::NWM * jp * 16 * (C::BN * 4 + 16) + C::BM * (C::BN / 64) * 8 > C::LDS) jp /= 2;
     return jp;
-}
-
-// ---- hand-scheduled fragment pipeline (PIPE 5): ds_read_b128 issued by inline asm so that hipcc does not
-// track them (it otherwise waits lgkmcnt(0) for a whole burst); completion is waited for with COUNTED
-// s_waitcnt lgkmcnt(N) placed by hand, each followed by sched_barrier(0) so no MFMA is hoisted above its wait.
-template <int OFF> __device__ __forceinline__ void lds_read_b128(u32x4& d, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-}
-template <int N> __device__ __forceinline__ void wait_lgkm() {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
-    __builtin_amdgcn_sched_barrier(0);
-}
-template <int ROWB, int... Is>
-__device__ __forceinline__ void lds_read_frags(u32x4* d, uint32_t addr, std::integer_sequence<int, Is...>) {
-    (lds_read_b128<Is * 16 * ROWB>(d[Is], addr), ...);
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// read number RI (0 .. R-1) of k-half 1: weight fragment RI, or activation fragment RI - TI
-template <class C, int RI>
-__device__ __forceinline__ void pipe5_issue(u32x4* f1, uint32_t wa1, uint32_t aa1) {
-    if constexpr (RI < C::TI) lds_read_b128<RI * 16 * C::ROWB>(f1[RI], wa1);
-    else if constexpr (RI < C::TI + C::TJ) lds_read_b128<(RI - C::TI) * 16 * C::ROWB>(f1[RI], aa1);
-}
-
-// k-half 0, group J: wait for activation fragment J, TI MFMAs, then issue reads 2J and 2J+1 of k-half 1
-template <class T, class C, int J>
-__device__ __forceinline__ void pipe5_half0(f32x4 (&acc)[C::TI][C::TJ], u32x4* f0, u32x4* f1, uint32_t wa1, uint32_t aa1) {
-    if constexpr (J < C::TJ) {
-        constexpr int R = C::TI + C::TJ;
-        constexpr int issued = R + (2 * J < R ? 2 * J : R);
-        wait_lgkm<issued - (C::TI + J + 1)>();
-#pragma unroll
-        for (int i = 0; i < C::TI; ++i) acc[i][J] = mfma16<T>(f0[i], f0[C::TI + J], acc[i][J]);
-        __builtin_amdgcn_sched_barrier(0);
-        pipe5_issue<C, 2 * J>(f1, wa1, aa1);
-        pipe5_issue<C, 2 * J + 1>(f1, wa1, aa1);
-        __builtin_amdgcn_sched_barrier(0);
-        pipe5_half0<T, C, J + 1>(acc, f0, f1, wa1, aa1);
-    }
-}
-
-// k-half 1, group J: every read is issued; fragment TI + J is complete once TJ - J - 1 younger reads remain
-template <class T, class C, int J>
-__device__ __forceinline__ void pipe5_half1(f32x4 (&acc)[C::TI][C::TJ], u32x4* f1) {
-    if constexpr (J < C::TJ) {
-        wait_lgkm<C::TJ - J - 1>();
-#pragma unroll
-        for (int i = 0; i < C::TI; ++i) acc[i][J] = mfma16<T>(f1[i], f1[C::TI + J], acc[i][J]);
-        __builtin_amdgcn_sched_barrier(0);
-        pipe5_half1<T, C, J + 1>(acc, f1);
-    }
 }
 
 template <class T, int EPI_, int AMODE, class C, bool EXPERT = false>
@@ -196,24 +124,6 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(GemmArgs g) {
     const int K = g.K;
     const int klen = (EPI_ == EPI_PARTIAL) ? K / g.splitk : K;   // this workgroup's k range: [kbase, kbase + klen)
     const int kbase = (EPI_ == EPI_PARTIAL) ? split * klen : 0;
-    if constexpr (LN_PROD) {
-        // experiment (tools build, VP_PROJ_STAGGER = 1000 mode + n): of the first round of workgroups (two per CU, all started together) the SECOND
-        // one of every CU starts n x 1024 cycles late, so that one workgroup of a CU is in its HBM-bound epilogue while the other runs its K-loop.
-        // mode 0: second = wave slots 2 / 3 of the SIMD (HW_REG_HW_ID), 1: blockIdx >= 256, 2: odd (blockIdx >> 3); whole CUs late (both workgroups):
-        // 3: odd CU id, 4: odd XCD, 5: odd shader engine
-        if (VP_STAGGER(g) > 0 && blockIdx.x < 512) {
-            const int mode = VP_STAGGER(g) / 1000, n = VP_STAGGER(g) % 1000;
-            const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);
-            bool late;
-            if (mode == 0) late = (hw >> 1) & 1;
-            else if (mode == 1) late = blockIdx.x >= 256;
-            else if (mode == 3) late = (hw >> 8) & 1;
-            else if (mode == 4) late = blockIdx.x & 1;
-            else if (mode == 5) late = (hw >> 13) & 1;
-            else late = (blockIdx.x >> 3) & 1;
-            if (late) for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(16);
-        }
-    }
 
     // ---- staging addresses: piece p of an operand = rows [(p*NWAVES + wave)*RPG, +RPG) ----
     const int rip = lane / C::SLOTS, pslot = lane % C::SLOTS;
@@ -279,124 +189,8 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(GemmArgs g) {
 #pragma unroll
         for (int j = 0; j < C::TJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+    // ---- main loop: a STAGES-deep ring of k-blocks, one barrier per KS of them ----
     const int nk = klen / C::BK;
-    if constexpr (C::PIPE == 2) {
-        // Register double-buffered fragments over a STAGES-deep LDS ring (BK = 32, one 32-deep MFMA step
-        // per barrier): while the MFMAs of tile kt run, the ds_reads of tile kt+1 (already landed and made
-        // visible by this step's barrier) fill the other fragment set and tile kt+STAGES-1 streams into the
-        // slot freed two barriers ago -- the matrix pipe never waits for LDS, only at the barrier itself.
-        static_assert(C::KK == 1 && C::STAGES >= 3, "PIPE 2 needs BK = 32 and >= 3 stages");
-        u32x4 wfA[C::TI], afA[C::TJ], wfB[C::TI], afB[C::TJ];
-        auto ldfrag = [&](u32x4(&wf)[C::TI], u32x4(&af)[C::TJ], int b) {
-            const char* sb = smem + b * C::STAGE_BYTES;
-#pragma unroll
-            for (int i = 0; i < C::TI; ++i) wf[i] = *(const u32x4*)(sb + (woff + i * 16 * C::ROWB));
-#pragma unroll
-            for (int j = 0; j < C::TJ; ++j) af[j] = *(const u32x4*)(sb + (aoff + j * 16 * C::ROWB));
-        };
-        auto settle = [&](u32x4(&wf)[C::TI], u32x4(&af)[C::TJ]) {   // make the compiler wait for a fragment set HERE
-#pragma unroll
-            for (int i = 0; i < C::TI; ++i) asm volatile("" ::"v"(wf[i]));
-#pragma unroll
-            for (int j = 0; j < C::TJ; ++j) asm volatile("" ::"v"(af[j]));
-        };
-        auto mma = [&](u32x4(&wf)[C::TI], u32x4(&af)[C::TJ]) {
-#pragma unroll
-            for (int i = 0; i < C::TI; ++i)
-#pragma unroll
-                for (int j = 0; j < C::TJ; ++j) acc[i][j] = mfma16<T>(wf[i], af[j], acc[i][j]);
-        };
-#pragma unroll
-        for (int s = 0; s < C::STAGES - 1; ++s)
-            if (s < nk) stage(s, s);
-        if (nk >= C::STAGES - 1) wait_vmcnt<C::G * (C::STAGES - 2)>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        ldfrag(wfA, afA, 0);
-        int nbuf = 1 % C::STAGES, pbuf = C::STAGES - 1;   // buffer of tile kt+1, buffer tile kt+STAGES-1 goes to
-        auto step = [&](int kt, u32x4(&cwf)[C::TI], u32x4(&caf)[C::TJ], u32x4(&nwf)[C::TI], u32x4(&naf)[C::TJ]) {
-            if (kt + C::STAGES - 2 < nk) wait_vmcnt<C::G * (C::STAGES - 3)>();   // tile kt+1 landed (own share)
-            else wait_vmcnt<0>();
-            __builtin_amdgcn_s_barrier();   // tile kt+1 visible; every wave is done with the slot of tile kt-1
-            asm volatile("" ::: "memory");
-            settle(cwf, caf);
-            __builtin_amdgcn_sched_barrier(0);
-            if (kt + C::STAGES - 1 < nk) stage(kt + C::STAGES - 1, pbuf);
-            if (kt + 1 < nk) ldfrag(nwf, naf, nbuf);
-            __builtin_amdgcn_sched_barrier(0);
-            mma(cwf, caf);
-            nbuf = (nbuf + 1 == C::STAGES) ? 0 : nbuf + 1;
-            pbuf = (pbuf + 1 == C::STAGES) ? 0 : pbuf + 1;
-        };
-        for (int kt = 0; kt < nk; kt += 2) {   // nk is even (K % 64 == 0, BK = 32)
-            step(kt, wfA, afA, wfB, afB);
-            step(kt + 1, wfB, afB, wfA, afA);
-        }
-    } else if constexpr (C::PIPE == 3) {
-        // Staggered two-group schedule (8 waves, BK = 32, 4-stage LDS ring).  Waves 0-3 (group A) and 4-7
-        // (group B) run the same LOAD -> barrier -> MFMA -> barrier sequence one barrier apart, so in every
-        // barrier interval one wave of each SIMD streams its 32 MFMAs while its SIMD partner reads the next
-        // fragments from LDS and issues the global_load_lds of tile k+3: the matrix pipe and the LDS/TA
-        // pipes are busy simultaneously instead of alternately.
-        //   A: LOAD(k) between barriers 2k..2k+1, MFMA(k) between 2k+1..2k+2;  B: one barrier later.
-        //   tile j: issued in LOAD(j-3) into slot j%4 (last read in LOAD(j-4), >= 1 barrier earlier),
-        //   landed before barrier 2j because every LOAD phase ends with vmcnt(2G) (two younger tiles in flight).
-        static_assert(C::KK == 1 && C::STAGES == 4 && C::NWAVES == 8, "PIPE 3: BK = 32, 4 stages, 8 waves");
-        const bool grp_b = __builtin_amdgcn_readfirstlane(tid) >= 256;
-        u32x4 wf[C::TI], af[C::TJ];
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-            if (s < nk) stage(s, s);
-        if (nk >= 3) wait_vmcnt<2 * C::G>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (grp_b) {
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
-        int rbuf = 0, pbuf = 3;
-        for (int k = 0; k < nk; ++k) {
-            // ---- LOAD(k)
-            const char* sb = smem + rbuf * C::STAGE_BYTES;
-#pragma unroll
-            for (int i = 0; i < C::TI; ++i) wf[i] = *(const u32x4*)(sb + (woff + i * 16 * C::ROWB));
-#pragma unroll
-            for (int j = 0; j < C::TJ; ++j) af[j] = *(const u32x4*)(sb + (aoff + j * 16 * C::ROWB));
-            if (k + 3 < nk) {
-                if (!(VP_ABLATE(g) & 1)) stage(k + 3, pbuf);
-                wait_vmcnt<2 * C::G>();
-            } else if (k + 2 < nk) {
-                wait_vmcnt<C::G>();
-            } else {
-                wait_vmcnt<0>();
-            }
-#pragma unroll
-            for (int i = 0; i < C::TI; ++i) asm volatile("" ::"v"(wf[i]));   // fragments complete before the barrier
-#pragma unroll
-            for (int j = 0; j < C::TJ; ++j) asm volatile("" ::"v"(af[j]));
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            // ---- MFMA(k)
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < C::TI; ++i)
-#pragma unroll
-                for (int j = 0; j < C::TJ; ++j) acc[i][j] = mfma16<T>(wf[i], af[j], acc[i][j]);
-            __builtin_amdgcn_s_setprio(0);
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            rbuf = (rbuf + 1) & 3;
-            pbuf = (pbuf + 1) & 3;
-        }
-        if (!grp_b) {
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
-    } else {
     // PIPE 6 (round 5, small batches): TWO k-blocks per barrier.  A 64 x 64 tile spends ~500 of the ~760 cycles of a k-step on the wait, the barrier and the
     // LDS round trip in front of its 8 MFMAs per wave, and at a few crops no second workgroup shares the SIMD to hide them; with two k-blocks per barrier that
     // overhead is paid once per 128 k.  Same k order, same MFMAs: bit-identical.  Ring: tile j in slot j % STAGES; the prologue issues STAGES - KS tiles, an
@@ -448,75 +242,56 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(GemmArgs g) {
         }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-        const int cbuf = buf + ks >= C::STAGES ? buf + ks - C::STAGES : buf + ks;
-        const char* sb = smem + cbuf * C::STAGE_BYTES;
-        if constexpr (C::PIPE == 5) {
-            // reads: per k-half wf[0..TI-1] then af[0..TJ-1] (R = TI + TJ); k-half 0 is issued up front, two
-            // reads of k-half 1 after each MFMA group of k-half 0.  Group (kk, j) = TI MFMAs wf[kk][*] x af[kk][j];
-            // it needs read TI + j of its half, so before it the allowed outstanding count is
-            //   half 0: R + min(R, 2j) - (TI + j + 1)        half 1: TJ - j - 1
-            static_assert(C::KK == 2 && C::TI + C::TJ <= 12 && 2 * C::TJ >= C::TI + C::TJ, "PIPE 5 schedule");
-            constexpr int R = C::TI + C::TJ;
-            u32x4 f0[R], f1[R];                       // [0, TI): weight fragments, [TI, R): activation fragments
-            const uint32_t lb = (uint32_t)(size_t)(lds_ptr_t)(smem) + cbuf * C::STAGE_BYTES;
-            const uint32_t wa0 = lb + woff, wa1 = lb + (woff ^ 64), aa0 = lb + aoff, aa1 = lb + (aoff ^ 64);
-            lds_read_frags<C::ROWB>(f0, wa0, std::make_integer_sequence<int, C::TI>{});
-            lds_read_frags<C::ROWB>(f0 + C::TI, aa0, std::make_integer_sequence<int, C::TJ>{});
-            __builtin_amdgcn_s_setprio(1);
-            __builtin_amdgcn_sched_barrier(0);
-            pipe5_half0<T, C, 0>(acc, f0, f1, wa1, aa1);
-            pipe5_half1<T, C, 0>(acc, f1);
-            __builtin_amdgcn_s_setprio(0);
-        } else if (C::PIPE == 1 && C::KK == 2) {
-            // software pipelined fragment reads: the ds_reads of k-half 1 are issued between the two MFMA
-            // blocks of k-half 0 and complete in their shadow (lgkmcnt is only 4 bits wide, so no more than
-            // one half's reads are outstanding at a wait); sched_barriers pin this order for the compiler.
-            u32x4 wf0[C::TI], af0[C::TJ], wf1[C::TI], af1[C::TJ];
+            const int cbuf = buf + ks >= C::STAGES ? buf + ks - C::STAGES : buf + ks;
+            const char* sb = smem + cbuf * C::STAGE_BYTES;
+            if (C::PIPE == 1 && C::KK == 2) {
+                // software pipelined fragment reads: the ds_reads of k-half 1 are issued between the two MFMA
+                // blocks of k-half 0 and complete in their shadow (lgkmcnt is only 4 bits wide, so no more than
+                // one half's reads are outstanding at a wait); sched_barriers pin this order for the compiler.
+                u32x4 wf0[C::TI], af0[C::TJ], wf1[C::TI], af1[C::TJ];
 #pragma unroll
-            for (int i = 0; i < C::TI; ++i) wf0[i] = *(const u32x4*)(sb + (woff + i * 16 * C::ROWB));
+                for (int i = 0; i < C::TI; ++i) wf0[i] = *(const u32x4*)(sb + (woff + i * 16 * C::ROWB));
 #pragma unroll
-            for (int j = 0; j < C::TJ; ++j) af0[j] = *(const u32x4*)(sb + (aoff + j * 16 * C::ROWB));
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
+                for (int j = 0; j < C::TJ; ++j) af0[j] = *(const u32x4*)(sb + (aoff + j * 16 * C::ROWB));
+                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int i = 0; i < C::TI / 2; ++i)
+                for (int i = 0; i < C::TI / 2; ++i)
 #pragma unroll
-                for (int j = 0; j < C::TJ; ++j) acc[i][j] = mfma16<T>(wf0[i], af0[j], acc[i][j]);
-            __builtin_amdgcn_sched_barrier(0);
+                    for (int j = 0; j < C::TJ; ++j) acc[i][j] = mfma16<T>(wf0[i], af0[j], acc[i][j]);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < C::TI; ++i) wf1[i] = *(const u32x4*)(sb + ((woff + i * 16 * C::ROWB) ^ 64));
+                for (int i = 0; i < C::TI; ++i) wf1[i] = *(const u32x4*)(sb + ((woff + i * 16 * C::ROWB) ^ 64));
 #pragma unroll
-            for (int j = 0; j < C::TJ; ++j) af1[j] = *(const u32x4*)(sb + ((aoff + j * 16 * C::ROWB) ^ 64));
-            __builtin_amdgcn_sched_barrier(0);
+                for (int j = 0; j < C::TJ; ++j) af1[j] = *(const u32x4*)(sb + ((aoff + j * 16 * C::ROWB) ^ 64));
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = C::TI / 2; i < C::TI; ++i)
+                for (int i = C::TI / 2; i < C::TI; ++i)
 #pragma unroll
-                for (int j = 0; j < C::TJ; ++j) acc[i][j] = mfma16<T>(wf0[i], af0[j], acc[i][j]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < C::TI; ++i)
-#pragma unroll
-                for (int j = 0; j < C::TJ; ++j) acc[i][j] = mfma16<T>(wf1[i], af1[j], acc[i][j]);
-            __builtin_amdgcn_s_setprio(0);
-        } else {
-#pragma unroll
-            for (int kk = 0; kk < C::KK; ++kk) {
-                u32x4 wf[C::TI], af[C::TJ];
-#pragma unroll
-                for (int i = 0; i < C::TI; ++i) wf[i] = *(const u32x4*)(sb + ((woff + i * 16 * C::ROWB) ^ (kk << 6)));
-#pragma unroll
-                for (int j = 0; j < C::TJ; ++j) af[j] = *(const u32x4*)(sb + ((aoff + j * 16 * C::ROWB) ^ (kk << 6)));
+                    for (int j = 0; j < C::TJ; ++j) acc[i][j] = mfma16<T>(wf0[i], af0[j], acc[i][j]);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < C::TI; ++i)
 #pragma unroll
-                    for (int j = 0; j < C::TJ; ++j) acc[i][j] = mfma16<T>(wf[i], af[j], acc[i][j]);
+                    for (int j = 0; j < C::TJ; ++j) acc[i][j] = mfma16<T>(wf1[i], af1[j], acc[i][j]);
+                __builtin_amdgcn_s_setprio(0);
+            } else {
+#pragma unroll
+                for (int kk = 0; kk < C::KK; ++kk) {
+                    u32x4 wf[C::TI], af[C::TJ];
+#pragma unroll
+                    for (int i = 0; i < C::TI; ++i) wf[i] = *(const u32x4*)(sb + ((woff + i * 16 * C::ROWB) ^ (kk << 6)));
+#pragma unroll
+                    for (int j = 0; j < C::TJ; ++j) af[j] = *(const u32x4*)(sb + ((aoff + j * 16 * C::ROWB) ^ (kk << 6)));
+#pragma unroll
+                    for (int i = 0; i < C::TI; ++i)
+#pragma unroll
+                        for (int j = 0; j < C::TJ; ++j) acc[i][j] = mfma16<T>(wf[i], af[j], acc[i][j]);
+                }
             }
-        }
         }
         buf = (buf + KS >= C::STAGES) ? buf + KS - C::STAGES : buf + KS;
         pbuf = (pbuf + KS >= C::STAGES) ? pbuf + KS - C::STAGES : pbuf + KS;
-    }
-
     }
 
     // ---- epilogue ----
@@ -623,7 +398,7 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(GemmArgs g) {
                 group(wB, u + 1);
             }
         }
-    } else if constexpr (LN_PROD && !C::DIRECT) {
+    } else if constexpr (LN_PROD) {
         // Fused-LayerNorm producer (patch embed, attn.proj, mlp.fc2).  The residual stream lives in HBM as two
         // 16-bit planes, x = hi + lo with hi = round16(x), lo = round16(x - hi): the same 4 bytes per element as
         // fp32 (>= 22 significant bits), but the hi plane IS the un-normalised 16-bit operand the next qkv / fc1
@@ -739,7 +514,7 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(GemmArgs g) {
             if (m < g.M && n < g.N && !(VP_ABLATE(g) & 8))
                 *(float2*)(g.stats_out + ((size_t)m * (g.N / 64) + (n >> 6)) * 2) = *(const float2*)(statbuf + t * 2);
         }
-    } else if constexpr (EPI != EPI_HEATMAP && !C::DIRECT) {
+    } else if constexpr (EPI != EPI_HEATMAP) {
         constexpr int ES = (EPI == EPI_BIAS_RESID || EPI == EPI_POS || EPI == EPI_PARTIAL) ? 4 : 2;   // bytes per staged element
         constexpr int ROWBYTES = C::BN * ES + 16;                               // +16 B: conflict-free fragment writes
         constexpr int JP = epi_rows_per_pass<C, ES>();
@@ -878,60 +653,23 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(GemmArgs g) {
             if (p + 1 < C::TJ / JP) __syncthreads();
         }
     } else {
-        // direct fragment-shaped stores: EPI_HEATMAP (final 1x1 conv, few n, transposed out[(img*Kp + n)*3072 + p])
-        // and the DIRECT A/B reference configurations
+        // EPI_HEATMAP (final 1x1 conv, few n, transposed out[(img*Kp + n)*3072 + p]): fragment-shaped stores straight from the registers
 #pragma unroll
         for (int j = 0; j < C::TJ; ++j) {
             const int m = m0 + wm * C::WM + j * 16 + frow;
             if (m >= g.M || (VP_ABLATE(g) & 8)) continue;
-            size_t orow;
-            if (EPI == EPI_DECONV) {
-                const int t = m / g.Win, jx = m - t * g.Win, ii = t % g.Hin, img = t / g.Hin;
-                orow = ((size_t)(img * 2 * g.Hin + 2 * ii + (parity >> 1)) * (2 * g.Win) + 2 * jx + (parity & 1)) * (size_t)g.ldo;
-            } else if (EPI == EPI_HEATMAP) {
-                const int img = m / 3072, pix = m - img * 3072;
-                orow = (size_t)img * g.Kp * 3072 + pix;
-            } else {
-                orow = (size_t)m * g.ldo;
-            }
-            if constexpr (EPI == EPI_HEATMAP) {
-                // weight rows come as [16 hi][16 lo] groups (weights.hip upload_final): fragments 2u and 2u + 1
-                // are the hi and lo products of output columns (n0 + wn WN) / 2 + 16 u + 4 fg .. + 3
+            const int img = m / 3072, pix = m - img * 3072;
+            const size_t orow = (size_t)img * g.Kp * 3072 + pix;
+            // weight rows come as [16 hi][16 lo] groups (weights.hip upload_final): fragments 2u and 2u + 1
+            // are the hi and lo products of output columns (n0 + wn WN) / 2 + 16 u + 4 fg .. + 3
 #pragma unroll
-                for (int u = 0; u < C::TI / 2; ++u) {
-                    const int nb = (n0 + wn * C::WN) / 2 + u * 16 + fg * 4;
-                    if (nb >= g.Kp) continue;
-                    const f32x4 v = acc[2 * u][j] + acc[2 * u + 1][j];
+            for (int u = 0; u < C::TI / 2; ++u) {
+                const int nb = (n0 + wn * C::WN) / 2 + u * 16 + fg * 4;
+                if (nb >= g.Kp) continue;
+                const f32x4 v = acc[2 * u][j] + acc[2 * u + 1][j];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (nb + r < g.Kp) ((float*)g.out)[orow + (size_t)(nb + r) * 3072] = v[r] + g.bias[nb + r];
-                }
-                continue;
-            }
-#pragma unroll
-            for (int i = 0; i < C::TI; ++i) {
-                const int nb = n0 + wn * C::WN + i * 16 + fg * 4;
-                if (nb >= g.N) continue;
-                f32x4 v = acc[i][j];
-                if (EPI != EPI_POS) v += *(const f32x4*)(g.bias + nb);
-                if (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_DECONV) {
-                    if (EPI == EPI_BIAS_GELU) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
-                    }
-                    if (EPI == EPI_DECONV) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-                    }
-                    u32x2 o;
-                    o[0] = pack2<T>(v[0], v[1]);
-                    o[1] = pack2<T>(v[2], v[3]);
-                    *(u32x2*)((uint16_t*)g.out + orow + nb) = o;
-                } else if (EPI == EPI_BIAS_RESID) {
-                    *(f32x4*)((float*)g.out + orow + nb) = v + *(const f32x4*)(g.aux + orow + nb);
-                } else {
-                    *(f32x4*)((float*)g.out + orow + nb) = v + *(const f32x4*)(g.aux + (size_t)(m % 192) * g.ldo + nb);
-                }
+                for (int r = 0; r < 4; ++r)
+                    if (nb + r < g.Kp) ((float*)g.out)[orow + (size_t)(nb + r) * 3072] = v[r] + g.bias[nb + r];
             }
         }
     }
@@ -1195,15 +933,15 @@ static hipError_t launch_persist(const GemmArgs& a, hipStream_t s) {
     grid &= ~7;
     if (grid < 8) return hipErrorInvalidValue;
     if (a.desc)
-        snprintf(a.desc, a.desc_cap, "gemm_persist_kernel<%s, %d, TileCfg<%d, %d, %d, %d, %d, %d, %d, %d>>", std::is_same<T, F16>::value ? "F16" : "BF16", EPI,
-                 C::BM, C::BN, C::BK, C::WM, C::WN, C::STAGES, C::PIPE, C::DIRECT);
+        snprintf(a.desc, a.desc_cap, "gemm_persist_kernel<%s, %d, TileCfg<%d, %d, %d, %d, %d, %d, %d>>", std::is_same<T, F16>::value ? "F16" : "BF16", EPI,
+                 C::BM, C::BN, C::BK, C::WM, C::WN, C::STAGES, C::PIPE);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS, s, a);
     return hipGetLastError();
 }
 
 // Tile configurations (id = GemmArgs::variant): the rows of tiles.h.  CfgAt<i> is row i as the kernels' template argument.
 template <int I>
-using CfgAt = TileCfg<TILES[I].BM, TILES[I].BN, TILES[I].BK, TILES[I].WM, TILES[I].WN, TILES[I].STAGES, TILES[I].PIPE, TILES[I].DIRECT>;
+using CfgAt = TileCfg<TILES[I].BM, TILES[I].BN, TILES[I].BK, TILES[I].WM, TILES[I].WN, TILES[I].STAGES, TILES[I].PIPE>;
 constexpr int tile_index(int id) { return (int)(find_tile(id) - TILES); }
 using Cfg3 = CfgAt<tile_index(3)>;   // 256 x 256: the fused deconv2 + final conv tile (EPI_DECONV_FINAL)
 using Cfg8 = CfgAt<tile_index(8)>;   // the default tile: the persistent variant
@@ -1216,7 +954,6 @@ static_assert(table_matches_kernels(std::make_integer_sequence<int, NUM_TILES>{}
 
 template <class T, int EPI, int AMODE, class C>
 static hipError_t launch(const GemmArgs& a, hipStream_t s) {
-    if constexpr ((EPI == EPI_BIAS_RESID_LN || EPI == EPI_POS_LN) && C::DIRECT) return hipErrorInvalidValue;
     auto kern = gemm_kernel<T, EPI, AMODE, C>;
     int ex = 0;   // the residual epilogues' per-crop expert instantiation (ViTPose+, GemmArgs::expert)
     if constexpr (EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_RESID_LN)
@@ -1225,7 +962,6 @@ static hipError_t launch(const GemmArgs& a, hipStream_t s) {
     constexpr int LDS_BYTES = (EPI == EPI_DECONV_FINAL && C::BM * (C::BN * 2 + 16) > C::LDS) ? C::BM * (C::BN * 2 + 16) : C::LDS;
     constexpr int LN_STAT_BYTES = C::BM * 8;   // (mean, rstd) per tile row behind the ring: used when GemmArgs::ln_part is set
     static_assert(LDS_BYTES + LN_STAT_BYTES <= 160 * 1024, "LDS");
-    if (a.ln_part && (C::PIPE == 2 || C::PIPE == 3 || C::DIRECT)) return hipErrorInvalidValue;   // the prologue merge lives in the generic loop
     if (C::PIPE == 6 && a.K % 128 != 0) return hipErrorInvalidValue;                                      // two k-blocks per barrier
     if (a.ln_part && (a.ln_tiles & 1)) return hipErrorInvalidValue;   // a row's partial statistics are fetched as 16-byte pieces: ln_tiles * 8 bytes must be a multiple of 16
     static bool attr_done[2][64] = {};   // the > 64 KiB LDS opt-in is a per-device function attribute
@@ -1242,12 +978,12 @@ static hipError_t launch(const GemmArgs& a, hipStream_t s) {
     if ((size_t)tiles_n * C::BN > (size_t)a.w_rows) return hipErrorInvalidValue;   // weight rows are padded at upload
     const int tiles = ((a.M + C::BM - 1) / C::BM) * tiles_n;
     if constexpr (EPI == EPI_PARTIAL) {
-        if (a.splitk < 1 || a.K % (a.splitk * C::BK * (C::PIPE == 6 ? 2 : 1)) != 0 || a.ldo != a.N || a.N % 4 != 0 || C::DIRECT || C::PIPE == 2 || C::PIPE == 3) return hipErrorInvalidValue;
+        if (a.splitk < 1 || a.K % (a.splitk * C::BK * (C::PIPE == 6 ? 2 : 1)) != 0 || a.ldo != a.N || a.N % 4 != 0) return hipErrorInvalidValue;
     }
     dim3 grid(AMODE == A_DECONV && a.parity_fast ? tiles * 4 : (EPI == EPI_PARTIAL ? tiles * a.splitk : tiles), AMODE == A_DECONV && !a.parity_fast ? 4 : 1);
     if (a.desc)
-        snprintf(a.desc, a.desc_cap, "gemm_kernel<%s, %d, %d, TileCfg<%d, %d, %d, %d, %d, %d, %d, %d>%s>", std::is_same<T, F16>::value ? "F16" : "BF16", EPI,
-                 AMODE, C::BM, C::BN, C::BK, C::WM, C::WN, C::STAGES, C::PIPE, C::DIRECT, ex ? ", true" : "");
+        snprintf(a.desc, a.desc_cap, "gemm_kernel<%s, %d, %d, TileCfg<%d, %d, %d, %d, %d, %d, %d>%s>", std::is_same<T, F16>::value ? "F16" : "BF16", EPI,
+                 AMODE, C::BM, C::BN, C::BK, C::WM, C::WN, C::STAGES, C::PIPE, ex ? ", true" : "");
     hipLaunchKernelGGL(kern, grid, dim3(C::NT), LDS_BYTES + (a.ln_part ? LN_STAT_BYTES : 0), s, g);
     return hipGetLastError();
 }
@@ -1310,14 +1046,6 @@ hipError_t gemm_launch(int dtype, int epi, const GemmArgs& a, hipStream_t s) {
 #endif
         return gemm8_launch(dtype, epi, a, t8->BN, s, t8->BM);
     }
-#ifdef VP_TOOLS
-    static const int proj_stagger_env = [] { const char* e = getenv("VP_PROJ_STAGGER"); return e ? atoi(e) : 0; }();
-    if (proj_stagger_env > 0 && (epi == EPI_BIAS_RESID_LN) && a.K <= a.N) {
-        GemmArgs b = a;
-        b.stagger = proj_stagger_env;
-        return dtype == DT_F16 ? dispatch<F16>(epi, b, s) : dispatch<BF16>(epi, b, s);
-    }
-#endif
     if (a.persist) {   // persistent variant: wide 16-bit-output GEMMs on the default tile (a 256x256 instantiation spilled and was slower)
         // (launch_persist allocates no statistics area behind the ring: a consumer that folds partial statistics itself, ln_part, is refused here, not only by resolve_gemm)
         if ((epi != EPI_BIAS && epi != EPI_BIAS_GELU) || a.variant != 8 || a.ln_part || a.K % 128 || a.N % 8 || a.ldo != a.N || a.reverse ||

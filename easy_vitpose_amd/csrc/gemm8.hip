@@ -194,8 +194,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
     constexpr int NKEEP = C::NKEEP;   // pieces of one LA + one LB issue (BM = 256: 2 + 4 + NW1): what a counted wait leaves in flight
     // the wait that leaves exactly one LB group in flight (last K-tile of a tile, ring start)
     auto wait_lb = [&]() {
-        if constexpr (C::BM == 256) wait_vm<C::INFLIGHT>();
-        else { if (wr) wait_vm<3 + C::NW1>(); else wait_vm<4 + C::NW1>(); }
+        if constexpr (C::BM == 256) wait_vmcnt<C::INFLIGHT>();
+        else { if (wr) wait_vmcnt<3 + C::NW1>(); else wait_vmcnt<4 + C::NW1>(); }
     };
     auto ktile = [&](auto Bc, auto Mc, int kA, int kB, bool swB, int nm0, int nn0) {
         constexpr int B = decltype(Bc)::value;
@@ -219,8 +219,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
         SEC(1);
         if constexpr (MODE != 4) issue(1, B ^ 1, kA);
         SEC(2);
-        if constexpr (MODE == 4) wait_vm<0>();   // last K-tile of a draining tile: nothing left to fetch, X1 of this K-tile is all that is in flight
-        else if constexpr (MODE != 1) wait_vm<NKEEP>();
+        if constexpr (MODE == 4) wait_vmcnt<0>();   // last K-tile of a draining tile: nothing left to fetch, X1 of this K-tile is all that is in flight
+        else if constexpr (MODE != 1) wait_vmcnt<NKEEP>();
         wait_lgkm<0>();
         SEC(3);
         KBAR();
@@ -255,9 +255,9 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
         }
         SEC(7);
         if constexpr (MODE == 2) wait_lb();
-        else if constexpr (MODE == 3) { if (wr) wait_vm<2>(); else wait_vm<1>(); }   // second-to-last K-tile of a draining tile (192-row geometry): LB fetches
+        else if constexpr (MODE == 3) { if (wr) wait_vmcnt<2>(); else wait_vmcnt<1>(); }   // second-to-last K-tile of a draining tile (192-row geometry): LB fetches
                                                                                        // nothing; X0 / W0 / W1 of the last K-tile landed, this LA's X1 pieces (1 / 2 per wave) stay in flight
-        else if constexpr (MODE < 3) wait_vm<NKEEP>();
+        else if constexpr (MODE < 3) wait_vmcnt<NKEEP>();
         wait_lgkm<0>();
         SEC(8);
         KBAR();
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
             }
 #pragma unroll
             for (int J = 0; J < TJ; ++J) st[J] = *(const float2*)(g.rowstat + 2 * (size_t)(mrow + rowJ(J)));
-            wait_vm<0>();
+            wait_vmcnt<0>();
             if (!wr) bar();     // undo the stagger: both groups meet here
             __syncthreads();    // every wave is done with the ring
             if (has_next) {     // the next tile's K-tile 0 (ring buffer 0) and X0 of its K-tile 1: on their way from here on
@@ -513,8 +513,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
                 // K-tile 0 has landed once only the operations issued behind its last piece are outstanding: X0 of K-tile 1 (2 / 1 pieces), this wave's
                 // output stores (waves 0-3: two query tiles = 10, waves 4-7: 5) and the four pieces above.  The stores themselves are NOT waited for here:
                 // the first counted wait of the K-loop (LB of K-tile 0) retires them, half a K-tile later.
-                if (VP_ABLATE(g) & (8 | 16)) { if (wr) wait_vm<5>(); else wait_vm<6>(); }
-                else { if (wr) wait_vm<10>(); else wait_vm<16>(); }
+                if (VP_ABLATE(g) & (8 | 16)) { if (wr) wait_vmcnt<5>(); else wait_vmcnt<6>(); }
+                else { if (wr) wait_vmcnt<10>(); else wait_vmcnt<16>(); }
                 bar();
                 if (wr) bar();   // stagger: waves 4-7 run one barrier behind waves 0-3
             }
@@ -718,7 +718,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
             auto tile_row = [&](int p, int lr) {
                 return (p / (4 / JPP)) * 128 + (lr / (16 * JPP)) * 64 + ((p % (4 / JPP)) * JPP + (lr / 16) % JPP) * 16 + (lr & 15);
             };
-            wait_vm<0>();
+            wait_vmcnt<0>();
             if (!wr) bar();     // undo the stagger: both groups meet here
             __syncthreads();    // every wave is done with the ring
             if (tl) rs[2] = __builtin_readcyclecounter();
@@ -767,7 +767,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
                         *(u32x4*)(out_lo + so) = ol;
                     }
                     float s1s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                    s1s = row8_sum8(s1s);
+                    s1s = row8_sum(s1s);
                     const float mg = s1s * (1.0f / 64.0f);
                     float s2 = 0.f;
 #pragma unroll
@@ -775,7 +775,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
                         const float d = v[e] - mg;
                         s2 = fmaf(d, d, s2);
                     }
-                    s2 = row8_sum8(s2);
+                    s2 = row8_sum(s2);
                     if ((ch & 7) == 0) *(float2*)(statbuf + (tile_row(p, lr) * GR + (ch >> 3)) * 2) = float2{s1s, s2};
                 }
                 __syncthreads();
@@ -805,7 +805,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
         m0 = nm0;
         n0 = nn0;
     }
-    wait_vm<0>();   // the ring's run-ahead DMAs must have landed before the LDS is released
+    wait_vmcnt<0>();   // the ring's run-ahead DMAs must have landed before the LDS is released
     if constexpr (!DRAIN) {
         if (!wr) bar();   // pair the extra barrier of the staggered group
     }

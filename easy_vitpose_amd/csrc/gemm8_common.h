@@ -1,4 +1,4 @@
-// Shared pieces of the 8-phase GEMM kernels (gemm8.hip, gemm8f.hip, qkvattn.hip): tile geometry, wait / barrier helpers, tile walk.
+// Shared pieces of the 8-phase GEMM kernels (gemm8.hip, gemm8f.hip, qkvattn.hip): tile geometry, barrier helper, tile walk.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -31,20 +31,10 @@ template <int BN_, int BM_ = 256> struct G8 {
     static_assert(BM == 256 || (BM == 192 && BN == 256), "BM");
 };
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void bar() {
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-}
-
-
-__device__ __forceinline__ float row8_sum8(float x) {   // identical to gemm.hip's row8_sum
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));
-    return x;
 }
 
 struct TileWalk {   // XCD-contiguous, grouped tile order (same as gemm.hip's persistent kernel)

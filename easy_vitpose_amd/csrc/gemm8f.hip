@@ -172,7 +172,7 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
         for (int j = 0; j < 4; ++j) xs[j] = rd8(sb + C::OFF_X0, xoff + j * 2048);
         __builtin_amdgcn_sched_barrier(0);
         issue(1, B ^ 1, kA, sx1[B ^ 1]);
-        if constexpr (MODE != 1) wait_vm<NKEEP>();
+        if constexpr (MODE != 1) wait_vmcnt<NKEEP>();
         asm volatile("" : "+v"(sx1[B]));     // retired by the wait above: re-defined HERE for the compiler, so that no copy or use of it can move in front of the wait
         wait_lgkm<0>();
         bar();
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
         issue(2, B, kB, dummy);
         issue(0, B, kB, sx0[B]);
         issue(3, B, kB, dummy);
-        if constexpr (MODE == 2) wait_vm<NLB>(); else wait_vm<NKEEP>();
+        if constexpr (MODE == 2) wait_vmcnt<NLB>(); else wait_vmcnt<NKEEP>();
         asm volatile("" : "+v"(sx0[B ^ 1]));   // retired by the wait above (read by the next K-tile's first MFMA section)
         wait_lgkm<0>();
         bar();
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
         int dummy;
         issue(2, 0, 0, dummy); issue(0, 0, 0, sx0[0]); issue(3, 0, 0, dummy); issue(1, 0, 0, sx1[0]);
         issue(2, 1, 1, dummy); issue(0, 1, 1, sx0[1]); issue(3, 1, 1, dummy);
-        wait_vm<NLB>();
+        wait_vmcnt<NLB>();
         bar();
         if (wr) bar();
     };
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
             auto tile_row = [&](int p, int lr) {
                 return (p / (4 / JPP)) * 128 + (lr / (16 * JPP)) * 64 + ((p % (4 / JPP)) * JPP + (lr / 16) % JPP) * 16 + (lr & 15);
             };
-            wait_vm<0>();
+            wait_vmcnt<0>();
             // The scale dwords the tile-boundary run-ahead fetched are dead in this variant (ring_start below fetches them again), and a
             // register hipcc considers dead is reused at once -- while the untracked load into it is still in flight (this was a memory
             // fault: a landed scale overwrote an epilogue address).  Keep the four registers allocated until the loads have retired.
@@ -451,7 +451,7 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
                     *(u32x4*)(out_hi + so) = oh;
                     *(u32x4*)(out_lo + so) = ol;
                     float s1s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                    s1s = row8_sum8(s1s);
+                    s1s = row8_sum(s1s);
                     const float mg = s1s * (1.0f / 64.0f);
                     float s2 = 0.f;
 #pragma unroll
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
                         const float d = v[e] - mg;
                         s2 = fmaf(d, d, s2);
                     }
-                    s2 = row8_sum8(s2);
+                    s2 = row8_sum(s2);
                     if ((ch & 7) == 0) *(float2*)(statbuf + (tile_row(p, lr) * GR + (ch >> 3)) * 2) = float2{s1s, s2};
                 }
                 __syncthreads();
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
         m0 = nm0;
         n0 = nn0;
     }
-    wait_vm<0>();
+    wait_vmcnt<0>();
     asm volatile("" ::"v"(sx0[0]), "v"(sx0[1]), "v"(sx1[0]), "v"(sx1[1]));   // see the residual epilogue: live until the run-ahead loads have landed
     if constexpr (!RESID_LDS) {
         if (!wr) bar();

@@ -6,7 +6,7 @@
 
 // Two builds of the same sources (easy_vitpose_amd/build.py): the PRODUCT library (libvitpose_hip.so) and, with -DVP_TOOLS, the
 // measurement library tools/ loads (libvitpose_hip_tools.so): ablation flags and start stagger inside the GEMM loops, cycle
-// stamps, the experimental tile configurations and kernel variants, the development environment switches -- and two translation
+// stamps, the candidate rows of the tile table (tiles.h) and kernel variants, the development environment switches -- and two translation
 // units of its own, probes.hip and tools_taps.hip.  In the product build GemmArgs::ablate / ::stagger read as the constant 0, so
 // none of those branches exists in its kernels.
 #ifdef VP_TOOLS

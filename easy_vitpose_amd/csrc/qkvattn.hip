@@ -136,8 +136,8 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
             for (int kk = 0; kk < 2; ++kk) xs[j][kk] = *(const u32x4*)(sb + QA::OFF_X0 + ((xoff + j * 2048) ^ (kk << 6)));
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (MODE != 3) issue(1, B ^ 1, kA);
-        if constexpr (MODE == 3) wait_vm<0>();
-        else if constexpr (MODE != 1) wait_vm<NKEEP>();
+        if constexpr (MODE == 3) wait_vmcnt<0>();
+        else if constexpr (MODE != 1) wait_vmcnt<NKEEP>();
         wait_lgkm<0>();
         bar();
         __builtin_amdgcn_s_setprio(1);
@@ -161,9 +161,9 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
             issue(2, B, kB);
             issue(0, B, kB);
             issue(3, B, kB);
-            wait_vm<NKEEP>();
+            wait_vmcnt<NKEEP>();
         } else if constexpr (MODE == 2) {
-            wait_vm<3>();   // X0 / W0 / W1 of the last K-tile (issued one LB ago) have landed; this LA's three X1 pieces stay in flight
+            wait_vmcnt<3>();   // X0 / W0 / W1 of the last K-tile (issued one LB ago) have landed; this LA's three X1 pieces stay in flight
         }
         wait_lgkm<0>();
         bar();
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
     auto ring_start = [&]() {
         issue(2, 0, 0); issue(0, 0, 0); issue(3, 0, 0); issue(1, 0, 0);
         issue(2, 1, 1); issue(0, 1, 1); issue(3, 1, 1);
-        wait_vm<6>();
+        wait_vmcnt<6>();
         bar();
         if (wr) bar();   // stagger: waves 4-7 run one barrier behind waves 0-3
     };
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
         const float* rs0 = g.rowstat + 2 * ((size_t)pair * 384 + wr * 96 + frow_e);   // crop 0 of the pair; crop 1: + 2 * 192 floats
 #pragma unroll
         for (int j = 0; j < 6; ++j) stat[j] = *(const float2*)(rs0 + 32 * j);          // crop 1's six follow inside the epilogue, under crop 0's stores
-        wait_vm<0>();
+        wait_vmcnt<0>();
         if (!wr) bar();     // undo the stagger: both groups meet here
         __syncthreads();    // every wave is done with the ring
 
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
         __syncthreads();    // every wave is done reading V before the rest of the ring refills the LDS
         if (prefetched) {   // K-tile 0 and X0 of K-tile 1 are on their way since the middle of the attention phase: W0, W1 of K-tile 1 complete ring_start's state
             issue(2, 1, 1); issue(3, 1, 1);
-            wait_vm<6>();   // leaves X0 / W0 / W1 of K-tile 1 (this tile's output stores are older than any load the count lets pass)
+            wait_vmcnt<6>();   // leaves X0 / W0 / W1 of K-tile 1 (this tile's output stores are older than any load the count lets pass)
             bar();
             if (wr) bar();
         } else {

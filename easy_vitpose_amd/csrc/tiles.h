@@ -12,62 +12,57 @@ namespace vp {
 // id = GemmArgs::variant.  product: instantiated in the product library (the ids a rule of tile_rules.hip can return); every row is instantiated in the
 // measurement build (-DVP_TOOLS).  partial: instantiated for EPI_PARTIAL (the tiles pick_splitk may name for the split-K partial products).
 struct TileRow {
-    int id, BM, BN, BK, WM, WN, STAGES, PIPE, DIRECT;
+    int id, BM, BN, BK, WM, WN, STAGES, PIPE;
     bool product, partial;
 };
 
+// PIPE = the k-step schedule: 0 plain, 1 the fragment reads of k-half 1 issued inside the MFMAs of k-half 0, 6 two k-blocks per barrier.
 // Measured on MI355X at M = 49152 (tools/gemm_tune.py, profiles/gemm_tune_r1.txt).  Default = id 8: one 192-token crop per m-tile, so the tile count divides
 // evenly over 256 CUs x 2 resident blocks for every encoder GEMM (no tail wave), and the epilogue of one block overlaps the main loop of its CU partner.
-// The others are kept as measured alternatives: 256x256 halves the L2->LDS operand traffic but runs 1 block / CU (epilogue exposed, tail wave at N = D);
-// id 6 is the staggered two-group (anti-phase wave pairs) schedule; id 5 the fragment-store A/B reference; id 10 = id 8 with hand-scheduled inline-asm
-// ds_reads and counted lgkmcnt (bare loop +7 %, end to end +0-2 %: the operand stream, not the intra-wave schedule, is what bounds these GEMMs).
+// 256x256 halves the L2->LDS operand traffic but runs 1 block / CU (epilogue exposed, tail wave at N = D).
 // id 11 = the id 8 block tile cut into 8 wave tiles of 48x64: same main-loop rate (LDS reads are at 18 % utilisation, so the smaller wave tile costs
 // nothing), but twice the threads for the VALU-heavy residual epilogue (plane split + LayerNorm statistics): proj+fc2 4.54 -> 4.30 ms per step; no gain
 // for qkv / fc1, slower for the deconvs (96x32 wave tiles: -25 %).
+// Ids 4, 5, 6 and 10 are retired: register double-buffered fragments (PIPE 2), fragment-shaped epilogue stores, the staggered two-group schedule (PIPE 3)
+// and hand-scheduled ds_reads with counted lgkmcnt (PIPE 5) all lost; their code can be read from commit a3d3210.
 // The trailing columns of the comments (ring KiB, waves, blocks / CU) are what tile_ring_bytes / tile_threads / tile_wgs_per_cu below compute.
 inline constexpr TileRow TILES[] = {
-    // id   BM   BN  BK   WM  WN ST PIPE DIRECT product partial
-    {0, 128, 128, 64, 64, 64, 2, 0, 0, false, false},    //  64 KiB   4   (2 blocks / CU)
-    {1, 128, 128, 64, 64, 64, 2, 1, 0, true, true},      //  same + pipelined fragment reads
-    {2, 256, 256, 64, 128, 64, 2, 0, 0, false, false},   // 128 KiB   8   (1 block / CU)
-    {3, 256, 256, 64, 128, 64, 2, 1, 0, true, false},    //  same + pipelined fragment reads
-    {4, 256, 256, 32, 128, 64, 4, 2, 0, false, false},   // 128 KiB   8   4-stage ring, register double-buffered fragments
-    {5, 128, 128, 64, 64, 64, 2, 0, 1, false, false},    //  id 0 with fragment-shaped epilogue stores (A/B reference)
-    {6, 256, 256, 32, 128, 64, 4, 3, 0, false, false},   // 128 KiB   8   staggered two-group schedule
-    {7, 192, 256, 64, 96, 64, 2, 1, 0, false, false},    // 112 KiB   8   (1 block / CU)
-    {8, 192, 128, 64, 96, 64, 2, 1, 0, true, false},     //  80 KiB   4   (2 blocks / CU)  <- default
-    {9, 64, 64, 64, 32, 32, 2, 0, 0, true, false},       //  32 KiB   4   (5 blocks / CU)  small batches: enough tiles to fill 256 CUs
-    {10, 192, 128, 64, 96, 64, 2, 5, 0, false, false},   //  id 8 with the hand-scheduled (inline-asm ds_read, counted lgkmcnt) fragment pipeline
-    {11, 192, 128, 64, 48, 64, 2, 1, 0, true, true},     //  80 KiB   8   id 8 tile as 8 waves of 48x64 (4 waves / SIMD, 122 VGPRs)  <- default for the residual GEMMs
+    // id   BM   BN  BK   WM  WN ST PIPE product partial
+    {0, 128, 128, 64, 64, 64, 2, 0, false, false},    //  64 KiB   4   (2 blocks / CU)
+    {1, 128, 128, 64, 64, 64, 2, 1, true, true},      //  same + pipelined fragment reads
+    {2, 256, 256, 64, 128, 64, 2, 0, false, false},   // 128 KiB   8   (1 block / CU)
+    {3, 256, 256, 64, 128, 64, 2, 1, true, false},    //  same + pipelined fragment reads
+    {7, 192, 256, 64, 96, 64, 2, 1, false, false},    // 112 KiB   8   (1 block / CU)
+    {8, 192, 128, 64, 96, 64, 2, 1, true, false},     //  80 KiB   4   (2 blocks / CU)  <- default
+    {9, 64, 64, 64, 32, 32, 2, 0, true, false},       //  32 KiB   4   (5 blocks / CU)  small batches: enough tiles to fill 256 CUs
+    {11, 192, 128, 64, 48, 64, 2, 1, true, true},     //  80 KiB   8   id 8 tile as 8 waves of 48x64 (4 waves / SIMD, 122 VGPRs)  <- default for the residual GEMMs
     // small batches (a few crops per GPU): the 2-stage ring waits for every k-block's full L2 latency; deeper rings keep 2-3 blocks in flight
-    {12, 64, 64, 64, 32, 32, 4, 0, 0, true, true},       //  64 KiB   4   (2 blocks / CU)  id 9 with a 4-stage ring
-    {13, 128, 128, 64, 64, 64, 3, 1, 0, false, false},   //  96 KiB   4   (1 block / CU)   id 1 with a 3-stage ring
-    {14, 64, 64, 64, 32, 32, 3, 0, 0, false, false},     //  48 KiB   4   (3 blocks / CU)  id 9 with a 3-stage ring
-    {15, 128, 64, 64, 64, 32, 3, 0, 0, true, true},      //  72 KiB   4   (2 blocks / CU)  128(m) x 64(n), 3-stage ring
+    {12, 64, 64, 64, 32, 32, 4, 0, true, true},       //  64 KiB   4   (2 blocks / CU)  id 9 with a 4-stage ring
+    {13, 128, 128, 64, 64, 64, 3, 1, false, false},   //  96 KiB   4   (1 block / CU)   id 1 with a 3-stage ring
+    {14, 64, 64, 64, 32, 32, 3, 0, false, false},     //  48 KiB   4   (3 blocks / CU)  id 9 with a 3-stage ring
+    {15, 128, 64, 64, 64, 32, 3, 0, true, true},      //  72 KiB   4   (2 blocks / CU)  128(m) x 64(n), 3-stage ring
     // (16-18 = the 8-phase kernel: TILES8 below.)  Round 5, small batches IN SITU: every layer's weights are first touched from HBM (ViTPose-L: 25 MB per layer,
     // 600 MB per forward -- more than L2 + the memory-side cache hold), so a k-block costs an HBM round trip, not the L2 hit the isolated sweeps of rounds 2-3 saw:
     // a workgroup retires STAGES - 1 k-blocks per round trip whatever its tile, and one full round of workgroups with a deep ring beats more, smaller tiles.
-    {19, 192, 128, 64, 96, 64, 3, 1, 0, false, false},   // 120 KiB   4   (1 block / CU)   id 8 with a 3-stage ring
-    {20, 192, 128, 64, 48, 64, 3, 1, 0, true, true},     // 120 KiB   8   (1 block / CU)   id 11 with a 3-stage ring
-    {21, 64, 64, 64, 32, 32, 5, 0, 0, false, false},     //  80 KiB   4   (2 blocks / CU)  id 9 with a 5-stage ring
-    {22, 128, 64, 64, 64, 32, 6, 0, 0, false, false},    // 144 KiB   4   (1 block / CU)   128(m) x 64(n), 6-stage ring
-    {23, 64, 64, 64, 32, 32, 8, 0, 0, false, false},     // 128 KiB   4   (1 block / CU)   id 9 with an 8-stage ring
-    {24, 128, 128, 64, 64, 64, 4, 1, 0, false, false},   // 128 KiB   4   (1 block / CU)   id 1 with a 4-stage ring
-    {25, 128, 128, 32, 64, 64, 4, 0, 0, false, false},   //  64 KiB   4   (2 blocks / CU)  128 x 128 with k-blocks of 32: 4-stage ring in id 1's LDS
-    {26, 128, 128, 32, 64, 64, 5, 0, 0, false, false},   //  80 KiB   4   (2 blocks / CU)  ... 5-stage
-    {27, 64, 64, 64, 32, 32, 4, 1, 0, false, false},     //  64 KiB   4   (2 blocks / CU)  id 12 with pipelined fragment reads
-    {28, 64, 64, 64, 32, 32, 5, 6, 0, false, false},     //  80 KiB   4   (2 blocks / CU)  64 x 64, two k-blocks per barrier, 5-stage ring (3 k-blocks in flight)
-    {29, 64, 64, 64, 32, 32, 4, 6, 0, false, false},     //  64 KiB   4   (2 blocks / CU)  ... 4-stage ring (2 in flight)
-    {30, 64, 64, 64, 32, 32, 6, 6, 0, true, true},       //  96 KiB   4   (1 block / CU)   ... 6-stage ring (4 in flight)
-    {31, 32, 64, 64, 16, 32, 6, 6, 0, true, true},       //  72 KiB   4   (2 blocks / CU)  32(m) x 64(n): twice the workgroups of a 1-2 crop GEMM, half the MFMAs per wave and k-block
-    {32, 32, 64, 64, 16, 32, 8, 6, 0, false, false},     //  96 KiB   4   (1 block / CU)   ... 8-stage ring (6 in flight)
-    {41, 96, 64, 64, 48, 32, 4, 0, 0, true, false},      //  80 KiB   4   (2 blocks / CU)  96(m) x 64(n), 4-stage ring: the residual GEMMs between the 64 x 64 and 128 x 64 regimes (round 6: <= 448 tiles;
-                                                         //                                 ViTPose-L 11-14 crops, -B 15-18, -H 9-11: profiles/small_batch_r6.txt call 18)
+    {19, 192, 128, 64, 96, 64, 3, 1, false, false},   // 120 KiB   4   (1 block / CU)   id 8 with a 3-stage ring
+    {20, 192, 128, 64, 48, 64, 3, 1, true, true},     // 120 KiB   8   (1 block / CU)   id 11 with a 3-stage ring
+    {21, 64, 64, 64, 32, 32, 5, 0, false, false},     //  80 KiB   4   (2 blocks / CU)  id 9 with a 5-stage ring
+    {22, 128, 64, 64, 64, 32, 6, 0, false, false},    // 144 KiB   4   (1 block / CU)   128(m) x 64(n), 6-stage ring
+    {23, 64, 64, 64, 32, 32, 8, 0, false, false},     // 128 KiB   4   (1 block / CU)   id 9 with an 8-stage ring
+    {24, 128, 128, 64, 64, 64, 4, 1, false, false},   // 128 KiB   4   (1 block / CU)   id 1 with a 4-stage ring
+    {25, 128, 128, 32, 64, 64, 4, 0, false, false},   //  64 KiB   4   (2 blocks / CU)  128 x 128 with k-blocks of 32: 4-stage ring in id 1's LDS
+    {26, 128, 128, 32, 64, 64, 5, 0, false, false},   //  80 KiB   4   (2 blocks / CU)  ... 5-stage
+    {27, 64, 64, 64, 32, 32, 4, 1, false, false},     //  64 KiB   4   (2 blocks / CU)  id 12 with pipelined fragment reads
+    {28, 64, 64, 64, 32, 32, 5, 6, false, false},     //  80 KiB   4   (2 blocks / CU)  64 x 64, two k-blocks per barrier, 5-stage ring (3 k-blocks in flight)
+    {29, 64, 64, 64, 32, 32, 4, 6, false, false},     //  64 KiB   4   (2 blocks / CU)  ... 4-stage ring (2 in flight)
+    {30, 64, 64, 64, 32, 32, 6, 6, true, true},       //  96 KiB   4   (1 block / CU)   ... 6-stage ring (4 in flight)
+    {31, 32, 64, 64, 16, 32, 6, 6, true, true},       //  72 KiB   4   (2 blocks / CU)  32(m) x 64(n): twice the workgroups of a 1-2 crop GEMM, half the MFMAs per wave and k-block
+    {32, 32, 64, 64, 16, 32, 8, 6, false, false},     //  96 KiB   4   (1 block / CU)   ... 8-stage ring (6 in flight)
+    {41, 96, 64, 64, 48, 32, 4, 0, true, false},      //  80 KiB   4   (2 blocks / CU)  96(m) x 64(n), 4-stage ring: the residual GEMMs between the 64 x 64 and 128 x 64 regimes (round 6: <= 448 tiles;
+                                                      //                                 ViTPose-L 11-14 crops, -B 15-18, -H 9-11: profiles/small_batch_r6.txt call 18)
 };
-// (round 6: the staggered two-group schedule -- PIPE 3, waves 0-3 / 4-7 one barrier apart -- on 256 x 128 / 128 x 128 / 128 x 256 tiles with k-blocks of 32 was measured for the
-// 8-crop wide GEMMs and lost everywhere, +8 ... +25 % per step, as did register double-buffered fragments -- PIPE 2 -- on 192 x 128 / 128 x 128 / 128 x 64 / 64 x 64 tiles with k-blocks of 32,
-// +3 ... +20 %: profiles/small_batch_r6.txt calls 9-10; the configurations are not kept.  Also measured and not kept (calls 13, 15): a 4-stage ring on the one-round
-// 192 x 128 tile (+1 %), the 96 x 64 tile with a 6-stage ring / two k-blocks per barrier (loses wherever the 4-stage one wins).)
+// (round 6, measured and not kept -- profiles/small_batch_r6.txt calls 13, 15: a 4-stage ring on the one-round 192 x 128 tile (+1 %), the 96 x 64 tile with a 6-stage ring /
+// two k-blocks per barrier (loses wherever the 4-stage one wins).)
 inline constexpr int NUM_TILES = (int)(sizeof(TILES) / sizeof(TILES[0]));
 
 // the row of an id, or nullptr

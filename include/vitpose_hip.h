@@ -452,7 +452,7 @@ VP_API int vp_set_profiling(vp_handle h, int32_t family_mask);
 VP_API int vp_reset_profile(vp_handle h);
 VP_API int vp_get_profile(vp_handle h, vp_profile* out);
 /* Name of the kernel the LAST launch of family `family` (VP_PROF_*) ran on, as the profiler prints it minus the namespace
- * (e.g. "gemm8_kernel<F16, 1, G8<256>>", "gemm_kernel<F16, 6, 0, TileCfg<192, 128, 64, 48, 64, 2, 1, 0>>"), written by the
+ * (e.g. "gemm8_kernel<F16, 1, G8<256>>", "gemm_kernel<F16, 6, 0, TileCfg<192, 128, 64, 48, 64, 2, 1>>"), written by the
  * launch code itself: bench.py reads `roofline.kernel` from here instead of restating the selection rule.  Empty string when
  * the family has not been launched yet.  Returns VP_ERR_INVALID for a bad family / NULL buffer. */
 VP_API int vp_profile_kernel(vp_handle h, int32_t family, char* buf, int32_t cap);

@@ -1,8 +1,8 @@
 /*
  * vitpose_hip_tools.h -- entry points of the MEASUREMENT build only (libvitpose_hip_tools.so = the sources of
  * libvitpose_hip.so compiled with -DVP_TOOLS, easy_vitpose_amd/build.py): cycle-stamp timelines of the GEMM kernels.  The
- * measurement build additionally honours GemmArgs::ablate / ::stagger inside the kernels, instantiates the experimental tile
- * configurations (the rows of csrc/tiles.h not marked `product`) and reads the
+ * measurement build additionally honours GemmArgs::ablate / ::stagger inside the kernels, instantiates the candidate tile
+ * configurations (the rows of csrc/tiles.h not marked `product`: what the sweeps of tools/ measure) and reads the
  * development environment switches.  tools/ loads it; the product path and tests/ never do.
  */
 #ifndef VITPOSE_HIP_TOOLS_H

@@ -101,9 +101,9 @@ def dark_conditioned(heatmaps: np.ndarray, vmin: float = 0.05) -> np.ndarray:
 PLAN_GEMMS = ('patch', 'qkv', 'proj', 'fc1', 'fc2', 'deconv1', 'deconv2', 'final')
 PICK_FIELDS = ('variant', 'group_m', 'persist', 'stagger', 'splitk', 'splitk_variant')
 # gemm.hip Cfg id -> TileCfg parameters, as the launch code names the kernel (vp_profile_kernel)
-TILE_CFGS = {1: '128, 128, 64, 64, 64, 2, 1, 0', 3: '256, 256, 64, 128, 64, 2, 1, 0', 8: '192, 128, 64, 96, 64, 2, 1, 0', 9: '64, 64, 64, 32, 32, 2, 0, 0',
-             11: '192, 128, 64, 48, 64, 2, 1, 0', 12: '64, 64, 64, 32, 32, 4, 0, 0', 15: '128, 64, 64, 64, 32, 3, 0, 0', 20: '192, 128, 64, 48, 64, 3, 1, 0',
-             30: '64, 64, 64, 32, 32, 6, 6, 0', 31: '32, 64, 64, 16, 32, 6, 6, 0', 41: '96, 64, 64, 48, 32, 4, 0, 0'}
+TILE_CFGS = {1: '128, 128, 64, 64, 64, 2, 1', 3: '256, 256, 64, 128, 64, 2, 1', 8: '192, 128, 64, 96, 64, 2, 1', 9: '64, 64, 64, 32, 32, 2, 0',
+             11: '192, 128, 64, 48, 64, 2, 1', 12: '64, 64, 64, 32, 32, 4, 0', 15: '128, 64, 64, 64, 32, 3, 0', 20: '192, 128, 64, 48, 64, 3, 1',
+             30: '64, 64, 64, 32, 32, 6, 6', 31: '32, 64, 64, 16, 32, 6, 6', 41: '96, 64, 64, 48, 32, 4, 0'}
 
 
 def chunk_plan(shape, dtype: str, max_batch: int, n: int) -> dict:

@@ -142,7 +142,7 @@ def test_distributed_step_never_blocks_the_host_between_inference_and_collective
     """the all-gather is enqueued behind the keypoints on the device's stream -- no host synchronisation between the
     inference call and the collective (bench.py's distributed step used to pass sync=True).  The fake engine and the
     patched collectives record the host-side call order at world size 2: inside a weak-scaling step and inside a strong-scaled frame
-    every inference call is un-synchronised and is followed DIRECTLY by the all-gather; the host blocks only in the fences."""
+    every inference call is un-synchronised and is followed directly by the all-gather; the host blocks only in the fences."""
     world = 2
     ctx = mp.get_context('spawn')
     q = ctx.Queue()

@@ -1,6 +1,6 @@
 """Every script under tools/ imports this first: it points the ctypes binding at the MEASUREMENT build of the library
 (libvitpose_hip_tools.so = the product sources compiled with -DVP_TOOLS: ablation flags, start stagger and cycle stamps inside the
-GEMM kernels, the experimental tile configurations and kernel variants, the development environment switches -- see
+GEMM kernels, the candidate rows of the tile table and kernel variants, the development environment switches -- see
 include/vitpose_hip_tools.h).  Build it in the build container (`python -m easy_vitpose_amd.build --tools`); the .so travels to the
 GPU box with the gpurun snapshot.  An explicit VP_HIP_LIB (tools/ab.sh) wins."""
 import os
