@@ -154,6 +154,61 @@ __device__ __forceinline__ float row8_sum(float x) {
     return x;
 }
 
+// ---- the producer row of the two-plane residual stream ----
+// v = st + (hi + lo), clamped and split into the output planes, with the (sum, M2 about the granule's own mean) statistics of every 64-column granule (merged
+// exactly by ln_merge: Chan et al., so the fused path has the two-pass LayerNorm's robustness to rows with a large common offset).  ONE definition for the
+// producer epilogues of gemm.hip, gemm8.hip and gemm8f.hip and for splitk_reduce_kernel: their bit identity is the race screen of the GEMM test matrix and what
+// lets a plan pick any tile for attn.proj and mlp.fc2.  A site keeps only where `st` comes from, its addresses and who stores the statistics.
+
+// the residual operand r of v = st + r: column e of 8 consecutive columns, r = hi + lo from the two planes' 16 bytes (the caller adds st + (hi + lo), in
+// that order)
+template <class T> __device__ __forceinline__ float planes_decode8(u32x4 hi, u32x4 lo, int e) {
+    const int sh = (e & 1) * 16;
+    return from_bits<T>((uint16_t)(hi[e >> 1] >> sh)) + from_bits<T>((uint16_t)(lo[e >> 1] >> sh));
+}
+// 8 consecutive columns -> their 16 bytes of each output plane.  v is clamped to the 16-bit range IN PLACE: the statistics are taken afterwards, of the value
+// that was stored
+template <class T> __device__ __forceinline__ void planes_split8(float* v, u32x4& oh, u32x4& ol) {
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+        uint32_t h, l;
+        split_planes2<T>(v[e], v[e + 1], h, l);
+        oh[e >> 1] = h;
+        ol[e >> 1] = l;
+    }
+}
+// The summation tree of a granule: per 8-column chunk ((v0+v1)+(v2+v3))+((v4+v5)+(v6+v7)) and, for M2, the fmaf(d, d, .) chain in column order about
+// mg = s1 / 64; then chunk pairs, then pairs of pairs.  Two lane layouts walk that ONE tree, and (s1, s2) reaches every lane of the granule:
+__device__ __forceinline__ float chunk8_sum(const float* v) { return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7])); }
+__device__ __forceinline__ float chunk8_m2(const float* v, float mg) {
+    float s2 = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float d = v[e] - mg;
+        s2 = fmaf(d, d, s2);
+    }
+    return s2;
+}
+// sum over the 4 lanes {l, l ^ 16, l ^ 32, l ^ 48}: chunk pairs live in one lane there, so this is row8_sum's second and third step
+__device__ __forceinline__ float quad16_sum(float x) {
+    x += __shfl_xor(x, 16, 64);
+    x += __shfl_xor(x, 32, 64);
+    return x;
+}
+// 8 columns per lane, the granule = 8 aligned lanes (LDS-staged epilogues, split-K reduction): chunk | 3 DPP steps
+__device__ __forceinline__ float2 granule_stats8(const float* v) {
+    const float s1 = row8_sum(chunk8_sum(v));
+    const float s2 = row8_sum(chunk8_m2(v, s1 * (1.0f / 64.0f)));
+    return float2{s1, s2};
+}
+// 16 columns per lane, the granule = the 4 lanes of a row (register-direct epilogues): 2 chunks | 1 add in the lane, 2 cross-lane steps
+__device__ __forceinline__ float2 granule_stats16(const float* v) {
+    const float s1 = quad16_sum(chunk8_sum(v) + chunk8_sum(v + 8));
+    const float mg = s1 * (1.0f / 64.0f);
+    const float s2 = quad16_sum(chunk8_m2(v, mg) + chunk8_m2(v + 8, mg));
+    return float2{s1, s2};
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

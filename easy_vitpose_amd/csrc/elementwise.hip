@@ -387,9 +387,8 @@ __global__ __launch_bounds__(64) void ln_finalize_kernel_t(const float* __restri
 }
 
 // Split-K reduction of a residual GEMM (round 6, small batches; gemm.hip EPI_PARTIAL): the S fp32 partial products of every output element are added in the
-// FIXED order s = 0 .. S - 1 (run-to-run deterministic; no atomics), then bias and the residual (hi + lo planes) exactly as the EPI_BIAS_RESID_LN epilogue adds
-// them -- st = sum + bias, v = st + (hi + lo) -- and the row leaves as the two planes + the (sum, centred M2) statistics of its 64-column granules (8 lanes of
-// 8 columns each, DPP adds in the epilogue's order).  One 8-column chunk per thread; every load of a thread is issued before the first add.
+// FIXED order s = 0 .. S - 1 (run-to-run deterministic; no atomics); st = sum + bias then goes through the producer row of common.h (planes_decode8,
+// planes_split8, granule_stats8) like the EPI_BIAS_RESID_LN epilogue's.  One 8-column chunk per thread; every load of a thread is issued before the first add.
 template <class T, int SMAX>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int S, const float* __restrict__ bias, uint16_t* __restrict__ x_hi,
                                                             size_t plane, float* __restrict__ stats_out, int M, int N) {
@@ -417,28 +416,14 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
             if (s < S) { a0 += p0[s]; a1 += p1[s]; }
         a0 += b0; a1 += b1;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int sh = (e & 1) * 16;
-            const float r = from_bits<T>((uint16_t)(ra[e >> 1] >> sh)) + from_bits<T>((uint16_t)(rb[e >> 1] >> sh));
-            v[e] = (e < 4 ? a0[e] : a1[e - 4]) + r;
-        }
+        for (int e = 0; e < 8; ++e) v[e] = (e < 4 ? a0[e] : a1[e - 4]) + planes_decode8<T>(ra, rb, e);
         u32x4 oh, ol;
-#pragma unroll
-        for (int e = 0; e < 8; e += 2) { uint32_t h_, l_; split_planes2<T>(v[e], v[e + 1], h_, l_); oh[e >> 1] = h_; ol[e >> 1] = l_; }
+        planes_split8<T>(v, oh, ol);
         *(u32x4*)(x_hi + off) = oh;
         *(u32x4*)(x_hi + plane + off) = ol;
     }
-    float s1 = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    s1 = row8_sum(s1);
-    const float mg = s1 * (1.0f / 64.0f);
-    float s2 = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float d = v[e] - mg;
-        s2 = fmaf(d, d, s2);
-    }
-    s2 = row8_sum(s2);
-    if (ok && (ch & 7) == 0) *(float2*)(stats_out + ((size_t)m * (N >> 6) + (ch >> 3)) * 2) = float2{s1, s2};
+    const float2 gs = granule_stats8(v);
+    if (ok && (ch & 7) == 0) *(float2*)(stats_out + ((size_t)m * (N >> 6) + (ch >> 3)) * 2) = gs;
 }
 
 hipError_t splitk_reduce_launch(int dtype, const float* partials, int S, const float* bias, uint16_t* x_hi, size_t plane, float* stats_out, int M, int N,

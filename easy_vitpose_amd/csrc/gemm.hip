@@ -404,9 +404,9 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(GemmArgs g) {
         // fp32 (>= 22 significant bits), but the hi plane IS the un-normalised 16-bit operand the next qkv / fc1
         // GEMM reads, so the fusion needs no extra copy.  Rows leave the LDS staging as 8-element chunks: two
         // 16-byte plane loads (residual) and two 16-byte plane stores per lane -- the same instruction count as
-        // the fp32 epilogue.  Partial row statistics (sum, centred sum of squares) are taken per 64-column granule = 8
-        // aligned lanes (DPP adds, fixed order: independent of the tile shape, hence of the batch size), parked in
-        // LDS and written once per tile.
+        // the fp32 epilogue.  Partial row statistics are taken per 64-column granule = 8 aligned lanes, parked in LDS
+        // and written once per tile.  The row arithmetic itself is common.h's (planes_decode8, planes_split8,
+        // granule_stats8: independent of the tile shape, hence of the batch size).
         constexpr int ROWBYTES = C::BN * 4 + 16;
         constexpr int JP = epi_rows_per_pass_ln<C>();
         constexpr int CR = C::NWM * JP * 16;          // rows staged per pass
@@ -469,40 +469,21 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(GemmArgs g) {
                     const f32x4 s1 = *(const f32x4*)(smem + lr * ROWBYTES + ch * 32 + 16);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        const float st = e < 4 ? s0[e] : s1[e - 4];
-                        float r;
-                        if (EPI == EPI_POS) {
-                            r = __builtin_bit_cast(float, e < 4 ? ra[q][e] : rb[q][e - 4]);
-                        } else {
-                            const int sh = (e & 1) * 16;
-                            r = from_bits<T>((uint16_t)(ra[q][e >> 1] >> sh)) + from_bits<T>((uint16_t)(rb[q][e >> 1] >> sh));
-                        }
-                        v[e] = st + r;
+                        const float r = EPI == EPI_POS ? __builtin_bit_cast(float, e < 4 ? ra[q][e] : rb[q][e - 4]) : planes_decode8<T>(ra[q], rb[q], e);
+                        v[e] = (e < 4 ? s0[e] : s1[e - 4]) + r;
                     }
                     u32x4 oh, ol;
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) { uint32_t h_, l_; split_planes2<T>(v[e], v[e + 1], h_, l_); oh[e >> 1] = h_; ol[e >> 1] = l_; }   // clamps v to the 16-bit range (statistics below see the stored value)
+                    planes_split8<T>(v, oh, ol);
                     if (!(VP_ABLATE(g) & 8)) {
                         *(u32x4*)(out_hi + orow_q[q] + n0 + ch * 8) = oh;
                         *(u32x4*)(out_lo + orow_q[q] + n0 + ch * 8) = ol;
                     }
                 }
-                // granule statistics as (sum, M2 about the granule's own mean): merged exactly by ln_finalize (Chan et
-                // al.), so the fused path has the two-pass LayerNorm's robustness to rows with a large common offset
-                float s1 = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                s1 = row8_sum(s1);
-                const float mg = s1 * (1.0f / 64.0f);
-                float s2 = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float d = v[e] - mg;
-                    s2 = fmaf(d, d, s2);
-                }
-                s2 = row8_sum(s2);
+                const float2 gs = granule_stats8(v);   // every lane of a granule takes part: lanes outside the matrix hold zeros
                 if ((ch & 7) == 0) {
                     const int wmr = lr / (JP * 16), rr = lr - wmr * (JP * 16);
                     const int trow = wmr * C::WM + p * JP * 16 + rr;
-                    *(float2*)(statbuf + (trow * GR + (ch >> 3)) * 2) = float2{s1, s2};
+                    *(float2*)(statbuf + (trow * GR + (ch >> 3)) * 2) = gs;
                 }
             }
             if (p + 1 < C::TJ / JP) __syncthreads();
@@ -919,14 +900,8 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_persist_kernel(GemmArgs g) {
 template <class T, int EPI, class C>
 static hipError_t launch_persist(const GemmArgs& a, hipStream_t s) {
     auto kern = gemm_persist_kernel<T, EPI, C>;
-    static bool attr_done[64] = {};   // the > 64 KiB LDS opt-in is a per-device function attribute
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) attr_done[dev] = true;
-    }
+    static bool attr_done[64] = {};
+    if (hipError_t e = lds_opt_in((const void*)kern, C::LDS, attr_done); e != hipSuccess) return e;
     const int tiles = ((a.M + C::BM - 1) / C::BM) * ((a.N + C::BN - 1) / C::BN);
     const int resident = 256 * (160 * 1024 / C::LDS);           // workgroups the chip holds at once
     int grid = tiles < resident ? tiles : resident;
@@ -964,14 +939,8 @@ static hipError_t launch(const GemmArgs& a, hipStream_t s) {
     static_assert(LDS_BYTES + LN_STAT_BYTES <= 160 * 1024, "LDS");
     if (C::PIPE == 6 && a.K % 128 != 0) return hipErrorInvalidValue;                                      // two k-blocks per barrier
     if (a.ln_part && (a.ln_tiles & 1)) return hipErrorInvalidValue;   // a row's partial statistics are fetched as 16-byte pieces: ln_tiles * 8 bytes must be a multiple of 16
-    static bool attr_done[2][64] = {};   // the > 64 KiB LDS opt-in is a per-device function attribute
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_done[ex][dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES + LN_STAT_BYTES);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) attr_done[ex][dev] = true;
-    }
+    static bool attr_done[2][64] = {};
+    if (hipError_t e = lds_opt_in((const void*)kern, LDS_BYTES + LN_STAT_BYTES, attr_done[ex]); e != hipSuccess) return e;
     GemmArgs g = a;
     const int tiles_n = (a.N + C::BN - 1) / C::BN;
     g.w_parity_stride = (size_t)a.w_rows * a.K;

@@ -38,8 +38,8 @@
 //    straight from registers as 16-byte pieces that complete 128-byte lines -- no LDS round trip, no epilogue barrier.
 //  * the residual epilogue (attn.proj / mlp.fc2: + bias + residual planes, two-plane output, LayerNorm row statistics):
 //    256 x 192 tiles stage the tile through LDS exactly like gemm.hip's producer epilogue; 256 x 256 tiles take it straight
-//    from registers (a row's four lanes are one 64-column statistics granule).  Both replicate gemm.hip's summation tree:
-//    bit-identical statistics.
+//    from registers (a row's four lanes are one 64-column statistics granule).  The row arithmetic is common.h's (planes_decode8,
+//    planes_split8, granule_stats8 / granule_stats16), as in every producer of the residual stream.
 //
 //  * 192(m) x 256(n) tiles (G8<256, 192>): X halves of 96 rows (12 DMA pieces: see gemm8_common.h for who issues which), three m-fragments
 //    per wave and half.  M of this model is always a multiple of 192 (a crop is 192 tokens) and N = 768 = 3 x 256: mlp.fc2 gets the
@@ -521,12 +521,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
         } else if constexpr (RESID && !RESID_LDS) {
             // ---- residual epilogue straight from registers (EPI_BIAS_RESID_LN on 256 x 256 tiles) ----
             // lane (fg_e, frow_e): rows m0 + (J >> 2) 128 + wr 64 + (J & 3) 16 + frow_e, columns nb .. nb + 15 (W rows are permuted on their
-            // way into LDS, see above).  v = acc + bias + (hi + lo) of the residual stream, written back as two 16-bit planes;
-            // LayerNorm partial statistics per (row, 64-column granule): the granule is the four lanes fg_e = 0..3 of a row, and the
-            // summation tree is gemm.hip's -- per 8-column chunk ((v0+v1)+(v2+v3))+((v4+v5)+(v6+v7)), then chunk pairs, then
-            // pairs of pairs (there: three DPP steps over 8 lanes; here: one add in the lane and two cross-lane adds) -- so the
-            // statistics and everything downstream stay bit-identical to the LDS-staged epilogues.  No LDS, no barrier: the operand
-            // ring runs on across the tile boundary exactly as for the 16-bit epilogues.
+            // way into LDS, see above).  st = acc + bias; the statistics granule is the four lanes fg_e = 0..3 of a row (common.h,
+            // granule_stats16).  No LDS, no barrier: the operand ring runs on across the tile boundary exactly as for the 16-bit epilogues.
             const int nb = n0 + wc * 64 + fg_e * 16;
             const int mrow = m0 + wr * (C::XR / 2) + frow_e;
             uint16_t* out_hi = (uint16_t*)g.out;
@@ -555,49 +551,24 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
                 const u32x4(&r)[4] = res[J % (RD + 1)];
                 const int m = mrow + rowJ(J);
                 const size_t o = (size_t)m * g.ldo + nb;
-                float v[16];
+                float v[16];   // column nb + c
 #pragma unroll
                 for (int f = 0; f < 4; ++f) {
                     const f32x4 st = acc[f][J] + bias4[f];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int c = f * 4 + e;                       // column nb + c
-                        const uint32_t wh = r[c >> 3][(c & 7) >> 1], wl = r[2 + (c >> 3)][(c & 7) >> 1];
-                        const int sh = (c & 1) * 16;
-                        v[c] = st[e] + (from_bits<T>((uint16_t)(wh >> sh)) + from_bits<T>((uint16_t)(wl >> sh)));
-                    }
+                    for (int e = 0; e < 4; ++e) v[f * 4 + e] = st[e] + planes_decode8<T>(r[f >> 1], r[2 + (f >> 1)], (f & 1) * 4 + e);
                 }
                 u32x4 oh[2], ol[2];
-#pragma unroll
-                for (int c = 0; c < 16; c += 2) {   // clamps v to the 16-bit range (the statistics below see the stored value)
-                    uint32_t h_, l_;
-                    split_planes2<T>(v[c], v[c + 1], h_, l_);
-                    oh[c >> 3][(c & 7) >> 1] = h_;
-                    ol[c >> 3][(c & 7) >> 1] = l_;
-                }
+                planes_split8<T>(v, oh[0], ol[0]);
+                planes_split8<T>(v + 8, oh[1], ol[1]);
                 if (store) {
                     *(u32x4*)(out_hi + o) = oh[0];
                     *(u32x4*)(out_hi + o + 8) = oh[1];
                     *(u32x4*)(out_lo + o) = ol[0];
                     *(u32x4*)(out_lo + o + 8) = ol[1];
                 }
-                float sa = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                float sb = ((v[8] + v[9]) + (v[10] + v[11])) + ((v[12] + v[13]) + (v[14] + v[15]));
-                float s1 = sa + sb;
-                s1 += __shfl_xor(s1, 16, 64);
-                s1 += __shfl_xor(s1, 32, 64);
-                const float mg = s1 * (1.0f / 64.0f);
-                float qa = 0.f, qb = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float da = v[e] - mg, db = v[8 + e] - mg;
-                    qa = fmaf(da, da, qa);
-                    qb = fmaf(db, db, qb);
-                }
-                float s2 = qa + qb;
-                s2 += __shfl_xor(s2, 16, 64);
-                s2 += __shfl_xor(s2, 32, 64);
-                if (fg_e == 0 && store) *(float2*)(g.stats_out + ((size_t)m * gran + (nb >> 6)) * 2) = float2{s1, s2};
+                const float2 gs = granule_stats16(v);
+                if (fg_e == 0 && store) *(float2*)(g.stats_out + ((size_t)m * gran + (nb >> 6)) * 2) = gs;
             }
         } else if constexpr (!RESID) {
             // lane (fg_e, frow_e): rows m0 + (J >> 2) 128 + wr 64 + (J & 3) 16 + frow_e; columns (SPLIT, TI = 4) n0 + wc 64 + fg_e 8 + [0, 8) from
@@ -693,7 +664,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
             }
         } else {
             // Residual epilogue through LDS (the ring is drained first and restarted afterwards: fc2's 48 K-tiles make
-            // the tile boundary cheap).  Arithmetic and statistics order = gemm.hip's fused-LayerNorm producer.
+            // the tile boundary cheap).  Staging and chunk walk as in gemm.hip's fused-LayerNorm producer.
             static_assert(C::BM == 256, "the LDS-staged residual epilogue is written for 256-row tiles");
             constexpr int ROWBYTES = C::BN * 4 + 16;
             constexpr int JPP = (C::BN == 256) ? 2 : 4;  // m-fragments (per wave and X half) staged per pass
@@ -751,32 +722,17 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
                     const f32x4 s0 = *(const f32x4*)(smem + lr * ROWBYTES + ch * 32);
                     const f32x4 s1 = *(const f32x4*)(smem + lr * ROWBYTES + ch * 32 + 16);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float st = e < 4 ? s0[e] : s1[e - 4];
-                        const int sh = (e & 1) * 16;
-                        const float r = from_bits<T>((uint16_t)(ra[q][e >> 1] >> sh)) + from_bits<T>((uint16_t)(rb[q][e >> 1] >> sh));
-                        v[e] = st + r;
-                    }
+                    for (int e = 0; e < 8; ++e) v[e] = (e < 4 ? s0[e] : s1[e - 4]) + planes_decode8<T>(ra[q], rb[q], e);
                     u32x4 oh, ol;
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) { uint32_t h_, l_; split_planes2<T>(v[e], v[e + 1], h_, l_); oh[e >> 1] = h_; ol[e >> 1] = l_; }   // clamps v to the 16-bit range (statistics below see the stored value)
+                    planes_split8<T>(v, oh, ol);
                     if (!(VP_ABLATE(g) & 8)) {
                         size_t so = orow_q[q] + n0 + ch * 8;
                         if (VP_ABLATE(g) & 128) so &= (size_t)0xFFFF8;   // tools/resid_store_probe.py: every store lands in the first 2 MB of the planes (stays in L2)
                         *(u32x4*)(out_hi + so) = oh;
                         *(u32x4*)(out_lo + so) = ol;
                     }
-                    float s1s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                    s1s = row8_sum(s1s);
-                    const float mg = s1s * (1.0f / 64.0f);
-                    float s2 = 0.f;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float d = v[e] - mg;
-                        s2 = fmaf(d, d, s2);
-                    }
-                    s2 = row8_sum(s2);
-                    if ((ch & 7) == 0) *(float2*)(statbuf + (tile_row(p, lr) * GR + (ch >> 3)) * 2) = float2{s1s, s2};
+                    const float2 gs = granule_stats8(v);
+                    if ((ch & 7) == 0) *(float2*)(statbuf + (tile_row(p, lr) * GR + (ch >> 3)) * 2) = gs;
                 }
                 __syncthreads();
             }
@@ -818,14 +774,8 @@ static hipError_t launch8(const GemmArgs& a, hipStream_t s) {
     if constexpr (EPI == EPI_BIAS_RESID_LN)
         if (a.expert) { kern = gemm8_kernel<T, EPI, C, true>; ex = 1; }
     constexpr int LDS = (EPI == EPI_QKV_ATTN) ? 160 * 1024 : (EPI == EPI_BIAS_RESID_LN && C::BN != 256) ? ((128 * (C::BN * 4 + 16) + C::BM * (C::BN / 64) * 8) > C::RING ? (128 * (C::BN * 4 + 16) + C::BM * (C::BN / 64) * 8) : C::RING) : C::RING;
-    static bool attr_done[2][64] = {};   // per device: the LDS opt-in is a per-device function attribute
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_done[ex][dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) attr_done[ex][dev] = true;
-    }
+    static bool attr_done[2][64] = {};
+    if (hipError_t e = lds_opt_in((const void*)kern, LDS, attr_done[ex]); e != hipSuccess) return e;
     const int tiles = (a.M / C::BM) * (a.N / C::BN);
     int grid = tiles < 256 ? tiles : 256;
 #ifdef VP_TOOLS   // experiment (tools/two_lane_probe.py): persistent grids of fewer workgroups, so that two handles' launches can share the chip

@@ -241,7 +241,7 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
         asm volatile("" : "+v"(frow_e), "+v"(fg_e));
         if constexpr (!RESID_LDS) { if (!wr) bar(); }
         if constexpr (RESID && !RESID_LDS) {
-            // residual epilogue straight from registers (256 x 256 tiles; gemm8.hip): v = acc * w_scale + bias + (hi + lo)
+            // residual epilogue straight from registers (256 x 256 tiles; gemm8.hip): st = fma(acc, w_scale, bias)
             const int nb = n0 + wc * 64 + fg_e * 16;
             const int mrow = m0 + wr * 64 + frow_e;
             uint16_t* out_hi = (uint16_t*)g.out;
@@ -256,50 +256,26 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
             for (int J = 0; J < 8; ++J) {
                 const int m = mrow + (J >> 2) * 128 + (J & 3) * 16;
                 const size_t o = (size_t)m * g.ldo + nb;
-                u32x4 r[4];
+                u32x4 r[4];   // hi cols 0-7, hi 8-15, lo 0-7, lo 8-15
                 r[0] = *(const u32x4*)(aux_hi + o);
                 r[1] = *(const u32x4*)(aux_hi + o + 8);
                 r[2] = *(const u32x4*)(aux_lo + o);
                 r[3] = *(const u32x4*)(aux_lo + o + 8);
-                float v[16];
+                float v[16];   // column nb + c
 #pragma unroll
                 for (int f = 0; f < 4; ++f)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int c = f * 4 + e;
-                        const uint32_t wh = r[c >> 3][(c & 7) >> 1], wl = r[2 + (c >> 3)][(c & 7) >> 1];
-                        const int sh = (c & 1) * 16;
-                        v[c] = __builtin_fmaf(acc[f][J][e], ws4[f][e], bias4[f][e]) + (from_bits<T>((uint16_t)(wh >> sh)) + from_bits<T>((uint16_t)(wl >> sh)));
-                    }
+                    for (int e = 0; e < 4; ++e)
+                        v[f * 4 + e] = __builtin_fmaf(acc[f][J][e], ws4[f][e], bias4[f][e]) + planes_decode8<T>(r[f >> 1], r[2 + (f >> 1)], (f & 1) * 4 + e);
                 u32x4 oh[2], ol[2];
-#pragma unroll
-                for (int c = 0; c < 16; c += 2) {
-                    uint32_t h_, l_;
-                    split_planes2<T>(v[c], v[c + 1], h_, l_);
-                    oh[c >> 3][(c & 7) >> 1] = h_;
-                    ol[c >> 3][(c & 7) >> 1] = l_;
-                }
+                planes_split8<T>(v, oh[0], ol[0]);
+                planes_split8<T>(v + 8, oh[1], ol[1]);
                 *(u32x4*)(out_hi + o) = oh[0];
                 *(u32x4*)(out_hi + o + 8) = oh[1];
                 *(u32x4*)(out_lo + o) = ol[0];
                 *(u32x4*)(out_lo + o + 8) = ol[1];
-                float sa = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                float sb2 = ((v[8] + v[9]) + (v[10] + v[11])) + ((v[12] + v[13]) + (v[14] + v[15]));
-                float s1 = sa + sb2;
-                s1 += __shfl_xor(s1, 16, 64);
-                s1 += __shfl_xor(s1, 32, 64);
-                const float mg = s1 * (1.0f / 64.0f);
-                float qa = 0.f, qb = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float da = v[e] - mg, db = v[8 + e] - mg;
-                    qa = fmaf(da, da, qa);
-                    qb = fmaf(db, db, qb);
-                }
-                float s2 = qa + qb;
-                s2 += __shfl_xor(s2, 16, 64);
-                s2 += __shfl_xor(s2, 32, 64);
-                if (fg_e == 0) *(float2*)(g.stats_out + ((size_t)m * gran + (nb >> 6)) * 2) = float2{s1, s2};
+                const float2 gs = granule_stats16(v);
+                if (fg_e == 0) *(float2*)(g.stats_out + ((size_t)m * gran + (nb >> 6)) * 2) = gs;
             }
         } else if constexpr (MXOUT) {
             // mlp.fc1: v = gelu(acc * w_scale + bias), written as MXFP8 (the A operand of mlp.fc2).  Lane (fg_e, frow_e) holds, for each
@@ -438,29 +414,14 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
                     const f32x4 s0 = *(const f32x4*)(smem + lr * ROWBYTES + ch * 32);
                     const f32x4 s1 = *(const f32x4*)(smem + lr * ROWBYTES + ch * 32 + 16);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float st = e < 4 ? s0[e] : s1[e - 4];
-                        const int sh = (e & 1) * 16;
-                        const float r = from_bits<T>((uint16_t)(ra[q][e >> 1] >> sh)) + from_bits<T>((uint16_t)(rb[q][e >> 1] >> sh));
-                        v[e] = st + r;
-                    }
+                    for (int e = 0; e < 8; ++e) v[e] = (e < 4 ? s0[e] : s1[e - 4]) + planes_decode8<T>(ra[q], rb[q], e);
                     u32x4 oh, ol;
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) { uint32_t h_, l_; split_planes2<T>(v[e], v[e + 1], h_, l_); oh[e >> 1] = h_; ol[e >> 1] = l_; }
+                    planes_split8<T>(v, oh, ol);
                     const size_t so = orow_q[q] + n0 + ch * 8;
                     *(u32x4*)(out_hi + so) = oh;
                     *(u32x4*)(out_lo + so) = ol;
-                    float s1s = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                    s1s = row8_sum(s1s);
-                    const float mg = s1s * (1.0f / 64.0f);
-                    float s2 = 0.f;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float d = v[e] - mg;
-                        s2 = fmaf(d, d, s2);
-                    }
-                    s2 = row8_sum(s2);
-                    if ((ch & 7) == 0) *(float2*)(statbuf + (tile_row(p, lr) * GR + (ch >> 3)) * 2) = float2{s1s, s2};
+                    const float2 gs = granule_stats8(v);
+                    if ((ch & 7) == 0) *(float2*)(statbuf + (tile_row(p, lr) * GR + (ch >> 3)) * 2) = gs;
                 }
                 __syncthreads();
             }
@@ -489,13 +450,7 @@ static hipError_t launch8f(const GemmArgs& a, hipStream_t s) {
     auto kern = gemm8f_kernel<EPI, C>;
     constexpr int LDS = (EPI == EPI_BIAS_RESID_LN && C::BN != 256) ? ((128 * (C::BN * 4 + 16) + C::BM * (C::BN / 64) * 8) > C::RING ? (128 * (C::BN * 4 + 16) + C::BM * (C::BN / 64) * 8) : C::RING) : C::RING;
     static bool attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) attr_done[dev] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)kern, LDS, attr_done); e != hipSuccess) return e;
     const int tiles = (a.M / C::BM) * (a.N / C::BN);
     const int grid = tiles < 256 ? tiles : 256;   // below 256 tiles: one workgroup per tile (TileWalk handles any count)
     if (grid < 8) return hipErrorInvalidValue;

@@ -27,6 +27,18 @@ namespace vp {
 
 enum { DT_F16 = 0, DT_BF16 = 1 };
 
+// More than 64 KiB of dynamic LDS is an opt-in, and a per-device function attribute: set once per (kernel instantiation, device).  `done` = the
+// instantiation's own flags, a function-local static of its launcher; a device index outside the table sets the attribute at every launch.
+inline hipError_t lds_opt_in(const void* kern, int bytes, bool (&done)[64]) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const bool known = dev >= 0 && dev < 64;
+    if (known && done[dev]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess && known) done[dev] = true;
+    return e;
+}
+
 // ----------------------------------------------------------------------- GEMM
 // C[m][n] = sum_k A[m][k] * W[n][k]   (A activations, W = nn.Linear weight [out,in])
 enum GemmEpi {

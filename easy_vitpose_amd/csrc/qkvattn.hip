@@ -445,15 +445,8 @@ hipError_t qkvattn_launch(int dtype, const QkvAttnArgs& a, hipStream_t s, char* 
     const int tiles = a.npairs * a.heads;
     const int grid = tiles < 256 ? tiles : 256;
     static bool attr_done[2][64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int di = dtype == DT_F16 ? 0 : 1;
     auto kern = dtype == DT_F16 ? qkvattn_kernel<F16> : qkvattn_kernel<BF16>;
-    if (dev < 0 || dev >= 64 || !attr_done[di][dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, QA::RING);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) attr_done[di][dev] = true;
-    }
+    if (hipError_t e = lds_opt_in((const void*)kern, QA::RING, attr_done[dtype == DT_F16 ? 0 : 1]); e != hipSuccess) return e;
     if (desc) snprintf(desc, desc_cap, "qkvattn_kernel<%s>", dtype == DT_F16 ? "F16" : "BF16");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(QA::NT), QA::RING, s, a);
     return hipGetLastError();
