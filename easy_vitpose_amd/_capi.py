@@ -36,7 +36,8 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_dbg_flip_partner', 'vp_dbg_flip_layout', 'vp_dbg_decode_flip',
            'vp_infer_experts_device_stream', 'vp_infer_frames_experts', 'vp_infer_boxes_experts_stream', 'vp_dbg_mix_plan', 'vp_dbg_decode_mix',
            'vp_set_flip_test_experts', 'vp_dbg_mix_plan_flip', 'vp_dbg_decode_flip_mix',
-           'vp_infer_images', 'vp_infer_boxes_images_stream', 'vp_dbg_image_plan', 'vp_dbg_crop_prep_image']
+           'vp_infer_images', 'vp_infer_boxes_images_stream', 'vp_dbg_image_plan', 'vp_dbg_crop_prep_image',
+           'vp_dbg_gemm_case_planes', 'vp_dbg_gemm_fp8_case_planes']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -161,6 +162,8 @@ def load_library():
     lib.vp_dbg_mx_gemm.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 7
     lib.vp_dbg_host_e4m3.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     lib.vp_dbg_gemm_fp8_case.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 8
+    lib.vp_dbg_gemm_case_planes.argtypes = [C.c_int32] * 9 + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3
+    lib.vp_dbg_gemm_fp8_case_planes.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 5
     lib.vp_expert_info.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vp_set_expert.argtypes = [H, C.c_int32]
     lib.vp_infer_experts.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -8,6 +8,45 @@ using namespace vpi;
 // `dtype` exactly as the production packer / producers do).  Used by tests/ only.
 // ---------------------------------------------------------------------------
 
+// the two-plane residual stream of a producer-row case, up: plane bits as given, or fp32 values split on the host as the producers split them
+static int upload_planes(vp_ctx* c, uint16_t** dst, const float* aux, const uint16_t* r_hi, const uint16_t* r_lo, size_t MN) {
+    if (!(r_hi && r_lo) && !aux) return fail(c, VP_ERR_INVALID, "aux required");
+    std::vector<uint16_t> hp(2 * MN);
+    if (r_hi && r_lo) {
+        std::memcpy(hp.data(), r_hi, MN * 2);
+        std::memcpy(hp.data() + MN, r_lo, MN * 2);
+    } else
+        for (size_t i = 0; i < MN; ++i) {
+            const uint16_t hi = host_to_bits(aux[i], c->dtype);
+            hp[i] = hi;
+            hp[MN + i] = host_to_bits(aux[i] - host_from_bits(hi, c->dtype), c->dtype);
+        }
+    int r;
+    if ((r = dalloc(c, dst, 2 * MN))) return r;
+    if (hipMemcpy(*dst, hp.data(), hp.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return fail(c, VP_ERR_HIP, "H2D");
+    return VP_OK;
+}
+// ... and down: the plane bits themselves (o_hi / o_lo), or hi + lo summed (out)
+static int download_planes(vp_ctx* c, const uint16_t* planes, float* out, uint16_t* o_hi, uint16_t* o_lo, size_t MN) {
+    if (o_hi && o_lo) {
+        if (hipMemcpy(o_hi, planes, MN * 2, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(o_lo, planes + MN, MN * 2, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(c, VP_ERR_HIP, "D2H");
+        return VP_OK;
+    }
+    std::vector<float> hi(MN), lo(MN);
+    int r;
+    if ((r = download16(c, planes, hi.data(), MN)) || (r = download16(c, planes + MN, lo.data(), MN))) return r;
+    for (size_t i = 0; i < MN; ++i) out[i] = hi[i] + lo[i];
+    return VP_OK;
+}
+
+// The residual stream of a producer-row case as plane BITS (vp_dbg_gemm_case_planes) instead of fp32 values split / summed here (vp_dbg_gemm_case)
+struct PlaneIO {
+    const uint16_t *r_hi, *r_lo;   // epi 6: the residual planes [M,N]
+    uint16_t *o_hi, *o_lo;         // the output planes [M,N]
+    bool in_place;                 // epi 6: out == aux, the kernel updates the residual planes themselves
+};
+
 extern "C" {
 
 // out = epilogue(A[M,K] . W[N,K]^T): epi 0 bias->16bit, 1 bias+gelu->16bit, 2 bias+aux[M,N]->fp32, 3 aux[m%192]->fp32
@@ -150,10 +189,10 @@ VP_API int vp_dbg_deconv(int32_t device, int32_t dtype, int32_t B, int32_t Hin, 
 //              stats [M, N/64, 2] = (sum, centred M2) per 64-column granule
 //   epi 5:     W = final 1x1 conv weight [N = Kp, K = 256], A = [M = B 3072, 256]; out = heatmaps [B, Kp, 3072] fp32
 // flags: 1 persistent, 2 out_blocked, 4 a_blocked, 8 reverse
-VP_API int vp_dbg_gemm_case(int32_t device, int32_t dtype, int32_t epi, int32_t variant, int32_t group_m, int32_t flags, int32_t M,
-                            int32_t N, int32_t K, const float* A, const float* W, const float* bias, const float* aux, const float* rowstat,
-                            const float* ln_s, float* out, float* stats) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % 64 || !A || !W || !bias || !out) return fail(nullptr, VP_ERR_INVALID, "bad gemm case");
+// the body of vp_dbg_gemm_case and vp_dbg_gemm_case_planes (io != NULL: epi 6 / 7 on plane bits; aux = pos for epi 7)
+static int gemm_case(int32_t device, int32_t dtype, int32_t epi, int32_t variant, int32_t group_m, int32_t flags, int32_t M, int32_t N, int32_t K, const float* A,
+                     const float* W, const float* bias, const float* aux, const float* rowstat, const float* ln_s, float* out, float* stats, const PlaneIO* io) {
+    if (M <= 0 || N <= 0 || K <= 0 || K % 64 || !A || !W || !bias) return fail(nullptr, VP_ERR_INVALID, "bad gemm case");
     vp_ctx* c = dbg_ctx(device, dtype);
     if (!c) return VP_ERR_HIP;
     c->Kp = N;
@@ -199,15 +238,7 @@ VP_API int vp_dbg_gemm_case(int32_t device, int32_t dtype, int32_t epi, int32_t 
         g.aux = dAux32;
     }
     if (epi == vp::EPI_BIAS_RESID_LN) {
-        if (!aux) return dbg_finish(c, fail(c, VP_ERR_INVALID, "aux required"));
-        std::vector<uint16_t> hp(2 * MN);
-        for (size_t i = 0; i < MN; ++i) {
-            const uint16_t hi = host_to_bits(aux[i], c->dtype);
-            hp[i] = hi;
-            hp[MN + i] = host_to_bits(aux[i] - host_from_bits(hi, c->dtype), c->dtype);
-        }
-        if ((r = dalloc(c, &dAux16, 2 * MN))) return dbg_finish(c, r);
-        if (hipMemcpy(dAux16, hp.data(), hp.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, "H2D"));
+        if ((r = upload_planes(c, &dAux16, aux, io ? io->r_hi : nullptr, io ? io->r_lo : nullptr, MN))) return dbg_finish(c, r);
         g.aux = (const float*)dAux16;
     }
     if (prod) {
@@ -215,10 +246,13 @@ VP_API int vp_dbg_gemm_case(int32_t device, int32_t dtype, int32_t epi, int32_t 
         if ((r = dalloc(c, &dStats, (size_t)M * (N / 64) * 2))) return dbg_finish(c, r);
         g.stats_out = dStats;
     }
-    char* o;
-    if ((r = dalloc(c, &o, out_bytes))) return dbg_finish(c, r);
-    dOut = o;
-    hipMemset(dOut, 0xff, out_bytes);
+    if (io && io->in_place) dOut = dAux16;   // as forward.hip launches the residual GEMMs: out == aux
+    else {
+        char* o;
+        if ((r = dalloc(c, &o, out_bytes))) return dbg_finish(c, r);
+        dOut = o;
+        hipMemset(dOut, 0xff, out_bytes);
+    }
     g.out = dOut;
     const int splitk = (flags >> 8) & 15;   // epi 6 only: S partial products (EPI_PARTIAL) + splitk_reduce_kernel instead of the one-launch residual epilogue
     hipError_t e;
@@ -246,14 +280,32 @@ VP_API int vp_dbg_gemm_case(int32_t device, int32_t dtype, int32_t epi, int32_t 
                 out[m * N + n] = t[src];
             }
     } else if (prod) {
-        std::vector<float> hi(MN), lo(MN);
-        if ((r = download16(c, (const uint16_t*)dOut, hi.data(), MN)) || (r = download16(c, (const uint16_t*)dOut + MN, lo.data(), MN))) return dbg_finish(c, r);
-        for (size_t i = 0; i < MN; ++i) out[i] = hi[i] + lo[i];
+        if ((r = download_planes(c, (const uint16_t*)dOut, out, io ? io->o_hi : nullptr, io ? io->o_lo : nullptr, MN))) return dbg_finish(c, r);
         if (stats && hipMemcpy(stats, dStats, (size_t)M * (N / 64) * 8, hipMemcpyDeviceToHost) != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, "D2H"));
     } else {
         if (hipMemcpy(out, dOut, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, "D2H"));
     }
     return dbg_finish(c, VP_OK);
+}
+
+VP_API int vp_dbg_gemm_case(int32_t device, int32_t dtype, int32_t epi, int32_t variant, int32_t group_m, int32_t flags, int32_t M,
+                            int32_t N, int32_t K, const float* A, const float* W, const float* bias, const float* aux, const float* rowstat,
+                            const float* ln_s, float* out, float* stats) {
+    if (!out) return fail(nullptr, VP_ERR_INVALID, "bad gemm case");
+    return gemm_case(device, dtype, epi, variant, group_m, flags, M, N, K, A, W, bias, aux, rowstat, ln_s, out, stats, nullptr);
+}
+
+// The producer row's own tap (tests/test_gpu_residual_row.py): vp_dbg_gemm_case for epi 6 / 7 with the residual stream as plane BITS on both sides, so that a test
+// sees hi and lo themselves (signs of zeros, subnormals, the saturated codes) and chooses residual planes no fp32 value splits into.  epi 6: r_hi / r_lo [M,N] =
+// the residual planes; epi 7: pos [192,N] fp32 (r_hi / r_lo unused).  o_hi / o_lo [M,N] = the output planes, stats [M, N/64, 2].  in_place (epi 6): the kernel
+// updates the residual planes themselves (out == aux, as forward.hip launches it); split-K (flags >> 8) is in place either way.
+VP_API int vp_dbg_gemm_case_planes(int32_t device, int32_t dtype, int32_t epi, int32_t variant, int32_t group_m, int32_t flags, int32_t M, int32_t N, int32_t K,
+                                   const float* A, const float* W, const float* bias, const uint16_t* r_hi, const uint16_t* r_lo, const float* pos,
+                                   int32_t in_place, uint16_t* o_hi, uint16_t* o_lo, float* stats) {
+    if ((epi != vp::EPI_BIAS_RESID_LN && epi != vp::EPI_POS_LN) || !o_hi || !o_lo || !stats || (epi == vp::EPI_BIAS_RESID_LN ? !r_hi || !r_lo : !pos || in_place))
+        return fail(nullptr, VP_ERR_INVALID, "bad gemm planes case");
+    const PlaneIO io{r_hi, r_lo, o_hi, o_lo, in_place != 0};
+    return gemm_case(device, dtype, epi, variant, group_m, flags, M, N, K, A, W, bias, pos, nullptr, nullptr, nullptr, stats, &io);
 }
 
 // image + crop geometry -> the uint8 [n,256,192,3] RGB crops the model is fed (the device crop/pad/resize kernel alone, behind the staging of
@@ -341,9 +393,10 @@ VP_API int vp_dbg_mx_gemm(int32_t device, int32_t M, int32_t N, int32_t K, const
 // a_deq / w_deq return what the codes and scales stand for, so that the test can restate the product exactly.
 //   epi 0: out = a.w^T * w_scale + bias, rounded to fp16        epi 1: out = gelu(...) as MXFP8 (returned de-quantised)
 //   epi 6: out = ... + aux (two-plane residual, returned as hi + lo), stats [M, N/64, 2]
-VP_API int vp_dbg_gemm_fp8_case(int32_t device, int32_t epi, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias,
-                                const float* aux, float* out, float* stats, float* a_deq, float* w_deq) {
-    if (M <= 0 || N <= 0 || K <= 0 || M % 256 || K % 256 || N % 64 || !A || !W || !bias || !out || (epi != 0 && epi != 1 && epi != 6))
+// the body of vp_dbg_gemm_fp8_case and vp_dbg_gemm_fp8_case_planes (io != NULL: epi 6 on plane bits)
+static int gemm_fp8_case(int32_t device, int32_t epi, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias, const float* aux, float* out,
+                         float* stats, float* a_deq, float* w_deq, const PlaneIO* io) {
+    if (M <= 0 || N <= 0 || K <= 0 || M % 256 || K % 256 || N % 64 || !A || !W || !bias || (epi != 0 && epi != 1 && epi != 6))
         return fail(nullptr, VP_ERR_INVALID, "bad fp8 gemm case");
     vp_ctx* c = dbg_ctx(device, VP_DTYPE_F16);
     if (!c) return VP_ERR_HIP;
@@ -359,21 +412,17 @@ VP_API int vp_dbg_gemm_fp8_case(int32_t device, int32_t epi, int32_t M, int32_t 
     hipError_t e = vp::mx_quantize_launch(dA, dA8, dAs, M, K, nullptr);
     if (e != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, "mx quantize"));
     const size_t out_bytes = epi == 0 ? MN * 2 : epi == 1 ? MN : MN * 4;
-    if ((r = dalloc(c, &dOut, out_bytes))) return dbg_finish(c, r);
-    hipMemset(dOut, 0xff, out_bytes);
     LnFuse ln;
     if (epi == 1 && (r = dalloc(c, &dOs, MN / 32))) return dbg_finish(c, r);
     if (epi == 6) {
-        if (!aux) return dbg_finish(c, fail(c, VP_ERR_INVALID, "aux required"));
-        std::vector<uint16_t> hp(2 * MN);
-        for (size_t i = 0; i < MN; ++i) {
-            const uint16_t hi = host_to_bits(aux[i], c->dtype);
-            hp[i] = hi;
-            hp[MN + i] = host_to_bits(aux[i] - host_from_bits(hi, c->dtype), c->dtype);
-        }
-        if ((r = dalloc(c, &dAux16, 2 * MN)) || (r = dalloc(c, &dStats, (size_t)M * (N / 64) * 2))) return dbg_finish(c, r);
-        if (hipMemcpy(dAux16, hp.data(), hp.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, "H2D"));
+        if ((r = upload_planes(c, &dAux16, aux, io ? io->r_hi : nullptr, io ? io->r_lo : nullptr, MN)) || (r = dalloc(c, &dStats, (size_t)M * (N / 64) * 2)))
+            return dbg_finish(c, r);
         ln.plane = MN; ln.stats_out = dStats;
+    }
+    if (io && io->in_place) dOut = (char*)dAux16;   // as forward.hip launches mlp.fc2: out == aux
+    else {
+        if ((r = dalloc(c, &dOut, out_bytes))) return dbg_finish(c, r);
+        hipMemset(dOut, 0xff, out_bytes);
     }
     const int fam = epi == 0 ? VP_PROF_GEMM_QKV : epi == 1 ? VP_PROF_GEMM_FC1 : VP_PROF_GEMM_FC2;
     r = gemm_fp8(c, fam, epi, resolve_gemm_fp8(fam, epi, M, N), dA8, dAs, dW8, dWs, dB, dOut, dOs, (const float*)dAux16, M, N, K, &ln);
@@ -407,12 +456,24 @@ VP_API int vp_dbg_gemm_fp8_case(int32_t device, int32_t epi, int32_t M, int32_t 
             for (size_t n = 0; n < (size_t)N; ++n)
                 out[m * N + n] = vp_host_e4m3_to_float(co[vp::mx_code_off(m, n, N)]) * std::ldexp(1.0f, (int)so[vp::mx_scale_off(m, n >> 5, N)] - 127);
     } else {
-        std::vector<float> hi(MN), lo(MN);
-        if ((r = download16(c, (const uint16_t*)dOut, hi.data(), MN)) || (r = download16(c, (const uint16_t*)dOut + MN, lo.data(), MN))) return dbg_finish(c, r);
-        for (size_t i = 0; i < MN; ++i) out[i] = hi[i] + lo[i];
+        if ((r = download_planes(c, (const uint16_t*)dOut, out, io ? io->o_hi : nullptr, io ? io->o_lo : nullptr, MN))) return dbg_finish(c, r);
         if (stats && hipMemcpy(stats, dStats, (size_t)M * (N / 64) * 8, hipMemcpyDeviceToHost) != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, "D2H"));
     }
     return dbg_finish(c, r);
+}
+
+VP_API int vp_dbg_gemm_fp8_case(int32_t device, int32_t epi, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias,
+                                const float* aux, float* out, float* stats, float* a_deq, float* w_deq) {
+    if (!out) return fail(nullptr, VP_ERR_INVALID, "bad fp8 gemm case");
+    return gemm_fp8_case(device, epi, M, N, K, A, W, bias, aux, out, stats, a_deq, w_deq, nullptr);
+}
+
+// ... and its producer-row sibling (epi 6), as vp_dbg_gemm_case_planes: residual and output as plane bits, in_place = out == aux; a_deq / w_deq as above
+VP_API int vp_dbg_gemm_fp8_case_planes(int32_t device, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias, const uint16_t* r_hi,
+                                       const uint16_t* r_lo, int32_t in_place, uint16_t* o_hi, uint16_t* o_lo, float* stats, float* a_deq, float* w_deq) {
+    if (!r_hi || !r_lo || !o_hi || !o_lo || !stats) return fail(nullptr, VP_ERR_INVALID, "bad fp8 gemm planes case");
+    const PlaneIO io{r_hi, r_lo, o_hi, o_lo, in_place != 0};
+    return gemm_fp8_case(device, 6, M, N, K, A, W, bias, nullptr, nullptr, stats, a_deq, w_deq, &io);
 }
 
 // host-only: fp32 -> OCP e4m3 codes with the library's own converter (the one the weight packer of the fp8 mode uses)

@@ -495,6 +495,13 @@ VP_API int vp_dbg_crop_prep(int32_t device_id, const uint8_t* frame, int32_t fh,
 VP_API int vp_dbg_gemm_case(int32_t device_id, int32_t dtype, int32_t epi, int32_t variant, int32_t group_m, int32_t flags,
                             int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias, const float* aux,
                             const float* rowstat, const float* ln_s, float* out, float* stats);
+/* vp_dbg_gemm_case for the producers of the two-plane residual stream (epi 6 / 7), with the stream as plane BITS on both sides: epi 6 reads the residual
+ * planes r_hi / r_lo [M, N] (16-bit codes of `dtype`), epi 7 the fp32 pos [192, N]; o_hi / o_lo [M, N] return the output planes, stats [M, N/64, 2] the
+ * granule statistics.  in_place != 0 (epi 6): the kernel updates the residual planes themselves (out == aux, as the forward launches it); split-K
+ * (flags bits 8-11) is in place either way. */
+VP_API int vp_dbg_gemm_case_planes(int32_t device_id, int32_t dtype, int32_t epi, int32_t variant, int32_t group_m, int32_t flags, int32_t M, int32_t N,
+                                   int32_t K, const float* A, const float* W, const float* bias, const uint16_t* r_hi, const uint16_t* r_lo,
+                                   const float* pos, int32_t in_place, uint16_t* o_hi, uint16_t* o_lo, float* stats);
 /* The sharding plan of vp_group_infer for n crops on w devices of max_batch maxb -- HOST ONLY, no device needed: the exact
  * function group_run executes.  Rounds of w * maxb crops; inside a round device i takes [off, off + cnt) with ceil(nr / w) crops
  * per device (trailing devices short or empty).  Entry e = round * w + device: offs[e], cnts[e].  Returns the number of
@@ -565,6 +572,10 @@ VP_API int vp_dbg_mx_gemm(int32_t device_id, int32_t M, int32_t N, int32_t K, co
  * (hi + lo returned), stats [M, N/64, 2].  M % 256 == 0, K % 256 == 0, K >= 512, N % 256 == 0 (epi 6: N % 192 == 0 or N % 256 == 0). */
 VP_API int vp_dbg_gemm_fp8_case(int32_t device_id, int32_t epi, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias,
                                 const float* aux, float* out, float* stats, float* a_deq, float* w_deq);
+/* vp_dbg_gemm_fp8_case, epi 6, with the residual stream as plane bits (fp16 codes) on both sides, as vp_dbg_gemm_case_planes */
+VP_API int vp_dbg_gemm_fp8_case_planes(int32_t device_id, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias,
+                                       const uint16_t* r_hi, const uint16_t* r_lo, int32_t in_place, uint16_t* o_hi, uint16_t* o_lo, float* stats,
+                                       float* a_deq, float* w_deq);
 /* HOST ONLY: fp32 -> OCP e4m3 codes with the converter the fp8 weight packer uses (round to nearest even, saturating at 448) */
 VP_API int vp_dbg_host_e4m3(const float* in, uint8_t* out, int64_t n);
 

@@ -5,7 +5,10 @@ LayerNorm-producer epilogue with its row statistics, the 64x64-blocked `hid` lay
 the hi+lo final 1x1 conv -- and bit identity between the configurations of one GEMM (same accumulation order by construction:
 any difference is a schedule bug or a race).  VERDICT r1 item 6: these kernels used to be validated only transitively.
 The dispatch of the tiles is generated from csrc/tiles.h, so every product tile (1, 3, 8, 9, 11, 12, 15, 20, 30, 31, 41) is launched once per epilogue
-class here, and the two configuration matrices also run on bf16."""
+class here, and the two configuration matrices also run on bf16.
+The data here are Gaussians and the residual taps return hi + lo summed: the edge values of the residual producer row (the fp16 clamp, fp16 subnormals and signed zeros in the
+planes, rows with a large common offset, the association st + (hi + lo), the in-place update) and the planes and statistics bit for bit against a host model live in
+tests/test_gpu_residual_row.py."""
 import ctypes as C
 
 import numpy as np
