@@ -37,7 +37,7 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_infer_experts_device_stream', 'vp_infer_frames_experts', 'vp_infer_boxes_experts_stream', 'vp_dbg_mix_plan', 'vp_dbg_decode_mix',
            'vp_set_flip_test_experts', 'vp_dbg_mix_plan_flip', 'vp_dbg_decode_flip_mix',
            'vp_infer_images', 'vp_infer_boxes_images_stream', 'vp_dbg_image_plan', 'vp_dbg_crop_prep_image',
-           'vp_dbg_gemm_case_planes', 'vp_dbg_gemm_fp8_case_planes']
+           'vp_dbg_gemm_case_planes', 'vp_dbg_gemm_fp8_case_planes', 'vp_dbg_attention_case']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -135,6 +135,7 @@ def load_library():
     lib.vp_last_error.restype = C.c_char_p
     lib.vp_dbg_gemm.argtypes = [C.c_int32] * 6 + [C.c_void_p] * 5
     lib.vp_dbg_attention.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 2
+    lib.vp_dbg_attention_case.argtypes = [C.c_int32] * 6 + [C.c_void_p] * 3
     lib.vp_dbg_layernorm.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 5
     lib.vp_dbg_deconv.argtypes = [C.c_int32] * 6 + [C.c_void_p, C.POINTER(vp_tensor_desc), C.c_int32, C.c_void_p]
     lib.vp_infer_flip.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,

@@ -92,6 +92,53 @@ VP_API int vp_dbg_attention(int32_t device, int32_t dtype, int32_t B, int32_t D,
     return dbg_finish(c, download16(c, dout, out, M * D));
 }
 
+// The attention core in every variant the launcher has (tests/test_gpu_attention.py): qkv [B*192, 3*D] fp32 (row-major, rounded to dtype) -> out [B*192, D] fp32.
+// flags: 1 = query split (three workgroups per (crop, head)), 2 = qkv handed over in the 64 x 64-blocked layout [M/64][3D/64][64][64] (kernels.h GemmArgs::out_blocked:
+// element (m, n) lives in block (m / 64, n / 64) at row m % 64, column n % 64), 4 = MXFP8 output: out = the de-blocked, de-quantised values, out_scales [M, D/32] =
+// the E8M0 bytes.  The device output is filled with 0xFF bytes before the launch (NaN in fp16 / bf16 and in e4m3): an unwritten element shows.  Combinations
+// attention_launch has no kernel for are VP_ERR_INVALID: blocked or MX off head dim 64, MX with bf16, MX with the query split.
+VP_API int vp_dbg_attention_case(int32_t device, int32_t dtype, int32_t B, int32_t D, int32_t heads, int32_t flags, const float* qkv, float* out, uint8_t* out_scales) {
+    if (B <= 0 || D <= 0 || heads <= 0 || D % heads || (flags & ~7) || !qkv || !out) return fail(nullptr, VP_ERR_INVALID, "bad attention case");
+    if (dtype != VP_DTYPE_F16 && dtype != VP_DTYPE_BF16) return fail(nullptr, VP_ERR_INVALID, "attention case: dtype");
+    const int hd = D / heads;
+    const bool qsplit = flags & 1, blocked = flags & 2, mx = flags & 4;
+    if (hd != 32 && hd != 64 && hd != 80) return fail(nullptr, VP_ERR_INVALID, "attention case: head dim");
+    if ((blocked || mx) && hd != 64) return fail(nullptr, VP_ERR_INVALID, "attention case: blocked qkv and MXFP8 output are head dim 64 only");
+    if (mx && (dtype != VP_DTYPE_F16 || qsplit || D % 128 || !out_scales)) return fail(nullptr, VP_ERR_INVALID, "attention case: MXFP8 output is fp16, unsplit");
+    vp_ctx* c = dbg_ctx(device, dtype);
+    if (!c) return VP_ERR_HIP;
+    const size_t M = (size_t)B * 192, N3 = 3 * (size_t)D, MD = M * D;
+    std::vector<uint16_t> hq(M * N3);
+    for (size_t m = 0; m < M; ++m)
+        for (size_t n = 0; n < N3; ++n) {
+            const size_t dst = blocked ? ((m / 64) * (N3 / 64) + n / 64) * 4096 + (m % 64) * 64 + n % 64 : m * N3 + n;
+            hq[dst] = host_to_bits(qkv[m * N3 + n], c->dtype);
+        }
+    uint16_t* dq;
+    char* dout;
+    uint8_t* dsc = nullptr;
+    int rc;
+    const size_t out_bytes = mx ? MD : MD * 2;
+    if ((rc = dalloc(c, &dq, M * N3)) || (rc = dalloc(c, &dout, out_bytes)) || (mx && (rc = dalloc(c, &dsc, MD / 32)))) return dbg_finish(c, rc);
+    hipError_t e = hipMemcpy(dq, hq.data(), hq.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dout, 0xff, out_bytes);
+    if (e == hipSuccess && mx) e = hipMemset(dsc, 0xff, MD / 32);
+    if (e == hipSuccess) e = vp::attention_launch(c->dtype, dq, (uint16_t*)dout, B, D, heads, nullptr, qsplit, blocked, dsc);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, std::string("attention case: ") + hipGetErrorString(e)));
+    if (!mx) return dbg_finish(c, download16(c, (const uint16_t*)dout, out, MD));
+    std::vector<uint8_t> co(MD), so(MD / 32);
+    if (hipMemcpy(co.data(), dout, MD, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(so.data(), dsc, MD / 32, hipMemcpyDeviceToHost) != hipSuccess)
+        return dbg_finish(c, fail(c, VP_ERR_HIP, "D2H"));
+    for (size_t m = 0; m < M; ++m)
+        for (size_t n = 0; n < (size_t)D; ++n) {
+            const uint8_t sb = so[vp::mx_scale_off(m, n >> 5, D)];
+            out[m * D + n] = vp_host_e4m3_to_float(co[vp::mx_code_off(m, n, D)]) * std::ldexp(1.0f, (int)sb - 127);
+            if (!(n & 31)) out_scales[m * (D / 32) + (n >> 5)] = sb;
+        }
+    return dbg_finish(c, VP_OK);
+}
+
 // attn.qkv + attention core in one kernel (qkvattn.hip): x [2 npairs 192, D] (rounded to dtype), Wqkv [3D, D], bias [3D] -> out [M, D] (as fp32).
 // Run with neutral LayerNorm statistics (mean 0, rstd 1, row sums 0: ln_fold(acc, 0, 0, 1, b) == acc + b exactly), so the result must equal
 // vp_dbg_gemm(epi 0) followed by vp_dbg_attention bit for bit.

@@ -473,6 +473,12 @@ VP_API int vp_dbg_gemm(int32_t device_id, int32_t dtype, int32_t epi, int32_t M,
 /* qkv [B*192, 3*D] -> attention core output [B*192, D]  (vit.py:167-176) */
 VP_API int vp_dbg_attention(int32_t device_id, int32_t dtype, int32_t B, int32_t D, int32_t heads,
                             const float* qkv, float* out);
+/* the attention core in any variant of its launcher: flags 1 = query split, 2 = qkv passed to the kernel in the 64x64-blocked layout (re-tiled inside from the
+ * row-major input), 4 = MXFP8 output (out = de-blocked, de-quantised values; out_scales [B*192, D/32] = the E8M0 bytes, NULL otherwise).  The device output is
+ * filled with 0xFF bytes first, so an unwritten element returns as NaN.  VP_ERR_INVALID for what has no kernel: flags 2 / 4 off head dim 64, 4 with bf16 or
+ * with flag 1. */
+VP_API int vp_dbg_attention_case(int32_t device_id, int32_t dtype, int32_t B, int32_t D, int32_t heads, int32_t flags, const float* qkv, float* out,
+                                 uint8_t* out_scales);
 /* attn.qkv + attention core in ONE kernel (csrc/qkvattn.hip; head dim 64): x [2 npairs 192, D], Wqkv [3D, D], bias [3D] -> [M, D].  Neutral
  * LayerNorm statistics: the result must equal vp_dbg_gemm(epi 0) + vp_dbg_attention bit for bit.  npairs * heads >= 8. */
 VP_API int vp_dbg_qkvattn(int32_t device_id, int32_t dtype, int32_t npairs, int32_t D, int32_t heads, const float* x, const float* W,
