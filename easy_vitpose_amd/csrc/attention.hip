@@ -2,27 +2,12 @@
 // (vit.py:164-176): one workgroup per (crop, head); the 192x192 score tile never
 // leaves the CU.
 //
-//  S^T = K Q^T   (MFMA A = K rows from LDS, B = Q rows straight from HBM)
-//  softmax over keys in fp32 registers (scale folded into the exponent)
-//  O^T = V^T P^T (MFMA A = V^T via the gfx950 LDS transpose read, B = P^T = the S^T
-//                 accumulators re-packed)
-//
-// Computing the TRANSPOSED products makes every lane own one query column
-// (q = lane & 15): row max / row sum need only two cross-lane steps (xor 16, 32), and
-// the S^T accumulator registers of two 16-key tiles are directly the 8-element
-// B fragment of the PV MFMA (the MFMA k index is a permutation-invariant sum: k slot
-// (g, e) = key 32 kb + 4 g + e for e < 4, 32 kb + 16 + 4 g + e - 4 otherwise).
-//
-// V stays ROW-MAJOR in LDS, cut into [192 keys][16 d] sub-tiles (32-byte rows, so the 8
-// rows a 32-lane half touches are one 256-byte bank row: conflict-free without padding);
-// `ds_read_b64_tr_b16` hands lane i of a 16-lane group column i of a [4 keys][16 d] block,
-// i.e. the V^T fragment, with no transposed staging pass.  When HD is a multiple of 32 the
-// d columns of sub-tile pairs are interleaved (column c of sub-tile dt = d 32(dt/2) +
-// 8(c/4) + 4(dt&1) + c%4) so that a lane's two O^T accumulators are 8 consecutive head-dim
-// values of one query = one 16-byte store.  K (HD = 64) is kept unpadded with the GEMM's
-// XOR swizzle.  LDS = 48 KiB at HD = 64 -> 3 blocks per CU.
+// The core itself -- the lane layout of the transposed products, the fp32 softmax, the V sub-tiles behind the gfx950 LDS transpose read and the
+// output conversion -- is csrc/attn_core.h, shared with the fused kernels of qkvattn.hip and gemm8.hip.  This file keeps the staging: Q
+// fragments straight from HBM, V row-major in [192 keys][16 d] sub-tiles (interleaved pairs when HD is a multiple of 32), K (HD = 64) unpadded with the GEMM's XOR swizzle.
+// LDS = 48 KiB at HD = 64 -> 3 blocks per CU.
 #include <cstdlib>
-#include "common.h"
+#include "attn_core.h"
 #include "kernels.h"
 #include "mx8.h"
 
@@ -40,13 +25,6 @@ template <int HD> struct AttnCfg {
     static constexpr bool PAIR = (DT % 2 == 0);       // interleaved sub-tile pairs -> 16-byte output stores
     static constexpr int LDS = K_BYTES + DT * VSUB;
 };
-
-__device__ __forceinline__ u32x2 lds_read_tr16(const char* p) {
-    typedef __attribute__((__vector_size__(4 * sizeof(__fp16)))) __fp16 h4;
-    typedef __attribute__((address_space(3))) h4* lds_h4;
-    const h4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_h4)(p));
-    return __builtin_bit_cast(u32x2, v);
-}
 
 // MX (fp8 mode, HD = 64 only): the output is written as MXFP8 -- e4m3 codes in the 64 x 128-blocked layout + one E8M0 scale per 32 columns
 // (csrc/mx8.h) -- the A operand of the fp8 attn.proj GEMM; `out` then points at the codes and `out_scales` at the scale bytes.  A block of 32
@@ -145,11 +123,10 @@ __global__ __launch_bounds__(256, QT == 3 ? 2 : 3) void attention_kernel(const u
         __syncthreads();
     };
 
-    // per-lane LDS bases: K fragment row fr (+16 kt), slot kk*4+fg; V transpose read: lane (4 j + m) of a 16-lane
-    // group supplies the address of (key 4 g + j, column chunk m) and receives column fr of keys 4 g .. 4 g + 3
+    // per-lane LDS bases: K fragment row fr (+16 kt), slot kk*4+fg; V transpose read: attn_core.h
     const char* kfrag = Ks + fr * C::KSTR;
     const int kswz = C::KSWZ ? ((fr >> 1) & 7) : 0;    // (row >> 1) & 7 with row = 16 kt + fr
-    const char* vfrag = Vs + (fg * 4 + (fr >> 2)) * 32 + (fr & 3) * 8;
+    const char* vfrag = Vs + (fg * 4 + (fr >> 2)) * 32 + (fr & 3) * 8;   // = attn_vfrag(Vs, fr, fg), see there
 
 #pragma unroll
     for (int t0 = 0; t0 < NTW; t0 += QT) {
@@ -169,40 +146,11 @@ __global__ __launch_bounds__(256, QT == 3 ? 2 : 3) void attention_kernel(const u
             }
         }
 
-        // ---- softmax over keys (per query column), fp32; P re-packed as PV B-fragments.  P is in [0, 1] and O a convex
-        //      combination of 16-bit V values: neither can overflow the 16-bit range, so no saturating conversion ----
+        // ---- softmax over keys (per query column), fp32; P re-packed as PV B-fragments ----
         u32x4 pf[QT][6];
         float inv_l[QT];
 #pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            float mx = -3.0e38f;
-#pragma unroll
-            for (int kt = 0; kt < 12; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[t][kt][r]);
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            float l = 0.f;
-            const float mb = mx * scale_log2e;
-#pragma unroll
-            for (int kt = 0; kt < 12; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float p = softmax_p(s[t][kt][r], scale_log2e, mb);
-                    s[t][kt][r] = p;
-                    l += p;
-                }
-            l += __shfl_xor(l, 16, 64);
-            l += __shfl_xor(l, 32, 64);
-            inv_l[t] = 1.0f / l;
-#pragma unroll
-            for (int kb = 0; kb < 6; ++kb) {
-                pf[t][kb][0] = pack2_nosat<Ty>(s[t][2 * kb][0], s[t][2 * kb][1]);
-                pf[t][kb][1] = pack2_nosat<Ty>(s[t][2 * kb][2], s[t][2 * kb][3]);
-                pf[t][kb][2] = pack2_nosat<Ty>(s[t][2 * kb + 1][0], s[t][2 * kb + 1][1]);
-                pf[t][kb][3] = pack2_nosat<Ty>(s[t][2 * kb + 1][2], s[t][2 * kb + 1][3]);
-            }
-        }
+        for (int t = 0; t < QT; ++t) inv_l[t] = attn_softmax<Ty>(s[t], scale_log2e, pf[t]);
 
         // ---- O^T[d][q] = sum_key V^T[d][key] P^T[key][q], sub-tile (pair) at a time ----
         if (t0 == 0) store_v();
@@ -218,10 +166,7 @@ __global__ __launch_bounds__(256, QT == 3 ? 2 : 3) void attention_kernel(const u
             for (int kb = 0; kb < 6; ++kb) {
 #pragma unroll
                 for (int u = 0; u < G; ++u) {
-                    const char* vp_ = vfrag + (dp + u) * C::VSUB + kb * 1024;
-                    const u32x2 lo = lds_read_tr16(vp_);          // keys 32 kb + 4 g + 0..3
-                    const u32x2 hi = lds_read_tr16(vp_ + 512);    // keys 32 kb + 16 + 4 g + 0..3
-                    const u32x4 vf = u32x4{lo[0], lo[1], hi[0], hi[1]};
+                    const u32x4 vf = attn_vt_frag<C::VSUB>(vfrag, dp + u, kb);
 #pragma unroll
                     for (int t = 0; t < QT; ++t) o[u][t] = mfma16<Ty>(vf, pf[t][kb], o[u][t]);
                 }
@@ -231,9 +176,8 @@ __global__ __launch_bounds__(256, QT == 3 ? 2 : 3) void attention_kernel(const u
                 const int q = (wave * 3 + part * NTW + t0 + t) * 16 + fr;
                 uint16_t* dst = out + ((size_t)b * T + q) * D + h * HD;
                 if constexpr (MX && C::PAIR) {
-                    float v[8];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { v[e] = o[0][t][e] * inv_l[t]; v[4 + e] = o[1][t][e] * inv_l[t]; }
+                    const f32x4 v0 = attn_out_scale(o[0][t], inv_l[t]), v1 = attn_out_scale(o[1][t], inv_l[t]);
+                    const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                     float amax = 0.f;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[e]));
@@ -247,17 +191,9 @@ __global__ __launch_bounds__(256, QT == 3 ? 2 : 3) void attention_kernel(const u
                         u32x2{mx_pack4(v[0], v[1], v[2], v[3], inv), mx_pack4(v[4], v[5], v[6], v[7], inv)};
                     if (fg == 0) out_scales[mx_scale_off(m, (size_t)(col >> 5), (size_t)D)] = (uint8_t)E;
                 } else if constexpr (C::PAIR) {   // accumulator rows of the pair = d 16 dp + 8 fg + {0..3} and + {4..7}
-                    u32x4 w;
-                    w[0] = pack2_nosat<Ty>(o[0][t][0] * inv_l[t], o[0][t][1] * inv_l[t]);
-                    w[1] = pack2_nosat<Ty>(o[0][t][2] * inv_l[t], o[0][t][3] * inv_l[t]);
-                    w[2] = pack2_nosat<Ty>(o[1][t][0] * inv_l[t], o[1][t][1] * inv_l[t]);
-                    w[3] = pack2_nosat<Ty>(o[1][t][2] * inv_l[t], o[1][t][3] * inv_l[t]);
-                    *(u32x4*)(dst + dp * 16 + fg * 8) = w;
+                    *(u32x4*)(dst + dp * 16 + fg * 8) = attn_out_pair<Ty>(o[0][t], o[1][t], inv_l[t]);
                 } else {
-                    u32x2 w;
-                    w[0] = pack2_nosat<Ty>(o[0][t][0] * inv_l[t], o[0][t][1] * inv_l[t]);
-                    w[1] = pack2_nosat<Ty>(o[0][t][2] * inv_l[t], o[0][t][3] * inv_l[t]);
-                    *(u32x2*)(dst + dp * 16 + fg * 4) = w;
+                    *(u32x2*)(dst + dp * 16 + fg * 4) = attn_out_single<Ty>(o[0][t], inv_l[t]);
                 }
             }
         }
@@ -272,16 +208,15 @@ static hipError_t launch(const uint16_t* qkv, uint16_t* out, int B, int D, int h
 #else
     auto kern = attention_kernel<Ty, HD, 1>;
 #endif
-    const float scale = 1.0f / sqrtf((float)HD);   // head_dim ** -0.5, vit.py:156
     if (blocked && HD != 64) return hipErrorInvalidValue;
     // small batches: three workgroups per (crop, head), one query tile per wave (QS = 3) while that still leaves CUs idle otherwise (profiles/small_batch_r6.txt)
     if (qsplit) {
         hipLaunchKernelGGL((attention_kernel<Ty, HD, 1, false, 3>), dim3(B * heads * 3), dim3(256), AttnCfg<HD>::LDS, s, qkv, out, D, heads,
-                           scale * 1.4426950408889634f, blocked, (uint8_t*)nullptr);
+                           softmax_scale_log2e(HD), blocked, (uint8_t*)nullptr);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(kern, dim3(B * heads), dim3(256), AttnCfg<HD>::LDS, s, qkv, out, D, heads,
-                       scale * 1.4426950408889634f, blocked, (uint8_t*)nullptr);
+                       softmax_scale_log2e(HD), blocked, (uint8_t*)nullptr);
     return hipGetLastError();
 }
 
@@ -291,7 +226,7 @@ hipError_t attention_launch(int dtype, const uint16_t* qkv, uint16_t* out, int B
     if (mx_scales) {   // fp8 mode: MXFP8 output (head dim 64, fp16 operands)
         if (hd != 64 || dtype != DT_F16 || D % 128) return hipErrorInvalidValue;
         hipLaunchKernelGGL((attention_kernel<F16, 64, 1, true>), dim3(B * heads), dim3(256), AttnCfg<64>::LDS, s, qkv, out, D, heads,
-                           (1.0f / 8.0f) * 1.4426950408889634f, qkv_blocked, mx_scales);
+                           softmax_scale_log2e(64), qkv_blocked, mx_scales);
         return hipGetLastError();
     }
 #define VP_ATT(HD)                                                                           \

@@ -164,7 +164,7 @@ VP_API int vp_dbg_qkvattn(int32_t device, int32_t dtype, int32_t npairs, int32_t
         vp::GemmArgs g80{};
         g80.A = dx; g80.W = dwh80; g80.bias = dbh80; g80.ln_s = dsh80; g80.rowstat = drow; g80.out = dy;
         g80.M = (int)M; g80.N = heads * 256; g80.K = D; g80.ldo = D; g80.w_rows = heads * 256; g80.variant = 18;
-        g80.attn_scale_log2e = (1.0f / sqrtf(80.0f)) * 1.4426950408889634f;
+        g80.attn_scale_log2e = vp::softmax_scale_log2e(80);
         if (e8 == hipSuccess && !vp::gemm8_supported(vp::EPI_QKV_ATTN, g80, 256, 192)) return dbg_finish(c, fail(c, VP_ERR_INVALID, "shape not supported by the fused qkv + attention tile (head dim 80)"));
         if (e8 == hipSuccess) e8 = vp::gemm_launch(c->dtype, vp::EPI_QKV_ATTN, g80, nullptr);
         if (e8 == hipSuccess) e8 = hipDeviceSynchronize();
@@ -174,8 +174,7 @@ VP_API int vp_dbg_qkvattn(int32_t device, int32_t dtype, int32_t npairs, int32_t
     hipError_t e = vp::qkv_head_major_launch(dw, db, ds, dwh, dbh, dsh, D, D, nullptr);
     vp::QkvAttnArgs qa{};
     qa.x_hi = dx; qa.wh = dwh; qa.bh = dbh; qa.sh = dsh; qa.rowstat = drow; qa.y = dy; qa.npairs = npairs; qa.ncrops = 2 * npairs; qa.heads = heads; qa.D = D;
-    const float scale = 1.0f / sqrtf(64.0f);
-    qa.scale_log2e = scale * 1.4426950408889634f;
+    qa.scale_log2e = vp::softmax_scale_log2e(64);
     if (e == hipSuccess && !vp::qkvattn_supported(qa)) return dbg_finish(c, fail(c, VP_ERR_INVALID, "shape not supported by the fused qkv + attention kernel"));
     if (e == hipSuccess) e = vp::qkvattn_launch(c->dtype, qa, nullptr, nullptr, 0);
     if (e == hipSuccess) e = hipDeviceSynchronize();

@@ -182,7 +182,7 @@ int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, const FwdOp
                 // tile order: groups of 8 crops x all heads, crop fastest -- the 32 workgroups of an XCD then work on 8 crops x 4 heads at a time (12 operand K-slices
                 // fetched per K-tile for 32 tiles instead of 18 with the head-fastest order: PMC traffic 800 -> ~450 MB per launch, profiles/qkvattn80_r5.txt)
                 g80.group_m = c->sw.qa80_group;
-                g80.attn_scale_log2e = (1.0f / sqrtf(80.0f)) * 1.4426950408889634f;
+                g80.attn_scale_log2e = vp::softmax_scale_log2e(80);
                 g80.ablate = c->gemm_ablate | c->sw.fam_ablate[VP_PROF_GEMM_QKV];
                 char desc[192];
                 desc[0] = 0;
@@ -193,7 +193,7 @@ int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, const FwdOp
                 vp::QkvAttnArgs qa{};
                 qa.x_hi = xh; qa.wh = b.w_qkvh; qa.bh = b.b_qkvh; qa.sh = b.s_qkvh; qa.rowstat = c->rowstat; qa.y = c->y;
                 qa.npairs = (n + 1) / 2; qa.ncrops = n; qa.heads = c->heads; qa.D = D;
-                qa.scale_log2e = (1.0f / sqrtf(64.0f)) * 1.4426950408889634f;
+                qa.scale_log2e = vp::softmax_scale_log2e(64);
                 char desc[96];
                 desc[0] = 0;
                 LAUNCH(c, VP_PROF_GEMM_QKV, qkv_attn_flops, qkv_attn_bytes, vp::qkvattn_launch(c->dtype, qa, c->stream, desc, (int)sizeof(desc)));

@@ -50,6 +50,7 @@
 #include <cstdio>
 
 #include <cstdlib>
+#include "attn_core.h"
 #include "gemm8_common.h"
 #ifndef VP_G8_RESD
 #define VP_G8_RESD 1
@@ -61,15 +62,6 @@
 
 
 namespace vp {
-
-namespace {
-__device__ __forceinline__ u32x2 lds_tr16(const char* p) {   // ds_read_b64_tr_b16: column i of a [4 keys][16 d] block to lane i of a 16-lane group
-    typedef __attribute__((__vector_size__(4 * sizeof(__fp16)))) __fp16 h4;
-    typedef __attribute__((address_space(3))) h4* lds_h4;
-    const h4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_h4)(p));
-    return __builtin_bit_cast(u32x2, v);
-}
-}  // namespace
 
 // EPI: EPI_BIAS / EPI_BIAS_GELU (16-bit output straight from registers, optional LayerNorm-consumer fold, optional
 // 64x64-blocked output) or EPI_BIAS_RESID_LN (two-plane residual stream + row statistics, staged through LDS).
@@ -363,9 +355,9 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
             //      without padding or swizzle), V as five [192 keys][16 d] sub-tiles (attention.hip's layout for an odd number of sub-tiles) = 90 KiB of
             //      the 112 KiB ring, which is drained first (the K-loop's run-ahead fetches of the next tile are dropped and re-issued by ring_start below,
             //      as in the LDS-staged residual epilogue).
-            //   2. the attention core of attention.hip<80>, instruction for instruction per query tile (S^T = K Q^T over three k-steps with the d >= 80
-            //      lanes zeroed on both operands, fp32 softmax, O^T = V^T P^T through ds_read_b64_tr_b16): 12 query tiles on 8 waves -- tiles 0-7 one per
-            //      wave, tiles 8-11 on waves 0-3 (every SIMD = waves w, w + 4 gets three tiles).  y is BIT-IDENTICAL to gemm (EPI_BIAS) + attention_launch.
+            //   2. the attention core (csrc/attn_core.h: the one definition attention.hip<80> runs too) per query tile, S^T = K Q^T over three k-steps with
+            //      the d >= 80 lanes zeroed on both operands: 12 query tiles on 8 waves -- tiles 0-7 one per wave, tiles 8-11 on waves 0-3 (every SIMD =
+            //      waves w, w + 4 gets three tiles).  y is BIT-IDENTICAL to gemm (EPI_BIAS) + attention_launch.
             //   3. LDS: q / k / v live in the LAST 90 KiB of the CU's 160 KiB ([70 K, 160 K): Q, K, V), so ring buffer 0 and the X0 slot of buffer 1
             //      ([0, 68 K)) are free from the barrier that ends the K-loop on: the next tile's first K-tile and X0 of its second stream in under the
             //      fold, the LDS hand-over and the whole attention phase; W0 / W1 of K-tile 1 (which overlap Q) follow behind the attention phase, and the
@@ -432,9 +424,10 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
                 // 16-byte slot of k-step kk: kk 4 + fg; the d >= 80 lanes of k-step 2 (fg 2, 3) read the slot of lane fg - 2 (a broadcast: no bank conflict) and are zeroed
                 const bool live2 = fgq < 2;
                 const int slot2 = (live2 ? 8 + fgq : 6 + fgq) * 16;
-                const char* vfrag = Vs + (fgq * 4 + (fr >> 2)) * 32 + (fr & 3) * 8;
+                const char* vfrag = Vs + (fgq * 4 + (fr >> 2)) * 32 + (fr & 3) * 8;   // = attn_vfrag(Vs, fr, fgq), see there
                 uint16_t* ybase = (uint16_t*)g.out + (size_t)m0 * K + (n0 >> 8) * HD;
                 const float scale_log2e = g.attn_scale_log2e;
+#pragma unroll   // both passes written out, as the compiler chose to before the core moved into attn_core.h
                 for (int pass = 0; pass < 2; ++pass) {
                     const int qt = pass * 8 + wave;
                     if (qt >= 12) break;
@@ -460,48 +453,15 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
                         sc[kt] = mfma16<T>(k1, qf[1], sc[kt]);
                         sc[kt] = mfma16<T>(k2, qf[2], sc[kt]);
                     }
-                    float mx = -3.0e38f;
-#pragma unroll
-                    for (int kt = 0; kt < 12; ++kt)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, sc[kt][r]);
-                    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-                    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                    float l = 0.f;
-                    const float mb = mx * scale_log2e;
-#pragma unroll
-                    for (int kt = 0; kt < 12; ++kt)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float pv = softmax_p(sc[kt][r], scale_log2e, mb);
-                            sc[kt][r] = pv;
-                            l += pv;
-                        }
-                    l += __shfl_xor(l, 16, 64);
-                    l += __shfl_xor(l, 32, 64);
-                    const float inv_l = 1.0f / l;
                     u32x4 pf[6];
-#pragma unroll
-                    for (int kb = 0; kb < 6; ++kb) {
-                        pf[kb][0] = pack2_nosat<T>(sc[2 * kb][0], sc[2 * kb][1]);
-                        pf[kb][1] = pack2_nosat<T>(sc[2 * kb][2], sc[2 * kb][3]);
-                        pf[kb][2] = pack2_nosat<T>(sc[2 * kb + 1][0], sc[2 * kb + 1][1]);
-                        pf[kb][3] = pack2_nosat<T>(sc[2 * kb + 1][2], sc[2 * kb + 1][3]);
-                    }
+                    const float inv_l = attn_softmax<T>(sc, scale_log2e, pf);
                     uint16_t* dst = ybase + (size_t)(qt * 16 + fr) * K;
 #pragma unroll
                     for (int dp = 0; dp < DT; ++dp) {
                         f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                        for (int kb = 0; kb < 6; ++kb) {
-                            const char* vp_ = vfrag + dp * VSUB + kb * 1024;
-                            const u32x2 lo = lds_tr16(vp_);          // keys 32 kb + 4 g + 0..3
-                            const u32x2 hi = lds_tr16(vp_ + 512);    // keys 32 kb + 16 + 4 g + 0..3
-                            o = mfma16<T>(u32x4{lo[0], lo[1], hi[0], hi[1]}, pf[kb], o);
-                        }
-                        u32x2 w;
-                        w[0] = pack2_nosat<T>(o[0] * inv_l, o[1] * inv_l);
-                        w[1] = pack2_nosat<T>(o[2] * inv_l, o[3] * inv_l);
+                        for (int kb = 0; kb < 6; ++kb) o = mfma16<T>(attn_vt_frag<VSUB>(vfrag, dp, kb), pf[kb], o);
+                        const u32x2 w = attn_out_single<T>(o, inv_l);
                         if (!(VP_ABLATE(g) & 8)) *(u32x2*)(dst + dp * 16 + fgq * 4) = w;
                     }
                 }

@@ -176,6 +176,9 @@ hipError_t mx_probe_launch(const float* dA, const float* dW, const float* dWs, u
 // mx_scales != nullptr (fp8 mode, head dim 64): the output is written as MXFP8 (codes at `out`, 64 x 128-blocked; E8M0 scales at mx_scales; no query split)
 hipError_t attention_launch(int dtype, const uint16_t* qkv, uint16_t* out, int B, int D, int heads, hipStream_t s, bool qsplit, int qkv_blocked = 0,
                             uint8_t* mx_scales = nullptr);
+// the softmax scale head_dim ** -0.5 (vit.py:156) folded into the base-2 exponent: what every attention kernel takes as scale_log2e.  ONE host
+// definition: the fused and the unfused kernels must be handed the same float
+inline float softmax_scale_log2e(int head_dim) { return (1.0f / sqrtf((float)head_dim)) * 1.4426950408889634f; }
 
 // attn.qkv + attention core in one kernel (qkvattn.hip; head dim 64): tile = (pair of crops, head); the qkv tensor never reaches HBM.
 // wh / bh / sh = head-major copies of the LayerNorm-folded qkv weights / bias / row sums (qkv_head_major_launch).  y bit-identical to

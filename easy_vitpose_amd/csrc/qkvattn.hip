@@ -8,15 +8,16 @@
 //   2. epilogue: LayerNorm fold + bias (common.h::ln_fold, the qkv epilogue's arithmetic), rounded to 16 bit and written to LDS in the
 //      attention kernel's layouts -- per crop Q and K as [192][128 B] rows with the XOR swizzle, V as [192 keys][16 d] sub-tile pairs --
 //      144 KiB for the two crops = exactly the operand ring, which is dead by then.
-//   3. the attention core of attention.hip (S^T = K Q^T in registers, fp32 softmax, O^T = V^T P^T through ds_read_b64_tr_b16), waves 0-3 on
-//      crop 2p, waves 4-7 on crop 2p+1, Q fragments from LDS instead of HBM; output rows straight to `y`.
+//   3. the attention core (csrc/attn_core.h: the one definition attention.hip runs too), waves 0-3 on crop 2p, waves 4-7 on crop 2p+1,
+//      Q fragments from LDS instead of HBM; output rows straight to `y`.
 //   The ring is drained before the epilogue and restarted on the next tile after the attention phase (both need the whole LDS).
-// Same accumulation order, same fold, same roundings, same attention arithmetic as gemm8 / gemm.hip + attention.hip: `y` is BIT-IDENTICAL to
+// Same accumulation order, same fold, same roundings as gemm8 / gemm.hip, the same attention core as attention.hip: `y` is BIT-IDENTICAL to
 // the unfused path (tests/test_gpu_api.py flips VP_FUSE_QKV_ATTN).  What it removes per layer at 256 crops: 226 MB written + 226 MB read,
 // qkv's write-back phase and one launch.
 #include <cstdio>
 #include <cstdlib>
 
+#include "attn_core.h"
 #include "gemm8_common.h"
 
 namespace vp {
@@ -36,13 +37,6 @@ struct QA {
     static constexpr int V_BASE = 4 * XS;
     static_assert(6 * XS == RING && BUF <= 3 * XS && BUF + XS <= 4 * XS, "the attention phase reuses exactly the ring; buffer 0 + X0 of buffer 1 inside Q0 K0 Q1 K1");
 };
-
-__device__ __forceinline__ u32x2 lds_read_tr16(const char* p) {
-    typedef __attribute__((__vector_size__(4 * sizeof(__fp16)))) __fp16 h4;
-    typedef __attribute__((address_space(3))) h4* lds_h4;
-    const h4 v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_h4)(p));
-    return __builtin_bit_cast(u32x2, v);
-}
 }  // namespace
 
 template <class T>
@@ -241,12 +235,10 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
 
         // ---------------- qkv epilogue: LayerNorm fold + bias -> 16 bit -> LDS (attention layouts) ----------------
         if (!(VP_ABLATE(g) & 2)) {
-            const int dcol = wc * 16 + fg_e * 4;                                   // head-dim column of this lane's four values
             const int qk_byte = (fg_e & 1) * 8;                                    // inside the 16-byte slot d >> 3 = wc 2 + (fg >> 1)
             const int qk_slot = wc * 2 + (fg_e >> 1);
             const int v_sub = 2 * (wc >> 1) + (fg_e & 1);                          // attention.hip: d 8 ch .. + 3 -> sub-tile 2 (ch / 4), + 4 .. + 7 -> 2 (ch / 4) + 1
             const int v_byte = ((wc & 1) * 2 + (fg_e >> 1)) * 8;
-            (void)dcol;
 #pragma unroll
             for (int j = 6; j < 12; ++j) stat[j] = *(const float2*)(rs0 + (twin ? 0 : 384) + 32 * (j - 6));
 #pragma unroll
@@ -269,7 +261,7 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
         }
         __syncthreads();
 
-        // ---------------- attention core (attention.hip, one query tile live at a time): waves 0-3 crop 0, waves 4-7 crop 1 ----------------
+        // ---------------- attention core (attn_core.h): waves 0-3 crop 0, waves 4-7 crop 1 ----------------
         if (!(VP_ABLATE(g) & 1)) {
             const int crop = wave >> 2, lw = wave & 3;
             const char* Qs = smem + crop * 2 * QA::XS;
@@ -281,10 +273,10 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
             asm volatile("" : "+v"(fr), "+v"(fg));
             const char* kfrag = Ks + fr * 128;
             const int kswz = (fr >> 1) & 7;
-            const char* vfrag = Vs + (fg * 4 + (fr >> 2)) * 32 + (fr & 3) * 8;
+            const char* vfrag = attn_vfrag(Vs, fr, fg);
             const size_t b = (size_t)pair * 2 + ((2 * pair + 1 < g.ncrops) ? crop : 0);
             // QT query tiles of the wave at a time.  QT = 3 (the accumulators are dead: 256 registers for this phase): every K / V^T fragment read from
-            // LDS feeds three MFMAs; QT = 1: attention.hip's shipped form.  Per query tile the arithmetic is attention.hip's, instruction for instruction.
+            // LDS feeds three MFMAs; QT = 1: attention.hip's shipped form.
 #pragma unroll
             for (int t0 = 0; t0 < 3; t0 += QT) {
                 u32x4 qf[QT][2];
@@ -317,35 +309,7 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
                 u32x4 pf[QT][6];
                 float inv_l[QT];
 #pragma unroll
-                for (int tq_ = 0; tq_ < QT; ++tq_) {
-                    float mx = -3.0e38f;
-#pragma unroll
-                    for (int kt = 0; kt < 12; ++kt)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[tq_][kt][r]);
-                    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-                    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                    float l = 0.f;
-                    const float mb = mx * g.scale_log2e;
-#pragma unroll
-                    for (int kt = 0; kt < 12; ++kt)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float p = softmax_p(s[tq_][kt][r], g.scale_log2e, mb);
-                            s[tq_][kt][r] = p;
-                            l += p;
-                        }
-                    l += __shfl_xor(l, 16, 64);
-                    l += __shfl_xor(l, 32, 64);
-                    inv_l[tq_] = 1.0f / l;
-#pragma unroll
-                    for (int kb = 0; kb < 6; ++kb) {
-                        pf[tq_][kb][0] = pack2_nosat<T>(s[tq_][2 * kb][0], s[tq_][2 * kb][1]);
-                        pf[tq_][kb][1] = pack2_nosat<T>(s[tq_][2 * kb][2], s[tq_][2 * kb][3]);
-                        pf[tq_][kb][2] = pack2_nosat<T>(s[tq_][2 * kb + 1][0], s[tq_][2 * kb + 1][1]);
-                        pf[tq_][kb][3] = pack2_nosat<T>(s[tq_][2 * kb + 1][2], s[tq_][2 * kb + 1][3]);
-                    }
-                }
+                for (int tq_ = 0; tq_ < QT; ++tq_) inv_l[tq_] = attn_softmax<T>(s[tq_], g.scale_log2e, pf[tq_]);
 #pragma unroll
                 for (int dp = 0; dp < 4; dp += 2) {
                     f32x4 o[2][QT];
@@ -357,10 +321,7 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
                     for (int kb = 0; kb < 6; ++kb)
 #pragma unroll
                         for (int u = 0; u < 2; ++u) {
-                            const char* vp_ = vfrag + (dp + u) * QA::VSUB + kb * 1024;
-                            const u32x2 lo = lds_read_tr16(vp_);
-                            const u32x2 hi = lds_read_tr16(vp_ + 512);
-                            const u32x4 vf = u32x4{lo[0], lo[1], hi[0], hi[1]};
+                            const u32x4 vf = attn_vt_frag<QA::VSUB>(vfrag, dp + u, kb);
 #pragma unroll
                             for (int tq_ = 0; tq_ < QT; ++tq_) o[u][tq_] = mfma16<T>(vf, pf[tq_][kb], o[u][tq_]);
                         }
@@ -368,12 +329,7 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
                     for (int tq_ = 0; tq_ < QT; ++tq_) {
                         const int q = (lw * 3 + t0 + tq_) * 16 + fr;
                         uint16_t* dst = g.y + (b * 192 + q) * g.D + head * 64;
-                        u32x4 w;
-                        w[0] = pack2_nosat<T>(o[0][tq_][0] * inv_l[tq_], o[0][tq_][1] * inv_l[tq_]);
-                        w[1] = pack2_nosat<T>(o[0][tq_][2] * inv_l[tq_], o[0][tq_][3] * inv_l[tq_]);
-                        w[2] = pack2_nosat<T>(o[1][tq_][0] * inv_l[tq_], o[1][tq_][1] * inv_l[tq_]);
-                        w[3] = pack2_nosat<T>(o[1][tq_][2] * inv_l[tq_], o[1][tq_][3] * inv_l[tq_]);
-                        *(u32x4*)(dst + dp * 16 + fg * 8) = w;
+                        *(u32x4*)(dst + dp * 16 + fg * 8) = attn_out_pair<T>(o[0][tq_], o[1][tq_], inv_l[tq_]);
                     }
                 }
             }

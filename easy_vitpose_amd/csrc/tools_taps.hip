@@ -94,12 +94,12 @@ VP_API int vp_dbg_qkvattn_bench(int32_t device, int32_t npairs, int32_t D, int32
     hipMemset(dbh, 0, 3 * (size_t)D * 4); hipMemset(dsh, 0, 3 * (size_t)D * 4); hipMemset(drow, 0, 2 * M * 4);
     vp::QkvAttnArgs qa{};
     qa.x_hi = dx; qa.wh = dwh; qa.bh = dbh; qa.sh = dsh; qa.rowstat = drow; qa.y = dy; qa.npairs = npairs; qa.ncrops = 2 * npairs; qa.heads = heads; qa.D = D; qa.ablate = ablate;
-    qa.scale_log2e = 0.125f * 1.4426950408889634f;
+    qa.scale_log2e = vp::softmax_scale_log2e(64);
     vp::GemmArgs g80{};   // head dim 80: gemm8.hip EPI_QKV_ATTN (heads * 256 head-major rows: the 3 D^2 buffer is larger than heads * 256 * D)
     const bool h80 = heads * 80 == D;
     g80.A = dx; g80.W = dwh; g80.bias = dbh; g80.ln_s = dsh; g80.rowstat = drow; g80.out = dy;
     g80.M = (int)M; g80.N = heads * 256; g80.K = D; g80.ldo = D; g80.w_rows = heads * 256; g80.variant = 18; g80.ablate = ablate;
-    g80.attn_scale_log2e = (1.0f / sqrtf(80.0f)) * 1.4426950408889634f;
+    g80.attn_scale_log2e = vp::softmax_scale_log2e(80);
     auto launch = [&]() { return h80 ? vp::gemm_launch(c->dtype, vp::EPI_QKV_ATTN, g80, nullptr) : vp::qkvattn_launch(c->dtype, qa, nullptr, nullptr, 0); };
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);

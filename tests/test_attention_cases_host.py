@@ -1,7 +1,7 @@
 """CPU: the attention cases of tests/attention_cases.py keep their promises, a float32 model of the kernel's arithmetic stays inside the per-element bound,
 and wrong kernels -- mutations of that model -- are caught by the checks tests/test_gpu_attention.py applies to the device's output.
 
-The model is the arithmetic of csrc/attention.hip: S in fp32, p = exp2(fma(s, c, -fl(max c))) with c = hd^-1/2 log2(e), l summed from the unrounded p, P rounded to the
+The model is the arithmetic of the attention core (csrc/attn_core.h, the one definition every attention kernel runs): S in fp32, p = exp2(fma(s, c, -fl(max c))) with c = hd^-1/2 log2(e), l summed from the unrounded p, P rounded to the
 16-bit type, PV in fp32, one rounding of o / l.  Its summation order is numpy's, not the MFMA's: the bound does not depend on the order.
 
 One mutation the issue lists is NOT caught, and cannot be by a per-element bound of this form: l summed from the ROUNDED P.  With P~_k = p_k (1 + e_k),

@@ -8,7 +8,8 @@ build.py::SOURCES (--tools: TOOLS_SOURCES with -DVP_TOOLS) is compiled in both w
 build.py, into a temporary directory.  Comment lines and the `__hip_cuid_*` lines (a hash of the compilation) are dropped, kernels are paired by order
 of appearance and their mangled symbols replaced by the ordinal, so a renamed template argument is no difference but any instruction, register count
 or kernel descriptor field is.  One line per translation unit: `identical`, or the kernels that differ with their register counts, spills, scratch
-and code size on both sides.  Exit status 1 if anything differs.  No GPU is needed.
+and code size on both sides, each followed by the opcodes whose COUNT differs (`same opcode counts`: registers and order moved, no instruction was
+added or dropped).  Exit status 1 if anything differs.  No GPU is needed.
 
 A refactor of a kernel source is behaviour- and speed-neutral exactly when this reports `identical` for the product build.  --tools is informative
 only where the change adds or retires rows of the tile table: those kernels (dis)appear in the measurement build by design.
@@ -22,6 +23,7 @@ import re
 import subprocess
 import sys
 import tempfile
+from collections import Counter
 from concurrent.futures import ThreadPoolExecutor
 
 STATS = ['.vgpr_count', '.sgpr_count', '.vgpr_spill_count', '.private_segment_fixed_size']
@@ -103,6 +105,11 @@ class Asm:
         self.rest = '\n'.join(rest)
 
 
+def opcode_counts(text: str) -> "dict[str, int]":
+    """Instructions of a kernel by opcode (assembler lines start with a tab; directives with a dot, labels and metadata do not match)."""
+    return dict(Counter(m.group(1) for m in re.finditer(r'^\t([a-z][a-z0-9_]*)\b', text, re.M)))
+
+
 def compare(name: str, a: Asm, b: Asm) -> "tuple[bool, list[str]]":
     out, n = [], min(len(a.kernels), len(b.kernels))
     differ = [i for i in range(n) if a.kernels[i][1:] != b.kernels[i][1:]]
@@ -118,6 +125,9 @@ def compare(name: str, a: Asm, b: Asm) -> "tuple[bool, list[str]]":
     for i in differ:
         sa, sb = a.kernels[i][2], b.kernels[i][2]
         out.append(f'  #{i} {b.kernels[i][0]}: ' + ', '.join(f'{k} {sa[k]} -> {sb[k]}' for k in STATS + ['codeLenInByte']))
+        ca, cb = opcode_counts(a.kernels[i][1]), opcode_counts(b.kernels[i][1])
+        moved = [f'{op} {ca.get(op, 0)} -> {cb.get(op, 0)}' for op in sorted(set(ca) | set(cb)) if ca.get(op, 0) != cb.get(op, 0)]
+        out.append('      ' + (', '.join(moved) if moved else 'same opcode counts'))
     return False, out
 
 
