@@ -37,7 +37,8 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_infer_experts_device_stream', 'vp_infer_frames_experts', 'vp_infer_boxes_experts_stream', 'vp_dbg_mix_plan', 'vp_dbg_decode_mix',
            'vp_set_flip_test_experts', 'vp_dbg_mix_plan_flip', 'vp_dbg_decode_flip_mix',
            'vp_infer_images', 'vp_infer_boxes_images_stream', 'vp_dbg_image_plan', 'vp_dbg_crop_prep_image',
-           'vp_dbg_gemm_case_planes', 'vp_dbg_gemm_fp8_case_planes', 'vp_dbg_attention_case']
+           'vp_dbg_gemm_case_planes', 'vp_dbg_gemm_fp8_case_planes', 'vp_dbg_attention_case',
+           'vp_pose_nms_stream', 'vp_pose_nms', 'vp_dbg_pose_nms_host', 'vp_dbg_pose_oks']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -67,6 +68,11 @@ class vp_frame(C.Structure):
 
 class vp_image(C.Structure):
     _fields_ = [('plane', C.c_void_p * 2), ('pitch', C.c_int64 * 2), ('h', C.c_int32), ('w', C.c_int32), ('format', C.c_int32), ('matrix', C.c_int32)]
+
+
+class vp_pose_nms_cfg(C.Structure):
+    _fields_ = [('oks_thr', C.c_float), ('vis_thr', C.c_float), ('use_vis_thr', C.c_int32), ('soft', C.c_int32), ('max_dets', C.c_int32),
+                ('n_sigmas', C.c_int32), ('sigmas', C.c_void_p)]
 
 
 class vp_profile(C.Structure):
@@ -193,6 +199,11 @@ def load_library():
     lib.vp_dbg_flip_partner.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.vp_dbg_flip_layout.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.vp_dbg_decode_flip.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    nms_host = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(vp_pose_nms_cfg), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vp_pose_nms_stream.argtypes = [H] + nms_host + [C.c_void_p]
+    lib.vp_pose_nms.argtypes = [H] + nms_host
+    lib.vp_dbg_pose_nms_host.argtypes = nms_host
+    lib.vp_dbg_pose_oks.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(vp_pose_nms_cfg), C.c_void_p]
     for name in SYMBOLS:
         if name not in ('vp_stream', 'vp_last_error', 'vp_host_alloc', 'vp_host_free', 'vp_group_member', 'vp_group_last_error'):
             getattr(lib, name).restype = C.c_int

@@ -7,6 +7,7 @@ pose path, track across frames (``is_video``), report FPS and write the ``--save
     python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --output-path out --save-json
     python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --frame-batch 16   # 16 frames per pose call
     python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --flip-test        # flip-test (COCO-17 pairs; else --flip-pairs FILE.json)
+    python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --pose-nms 0.9 --soft-nms   # person scores + OKS pose NMS per frame
 
 Not rebuilt (outside the hot path): drawing / preview windows (``--show``, ``--save-img``: OpenCV) and video
 decoding -- a video is accepted as a ``.npy`` stack ``[frames, H, W, 3]`` uint8 RGB, or as a directory of image files.
@@ -51,6 +52,17 @@ def flip_test_argument(args):
     return True if args.flip_test else None
 
 
+def pose_nms_argument(args):
+    """--pose-nms [THR] / --soft-nms / --vis-thr V / --sigmas FILE.json -> VitInference's pose_nms=: None (off) or a PoseNms."""
+    if args.pose_nms is None:
+        if args.soft_nms or args.vis_thr is not None or args.sigmas is not None:
+            raise ValueError('--soft-nms, --vis-thr and --sigmas belong to --pose-nms')
+        return None
+    from easy_vitpose_amd.posenms import PoseNms, load_sigmas
+    return PoseNms(oks_thr=args.pose_nms, vis_thr=0.2 if args.vis_thr is None else args.vis_thr, soft=args.soft_nms,
+                   sigmas=None if args.sigmas is None else load_sigmas(args.sigmas))
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--input', required=True, help='image file, .npy frame stack, or directory of images')
@@ -78,6 +90,11 @@ def build_parser() -> argparse.ArgumentParser:
                     'configs); on its own it stands for the COCO-17 mirror pairs, any other dataset needs --flip-pairs')
     ap.add_argument('--flip-pairs', default=None, metavar='FILE.json', help='mirror joint pairs [[left, right], ...] of the dataset (implies --flip-test)')
     ap.add_argument('--shift-heatmap', action='store_true', help='flip-test: shift the flipped-back heatmaps one pixel right (the reference\'s shift_heatmap)')
+    ap.add_argument('--pose-nms', type=float, nargs='?', const=0.9, default=None, metavar='THR', help='person score = mean keypoint confidence x box score, and '
+                    'OKS pose NMS per frame at this threshold (default 0.9, the reference\'s oks_thr): duplicate poses leave the output')
+    ap.add_argument('--soft-nms', action='store_true', help='--pose-nms: soft OKS NMS (scores decay instead of a hard cut; the reference\'s soft_nms)')
+    ap.add_argument('--vis-thr', type=float, default=None, metavar='V', help='--pose-nms: joints at or below this confidence do not count (default 0.2)')
+    ap.add_argument('--sigmas', default=None, metavar='FILE.json', help='--pose-nms: per-joint OKS sigmas of the dataset (built in for COCO-17 only)')
     return ap
 
 
@@ -113,7 +130,7 @@ def main(argv=None) -> int:
     model = VitInference(state_dict if state_dict is not None else args.model, detector, args.model_name or args.synthetic,
                          args.det_class, dataset, args.yolo_size, is_video=is_video, single_pose=args.single_pose,
                          yolo_step=args.yolo_step, dtype=args.dtype, max_batch=args.max_batch,
-                         flip_test=flip_test_argument(args), shift_heatmap=args.shift_heatmap)
+                         flip_test=flip_test_argument(args), shift_heatmap=args.shift_heatmap, pose_nms=pose_nms_argument(args))
     print(f'>>> Model loaded: {args.model or "synthetic ViTPose-" + args.synthetic.upper()}')
     print(f'>>> Running inference on {args.input}')
     keypoints, dts = [], []

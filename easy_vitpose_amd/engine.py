@@ -15,6 +15,8 @@ from . import _capi as capi
 from . import moe
 from .configs import HM_H, HM_W, IMG_H, IMG_W, ModelShape
 from .cropprep import PIX_FORMATS, YUV_MATRIX_IDS, Frame
+from .posenms import PoseNms, resolve_sigmas
+from .posenms import c_config as nms_c_config
 
 
 def _as_f32_numpy(v) -> np.ndarray:
@@ -409,7 +411,8 @@ class VitPoseHip:
             table[i] = capi.vp_image((C.c_void_p * 2)(p0, p1), (C.c_int64 * 2)(*f.pitch), f.h, f.w, PIX_FORMATS[f.format], YUV_MATRIX_IDS[f.matrix])
         return table
 
-    def infer_boxes(self, frames, boxes, frame_index=None, pad: int = 10, out=None, crop_params: bool = False, status: bool = False, datasets=None):
+    def infer_boxes(self, frames, boxes, frame_index=None, pad: int = 10, out=None, crop_params: bool = False, status: bool = False, datasets=None,
+                    nms: PoseNms | None = None, box_scores=None):
         """Detector boxes on device frames -> keypoints in FRAME pixels, all on the device (vp_infer_boxes_stream, contract in
         include/vitpose_hip.h).  `frames`: torch uint8 CUDA tensors [H, W, 3] on this handle's device (RGB; rows may be pitched: a view of a wider buffer),
         or `Frame` objects over device planes (`Frame.bgr`, `Frame.nv12`: vp_infer_boxes_images_stream), read in place; `boxes`: float32 CUDA
@@ -420,9 +423,19 @@ class VitPoseHip:
         a host synchronisation, under the ordering notes of `infer_device`: consume the results with torch ops on that stream.
         `datasets` (a ViTPose+ handle: one name or expert index per box, on the host, as in `infer_mixed`): a dataset per box in the same call
         (vp_infer_boxes_experts_stream) -- `out` is then [n, Kmax, 3], row i's first `dataset_k(datasets)[i]` joints filled and the rest 0;
-        crop params and status are the plain call's."""
+        crop params and status are the plain call's.
+        `nms` (a PoseNms): person scores and per-frame OKS pose NMS run behind the boxes entry on the same stream (`pose_nms`); the call then returns
+        (out, score, rank, count[, crop_params][, status]).  The box scores are `box_scores` (float32 CUDA [n]) or column 4 of `boxes`.  Not together with
+        `datasets`: poses of different joint layouts are not comparable."""
         import torch
         dev = torch.device('cuda', self.device_id)
+        if nms is not None:
+            if datasets is not None:
+                raise ValueError('infer_boxes: nms= does not run together with datasets= (poses of different joint layouts are not comparable)')
+            if not isinstance(nms, PoseNms):
+                raise TypeError(f'nms: a PoseNms expected, got {type(nms).__name__}')
+            if box_scores is None and not (hasattr(boxes, 'ndim') and boxes.ndim == 2 and boxes.shape[1] >= 5):
+                raise ValueError('infer_boxes: nms= needs the box scores: box_scores=, or boxes with a score in column 4')
         frames = [self._as_frame(f, i) for i, f in enumerate(frames)]
         table = self._image_table(frames, device_only=True)
         if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda and boxes.dtype == torch.float32):
@@ -447,15 +460,73 @@ class VitPoseHip:
         elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
                   and out.device == dev and out.numel() == n * K * 3):
             raise ValueError(f'out: a contiguous float32 tensor of {n} x {K} x 3 on {dev} expected')
-        cp = torch.empty((n, 9), dtype=torch.int32, device=dev) if crop_params else None
-        st = torch.empty((n,), dtype=torch.int32, device=dev) if status else None
+        cp = torch.empty((n, 9), dtype=torch.int32, device=dev) if crop_params or nms is not None else None
+        st = torch.empty((n,), dtype=torch.int32, device=dev) if status or nms is not None else None
+        bsc = None if nms is None else (box_scores if box_scores is not None else boxes[:, 4])
         cs = torch.cuda.current_stream(dev).cuda_stream
         capi.check(self.lib.vp_infer_boxes_images_stream(self._h, table, len(frames), boxes.data_ptr(), row_stride, fip, n, int(pad),
                                                          None if ids is None else ids.ctypes.data, out.data_ptr(), None if cp is None else cp.data_ptr(),
                                                          None if st is None else st.data_ptr(), cs), self._h)
+        if nms is not None:   # the same stream, directly behind the boxes entry
+            score, rank, count = self.pose_nms(out, bsc, cp, len(frames), nms, status=st)
+            return (out, score, rank, count) + ((cp,) if crop_params else ()) + ((st,) if status else ())
         if cp is None and st is None:
             return out
         return (out,) + tuple(t for t in (cp, st) if t is not None)
+
+    # ------------------------------------------------------------ pose NMS
+    def _nms_sigmas(self, cfg: PoseNms, K: int) -> np.ndarray:
+        """the sigma table of a call.  The handle of a plain checkpoint does not know its dataset: its 17 joints are taken as COCO's when `cfg.sigmas` is None
+        (VitInference, which knows the dataset, resolves them first)."""
+        if not isinstance(cfg, PoseNms):
+            raise TypeError(f'a PoseNms expected, got {type(cfg).__name__}')
+        return resolve_sigmas(getattr(self, 'dataset', 'coco') if self._moe else 'coco', K, cfg.sigmas)
+
+    def pose_nms(self, keypoints, box_scores, crop_params, n_frames: int, cfg: PoseNms, status=None):
+        """Person scores and per-frame OKS pose NMS on the device (vp_pose_nms_stream, contract in include/vitpose_hip.h), stream-ordered on torch's current
+        stream without a host synchronisation.  `keypoints`: float32 CUDA [n, K, 3] in frame pixels (`infer_boxes`' out); `box_scores`: float32 CUDA [n], any
+        element stride (column 4 of a detector's [n, 6] tensor passes as the view it is); `crop_params`: int32 CUDA [n, 9]; `status`: int32 CUDA [n] or None.
+        Returns (score float32 [n], rank int32 [n], count int32 [n_frames]): keep the rows with `rank >= 0`."""
+        import torch
+        dev = torch.device('cuda', self.device_id)
+
+        def want(t, name, dtype, shape_ok, what):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype):
+                raise TypeError(f'{name}: a {dtype} torch CUDA tensor expected')
+            if t.device != dev or not shape_ok(t):
+                raise ValueError(f'{name}: {what} on {dev} expected, got {tuple(t.shape)} on {t.device}')
+        want(keypoints, 'keypoints', torch.float32, lambda t: t.ndim == 3 and t.shape[2] == 3 and t.is_contiguous(), 'contiguous [n, K, 3]')
+        n, K = keypoints.shape[0], keypoints.shape[1]
+        want(box_scores, 'box_scores', torch.float32, lambda t: tuple(t.shape) == (n,) and (n < 2 or t.stride(0) >= 1), f'[{n}] with a positive stride')
+        want(crop_params, 'crop_params', torch.int32, lambda t: tuple(t.shape) == (n, 9) and t.is_contiguous(), f'contiguous [{n}, 9]')
+        if status is not None:
+            want(status, 'status', torch.int32, lambda t: tuple(t.shape) == (n,) and t.is_contiguous(), f'contiguous [{n}]')
+        c, keep = nms_c_config(cfg, self._nms_sigmas(cfg, K))
+        score = torch.empty((n,), dtype=torch.float32, device=dev)
+        rank = torch.empty((n,), dtype=torch.int32, device=dev)
+        count = torch.empty((max(int(n_frames), 0),), dtype=torch.int32, device=dev)
+        cs = torch.cuda.current_stream(dev).cuda_stream
+        capi.check(self.lib.vp_pose_nms_stream(self._h, keypoints.data_ptr(), n, K, box_scores.data_ptr(), box_scores.stride(0) if n > 1 else 1,
+                                               crop_params.data_ptr(), None if status is None else status.data_ptr(), int(n_frames), C.byref(c),
+                                               score.data_ptr(), rank.data_ptr(), count.data_ptr(), cs), self._h)
+        return score, rank, count
+
+    def pose_nms_host(self, keypoints, box_scores, crop_params, n_frames: int, cfg: PoseNms, status=None):
+        """`pose_nms` on numpy arrays (vp_pose_nms: upload, the same kernel, download, synchronous)."""
+        kp = np.ascontiguousarray(keypoints, dtype=np.float32)
+        if kp.ndim != 3 or kp.shape[2] != 3:
+            raise ValueError(f'keypoints: [n, K, 3] expected, got {kp.shape}')
+        n, K = kp.shape[0], kp.shape[1]
+        bs = np.ascontiguousarray(box_scores, dtype=np.float32)
+        p9 = np.ascontiguousarray(crop_params, dtype=np.int32)
+        st = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        if bs.shape != (n,) or p9.shape != (n, 9) or (st is not None and st.shape != (n,)):
+            raise ValueError(f'box_scores [{n}], crop_params [{n}, 9] and status [{n}] expected')
+        c, keep = nms_c_config(cfg, self._nms_sigmas(cfg, K))
+        score, rank, count = np.empty(n, np.float32), np.empty(n, np.int32), np.empty(max(int(n_frames), 0), np.int32)
+        capi.check(self.lib.vp_pose_nms(self._h, kp.ctypes.data, n, K, bs.ctypes.data, 1, p9.ctypes.data, None if st is None else st.ctypes.data,
+                                        int(n_frames), C.byref(c), score.ctypes.data, rank.ctypes.data, count.ctypes.data), self._h)
+        return score, rank, count
 
     def heatmaps(self, crops: np.ndarray) -> np.ndarray:
         crops = np.ascontiguousarray(crops)

@@ -5,7 +5,8 @@ Kept from the reference: constructor signature (:81-90), ``reset`` (:174-185),
 ``postprocess`` (:187-205), ``inference(img) -> {id: (K,3) (y,x,score)}`` (:221-281),
 ``pre_img`` (:314-318), the state attributes (:112-116, :274-279) and the exception
 types.  Added: ``flip_test=`` (keyword): the reference's test-time flip averaging as a mode
-of the engine handle (a pair list, or True for the COCO-17 table).  Changed on purpose: the per-box Python loop that ran the model once per
+of the engine handle (a pair list, or True for the COCO-17 table); ``pose_nms=`` (keyword, a ``PoseNms``): person scores
+(keypoint confidence x box score, the reference's open note at :272) and per-frame OKS pose NMS after the pose call.  Changed on purpose: the per-box Python loop that ran the model once per
 crop (:259-272) becomes ONE batched call into the C ABI (``_inference_batch``);
 ``_inference`` (single crop, :207-219) is still there and returns ``[1, K, 3]``.
 
@@ -16,6 +17,7 @@ with the SORT ``update`` interface.  ``draw`` is not provided.
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 import typing
 from typing import Optional
@@ -26,6 +28,7 @@ from .configs import IMG_H, IMG_W, infer_dataset_by_path, infer_variant_from_sta
 from .cropprep import frames_crop_params, resize_linear_u8
 from .engine import VitPoseHip, decode_heatmaps
 from .moe import DATASETS as MOE_DATASETS, is_vitpose_plus
+from .posenms import PoseNms, resolve_sigmas
 
 __all__ = ['VitInference']
 
@@ -70,7 +73,8 @@ class VitInference:
                  is_video: Optional[bool] = False,
                  single_pose: Optional[bool] = False,
                  yolo_step: Optional[int] = 1,
-                 *, dtype: str = 'fp16', max_batch: int = 64, tracker=None, flip_test=None, shift_heatmap: bool = False):
+                 *, dtype: str = 'fp16', max_batch: int = 64, tracker=None, flip_test=None, shift_heatmap: bool = False,
+                 pose_nms: Optional[PoseNms] = None):
         state_dict = None
         dataset_given = dataset is not None
         if isinstance(model, (str, os.PathLike)):
@@ -142,6 +146,13 @@ class VitInference:
         shape = model_shape(model_name, None if nk else dataset, nk)
         # flip_test (the reference's test configs: flip_test=True): a pair list, or True for the COCO-17 table; refused before anything is loaded
         flip_pairs = resolve_flip_pairs(flip_test, dataset, shape.num_keypoints)
+        # pose_nms (data_cfg's oks_thr / vis_thr / soft_nms): off unless given; its sigma table is resolved, or refused, before anything is loaded
+        if pose_nms is not None and not isinstance(pose_nms, PoseNms):
+            raise TypeError(f'pose_nms: a PoseNms (or None) expected, got {type(pose_nms).__name__}')
+        self._pose_nms = None
+        if pose_nms is not None:
+            sig = resolve_sigmas(dataset, shape.num_keypoints, pose_nms.sigmas)
+            self._pose_nms = dataclasses.replace(pose_nms, sigmas=tuple(float(v) for v in sig))
         self._vit_pose = VitPoseHip(shape, state_dict,
                                     dtype=dtype, device_id=dev_id, max_batch=max_batch, dataset=dataset if plus else None)
         if flip_pairs is not None:   # a mode of the handle: every call below (inference, inference_frames, the boxes route) inherits it
@@ -259,6 +270,18 @@ class VitInference:
                 frame_keypoints[id_] = k
                 scores_bbox[id_] = score
             results.append((frame_keypoints, scores_bbox))
+        if self._pose_nms is not None and len(kps):
+            # kps holds frame pixels by now (the offsets above were added in place): one call for all frames, NMS per frame on the device
+            box = np.array([s for d in dets for s in d[2]], dtype=np.float32)
+            score, rank, _ = self._vit_pose.pose_nms_host(kps, box, p9, len(frames), self._pose_nms)
+            start = 0
+            for (bboxes, ids, scores), (frame_keypoints, scores_bbox) in zip(dets, results):
+                for i, id_ in enumerate(ids):
+                    if rank[start + i] < 0:   # a duplicate of a better pose of this frame (or beyond max_dets under soft NMS)
+                        del frame_keypoints[id_], scores_bbox[id_]
+                    else:
+                        scores_bbox[id_] = float(score[start + i])
+                start += len(bboxes)
         if self.save_state and len(imgs):
             bboxes, ids, scores = dets[-1]
             self._img = imgs[-1]

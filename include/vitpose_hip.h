@@ -405,6 +405,52 @@ VP_API int vp_dbg_image_plan(const vp_image* images, int32_t n_images, const int
 /* the device crop / zero-pad / resize kernel alone on ONE image whose planes are on the host (vp_dbg_crop_prep over vp_image): uint8 RGB crops [n, 256, 192, 3] */
 VP_API int vp_dbg_crop_prep_image(int32_t device_id, const vp_image* image, const int32_t* crop_params, int32_t n, uint8_t* out);
 
+/* Person scores and OKS pose NMS on the device, the stage behind the boxes entries (the reference's vit_utils/post_processing/nms.py oks_iou / oks_nms /
+ * soft_oks_nms with data_cfg's oks_thr, vis_thr, soft_nms; csrc/posenms.h states the arithmetic once for the kernel and the host taps).
+ * A row is one person: d_kpts float32 [n, k, 3] (y, x, conf) in frame pixels (the d_out of a boxes entry), a box score at d_box_score + i * score_stride
+ * (a detector's [n, 6] tensor passes in place as d_boxes + 4 with stride 6), a d_crop_params row {frame, x0, y0, cw, ch, ...} and d_status (may be NULL:
+ * every row good; then a bad box's all-zero d_crop_params row counts as a person of area 0 on frame 0).
+ *   area  = (double)cw * (double)ch.
+ *   score = (float)(mean of conf over the joints with conf > vis_thr, 0 if none; fp64 in joint order) * (double)box_score); use_vis_thr = 0: every joint.
+ *   oks(d | g) as nms.py:51-86: float32 dx, dy, dx*dx + dy*dy, then fp64 e = that / (2 sigma_j)^2 / ((a_g + a_d) / 2 + 2^-52) / 2 over the joints whose
+ *           CANDIDATE conf > vis_thr (the reference's `list(vg > t) and list(vd > t)` is the second list), oks = (float)(sum exp(-e) / count), 0 without joints.
+ *   Per frame: the live row with the highest score is picked (equal scores: the lower row; the reference's tie order is an argsort artefact) and gets the next
+ *   rank; hard: every live row with oks > oks_thr (float32 compare) is suppressed; soft != 0: every live row's fp64 score *= exp(-oks^2 / oks_thr), at most
+ *   max_dets picks, and a picked row's d_score is the score it was picked with (every other row keeps its instance score).
+ * d_score float32 [n]; d_rank int32 [n]: the pick order within the row's frame from 0, -1 suppressed / not reached within max_dets / status != 0 / frame
+ * outside [0, n_frames), -2 for every row of a frame with more than VP_NMS_MAX_PER_FRAME good rows (that frame is not processed; its rows keep their instance
+ * score); d_count (may be NULL) int32 [n_frames]: rows kept per frame.  Rows of a frame may lie anywhere in the call; a frame may have none.
+ * vp_pose_nms_stream only enqueues on caller_stream (one kernel, one workgroup per frame; the (2 sigma)^2 table travels by kernel argument): no synchronisation,
+ * no copy from host memory, no allocation, none of the handle's buffers -- correct directly behind a boxes entry on the same stream.  cfg and sigmas are HOST memory.
+ * VP_ERR_INVALID before anything is enqueued: a NULL required pointer with n > 0, k outside 1..VP_NMS_MAX_K, n_sigmas != k, a sigma that is not finite or <= 0,
+ * oks_thr outside (0, 1], soft with max_dets < 1, n > 0 with n_frames < 1, score_stride < 1.  n = 0: VP_OK, only d_count is written (zeros).
+ * vp_pose_nms: the synchronous twin on host pointers (upload, the same kernel, download).  Library builds that carry the stage define VP_HAS_POSE_NMS. */
+#define VP_HAS_POSE_NMS 1
+#define VP_NMS_MAX_PER_FRAME 1024
+#define VP_NMS_MAX_K 256
+typedef struct vp_pose_nms_cfg {
+    float oks_thr;
+    float vis_thr;
+    int32_t use_vis_thr;
+    int32_t soft;
+    int32_t max_dets;
+    int32_t n_sigmas;
+    const float* sigmas;   /* host [n_sigmas] */
+} vp_pose_nms_cfg;
+VP_API int vp_pose_nms_stream(vp_handle h, const float* d_kpts, int32_t n, int32_t k, const float* d_box_score, int32_t score_stride,
+                              const int32_t* d_crop_params, const int32_t* d_status, int32_t n_frames, const vp_pose_nms_cfg* cfg, float* d_score,
+                              int32_t* d_rank, int32_t* d_count, void* caller_stream);
+VP_API int vp_pose_nms(vp_handle h, const float* kpts, int32_t n, int32_t k, const float* box_score, int32_t score_stride, const int32_t* crop_params,
+                       const int32_t* status, int32_t n_frames, const vp_pose_nms_cfg* cfg, float* score, int32_t* rank, int32_t* count);
+/* HOST ONLY, no device needed: csrc/posenms.h run row by row on the host, the model the device is tested against (a test tap, never a fallback); the
+ * refusals of vp_pose_nms_stream, the reason in vp_last_error(NULL). */
+VP_API int vp_dbg_pose_nms_host(const float* kpts, int32_t n, int32_t k, const float* box_score, int32_t score_stride, const int32_t* crop_params,
+                                const int32_t* status, int32_t n_frames, const vp_pose_nms_cfg* cfg, float* score, int32_t* rank, int32_t* count);
+/* The pairwise tap: oks [n, n] float32, entry (g, d) = candidate d against pick g over all n rows (host pointers; no status, no frames; n <= 32768);
+ * device_id = -1: on the host (the serial sum of csrc/posenms.h), no device needed; a device runs the NMS kernel's evaluation -- the terms of an entry spread over
+ * the L lanes a frame of n members gets, added in joint order -- so n chooses the L under test (64 up to 4 rows, 16 at 16, 2 at 128, 1 beyond). */
+VP_API int vp_dbg_pose_oks(int32_t device_id, const float* kpts, int32_t n, int32_t k, const int32_t* crop_params, const vp_pose_nms_cfg* cfg, float* oks);
+
 /* HOST ONLY, no device needed: the plan those entries run for expert_ids [n] on a handle of n_experts experts and max_batch crops per chunk -- the pure function
  * ids -> order, segments that shapes their launches.  Per chunk c (crops [c max_batch, ...)), with B = max_batch rounded up to a multiple of 4:
  *   order [n]: position j of chunk c holds the chunk-local caller row order[c max_batch + j] (stable expert order)
