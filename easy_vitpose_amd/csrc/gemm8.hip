@@ -39,7 +39,10 @@
 //  * the residual epilogue (attn.proj / mlp.fc2: + bias + residual planes, two-plane output, LayerNorm row statistics):
 //    256 x 192 tiles stage the tile through LDS exactly like gemm.hip's producer epilogue; 256 x 256 tiles take it straight
 //    from registers (a row's four lanes are one 64-column statistics granule).  The row arithmetic is common.h's (planes_decode8,
-//    planes_split8, granule_stats8 / granule_stats16), as in every producer of the residual stream.
+//    planes_split8, granule_stats8 / granule_stats16), as in every producer of the residual stream.  What this kernel shares with gemm8f.hip is
+//    written once in gemm8_epilogue.h: the register-direct epilogue itself (g8_resid_regs: this kernel passes acc + bias as the lane's value) and
+//    the geometry of the LDS-staged one (G8ResidLds: passes, chunks, tile_row, LDS bytes -- also what launch8 opts in for).  The pass loop of the
+//    LDS-staged epilogue is still spelled out here and there: moved into a shared function it spills in this kernel (229-233 VGPRs as written).
 //
 //  * 192(m) x 256(n) tiles (G8<256, 192>): X halves of 96 rows (12 DMA pieces: see gemm8_common.h for who issues which), three m-fragments
 //    per wave and half.  M of this model is always a multiple of 192 (a crop is 192 tokens) and N = 768 = 3 x 256: mlp.fc2 gets the
@@ -51,7 +54,7 @@
 
 #include <cstdlib>
 #include "attn_core.h"
-#include "gemm8_common.h"
+#include "gemm8_epilogue.h"
 #ifndef VP_G8_RESD
 #define VP_G8_RESD 1
 #endif
@@ -157,7 +160,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
     f32x4 acc[C::TI][TJ];
     // fragment registers: the current X half (both k-halves), W0, W1
     u32x4 xs[MJ][2], fa[2][2], fb[2][2];
-    auto rowJ = [](int J) { return (J / MJ) * C::XR + (J % MJ) * 16; };   // tile row of m-fragment J of a wave (+ wr XR/2 + lane row)
+    auto rowJ = [](int J) { return g8_rowJ<C>(J); };   // tile row of m-fragment J of a wave (+ wr XR/2 + lane row)
 
     auto zero_acc = [&]() {
 #pragma unroll
@@ -273,13 +276,6 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
     };
 #undef KBAR
 #undef SEC
-    using M0 = std::integral_constant<int, 0>;
-    using M1 = std::integral_constant<int, 1>;
-    using M2 = std::integral_constant<int, 2>;
-    using M3 = std::integral_constant<int, 3>;
-    using M4 = std::integral_constant<int, 4>;
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
     // (re)start of the ring on the issue tile: K-tile 0 and X0 / W0 / W1 of K-tile 1 issued, K-tile 0 landed and visible
     auto ring_start = [&]() {
         issue(2, 0, 0, true); issue(0, 0, 0, true); issue(3, 0, 0, true); issue(1, 0, 0, true);
@@ -479,57 +475,14 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
                 if (wr) bar();   // stagger: waves 4-7 run one barrier behind waves 0-3
             }
         } else if constexpr (RESID && !RESID_LDS) {
-            // ---- residual epilogue straight from registers (EPI_BIAS_RESID_LN on 256 x 256 tiles) ----
-            // lane (fg_e, frow_e): rows m0 + (J >> 2) 128 + wr 64 + (J & 3) 16 + frow_e, columns nb .. nb + 15 (W rows are permuted on their
-            // way into LDS, see above).  st = acc + bias; the statistics granule is the four lanes fg_e = 0..3 of a row (common.h,
-            // granule_stats16).  No LDS, no barrier: the operand ring runs on across the tile boundary exactly as for the 16-bit epilogues.
+            // ---- residual epilogue straight from registers (EPI_BIAS_RESID_LN on 256-wide tiles): gemm8_epilogue.h, value = acc + bias ----
             const int nb = n0 + wc * 64 + fg_e * 16;
             const int mrow = m0 + wr * (C::XR / 2) + frow_e;
-            uint16_t* out_hi = (uint16_t*)g.out;
-            uint16_t* out_lo = out_hi + g.plane;
-            const uint16_t* aux_hi = (const uint16_t*)g.aux;
-            const uint16_t* aux_lo = aux_hi + g.plane;
             f32x4 bias4[4];
 #pragma unroll
             for (int f = 0; f < 4; ++f) bias4[f] = *(const f32x4*)(tbias + nb + f * 4);
-            const bool store = !(VP_ABLATE(g) & 8);
-            const int gran = g.N >> 6;
-            constexpr int RD = C::BM == 192 ? VP_G8_RESD192 : VP_G8_RESD;   // residual of row group J: hi cols 0-7, hi 8-15, lo 0-7, lo 8-15; fetched RD row groups ahead
-            u32x4 res[RD + 1][4];
-            auto load_res = [&](int J, u32x4(&r)[4]) {
-                const size_t o = (size_t)(mrow + rowJ(J)) * g.ldo + nb;
-                r[0] = *(const u32x4*)(aux_hi + o);
-                r[1] = *(const u32x4*)(aux_hi + o + 8);
-                r[2] = *(const u32x4*)(aux_lo + o);
-                r[3] = *(const u32x4*)(aux_lo + o + 8);
-            };
-#pragma unroll
-            for (int J = 0; J < RD; ++J) load_res(J, res[J]);
-#pragma unroll
-            for (int J = 0; J < TJ; ++J) {
-                if (J + RD < TJ) load_res(J + RD, res[(J + RD) % (RD + 1)]);
-                const u32x4(&r)[4] = res[J % (RD + 1)];
-                const int m = mrow + rowJ(J);
-                const size_t o = (size_t)m * g.ldo + nb;
-                float v[16];   // column nb + c
-#pragma unroll
-                for (int f = 0; f < 4; ++f) {
-                    const f32x4 st = acc[f][J] + bias4[f];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[f * 4 + e] = st[e] + planes_decode8<T>(r[f >> 1], r[2 + (f >> 1)], (f & 1) * 4 + e);
-                }
-                u32x4 oh[2], ol[2];
-                planes_split8<T>(v, oh[0], ol[0]);
-                planes_split8<T>(v + 8, oh[1], ol[1]);
-                if (store) {
-                    *(u32x4*)(out_hi + o) = oh[0];
-                    *(u32x4*)(out_hi + o + 8) = oh[1];
-                    *(u32x4*)(out_lo + o) = ol[0];
-                    *(u32x4*)(out_lo + o + 8) = ol[1];
-                }
-                const float2 gs = granule_stats16(v);
-                if (fg_e == 0 && store) *(float2*)(g.stats_out + ((size_t)m * gran + (nb >> 6)) * 2) = gs;
-            }
+            constexpr int RD = C::BM == 192 ? VP_G8_RESD192 : VP_G8_RESD;   // look-ahead of the residual loads, in row groups
+            g8_resid_regs<T, C, RD>(g, mrow, nb, fg_e, [&](int f, int J) { return acc[f][J] + bias4[f]; });
         } else if constexpr (!RESID) {
             // lane (fg_e, frow_e): rows m0 + (J >> 2) 128 + wr 64 + (J & 3) 16 + frow_e; columns (SPLIT, TI = 4) n0 + wc 64 + fg_e 8 + [0, 8) from
             // fragments 0, 1 and + 32 + [0, 8) from fragments 2, 3; otherwise n0 + wc 16 TI + fg_e 4 TI + [0, 4 TI).
@@ -589,13 +542,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
                     }
                     if (store) {
                         if constexpr (C::TI == 4) {
-                            if (VP_ABLATE(g) & 64) {   // experiment: streaming (non-temporal) stores
-                                __builtin_nontemporal_store(u32x4{o[0], o[1], o[2], o[3]}, (u32x4*)dst);
-                                __builtin_nontemporal_store(u32x4{o[4], o[5], o[6], o[7]}, (u32x4*)(dst + 32));
-                            } else {
-                                *(u32x4*)dst = u32x4{o[0], o[1], o[2], o[3]};
-                                *(u32x4*)(dst + 32) = u32x4{o[4], o[5], o[6], o[7]};   // SPLIT: the second run of 8 columns
-                            }
+                            *(u32x4*)dst = u32x4{o[0], o[1], o[2], o[3]};
+                            *(u32x4*)(dst + 32) = u32x4{o[4], o[5], o[6], o[7]};   // SPLIT: the second run of 8 columns
                         } else {   // 12 columns = 24 bytes, 8-byte aligned
                             *(u32x2*)dst = u32x2{o[0], o[1]};
                             *(u32x2*)(dst + 4) = u32x2{o[2], o[3]};
@@ -624,18 +572,12 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
             }
         } else {
             // Residual epilogue through LDS (the ring is drained first and restarted afterwards: fc2's 48 K-tiles make
-            // the tile boundary cheap).  Staging and chunk walk as in gemm.hip's fused-LayerNorm producer.
+            // the tile boundary cheap).  Staging and chunk walk as in gemm.hip's fused-LayerNorm producer; gemm8f.hip carries the same
+            // pass loop with its own value (a fix here is a fix there).
             static_assert(C::BM == 256, "the LDS-staged residual epilogue is written for 256-row tiles");
-            constexpr int ROWBYTES = C::BN * 4 + 16;
-            constexpr int JPP = (C::BN == 256) ? 2 : 4;  // m-fragments (per wave and X half) staged per pass
-            constexpr int CR = 32 * JPP;                 // rows per pass
-            constexpr int NPASS = 256 / CR;
-            constexpr int CPR = C::BN / 8;               // 8-element chunks per row
-            constexpr int NCH = CR * CPR / C::NT;        // chunks per thread per pass
-            constexpr int GR = C::BN / 64;
-            static_assert(NCH * C::NT == CR * CPR, "chunks must split evenly over threads");
-            static_assert(CR * ROWBYTES + C::BM * GR * 8 <= 160 * 1024, "LDS");
-            float* statbuf = (float*)(smem + CR * ROWBYTES);
+            using L = G8ResidLds<C>;   // geometry of the passes: gemm8_epilogue.h
+            constexpr int ROWBYTES = L::ROWBYTES, JPP = L::JPP, NPASS = L::NPASS, CPR = L::CPR, NCH = L::NCH, GR = L::GR;
+            float* statbuf = (float*)(smem + L::CR * ROWBYTES);
             uint16_t* out_hi = (uint16_t*)g.out;
             uint16_t* out_lo = out_hi + g.plane;
             const uint16_t* aux_hi = (const uint16_t*)g.aux;
@@ -645,10 +587,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
 #pragma unroll
             for (int f = 0; f < C::TI; ++f) bias4[f] = *(const f32x4*)(tbias + n0 + nl + f * 4);
             unsigned long long rs[6] = {ts0, ts1, 0, 0, 0, 0};   // tools/gemm8_timeline.py --resid: drain, passes, statistics, restart
-            // staged row lr of pass p  <->  tile row (p / (4/JPP)) 128 + (lr / (16 JPP)) 64 + ((p % (4/JPP)) JPP + (lr / 16) % JPP) 16 + lr % 16
-            auto tile_row = [&](int p, int lr) {
-                return (p / (4 / JPP)) * 128 + (lr / (16 * JPP)) * 64 + ((p % (4 / JPP)) * JPP + (lr / 16) % JPP) * 16 + (lr & 15);
-            };
+            auto tile_row = [&](int p, int lr) { return L::tile_row(p, lr); };   // (through a local lambda: called directly, hipcc allots two scalar registers the other way round)
             wait_vmcnt<0>();
             if (!wr) bar();     // undo the stagger: both groups meet here
             __syncthreads();    // every wave is done with the ring
@@ -733,7 +672,7 @@ static hipError_t launch8(const GemmArgs& a, hipStream_t s) {
     int ex = 0;   // the residual epilogue's per-crop expert instantiation (ViTPose+, GemmArgs::expert)
     if constexpr (EPI == EPI_BIAS_RESID_LN)
         if (a.expert) { kern = gemm8_kernel<T, EPI, C, true>; ex = 1; }
-    constexpr int LDS = (EPI == EPI_QKV_ATTN) ? 160 * 1024 : (EPI == EPI_BIAS_RESID_LN && C::BN != 256) ? ((128 * (C::BN * 4 + 16) + C::BM * (C::BN / 64) * 8) > C::RING ? (128 * (C::BN * 4 + 16) + C::BM * (C::BN / 64) * 8) : C::RING) : C::RING;
+    constexpr int LDS = (EPI == EPI_QKV_ATTN) ? 160 * 1024 : (EPI == EPI_BIAS_RESID_LN && C::BN != 256) ? G8ResidLds<C>::LDS : C::RING;
     static bool attr_done[2][64] = {};
     if (hipError_t e = lds_opt_in((const void*)kern, LDS, attr_done[ex]); e != hipSuccess) return e;
     const int tiles = (a.M / C::BM) * (a.N / C::BN);

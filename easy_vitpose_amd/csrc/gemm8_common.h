@@ -1,4 +1,5 @@
-// Shared pieces of the 8-phase GEMM kernels (gemm8.hip, gemm8f.hip, qkvattn.hip): tile geometry, barrier helper, tile walk.
+// Shared pieces of the 8-phase GEMM kernels (gemm8.hip, gemm8f.hip, qkvattn.hip): tile geometry, barrier helper, tile walk, the compile-time
+// tags of ktile().  The epilogues gemm8.hip and gemm8f.hip share are in gemm8_epilogue.h.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -37,22 +38,35 @@ __device__ __forceinline__ void bar() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// compile-time arguments of the kernels' ktile(): ring buffer B0 / B1, MODE M0 .. M4 (each kernel documents its modes at ktile)
+using M0 = std::integral_constant<int, 0>;
+using M1 = std::integral_constant<int, 1>;
+using M2 = std::integral_constant<int, 2>;
+using M3 = std::integral_constant<int, 3>;
+using M4 = std::integral_constant<int, 4>;
+using B0 = std::integral_constant<int, 0>;
+using B1 = std::integral_constant<int, 1>;
+
+// XCD-contiguous tile ranges: XCD x (= blockIdx & 7) owns tiles [base, base + cnt) of `ntiles`; this workgroup is number j0 of the nloc
+// workgroups on its XCD and walks tiles base + j0, base + j0 + nloc, ...  A launch of fewer than 256 tiles is one workgroup per tile, whatever the
+// count: XCD x then holds (G >> 3) + (x < (G & 7)) workgroups and owns exactly as many tiles -- nobody has a second tile.  (Rounding the grid down to a
+// multiple of 8 sent the last 1-7 tiles of e.g. a 252-tile launch into a second round: ViTPose-L fc2 at 63 crops 108 -> 147 us.)
+__device__ __forceinline__ void xcd_range(int ntiles, int& base, int& cnt, int& nloc, int& j0) {
+    const int xcd = blockIdx.x & 7;
+    j0 = blockIdx.x >> 3;
+    nloc = (gridDim.x >> 3) + (xcd < (int)(gridDim.x & 7) ? 1 : 0);
+    const int q = ntiles >> 3, r8 = ntiles & 7;
+    base = (xcd < r8) ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q;
+    cnt = q + (xcd < r8 ? 1 : 0);
+}
+
 struct TileWalk {   // XCD-contiguous, grouped tile order (same as gemm.hip's persistent kernel)
     int tiles_m, tiles_n, group_m, base, cnt, j0, nloc;
     __device__ __forceinline__ void init(const GemmArgs& g, int BM, int BN) {
         tiles_n = (g.N + BN - 1) / BN;
         tiles_m = (g.M + BM - 1) / BM;
         group_m = g.group_m;
-        const int ntiles = tiles_m * tiles_n;
-        const int xcd = blockIdx.x & 7;
-        j0 = blockIdx.x >> 3;
-        // workgroups on this XCD.  A launch of fewer than 256 tiles is one workgroup per tile, whatever the count: XCD x then holds
-        // (G >> 3) + (x < (G & 7)) workgroups and owns exactly as many tiles -- nobody has a second tile.  (Rounding the grid down to a multiple
-        // of 8 sent the last 1-7 tiles of e.g. a 252-tile launch into a second round: ViTPose-L fc2 at 63 crops 108 -> 147 us.)
-        nloc = (gridDim.x >> 3) + (xcd < (int)(gridDim.x & 7) ? 1 : 0);
-        const int q = ntiles >> 3, r8 = ntiles & 7;
-        base = (xcd < r8) ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q;
-        cnt = q + (xcd < r8 ? 1 : 0);
+        xcd_range(tiles_m * tiles_n, base, cnt, nloc, j0);
     }
     __device__ __forceinline__ void origin(int t, int reverse, int BM, int BN, int& m0, int& n0) const {
         int bid = base + t;

@@ -7,6 +7,10 @@
 //
 // Structure = gemm8.hip's (read its header first): 512-thread persistent workgroups, 256 x BN tiles, ring of two K-tiles of four slots,
 // two load / two MFMA sections per K-tile, two wave groups one barrier apart, counted vmcnt, W rows permuted on their way into LDS.
+// Shared code: tile geometry, tile walk, barrier helper and ktile()'s tags (gemm8_common.h); the register-direct residual epilogue
+// (g8_resid_regs) and the geometry of the LDS-staged one (G8ResidLds) (gemm8_epilogue.h).  This file's own: the K-loop on one-byte operands
+// with its scale loads and scale-register pinning, the MXFP8 output epilogue of mlp.fc1, and -- transcribed from gemm8.hip with
+// fma(acc, w_scale, bias) as the lane's value -- the pass loop of the LDS-staged residual epilogue and the 16-bit store addressing of attn.qkv.
 // What changes with one-byte operands:
 //   * a K-tile is 128 k (the same 128-byte LDS rows, the same slot geometry and swizzle): K = 768 is 6 K-tiles instead of 12, and a
 //     fragment pair (the two 16-byte reads of a row's k-halves, slots g and g + 4) is ONE MFMA operand: the instruction wants
@@ -25,7 +29,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "gemm8_common.h"
+#include "gemm8_epilogue.h"
 #include "mx8.h"
 
 namespace vp {
@@ -198,11 +202,6 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
         __builtin_amdgcn_s_setprio(0);
         bar();
     };
-    using M0 = std::integral_constant<int, 0>;
-    using M1 = std::integral_constant<int, 1>;
-    using M2 = std::integral_constant<int, 2>;
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
     // (re)start of the ring on the issue tile: K-tile 0 complete (incl. both scale dwords), X0 / W0 / W1 + scale of K-tile 1 in flight
     auto ring_start = [&]() {
         int dummy;
@@ -241,42 +240,18 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
         asm volatile("" : "+v"(frow_e), "+v"(fg_e));
         if constexpr (!RESID_LDS) { if (!wr) bar(); }
         if constexpr (RESID && !RESID_LDS) {
-            // residual epilogue straight from registers (256 x 256 tiles; gemm8.hip): st = fma(acc, w_scale, bias)
+            // residual epilogue straight from registers (256 x 256 tiles): gemm8_epilogue.h, value = fma(acc, w_scale, bias)
             const int nb = n0 + wc * 64 + fg_e * 16;
             const int mrow = m0 + wr * 64 + frow_e;
-            uint16_t* out_hi = (uint16_t*)g.out;
-            uint16_t* out_lo = out_hi + g.plane;
-            const uint16_t* aux_hi = (const uint16_t*)g.aux;
-            const uint16_t* aux_lo = aux_hi + g.plane;
             f32x4 bias4[4], ws4[4];
 #pragma unroll
             for (int f = 0; f < 4; ++f) { bias4[f] = *(const f32x4*)(g.bias + nb + f * 4); ws4[f] = *(const f32x4*)(g.w_scale + nb + f * 4); }
-            const int gran = g.N >> 6;
+            g8_resid_regs<T, C, 0>(g, mrow, nb, fg_e, [&](int f, int J) {
+                f32x4 v;
 #pragma unroll
-            for (int J = 0; J < 8; ++J) {
-                const int m = mrow + (J >> 2) * 128 + (J & 3) * 16;
-                const size_t o = (size_t)m * g.ldo + nb;
-                u32x4 r[4];   // hi cols 0-7, hi 8-15, lo 0-7, lo 8-15
-                r[0] = *(const u32x4*)(aux_hi + o);
-                r[1] = *(const u32x4*)(aux_hi + o + 8);
-                r[2] = *(const u32x4*)(aux_lo + o);
-                r[3] = *(const u32x4*)(aux_lo + o + 8);
-                float v[16];   // column nb + c
-#pragma unroll
-                for (int f = 0; f < 4; ++f)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        v[f * 4 + e] = __builtin_fmaf(acc[f][J][e], ws4[f][e], bias4[f][e]) + planes_decode8<T>(r[f >> 1], r[2 + (f >> 1)], (f & 1) * 4 + e);
-                u32x4 oh[2], ol[2];
-                planes_split8<T>(v, oh[0], ol[0]);
-                planes_split8<T>(v + 8, oh[1], ol[1]);
-                *(u32x4*)(out_hi + o) = oh[0];
-                *(u32x4*)(out_hi + o + 8) = oh[1];
-                *(u32x4*)(out_lo + o) = ol[0];
-                *(u32x4*)(out_lo + o + 8) = ol[1];
-                const float2 gs = granule_stats16(v);
-                if (fg_e == 0) *(float2*)(g.stats_out + ((size_t)m * gran + (nb >> 6)) * 2) = gs;
-            }
+                for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(acc[f][J][e], ws4[f][e], bias4[f][e]);
+                return v;
+            });
         } else if constexpr (MXOUT) {
             // mlp.fc1: v = gelu(acc * w_scale + bias), written as MXFP8 (the A operand of mlp.fc2).  Lane (fg_e, frow_e) holds, for each
             // of its 8 rows, 16 CONSECUTIVE columns n0 + wc 64 + fg_e 16 + [0, 16): a 32-column block is this lane and lane ^ 16.
@@ -351,17 +326,10 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
                 }
             }
         } else {
-            // residual epilogue through LDS (256 x 192 tiles; gemm8.hip): the ring is drained first and restarted afterwards
-            constexpr int ROWBYTES = C::BN * 4 + 16;
-            constexpr int JPP = (C::BN == 256) ? 2 : 4;
-            constexpr int CR = 32 * JPP;
-            constexpr int NPASS = 256 / CR;
-            constexpr int CPR = C::BN / 8;
-            constexpr int NCH = CR * CPR / C::NT;
-            constexpr int GR = C::BN / 64;
-            static_assert(NCH * C::NT == CR * CPR, "chunks must split evenly over threads");
-            static_assert(CR * ROWBYTES + C::BM * GR * 8 <= 160 * 1024, "LDS");
-            float* statbuf = (float*)(smem + CR * ROWBYTES);
+            // residual epilogue through LDS (256 x 192 tiles; gemm8.hip's pass loop with this kernel's value): the ring is drained first and restarted afterwards
+            using L = G8ResidLds<C>;   // geometry of the passes: gemm8_epilogue.h
+            constexpr int ROWBYTES = L::ROWBYTES, JPP = L::JPP, NPASS = L::NPASS, CPR = L::CPR, NCH = L::NCH, GR = L::GR;
+            float* statbuf = (float*)(smem + L::CR * ROWBYTES);
             uint16_t* out_hi = (uint16_t*)g.out;
             uint16_t* out_lo = out_hi + g.plane;
             const uint16_t* aux_hi = (const uint16_t*)g.aux;
@@ -370,9 +338,7 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
             f32x4 bias4[C::TI], ws4[C::TI];
 #pragma unroll
             for (int f = 0; f < C::TI; ++f) { bias4[f] = *(const f32x4*)(g.bias + n0 + nl + f * 4); ws4[f] = *(const f32x4*)(g.w_scale + n0 + nl + f * 4); }
-            auto tile_row = [&](int p, int lr) {
-                return (p / (4 / JPP)) * 128 + (lr / (16 * JPP)) * 64 + ((p % (4 / JPP)) * JPP + (lr / 16) % JPP) * 16 + (lr & 15);
-            };
+            auto tile_row = [&](int p, int lr) { return L::tile_row(p, lr); };   // (through a local lambda: called directly, hipcc allots two scalar registers the other way round)
             wait_vmcnt<0>();
             // The scale dwords the tile-boundary run-ahead fetched are dead in this variant (ring_start below fetches them again), and a
             // register hipcc considers dead is reused at once -- while the untracked load into it is still in flight (this was a memory
@@ -448,7 +414,7 @@ __global__ __launch_bounds__(512, 2) void gemm8f_kernel(GemmArgs g) {
 template <int EPI, class C>
 static hipError_t launch8f(const GemmArgs& a, hipStream_t s) {
     auto kern = gemm8f_kernel<EPI, C>;
-    constexpr int LDS = (EPI == EPI_BIAS_RESID_LN && C::BN != 256) ? ((128 * (C::BN * 4 + 16) + C::BM * (C::BN / 64) * 8) > C::RING ? (128 * (C::BN * 4 + 16) + C::BM * (C::BN / 64) * 8) : C::RING) : C::RING;
+    constexpr int LDS = (EPI == EPI_BIAS_RESID_LN && C::BN != 256) ? G8ResidLds<C>::LDS : C::RING;
     static bool attr_done[64] = {};
     if (hipError_t e = lds_opt_in((const void*)kern, LDS, attr_done); e != hipSuccess) return e;
     const int tiles = (a.M / C::BM) * (a.N / C::BN);

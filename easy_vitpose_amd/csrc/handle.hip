@@ -126,7 +126,7 @@ void read_switches(Switches& s) {
     on("VP_BLOCKED_HID", s.blocked_hid);
     num("VP_ORDER", s.order_mask);
     num("VP_G8_STAGGER", s.g8_stagger);
-    if (const char* t = getenv("VP_ABLATE_FAM")) {   // e.g. "2:64,1:64" = non-temporal stores in the qkv and fc1 epilogues
+    if (const char* t = getenv("VP_ABLATE_FAM")) {   // e.g. "2:8,1:8" = no output stores in the qkv and fc1 epilogues
         int f, b, used = 0;
         while (sscanf(t, "%d:%d%n", &f, &b, &used) == 2) {
             if (f >= 0 && f < VP_PROF_COUNT) s.fam_ablate[f] = b;

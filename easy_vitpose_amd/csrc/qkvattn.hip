@@ -49,12 +49,8 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
     const int K = g.D, nk = K >> 6;
     // tile walk: XCD x (= blockIdx & 7) owns a contiguous range of (pair, head) tiles, head fastest: the workgroups resident on one XCD
     // share a few X panels and the whole weight matrix in its L2
-    const int ntiles = g.npairs * g.heads;
-    const int xcd = blockIdx.x & 7, j0 = blockIdx.x >> 3;
-    const int nloc = (gridDim.x >> 3) + (xcd < (int)(gridDim.x & 7) ? 1 : 0);   // workgroups on this XCD (fewer than 256 tiles: one workgroup per tile, any count)
-    const int tq = ntiles >> 3, tr8 = ntiles & 7;
-    const int tbase = (xcd < tr8) ? xcd * (tq + 1) : tr8 * (tq + 1) + (xcd - tr8) * tq;
-    const int tcnt = tq + (xcd < tr8 ? 1 : 0);
+    int tbase, tcnt, nloc, j0;
+    xcd_range(g.npairs * g.heads, tbase, tcnt, nloc, j0);
     if (j0 >= tcnt) return;
 
     // ---- staging: piece p = LDS rows 8p .. 8p+7 of a slot (one DMA wave-instruction); wave w issues pieces w, w + 8 (, w + 16) ----
@@ -173,12 +169,6 @@ __global__ __launch_bounds__(512, 2) void qkvattn_kernel(QkvAttnArgs g) {
         __builtin_amdgcn_s_setprio(0);
         bar();
     };
-    using M0 = std::integral_constant<int, 0>;
-    using M1 = std::integral_constant<int, 1>;
-    using M2 = std::integral_constant<int, 2>;
-    using M3 = std::integral_constant<int, 3>;
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
     // start of the ring on the current tile: K-tile 0 landed and visible, X0 / W0 / W1 of K-tile 1 in flight (its X1 is issued by the first LA)
     auto ring_start = [&]() {
         issue(2, 0, 0); issue(0, 0, 0); issue(3, 0, 0); issue(1, 0, 0);

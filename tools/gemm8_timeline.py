@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where a gemm8 workgroup's time goes (GPU box only): cycle stamps of waves 0 and 4 of every workgroup of one qkv / fc1 launch.
-    python tools/gemm8_timeline.py [--ablate N] (N: 8 = no stores, 64 = non-temporal stores)   env VP_G8_STAGGER=n"""
+    python tools/gemm8_timeline.py [--ablate N] (N: 8 = no stores)   env VP_G8_STAGGER=n"""
 import argparse
 import ctypes as C
 import os
