@@ -38,7 +38,8 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_set_flip_test_experts', 'vp_dbg_mix_plan_flip', 'vp_dbg_decode_flip_mix',
            'vp_infer_images', 'vp_infer_boxes_images_stream', 'vp_dbg_image_plan', 'vp_dbg_crop_prep_image',
            'vp_dbg_gemm_case_planes', 'vp_dbg_gemm_fp8_case_planes', 'vp_dbg_attention_case',
-           'vp_pose_nms_stream', 'vp_pose_nms', 'vp_dbg_pose_nms_host', 'vp_dbg_pose_oks']
+           'vp_pose_nms_stream', 'vp_pose_nms', 'vp_dbg_pose_nms_host', 'vp_dbg_pose_oks',
+           'vp_dbg_ln_finalize', 'vp_dbg_gemm_case_lnpart', 'vp_dbg_qkvattn_ln', 'vp_dbg_ln_quant']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -183,6 +184,10 @@ def load_library():
     lib.vp_dbg_decode_mix.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vp_dbg_chunk_plan.argtypes = [C.POINTER(vp_config), C.c_int32, C.c_void_p, C.c_int32]
     lib.vp_dbg_qkvattn.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 4
+    lib.vp_dbg_qkvattn_ln.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 6
+    lib.vp_dbg_ln_finalize.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 2
+    lib.vp_dbg_gemm_case_lnpart.argtypes = [C.c_int32] * 9 + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 2
+    lib.vp_dbg_ln_quant.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 4
     lib.vp_set_flip_test.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32]
     lib.vp_clear_flip_test.argtypes = [H]
     lib.vp_flip_test_enabled.argtypes = [H]

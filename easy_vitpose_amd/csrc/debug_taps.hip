@@ -139,11 +139,16 @@ VP_API int vp_dbg_attention_case(int32_t device, int32_t dtype, int32_t B, int32
     return dbg_finish(c, VP_OK);
 }
 
+}  // extern "C"
+
 // attn.qkv + attention core in one kernel (qkvattn.hip): x [2 npairs 192, D] (rounded to dtype), Wqkv [3D, D], bias [3D] -> out [M, D] (as fp32).
 // Run with neutral LayerNorm statistics (mean 0, rstd 1, row sums 0: ln_fold(acc, 0, 0, 1, b) == acc + b exactly), so the result must equal
 // vp_dbg_gemm(epi 0) followed by vp_dbg_attention bit for bit.
-VP_API int vp_dbg_qkvattn(int32_t device, int32_t dtype, int32_t npairs, int32_t D, int32_t heads, const float* x, const float* W, const float* bias, float* out) {
-    if (npairs <= 0 || D <= 0 || heads <= 0 || !x || !W || !bias || !out) return fail(nullptr, VP_ERR_INVALID, "bad qkvattn test shape");
+// the body of vp_dbg_qkvattn (rowstat == ln_s == NULL: the neutral statistics) and vp_dbg_qkvattn_ln (the caller's rowstat [M,2] and row sums ln_s [3D], through the same
+// head-major repack as the bias)
+static int qkvattn_case(int32_t device, int32_t dtype, int32_t npairs, int32_t D, int32_t heads, const float* x, const float* W, const float* bias, const float* rowstat,
+                        const float* ln_s, float* out) {
+    if (npairs <= 0 || D <= 0 || heads <= 0 || !x || !W || !bias || !out || !rowstat != !ln_s) return fail(nullptr, VP_ERR_INVALID, "bad qkvattn test shape");
     vp_ctx* c = dbg_ctx(device, dtype);
     if (!c) return VP_ERR_HIP;
     const size_t M = (size_t)npairs * 384;
@@ -153,7 +158,7 @@ VP_API int vp_dbg_qkvattn(int32_t device, int32_t dtype, int32_t npairs, int32_t
     std::vector<float> zeros(3 * (size_t)D, 0.f), row(2 * M);
     for (size_t m = 0; m < M; ++m) { row[2 * m] = 0.f; row[2 * m + 1] = 1.f; }
     if ((rc = upload_mat(c, &dx, x, M, D, M)) || (rc = upload_mat(c, &dw, W, 3 * (size_t)D, D, pad128(3 * (size_t)D))) || (rc = upload_f32(c, &db, bias, 3 * (size_t)D)) ||
-        (rc = upload_f32(c, &ds, zeros.data(), 3 * (size_t)D)) || (rc = upload_f32(c, &drow, row.data(), 2 * M)) || (rc = dalloc(c, &dwh, 3 * (size_t)D * D)) ||
+        (rc = upload_f32(c, &ds, ln_s ? ln_s : zeros.data(), 3 * (size_t)D)) || (rc = upload_f32(c, &drow, rowstat ? rowstat : row.data(), 2 * M)) || (rc = dalloc(c, &dwh, 3 * (size_t)D * D)) ||
         (rc = dalloc(c, &dbh, 3 * (size_t)D)) || (rc = dalloc(c, &dsh, 3 * (size_t)D)) || (rc = dalloc(c, &dy, M * D)))
         return dbg_finish(c, rc);
     if (heads * 80 == D) {   // head dim 80: gemm8.hip EPI_QKV_ATTN on the 192 x 256 tile (one crop x one head), head-major weights of heads * 256 rows
@@ -180,6 +185,62 @@ VP_API int vp_dbg_qkvattn(int32_t device, int32_t dtype, int32_t npairs, int32_t
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, std::string("qkvattn: ") + hipGetErrorString(e)));
     return dbg_finish(c, download16(c, dy, out, M * D));
+}
+
+extern "C" {
+
+VP_API int vp_dbg_qkvattn(int32_t device, int32_t dtype, int32_t npairs, int32_t D, int32_t heads, const float* x, const float* W, const float* bias, float* out) {
+    return qkvattn_case(device, dtype, npairs, D, heads, x, W, bias, nullptr, nullptr, out);
+}
+
+// vp_dbg_qkvattn with the caller's LayerNorm statistics (tests/test_gpu_ln_consumer.py): rowstat [M,2] = (mean, rstd) per row, ln_s [3D] = the row sums of W.  Must equal
+// vp_dbg_gemm_case (epi 0, the same rowstat and ln_s) followed by vp_dbg_attention bit for bit.
+VP_API int vp_dbg_qkvattn_ln(int32_t device, int32_t dtype, int32_t npairs, int32_t D, int32_t heads, const float* x, const float* W, const float* bias,
+                             const float* rowstat, const float* ln_s, float* out) {
+    if (!rowstat || !ln_s) return fail(nullptr, VP_ERR_INVALID, "bad qkvattn test shape");
+    return qkvattn_case(device, dtype, npairs, D, heads, x, W, bias, rowstat, ln_s, out);
+}
+
+// ln_finalize_launch alone: partials [M, tiles, 2] = (sum, M2 about the granule mean) per 64-column granule -> rowstat [M, 2] = (mean, rstd) of rows of D columns
+// (tiles = 6 / 12 / 16 / 20: ln_finalize_kernel_t; anything else: the generic ln_finalize_kernel)
+VP_API int vp_dbg_ln_finalize(int32_t device, int32_t M, int32_t tiles, int32_t D, const float* partials, float* rowstat) {
+    if (M <= 0 || tiles <= 0 || D <= 0 || !partials || !rowstat) return fail(nullptr, VP_ERR_INVALID, "bad ln_finalize case");
+    vp_ctx* c = dbg_ctx(device, VP_DTYPE_F16);
+    if (!c) return VP_ERR_HIP;
+    float *dP, *dR;
+    int rc;
+    if ((rc = upload_f32(c, &dP, partials, (size_t)M * tiles * 2)) || (rc = dalloc(c, &dR, (size_t)M * 2))) return dbg_finish(c, rc);
+    hipError_t e = hipMemset(dR, 0xff, (size_t)M * 8);
+    if (e == hipSuccess) e = vp::ln_finalize_launch(dP, dR, M, tiles, D, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(rowstat, dR, (size_t)M * 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(c, VP_ERR_HIP, std::string("ln_finalize: ") + hipGetErrorString(e));
+    return dbg_finish(c, rc);
+}
+
+// ln_quant_launch alone (fp8 mode): x_hi [M, D] = the hi plane as 16-bit codes of `dtype`, partials [M, D / 64, 2] -> codes [Mp * D] (the blocked layout of csrc/mx8.h) and
+// scales [Mp * D / 32] (the packed dwords).  Both outputs are filled with 0xFF bytes before the launch: the padding rows M .. Mp - 1 must come back written (zero).
+VP_API int vp_dbg_ln_quant(int32_t device, int32_t dtype, int32_t M, int32_t Mp, int32_t D, const uint16_t* x_hi, const float* partials, uint8_t* codes, uint8_t* scales) {
+    if (M <= 0 || Mp < M || Mp % 64 || D <= 0 || D % 128 || !x_hi || !partials || !codes || !scales || (dtype != VP_DTYPE_F16 && dtype != VP_DTYPE_BF16))
+        return fail(nullptr, VP_ERR_INVALID, "bad ln_quant case");
+    vp_ctx* c = dbg_ctx(device, dtype);
+    if (!c) return VP_ERR_HIP;
+    const size_t MD = (size_t)M * D, PD = (size_t)Mp * D;
+    uint16_t* dX;
+    float* dP;
+    uint8_t *dC, *dS;
+    int rc;
+    if ((rc = dalloc(c, &dX, MD)) || (rc = upload_f32(c, &dP, partials, (size_t)M * (D / 64) * 2)) || (rc = dalloc(c, &dC, PD)) || (rc = dalloc(c, &dS, PD / 32)))
+        return dbg_finish(c, rc);
+    hipError_t e = hipMemcpy(dX, x_hi, MD * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dC, 0xff, PD);
+    if (e == hipSuccess) e = hipMemset(dS, 0xff, PD / 32);
+    if (e == hipSuccess) e = vp::ln_quant_launch(c->dtype, dX, dP, D / 64, dC, dS, M, Mp, D, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(codes, dC, PD, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(scales, dS, PD / 32, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(c, VP_ERR_HIP, std::string("ln_quant: ") + hipGetErrorString(e));
+    return dbg_finish(c, rc);
 }
 
 // LayerNorm(eps 1e-6): x [M,D] fp32 -> out16 (as fp32) [M,D] and out32 [M,D]
@@ -237,7 +298,8 @@ VP_API int vp_dbg_deconv(int32_t device, int32_t dtype, int32_t B, int32_t Hin, 
 // flags: 1 persistent, 2 out_blocked, 4 a_blocked, 8 reverse
 // the body of vp_dbg_gemm_case and vp_dbg_gemm_case_planes (io != NULL: epi 6 / 7 on plane bits; aux = pos for epi 7)
 static int gemm_case(int32_t device, int32_t dtype, int32_t epi, int32_t variant, int32_t group_m, int32_t flags, int32_t M, int32_t N, int32_t K, const float* A,
-                     const float* W, const float* bias, const float* aux, const float* rowstat, const float* ln_s, float* out, float* stats, const PlaneIO* io) {
+                     const float* W, const float* bias, const float* aux, const float* rowstat, const float* ln_s, float* out, float* stats, const PlaneIO* io,
+                     const float* ln_part = nullptr, int ln_tiles = 0) {
     if (M <= 0 || N <= 0 || K <= 0 || K % 64 || !A || !W || !bias) return fail(nullptr, VP_ERR_INVALID, "bad gemm case");
     vp_ctx* c = dbg_ctx(device, dtype);
     if (!c) return VP_ERR_HIP;
@@ -271,6 +333,11 @@ static int gemm_case(int32_t device, int32_t dtype, int32_t epi, int32_t variant
     if (rowstat && ln_s) {
         if ((r = upload_f32(c, &dRow, rowstat, (size_t)M * 2)) || (r = upload_f32(c, &dS, ln_s, N, wrows))) return dbg_finish(c, r);
         g.rowstat = dRow; g.ln_s = dS;
+    }
+    if (ln_part) {   // the consumer merges the producer's partial statistics itself: set as forward.hip sets them
+        float* dPart;
+        if ((r = upload_f32(c, &dPart, ln_part, (size_t)M * ln_tiles * 2)) || (r = upload_f32(c, &dS, ln_s, N, wrows))) return dbg_finish(c, r);
+        g.ln_part = dPart; g.ln_tiles = ln_tiles; g.ln_inv_d = 1.0f / (float)K; g.ln_s = dS;
     }
     size_t out_bytes = 0;
     const bool prod = epi == vp::EPI_BIAS_RESID_LN || epi == vp::EPI_POS_LN;
@@ -339,6 +406,14 @@ VP_API int vp_dbg_gemm_case(int32_t device, int32_t dtype, int32_t epi, int32_t 
                             const float* ln_s, float* out, float* stats) {
     if (!out) return fail(nullptr, VP_ERR_INVALID, "bad gemm case");
     return gemm_case(device, dtype, epi, variant, group_m, flags, M, N, K, A, W, bias, aux, rowstat, ln_s, out, stats, nullptr);
+}
+
+// vp_dbg_gemm_case for a LayerNorm consumer that merges the partial statistics in its prologue (GemmArgs::ln_part, epi 0 / 1): partials [M, ln_tiles, 2] instead of
+// rowstat, ln_inv_d = 1 / K as forward.hip sets it.  What gemm_launch refuses (an 8-phase tile, the persistent kernel, an odd ln_tiles) comes back as the error it is.
+VP_API int vp_dbg_gemm_case_lnpart(int32_t device, int32_t dtype, int32_t epi, int32_t variant, int32_t group_m, int32_t flags, int32_t M, int32_t N, int32_t K,
+                                   const float* A, const float* W, const float* bias, const float* partials, int32_t ln_tiles, const float* ln_s, float* out) {
+    if ((epi != vp::EPI_BIAS && epi != vp::EPI_BIAS_GELU) || !partials || ln_tiles <= 0 || !ln_s || !out) return fail(nullptr, VP_ERR_INVALID, "bad gemm ln_part case");
+    return gemm_case(device, dtype, epi, variant, group_m, flags, M, N, K, A, W, bias, nullptr, nullptr, ln_s, out, nullptr, nullptr, partials, ln_tiles);
 }
 
 // The producer row's own tap (tests/test_gpu_residual_row.py): vp_dbg_gemm_case for epi 6 / 7 with the residual stream as plane BITS on both sides, so that a test

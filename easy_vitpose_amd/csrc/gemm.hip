@@ -1005,6 +1005,8 @@ hipError_t gemm_launch(int dtype, int epi, const GemmArgs& a, hipStream_t s) {
     if (a.K % 64 != 0 || a.M <= 0 || a.N <= 0) return hipErrorInvalidValue;
     if (a.expert && ((epi != EPI_BIAS_RESID && epi != EPI_BIAS_RESID_LN) || a.persist || a.M % 192)) return hipErrorInvalidValue;   // per-crop experts: the residual GEMM only
     if (const Tile8Row* t8 = find_tile8(a.variant)) {   // the 8-phase kernel's tiles
+        // (their epilogues read rowstat only: a consumer handed partial statistics would run WITHOUT the fold.  resolve_gemm never plans it; refused here as well)
+        if (a.ln_part && (epi == EPI_BIAS || epi == EPI_BIAS_GELU)) return hipErrorInvalidValue;
 #ifdef VP_TOOLS
         static const int stagger_env = [] { const char* e = getenv("VP_G8_STAGGER"); return e ? atoi(e) : -1; }();
         if (stagger_env >= 0) {

@@ -554,6 +554,21 @@ VP_API int vp_dbg_gemm_case(int32_t device_id, int32_t dtype, int32_t epi, int32
 VP_API int vp_dbg_gemm_case_planes(int32_t device_id, int32_t dtype, int32_t epi, int32_t variant, int32_t group_m, int32_t flags, int32_t M, int32_t N,
                                    int32_t K, const float* A, const float* W, const float* bias, const uint16_t* r_hi, const uint16_t* r_lo,
                                    const float* pos, int32_t in_place, uint16_t* o_hi, uint16_t* o_lo, float* stats);
+/* The consumer side of the fused LayerNorm, one kernel each on host data (tests/test_gpu_ln_consumer.py).
+ * vp_dbg_ln_finalize: partials [M, tiles, 2] = (sum, M2 about the granule mean) per 64-column granule -> rowstat [M, 2] = (mean, rstd) of rows of D columns.
+ * vp_dbg_gemm_case_lnpart: vp_dbg_gemm_case for epi 0 / 1 with the partials [M, ln_tiles, 2] in place of rowstat -- the consumer merges them in its prologue
+ *   (ln_inv_d = 1 / K); an 8-phase tile, the persistent kernel and an odd ln_tiles are refused by the launcher and come back as an error, nothing is launched.
+ * vp_dbg_qkvattn_ln: vp_dbg_qkvattn with the caller's rowstat [M, 2] and row sums ln_s [3D] (head dim 64 and 80, through the same head-major repack).
+ * vp_dbg_ln_quant (fp8 mode): x_hi [M, D] = the hi plane as 16-bit codes, partials [M, D/64, 2] -> codes [Mp * D] and scales [Mp * D / 32] in the layouts of
+ *   csrc/mx8.h, both filled with 0xFF bytes before the launch (the padding rows M .. Mp - 1 must come back zero).  Mp % 64 == 0, D % 128 == 0. */
+VP_API int vp_dbg_ln_finalize(int32_t device_id, int32_t M, int32_t tiles, int32_t D, const float* partials, float* rowstat);
+VP_API int vp_dbg_gemm_case_lnpart(int32_t device_id, int32_t dtype, int32_t epi, int32_t variant, int32_t group_m, int32_t flags, int32_t M, int32_t N,
+                                   int32_t K, const float* A, const float* W, const float* bias, const float* partials, int32_t ln_tiles, const float* ln_s,
+                                   float* out);
+VP_API int vp_dbg_qkvattn_ln(int32_t device_id, int32_t dtype, int32_t npairs, int32_t D, int32_t heads, const float* x, const float* W, const float* bias,
+                             const float* rowstat, const float* ln_s, float* out);
+VP_API int vp_dbg_ln_quant(int32_t device_id, int32_t dtype, int32_t M, int32_t Mp, int32_t D, const uint16_t* x_hi, const float* partials, uint8_t* codes,
+                           uint8_t* scales);
 /* The sharding plan of vp_group_infer for n crops on w devices of max_batch maxb -- HOST ONLY, no device needed: the exact
  * function group_run executes.  Rounds of w * maxb crops; inside a round device i takes [off, off + cnt) with ceil(nr / w) crops
  * per device (trailing devices short or empty).  Entry e = round * w + device: offs[e], cnts[e].  Returns the number of
