@@ -39,7 +39,9 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_infer_images', 'vp_infer_boxes_images_stream', 'vp_dbg_image_plan', 'vp_dbg_crop_prep_image',
            'vp_dbg_gemm_case_planes', 'vp_dbg_gemm_fp8_case_planes', 'vp_dbg_attention_case',
            'vp_pose_nms_stream', 'vp_pose_nms', 'vp_dbg_pose_nms_host', 'vp_dbg_pose_oks',
-           'vp_dbg_ln_finalize', 'vp_dbg_gemm_case_lnpart', 'vp_dbg_qkvattn_ln', 'vp_dbg_ln_quant']
+           'vp_dbg_ln_finalize', 'vp_dbg_gemm_case_lnpart', 'vp_dbg_qkvattn_ln', 'vp_dbg_ln_quant',
+           'vp_infer_images_affine', 'vp_infer_boxes_affine_stream', 'vp_dbg_box_cs', 'vp_dbg_affine_plan', 'vp_dbg_crop_affine', 'vp_dbg_decode_affine',
+           'vp_dbg_decode_affine_flip']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -209,6 +211,14 @@ def load_library():
     lib.vp_pose_nms.argtypes = [H] + nms_host
     lib.vp_dbg_pose_nms_host.argtypes = nms_host
     lib.vp_dbg_pose_oks.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(vp_pose_nms_cfg), C.c_void_p]
+    lib.vp_infer_images_affine.argtypes = [H, C.POINTER(vp_image), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.vp_infer_boxes_affine_stream.argtypes = [H, C.POINTER(vp_image), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vp_dbg_box_cs.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
+    lib.vp_dbg_affine_plan.argtypes = [C.POINTER(vp_image), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.vp_dbg_crop_affine.argtypes = [C.c_int32, C.POINTER(vp_image), C.c_void_p, C.c_int32, C.c_void_p]
+    lib.vp_dbg_decode_affine.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.vp_dbg_decode_affine_flip.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if name not in ('vp_stream', 'vp_last_error', 'vp_host_alloc', 'vp_host_free', 'vp_group_member', 'vp_group_last_error'):
             getattr(lib, name).restype = C.c_int

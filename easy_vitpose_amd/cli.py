@@ -95,6 +95,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--soft-nms', action='store_true', help='--pose-nms: soft OKS NMS (scores decay instead of a hard cut; the reference\'s soft_nms)')
     ap.add_argument('--vis-thr', type=float, default=None, metavar='V', help='--pose-nms: joints at or below this confidence do not count (default 0.2)')
     ap.add_argument('--sigmas', default=None, metavar='FILE.json', help='--pose-nms: per-joint OKS sigmas of the dataset (built in for COCO-17 only)')
+    ap.add_argument('--crop', default='pad', choices=['pad', 'affine'], help='how a box becomes the 256 x 192 crop: pad (the default: +10 px, clipped, zero-padded to '
+                    '3:4 and resized, as VitInference.inference does) or affine (the training / evaluation protocol: the box extended to 3:4 with image content, '
+                    'scaled by --box-scale and warped; not together with --pose-nms)')
+    ap.add_argument('--box-scale', type=float, default=1.25, metavar='S', help='--crop affine: the factor the box is scaled by (the reference\'s 1.25)')
     return ap
 
 
@@ -130,7 +134,8 @@ def main(argv=None) -> int:
     model = VitInference(state_dict if state_dict is not None else args.model, detector, args.model_name or args.synthetic,
                          args.det_class, dataset, args.yolo_size, is_video=is_video, single_pose=args.single_pose,
                          yolo_step=args.yolo_step, dtype=args.dtype, max_batch=args.max_batch,
-                         flip_test=flip_test_argument(args), shift_heatmap=args.shift_heatmap, pose_nms=pose_nms_argument(args))
+                         flip_test=flip_test_argument(args), shift_heatmap=args.shift_heatmap, pose_nms=pose_nms_argument(args),
+                         crop=args.crop, box_scale=args.box_scale)
     print(f'>>> Model loaded: {args.model or "synthetic ViTPose-" + args.synthetic.upper()}')
     print(f'>>> Running inference on {args.input}')
     keypoints, dts = [], []

@@ -256,3 +256,97 @@ def to_rgb(frame) -> np.ndarray:
         return nv12_to_rgb(frame.planes[0], frame.planes[1], frame.matrix)
     a = _host(frame.planes[0])
     return np.ascontiguousarray(a[..., ::-1] if frame.format == 'bgr' else a)
+
+
+# ---- the training-protocol affine crop (csrc/affinegeom.h is the one device definition; include/vitpose_hip.h vp_infer_images_affine) ----------------
+BOX_MAX_SIDE = 1 << 24
+AFFINE_LIMIT = float(1 << 40)
+
+
+def box_to_cs(boxes, box_scale: float = 1.25) -> np.ndarray:
+    """float32 boxes [n, >= 4] (x1, y1, x2, y2) -> float32 [n, 4] (cx, cy, S_w, S_h): the centre and `scale * 200` of the reference's `_xywh2cs`
+    (datasets/COCO.py:322-337) at its widths under numpy 2 -- float64 up to the centre and the 3:4 extension, float32 from `w / 200` on.  The box is
+    extended to 3:4 with image content and scaled by `box_scale` (the reference's 1.25), not clipped to the frame; a side above 2^24 is clamped to 2^24.
+    Raises ValueError for a box that is not finite, has w <= 0 or h <= 0, or whose side underflows to 0 (the device entry gives those a status instead)."""
+    s = np.float32(box_scale)
+    if not (np.isfinite(s) and s > 0):
+        raise ValueError(f'box_scale must be finite and > 0, got {box_scale!r}')
+    b = np.ascontiguousarray(np.asarray(_host(boxes))[:, :4], dtype=np.float32).astype(np.float64)
+    if not np.isfinite(b).all():
+        raise ValueError('box_to_cs: a box coordinate is not finite')
+    w, h = b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]
+    if not ((w > 0).all() and (h > 0).all()):
+        raise ValueError('box_to_cs: an empty box (w <= 0 or h <= 0)')
+    cx, cy = (b[:, 0] + w * 0.5).astype(np.float32), (b[:, 1] + h * 0.5).astype(np.float32)
+    t = 0.75 * h
+    h2 = np.where(w > t, w / 0.75, h)
+    w2 = np.where(w < t, h * 0.75, w)
+    out = np.empty((len(b), 4), dtype=np.float32)
+    out[:, 0], out[:, 1] = cx, cy
+    with np.errstate(over='ignore'):
+        for j, side in ((2, w2), (3, h2)):
+            v = (side / 200.0).astype(np.float32)
+            v = (v * s).astype(np.float32)
+            v = (v * np.float32(200.0)).astype(np.float32)
+            out[:, j] = np.minimum(v, np.float32(BOX_MAX_SIDE))
+    if not (out[:, 2:] > 0).all():
+        raise ValueError('box_to_cs: an empty box (a side underflows to 0)')
+    return out
+
+
+def _affine_axis(n_out: int, a: float, b: float):
+    """source position and 1/32 fraction of every output index of one axis: Xq = floor((o a + b) 32 + 0.5), product and sum unfused in float64"""
+    src = np.arange(n_out, dtype=np.float64) * np.float64(a) + np.float64(b)
+    xq = np.floor(np.clip(src * 32.0 + 0.5, -AFFINE_LIMIT, AFFINE_LIMIT)).astype(np.int64)
+    return xq >> 5, xq & 31
+
+
+def affine_map(cs) -> tuple:
+    """(A_x, B_x, A_y, B_y) of one (cx, cy, S_w, S_h): src_x(ox) = ox A_x + B_x, src_y(oy) = oy A_y + B_y, float64 -- the inverse of
+    get_warp_matrix(0, c 2, [191, 255], S)"""
+    cx, cy, sw, sh = (np.float64(np.float32(v)) for v in cs)
+    return sw / 191.0, cx - sw * 0.5, sh / 255.0, cy - sh * 0.5
+
+
+def check_cs(cs) -> np.ndarray:
+    cs = np.ascontiguousarray(cs, dtype=np.float32).reshape(-1, 4)
+    if not (np.isfinite(cs).all() and (cs[:, 2:] > 0).all() and (cs[:, 2:] <= BOX_MAX_SIDE).all()):
+        raise ValueError('cs: finite (cx, cy, S_w, S_h) rows with 0 < S <= 2^24 expected')
+    return cs
+
+
+def affine_crops_host(frame, cs) -> np.ndarray:
+    """The affine crop on the host -> uint8 RGB [n, 256, 192, 3] (what `crop_affine_kernel` must reproduce bit for bit).  `frame`: anything `to_rgb` takes;
+    `cs` float32 [n, 4] (`box_to_cs`).  The project's own fixed-point contract: 1/32-pixel source positions, weights (32 - ax)(32 - ay) 32, ..., summing to 32768,
+    out = (sum w p + 16384) >> 15 per channel on source pixels converted to RGB8, a tap outside the frame 0; integer from Xq on.  Modelled on OpenCV's 8-bit
+    warpAffine(INTER_LINEAR, BORDER_CONSTANT 0); against that binary it is PARITY UNPINNED (cv2 is not installed here)."""
+    rgb = to_rgb(frame)
+    H, W = rgb.shape[:2]
+    cs = check_cs(cs)
+    padded = np.zeros((H + 2, W + 2, 3), dtype=np.int64)   # index 0 and H + 1 / W + 1: every position outside the frame
+    padded[1:-1, 1:-1] = rgb
+    out = np.empty((len(cs), IMG_H, IMG_W, 3), dtype=np.uint8)
+    for i, row in enumerate(cs):
+        a_x, b_x, a_y, b_y = affine_map(row)
+        sx, ax = _affine_axis(IMG_W, a_x, b_x)
+        sy, ay = _affine_axis(IMG_H, a_y, b_y)
+        x0, x1 = np.clip(sx + 1, 0, W + 1), np.clip(sx + 2, 0, W + 1)
+        y0, y1 = np.clip(sy + 1, 0, H + 1), np.clip(sy + 2, 0, H + 1)
+        ax, ay = ax[None, :, None], ay[:, None, None]
+        acc = ((32 - ax) * (32 - ay) * 32 * padded[y0[:, None], x0[None, :]] + ax * (32 - ay) * 32 * padded[y0[:, None], x1[None, :]]
+               + (32 - ax) * ay * 32 * padded[y1[:, None], x0[None, :]] + ax * ay * 32 * padded[y1[:, None], x1[None, :]])
+        out[i] = ((acc + 16384) >> 15).astype(np.uint8)
+    return out
+
+
+def affine_back_map(kp_hm, cs) -> np.ndarray:
+    """Heatmap-pixel keypoints [n, K, 3] (y, x, conf) with x in [0, 47], y in [0, 63] -> frame pixels as the affine decode writes them: float64,
+    x = rx (S_w / 47) + cx - S_w 0.5 step by step, rounded to float32 once (transform_preds(center, scale, use_udp=True))."""
+    kp = np.asarray(kp_hm)
+    cs = check_cs(cs).astype(np.float64)
+    out = np.empty(kp.shape, dtype=np.float32)
+    ry, rx = kp[..., 0].astype(np.float64), kp[..., 1].astype(np.float64)
+    out[..., 1] = (rx * (cs[:, 2] / 47.0)[:, None] + cs[:, 0][:, None] - (cs[:, 2] * 0.5)[:, None]).astype(np.float32)
+    out[..., 0] = (ry * (cs[:, 3] / 63.0)[:, None] + cs[:, 1][:, None] - (cs[:, 3] * 0.5)[:, None]).astype(np.float32)
+    out[..., 2] = kp[..., 2]
+    return out

@@ -170,6 +170,7 @@ struct vp_ctx {
         int expert = 0;                  // a ViTPose+ handle's active expert (fc2 weights, head, K)
         const int32_t* post = nullptr;   // vp_infer_boxes_stream: the frame-offset kernel after the decode (its aux buffer; null: none)
         uint32_t flip = 0;               // the flip-test mode's generation the launches were captured under (flip_gen; 0: mode off)
+        const float* cs = nullptr;       // the affine crop route: the decode reads (cx, cy, S_w, S_h) per crop here and writes frame pixels (null: the pad route's decode)
         // the per-crop expert entries (vp_infer_experts_device_stream, ...).  mix = the chunk's expert pattern, the count per expert in an exact encoding
         // (mix_pattern): with the crops in stable expert order the counts determine every launch -- the gather, the encoder's tile bounds, each head's rows -- and
         // the permutation lives in table buffers the launches only point at.  0 for every chunk that runs one expert.  wide: the decode goes the record route
@@ -178,7 +179,7 @@ struct vp_ctx {
         bool wide = false;
         bool operator==(const GraphKey& o) const {
             return n == o.n && fmt == o.fmt && src == o.src && wh == o.wh && out == o.out && expert == o.expert && post == o.post && flip == o.flip &&
-                   mix == o.mix && wide == o.wide;
+                   cs == o.cs && mix == o.mix && wide == o.wide;
         }
     };
     struct GraphEntry { GraphKey key; hipGraphExec_t exec = nullptr; bool no_graph = false; };   // no_graph: capture or launch failed once, the key stays eager
@@ -198,6 +199,8 @@ struct vp_ctx {
     uint8_t* frame_stage = nullptr;   // staging arena of vp_infer_frames / vp_infer_frame: the row band of every host frame of the current call
     size_t frame_cap = 0;
     vp::CropRec* crecs = nullptr;     // per-crop source + geometry of the current chunk [max_batch]
+    vp::AffRec* arecs = nullptr;      // the affine crop route (vp_infer_images_affine, vp_infer_boxes_affine_stream): per-crop source + inverse map of the current chunk [max_batch]
+    float* cs_stage = nullptr;        // ... and its (cx, cy, S_w, S_h) rows, what the affine decode reads [max_batch][4]
     int32_t* box_aux = nullptr;       // vp_infer_boxes_stream: per box of the current chunk (y0 - top_pad, x0 - left_pad, status, 0) [max_batch][4]
     // ViTPose+ (multi-dataset "mixture of experts") handle, vp_load_weights on a state dict with backbone.blocks.*.mlp.experts.*: mlp.fc2 of block l is one full
     // [D, 4D] matrix + [D] bias per expert (the split model's: shared rows then the expert's P rows), blocks[l].w_fc2 / b_fc2 point at expert 0 and expert e lies
@@ -317,6 +320,14 @@ int image_plan(const vp_image* frames, int n_frames, const int32_t* p9, int n, i
 // memory of the handle's device first).  recs[n] (host), enqueued on c->stream
 int stage_frames(vp_ctx* c, const vp_image* frames, int n_frames, bool on_device, const int32_t* p9, int n, const int32_t* bands,
                  std::vector<vp::CropRec>& recs);
+// its first half, shared with the affine route: row0_ptr[2 f + p] = plane p of frame f at the first row of its band (null: no band), staged or in place
+int stage_bands(vp_ctx* c, const vp_image* frames, int n_frames, bool on_device, const int32_t* bands, std::vector<const uint8_t*>& row0_ptr);
+// vp_infer_images_affine's plan (HOST ONLY): checks every crop (frame index, finite centre, 0 < S <= BOX_MAX_SIDE) and, at the first crop that names it, its frame;
+// bands [n_frames, 2] = frame rows [row0, row1) its crops tap (affinegeom.h affine_row_band; {0, 0}: none; may be NULL).  VP_OK or VP_ERR_INVALID with the reason in *why
+int affine_plan(const vp_image* frames, int n_frames, const int32_t* frame_idx, const float* cs, int n, int32_t* bands, std::string* why);
+// the crops of (frame_idx, cs) as affine crop records over the bands stage_bands placed
+void affine_records(const vp_image* frames, const int32_t* frame_idx, const float* cs, int n, const int32_t* bands, const std::vector<const uint8_t*>& row0_ptr,
+                    std::vector<vp::AffRec>& recs);
 // vp_infer_boxes_stream / vp_dbg_box_geometry (HOST ONLY): the host arguments of a boxes call (sizes of every frame, row stride, pad, counts).
 // VP_OK or VP_ERR_INVALID with the reason in *why
 int box_args(int n_frames, const int32_t* frame_hw, int hw_stride, int row_stride, int n, int pad, std::string* why);
@@ -398,10 +409,10 @@ struct FwdOpts {
 };
 int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, const FwdOpts& o = FwdOpts());
 int head_chunk(vp_ctx* c, const uint16_t* y, int nh, float* hm, const HeadPlan& hp);
-int decode_chunk(vp_ctx* c, const int32_t* d_wh, float* d_out, int n, bool twin);
+int decode_chunk(vp_ctx* c, const int32_t* d_wh, float* d_out, int n, bool twin, const float* d_cs = nullptr);   // d_cs: the affine route's decode (d_wh unused)
 int chunk_cap(const vp_ctx* c);
 int chunk_rows(const vp_ctx* c, int nb);
 int forward_mode_chunk(vp_ctx* c, const void* d_src, int fmt, int nb);
-int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh, float* d_out, const int32_t* post = nullptr);
+int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh, float* d_out, const int32_t* post = nullptr, const float* d_cs = nullptr);
 
 }  // namespace vpi

@@ -455,6 +455,31 @@ VP_API int vp_dbg_crop_prep_image(int32_t device, const vp_image* image, const i
     return dbg_finish(c, rc);
 }
 
+// image + centres and scales -> the uint8 [n,256,192,3] RGB crops of the affine route (crop_affine_kernel alone, behind the staging of vp_infer_images_affine:
+// the one-frame case)
+VP_API int vp_dbg_crop_affine(int32_t device, const vp_image* image, const float* cs, int32_t n, uint8_t* out) {
+    if (!image || !cs || !out || n <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
+    int32_t band[2];
+    std::string why;
+    if (affine_plan(image, 1, nullptr, cs, n, band, &why)) return fail(nullptr, VP_ERR_INVALID, why);
+    vp_ctx* c = dbg_ctx(device, VP_DTYPE_F16);
+    if (!c) return VP_ERR_HIP;
+    std::vector<const uint8_t*> row0_ptr;
+    std::vector<vp::AffRec> recs;
+    uint8_t* dout;
+    vp::AffRec* drec;
+    int rc;
+    const size_t ob = (size_t)n * 256 * 192 * 3;
+    if ((rc = stage_bands(c, image, 1, false, band, row0_ptr)) || (rc = dalloc(c, &dout, ob)) || (rc = dalloc(c, &drec, (size_t)n))) return dbg_finish(c, rc);
+    affine_records(image, nullptr, cs, n, band, row0_ptr, recs);
+    hipError_t e = hipMemcpy(drec, recs.data(), (size_t)n * sizeof(vp::AffRec), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = vp::crop_affine_launch(drec, dout, n, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(c, VP_ERR_HIP, std::string("crop_affine: ") + hipGetErrorString(e));
+    return dbg_finish(c, rc);
+}
+
 // ... on a packed RGB frame
 VP_API int vp_dbg_crop_prep(int32_t device, const uint8_t* frame, int32_t fh, int32_t fw, const int32_t* crop_params, int32_t n, uint8_t* out) {
     if (!frame || fh <= 0 || fw <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");

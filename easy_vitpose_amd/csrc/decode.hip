@@ -42,7 +42,12 @@ struct GaussK { float w[11]; };
 // FLIP and MIX (the per-expert flip-test mode, decode_flip_mix_launch): `recs` holds MixRecFlip records, `partner` the [n_experts, Kmax] table.  The crop's K_e maps
 // start at `first`, its mirror's at first + K_e (a [2, K_e, 64, 48] pair), and the mirror is read through row e of the table: the FLIP body on the values it sees
 // for that pair under expert e's table, so the bits are decode_kernel<true, false>'s.  The three other instantiations keep their instruction streams.
-template <bool FLIP, bool MIX>
+//
+// AFF (the affine crop route, decode_affine_launch / decode_affine_flip_launch; never with MIX): `org_wh` carries float32 cs[row] = (cx, cy, S_w, S_h) instead of integer
+// sizes, and the last thread writes FRAME pixels with one rounding, transform_preds(center, scale, use_udp=True) on the box's own centre and scale:
+// x = (float)(rx (S_w / 47) + cx - S_w 0.5) in fp64, every step unfused (so a host restatement in numpy has the same bits), y with 63 and S_h.  A row whose
+// S_w is not > 0 is a refused box: all zero.  AFF is compile-time too: the four instantiations without it keep their instruction streams.
+template <bool FLIP, bool MIX, bool AFF = false>
 __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ hm, const int32_t* __restrict__ org_wh,
                                                      float* __restrict__ out, int K, GaussK gk, const int32_t* __restrict__ partner, int shift,
                                                      const MixRec* __restrict__ recs) {
@@ -170,6 +175,18 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
         const float ry = (float)((double)cy - oy);
         // transform_preds(use_udp=True) with center = (w//2, h//2), scale = (w, h)
         // (post_transforms.py:183-192, inference.py:200-204), float64 then float32
+        if (AFF) {
+            const float* q = (const float*)org_wh + 4 * (size_t)n;
+            const double sw = (double)q[2], sh = (double)q[3];
+            float* o = out + (size_t)blockIdx.x * 3;
+            if (!(q[2] > 0.f)) { o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; return; }
+            const double fx = __dsub_rn(__dadd_rn(__dmul_rn((double)rx, __ddiv_rn(sw, WW - 1.0)), (double)q[0]), __dmul_rn(sw, 0.5));
+            const double fy = __dsub_rn(__dadd_rn(__dmul_rn((double)ry, __ddiv_rn(sh, HH - 1.0)), (double)q[1]), __dmul_rn(sh, 0.5));
+            o[0] = (float)fy;
+            o[1] = (float)fx;
+            o[2] = maxval;
+            return;
+        }
         int ow = 192, oh = 256;
         if (org_wh) { ow = org_wh[2 * (MIX ? row : n)]; oh = org_wh[2 * (MIX ? row : n) + 1]; }
         const double fx = (double)rx * ((double)ow / (WW - 1.0)) + (double)(ow / 2) - (double)ow * 0.5;
@@ -211,6 +228,18 @@ hipError_t decode_flip_mix_launch(const float* hm, const MixRecFlip* recs, const
                                   hipStream_t s) {
     if (!recs || !partners) return hipErrorInvalidValue;
     hipLaunchKernelGGL((decode_kernel<true, true>), dim3(N * Kmax), dim3(256), 0, s, hm, org_wh, out, Kmax, gauss11(), partners, shift, (const MixRec*)recs);
+    return hipGetLastError();
+}
+
+hipError_t decode_affine_launch(const float* hm, const float* cs, float* out, int N, int K, hipStream_t s) {
+    if (!cs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((decode_kernel<false, false, true>), dim3(N * K), dim3(256), 0, s, hm, (const int32_t*)cs, out, K, gauss11(), (const int32_t*)nullptr, 0, (const MixRec*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t decode_affine_flip_launch(const float* hm, const int32_t* partner, int shift, const float* cs, float* out, int N, int K, hipStream_t s) {
+    if (!cs || !partner) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((decode_kernel<true, false, true>), dim3(N * K), dim3(256), 0, s, hm, (const int32_t*)cs, out, K, gauss11(), partner, shift, (const MixRec*)nullptr);
     return hipGetLastError();
 }
 

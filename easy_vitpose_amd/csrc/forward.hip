@@ -252,8 +252,13 @@ int head_chunk(vp_ctx* c, const uint16_t* y, int nh, float* hm, const HeadPlan& 
 }
 
 // twin: c->hm holds the 2 n interleaved maps forward_mode_chunk leaves under the flip-test mode (never vp_infer_flip's own two passes, whatever the mode)
-int decode_chunk(vp_ctx* c, const int32_t* d_wh, float* d_out, int n, bool twin) {
-    if (twin)
+int decode_chunk(vp_ctx* c, const int32_t* d_wh, float* d_out, int n, bool twin, const float* d_cs) {
+    if (d_cs && twin)
+        LAUNCH(c, VP_PROF_DECODE, 0.0, 8.0 * n * c->Kp * 3072.0 + 12.0 * n * c->Kp,
+               vp::decode_affine_flip_launch(c->hm, flip_table_now(c), c->flip_shift, d_cs, d_out, n, c->Kp, c->stream));
+    else if (d_cs)
+        LAUNCH(c, VP_PROF_DECODE, 0.0, 4.0 * n * c->Kp * 3072.0 + 12.0 * n * c->Kp, vp::decode_affine_launch(c->hm, d_cs, d_out, n, c->Kp, c->stream));
+    else if (twin)
         LAUNCH(c, VP_PROF_DECODE, 0.0, 8.0 * n * c->Kp * 3072.0 + 12.0 * n * c->Kp,
                vp::decode_flip_launch(c->hm, flip_table_now(c), c->flip_shift, d_wh, d_out, n, c->Kp, c->stream));
     else
@@ -337,7 +342,7 @@ static int chunk_body(vp_ctx* c, const GraphKey& k) {
     int rc;
     if (k.wide) return mix_chunk_body(c, k);
     if ((rc = forward_mode_chunk(c, k.src, k.fmt, k.n))) return rc;
-    if ((rc = decode_chunk(c, k.wh, k.out, k.n, c->flip_on))) return rc;
+    if ((rc = decode_chunk(c, k.wh, k.out, k.n, c->flip_on, k.cs))) return rc;
     return k.post ? offsets_chunk(c, k.post, k.out, k.n) : VP_OK;
 }
 
@@ -393,9 +398,10 @@ static int graph_give_up(vp_ctx* c, GraphEntry* ge) {
 // forward + decode of one chunk.  Small chunks (<= graph_max_n rows, profiling off) are launch-bound -- ~110-290 launches of a few
 // microseconds each -- so the second time the same key (GraphKey, api_internal.h) is seen the chunk is captured into a hipGraph
 // and from then on replayed with one hipGraphLaunch.
-int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh, float* d_out, const int32_t* post) {
+int run_chunk(vp_ctx* c, const void* d_src, int fmt, int nb, const int32_t* d_wh, float* d_out, const int32_t* post, const float* d_cs) {
     if (nb > chunk_cap(c)) return fail(c, VP_ERR_INVALID, "a chunk of " + std::to_string(nb) + " crops exceeds what the handle's workspaces hold in this mode");
-    GraphKey key{nb, fmt, d_src, d_wh, d_out, c->expert, post, c->flip_gen};
+    GraphKey key{nb, fmt, d_src, d_wh, d_out, c->expert, post, c->flip_gen, d_cs};
+    if (c->mix && d_cs) return fail(c, VP_ERR_STATE, "the affine crop route does not run a chunk with per-crop experts");
     if (c->mix) {   // a per-crop expert entry: its chunk's pattern, or the one expert the whole chunk runs
         if ((c->flip_on && !c->flip_ex) || c->mix->nb != nb) return fail(c, VP_ERR_STATE, "a chunk with per-crop experts under the single-table flip-test mode, or a plan of another chunk");
         key.wide = true;

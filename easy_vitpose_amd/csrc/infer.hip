@@ -1,6 +1,7 @@
 // The inference entries of the C ABI (include/vitpose_hip.h) and their staging: host crops, device crops on the handle's or a caller's stream,
 // the two asynchronous slots, frames, device boxes, ViTPose+ mixed batches (vp_infer_experts; per-crop experts on the device, frames and boxes entries with
 // their host-side plan, mix_plan, and its doubled form under the per-expert flip-test mode, mix_records_flip), vp_infer_flip.  Each walks its crops in chunks (for_chunks) and hands a chunk to forward.hip.
+#include "affinegeom.h"
 #include "api_internal.h"
 #include "boxgeom.h"
 #include "pixfmt.h"
@@ -243,10 +244,9 @@ int image_plan(const vp_image* frames, int n_frames, const int32_t* p9, int n, i
     return VP_OK;
 }
 
-int stage_frames(vp_ctx* c, const vp_image* frames, int n_frames, bool on_device, const int32_t* p9, int n, const int32_t* bands,
-                 std::vector<vp::CropRec>& recs) {
+int stage_bands(vp_ctx* c, const vp_image* frames, int n_frames, bool on_device, const int32_t* bands, std::vector<const uint8_t*>& row0_ptr) {
     // plane p of frame f at the first row of its band, where the kernel reads it: Y / RGB row bands[2 f], UV row bands[2 f] >> 1
-    std::vector<const uint8_t*> row0_ptr((size_t)n_frames * 2, nullptr);
+    row0_ptr.assign((size_t)n_frames * 2, nullptr);
     auto band_rows = [&](int f, int p, int64_t* r0, int64_t* r1) {   // rows [*r0, *r1) of plane p the band covers
         *r0 = p ? bands[2 * f] >> 1 : bands[2 * f];
         *r1 = p ? ((int64_t)bands[2 * f + 1] + 1) >> 1 : bands[2 * f + 1];
@@ -290,6 +290,13 @@ int stage_frames(vp_ctx* c, const vp_image* frames, int n_frames, bool on_device
             }
         }
     }
+    return VP_OK;
+}
+
+int stage_frames(vp_ctx* c, const vp_image* frames, int n_frames, bool on_device, const int32_t* p9, int n, const int32_t* bands,
+                 std::vector<vp::CropRec>& recs) {
+    std::vector<const uint8_t*> row0_ptr;
+    if (const int rc = stage_bands(c, frames, n_frames, on_device, bands, row0_ptr)) return rc;
     recs.resize(n);
     for (int i = 0; i < n; ++i) {
         const int32_t* p = p9 + 9 * (size_t)i;
@@ -305,6 +312,57 @@ int stage_frames(vp_ctx* c, const vp_image* frames, int n_frames, bool on_device
         r.format = im.format; r.matrix = im.matrix; r.oy = p[2] & 1; r.ox = p[1] & 1;
     }
     return VP_OK;
+}
+
+int affine_plan(const vp_image* frames, int n_frames, const int32_t* frame_idx, const float* cs, int n, int32_t* bands, std::string* why) {
+    auto bad = [&](const std::string& m) { if (why) *why = m; return VP_ERR_INVALID; };
+    if (n < 0) return bad("negative crop count");
+    if (n > 0 && n_frames <= 0) return bad("crops given but no frames");
+    if (n > 0 && (!frames || !cs)) return bad("null frame table or centre / scale table");
+    const int nf = n_frames > 0 ? n_frames : 0;
+    std::vector<int32_t> lo(nf, INT32_MAX), hi(nf, -1);
+    std::vector<uint8_t> seen(nf, 0);
+    for (int i = 0; i < n; ++i) {
+        const int f = frame_idx ? frame_idx[i] : 0;
+        const float* q = cs + 4 * (size_t)i;
+        const std::string at = "crop " + std::to_string(i) + ": ";
+        if (f < 0 || f >= n_frames) return bad(at + "frame index " + std::to_string(f) + " outside [0, " + std::to_string(n_frames) + ")");
+        const vp_image& fr = frames[f];
+        if (!fr.plane[0]) return bad(at + "frame " + std::to_string(f) + " has no data");
+        if (fr.h <= 0 || fr.w <= 0 || fr.h > vp::BOX_MAX_SIDE || fr.w > vp::BOX_MAX_SIDE) return bad(at + "frame " + std::to_string(f) + " has a size outside [1, 2^24]");
+        if (!seen[f]) {   // the first crop that names the frame: its layout
+            std::string w;
+            if (image_check(fr, f, &w)) return bad(at + w);
+            seen[f] = 1;
+        }
+        if (!vp::cs_valid(q)) return bad(at + "centre not finite, or a scale that is not finite, not positive or above 2^24");
+        int32_t l, h;
+        vp::affine_row_band(q, fr.h, &l, &h);
+        if (l < h) { lo[f] = std::min(lo[f], l); hi[f] = std::max(hi[f], h); }
+    }
+    if (bands)
+        for (int f = 0; f < nf; ++f) {
+            bands[2 * f] = hi[f] < 0 ? 0 : lo[f];
+            bands[2 * f + 1] = hi[f] < 0 ? 0 : hi[f];
+        }
+    return VP_OK;
+}
+
+void affine_records(const vp_image* frames, const int32_t* frame_idx, const float* cs, int n, const int32_t* bands, const std::vector<const uint8_t*>& row0_ptr,
+                    std::vector<vp::AffRec>& recs) {
+    recs.resize(n);
+    for (int i = 0; i < n; ++i) {
+        const int f = frame_idx ? frame_idx[i] : 0;
+        const vp_image& im = frames[f];
+        const bool nv12 = im.format == vp::PIX_NV12;
+        const vp::AffineMap m = vp::affine_map(cs + 4 * (size_t)i);
+        vp::AffRec& r = recs[i];
+        r.plane[0] = row0_ptr[2 * f]; r.plane[1] = nv12 ? row0_ptr[2 * f + 1] : nullptr;
+        r.pitch[0] = im.pitch[0]; r.pitch[1] = nv12 ? im.pitch[1] : 0;
+        r.ax = m.ax; r.bx = m.bx; r.ay = m.ay; r.by = m.by;
+        r.w = im.w; r.y0 = bands[2 * f]; r.y1 = bands[2 * f + 1];   // (a frame without a band: y0 == y1, no read)
+        r.format = im.format; r.matrix = im.matrix; r.pad_ = 0;
+    }
 }
 
 int box_args(int n_frames, const int32_t* frame_hw, int hw_stride, int row_stride, int n, int pad, std::string* why) {
@@ -752,6 +810,97 @@ int vp_infer_boxes_images_stream(vp_handle c, const vp_image* images, int32_t n_
                       d_status, caller_stream);
 }
 
+// ---- the affine crop route (affinegeom.h): the frames entry on host centres and scales, the boxes entry on device boxes
+int vp_infer_images_affine(vp_handle c, const vp_image* images, int32_t n_images, int32_t on_device, const int32_t* frame_idx, const float* cs, int32_t n, float* out) {
+    if (!c) return VP_ERR_INVALID;
+    std::vector<int32_t> bands((size_t)(n_images > 0 ? n_images : 0) * 2);
+    std::string why;
+    if (affine_plan(images, n_images, frame_idx, cs, n, bands.data(), &why)) return fail(c, VP_ERR_INVALID, "vp_infer_images_affine: " + why);   // before any copy or launch
+    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, cs, out);
+    if (rc || n == 0) return rc;
+    std::vector<const uint8_t*> row0_ptr;
+    std::vector<vp::AffRec> recs;
+    if ((rc = stage_bands(c, images, n_images, on_device != 0, bands.data(), row0_ptr))) return rc;
+    affine_records(images, frame_idx, cs, n, bands.data(), row0_ptr, recs);
+    if (!c->arecs && (rc = dalloc(c, &c->arecs, (size_t)c->maxb))) return rc;
+    if (!c->cs_stage && (rc = dalloc(c, &c->cs_stage, (size_t)c->maxb * 4))) return rc;
+    return for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // vp_infer_images' chunks
+        HIPCHK(c, hipMemcpyAsync(c->arecs, recs.data() + off, (size_t)nb * sizeof(vp::AffRec), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->cs_stage, cs + 4 * (size_t)off, (size_t)nb * 16, hipMemcpyHostToDevice, c->stream));
+        LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5, vp::crop_affine_launch(c->arecs, (uint8_t*)c->in_stage, nb, c->stream));
+        if (const int rc = run_chunk(c, c->in_stage, VP_INPUT_U8_NHWC, nb, nullptr, c->kp, nullptr, c->cs_stage)) return rc;
+        return copy_out_sync(c, out, c->kp, (size_t)c->Kp * 3, off, nb);   // (also: the caller's cs and recs are read before the call returns)
+    });
+}
+
+int vp_infer_boxes_affine_stream(vp_handle c, const vp_image* images, int32_t n_images, const float* d_xyxy, int32_t row_stride, const int32_t* d_frame_idx, int32_t n,
+                                 float box_scale, float* d_out, float* d_cs, int32_t* d_status, void* caller_stream) {
+    if (!c) return VP_ERR_INVALID;
+    // every host argument is checked before anything is enqueued
+    if (n > 0 && (!images || !d_xyxy || !d_out)) return fail(c, VP_ERR_INVALID, "null frame table, box or output pointer");
+    if (!std::isfinite(box_scale) || !(box_scale > 0.f)) return fail(c, VP_ERR_INVALID, "vp_infer_boxes_affine_stream: box_scale must be finite and > 0");
+    std::vector<int32_t> hw((size_t)std::max(n > 0 ? n_images : 0, 0) * 2);
+    for (size_t f = 0; f < hw.size() / 2; ++f) { hw[2 * f] = images[f].h; hw[2 * f + 1] = images[f].w; }
+    std::string why;
+    if (box_args(n_images, hw.data(), 2, row_stride, n, 0, &why)) return fail(c, VP_ERR_INVALID, why);
+    for (int f = 0; f < n_images && n > 0; ++f)   // the layout of every frame of the table
+        if (image_check(images[f], f, &why)) return fail(c, VP_ERR_INVALID, why);
+    int rc = check_ready(c, VP_INPUT_U8_NHWC, n, d_xyxy, d_out, false);
+    if (rc || n == 0) return rc;
+    for (int f = 0; f < n_images; ++f)   // every frame of the table: which ones the boxes name is on the device
+        if ((rc = check_device_frame(c, images[f], f))) return rc;
+    if (!c->arecs && (rc = dalloc(c, &c->arecs, (size_t)c->maxb))) return rc;
+    if (!c->cs_stage && (rc = dalloc(c, &c->cs_stage, (size_t)c->maxb * 4))) return rc;
+    return caller_ordered(c, (hipStream_t)caller_stream, n, [&]() {
+        return for_chunks(n, chunk_cap(c), [&](int off, int nb) -> int {   // vp_infer_images_affine's chunks: the same crops per chunk, so the same bits
+            // geometry + crop run eagerly in front of the chunk's graph: the frame pointers change from call to call, the graph's buffers do not
+            for (int f0 = 0; f0 < n_images; f0 += vp::BOX_FRAMES_PER_LAUNCH) {
+                vp::BoxFrames bf;
+                std::memset(&bf, 0, sizeof(bf));
+                bf.f0 = f0; bf.count = std::min(n_images - f0, vp::BOX_FRAMES_PER_LAUNCH); bf.n_frames = n_images;
+                for (int j = 0; j < bf.count; ++j) {
+                    const vp_image& im = images[f0 + j];
+                    bf.fr[j] = vp::BoxFrame{{im.plane[0], im.plane[1]}, {im.pitch[0], im.pitch[1]}, im.h, im.w, im.format, im.matrix};
+                }
+                LAUNCH(c, VP_PROF_IM2COL, 0.0, 64.0 * nb,
+                       vp::box_cs_launch(bf, d_xyxy + (size_t)off * row_stride, row_stride, d_frame_idx ? d_frame_idx + off : nullptr, nb, box_scale, c->arecs, c->cs_stage,
+                                         d_cs ? d_cs + (size_t)off * 4 : nullptr, d_status ? d_status + off : nullptr, c->stream));
+            }
+            LAUNCH(c, VP_PROF_IM2COL, 0.0, (double)nb * 256 * 192 * 3 * 5, vp::crop_affine_launch(c->arecs, (uint8_t*)c->in_stage, nb, c->stream));
+            return run_chunk(c, c->in_stage, VP_INPUT_U8_NHWC, nb, nullptr, d_out + (size_t)off * c->Kp * 3, nullptr, c->cs_stage);
+        });
+    });
+}
+
+int vp_dbg_box_cs(const float* xyxy, int32_t row_stride, const int32_t* frame_idx, int32_t n_frames, int32_t n, float box_scale, float* cs, int32_t* status) {
+    std::string why;
+    if (n < 0) why = "negative box count";
+    else if (n > 0 && !xyxy) why = "null box table";
+    else if (row_stride < 4) why = "row_stride " + std::to_string(row_stride) + " < 4 (x1, y1, x2, y2 per row)";
+    else if (!std::isfinite(box_scale) || !(box_scale > 0.f)) why = "box_scale must be finite and > 0";
+    if (!why.empty()) { g_create_error = why; return VP_ERR_INVALID; }
+    for (int i = 0; i < n; ++i) {   // what box_cs_kernel computes for box i
+        const int32_t f = frame_idx ? frame_idx[i] : 0;
+        float q[4] = {0.f, 0.f, 0.f, 0.f};
+        int st = vp::BOX_BAD_FRAME;
+        if (f >= 0 && f < n_frames) {
+            const float* b = xyxy + (size_t)i * row_stride;
+            st = vp::box_cs(b[0], b[1], b[2], b[3], box_scale, q);
+            if (st != vp::BOX_OK) q[0] = q[1] = q[2] = q[3] = 0.f;
+        }
+        if (cs) std::memcpy(cs + 4 * (size_t)i, q, sizeof(q));
+        if (status) status[i] = st;
+    }
+    return VP_OK;
+}
+
+int vp_dbg_affine_plan(const vp_image* images, int32_t n_images, const int32_t* frame_idx, const float* cs, int32_t n, int32_t* bands) {
+    std::string why;
+    const int rc = affine_plan(images, n_images, frame_idx, cs, n, bands, &why);
+    if (rc) g_create_error = why;
+    return rc;
+}
+
 int vp_dbg_box_geometry(const float* xyxy, int32_t row_stride, const int32_t* frame_idx, const int32_t* frame_hw, int32_t n_frames, int32_t n, int32_t pad,
                         int32_t* out9, int32_t* status) {
     std::string why;
@@ -780,16 +929,16 @@ int vp_dbg_box_geometry(const float* xyxy, int32_t row_stride, const int32_t* fr
 // records != null: n_maps maps by records into [n, k] rows;  partner != null: the interleaved [n_maps = 2 n, k, 64, 48] of the flip-test mode;  neither: [n, k, 64, 48];
 // both (n_tables > 0): four-field records and a [n_tables, k] partner table, the per-expert flip-test mode
 static int decode_host(const char* who, int32_t device_id, const float* heatmaps, size_t n_maps, int32_t n, int32_t k, const int32_t* partner, int32_t shift,
-                       const int32_t* records, const int32_t* org_wh, float* out, int32_t n_tables = 0) {
+                       const int32_t* records, const int32_t* org_wh, float* out, int32_t n_tables = 0, const float* cs = nullptr) {
     if (!heatmaps || !out || n <= 0 || k <= 0) return fail(nullptr, VP_ERR_INVALID, "bad argument");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, VP_ERR_HIP, "no HIP device available (no CPU fallback)");
     if (device_id < 0 || device_id >= ndev) return fail(nullptr, VP_ERR_INVALID, "device_id out of range");
     vp_ctx* c = nullptr;   // errors below are reported through the create-error slot
     HIPCHK(c, hipSetDevice(device_id));
-    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the maps, the sizes, the partner table, the records (each where given), the output
-    const void* h[4] = {heatmaps, org_wh, partner, records};
-    const size_t bytes[5] = {n_maps * 3072 * 4, (size_t)n * 8, (size_t)k * 4 * (n_tables ? n_tables : 1), (size_t)n * (n_tables ? sizeof(vp::MixRecFlip) : sizeof(vp::MixRec)),
+    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the maps, the sizes (the affine route: cs [n, 4]), the partner table, the records (each where given), the output
+    const void* h[4] = {heatmaps, cs ? (const void*)cs : (const void*)org_wh, partner, records};
+    const size_t bytes[5] = {n_maps * 3072 * 4, (size_t)n * (cs ? 16 : 8), (size_t)k * 4 * (n_tables ? n_tables : 1), (size_t)n * (n_tables ? sizeof(vp::MixRecFlip) : sizeof(vp::MixRec)),
                              (size_t)n * k * 12};
     hipError_t e = hipMalloc(&d[4], bytes[4]);
     if (e == hipSuccess) e = hipMemset(d[4], 0xff, bytes[4]);
@@ -801,7 +950,9 @@ static int decode_host(const char* who, int32_t device_id, const float* heatmaps
     const float* d_hm = (const float*)d[0];
     const int32_t* d_wh = (const int32_t*)d[1];
     if (e == hipSuccess)
-        e = n_tables  ? vp::decode_flip_mix_launch(d_hm, (const vp::MixRecFlip*)d[3], (const int32_t*)d[2], shift ? 1 : 0, d_wh, (float*)d[4], n, k, nullptr)
+        e = cs        ? (partner ? vp::decode_affine_flip_launch(d_hm, (const int32_t*)d[2], shift ? 1 : 0, (const float*)d[1], (float*)d[4], n, k, nullptr)
+                                 : vp::decode_affine_launch(d_hm, (const float*)d[1], (float*)d[4], n, k, nullptr))
+            : n_tables ? vp::decode_flip_mix_launch(d_hm, (const vp::MixRecFlip*)d[3], (const int32_t*)d[2], shift ? 1 : 0, d_wh, (float*)d[4], n, k, nullptr)
             : records ? vp::decode_mix_launch(d_hm, (const vp::MixRec*)d[3], d_wh, (float*)d[4], n, k, nullptr)
             : partner   ? vp::decode_flip_launch(d_hm, (const int32_t*)d[2], shift ? 1 : 0, d_wh, (float*)d[4], n, k, nullptr)
                         : vp::decode_launch(d_hm, d_wh, (float*)d[4], n, k, nullptr);
@@ -815,6 +966,21 @@ static int decode_host(const char* who, int32_t device_id, const float* heatmaps
 
 int vp_decode_only(int32_t device_id, const float* heatmaps, int32_t n, int32_t k, const int32_t* org_wh, float* out) {
     return decode_host("vp_decode_only", device_id, heatmaps, (size_t)n * k, n, k, nullptr, 0, nullptr, org_wh, out);
+}
+
+int vp_dbg_decode_affine(int32_t device_id, const float* heatmaps, int32_t n, int32_t k, const float* cs, float* out) {
+    if (!cs) return fail(nullptr, VP_ERR_INVALID, "bad argument");
+    return decode_host("vp_dbg_decode_affine", device_id, heatmaps, (size_t)n * k, n, k, nullptr, 0, nullptr, nullptr, out, 0, cs);
+}
+
+// ... under the flip-test mode: the interleaved [2 n, k, 64, 48] batch
+int vp_dbg_decode_affine_flip(int32_t device_id, const float* heatmaps2, int32_t n, int32_t k, const int32_t* flip_pairs, int32_t n_pairs, int32_t shift_heatmap,
+                              const float* cs, float* out) {
+    if (k <= 0 || !cs) return fail(nullptr, VP_ERR_INVALID, "bad argument");
+    std::vector<int32_t> partner((size_t)k);
+    std::string why;
+    if (flip_partner_table(k, flip_pairs, n_pairs, partner.data(), &why)) return fail(nullptr, VP_ERR_INVALID, why);
+    return decode_host("vp_dbg_decode_affine_flip", device_id, heatmaps2, (size_t)n * k * 2, n, k, partner.data(), shift_heatmap, nullptr, nullptr, out, 0, cs);
 }
 
 int vp_dbg_decode_flip(int32_t device_id, const float* heatmaps2, int32_t n, int32_t k, const int32_t* flip_pairs, int32_t n_pairs, int32_t shift_heatmap,

@@ -249,12 +249,35 @@ struct BoxFrames {
 hipError_t box_geometry_launch(const BoxFrames& fr, const float* xyxy, int row_stride, const int32_t* frame_idx, int n, int pad, const uint8_t* zero_px,
                                CropRec* recs, int32_t* wh, int32_t* aux, int32_t* p9_out, int32_t* status_out, hipStream_t s, const int32_t* slot = nullptr);
 
+// ---- the training-protocol affine crop (affinegeom.h): the second crop kernel, writing the same RGB8 crop buffer
+// one crop: plane[p] = plane p of the frame at the first row the record may read (row y0 of plane 0, row y0 >> 1 of an NV12 frame's UV plane), in a staged row band
+// or in the caller's device frame; rows [y0, y1) x columns [0, w) are the frame pixels that exist for this crop (a device frame: [0, h)), every other tap is 0.
+// src(o) = o a + b per axis (affine_map).  A refused box is a record with y0 == y1: it reads nothing and gives a black crop
+struct AffRec {
+    const uint8_t* plane[2];
+    int64_t pitch[2];
+    double ax, bx, ay, by;
+    int32_t w, y0, y1, format, matrix, pad_;
+};
+// recs: device AffRec [n] -> crops u8 [n,256,192,3] RGB
+hipError_t crop_affine_launch(const AffRec* recs, uint8_t* out, int n, hipStream_t s);
+// boxes xyxy (row i at xyxy + i * row_stride) + frame index [n] (NULL: frame 0) -> crop records, cs [n, 4] = (cx, cy, S_w, S_h) (what the affine decode reads;
+// a box with a non-zero status: an all-zero row and a record that reads nothing); optional cs_out [n, 4] (the same rows) and status_out [n].  Frames by kernel
+// argument and one writer per box, as box_geometry_launch
+hipError_t box_cs_launch(const BoxFrames& fr, const float* xyxy, int row_stride, const int32_t* frame_idx, int n, float box_scale, AffRec* recs, float* cs,
+                         float* cs_out, int32_t* status_out, hipStream_t s);
+
 // --------------------------------------------------------------------- decode
 // heatmaps fp32 [N, K, 64, 48] -> out fp32 [N, K, 3] (y, x, conf); org_wh int32 [N,2] or null
 hipError_t decode_launch(const float* hm, const int32_t* org_wh, float* out, int N, int K, hipStream_t s);
 // flip-test mode: hm = the interleaved batch [2 N, K, 64, 48] (crop, mirror, crop, mirror, ...); decodes 0.5 (crop + flip_back(mirror)) without materialising it,
 // bit for bit flip_merge_launch + decode_launch
 hipError_t decode_flip_launch(const float* hm, const int32_t* partner, int shift, const int32_t* org_wh, float* out, int N, int K, hipStream_t s);
+
+// the affine route: cs float32 [N, 4] = (cx, cy, S_w, S_h) per crop instead of org_wh; out (y, x) in FRAME pixels with one rounding,
+// x = (float)(rx (S_w / 47) + cx - S_w 0.5) in fp64 with unfused steps, y with 63; a row whose S_w is not > 0 (a refused box) is all zero
+hipError_t decode_affine_launch(const float* hm, const float* cs, float* out, int N, int K, hipStream_t s);
+hipError_t decode_affine_flip_launch(const float* hm, const int32_t* partner, int shift, const float* cs, float* out, int N, int K, hipStream_t s);
 
 // ViTPose+ chunk with per-crop experts: the crop at position j of the chunk's expert order.  `first` = index of its first 64 x 48 map in the chunk's heatmap
 // buffer, K = its expert's joint count, dst = its row in the caller's order (output row, and row of org_wh)

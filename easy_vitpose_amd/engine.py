@@ -347,7 +347,14 @@ class VitPoseHip:
                                            params.ctypes.data, n, out.ctypes.data), self._h)
         return out
 
-    def infer_frames(self, frames, params: np.ndarray, datasets=None):
+    @staticmethod
+    def _crop_mode(crop) -> bool:
+        """True for crop='affine', False for crop='pad' (the default at every layer); anything else is refused"""
+        if crop not in ('pad', 'affine'):
+            raise ValueError(f"crop: 'pad' or 'affine' expected, got {crop!r}")
+        return crop == 'affine'
+
+    def infer_frames(self, frames, params: np.ndarray, datasets=None, crop: str = 'pad'):
         """The crops of several frames in one call (vp_infer_frames): params [n, 9] (cropprep.frames_crop_params) -> [n, K, 3] in
         padded-crop pixels.  `datasets` (a ViTPose+ handle: one name or expert index per crop, as in `infer_mixed`): a dataset per crop in the
         same call (vp_infer_frames_experts) -- returns ``(out, k)`` as `infer_mixed` does, ``out`` [n, Kmax, 3] with row i's first ``k[i]``
@@ -355,7 +362,20 @@ class VitPoseHip:
         or torch uint8 CUDA tensors [H, W, 3] on this handle's device (read in place, once torch's current stream on that
         device has been synchronised), or `Frame` objects (`Frame.rgb / bgr / nv12`: BGR, NV12 surfaces, pitched planes; vp_infer_images) -- formats may differ
         within a call, and the result has the bits of the call on `cropprep.to_rgb` of every frame.  A bare array or tensor is RGB; rows at a pitch (strides
-        (pitch, 3, 1)) pass in place.  A list that mixes host and device frames raises TypeError."""
+        (pitch, 3, 1)) pass in place.  A list that mixes host and device frames raises TypeError.
+        `crop='affine'` (vp_infer_images_affine): the training-protocol crop instead of the pad route.  `params` is then float [n, 5]
+        (frame, cx, cy, S_w, S_h) -- the frame index and a `cropprep.box_to_cs` row -- and the result is [n, K, 3] in FRAME pixels, the bits of `infer` on
+        `cropprep.affine_crops_host` followed by `cropprep.affine_back_map`.  Not together with `datasets`."""
+        affine = self._crop_mode(crop)
+        if affine and datasets is not None:
+            raise ValueError("infer_frames: crop='affine' does not run together with datasets= (the affine route runs the handle's active dataset)")
+        if affine:
+            p5 = np.asarray(params, dtype=np.float64).reshape(-1, 5)
+            fidx = p5[:, 0].astype(np.int32)
+            if not (p5[:, 0] == fidx).all():
+                raise ValueError("infer_frames: crop='affine' takes params [n, 5] = (frame, cx, cy, S_w, S_h) with a whole frame index")
+            cs = np.ascontiguousarray(np.asarray(params).reshape(-1, 5)[:, 1:], dtype=np.float32)
+            params = np.zeros((len(p5), 9), dtype=np.int32)
         params = np.ascontiguousarray(params, dtype=np.int32).reshape(-1, 9)
         n = params.shape[0]
         frames = [self._as_frame(f, i) for i, f in enumerate(frames)]
@@ -369,7 +389,9 @@ class VitPoseHip:
         if n and on_device:
             import torch
             torch.cuda.current_stream(torch.device('cuda', self.device_id)).synchronize()   # the frames are complete before the library reads them
-        if n:
+        if n and affine:
+            capi.check(self.lib.vp_infer_images_affine(self._h, table, len(frames), int(on_device), fidx.ctypes.data, cs.ctypes.data, n, out.ctypes.data), self._h)
+        elif n:
             capi.check(self.lib.vp_infer_images(self._h, table, len(frames), int(on_device), params.ctypes.data, n, None if ids is None else ids.ctypes.data,
                                                 out.ctypes.data), self._h)
         return out if ids is None else (out, self.dataset_k(ids))
@@ -412,7 +434,7 @@ class VitPoseHip:
         return table
 
     def infer_boxes(self, frames, boxes, frame_index=None, pad: int = 10, out=None, crop_params: bool = False, status: bool = False, datasets=None,
-                    nms: PoseNms | None = None, box_scores=None):
+                    nms: PoseNms | None = None, box_scores=None, crop: str = 'pad', box_scale: float = 1.25, cs: bool = False):
         """Detector boxes on device frames -> keypoints in FRAME pixels, all on the device (vp_infer_boxes_stream, contract in
         include/vitpose_hip.h).  `frames`: torch uint8 CUDA tensors [H, W, 3] on this handle's device (RGB; rows may be pitched: a view of a wider buffer),
         or `Frame` objects over device planes (`Frame.bgr`, `Frame.nv12`: vp_infer_boxes_images_stream), read in place; `boxes`: float32 CUDA
@@ -426,9 +448,25 @@ class VitPoseHip:
         crop params and status are the plain call's.
         `nms` (a PoseNms): person scores and per-frame OKS pose NMS run behind the boxes entry on the same stream (`pose_nms`); the call then returns
         (out, score, rank, count[, crop_params][, status]).  The box scores are `box_scores` (float32 CUDA [n]) or column 4 of `boxes`.  Not together with
-        `datasets`: poses of different joint layouts are not comparable."""
+        `datasets`: poses of different joint layouts are not comparable.
+        `crop='affine'` (vp_infer_boxes_affine_stream): the training-protocol crop -- the box extended to 3:4 with image content and scaled by `box_scale`
+        (the reference's 1.25), not clipped to the frame, `pad` unused.  Returns ``(out[, cs][, status])``: `cs=True` adds float32 [n, 4] (cx, cy, S_w, S_h)
+        per box (`cropprep.box_to_cs`; a zero row where the status is not 0).  The keypoints have the bits of `infer_frames(crop='affine')` on those rows.
+        Not together with `nms` (its area is the pad route's crop), `datasets` or `crop_params`."""
         import torch
         dev = torch.device('cuda', self.device_id)
+        affine = self._crop_mode(crop)
+        if affine:
+            if nms is not None:
+                raise ValueError("infer_boxes: nms= does not run together with crop='affine' (the NMS area is defined on the pad route's crop)")
+            if datasets is not None:
+                raise ValueError("infer_boxes: crop='affine' does not run together with datasets= (the affine route runs the handle's active dataset)")
+            if crop_params:
+                raise ValueError("infer_boxes: crop='affine' has no crop params: ask for cs=True")
+            if not (np.isfinite(box_scale) and box_scale > 0):
+                raise ValueError(f'infer_boxes: box_scale must be finite and > 0, got {box_scale!r}')
+        elif cs:
+            raise ValueError("infer_boxes: cs=True belongs to crop='affine' (the pad route returns crop_params)")
         if nms is not None:
             if datasets is not None:
                 raise ValueError('infer_boxes: nms= does not run together with datasets= (poses of different joint layouts are not comparable)')
@@ -463,7 +501,14 @@ class VitPoseHip:
         cp = torch.empty((n, 9), dtype=torch.int32, device=dev) if crop_params or nms is not None else None
         st = torch.empty((n,), dtype=torch.int32, device=dev) if status or nms is not None else None
         bsc = None if nms is None else (box_scores if box_scores is not None else boxes[:, 4])
-        cs = torch.cuda.current_stream(dev).cuda_stream
+        want_cs, cs = cs, torch.cuda.current_stream(dev).cuda_stream
+        if affine:
+            d_cs = torch.empty((n, 4), dtype=torch.float32, device=dev) if want_cs else None
+            capi.check(self.lib.vp_infer_boxes_affine_stream(self._h, table, len(frames), boxes.data_ptr(), row_stride, fip, n, float(box_scale), out.data_ptr(),
+                                                             None if d_cs is None else d_cs.data_ptr(), None if st is None else st.data_ptr(), cs), self._h)
+            if d_cs is None and st is None:
+                return out
+            return (out,) + tuple(t for t in (d_cs, st) if t is not None)
         capi.check(self.lib.vp_infer_boxes_images_stream(self._h, table, len(frames), boxes.data_ptr(), row_stride, fip, n, int(pad),
                                                          None if ids is None else ids.ctypes.data, out.data_ptr(), None if cp is None else cp.data_ptr(),
                                                          None if st is None else st.data_ptr(), cs), self._h)
@@ -609,6 +654,74 @@ def decode_flip_heatmaps(heatmaps2: np.ndarray, pairs, shift_heatmap: bool = Fal
     wh = None if org_wh is None else np.ascontiguousarray(org_wh, dtype=np.int32).reshape(n2 // 2, 2)
     capi.check(lib.vp_dbg_decode_flip(device_id, hm.ctypes.data, n2 // 2, k, pairs.ctypes.data if len(pairs) else None, len(pairs),
                                       int(bool(shift_heatmap)), None if wh is None else wh.ctypes.data, out.ctypes.data))
+    return out
+
+
+def box_cs_host(boxes, frame_index=None, n_frames: int = 1, box_scale: float = 1.25):
+    """What the box kernel of the affine boxes entry computes, on the host (vp_dbg_box_cs: csrc/affinegeom.h itself; no device needed): float32 boxes
+    [n, >= 4] -> (cs float32 [n, 4], status int32 [n])."""
+    lib = capi.load_library()
+    b = np.ascontiguousarray(boxes, dtype=np.float32)
+    assert b.ndim == 2 and b.shape[1] >= 4
+    fi = None if frame_index is None else np.ascontiguousarray(frame_index, dtype=np.int32)
+    cs = np.empty((len(b), 4), dtype=np.float32)
+    st = np.empty((len(b),), dtype=np.int32)
+    capi.check(lib.vp_dbg_box_cs(b.ctypes.data, b.shape[1], None if fi is None else fi.ctypes.data, int(n_frames), len(b), float(box_scale),
+                                 cs.ctypes.data, st.ctypes.data))
+    return cs, st
+
+
+def _host_image(frame: Frame):
+    if frame.on_device:
+        raise TypeError('a frame whose planes are on the host expected')
+    p0, p1 = frame.pointers()
+    return capi.vp_image((C.c_void_p * 2)(p0, p1), (C.c_int64 * 2)(*frame.pitch), frame.h, frame.w, PIX_FORMATS[frame.format], YUV_MATRIX_IDS[frame.matrix])
+
+
+def affine_plan_host(frames, frame_index, cs) -> np.ndarray:
+    """The plan of the host-frames affine route (vp_dbg_affine_plan; no device needed): int32 [n_frames, 2] = the frame rows [row0, row1) each
+    frame's crops tap, {0, 0} for a frame without any.  Raises VpError for what vp_infer_images_affine refuses."""
+    lib = capi.load_library()
+    frames = [VitPoseHip._as_frame(f, i) for i, f in enumerate(frames)]
+    table = (capi.vp_image * max(len(frames), 1))()
+    for i, f in enumerate(frames):
+        table[i] = _host_image(f)
+    cs = np.ascontiguousarray(cs, dtype=np.float32).reshape(-1, 4)
+    fi = None if frame_index is None else np.ascontiguousarray(frame_index, dtype=np.int32)
+    bands = np.zeros((len(frames), 2), dtype=np.int32)
+    capi.check(lib.vp_dbg_affine_plan(table, len(frames), None if fi is None else fi.ctypes.data, cs.ctypes.data, len(cs), bands.ctypes.data))
+    return bands
+
+
+def crop_affine_device(frame, cs, device_id: int = 0) -> np.ndarray:
+    """The device affine crop kernel alone on one host frame of any layout (vp_dbg_crop_affine): uint8 RGB [n, 256, 192, 3]."""
+    lib = capi.load_library()
+    frame = VitPoseHip._as_frame(frame, 0)
+    cs = np.ascontiguousarray(cs, dtype=np.float32).reshape(-1, 4)
+    out = np.empty((len(cs), IMG_H, IMG_W, 3), dtype=np.uint8)
+    im = _host_image(frame)
+    capi.check(lib.vp_dbg_crop_affine(device_id, C.byref(im), cs.ctypes.data, len(cs), out.ctypes.data))
+    return out
+
+
+def decode_affine_heatmaps(heatmaps: np.ndarray, cs, device_id: int = 0, flip_pairs=None, shift_heatmap: bool = False) -> np.ndarray:
+    """The affine decode alone (vp_dbg_decode_affine): host heatmaps [N, K, 64, 48] and cs [N, 4] -> [N, K, 3] (y, x, conf) in frame pixels.
+    `flip_pairs` given: the flip-test mode's interleaved [2 N, K, 64, 48] (vp_dbg_decode_affine_flip)."""
+    lib = capi.load_library()
+    hm = np.ascontiguousarray(heatmaps, dtype=np.float32)
+    n, k, h, w = hm.shape
+    assert (h, w) == (HM_H, HM_W)
+    if flip_pairs is not None:
+        assert n % 2 == 0
+        n //= 2
+    cs = np.ascontiguousarray(cs, dtype=np.float32).reshape(n, 4)
+    out = np.empty((n, k, 3), dtype=np.float32)
+    if flip_pairs is None:
+        capi.check(lib.vp_dbg_decode_affine(device_id, hm.ctypes.data, n, k, cs.ctypes.data, out.ctypes.data))
+    else:
+        pairs = _flip_pairs_array(flip_pairs)
+        capi.check(lib.vp_dbg_decode_affine_flip(device_id, hm.ctypes.data, n, k, pairs.ctypes.data if len(pairs) else None, len(pairs), int(bool(shift_heatmap)),
+                                                 cs.ctypes.data, out.ctypes.data))
     return out
 
 

@@ -25,7 +25,7 @@ from typing import Optional
 import numpy as np
 
 from .configs import IMG_H, IMG_W, infer_dataset_by_path, infer_variant_from_state_dict, model_shape, resolve_flip_pairs
-from .cropprep import frames_crop_params, resize_linear_u8
+from .cropprep import box_to_cs, frames_crop_params, resize_linear_u8
 from .engine import VitPoseHip, decode_heatmaps
 from .moe import DATASETS as MOE_DATASETS, is_vitpose_plus
 from .posenms import PoseNms, resolve_sigmas
@@ -74,7 +74,15 @@ class VitInference:
                  single_pose: Optional[bool] = False,
                  yolo_step: Optional[int] = 1,
                  *, dtype: str = 'fp16', max_batch: int = 64, tracker=None, flip_test=None, shift_heatmap: bool = False,
-                 pose_nms: Optional[PoseNms] = None):
+                 pose_nms: Optional[PoseNms] = None, crop: str = 'pad', box_scale: float = 1.25):
+        # crop='affine': the training-protocol crop (cropprep.box_to_cs, VitPoseHip.infer_frames(crop='affine')) instead of the pad route; refused before anything is loaded
+        if crop not in ('pad', 'affine'):
+            raise ValueError(f"crop: 'pad' or 'affine' expected, got {crop!r}")
+        if crop == 'affine' and pose_nms is not None:
+            raise ValueError("pose_nms= does not run together with crop='affine' (the NMS area is defined on the pad route's crop)")
+        if not (np.isfinite(box_scale) and box_scale > 0):
+            raise ValueError(f'box_scale must be finite and > 0, got {box_scale!r}')
+        self.crop, self.box_scale = crop, float(box_scale)
         state_dict = None
         dataset_given = dataset is not None
         if isinstance(model, (str, os.PathLike)):
@@ -252,6 +260,8 @@ class VitInference:
 
         # crop + zero-pad to 3:4 + resize + normalise all happen on device, each frame uploaded once
         frames = [np.ascontiguousarray(img) for img in imgs]
+        if self.crop == 'affine':
+            return self._affine_frames(imgs, frames, dets)
         p9 = frames_crop_params([d[0] for d in dets], [f.shape for f in frames], pad_bbox)
         kps = self._vit_pose.infer_frames(frames, p9)
 
@@ -286,6 +296,24 @@ class VitInference:
             bboxes, ids, scores = dets[-1]
             self._img = imgs[-1]
             self._tracker_res = (bboxes, ids, scores)
+            self._keypoints, self._scores_bbox = results[-1]
+        return [r[0] for r in results]
+
+    def _affine_frames(self, imgs, frames, dets):
+        """the pose call of `inference_frames` under crop='affine': the tracker's boxes go through the affine route and the keypoints arrive in frame
+        pixels, so no offset is added; the stored boxes stay the detector's"""
+        fidx = np.concatenate([np.full(len(d[0]), f, dtype=np.float64) for f, d in enumerate(dets)] + [np.zeros(0)])
+        boxes = np.concatenate([d[0].reshape(-1, 4) for d in dets] + [np.zeros((0, 4), dtype=int)]).astype(np.float32)
+        cs = box_to_cs(boxes, self.box_scale) if len(boxes) else np.zeros((0, 4), dtype=np.float32)
+        kps = self._vit_pose.infer_frames(frames, np.concatenate([fidx[:, None], cs.astype(np.float64)], axis=1), crop='affine')
+        results, start = [], 0
+        for bboxes, ids, scores in dets:
+            kps_f = kps[start:start + len(bboxes)]
+            start += len(bboxes)
+            results.append(({id_: kps_f[i] for i, id_ in enumerate(ids)}, {id_: score for id_, score in zip(ids, scores)}))
+        if self.save_state and len(imgs):
+            self._img = imgs[-1]
+            self._tracker_res = dets[-1]
             self._keypoints, self._scores_bbox = results[-1]
         return [r[0] for r in results]
 

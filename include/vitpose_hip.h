@@ -405,6 +405,45 @@ VP_API int vp_dbg_image_plan(const vp_image* images, int32_t n_images, const int
 /* the device crop / zero-pad / resize kernel alone on ONE image whose planes are on the host (vp_dbg_crop_prep over vp_image): uint8 RGB crops [n, 256, 192, 3] */
 VP_API int vp_dbg_crop_prep_image(int32_t device_id, const vp_image* image, const int32_t* crop_params, int32_t n, uint8_t* out);
 
+/* The training-protocol crop: TopDownAffine(use_udp=True) on the box's own centre and scale, the crop ViTPose checkpoints were trained and evaluated on
+ * (the reference's datasets/COCO.py _xywh2cs, post_transforms.py get_warp_matrix, and transform_preds(center, scale, use_udp=True) on the way back), as a second
+ * crop route beside the pad route above; the pad route stays the default everywhere.  csrc/affinegeom.h states the arithmetic once:
+ *   box -> (cx, cy, S_w, S_h): the box centre, the box EXTENDED to 3:4 with image content (not padded with black) and scaled by box_scale (the reference: 1.25),
+ *     float32 at the reference's widths; the box is not clipped to the frame, pixels outside it read as 0; a side above 2^24 is clamped to 2^24.
+ *   crop pixel (ox, oy) of the 192 x 256 crop samples the frame at  x = ox (S_w / 191) + (cx - S_w / 2),  y = oy (S_h / 255) + (cy - S_h / 2)  (fp64), bilinear
+ *     in fixed point: 1/32-pixel positions Xq = floor(32 x + 0.5), 15-bit weights, (sum + 16384) >> 15 on source pixels converted to RGB8 as the pad route converts
+ *     them.  Modelled on OpenCV's 8-bit warpAffine(INTER_LINEAR, BORDER_CONSTANT 0); parity against that binary is unpinned and not claimed.
+ *   keypoints come back in FRAME pixels with one rounding: x = (float)(rx (S_w / 47) + cx - S_w / 2), y with 63 and S_h; no offsets follow.
+ * vp_infer_images_affine: the frames entry.  frame_idx int32 [n] (NULL: frame 0) and cs float32 [n, 4] = (cx, cy, S_w, S_h) on the host (easy_vitpose_amd/cropprep.py
+ *   box_to_cs), out [n, K, 3] (y, x, conf) in frame pixels.  Host frames are uploaded once: the row band their crops sample, computed from the map and clipped to
+ *   the frame.  The chunks, the host waits and the frame refusals are vp_infer_images'; VP_ERR_INVALID too for a centre that is not finite or a scale that is not
+ *   finite, not positive or above 2^24 (vp_dbg_affine_plan).
+ * vp_infer_boxes_affine_stream: the boxes entry, under the ordering rules of vp_infer_boxes_images_stream word for word -- no synchronisation and no host copy,
+ *   batches of up to 16 crops on the caller's stream.  d_cs float32 [n, 4] (may be NULL) receives every box's centre and scale, d_status (may be NULL) the status
+ *   codes of vp_infer_boxes_stream (3: w <= 0 or h <= 0 of the box itself).  A row with a non-zero status reads no frame and gets zero keypoints and a zero d_cs row.
+ *   VP_ERR_INVALID, before anything is enqueued, for everything vp_infer_boxes_images_stream refuses and for a box_scale that is not finite or <= 0.
+ * Both run under the handle's flip-test mode, and a ViTPose+ handle runs its active expert.  Not part of this route: per-crop experts, pose NMS on its output (the
+ * NMS area is the pad route's cw ch), the group, the submit / wait slots, rotation, and the non-UDP get_affine_transform.
+ * Library builds that carry the route define VP_HAS_AFFINE_CROP. */
+#define VP_HAS_AFFINE_CROP 1
+VP_API int vp_infer_images_affine(vp_handle h, const vp_image* images, int32_t n_images, int32_t images_on_device, const int32_t* frame_idx, const float* cs,
+                                  int32_t n, float* out);
+VP_API int vp_infer_boxes_affine_stream(vp_handle h, const vp_image* images, int32_t n_images, const float* d_xyxy, int32_t row_stride,
+                                        const int32_t* d_frame_idx, int32_t n, float box_scale, float* d_out, float* d_cs, int32_t* d_status,
+                                        void* caller_stream);
+/* HOST ONLY, no device needed.  vp_dbg_box_cs: what the box kernel of vp_infer_boxes_affine_stream computes, cs [n, 4] and status [n] (either may be NULL; a frame
+ * index outside [0, n_frames) is status 1).  vp_dbg_affine_plan: the function vp_infer_images_affine runs first (bands [n_images, 2] in frame rows, may be NULL);
+ * VP_ERR_INVALID with the crop named in vp_last_error(NULL). */
+VP_API int vp_dbg_box_cs(const float* xyxy, int32_t row_stride, const int32_t* frame_idx, int32_t n_frames, int32_t n, float box_scale, float* cs, int32_t* status);
+VP_API int vp_dbg_affine_plan(const vp_image* images, int32_t n_images, const int32_t* frame_idx, const float* cs, int32_t n, int32_t* bands);
+/* One kernel on host data.  vp_dbg_crop_affine: the affine crop kernel alone on ONE image whose planes are on the host, behind the staging of vp_infer_images_affine:
+ * uint8 RGB crops [n, 256, 192, 3].  vp_dbg_decode_affine: the affine decode on heatmaps [n, k, 64, 48] and cs [n, 4] -> [n, k, 3] in frame pixels;
+ * vp_dbg_decode_affine_flip: on the flip-test mode's interleaved [2 n, k, 64, 48] (vp_dbg_decode_flip's arguments). */
+VP_API int vp_dbg_crop_affine(int32_t device_id, const vp_image* image, const float* cs, int32_t n, uint8_t* out);
+VP_API int vp_dbg_decode_affine(int32_t device_id, const float* heatmaps, int32_t n, int32_t k, const float* cs, float* out);
+VP_API int vp_dbg_decode_affine_flip(int32_t device_id, const float* heatmaps2, int32_t n, int32_t k, const int32_t* flip_pairs, int32_t n_pairs,
+                                     int32_t shift_heatmap, const float* cs, float* out);
+
 /* Person scores and OKS pose NMS on the device, the stage behind the boxes entries (the reference's vit_utils/post_processing/nms.py oks_iou / oks_nms /
  * soft_oks_nms with data_cfg's oks_thr, vis_thr, soft_nms; csrc/posenms.h states the arithmetic once for the kernel and the host taps).
  * A row is one person: d_kpts float32 [n, k, 3] (y, x, conf) in frame pixels (the d_out of a boxes entry), a box score at d_box_score + i * score_stride

@@ -13,6 +13,12 @@ Per cell: ms = host clock around one call followed by a device synchronisation (
 call itself before that synchronisation (all of it for (a)).  Both routes' keypoints are checked to be bit-identical first.
 
     python tools/boxes_bench.py [--persons 1,4,16] [--frames 1,8,32] [--reps 15] [--max-batch 256] [--out FILE]
+
+--crop affine: the pad route of infer_boxes against infer_boxes(crop='affine') (vp_infer_boxes_affine_stream) instead, INTERLEAVED -- rounds of one pad call and
+one affine call, each followed by a device synchronisation -- so that both see the same clocks.  Per cell: median and the 10th .. 90th percentile of each route's
+calls, and the im2col family of the handle's profile (box kernel + crop kernel + patch gather, the only launches that differ) from one profiled call per route.
+
+    python tools/boxes_bench.py --crop affine --persons 1,8,64,256 --frames 1 --reps 40 --out profiles/affine_crop.txt
 """
 from __future__ import annotations
 
@@ -42,6 +48,7 @@ def main():
     ap.add_argument('--height', type=int, default=1080)
     ap.add_argument('--width', type=int, default=1920)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--crop', default='pad', choices=['pad', 'affine'], help="affine: the pad route against crop='affine', interleaved")
     args = ap.parse_args()
 
     import torch
@@ -80,6 +87,57 @@ def main():
             host.append(t1 - t0)
             tot.append(t2 - t0)
         return float(np.median(tot)) * 1e3, float(np.median(host)) * 1e3
+
+    def affine_cells():
+        """the pad route and the affine route of infer_boxes, interleaved"""
+        lines = [f'# boxes_bench --crop affine: ViTPose-{args.variant.upper()} coco {args.dtype}, {W}x{H} device frames, max_batch {args.max_batch}; rounds of one pad call and '
+                 f'one affine call, each followed by a device synchronisation (host clock), {args.reps} rounds after {args.warmup} warm-up rounds per cell',
+                 '# ms = median [10th .. 90th percentile] of call + sync; im2col = the im2col family of one profiled call (box kernel + crop kernel + patch gather); '
+                 'x = affine median / pad median',
+                 f'{"P":>3} {"F":>3} {"crops":>5} | {"pad ms":>8} {"p10":>8} {"p90":>8} {"im2col":>7} | {"affine ms":>9} {"p10":>8} {"p90":>8} {"im2col":>7} | {"x":>6}']
+        print('\n'.join(lines), flush=True)
+        for P in Ps:
+            boxes = [person_boxes(np.random.default_rng(1000 * P + i), P, H, W) for i in range(nF)]
+            for F in Fs:
+                b6 = np.zeros((P * F, 6), np.float32)
+                b6[:, :5] = np.concatenate(boxes[:F])
+                d_boxes = torch.from_numpy(b6).cuda()
+                d_fidx = torch.from_numpy(np.repeat(np.arange(F, dtype=np.int32), P)).cuda()
+                outs = {c: torch.empty((P * F, eng.K, 3), device='cuda') for c in ('pad', 'affine')}
+                frames = dev[:F]
+                calls = {c: (lambda c=c: eng.infer_boxes(frames, d_boxes, d_fidx, out=outs[c], crop=c)) for c in ('pad', 'affine')}
+                ms = {'pad': [], 'affine': []}
+                for r in range(args.warmup + args.reps):
+                    for c in ('pad', 'affine'):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        calls[c]()
+                        torch.cuda.synchronize()
+                        if r >= args.warmup:
+                            ms[c].append((time.perf_counter() - t0) * 1e3)
+                fam = {}
+                for c in ('pad', 'affine'):   # one profiled call per route, outside the timed rounds (profiling serialises the launches)
+                    eng.set_profiling(['im2col'])
+                    eng.reset_profile()
+                    calls[c]()
+                    torch.cuda.synchronize()
+                    fam[c] = eng.profile()['im2col']['ms']
+                    eng.set_profiling(False)
+                q = {c: np.percentile(ms[c], [50, 10, 90]) for c in ms}
+                row = (f'{P:>3} {F:>3} {P * F:>5} | {q["pad"][0]:>8.3f} {q["pad"][1]:>8.3f} {q["pad"][2]:>8.3f} {fam["pad"]:>7.3f} | '
+                       f'{q["affine"][0]:>9.3f} {q["affine"][1]:>8.3f} {q["affine"][2]:>8.3f} {fam["affine"]:>7.3f} | {q["affine"][0] / q["pad"][0]:>6.3f}')
+                print(row, flush=True)
+                lines.append(row)
+        return lines
+
+    if args.crop == 'affine':
+        lines = affine_cells()
+        eng.close()
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'w') as fh:
+                fh.write('\n'.join(lines) + '\n')
+        return
 
     lines = [f'# boxes_bench: ViTPose-{args.variant.upper()} coco {args.dtype}, {W}x{H} device frames, max_batch {args.max_batch}, median of '
              f'{args.reps} calls, each followed by a device synchronisation (host clock), {args.warmup} warm-up calls per cell and route',

@@ -79,13 +79,24 @@ class Asm:
         body, _, meta = text.partition('\t.amdgpu_metadata\n')
         parts, cur = [[] for _ in range(len(syms) + 1)], -1
         tag = re.compile(r'@K(\d+)@')
+        closing = False   # behind the last kernel: the register maximums and the constant tables of ALL kernels, which close the unit
         for ln in body.split('\n'):
-            m = tag.search(ln)
+            closing = closing or '.AMDGPU.gpr_maximums' in ln
+            m = None if closing else tag.search(ln)
             if m and int(m.group(1)) > cur:
                 cur = int(m.group(1))
-            parts[cur + 1].append(ln)
+            parts[0 if closing else cur + 1].append(ln)
+        # ... and neither do the lines behind a kernel's last own line (section switches, padding): without this the unit's tail counts as part of its last
+        # kernel, and a kernel added behind it would show as a difference of that one
+        tail = []
+        for k in range(1, len(parts)):
+            last = max((i for i, ln in enumerate(parts[k]) if tag.search(ln)), default=-1)
+            tail += parts[k][last + 1:]
+            del parts[k][last + 1:]
+        parts[0] += tail
         # metadata: one YAML list item per kernel
-        items = re.split(r'\n(?=  - )', meta)
+        meta, sep, closing_meta = meta.partition('\namdhsa.target:')   # what follows the last kernel's item is no part of it
+        items = re.split(r'\n(?=  - )', meta) + ([sep + closing_meta] if sep else [])
         stats = [dict() for _ in syms]
         rest = ['\n'.join(parts[0])]
         for it in items:
