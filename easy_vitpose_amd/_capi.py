@@ -41,7 +41,8 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_pose_nms_stream', 'vp_pose_nms', 'vp_dbg_pose_nms_host', 'vp_dbg_pose_oks',
            'vp_dbg_ln_finalize', 'vp_dbg_gemm_case_lnpart', 'vp_dbg_qkvattn_ln', 'vp_dbg_ln_quant',
            'vp_infer_images_affine', 'vp_infer_boxes_affine_stream', 'vp_dbg_box_cs', 'vp_dbg_affine_plan', 'vp_dbg_crop_affine', 'vp_dbg_decode_affine',
-           'vp_dbg_decode_affine_flip']
+           'vp_dbg_decode_affine_flip',
+           'vp_draw_poses_stream', 'vp_draw_poses', 'vp_dbg_draw_host']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -76,6 +77,11 @@ class vp_image(C.Structure):
 class vp_pose_nms_cfg(C.Structure):
     _fields_ = [('oks_thr', C.c_float), ('vis_thr', C.c_float), ('use_vis_thr', C.c_int32), ('soft', C.c_int32), ('max_dets', C.c_int32),
                 ('n_sigmas', C.c_int32), ('sigmas', C.c_void_p)]
+
+
+class vp_draw_cfg(C.Structure):
+    _fields_ = [('conf_thr', C.c_float), ('radius', C.c_int32), ('thickness', C.c_int32), ('n_limbs', C.c_int32), ('limbs', C.c_void_p),
+                ('n_point_colors', C.c_int32), ('point_colors', C.c_void_p), ('n_limb_colors', C.c_int32), ('limb_colors', C.c_void_p)]
 
 
 class vp_profile(C.Structure):
@@ -219,6 +225,11 @@ def load_library():
     lib.vp_dbg_crop_affine.argtypes = [C.c_int32, C.POINTER(vp_image), C.c_void_p, C.c_int32, C.c_void_p]
     lib.vp_dbg_decode_affine.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.vp_dbg_decode_affine_flip.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    draw_host = [C.POINTER(vp_image), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                 C.POINTER(vp_draw_cfg)]
+    lib.vp_draw_poses_stream.argtypes = [H] + draw_host + [C.c_void_p]
+    lib.vp_draw_poses.argtypes = [H] + draw_host
+    lib.vp_dbg_draw_host.argtypes = draw_host
     for name in SYMBOLS:
         if name not in ('vp_stream', 'vp_last_error', 'vp_host_alloc', 'vp_host_free', 'vp_group_member', 'vp_group_last_error'):
             getattr(lib, name).restype = C.c_int

@@ -9,7 +9,11 @@ pose path, track across frames (``is_video``), report FPS and write the ``--save
     python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --flip-test        # flip-test (COCO-17 pairs; else --flip-pairs FILE.json)
     python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --pose-nms 0.9 --soft-nms   # person scores + OKS pose NMS per frame
 
-Not rebuilt (outside the hot path): drawing / preview windows (``--show``, ``--save-img``: OpenCV) and video
+    python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --output-path out --save-img        # the frames with the skeletons drawn on them, as PNG
+
+``--save-img`` writes ``<stem>_<frame>.png`` per frame (``VitInference.draw``: skeletons drawn on the device, csrc/drawgeom.h; no text labels) into the
+``--save-json`` directory; a dataset other than COCO-17 needs ``--skeleton FILE.json``.
+Not rebuilt (outside the hot path): preview windows (``--show``: OpenCV) and video
 decoding -- a video is accepted as a ``.npy`` stack ``[frames, H, W, 3]`` uint8 RGB, or as a directory of image files.
 ``--boxes`` (JSON: one ``[[x1, y1, x2, y2, conf], ...]`` list per frame, or a single list used for every frame) replaces the
 detector when ultralytics is not installed (there is no network in the build image to fetch it or its weights).
@@ -82,7 +86,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--single-pose', action='store_true')
     ap.add_argument('--save-json', action='store_true')
     ap.add_argument('--show', action='store_true')
-    ap.add_argument('--save-img', action='store_true')
+    ap.add_argument('--save-img', action='store_true', help='write every frame with its skeletons drawn on it as <stem>_<frame>.png into the output directory')
+    ap.add_argument('--skeleton', default=None, metavar='FILE.json', help='--save-img: the limb table [[a, b], ...] of the dataset (built in for COCO-17 only)')
     ap.add_argument('--max-batch', type=int, default=64)
     ap.add_argument('--dtype', default='fp16', choices=['fp16', 'bf16'])
     ap.add_argument('--frame-batch', type=int, default=1, help='frames per pose call: the crops of N frames run as one batch (VitInference.inference_frames)')
@@ -104,8 +109,9 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
-    assert not (args.show or args.save_img), 'drawing / preview (OpenCV) is outside the HIP hot path: use --save-json'
-    assert not args.save_json or args.output_path, 'Specify an output path if using save-img or save-json flags'
+    assert not args.show, 'preview windows (OpenCV) are outside the HIP hot path: use --save-img or --save-json'
+    assert not (args.save_json or args.save_img) or args.output_path, 'Specify an output path if using save-img or save-json flags'
+    assert args.skeleton is None or args.save_img, '--skeleton belongs to --save-img'
     assert (args.model is None) != (args.synthetic is None), 'give exactly one of --model / --synthetic'
     assert args.frame_batch >= 1, '--frame-batch must be at least 1'
 
@@ -127,6 +133,10 @@ def main(argv=None) -> int:
             return np.asarray(b, dtype=np.float64).reshape(-1, 5)
     assert detector is not None, 'give --yolo (ultralytics weights) or --boxes'
 
+    skeleton = None
+    if args.skeleton is not None:
+        from easy_vitpose_amd.draw import load_skeleton
+        skeleton = load_skeleton(args.skeleton)
     state_dict = None
     if args.synthetic:
         from easy_vitpose_amd.synth import synthetic_state_dict
@@ -135,25 +145,31 @@ def main(argv=None) -> int:
                          args.det_class, dataset, args.yolo_size, is_video=is_video, single_pose=args.single_pose,
                          yolo_step=args.yolo_step, dtype=args.dtype, max_batch=args.max_batch,
                          flip_test=flip_test_argument(args), shift_heatmap=args.shift_heatmap, pose_nms=pose_nms_argument(args),
-                         crop=args.crop, box_scale=args.box_scale)
+                         crop=args.crop, box_scale=args.box_scale, skeleton=skeleton)
     print(f'>>> Model loaded: {args.model or "synthetic ViTPose-" + args.synthetic.upper()}')
     print(f'>>> Running inference on {args.input}')
+    base = os.path.basename(args.input.rstrip('/'))
+    stem = base[:base.rfind('.')] if '.' in base else base
+    out_dir = os.path.join(args.output_path, base)
+    if args.save_img:
+        assert args.frame_batch == 1, '--save-img draws the state of the last frame of a pose call: use --frame-batch 1'
+        from PIL import Image
+        os.makedirs(out_dir, exist_ok=True)
     keypoints, dts = [], []
     for s in range(0, len(frames), args.frame_batch):
         batch = frames[s:s + args.frame_batch]
         t0 = time.time()
         keypoints.extend(model.inference_frames(batch))
         dts.extend([(time.time() - t0) / len(batch)] * len(batch))   # per frame: the batch's time over its frame count
+        if args.save_img:   # outside the timed span, as the reference's drawing is
+            Image.fromarray(model.draw(confidence_threshold=args.conf_threshold)).save(os.path.join(out_dir, f'{stem}_{s}.png'))
     if is_video:
         tot = sum(len(k) for k in keypoints)
         print(f'>>> Mean inference FPS: {1 / np.mean(dts):.2f}')
         print(f'>>> Total poses predicted: {tot} mean per frame: {tot / len(frames):.2f}')
         print(f'>>> Mean FPS per pose: {tot / max(sum(dts), 1e-9):.2f}')
     if args.save_json:
-        out_dir = os.path.join(args.output_path, os.path.basename(args.input.rstrip('/')))
         os.makedirs(out_dir, exist_ok=True)
-        base = os.path.basename(args.input.rstrip('/'))
-        stem = base[:base.rfind('.')] if '.' in base else base
         path = os.path.join(out_dir, stem + '_result.json')
         print('>>> Saving output json')
         save_json(path, keypoints, COCO17_JOINTS if model._vit_pose.K == 17 and model.dataset == 'coco' else None)

@@ -17,6 +17,9 @@ from .configs import HM_H, HM_W, IMG_H, IMG_W, ModelShape
 from .cropprep import PIX_FORMATS, YUV_MATRIX_IDS, Frame
 from .posenms import PoseNms, resolve_sigmas
 from .posenms import c_config as nms_c_config
+from .draw import DrawStyle, check_records, check_rows, resolve_skeleton
+from .draw import c_config as draw_c_config
+from .draw import host_frame as host_draw_frame
 
 
 def _as_f32_numpy(v) -> np.ndarray:
@@ -572,6 +575,59 @@ class VitPoseHip:
         capi.check(self.lib.vp_pose_nms(self._h, kp.ctypes.data, n, K, bs.ctypes.data, 1, p9.ctypes.data, None if st is None else st.ctypes.data,
                                         int(n_frames), C.byref(c), score.ctypes.data, rank.ctypes.data, count.ctypes.data), self._h)
         return score, rank, count
+
+    # ------------------------------------------------------------ skeleton overlay
+    def _draw_skeleton(self, style: DrawStyle, K: int) -> np.ndarray:
+        """the limb table of a call.  The handle of a plain checkpoint does not know its dataset: its 17 joints are taken as COCO's when `style.skeleton` is None
+        (VitInference, which knows the dataset, resolves it first)."""
+        if not isinstance(style, DrawStyle):
+            raise TypeError(f'a DrawStyle expected, got {type(style).__name__}')
+        return resolve_skeleton(getattr(self, 'dataset', 'coco') if self._moe else 'coco', K, style.skeleton)
+
+    def draw_poses(self, frames, keypoints, frame_index, style: DrawStyle = DrawStyle(), rank=None, ids=None, boxes=None):
+        """Skeletons drawn onto device frames IN PLACE (vp_draw_poses_stream, contract in include/vitpose_hip.h), stream-ordered on torch's current stream without a
+        host synchronisation: correct directly behind `infer_boxes` and `pose_nms`.  `frames`: what `infer_boxes` takes (uint8 CUDA tensors [H, W, 3] = RGB, or
+        `Frame.rgb / bgr / nv12` over device planes, up to 8192 x 8192); `keypoints`: float32 CUDA [n, K, 3] in frame pixels; `frame_index`: int32 CUDA [n], or
+        a column view such as `crop_params[:, 0]` (any positive element stride); `rank`: int32 CUDA [n] or None, rows with rank < 0 are not drawn; `ids`: int32
+        CUDA [n] or None (the row index), the colour of a person's limbs; `boxes`: float32 CUDA [n, >= 4] with unit column stride or None, outlines drawn under the
+        skeletons.  Returns the frames as `Frame` objects."""
+        import torch
+        dev = torch.device('cuda', self.device_id)
+
+        def want(t, name, dtype, shape_ok, what):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype):
+                raise TypeError(f'{name}: a {dtype} torch CUDA tensor expected')
+            if t.device != dev or not shape_ok(t):
+                raise ValueError(f'{name}: {what} on {dev} expected, got {tuple(t.shape)} on {t.device}')
+        want(keypoints, 'keypoints', torch.float32, lambda t: t.ndim == 3 and t.shape[2] == 3 and t.is_contiguous(), 'contiguous [n, K, 3]')
+        n, K = keypoints.shape[0], keypoints.shape[1]
+        want(frame_index, 'frame_index', torch.int32, lambda t: tuple(t.shape) == (n,) and (n < 2 or t.stride(0) >= 1), f'[{n}] with a positive stride')
+        for t, name in ((rank, 'rank'), (ids, 'ids')):
+            if t is not None:
+                want(t, name, torch.int32, lambda t: tuple(t.shape) == (n,) and t.is_contiguous(), f'contiguous [{n}]')
+        if boxes is not None:
+            want(boxes, 'boxes', torch.float32, lambda t: t.ndim == 2 and t.shape[0] == n and t.shape[1] >= 4 and (n == 0 or t.stride(1) == 1) and (n < 2 or t.stride(0) >= 1),
+                 f'[{n}, >= 4] with unit column stride')
+        c, keep = draw_c_config(style, self._draw_skeleton(style, K))
+        check_records(n, K, keep[0].shape[0], boxes is not None)
+        frames = [self._as_frame(f, i) for i, f in enumerate(frames)]
+        table = self._image_table(frames, device_only=True)
+        cs = torch.cuda.current_stream(dev).cuda_stream
+        capi.check(self.lib.vp_draw_poses_stream(self._h, table, len(frames), keypoints.data_ptr(), n, K, frame_index.data_ptr(), frame_index.stride(0) if n > 1 else 1,
+                                                 None if rank is None else rank.data_ptr(), None if ids is None else ids.data_ptr(),
+                                                 None if boxes is None else boxes.data_ptr(), 4 if boxes is None or n < 2 else boxes.stride(0), C.byref(c), cs), self._h)
+        return frames
+
+    def draw_poses_host(self, frames, keypoints, frame_index, style: DrawStyle = DrawStyle(), rank=None, ids=None, boxes=None):
+        """`draw_poses` on numpy arrays and host frames, in place (vp_draw_poses: upload, the same kernels, download, synchronous).  Returns the frames as `Frame`s."""
+        frames = [host_draw_frame(f, i) for i, f in enumerate(frames)]
+        kp, fi, rk, pid, bx = check_rows(keypoints, frame_index, rank, ids, boxes)
+        c, keep = draw_c_config(style, self._draw_skeleton(style, kp.shape[1]))
+        check_records(kp.shape[0], kp.shape[1], keep[0].shape[0], bx is not None)
+        capi.check(self.lib.vp_draw_poses(self._h, self._image_table(frames), len(frames), kp.ctypes.data, kp.shape[0], kp.shape[1], fi.ctypes.data, 1,
+                                          None if rk is None else rk.ctypes.data, None if pid is None else pid.ctypes.data,
+                                          None if bx is None else bx.ctypes.data, 4, C.byref(c)), self._h)
+        return frames
 
     def heatmaps(self, crops: np.ndarray) -> np.ndarray:
         crops = np.ascontiguousarray(crops)

@@ -490,6 +490,51 @@ VP_API int vp_dbg_pose_nms_host(const float* kpts, int32_t n, int32_t k, const f
  * the L lanes a frame of n members gets, added in joint order -- so n chooses the L under test (64 up to 4 rows, 16 at 16, 2 at 128, 1 beyond). */
 VP_API int vp_dbg_pose_oks(int32_t device_id, const float* kpts, int32_t n, int32_t k, const int32_t* crop_params, const vp_pose_nms_cfg* cfg, float* oks);
 
+/* The skeleton overlay on device frames, the stage behind a boxes entry and vp_pose_nms_stream (modelled on the reference's draw_points_and_skeleton,
+ * vit_utils/visualization.py:360-481: opaque colours, no anti-aliasing; csrc/drawgeom.h states the arithmetic once for the kernels and the host tap).  The
+ * rasterisation is this library's own integer one: parity against OpenCV's circle / line / rectangle is unpinned and not claimed.
+ * A row is one person: d_kpts float32 [n, k, 3] (y, x, conf) in frame pixels, a frame index at d_frame_idx + i * frame_stride (column 0 of a [n, 9] crop-params
+ * tensor passes in place with stride 9; a row whose index is outside [0, n_images) is not drawn), d_rank (may be NULL) int32 [n]: a row with rank < 0 is not drawn
+ * (the NMS output passes as it is), d_ids (may be NULL: the row's index) int32 [n]: the reference's person_index, d_boxes (may be NULL: no outlines) float32
+ * (x1, y1, x2, y2) at d_boxes + i * box_stride.
+ *   A float v is usable iff -16384 < v < 16384 (never for NaN / inf); its pixel is (int)v.  A joint is visible iff conf > conf_thr (float32) and x, y are usable.
+ *   joint: the disk |p - c|^2 <= r^2.  limb (a, b), both joints visible, thickness t: with d = b - a, q = p - a the pixels with 0 <= q.d <= |d|^2 and
+ *   (q x d)^2 <= floor(t^2 |d|^2 / 4), plus the caps 4 |p - a|^2 <= t^2 and 4 |p - b|^2 <= t^2.  box, four usable values: the outline of t pixels per side, the
+ *   outermost t / 2 of them outside the box.  All in int64, exact for frames of up to 8192 x 8192.
+ *   Order: rows ascending; within a row box, limbs in table order, joints in joint order; a pixel shows the LAST primitive that covers it, whatever the launch shape.
+ *   Colours: limbs and box limb_colors[id mod n_limb_colors], joint j point_colors[j mod n_point_colors] (mathematical mod).  NV12 frames: each colour once through
+ *   the forward matrix of the frame's `matrix` (round(x 2^8) integers, csrc/drawgeom.h); Y per covered pixel, a chroma sample takes the (U, V) of the last
+ *   primitive that covers any of its up-to-four pixels.  No byte outside a covered pixel or chroma sample is written, pitch padding included.
+ * vp_draw_poses_stream only enqueues on caller_stream (two kernels per 32 frames of the table; limb table, palettes and style travel by kernel argument): no
+ * synchronisation, no copy from host memory, no allocation -- correct directly behind a boxes entry and vp_pose_nms_stream on the same stream.  The primitive
+ * records live in a workspace of the handle (VP_DRAW_MAX_RECORDS, allocated by vp_create): calls on one handle from different streams are the caller's to order.
+ * `images` are DEVICE frames; vp_image's plane pointers are const, and this entry WRITES through them.  cfg and its tables are HOST memory.
+ * VP_ERR_INVALID before anything is enqueued: a NULL images / d_kpts / d_frame_idx or n_images < 1 with n > 0, k outside 1..256, n_limbs outside
+ * 0..VP_DRAW_MAX_LIMBS or a limb index >= k, colour counts outside 1..VP_DRAW_MAX_COLORS, a NULL table, conf_thr not finite, radius outside 0..64, thickness outside
+ * 1..16, frame_stride < 1 (box_stride < 1 with boxes), n * (box + n_limbs + k) above VP_DRAW_MAX_RECORDS, and for every image of the table: no data, h or w outside
+ * 1..8192, the image refusals of vp_dbg_image_plan, a plane that is not device memory of the handle's device inside one allocation.  n = 0: VP_OK, nothing enqueued.
+ * vp_draw_poses: the synchronous twin on host pointers and host planes (upload, the same kernels, download).
+ * vp_dbg_draw_host: HOST ONLY, no device needed: csrc/drawgeom.h pixel by pixel on host planes, the model the device is tested against (a test tap, never a
+ * fallback); the same refusals, the reason in vp_last_error(NULL).  Library builds that carry the stage define VP_HAS_DRAW. */
+#define VP_HAS_DRAW 1
+#define VP_DRAW_MAX_LIMBS  256
+#define VP_DRAW_MAX_COLORS 32
+#define VP_DRAW_MAX_RECORDS 65536   /* primitive slots of one call: n * ((d_boxes != NULL) + n_limbs + k) */
+typedef struct vp_draw_cfg {
+    float   conf_thr;                       /* joints at or below are not drawn; the reference's 0.5 */
+    int32_t radius, thickness;              /* radius 0: max(1, min(h, w) / 150) per frame */
+    int32_t n_limbs;  const uint8_t* limbs; /* host [n_limbs, 2] joint indices < k */
+    int32_t n_point_colors; const uint8_t* point_colors;  /* host [n, 3] RGB */
+    int32_t n_limb_colors;  const uint8_t* limb_colors;   /* host [n, 3] RGB */
+} vp_draw_cfg;
+VP_API int vp_draw_poses_stream(vp_handle h, const vp_image* images, int32_t n_images, const float* d_kpts, int32_t n, int32_t k, const int32_t* d_frame_idx,
+                                int32_t frame_stride, const int32_t* d_rank, const int32_t* d_ids, const float* d_boxes, int32_t box_stride,
+                                const vp_draw_cfg* cfg, void* caller_stream);
+VP_API int vp_draw_poses(vp_handle h, const vp_image* images, int32_t n_images, const float* kpts, int32_t n, int32_t k, const int32_t* frame_idx,
+                         int32_t frame_stride, const int32_t* rank, const int32_t* ids, const float* boxes, int32_t box_stride, const vp_draw_cfg* cfg);
+VP_API int vp_dbg_draw_host(const vp_image* images, int32_t n_images, const float* kpts, int32_t n, int32_t k, const int32_t* frame_idx, int32_t frame_stride,
+                            const int32_t* rank, const int32_t* ids, const float* boxes, int32_t box_stride, const vp_draw_cfg* cfg);
+
 /* HOST ONLY, no device needed: the plan those entries run for expert_ids [n] on a handle of n_experts experts and max_batch crops per chunk -- the pure function
  * ids -> order, segments that shapes their launches.  Per chunk c (crops [c max_batch, ...)), with B = max_batch rounded up to a multiple of 4:
  *   order [n]: position j of chunk c holds the chunk-local caller row order[c max_batch + j] (stable expert order)
