@@ -42,7 +42,9 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_dbg_ln_finalize', 'vp_dbg_gemm_case_lnpart', 'vp_dbg_qkvattn_ln', 'vp_dbg_ln_quant',
            'vp_infer_images_affine', 'vp_infer_boxes_affine_stream', 'vp_dbg_box_cs', 'vp_dbg_affine_plan', 'vp_dbg_crop_affine', 'vp_dbg_decode_affine',
            'vp_dbg_decode_affine_flip',
-           'vp_draw_poses_stream', 'vp_draw_poses', 'vp_dbg_draw_host']
+           'vp_draw_poses_stream', 'vp_draw_poses', 'vp_dbg_draw_host',
+           'vp_tracker_create', 'vp_tracker_destroy', 'vp_tracker_reset_stream', 'vp_tracker_update_stream', 'vp_tracker_update', 'vp_tracker_state_bytes',
+           'vp_tracker_download_state', 'vp_dbg_track_host', 'vp_dbg_lsap']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -82,6 +84,10 @@ class vp_pose_nms_cfg(C.Structure):
 class vp_draw_cfg(C.Structure):
     _fields_ = [('conf_thr', C.c_float), ('radius', C.c_int32), ('thickness', C.c_int32), ('n_limbs', C.c_int32), ('limbs', C.c_void_p),
                 ('n_point_colors', C.c_int32), ('point_colors', C.c_void_p), ('n_limb_colors', C.c_int32), ('limb_colors', C.c_void_p)]
+
+
+class vp_track_cfg(C.Structure):
+    _fields_ = [('max_age', C.c_int32), ('min_hits', C.c_int32), ('iou_threshold', C.c_float), ('n_streams', C.c_int32)]
 
 
 class vp_profile(C.Structure):
@@ -230,6 +236,16 @@ def load_library():
     lib.vp_draw_poses_stream.argtypes = [H] + draw_host + [C.c_void_p]
     lib.vp_draw_poses.argtypes = [H] + draw_host
     lib.vp_dbg_draw_host.argtypes = draw_host
+    trk_io = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.vp_tracker_create.argtypes = [H, C.POINTER(vp_track_cfg), C.POINTER(C.c_void_p)]
+    lib.vp_tracker_destroy.argtypes = [C.c_void_p]
+    lib.vp_tracker_reset_stream.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.vp_tracker_update_stream.argtypes = [C.c_void_p] + trk_io + [C.c_void_p]
+    lib.vp_tracker_update.argtypes = [C.c_void_p] + trk_io
+    lib.vp_tracker_state_bytes.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
+    lib.vp_tracker_download_state.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vp_dbg_track_host.argtypes = [C.c_void_p, C.POINTER(vp_track_cfg)] + trk_io
+    lib.vp_dbg_lsap.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
     for name in SYMBOLS:
         if name not in ('vp_stream', 'vp_last_error', 'vp_host_alloc', 'vp_host_free', 'vp_group_member', 'vp_group_last_error'):
             getattr(lib, name).restype = C.c_int

@@ -84,6 +84,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--rotate', type=int, default=0, choices=[0, 90, 180, 270])
     ap.add_argument('--yolo-step', type=int, default=1)
     ap.add_argument('--single-pose', action='store_true')
+    ap.add_argument('--tracker', default='host', choices=['host', 'device'], help='video input: the SORT box tracker on the host (tracker.Sort, the default) or on '
+                    'the device (devtracker.DeviceSort), with the reference\'s parameters either way')
     ap.add_argument('--save-json', action='store_true')
     ap.add_argument('--show', action='store_true')
     ap.add_argument('--save-img', action='store_true', help='write every frame with its skeletons drawn on it as <stem>_<frame>.png into the output directory')
@@ -145,7 +147,7 @@ def main(argv=None) -> int:
                          args.det_class, dataset, args.yolo_size, is_video=is_video, single_pose=args.single_pose,
                          yolo_step=args.yolo_step, dtype=args.dtype, max_batch=args.max_batch,
                          flip_test=flip_test_argument(args), shift_heatmap=args.shift_heatmap, pose_nms=pose_nms_argument(args),
-                         crop=args.crop, box_scale=args.box_scale, skeleton=skeleton)
+                         crop=args.crop, box_scale=args.box_scale, skeleton=skeleton, tracker='device' if args.tracker == 'device' else None)
     print(f'>>> Model loaded: {args.model or "synthetic ViTPose-" + args.synthetic.upper()}')
     print(f'>>> Running inference on {args.input}')
     base = os.path.basename(args.input.rstrip('/'))

@@ -576,6 +576,11 @@ class VitPoseHip:
                                         int(n_frames), C.byref(c), score.ctypes.data, rank.ctypes.data, count.ctypes.data), self._h)
         return score, rank, count
 
+    def tracker(self, cfg=None):
+        """A box tracker on this handle's device (devtracker.DeviceTracker over vp_tracker_*): the stream-ordered stage in front of `infer_boxes`."""
+        from .devtracker import DeviceTracker, TrackCfg
+        return DeviceTracker(self, TrackCfg() if cfg is None else cfg)
+
     # ------------------------------------------------------------ skeleton overlay
     def _draw_skeleton(self, style: DrawStyle, K: int) -> np.ndarray:
         """the limb table of a call.  The handle of a plain checkpoint does not know its dataset: its 17 joints are taken as COCO's when `style.skeleton` is None

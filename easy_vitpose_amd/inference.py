@@ -10,10 +10,12 @@ of the engine handle (a pair list, or True for the COCO-17 table); ``pose_nms=``
 crop (:259-272) becomes ONE batched call into the C ABI (``_inference_batch``);
 ``_inference`` (single crop, :207-219) is still there and returns ``[1, K, 3]``.
 
-Out of scope here: the YOLO detector and the SORT tracker
-are third-party / CPU-side; ``yolo`` may be a path (needs ``ultralytics``) or any
-callable ``img_rgb -> ndarray[n, 5] (x1, y1, x2, y2, conf)``, ``tracker`` any object
-with the SORT ``update`` interface.  ``draw`` is not provided.
+Out of scope here (SURVEY.md section 2 / 8f): the YOLO detector is third-party;
+``yolo`` may be a path (needs ``ultralytics``) or any callable
+``img_rgb -> ndarray[n, 5] (x1, y1, x2, y2, conf)``.  The SORT tracker is ``tracker.Sort``
+on the host by default, ``tracker='device'`` selects the device tracker
+(``devtracker.DeviceSort``, vp_tracker_update), and a factory of any object with the
+SORT ``update`` interface is taken as it is.
 """
 from __future__ import annotations
 
@@ -81,6 +83,8 @@ class VitInference:
             raise ValueError(f"crop: 'pad' or 'affine' expected, got {crop!r}")
         if crop == 'affine' and pose_nms is not None:
             raise ValueError("pose_nms= does not run together with crop='affine' (the NMS area is defined on the pad route's crop)")
+        if not (tracker is None or tracker == 'device' or callable(tracker)):
+            raise ValueError(f"tracker: None (the host Sort), 'device' (devtracker.DeviceSort) or a factory expected, got {tracker!r}")
         if not (np.isfinite(box_scale) and box_scale > 0):
             raise ValueError(f'box_scale must be finite and > 0, got {box_scale!r}')
         self.crop, self.box_scale = crop, float(box_scale)
@@ -167,6 +171,8 @@ class VitInference:
                                     dtype=dtype, device_id=dev_id, max_batch=max_batch, dataset=dataset if plus else None)
         if flip_pairs is not None:   # a mode of the handle: every call below (inference, inference_frames, the boxes route) inherits it
             self._vit_pose.set_flip_test(flip_pairs, shift_heatmap)
+        if tracker == 'device':   # the device tracker lives on the engine's device: built now that there is one
+            self.reset()
         self._inference = self._inference_hip
 
     @staticmethod
@@ -193,9 +199,15 @@ class VitInference:
         use_tracker = self.is_video and not self.single_pose
         self.tracker = None
         if use_tracker:
-            if self._tracker_factory is None:   # the reference's own choice and parameters (inference.py:179-184):
-                from .tracker import Sort       # with detector-skipped frames (yolo_step > 1) a coasting track's hit streak restarts at every
-                min_hits = 3 if self.yolo_step == 1 else 1   # re-match, so min_hits must be 1 there or no pose is reported on detector frames
+            # the reference's own parameters (inference.py:179-184): with detector-skipped frames (yolo_step > 1) a coasting track's hit streak restarts at
+            # every re-match, so min_hits must be 1 there or no pose is reported on detector frames
+            min_hits = 3 if self.yolo_step == 1 else 1
+            if self._tracker_factory == 'device':   # ... on the device tracker (devtracker.DeviceSort: vp_tracker_update), once the engine exists
+                if getattr(self, '_vit_pose', None) is not None:
+                    from .devtracker import DeviceSort
+                    self.tracker = DeviceSort(self._vit_pose, max_age=self.yolo_step, min_hits=min_hits, iou_threshold=0.3)
+            elif self._tracker_factory is None:     # ... on the reference's own choice, the host Sort
+                from .tracker import Sort
                 self.tracker = Sort(max_age=self.yolo_step, min_hits=min_hits, iou_threshold=0.3)
             else:
                 self.tracker = self._tracker_factory()

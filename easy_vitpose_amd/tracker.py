@@ -10,12 +10,18 @@ iou_threshold=0.3)`` at ``easy_ViTPose/inference.py:179-184``).  The Kalman filt
 noise model of the SORT paper's public implementation (R = diag(1, 1, 10, 10), P0 = diag(10 x4, 1e4 x3),
 Q = diag(1, 1, 1, 1, 0.01, 0.01, 1e-4)); no filterpy, no lap.
 
-Two deliberate differences from the reference's tracker, neither visible through ``VitInference``'s contract within one video:
+Three deliberate differences from the reference's tracker, none visible through ``VitInference``'s contract within one video:
 * track ids restart at 1 for every ``Sort`` instance (``VitInference.reset()`` builds a new one per video); the reference numbers
   tracks from the class-global ``KalmanBoxTracker.count`` (``sort.py:96,112-113``), which is never reset, so its ids keep growing
   across ``reset()`` calls and videos;
 * a degenerate (zero-area) detection AND track pair has IoU 0 here; the reference divides 0 by 0 there and its assignment step then
-  raises ``ValueError`` on the NaN.
+  raises ``ValueError`` on the NaN;
+* tracks born in one frame are numbered in DETECTION-INDEX order.  The reference appends first the detections that are absent from the assignment, then
+  those whose assigned pair fell below the threshold (``sort.py:178-192``); with more detections than tracks, which zero-IoU detection its solver pairs
+  with a leftover track is a tie-break inside scipy, so its ids depend on that.  On the seeded crowds of ``tests/track_cases.py`` the two produce the same
+  (frame, box, score) rows exactly and ids that agree up to a bijection between tracks born in the same frame: 0 of 14 and 0 of 24 ids relabelled at 12
+  and 24 persons, 16 of 64 at 40, 6 of 104 at 100, 26 of 124 at 120 (``tests/test_track_host.py``, ``tests/golden/sort_crowd.npz``).  Detection-index order
+  does not depend on the tie-break; it is the rule ``csrc/sortgeom.h`` keeps for the device tracker (``devtracker.py``), of which this module is the Python twin.
 """
 from __future__ import annotations
 

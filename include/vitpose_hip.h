@@ -535,6 +535,63 @@ VP_API int vp_draw_poses(vp_handle h, const vp_image* images, int32_t n_images, 
 VP_API int vp_dbg_draw_host(const vp_image* images, int32_t n_images, const float* kpts, int32_t n, int32_t k, const int32_t* frame_idx, int32_t frame_stride,
                             const int32_t* rank, const int32_t* ids, const float* boxes, int32_t box_stride, const vp_draw_cfg* cfg);
 
+/* The box tracker on the device, the stage IN FRONT of a boxes entry: SORT as the reference's video path runs it (sort.py Sort.update behind inference.py:247-249;
+ * csrc/sortgeom.h states the arithmetic once for the kernels and the host taps, easy_vitpose_amd/tracker.py is the Python twin).  A tracker object holds n_streams
+ * independent SORT states (one per camera: the multi-frame shape of vp_infer_frames and of the NMS) in device memory of the handle's device; a stream holds at most
+ * VP_TRACK_MAX live tracks and takes at most VP_TRACK_MAX detections per call.
+ *   d_dets float32 rows (x1, y1, x2, y2, score) at d_dets + i * row_stride (a detector's [n, 6] tensor passes in place with stride 6); d_frame_idx int32 [n_dets]: the
+ *   stream of every row (NULL: all rows are stream 0).  Rows of a stream keep their call order.  step_mask: bit s = stream s advances one frame in this call; a stream
+ *   in the mask without a detection row steps with empty input (the detector-skipped frame: every listed track's PREDICTED box is reported), a stream outside the
+ *   mask is untouched and its rows are ignored.  n_dets = 0 is legal: the coasting call.
+ *   Per stream (fp64, nothing contracted, correctly rounded sqrt and division): predict every track (area guard x[6] + x[2] <= 0 -> x[6] = 0); tracks whose predicted
+ *   box is not finite leave the list; IoU against the detections (a zero-area pair: 0); association as tracker.associate: where every row and column of iou > thr
+ *   holds at most one entry those entries are the pairs, otherwise the exact rectangular linear-sum assignment that maximises the total IoU (shortest augmenting
+ *   paths, fp64 duals, every loop bounded by the matrix sides); pairs with iou < thr are dropped; matched tracks take the Kalman update in Joseph form; the
+ *   unmatched detections become new tracks in DETECTION-INDEX order (the reference's order depends on a tie-break inside its assignment solver: tracker.py), ids from
+ *   1 per stream; a track is reported when time_since_update < 1 and (hit_streak >= min_hits or frame_count <= min_hits); tracks leave when
+ *   time_since_update > max_age.
+ *   Output: d_rows float32 [n_out, 6] (x1, y1, x2, y2, score, id), the fp64 values rounded once; d_ids, d_stream int32 [n_out]; streams ascending, within a stream
+ *   the reference's order (reversed track list).  Rows beyond the total are "absent": box NaN, score 0, id -1, stream -1 -- vp_infer_boxes_stream gives such a row
+ *   status 1, reads no frame and returns zeros, the NMS gives it rank -1.  So d_rows passes in place to vp_infer_boxes_stream (row_stride 6, d_stream as d_frame_idx)
+ *   and to the NMS as d_rows + 4.  d_count int32 [n_streams + 1]: rows per stream, last = the true total, whatever n_out.  d_flags (may be NULL) int32 [n_streams]:
+ *   1 detections beyond VP_TRACK_MAX ignored (the first in call order kept); 2 births dropped at VP_TRACK_MAX live tracks (the lowest detection indices kept);
+ *   4 rows of this stream cut by n_out (a stream without rows behind the cut is not flagged); 8 a detection row of this stream that is not finite was skipped, or a row of the call names a stream outside the table (that
+ *   is raised on every stepped stream).
+ * vp_tracker_update_stream only enqueues on caller_stream (two kernels: one workgroup per stepped stream, then one workgroup that packs the rows; the configuration
+ * travels by kernel argument): no synchronisation, no copy from host memory, no allocation, none of the handle's workspaces.  Calls on one tracker from different
+ * streams are the caller's to order.  vp_tracker_reset_stream zeroes the state of the streams in the mask on caller_stream (ids restart at 1).
+ * VP_ERR_INVALID before anything is enqueued: a NULL cfg / d_count, NULL d_dets with n_dets > 0, NULL d_rows / d_ids / d_stream with n_out > 0, row_stride < 5,
+ * n_streams outside 1..VP_TRACK_MAX_STREAMS, max_age < 0, min_hits < 0, iou_threshold not in (0, 1), n_dets < 0, n_out < 0, a mask bit beyond n_streams.
+ * vp_tracker_update: the synchronous twin on host pointers (upload, the same kernels, download).  vp_tracker_create: on the device of h, state zeroed; the tracker
+ * must be destroyed before h.  Library builds that carry the stage define VP_HAS_TRACKER. */
+#define VP_HAS_TRACKER 1
+#define VP_TRACK_MAX 128
+#define VP_TRACK_MAX_STREAMS 64
+typedef struct vp_track_cfg {
+    int32_t max_age, min_hits;
+    float   iou_threshold;
+    int32_t n_streams;
+} vp_track_cfg;
+typedef struct vp_tracker* vp_tracker_handle;
+VP_API int vp_tracker_create(vp_handle h, const vp_track_cfg* cfg, vp_tracker_handle* out);
+VP_API int vp_tracker_destroy(vp_tracker_handle t);
+VP_API int vp_tracker_reset_stream(vp_tracker_handle t, uint64_t stream_mask, void* caller_stream);
+VP_API int vp_tracker_update_stream(vp_tracker_handle t, const float* d_dets, int32_t row_stride, const int32_t* d_frame_idx, int32_t n_dets, uint64_t step_mask,
+                                    float* d_rows, int32_t* d_ids, int32_t* d_stream, int32_t n_out, int32_t* d_count, int32_t* d_flags, void* caller_stream);
+VP_API int vp_tracker_update(vp_tracker_handle t, const float* dets, int32_t row_stride, const int32_t* frame_idx, int32_t n_dets, uint64_t step_mask, float* rows,
+                             int32_t* ids, int32_t* stream, int32_t n_out, int32_t* count, int32_t* flags);
+/* The state as csrc/sortgeom.h lays it out (TrkStream [n_streams]; easy_vitpose_amd/devtracker.py STATE_DTYPE), for tests: its size, and a synchronous download
+ * (it waits for the device first). */
+VP_API int vp_tracker_state_bytes(int32_t n_streams, int64_t* bytes);
+VP_API int vp_tracker_download_state(vp_tracker_handle t, void* out);
+/* HOST ONLY, no device needed: csrc/sortgeom.h run serially on a host state blob of vp_tracker_state_bytes (zeroed = a new tracker), the model the device is tested
+ * against (a test tap, never a fallback); the refusals of vp_tracker_create and vp_tracker_update_stream, the reason in vp_last_error(NULL). */
+VP_API int vp_dbg_track_host(void* state, const vp_track_cfg* cfg, const float* dets, int32_t row_stride, const int32_t* frame_idx, int32_t n_dets, uint64_t step_mask,
+                             float* rows, int32_t* ids, int32_t* stream, int32_t n_out, int32_t* count, int32_t* flags);
+/* The association alone on iou [nd, nt] fp64 (host pointers, nd, nt <= VP_TRACK_MAX): trk_of_det [nd] = the track paired with every detection or -1, shortcut,
+ * assignment and threshold filter included.  device_id = -1: on the host, no device needed; a device runs the tracker kernel's association (one column per lane). */
+VP_API int vp_dbg_lsap(int32_t device_id, const double* iou, int32_t nd, int32_t nt, float thr, int32_t* trk_of_det);
+
 /* HOST ONLY, no device needed: the plan those entries run for expert_ids [n] on a handle of n_experts experts and max_batch crops per chunk -- the pure function
  * ids -> order, segments that shapes their launches.  Per chunk c (crops [c max_batch, ...)), with B = max_batch rounded up to a multiple of 4:
  *   order [n]: position j of chunk c holds the chunk-local caller row order[c max_batch + j] (stable expert order)

@@ -4,7 +4,7 @@
     python tools/isa_diff.py A B [--tools] [-j N]
 
 A and B are two checkouts of this repository (for instance `git worktree add ../parent HEAD~1` and the working tree).  Every translation unit of
-build.py::SOURCES (--tools: TOOLS_SOURCES with -DVP_TOOLS) is compiled in both with build.py::FLAGS + `--cuda-device-only -S`, each tree with its own
+build.py::SOURCES (--tools: TOOLS_SOURCES with -DVP_TOOLS) is compiled in both with build.py::FLAGS (+ its SOURCE_FLAGS entry, where a tree has one) + `--cuda-device-only -S`, each tree with its own
 build.py, into a temporary directory.  Comment lines and the `__hip_cuid_*` lines (a hash of the compilation) are dropped, kernels are paired by order
 of appearance and their mangled symbols replaced by the ordinal, so a renamed template argument is no difference but any instruction, register count
 or kernel descriptor field is.  One line per translation unit: `identical`, or the kernels that differ with their register counts, spills, scratch
@@ -49,7 +49,7 @@ def describe(tree: str) -> str:
 
 def compile_asm(build, src: str, out: str, tools: bool):
     # run inside csrc with a relative source name: no path of the tree reaches the assembly
-    cmd = [build._hipcc(), *build.FLAGS, *(['-DVP_TOOLS'] if tools else []), '--cuda-device-only', '-S', src, '-o', out]
+    cmd = [build._hipcc(), *build.FLAGS, *getattr(build, 'SOURCE_FLAGS', {}).get(src, []), *(['-DVP_TOOLS'] if tools else []), '--cuda-device-only', '-S', src, '-o', out]
     r = subprocess.run(cmd, cwd=build.CSRC, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f'hipcc failed in {build.CSRC}: {" ".join(cmd)}\n{r.stdout}\n{r.stderr}')
