@@ -44,7 +44,9 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_dbg_decode_affine_flip',
            'vp_draw_poses_stream', 'vp_draw_poses', 'vp_dbg_draw_host',
            'vp_tracker_create', 'vp_tracker_destroy', 'vp_tracker_reset_stream', 'vp_tracker_update_stream', 'vp_tracker_update', 'vp_tracker_state_bytes',
-           'vp_tracker_download_state', 'vp_dbg_track_host', 'vp_dbg_lsap']
+           'vp_tracker_download_state', 'vp_dbg_track_host', 'vp_dbg_lsap',
+           'vp_smoother_create', 'vp_smoother_destroy', 'vp_smoother_reset_stream', 'vp_smooth_update_stream', 'vp_smooth_update', 'vp_smoother_state_bytes',
+           'vp_smoother_download_state', 'vp_dbg_smooth_host']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -88,6 +90,11 @@ class vp_draw_cfg(C.Structure):
 
 class vp_track_cfg(C.Structure):
     _fields_ = [('max_age', C.c_int32), ('min_hits', C.c_int32), ('iou_threshold', C.c_float), ('n_streams', C.c_int32)]
+
+
+class vp_smooth_cfg(C.Structure):
+    _fields_ = [('min_cutoff', C.c_double), ('beta', C.c_double), ('d_cutoff', C.c_double), ('max_age', C.c_int32), ('n_streams', C.c_int32),
+                ('n_joints', C.c_int32), ('max_rows', C.c_int32), ('missing', C.c_int32)]
 
 
 class vp_profile(C.Structure):
@@ -246,6 +253,15 @@ def load_library():
     lib.vp_tracker_download_state.argtypes = [C.c_void_p, C.c_void_p]
     lib.vp_dbg_track_host.argtypes = [C.c_void_p, C.POINTER(vp_track_cfg)] + trk_io
     lib.vp_dbg_lsap.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
+    smooth_io = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vp_smoother_create.argtypes = [H, C.POINTER(vp_smooth_cfg), C.POINTER(C.c_void_p)]
+    lib.vp_smoother_destroy.argtypes = [C.c_void_p]
+    lib.vp_smoother_reset_stream.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.vp_smooth_update_stream.argtypes = [C.c_void_p] + smooth_io + [C.c_void_p]
+    lib.vp_smooth_update.argtypes = [C.c_void_p] + smooth_io
+    lib.vp_smoother_state_bytes.argtypes = [C.POINTER(vp_smooth_cfg), C.POINTER(C.c_int64)]
+    lib.vp_smoother_download_state.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vp_dbg_smooth_host.argtypes = [C.c_void_p, C.POINTER(vp_smooth_cfg)] + smooth_io
     for name in SYMBOLS:
         if name not in ('vp_stream', 'vp_last_error', 'vp_host_alloc', 'vp_host_free', 'vp_group_member', 'vp_group_last_error'):
             getattr(lib, name).restype = C.c_int

@@ -67,6 +67,21 @@ def pose_nms_argument(args):
                    sigmas=None if args.sigmas is None else load_sigmas(args.sigmas))
 
 
+def smooth_argument(args):
+    """--smooth / --smooth-fps F / --min-cutoff / --beta / --smooth-missing -> VitInference's smooth=: None (off) or a SmoothCfg."""
+    if not args.smooth and args.smooth_fps is None:
+        if args.min_cutoff is not None or args.beta is not None or args.smooth_missing is not None:
+            raise ValueError('--min-cutoff, --beta and --smooth-missing belong to --smooth')
+        return None
+    from easy_vitpose_amd.devsmooth import SmoothCfg
+    kw = dict(fps=args.smooth_fps, missing=args.smooth_missing or 'reference')
+    if args.min_cutoff is not None:
+        kw['min_cutoff'] = args.min_cutoff
+    if args.beta is not None:
+        kw['beta'] = args.beta
+    return SmoothCfg(**kw)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--input', required=True, help='image file, .npy frame stack, or directory of images')
@@ -105,6 +120,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--crop', default='pad', choices=['pad', 'affine'], help='how a box becomes the 256 x 192 crop: pad (the default: +10 px, clipped, zero-padded to '
                     '3:4 and resized, as VitInference.inference does) or affine (the training / evaluation protocol: the box extended to 3:4 with image content, '
                     'scaled by --box-scale and warped; not together with --pose-nms)')
+    ap.add_argument('--smooth', action='store_true', help='video input: One-Euro smoothing of every tracked person\'s keypoints on the device, keyed by the '
+                    'tracker\'s ids (the reference\'s one_euro_filter.py with its defaults: min_cutoff 1.7, beta 0.3, d_cutoff 30)')
+    ap.add_argument('--smooth-fps', type=float, default=None, metavar='F', help='--smooth with d_cutoff = F, the frame rate of the video (implies --smooth)')
+    ap.add_argument('--min-cutoff', type=float, default=None, help='--smooth: the filter\'s min_cutoff (default 1.7)')
+    ap.add_argument('--beta', type=float, default=None, help='--smooth: the filter\'s beta (default 0.3)')
+    ap.add_argument('--smooth-missing', default=None, choices=['reference', 'restart'], help='--smooth: a joint at a coordinate <= 0 is reported at -10; afterwards '
+                    'the filter blends away from -10 (reference, the default) or starts afresh from the next sample (restart)')
     ap.add_argument('--box-scale', type=float, default=1.25, metavar='S', help='--crop affine: the factor the box is scaled by (the reference\'s 1.25)')
     return ap
 
@@ -147,7 +169,8 @@ def main(argv=None) -> int:
                          args.det_class, dataset, args.yolo_size, is_video=is_video, single_pose=args.single_pose,
                          yolo_step=args.yolo_step, dtype=args.dtype, max_batch=args.max_batch,
                          flip_test=flip_test_argument(args), shift_heatmap=args.shift_heatmap, pose_nms=pose_nms_argument(args),
-                         crop=args.crop, box_scale=args.box_scale, skeleton=skeleton, tracker='device' if args.tracker == 'device' else None)
+                         crop=args.crop, box_scale=args.box_scale, skeleton=skeleton, tracker='device' if args.tracker == 'device' else None,
+                         smooth=smooth_argument(args))
     print(f'>>> Model loaded: {args.model or "synthetic ViTPose-" + args.synthetic.upper()}')
     print(f'>>> Running inference on {args.input}')
     base = os.path.basename(args.input.rstrip('/'))

@@ -581,6 +581,12 @@ class VitPoseHip:
         from .devtracker import DeviceTracker, TrackCfg
         return DeviceTracker(self, TrackCfg() if cfg is None else cfg)
 
+    def smoother(self, cfg=None):
+        """A keypoint smoother for this handle's K joints on its device (devsmooth.DeviceSmoother over vp_smooth_*): the stream-ordered One-Euro stage behind
+        `infer_boxes` (and its NMS), keyed by the tracker's (stream, id), in front of `draw_poses`."""
+        from .devsmooth import DeviceSmoother, SmoothCfg
+        return DeviceSmoother(self, self.K, SmoothCfg() if cfg is None else cfg)
+
     # ------------------------------------------------------------ skeleton overlay
     def _draw_skeleton(self, style: DrawStyle, K: int) -> np.ndarray:
         """the limb table of a call.  The handle of a plain checkpoint does not know its dataset: its 17 joints are taken as COCO's when `style.skeleton` is None

@@ -6,7 +6,9 @@ Kept from the reference: constructor signature (:81-90), ``reset`` (:174-185),
 ``pre_img`` (:314-318), the state attributes (:112-116, :274-279) and the exception
 types.  Added: ``flip_test=`` (keyword): the reference's test-time flip averaging as a mode
 of the engine handle (a pair list, or True for the COCO-17 table); ``pose_nms=`` (keyword, a ``PoseNms``): person scores
-(keypoint confidence x box score, the reference's open note at :272) and per-frame OKS pose NMS after the pose call.  Changed on purpose: the per-box Python loop that ran the model once per
+(keypoint confidence x box score, the reference's open note at :272) and per-frame OKS pose NMS after the pose call; ``smooth=`` (keyword, True or a
+``SmoothCfg``): with ``is_video``, One-Euro smoothing of every tracked person's keypoints on the device (``devsmooth``; the reference's
+``post_processing/one_euro_filter.py``), keyed by the tracker's ids, before the result dict and ``draw()``.  Changed on purpose: the per-box Python loop that ran the model once per
 crop (:259-272) becomes ONE batched call into the C ABI (``_inference_batch``);
 ``_inference`` (single crop, :207-219) is still there and returns ``[1, K, 3]``.
 
@@ -77,7 +79,7 @@ class VitInference:
                  single_pose: Optional[bool] = False,
                  yolo_step: Optional[int] = 1,
                  *, dtype: str = 'fp16', max_batch: int = 64, tracker=None, flip_test=None, shift_heatmap: bool = False,
-                 pose_nms: Optional[PoseNms] = None, crop: str = 'pad', box_scale: float = 1.25, skeleton=None):
+                 pose_nms: Optional[PoseNms] = None, crop: str = 'pad', box_scale: float = 1.25, skeleton=None, smooth=None):
         # crop='affine': the training-protocol crop (cropprep.box_to_cs, VitPoseHip.infer_frames(crop='affine')) instead of the pad route; refused before anything is loaded
         if crop not in ('pad', 'affine'):
             raise ValueError(f"crop: 'pad' or 'affine' expected, got {crop!r}")
@@ -85,6 +87,12 @@ class VitInference:
             raise ValueError("pose_nms= does not run together with crop='affine' (the NMS area is defined on the pad route's crop)")
         if not (tracker is None or tracker == 'device' or callable(tracker)):
             raise ValueError(f"tracker: None (the host Sort), 'device' (devtracker.DeviceSort) or a factory expected, got {tracker!r}")
+        # smooth: One-Euro keypoint smoothing per tracked person (devsmooth.SmoothCfg; True = the reference's defaults); refused before anything is loaded
+        from .devsmooth import SmoothCfg
+        if not (smooth is None or smooth is True or smooth is False or isinstance(smooth, SmoothCfg)):
+            raise TypeError(f'smooth: None, True or a SmoothCfg expected, got {smooth!r}')
+        self._smooth_cfg = SmoothCfg() if smooth is True else (smooth or None)
+        self._smoother = None
         if not (np.isfinite(box_scale) and box_scale > 0):
             raise ValueError(f'box_scale must be finite and > 0, got {box_scale!r}')
         self.crop, self.box_scale = crop, float(box_scale)
@@ -171,7 +179,7 @@ class VitInference:
                                     dtype=dtype, device_id=dev_id, max_batch=max_batch, dataset=dataset if plus else None)
         if flip_pairs is not None:   # a mode of the handle: every call below (inference, inference_frames, the boxes route) inherits it
             self._vit_pose.set_flip_test(flip_pairs, shift_heatmap)
-        if tracker == 'device':   # the device tracker lives on the engine's device: built now that there is one
+        if tracker == 'device' or self._smooth_cfg is not None:   # the device tracker and the smoother live on the engine's device: built now that there is one
             self.reset()
         self._inference = self._inference_hip
 
@@ -211,7 +219,27 @@ class VitInference:
                 self.tracker = Sort(max_age=self.yolo_step, min_hits=min_hits, iou_threshold=0.3)
             else:
                 self.tracker = self._tracker_factory()
+        # keypoint smoothing is keyed by the tracker's ids, so it runs only where a tracker does; a new video starts with empty filter tables
+        if getattr(self, '_smoother', None) is not None:
+            self._smoother.close()
+        self._smoother = None
+        if use_tracker and getattr(self, '_smooth_cfg', None) is not None and getattr(self, '_vit_pose', None) is not None:
+            self._smoother = self._vit_pose.smoother(self._smooth_cfg)
         self.frame_counter = 0
+
+    def _smooth_results(self, results):
+        """VitInference(smooth=): the keypoints of every person of every frame, in frame order, through the smoother's synchronous twin (vp_smooth_update), keyed by
+        the tracker's ids on stream 0, before they enter the result dict and draw().  One call per frame (an empty frame ages the filters); a frame with more
+        persons than the configuration's max_rows smooths the first max_rows of them."""
+        if self._smoother is None:
+            return
+        K, cap = self._vit_pose.K, self._smoother.cfg.max_rows
+        for frame_keypoints, _ in results:
+            ids = list(frame_keypoints.keys())[:cap]
+            kp = np.stack([frame_keypoints[i] for i in ids]).astype(np.float32) if ids else np.zeros((0, K, 3), np.float32)
+            out, _ = self._smoother.update_host(kp, np.array(ids, dtype=np.int32).reshape(-1))
+            for k, i in enumerate(ids):
+                frame_keypoints[i] = out[k]
 
     @classmethod
     def postprocess(cls, heatmaps, org_w, org_h):
@@ -306,6 +334,7 @@ class VitInference:
                     else:
                         scores_bbox[id_] = float(score[start + i])
                 start += len(bboxes)
+        self._smooth_results(results)
         if self.save_state and len(imgs):
             bboxes, ids, scores = dets[-1]
             self._img = imgs[-1]
@@ -325,6 +354,7 @@ class VitInference:
             kps_f = kps[start:start + len(bboxes)]
             start += len(bboxes)
             results.append(({id_: kps_f[i] for i, id_ in enumerate(ids)}, {id_: score for id_, score in zip(ids, scores)}))
+        self._smooth_results(results)
         if self.save_state and len(imgs):
             self._img = imgs[-1]
             self._tracker_res = dets[-1]

@@ -592,6 +592,62 @@ VP_API int vp_dbg_track_host(void* state, const vp_track_cfg* cfg, const float* 
  * assignment and threshold filter included.  device_id = -1: on the host, no device needed; a device runs the tracker kernel's association (one column per lane). */
 VP_API int vp_dbg_lsap(int32_t device_id, const double* iou, int32_t nd, int32_t nt, float thr, int32_t* trk_of_det);
 
+/* Keypoint smoothing on the device, the stage BEHIND a boxes entry (and its NMS) and in front of vp_draw_poses_stream: the One-Euro filter of the reference's
+ * post_processing/one_euro_filter.py in its fixed-rate mode, one filter per (stream, track id) (csrc/eurogeom.h states the arithmetic once for the kernels and the
+ * host tap, easy_vitpose_amd/smooth.py is the numpy twin).  A smoother object holds n_streams tables of VP_SMOOTH_SLOTS slots for n_joints joints in device memory
+ * of the handle's device: per slot an id, last_seen and 2 n_joints coordinate states (x_prev, dx_prev fp64, a fresh byte), per stream a frame_count.
+ *   d_kpts float32 [n, n_joints, 3] rows of (y, x, conf); d_ids int32 [n] (the tracker's d_ids); d_stream int32 [n] (NULL: all rows are stream 0); d_rank int32 [n]
+ *   (NULL: none; the NMS's rank); t_e HOST double [n_streams] (NULL: 1.0 each), copied into the kernel arguments; d_out float32 [n, n_joints, 3], may be d_kpts.
+ *   Per stream s in step_mask, in this order: (1) frame_count += 1.  (2) slots with frame_count - last_seen > max_age + 1 become free (last_seen = the frame_count
+ *   of the call that last updated the slot: a slot survives max_age stepped calls without a row).  (3) the rows of s in call order with id >= 0, rank >= 0 where
+ *   a rank is given, and every y and x finite are ACTIVE.  Taken in call order: (4) an active row whose id owns a slot that no earlier row of this call touched is
+ *   UPDATED with t_e[s] * (frame_count - last_seen) -- a track that skipped frames is filtered over the gap -- and last_seen = frame_count; (5) an active row whose
+ *   id owns no slot is BORN into the lowest free slot (x_prev = x, dx_prev = 0, fresh; returned unchanged, nothing masked).  (6) every other row is copied through
+ *   bit for bit and touches no state: id < 0 or a stream outside the table (the tracker's absent rows), rows of streams not in step_mask, rows that are not
+ *   active, a row whose id an earlier row of this call already updated or bore (the first in call order wins), a birth that finds no free slot.
+ *   The update of a coordinate (fp64, nothing contracted, division correctly rounded), x the float32 input, conf never touched:
+ *     d = fresh ? (double)((float)x - (float)x_prev) : (double)x - x_prev;  dx = d / t_e;  r = (2 pi d_cutoff) t_e;  a_d = r / (r + 1);
+ *     dx_hat = a_d dx + (1 - a_d) dx_prev;  cutoff = min_cutoff + beta |dx_hat|;  r = (2 pi cutoff) t_e;  a = r / (r + 1);  x_hat = a x + (1 - a) x_prev;
+ *     x_hat = -10 where x <= 0;  x_prev = x_hat, dx_prev = dx_hat, fresh cleared;  the output is (float)x_hat.
+ *   missing = 0: exactly that (the reference: after a masked sample the filter blends away from -10).  missing = 1 (restart): a coordinate whose x_prev <= 0 takes
+ *   x_hat = x (-10 where x <= 0), dx_hat = 0 and is fresh again.
+ *   d_flags (may be NULL) int32 [n_streams], 0 for a stream outside step_mask: 1 a row with an id already seen in this call was passed through; 2 a birth was
+ *   dropped because the table is full; 8 an active-looking row of this stream (id >= 0, rank >= 0) that is not finite was skipped, or a row with id >= 0 names a
+ *   stream outside the table (that is raised on every stepped stream).
+ * vp_smooth_update_stream only enqueues on caller_stream (two kernels: one workgroup per stepped stream that ages, matches and bears, then one thread per row and
+ * joint that filters; the configuration and t_e travel by kernel argument): no synchronisation, no copy from host memory, no allocation, none of the handle's
+ * workspaces.  Calls on one smoother from different streams are the caller's to order.  vp_smoother_reset_stream zeroes the tables of the streams in the mask on
+ * caller_stream.  n = 0 with a non-zero mask is legal: it ages the streams.
+ * VP_ERR_INVALID before anything is enqueued: a NULL cfg, NULL d_kpts / d_ids / d_out with n > 0, n < 0 or n > max_rows, n_streams outside
+ * 1..VP_TRACK_MAX_STREAMS, n_joints outside 1..1024, max_rows outside 1..VP_SMOOTH_MAX_ROWS, max_age < 0, min_cutoff / d_cutoff / any t_e not finite or <= 0, beta
+ * not finite or < 0, missing not 0 or 1, a mask bit beyond n_streams.
+ * vp_smooth_update: the synchronous twin on host pointers (upload, the same kernels, download).  vp_smoother_create: on the device of h, state zeroed (zeroed =
+ * new); the smoother must be destroyed before h.  Library builds that carry the stage define VP_HAS_SMOOTHER. */
+#define VP_HAS_SMOOTHER 1
+#define VP_SMOOTH_SLOTS 128
+#define VP_SMOOTH_MAX_ROWS 65536
+typedef struct vp_smooth_cfg {
+    double  min_cutoff, beta, d_cutoff;
+    int32_t max_age, n_streams, n_joints, max_rows, missing;
+} vp_smooth_cfg;
+typedef struct vp_smoother* vp_smoother_handle;
+VP_API int vp_smoother_create(vp_handle h, const vp_smooth_cfg* cfg, vp_smoother_handle* out);
+VP_API int vp_smoother_destroy(vp_smoother_handle s);
+VP_API int vp_smoother_reset_stream(vp_smoother_handle s, uint64_t stream_mask, void* caller_stream);
+VP_API int vp_smooth_update_stream(vp_smoother_handle s, const float* d_kpts, const int32_t* d_ids, const int32_t* d_stream, const int32_t* d_rank, int32_t n,
+                                   uint64_t step_mask, const double* t_e, float* d_out, int32_t* d_flags, void* caller_stream);
+VP_API int vp_smooth_update(vp_smoother_handle s, const float* kpts, const int32_t* ids, const int32_t* stream, const int32_t* rank, int32_t n, uint64_t step_mask,
+                            const double* t_e, float* out, int32_t* flags);
+/* The state as csrc/eurogeom.h lays it out, for tests: n_streams blobs of  int32 frame_count, pad[3] | int32 id[128] | int32 last_seen[128] (0 = free) |
+ * double x_prev[128][n_joints][2] | double dx_prev[128][n_joints][2] | uint8 fresh[128][n_joints][2]  (the pair = (y, x); easy_vitpose_amd/devsmooth.py
+ * state_dtype); its size, and a synchronous download (it waits for the device first). */
+VP_API int vp_smoother_state_bytes(const vp_smooth_cfg* cfg, int64_t* bytes);
+VP_API int vp_smoother_download_state(vp_smoother_handle s, void* out);
+/* HOST ONLY, no device needed: csrc/eurogeom.h run serially on a host state blob of vp_smoother_state_bytes (zeroed = a new smoother), the model the device is
+ * tested against (a test tap, never a fallback); the refusals of vp_smoother_create and vp_smooth_update_stream, the reason in vp_last_error(NULL). */
+VP_API int vp_dbg_smooth_host(void* state, const vp_smooth_cfg* cfg, const float* kpts, const int32_t* ids, const int32_t* stream, const int32_t* rank, int32_t n,
+                              uint64_t step_mask, const double* t_e, float* out, int32_t* flags);
+
 /* HOST ONLY, no device needed: the plan those entries run for expert_ids [n] on a handle of n_experts experts and max_batch crops per chunk -- the pure function
  * ids -> order, segments that shapes their launches.  Per chunk c (crops [c max_batch, ...)), with B = max_batch rounded up to a multiple of 4:
  *   order [n]: position j of chunk c holds the chunk-local caller row order[c max_batch + j] (stable expert order)
