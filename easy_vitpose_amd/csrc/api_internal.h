@@ -399,6 +399,9 @@ HeadPlan plan_head(const Switches& s, int D, int nh, size_t fin_rows);
 // ---- forward.hip: one GEMM of the path as `pk` resolved it (also what the vp_dbg_gemm* taps launch).  EPI_DECONV_FINAL: `out` = the fp32 heatmaps
 int gemm(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint16_t* A, const uint16_t* W, const float* bias, void* out,
          const float* aux, int M, int N, int K, int ldo, int Hin = 0, int Win = 0, int Cin = 0, const LnFuse* ln = nullptr);
+// ... and the arguments it launches with (vp_dbg_head_case launches the head's GEMMs from the same function)
+vp::GemmArgs gemm_args(const vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint16_t* A, const uint16_t* W, const float* bias, void* out,
+                       const float* aux, int M, int N, int K, int ldo, int Hin = 0, int Win = 0, int Cin = 0, const LnFuse* ln = nullptr);
 int gemm_fp8(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint8_t* A8, const uint8_t* a_scales, const uint8_t* W8, const float* w_scale, const float* bias,
              void* out, uint8_t* out_scales, const float* aux, int M, int N, int K, const LnFuse* ln);
 // what a forward_chunk call asks for beyond the plain forward to heatmaps in c->hm

@@ -285,6 +285,67 @@ VP_API int vp_dbg_deconv(int32_t device, int32_t dtype, int32_t B, int32_t Hin, 
     return dbg_finish(c, rc);
 }
 
+// ONE GEMM of the keypoint head on a chosen tile (tests/test_gpu_head.py), launched through vp::gemm_launch with the arguments forward.hip's own gemm_args builds for it.
+//   stage 0: EPI_DECONV                       x [B,Hin,Win,Cin] NHWC -> out = the 16-bit NHWC tensor [B,2Hin,2Win,256] (as fp32)
+//   stage 1: EPI_DECONV_FINAL                 ... -> out = the fp32 heatmaps [B,Kp,2Hin,2Win] (deconv + folded BN + ReLU + the final 1x1 conv in one kernel)
+//   stage 2: EPI_DECONV, then EPI_HEATMAP     the un-fused head on the same operands: mid = the 16-bit tensor, out = the heatmaps (EPI_HEATMAP's images are 64 x 48:
+//                                             Hin x Win = 32 x 24, Cin = 256 only; its launch runs on the rule's tile)
+// variant = the deconv's tile (a gemm.hip Cfg id), -1 = what resolve_gemm picks for the shape; parity_fast = Switches::deconv_parity_fast for this call.  tensors = the raw
+// deconv + BN tensors as for vp_dbg_deconv (packed by pack_deconv); stages 1 / 2: w_fin [Kp,256], b_fin [Kp] (upload_final: hi + lo planes).  x is rounded to dtype on
+// upload (a no-op on values that are already of that type).  Every device output is filled with 0xFF bytes first and has 16 * (4 Hin Win) more elements behind it, which come
+// back as bytes in guard / mid_guard: an unwritten element returns as NaN, a write past the end shows in the guard.  What gemm_launch refuses comes back as its error.
+VP_API int vp_dbg_head_case(int32_t device, int32_t dtype, int32_t stage, int32_t variant, int32_t parity_fast, int32_t B, int32_t Hin, int32_t Win, int32_t Cin,
+                            const float* x, const vp_tensor_desc* tensors, int32_t n_tensors, int32_t Kp, const float* w_fin, const float* b_fin, float* out,
+                            uint8_t* guard, float* mid, uint8_t* mid_guard) {
+    if (stage < 0 || stage > 2 || (parity_fast & ~1) || B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cin % 64 || !x || !tensors || n_tensors <= 0 || !out || !guard ||
+        (dtype != VP_DTYPE_F16 && dtype != VP_DTYPE_BF16) || (size_t)B * Hin * Win > ((size_t)1 << 20))
+        return fail(nullptr, VP_ERR_INVALID, "bad head case");
+    if (stage >= 1 && (Kp <= 0 || Kp > 4096 || !w_fin || !b_fin)) return fail(nullptr, VP_ERR_INVALID, "head case: the final conv's Kp, w_fin and b_fin required");
+    if (stage == 2 && (Hin != 32 || Win != 24 || Cin != 256 || !mid || !mid_guard))
+        return fail(nullptr, VP_ERR_INVALID, "head case: the un-fused head is deconv2's geometry (32 x 24 x 256) and returns the 16-bit tensor too");
+    vp_ctx* c = dbg_ctx(device, dtype);
+    if (!c) return VP_ERR_HIP;
+    Lookup lk;
+    lk.c = c;
+    for (int i = 0; i < n_tensors; ++i) lk.map[tensors[i].name] = &tensors[i];
+    const size_t Min = (size_t)B * Hin * Win, opix = (size_t)4 * Hin * Win, G = 16 * opix;
+    const size_t act_n = Min * 4 * 256, hm_n = (size_t)B * (stage ? Kp : 0) * opix;
+    uint16_t *dx, *dw;
+    float* db;
+    char *d_act = nullptr, *d_hm = nullptr;
+    int rc;
+    if ((rc = pack_deconv(c, lk, 0, Cin, &dw, &db)) || (rc = upload_mat(c, &dx, x, Min, Cin, Min)) || (rc = dalloc(c, &c->zero, (size_t)256))) return dbg_finish(c, rc);
+    if (hipMemset(c->zero, 0, 512) != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, "memset"));
+    if (stage != 1 && ((rc = dalloc(c, &d_act, (act_n + G) * 2)) || hipMemset(d_act, 0xff, (act_n + G) * 2) != hipSuccess)) return dbg_finish(c, rc ? rc : fail(c, VP_ERR_HIP, "memset"));
+    if (stage >= 1) {
+        c->Kp = Kp;
+        if ((rc = upload_final(c, &c->w_fin, w_fin, Kp, 256, &c->fin_rows)) || (rc = upload_f32(c, &c->b_fin, b_fin, Kp, pad128(Kp))) || (rc = dalloc(c, &d_hm, (hm_n + G) * 4)))
+            return dbg_finish(c, rc);
+        if (hipMemset(d_hm, 0xff, (hm_n + G) * 4) != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, "memset"));
+    }
+    c->sw.deconv_parity_fast = parity_fast != 0;
+    const int epi = stage == 1 ? vp::EPI_DECONV_FINAL : vp::EPI_DECONV;
+    GemmPick pk = resolve_gemm(c->sw, VP_PROF_GEMM_DECONV, epi, (int)Min, 256, 4 * Cin);
+    if (variant >= 0) { pk = GemmPick{}; pk.variant = variant; }
+    const vp::GemmArgs g = gemm_args(c, VP_PROF_GEMM_DECONV, epi, pk, dx, dw, db, stage == 1 ? (void*)d_hm : (void*)d_act, nullptr, (int)Min, 256, 4 * Cin, 256, Hin, Win, Cin);
+    hipError_t e = vp::gemm_launch(c->dtype, epi, g, nullptr);
+    if (e == hipSuccess && stage == 2) {
+        const int M2 = B * 3072, N2 = (int)c->fin_rows;
+        const vp::GemmArgs h = gemm_args(c, VP_PROF_GEMM_FINAL, vp::EPI_HEATMAP, resolve_gemm(c->sw, VP_PROF_GEMM_FINAL, vp::EPI_HEATMAP, M2, N2, 256), (const uint16_t*)d_act,
+                                         c->w_fin, c->b_fin, d_hm, nullptr, M2, N2, 256, 0);
+        e = vp::gemm_launch(c->dtype, vp::EPI_HEATMAP, h, nullptr);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, std::string("head case: ") + hipGetErrorString(e)));
+    if (d_act) {
+        if ((rc = download16(c, (const uint16_t*)d_act, stage == 0 ? out : mid, act_n))) return dbg_finish(c, rc);
+        if (hipMemcpy(stage == 0 ? guard : mid_guard, d_act + act_n * 2, G * 2, hipMemcpyDeviceToHost) != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, "D2H"));
+    }
+    if (d_hm && (hipMemcpy(out, d_hm, hm_n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(guard, d_hm + hm_n * 4, G * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        return dbg_finish(c, fail(c, VP_ERR_HIP, "D2H"));
+    return dbg_finish(c, VP_OK);
+}
+
 // ---- production-configuration GEMM tap (tests/test_gpu_gemm_cfgs.py, tools/gemm8_check.py) ----
 
 // ONE launch of any production GEMM configuration on HOST fp32 data (tests/test_gpu_gemm_cfgs.py): operands are rounded to

@@ -12,8 +12,10 @@ static void note_kernel(vp_ctx* c, int fam, const char* desc) {
     if (desc[0] && c->kernel_desc[fam] != desc) c->kernel_desc[fam] = desc;
 }
 
-int gemm(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint16_t* A, const uint16_t* W, const float* bias, void* out,
-         const float* aux, int M, int N, int K, int ldo, int Hin, int Win, int Cin, const LnFuse* ln) {
+// the launch arguments of one 2-phase / 8-phase GEMM of the path as `pk` resolved it: everything gemm() hands to vp::gemm_launch but the kernel-name buffer
+// (also what vp_dbg_head_case launches, so that the tap cannot drift from the path)
+vp::GemmArgs gemm_args(const vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint16_t* A, const uint16_t* W, const float* bias, void* out,
+                       const float* aux, int M, int N, int K, int ldo, int Hin, int Win, int Cin, const LnFuse* ln) {
     vp::GemmArgs g{};
     g.A = A; g.W = W; g.bias = bias; g.out = out; g.aux = aux;
     g.M = M; g.N = N; g.K = K; g.ldo = ldo;
@@ -27,9 +29,15 @@ int gemm(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint16_t* A, con
         g.a_blocked = ln->a_blocked; g.out_blocked = ln->out_blocked; g.reverse = ln->reverse;
         g.plane = ln->plane; g.stats_out = ln->stats_out; g.rowstat = ln->rowstat; g.ln_s = ln->ln_s;
         g.ln_part = ln->ln_part; g.ln_tiles = ln->ln_tiles; g.ln_inv_d = 1.0f / (float)K;
-        if (ln->tiles_out) *ln->tiles_out = N / 64;   // partial statistics are written per 64 columns, whatever the tile
     }
     if (epi == vp::EPI_DECONV_FINAL) { g.W2 = c->w_fin; g.bias2 = c->b_fin; g.out2 = (float*)out; g.out = nullptr; }   // deconv2 + final 1x1 conv in one kernel: `out` = the heatmaps, nothing else is written
+    return g;
+}
+
+int gemm(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint16_t* A, const uint16_t* W, const float* bias, void* out,
+         const float* aux, int M, int N, int K, int ldo, int Hin, int Win, int Cin, const LnFuse* ln) {
+    vp::GemmArgs g = gemm_args(c, fam, epi, pk, A, W, bias, out, aux, M, N, K, ldo, Hin, Win, Cin, ln);
+    if (ln && ln->tiles_out) *ln->tiles_out = N / 64;   // partial statistics are written per 64 columns, whatever the tile
     const bool deconv = epi == vp::EPI_DECONV || epi == vp::EPI_DECONV_FINAL;
     const double par = deconv ? 4.0 : 1.0;
     const double Nalg = (epi == vp::EPI_HEATMAP) ? (double)c->Kp : (double)N;   // heatmap: N counts the hi + lo weight rows

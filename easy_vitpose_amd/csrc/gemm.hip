@@ -305,7 +305,9 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_kernel(GemmArgs g) {
         // tensor, 402 MB at batch 256, is never written or read) and a second small MFMA product with the hi + lo final-layer
         // weights (weights.hip upload_final: [16 hi rows][16 lo rows] groups) gives the heatmaps.  Arithmetic and
         // accumulation order are those of EPI_DECONV followed by EPI_HEATMAP (k ascending in steps of 32, hi and lo products
-        // in separate accumulators, hi + lo, + bias): bit-identical heatmaps -- tests/test_gpu_gemm_cfgs.py, test_gpu_api.py.
+        // in separate accumulators, hi + lo, + bias): bit-identical heatmaps -- tests/test_gpu_head.py::test_final_fused_is_the_two_launches (this kernel against the
+        // two launches on the same operands, Kp = 1, 16, 17, 25, 133, both types and parity orders, guard planes behind the output) and, through whole engines,
+        // tests/test_gpu_api.py::test_fused_head_is_bit_identical.
         static_assert(C::BN == 256 && C::BM % (C::NWAVES * 16) == 0, "the fused head needs all 256 channels in one tile");
         constexpr int RB = C::BN * 2 + 16;                 // staged row: 256 channels x 16 bit + 16 B (conflict-free fragment reads)
         constexpr int RPW = C::BM / C::NWAVES, JW = RPW / 16;   // rows / 16-row fragments of the second product per wave

@@ -733,6 +733,16 @@ VP_API int vp_dbg_layernorm(int32_t device_id, int32_t dtype, int32_t M, int32_t
  * x [B,Hin,Win,Cin] -> NHWC [B,2Hin,2Win,256]; tensors named keypoint_head.deconv_layers.{0,1}.* */
 VP_API int vp_dbg_deconv(int32_t device_id, int32_t dtype, int32_t B, int32_t Hin, int32_t Win, int32_t Cin,
                          const float* x, const vp_tensor_desc* tensors, int32_t n_tensors, float* out);
+/* ONE GEMM of the keypoint head on a chosen tile, launched with the arguments the forward builds for it (tests/test_gpu_head.py).  stage 0: deconv + BN + ReLU
+ * (x [B,Hin,Win,Cin] NHWC -> out [B,2Hin,2Win,256], 16-bit returned as fp32); stage 1: the same with the final 1x1 conv fused behind it (out = fp32 heatmaps
+ * [B,Kp,2Hin,2Win]); stage 2: the un-fused pair of launches on the same operands (mid = the 16-bit tensor, out = the heatmaps; 32 x 24 x 256 only).  variant = the
+ * deconv's tile (gemm.hip Cfg id; -1 = the selection rule's pick), parity_fast = 1 the product's launch order / 0 that of VP_DECONV_PARITY_FAST=0.  tensors as for
+ * vp_dbg_deconv; stages 1 / 2: w_fin [Kp,256], b_fin [Kp].  Every device output is filled with 0xFF bytes before the launch (an unwritten element returns as NaN)
+ * and followed by 16 * (4 Hin Win) guard elements, returned as bytes in guard (of out: 2 bytes per element at stage 0, else 4) and mid_guard (of mid, 2 bytes per
+ * element).  What the launcher refuses (a tile without a kernel for the epilogue, ...) comes back as an error, nothing is launched. */
+VP_API int vp_dbg_head_case(int32_t device_id, int32_t dtype, int32_t stage, int32_t variant, int32_t parity_fast, int32_t B, int32_t Hin, int32_t Win,
+                            int32_t Cin, const float* x, const vp_tensor_desc* tensors, int32_t n_tensors, int32_t Kp, const float* w_fin,
+                            const float* b_fin, float* out, uint8_t* guard, float* mid, uint8_t* mid_guard);
 /* the device crop / zero-pad / resize kernel alone: uint8 crops [n, 256, 192, 3] */
 VP_API int vp_dbg_crop_prep(int32_t device_id, const uint8_t* frame, int32_t fh, int32_t fw, const int32_t* crop_params,
                             int32_t n, uint8_t* out);
