@@ -44,7 +44,8 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_dbg_decode_affine_flip',
            'vp_draw_poses_stream', 'vp_draw_poses', 'vp_dbg_draw_host',
            'vp_tracker_create', 'vp_tracker_destroy', 'vp_tracker_reset_stream', 'vp_tracker_update_stream', 'vp_tracker_update', 'vp_tracker_state_bytes',
-           'vp_tracker_download_state', 'vp_dbg_track_host', 'vp_dbg_lsap',
+           'vp_tracker_download_state', 'vp_dbg_track_host', 'vp_dbg_lsap', 'vp_tracker_update_counted_stream',
+           'vp_detector_create', 'vp_detector_destroy', 'vp_detect_stream', 'vp_detect', 'vp_dbg_detect_host',
            'vp_smoother_create', 'vp_smoother_destroy', 'vp_smoother_reset_stream', 'vp_smooth_update_stream', 'vp_smooth_update', 'vp_smoother_state_bytes',
            'vp_smoother_download_state', 'vp_dbg_smooth_host',
            'vp_dbg_head_case']
@@ -91,6 +92,15 @@ class vp_draw_cfg(C.Structure):
 
 class vp_track_cfg(C.Structure):
     _fields_ = [('max_age', C.c_int32), ('min_hits', C.c_int32), ('iou_threshold', C.c_float), ('n_streams', C.c_int32)]
+
+
+class vp_det_cfg(C.Structure):
+    _fields_ = [('nc', C.c_int32), ('max_anchors', C.c_int32), ('max_images', C.c_int32), ('dtype', C.c_int32), ('layout', C.c_int32), ('conf_thr', C.c_float),
+                ('iou_thr', C.c_float), ('extent', C.c_float), ('agnostic', C.c_int32), ('max_det', C.c_int32), ('class_mask', C.c_uint32 * 8)]
+
+
+class vp_det_image(C.Structure):
+    _fields_ = [('gain', C.c_float), ('pad_x', C.c_float), ('pad_y', C.c_float), ('frame_w', C.c_float), ('frame_h', C.c_float)]
 
 
 class vp_smooth_cfg(C.Structure):
@@ -255,6 +265,14 @@ def load_library():
     lib.vp_tracker_download_state.argtypes = [C.c_void_p, C.c_void_p]
     lib.vp_dbg_track_host.argtypes = [C.c_void_p, C.POINTER(vp_track_cfg)] + trk_io
     lib.vp_dbg_lsap.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
+    lib.vp_tracker_update_counted_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    det_io = [C.c_void_p, C.c_int32, C.POINTER(vp_det_image), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.vp_detector_create.argtypes = [H, C.POINTER(vp_det_cfg), C.POINTER(C.c_void_p)]
+    lib.vp_detector_destroy.argtypes = [C.c_void_p]
+    lib.vp_detect_stream.argtypes = [C.c_void_p] + det_io + [C.c_void_p]
+    lib.vp_detect.argtypes = [C.c_void_p] + det_io
+    lib.vp_dbg_detect_host.argtypes = [C.POINTER(vp_det_cfg)] + det_io
     smooth_io = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vp_smoother_create.argtypes = [H, C.POINTER(vp_smooth_cfg), C.POINTER(C.c_void_p)]
     lib.vp_smoother_destroy.argtypes = [C.c_void_p]

@@ -11,6 +11,10 @@ pose path, track across frames (``is_video``), report FPS and write the ``--save
 
     python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --boxes boxes.json --output-path out --save-img        # the frames with the skeletons drawn on them, as PNG
 
+    python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --det-heads heads.npz --det-input 640 640                # the detector's raw heads: decode, filter and box NMS on the device
+
+``--det-heads`` (an ``.npz`` with the raw YOLOv8 head ``[4 + nc, A]`` of every frame, as an engine on the same GPU leaves it) replaces ``--yolo`` / ``--boxes``:
+the boxes then come from the detector stage (``devdetect``, ``VitInference(detect=)``); ``--det-input`` is the size the frames were letterboxed into.
 ``--save-img`` writes ``<stem>_<frame>.png`` per frame (``VitInference.draw``: skeletons drawn on the device, csrc/drawgeom.h; no text labels) into the
 ``--save-json`` directory; a dataset other than COCO-17 needs ``--skeleton FILE.json``.
 Not rebuilt (outside the hot path): preview windows (``--show``: OpenCV) and video
@@ -82,6 +86,29 @@ def smooth_argument(args):
     return SmoothCfg(**kw)
 
 
+def detect_argument(args):
+    """--det-heads FILE.npz / --det-input H W / --det-conf / --det-iou -> (the raw head of every frame, VitInference's detect=).  The file holds one array
+    [frames, 4 + nc, A], or one [4 + nc, A] array per frame (taken in the order of their names), float16 or float32, YOLOv8's export layout."""
+    from easy_vitpose_amd.devdetect import DetectCfg
+    with np.load(args.det_heads) as z:
+        arrays = [z[k] for k in sorted(z.files)]
+    heads = list(arrays[0]) if len(arrays) == 1 and arrays[0].ndim == 3 else arrays
+    if not heads or any(h.ndim != 2 or h.shape != heads[0].shape or h.dtype != heads[0].dtype for h in heads):
+        raise ValueError(f'{args.det_heads}: one [frames, 4 + nc, A] array or one [4 + nc, A] array per frame expected')
+    if heads[0].dtype not in (np.float16, np.float32) or heads[0].shape[0] < 5:
+        raise ValueError(f'{args.det_heads}: float16 or float32 heads of at least 5 channels expected, got {heads[0].dtype} {heads[0].shape}')
+    kw = {}
+    if args.det_conf is not None:
+        kw['conf_thr'] = args.det_conf
+    if args.det_iou is not None:
+        kw['iou_thr'] = args.det_iou
+    dataset = args.dataset or 'coco'
+    det_class = args.det_class or ('animals' if dataset in ('ap10k', 'apt36k') else 'human')
+    cfg = DetectCfg(nc=heads[0].shape[0] - 4, dtype='fp16' if heads[0].dtype == np.float16 else 'fp32', classes=det_class if heads[0].shape[0] - 4 == 80 else None,
+                    max_anchors=heads[0].shape[1], max_images=1, **kw)
+    return heads, cfg
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--input', required=True, help='image file, .npy frame stack, or directory of images')
@@ -90,6 +117,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--synthetic', default=None, choices=['s', 'b', 'l', 'h'], help='seeded peaked synthetic checkpoint of this size instead of --model')
     ap.add_argument('--yolo', default=None, help='ultralytics detector weights')
     ap.add_argument('--boxes', default=None, help='JSON file with detector boxes (replaces --yolo)')
+    ap.add_argument('--det-heads', default=None, metavar='FILE.npz', help='the detector\'s RAW head of every frame ([4 + nc, A], YOLOv8\'s export) instead of --yolo / '
+                    '--boxes: best class, confidence threshold, class filter (--det-class; heads of 80 classes) and box NMS run on the device (devdetect)')
+    ap.add_argument('--det-input', type=int, nargs=2, default=[640, 640], metavar=('H', 'W'), help='--det-heads: the detector input the frames were letterboxed into')
+    ap.add_argument('--det-conf', type=float, default=None, help='--det-heads: confidence threshold (default 0.35, the reference\'s)')
+    ap.add_argument('--det-iou', type=float, default=None, help='--det-heads: IoU threshold of the box NMS (default 0.7, ultralytics\')')
     ap.add_argument('--dataset', default=None, help='dataset of the checkpoint (default: from the --model file name); required for a ViTPose+ '
                     'checkpoint, whose six datasets are coco, aic, mpii, ap10k, apt36k, wholebody')
     ap.add_argument('--det-class', default=None)
@@ -155,7 +187,17 @@ def main(argv=None) -> int:
             b = boxes[min(state['i'], len(boxes) - 1)] if per_frame else boxes
             state['i'] += 1
             return np.asarray(b, dtype=np.float64).reshape(-1, 5)
-    assert detector is not None, 'give --yolo (ultralytics weights) or --boxes'
+    detect = None
+    if args.det_heads is not None:
+        assert args.yolo is None and args.boxes is None, '--det-heads replaces --yolo / --boxes'
+        heads, detect = detect_argument(args)
+        state = {'i': 0}
+
+        def detector(img):   # noqa: F811 -- the raw head of every detector frame, in order (the last one again beyond the file)
+            h = heads[min(state['i'], len(heads) - 1)]
+            state['i'] += 1
+            return h, tuple(args.det_input)
+    assert detector is not None, 'give --yolo (ultralytics weights), --boxes or --det-heads'
 
     skeleton = None
     if args.skeleton is not None:
@@ -170,7 +212,7 @@ def main(argv=None) -> int:
                          yolo_step=args.yolo_step, dtype=args.dtype, max_batch=args.max_batch,
                          flip_test=flip_test_argument(args), shift_heatmap=args.shift_heatmap, pose_nms=pose_nms_argument(args),
                          crop=args.crop, box_scale=args.box_scale, skeleton=skeleton, tracker='device' if args.tracker == 'device' else None,
-                         smooth=smooth_argument(args))
+                         smooth=smooth_argument(args), detect=detect)
     print(f'>>> Model loaded: {args.model or "synthetic ViTPose-" + args.synthetic.upper()}')
     print(f'>>> Running inference on {args.input}')
     base = os.path.basename(args.input.rstrip('/'))

@@ -1,6 +1,6 @@
 // vp_tracker_*: the box tracker (SORT) as a stream-ordered device stage in front of the boxes entry (semantics: sortgeom.h), its synchronous host twin
 // vp_tracker_update and the two taps vp_dbg_track_host / vp_dbg_lsap.  Two launches per call: track_update_kernel, one workgroup per stepped stream, and
-// track_gather_kernel, one workgroup.  No atomics, no flags between workgroups, every reduction in a fixed order: a call is bit-identical from run to run.
+// track_gather_kernel, one workgroup.  vp_tracker_update_counted_stream is the same call with the detection count read from device memory.  No atomics, no flags between workgroups, every reduction in a fixed order: a call is bit-identical from run to run.
 #include "api_internal.h"
 #include "sortgeom.h"
 
@@ -126,9 +126,14 @@ __device__ inline void associate_lanes(TrkLds& L, int nr, int nc, double thr) {
 }
 
 __global__ __launch_bounds__(TRK_THREADS) void track_update_kernel(TrkStream* __restrict__ state, TrkParams p, const float* __restrict__ dets, int row_stride,
-                                                                   const int32_t* __restrict__ fidx, int n_dets, unsigned long long step_mask) {
+                                                                   const int32_t* __restrict__ fidx, int n_dets, const int32_t* __restrict__ d_n_dets,
+                                                                   unsigned long long step_mask) {
     __shared__ TrkLds L;
     const int tid = threadIdx.x;
+    if (d_n_dets) {   // the counted entry: the rows of this call are the first min(*d_n_dets, n_dets); the others are never read
+        const int m = *d_n_dets;
+        n_dets = m < 0 ? 0 : (m < n_dets ? m : n_dets);
+    }
     int s = -1;   // the blockIdx.x-th stream of the mask
     for (int b = 0, k = -1; b < TRK_MAX_STREAMS; ++b)
         if ((step_mask >> b) & 1ull) {
@@ -545,14 +550,14 @@ int update_args(const vp::TrkParams& p, const void* dets, int row_stride, int n_
 int popcount64(uint64_t m) { int n = 0; for (; m; m &= m - 1) ++n; return n; }
 
 // the checked call on stream s: two launches
-int update_enqueue(vp_tracker* t, const float* d_dets, int row_stride, const int32_t* d_fidx, int n_dets, uint64_t step_mask, float* d_rows, int32_t* d_ids,
-                   int32_t* d_stream, int n_out, int32_t* d_count, int32_t* d_flags, hipStream_t s) {
+int update_enqueue(vp_tracker* t, const float* d_dets, int row_stride, const int32_t* d_fidx, int n_dets, const int32_t* d_n_dets, uint64_t step_mask, float* d_rows,
+                   int32_t* d_ids, int32_t* d_stream, int n_out, int32_t* d_count, int32_t* d_flags, hipStream_t s) {
     vp_ctx* c = t->c;
     HIPCHK(c, hipSetDevice(c->cfg.device_id));
     const int blocks = popcount64(step_mask);
     if (blocks > 0) {
         hipLaunchKernelGGL(vp::track_update_kernel, dim3(blocks), dim3(vp::TRK_THREADS), 0, s, t->state, t->p, d_dets, row_stride, d_fidx, n_dets,
-                           (unsigned long long)step_mask);
+                           d_n_dets, (unsigned long long)step_mask);
         HIPCHK(c, hipGetLastError());
     }
     hipLaunchKernelGGL(vp::track_gather_kernel, dim3(1), dim3(vp::GATHER_THREADS), 0, s, t->state, t->p.n_streams, (unsigned long long)step_mask, d_rows, d_ids, d_stream,
@@ -612,7 +617,17 @@ int vp_tracker_update_stream(vp_tracker_handle t, const float* d_dets, int32_t r
     if (!t) return VP_ERR_INVALID;
     std::string why;
     if (update_args(t->p, d_dets, row_stride, n_dets, step_mask, d_rows, d_ids, d_stream, n_out, d_count, &why)) return fail(t->c, VP_ERR_INVALID, why);
-    return update_enqueue(t, d_dets, row_stride, d_frame_idx, n_dets, step_mask, d_rows, d_ids, d_stream, n_out, d_count, d_flags, (hipStream_t)caller_stream);
+    return update_enqueue(t, d_dets, row_stride, d_frame_idx, n_dets, nullptr, step_mask, d_rows, d_ids, d_stream, n_out, d_count, d_flags, (hipStream_t)caller_stream);
+}
+
+int vp_tracker_update_counted_stream(vp_tracker_handle t, const float* d_dets, int32_t row_stride, const int32_t* d_frame_idx, int32_t n_dets_cap, const int32_t* d_n_dets,
+                                     uint64_t step_mask, float* d_rows, int32_t* d_ids, int32_t* d_stream, int32_t n_out, int32_t* d_count, int32_t* d_flags,
+                                     void* caller_stream) {
+    if (!t) return VP_ERR_INVALID;
+    std::string why;
+    if (!d_n_dets) return fail(t->c, VP_ERR_INVALID, "tracker: null d_n_dets");
+    if (update_args(t->p, d_dets, row_stride, n_dets_cap, step_mask, d_rows, d_ids, d_stream, n_out, d_count, &why)) return fail(t->c, VP_ERR_INVALID, why);
+    return update_enqueue(t, d_dets, row_stride, d_frame_idx, n_dets_cap, d_n_dets, step_mask, d_rows, d_ids, d_stream, n_out, d_count, d_flags, (hipStream_t)caller_stream);
 }
 
 int vp_tracker_update(vp_tracker_handle t, const float* dets, int32_t row_stride, const int32_t* frame_idx, int32_t n_dets, uint64_t step_mask, float* rows, int32_t* ids,
@@ -641,7 +656,7 @@ int vp_tracker_update(vp_tracker_handle t, const float* dets, int32_t row_stride
     auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
     if (n_dets) chk(hipMemcpyAsync(d_det, dets, ((size_t)(n_dets - 1) * row_stride + 5) * 4, hipMemcpyHostToDevice, s), "upload detections");
     if (n_dets && frame_idx) chk(hipMemcpyAsync(d_fi, frame_idx, (size_t)n_dets * 4, hipMemcpyHostToDevice, s), "upload frame index");
-    if (!rc) rc = update_enqueue(t, n_dets ? d_det : nullptr, row_stride, n_dets && frame_idx ? d_fi : nullptr, n_dets, step_mask, d_rows, d_ids, d_st, n_out, d_ct, d_fl, s);
+    if (!rc) rc = update_enqueue(t, n_dets ? d_det : nullptr, row_stride, n_dets && frame_idx ? d_fi : nullptr, n_dets, nullptr, step_mask, d_rows, d_ids, d_st, n_out, d_ct, d_fl, s);
     if (!rc) {
         if (n_out) {
             chk(hipMemcpyAsync(rows, d_rows, (size_t)n_out * 24, hipMemcpyDeviceToHost, s), "download rows");

@@ -176,11 +176,13 @@ class DeviceTracker:
         reports its listed tracks, and rows beyond `n_dets` are cut under flag 4."""
         return self._bound.bound(n_dets, bin(mask_of(step, self.cfg.n_streams)).count('1'))
 
-    def update(self, dets, frame_index=None, n_out=None, step=None):
+    def update(self, dets, frame_index=None, n_out=None, step=None, n_dets=None):
         """One step of the streams in `step` (None: all) on torch's current stream, no synchronisation.  `dets`: float32 CUDA [n, >= 5] rows
         (x1, y1, x2, y2, score, ...), row-contiguous; `frame_index`: int32 CUDA [n] (None: stream 0).  Returns (rows float32 [n_out, 6], ids int32 [n_out],
         stream int32 [n_out], count int32 [n_streams + 1], flags int32 [n_streams]) device tensors; n_out defaults to `row_bound(n, step)` (see there for the one
-        input it does not cover: a one-stream call whose rows are ALL non-finite).  Every call is recorded for the bound, with or without an `n_out`."""
+        input it does not cover: a one-stream call whose rows are ALL non-finite).  Every call is recorded for the bound, with or without an `n_out`.
+        `n_dets`: an int32 CUDA tensor of one element, the detection count decided on the device (vp_tracker_update_counted_stream): only the first
+        min(n_dets, n) rows are read -- the detector stage's rows, image and count[-1:] pass in place; the bound is recorded with n."""
         import torch
         dev = torch.device('cuda', self.engine.device_id)
         if not (isinstance(dets, torch.Tensor) and dets.is_cuda and dets.dtype == torch.float32):
@@ -204,9 +206,16 @@ class DeviceTracker:
         count = torch.empty((ns + 1,), dtype=torch.int32, device=dev)
         flags = torch.empty((ns,), dtype=torch.int32, device=dev)
         cs = torch.cuda.current_stream(dev).cuda_stream
-        capi.check(self.lib.vp_tracker_update_stream(self._t, dets.data_ptr() if n else None, dets.stride(0) if n > 1 else max(dets.shape[1], 5),
-                                                     None if frame_index is None or n == 0 else frame_index.data_ptr(), n, mask, rows.data_ptr(), ids.data_ptr(),
-                                                     stream.data_ptr(), n_out, count.data_ptr(), flags.data_ptr(), cs), self.engine._h)
+        io = (dets.data_ptr() if n else None, dets.stride(0) if n > 1 else max(dets.shape[1], 5), None if frame_index is None or n == 0 else frame_index.data_ptr(), n)
+        out = (mask, rows.data_ptr(), ids.data_ptr(), stream.data_ptr(), n_out, count.data_ptr(), flags.data_ptr(), cs)
+        if n_dets is None:
+            capi.check(self.lib.vp_tracker_update_stream(self._t, *io, *out), self.engine._h)
+        else:
+            if not (isinstance(n_dets, torch.Tensor) and n_dets.is_cuda and n_dets.dtype == torch.int32):
+                raise TypeError('n_dets: an int32 torch CUDA tensor expected')
+            if n_dets.device != dev or n_dets.numel() != 1:
+                raise ValueError(f'n_dets: one element on {dev} expected')
+            capi.check(self.lib.vp_tracker_update_counted_stream(self._t, *io, n_dets.data_ptr(), *out), self.engine._h)
         self._bound.push(n, bin(mask).count('1'))
         return rows, ids, stream, count, flags
 

@@ -581,6 +581,12 @@ class VitPoseHip:
         from .devtracker import DeviceTracker, TrackCfg
         return DeviceTracker(self, TrackCfg() if cfg is None else cfg)
 
+    def detector(self, cfg=None):
+        """A detector stage on this handle's device (devdetect.DeviceDetector over vp_detect_*): a detector's raw head to box rows, the stream-ordered stage in
+        front of `tracker().update(rows, image, n_dets=count[-1:])`."""
+        from .devdetect import DetectCfg, DeviceDetector
+        return DeviceDetector(self, DetectCfg() if cfg is None else cfg)
+
     def smoother(self, cfg=None):
         """A keypoint smoother for this handle's K joints on its device (devsmooth.DeviceSmoother over vp_smooth_*): the stream-ordered One-Euro stage behind
         `infer_boxes` (and its NMS), keyed by the tracker's (stream, id), in front of `draw_poses`."""

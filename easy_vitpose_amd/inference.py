@@ -14,7 +14,9 @@ crop (:259-272) becomes ONE batched call into the C ABI (``_inference_batch``);
 
 Out of scope here (SURVEY.md section 2 / 8f): the YOLO detector is third-party;
 ``yolo`` may be a path (needs ``ultralytics``) or any callable
-``img_rgb -> ndarray[n, 5] (x1, y1, x2, y2, conf)``.  The SORT tracker is ``tracker.Sort``
+``img_rgb -> ndarray[n, 5] (x1, y1, x2, y2, conf)``.  With ``detect=`` (keyword, a ``devdetect.DetectCfg``) the
+callable returns ``(raw head [4 + nc, A], (in_h, in_w))`` instead and the detector stage (vp_detect: best class, threshold,
+class filter, box NMS, letterbox undone) makes the boxes on the device.  The SORT tracker is ``tracker.Sort``
 on the host by default, ``tracker='device'`` selects the device tracker
 (``devtracker.DeviceSort``, vp_tracker_update), and a factory of any object with the
 SORT ``update`` interface is taken as it is.
@@ -79,7 +81,7 @@ class VitInference:
                  single_pose: Optional[bool] = False,
                  yolo_step: Optional[int] = 1,
                  *, dtype: str = 'fp16', max_batch: int = 64, tracker=None, flip_test=None, shift_heatmap: bool = False,
-                 pose_nms: Optional[PoseNms] = None, crop: str = 'pad', box_scale: float = 1.25, skeleton=None, smooth=None):
+                 pose_nms: Optional[PoseNms] = None, crop: str = 'pad', box_scale: float = 1.25, skeleton=None, smooth=None, detect=None):
         # crop='affine': the training-protocol crop (cropprep.box_to_cs, VitPoseHip.infer_frames(crop='affine')) instead of the pad route; refused before anything is loaded
         if crop not in ('pad', 'affine'):
             raise ValueError(f"crop: 'pad' or 'affine' expected, got {crop!r}")
@@ -93,6 +95,11 @@ class VitInference:
             raise TypeError(f'smooth: None, True or a SmoothCfg expected, got {smooth!r}')
         self._smooth_cfg = SmoothCfg() if smooth is True else (smooth or None)
         self._smoother = None
+        # detect: the detector stage (devdetect.DetectCfg): `yolo(img)` then returns (raw head, (in_h, in_w)) and the box rows come from vp_detect; refused before anything is loaded
+        from .devdetect import DetectCfg
+        if not (detect is None or isinstance(detect, DetectCfg)):
+            raise TypeError(f'detect: None or a DetectCfg expected, got {detect!r}')
+        self._detect_cfg, self._detector = detect, None
         if not (np.isfinite(box_scale) and box_scale > 0):
             raise ValueError(f'box_scale must be finite and > 0, got {box_scale!r}')
         self.crop, self.box_scale = crop, float(box_scale)
@@ -179,6 +186,8 @@ class VitInference:
                                     dtype=dtype, device_id=dev_id, max_batch=max_batch, dataset=dataset if plus else None)
         if flip_pairs is not None:   # a mode of the handle: every call below (inference, inference_frames, the boxes route) inherits it
             self._vit_pose.set_flip_test(flip_pairs, shift_heatmap)
+        if self._detect_cfg is not None:
+            self._detector = self._vit_pose.detector(dataclasses.replace(self._detect_cfg, max_images=1))
         if tracker == 'device' or self._smooth_cfg is not None:   # the device tracker and the smoother live on the engine's device: built now that there is one
             self.reset()
         self._inference = self._inference_hip
@@ -226,6 +235,13 @@ class VitInference:
         if use_tracker and getattr(self, '_smooth_cfg', None) is not None and getattr(self, '_vit_pose', None) is not None:
             self._smoother = self._vit_pose.smoother(self._smooth_cfg)
         self.frame_counter = 0
+
+    def _detect_rows(self, img, head, input_hw):
+        """VitInference(detect=): the detector's raw head of one frame ([4 + nc, A], or [A, 4 + nc] under layout 1, with or without a leading 1) through the detector
+        stage's synchronous twin (vp_detect): the [m, 5] rows (x1, y1, x2, y2, score) in frame pixels.  Every row is over DetectCfg.conf_thr already."""
+        head = np.asarray(head)
+        rows, _, _, count, _ = self._detector.detect_host(head.reshape((1,) + head.shape[-2:]), img.shape[:2], input_hw)
+        return rows[:int(count[-1]), :5]
 
     def _smooth_results(self, results):
         """VitInference(smooth=): the keypoints of every person of every frame, in frame order, through the smoother's synchronous twin (vp_smooth_update), keyed by
@@ -286,7 +302,8 @@ class VitInference:
         for img in imgs:
             res_pd = np.empty((0, 5))
             if (self.tracker is None or (self.frame_counter % self.yolo_step == 0 or self.frame_counter < 3)):
-                det = np.asarray(self.yolo(img), dtype=np.float64).reshape((-1, 5))
+                det = self.yolo(img) if self._detector is None else self._detect_rows(img, *self.yolo(img))
+                det = np.asarray(det, dtype=np.float64).reshape((-1, 5))
                 res_pd = det[det[:, 4] > 0.35].reshape((-1, 5))
             self.frame_counter += 1
 

@@ -591,6 +591,73 @@ VP_API int vp_dbg_track_host(void* state, const vp_track_cfg* cfg, const float* 
 /* The association alone on iou [nd, nt] fp64 (host pointers, nd, nt <= VP_TRACK_MAX): trk_of_det [nd] = the track paired with every detection or -1, shortcut,
  * assignment and threshold filter included.  device_id = -1: on the host, no device needed; a device runs the tracker kernel's association (one column per lane). */
 VP_API int vp_dbg_lsap(int32_t device_id, const double* iou, int32_t nd, int32_t nt, float thr, int32_t* trk_of_det);
+/* vp_tracker_update_stream with the detection count in device memory: the rows of the call are the first min(*d_n_dets, n_dets_cap) (a negative count: none); rows
+ * from there on are never read, so they may hold anything (NaN, streams outside the table) and raise no flag.  The detector stage's d_rows, d_image and
+ * d_count + n_images pass in place.  The same kernels: vp_tracker_update_stream is the d_n_dets == NULL case, bit for bit.  VP_ERR_INVALID for a NULL d_n_dets
+ * and for everything vp_tracker_update_stream refuses (n_dets_cap in the place of n_dets). */
+VP_API int vp_tracker_update_counted_stream(vp_tracker_handle t, const float* d_dets, int32_t row_stride, const int32_t* d_frame_idx, int32_t n_dets_cap,
+                                            const int32_t* d_n_dets, uint64_t step_mask, float* d_rows, int32_t* d_ids, int32_t* d_stream, int32_t n_out,
+                                            int32_t* d_count, int32_t* d_flags, void* caller_stream);
+
+/* The detector stage, IN FRONT of the tracker: a detector's raw head tensor, left in device memory by an engine on the same GPU, to the [n, 6] box rows every entry
+ * above takes in place -- best-class pick, confidence threshold, class filter, greedy box NMS, letterbox undone (the reference's YOLOv8 post-processing behind
+ * inference.py:240-241; csrc/detgeom.h states the arithmetic once for the kernels and the host tap).  The detector network itself and the letterboxing of the frame
+ * into its input are not this library's: the stage takes the letterbox geometry as numbers.  Up to VP_DET_MAX_IMAGES images per call; the image index is the
+ * tracker's stream.  Everything is float32, nothing contracted, division correctly rounded.
+ *   d_pred: the head, contiguous, float32 (VP_DET_F32) or float16 (VP_DET_F16, widened exactly); layout 0 = [n_images, 4 + nc, A] (YOLOv8's export), layout 1 =
+ *   [n_images, A, 4 + nc].  Channels 0..3 = (cx, cy, w, h) in detector-input pixels, channels 4.. = class scores, already sigmoided.
+ *   Per anchor: best = the first class of the strictly largest score (a NaN never wins; all NaN: no candidate).  The anchor is a CANDIDATE iff score > conf_thr,
+ *   bit `best` of class_mask is set (the filter comes after the arg-max over ALL classes, as in ultralytics' non_max_suppression: a box that a masked class
+ *   out-scores is no candidate) and cx, cy, w, h are finite; one that passes score and class with a box that is not finite is skipped and raises flag 8.
+ *   Box: x1 = cx - w * 0.5f, x2 = cx + w * 0.5f, likewise y.  Order: score descending, equal scores by anchor ascending.
+ *   Greedy NMS on those input-space boxes: side = (x2 - x1) + extent, area = side_x * side_y, iw = max(0, (min(x2a, x2b) - max(x1a, x1b)) + extent), likewise ih,
+ *   iou = iw * ih / ((area_a + area_b) - iw * ih).  Walking the order, a live candidate is picked and suppresses every later live b with !(iou <= iou_thr) (the
+ *   reference's keep rule `ovr <= thr`: a NaN suppresses); with agnostic = 0 only candidates of the same class suppress each other (no coordinate offset).  At most
+ *   max_det picks.  extent = 0: the continuous convention (ultralytics, torchvision), 1: the pixel convention of the reference's post_processing/nms.py.
+ *   The picks go to frame pixels: v = (v - pad) / gain, then min(max(v, 0), frame side), per image from the host table `images`.
+ *   An image with more than VP_DET_MAX_CAND candidates is not processed: zero rows and flag 1 (so the result never depends on the order workgroups run in).
+ *   Output: d_rows float32 [n_out, 6] = (x1, y1, x2, y2, score, class); d_image, d_anchor int32 [n_out]; images ascending, pick order within an image.  Rows beyond
+ *   the total are "absent" as the tracker's: box NaN, score 0, class -1, image -1, anchor -1.  d_count int32 [n_images + 1]: rows per image, last = the true total
+ *   whatever n_out.  d_flags (may be NULL) int32 [n_images]: 1 more than VP_DET_MAX_CAND candidates; 4 rows of this image cut by n_out; 8 a box that is not finite
+ *   was skipped.
+ * vp_detect_stream only enqueues on caller_stream (three kernels: the scan over anchor tiles x images, the NMS with one workgroup per image, a pack kernel with one thread per
+ * output row; configuration and image table travel by kernel argument; the NMS kernel re-zeroes the counters, so back-to-back calls and captured graphs work): no
+ * synchronisation, no copy from host memory, no allocation -- the detector object owns the candidate workspace.  Calls on one detector from different streams are the
+ * caller's to order.  n_images = 0 is legal.
+ * VP_ERR_INVALID before anything is enqueued: a NULL cfg / d_count, NULL d_pred / images with n_images > 0, NULL d_rows / d_image / d_anchor with n_out > 0, nc
+ * outside 1..VP_DET_MAX_CLASSES, max_anchors outside 1..2^20, max_images outside 1..VP_DET_MAX_IMAGES, an unknown dtype or layout, conf_thr not finite or < 0,
+ * iou_thr outside [0, 1], extent not finite or < 0, agnostic not 0 / 1, max_det outside 1..VP_DET_MAX_DET, a class_mask without a class below nc, A outside
+ * 1..max_anchors, n_images outside 0..max_images, n_out < 0, d_pred not aligned to its element, an image whose gain is not finite and > 0, whose pad is not
+ * finite or whose frame size is not finite and >= 0.
+ * vp_detect: the synchronous twin on host pointers (upload, the same kernels, download).  vp_detector_create: on the device of h; the detector must be destroyed
+ * before h.  Library builds that carry the stage define VP_HAS_DETECT. */
+#define VP_HAS_DETECT 1
+#define VP_DET_MAX_IMAGES 64
+#define VP_DET_MAX_CLASSES 256
+#define VP_DET_MAX_CAND 2048
+#define VP_DET_MAX_DET 1024
+#define VP_DET_F32 0
+#define VP_DET_F16 1
+typedef struct vp_det_cfg {
+    int32_t  nc, max_anchors, max_images, dtype, layout;
+    float    conf_thr, iou_thr, extent;
+    int32_t  agnostic, max_det;
+    uint32_t class_mask[8];   /* bit c of word c / 32: class c passes */
+} vp_det_cfg;
+typedef struct vp_det_image {
+    float gain, pad_x, pad_y, frame_w, frame_h;
+} vp_det_image;
+typedef struct vp_detector* vp_detector_handle;
+VP_API int vp_detector_create(vp_handle h, const vp_det_cfg* cfg, vp_detector_handle* out);
+VP_API int vp_detector_destroy(vp_detector_handle d);
+VP_API int vp_detect_stream(vp_detector_handle d, const void* d_pred, int32_t A, const vp_det_image* images, int32_t n_images, float* d_rows, int32_t* d_image,
+                            int32_t* d_anchor, int32_t n_out, int32_t* d_count, int32_t* d_flags, void* caller_stream);
+VP_API int vp_detect(vp_detector_handle d, const void* pred, int32_t A, const vp_det_image* images, int32_t n_images, float* rows, int32_t* image, int32_t* anchor,
+                     int32_t n_out, int32_t* count, int32_t* flags);
+/* HOST ONLY, no device needed: csrc/detgeom.h run serially, the model the device is tested against (a test tap, never a fallback); the refusals of
+ * vp_detector_create and vp_detect_stream, the reason in vp_last_error(NULL). */
+VP_API int vp_dbg_detect_host(const vp_det_cfg* cfg, const void* pred, int32_t A, const vp_det_image* images, int32_t n_images, float* rows, int32_t* image,
+                              int32_t* anchor, int32_t n_out, int32_t* count, int32_t* flags);
 
 /* Keypoint smoothing on the device, the stage BEHIND a boxes entry (and its NMS) and in front of vp_draw_poses_stream: the One-Euro filter of the reference's
  * post_processing/one_euro_filter.py in its fixed-rate mode, one filter per (stream, track id) (csrc/eurogeom.h states the arithmetic once for the kernels and the
