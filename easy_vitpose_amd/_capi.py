@@ -46,6 +46,7 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_tracker_create', 'vp_tracker_destroy', 'vp_tracker_reset_stream', 'vp_tracker_update_stream', 'vp_tracker_update', 'vp_tracker_state_bytes',
            'vp_tracker_download_state', 'vp_dbg_track_host', 'vp_dbg_lsap', 'vp_tracker_update_counted_stream',
            'vp_detector_create', 'vp_detector_destroy', 'vp_detect_stream', 'vp_detect', 'vp_dbg_detect_host',
+           'vp_letterbox_plan', 'vp_letterbox_stream', 'vp_letterbox', 'vp_dbg_letterbox_host',
            'vp_smoother_create', 'vp_smoother_destroy', 'vp_smoother_reset_stream', 'vp_smooth_update_stream', 'vp_smooth_update', 'vp_smoother_state_bytes',
            'vp_smoother_download_state', 'vp_dbg_smooth_host',
            'vp_dbg_head_case']
@@ -101,6 +102,11 @@ class vp_det_cfg(C.Structure):
 
 class vp_det_image(C.Structure):
     _fields_ = [('gain', C.c_float), ('pad_x', C.c_float), ('pad_y', C.c_float), ('frame_w', C.c_float), ('frame_h', C.c_float)]
+
+
+class vp_letterbox_cfg(C.Structure):
+    _fields_ = [('in_h', C.c_int32), ('in_w', C.c_int32), ('dtype', C.c_int32), ('layout', C.c_int32), ('order', C.c_int32), ('pad_value', C.c_int32),
+                ('scaleup', C.c_int32)]
 
 
 class vp_smooth_cfg(C.Structure):
@@ -273,6 +279,12 @@ def load_library():
     lib.vp_detect_stream.argtypes = [C.c_void_p] + det_io + [C.c_void_p]
     lib.vp_detect.argtypes = [C.c_void_p] + det_io
     lib.vp_dbg_detect_host.argtypes = [C.POINTER(vp_det_cfg)] + det_io
+    lb_io = [C.POINTER(vp_letterbox_cfg), C.POINTER(vp_image), C.c_int32]
+    lb_tabs = [C.POINTER(vp_det_image), C.c_void_p]
+    lib.vp_letterbox_plan.argtypes = lb_io + lb_tabs
+    lib.vp_letterbox_stream.argtypes = [H] + lb_io + [C.c_void_p] + lb_tabs + [C.c_void_p]
+    lib.vp_letterbox.argtypes = [H] + lb_io + [C.c_void_p] + lb_tabs
+    lib.vp_dbg_letterbox_host.argtypes = lb_io + [C.c_void_p] + lb_tabs
     smooth_io = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vp_smoother_create.argtypes = [H, C.POINTER(vp_smooth_cfg), C.POINTER(C.c_void_p)]
     lib.vp_smoother_destroy.argtypes = [C.c_void_p]

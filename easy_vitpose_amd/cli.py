@@ -13,6 +13,12 @@ pose path, track across frames (``is_video``), report FPS and write the ``--save
 
     python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --det-heads heads.npz --det-input 640 640                # the detector's raw heads: decode, filter and box NMS on the device
 
+    python -m easy_vitpose_amd.cli --input clip.npy --synthetic b --det-engine mypkg.engine:make --det-input 640 640          # a detector engine on the same GPU
+
+``--det-engine MODULE:FACTORY`` imports ``FACTORY`` from ``MODULE`` and calls it once: it returns the callable that takes the letterboxed device tensor
+``[1, 3, H, W]`` (the letterbox stage, ``devletterbox``: ``--det-input``, fp16 unless ``--det-input-dtype`` says otherwise) and returns the raw head, a device
+tensor or an ndarray.  The callable may carry ``nc`` (classes of its head, default 80) and ``head_dtype`` ('fp16' / 'fp32', default: fp32 for an fp32 input, else
+fp16).  It is refused together with ``--yolo`` / ``--boxes`` / ``--det-heads``.
 ``--det-heads`` (an ``.npz`` with the raw YOLOv8 head ``[4 + nc, A]`` of every frame, as an engine on the same GPU leaves it) replaces ``--yolo`` / ``--boxes``:
 the boxes then come from the detector stage (``devdetect``, ``VitInference(detect=)``); ``--det-input`` is the size the frames were letterboxed into.
 ``--save-img`` writes ``<stem>_<frame>.png`` per frame (``VitInference.draw``: skeletons drawn on the device, csrc/drawgeom.h; no text labels) into the
@@ -109,6 +115,32 @@ def detect_argument(args):
     return heads, cfg
 
 
+def det_engine_argument(args):
+    """--det-engine MODULE:FACTORY / --det-input H W / --det-input-dtype / --det-conf / --det-iou -> (the engine callable, VitInference's detect=, its letterbox=)"""
+    import importlib
+    from easy_vitpose_amd.devdetect import DetectCfg
+    from easy_vitpose_amd.devletterbox import LetterboxCfg
+    if args.yolo is not None or args.boxes is not None or args.det_heads is not None:
+        raise ValueError('--det-engine replaces --yolo / --boxes / --det-heads')
+    module, sep, factory = args.det_engine.partition(':')
+    if not (module and sep and factory):
+        raise ValueError(f'--det-engine: MODULE:FACTORY expected, got {args.det_engine!r}')
+    engine = getattr(importlib.import_module(module), factory)()
+    if not callable(engine):
+        raise TypeError(f'--det-engine: {args.det_engine} returned {type(engine).__name__}, not a callable')
+    letterbox = LetterboxCfg(tuple(args.det_input), dtype=args.det_input_dtype or 'fp16')
+    kw = {}
+    if args.det_conf is not None:
+        kw['conf_thr'] = args.det_conf
+    if args.det_iou is not None:
+        kw['iou_thr'] = args.det_iou
+    nc = int(getattr(engine, 'nc', 80))
+    dataset = args.dataset or 'coco'
+    det_class = args.det_class or ('animals' if dataset in ('ap10k', 'apt36k') else 'human')
+    detect = DetectCfg(nc=nc, dtype=getattr(engine, 'head_dtype', 'fp32' if letterbox.dtype == 'fp32' else 'fp16'), classes=det_class if nc == 80 else None, max_images=1, **kw)
+    return engine, detect, letterbox
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--input', required=True, help='image file, .npy frame stack, or directory of images')
@@ -120,6 +152,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--det-heads', default=None, metavar='FILE.npz', help='the detector\'s RAW head of every frame ([4 + nc, A], YOLOv8\'s export) instead of --yolo / '
                     '--boxes: best class, confidence threshold, class filter (--det-class; heads of 80 classes) and box NMS run on the device (devdetect)')
     ap.add_argument('--det-input', type=int, nargs=2, default=[640, 640], metavar=('H', 'W'), help='--det-heads: the detector input the frames were letterboxed into')
+    ap.add_argument('--det-engine', default=None, metavar='MODULE:FACTORY', help='a detector engine on the same GPU instead of --yolo / --boxes / --det-heads: FACTORY() '
+                    'returns the callable that takes the letterboxed device tensor [1, 3, H, W] (--det-input; the letterbox stage, devletterbox) and returns the raw head')
+    ap.add_argument('--det-input-dtype', default=None, choices=['fp16', 'fp32', 'u8'], help='--det-engine: the dtype of the letterboxed tensor (default fp16)')
     ap.add_argument('--det-conf', type=float, default=None, help='--det-heads: confidence threshold (default 0.35, the reference\'s)')
     ap.add_argument('--det-iou', type=float, default=None, help='--det-heads: IoU threshold of the box NMS (default 0.7, ultralytics\')')
     ap.add_argument('--dataset', default=None, help='dataset of the checkpoint (default: from the --model file name); required for a ViTPose+ '
@@ -170,6 +205,9 @@ def main(argv=None) -> int:
     assert args.skeleton is None or args.save_img, '--skeleton belongs to --save-img'
     assert (args.model is None) != (args.synthetic is None), 'give exactly one of --model / --synthetic'
     assert args.frame_batch >= 1, '--frame-batch must be at least 1'
+    # --det-engine: resolved (and refused together with the other detector options) before any file is read
+    engine = det_engine_argument(args) if args.det_engine is not None else None
+    assert engine is not None or args.det_input_dtype is None, '--det-input-dtype belongs to --det-engine'
 
     from easy_vitpose_amd import VitInference
     from easy_vitpose_amd.configs import model_shape
@@ -197,7 +235,10 @@ def main(argv=None) -> int:
             h = heads[min(state['i'], len(heads) - 1)]
             state['i'] += 1
             return h, tuple(args.det_input)
-    assert detector is not None, 'give --yolo (ultralytics weights), --boxes or --det-heads'
+    letterbox = None
+    if engine is not None:
+        detector, detect, letterbox = engine
+    assert detector is not None, 'give --yolo (ultralytics weights), --boxes, --det-heads or --det-engine'
 
     skeleton = None
     if args.skeleton is not None:
@@ -212,7 +253,7 @@ def main(argv=None) -> int:
                          yolo_step=args.yolo_step, dtype=args.dtype, max_batch=args.max_batch,
                          flip_test=flip_test_argument(args), shift_heatmap=args.shift_heatmap, pose_nms=pose_nms_argument(args),
                          crop=args.crop, box_scale=args.box_scale, skeleton=skeleton, tracker='device' if args.tracker == 'device' else None,
-                         smooth=smooth_argument(args), detect=detect)
+                         smooth=smooth_argument(args), detect=detect, letterbox=letterbox)
     print(f'>>> Model loaded: {args.model or "synthetic ViTPose-" + args.synthetic.upper()}')
     print(f'>>> Running inference on {args.input}')
     base = os.path.basename(args.input.rstrip('/'))

@@ -5,8 +5,8 @@ and ``HostDetector`` (the host tap vp_dbg_detect_host: the model the device is t
 ``DeviceDetector.detect`` is stream-ordered on torch's current stream and never synchronises: its rows, image index and ``count[-1:]`` pass in place to
 ``DeviceTracker.update(rows, image, n_dets=count[-1:])``.  Rows beyond the total are "absent" (box NaN, score 0, class -1, image -1, anchor -1).
 
-The detector network itself stays third-party, and so does the letterboxing of a frame into its input: ``letterbox_params`` only computes the geometry
-ultralytics' LetterBox / scale_boxes use, which the stage takes as numbers.
+The detector network itself stays third-party.  The letterboxing of a frame into its input is the letterbox stage (``devletterbox``): ``detect`` takes the
+undo table that stage returned in place of ``frames_hw, input_hw``; ``letterbox_params`` computes the same numbers (ultralytics' scale_boxes) from the sizes alone.
 """
 from __future__ import annotations
 
@@ -116,7 +116,16 @@ def letterbox_params(frame_hw, input_hw):
 
 
 def image_table(frames_hw, input_hw, n_images: int):
-    """the C table of a call: `frames_hw` = one (h, w) for every image or [n_images] of them"""
+    """the C table of a call: `frames_hw` = one (h, w) for every image or [n_images] of them; with `input_hw` None, `frames_hw` is the table itself as the
+    letterbox stage returned it (float32 [n_images, 5] rows of (gain, pad_x, pad_y, frame_w, frame_h))"""
+    if input_hw is None:
+        rows = np.asarray(frames_hw)
+        if rows.dtype != np.float32 or rows.shape != (n_images, 5):
+            raise ValueError(f'table: float32 [{n_images}, 5] rows (gain, pad_x, pad_y, frame_w, frame_h) expected, got {rows.dtype} {rows.shape}')
+        tab = (capi.vp_det_image * max(n_images, 1))()
+        for i in range(n_images):
+            tab[i] = capi.vp_det_image(*(float(v) for v in rows[i]))
+        return tab
     hw = np.asarray(frames_hw, dtype=np.int64)
     if hw.shape == (2,):
         hw = np.broadcast_to(hw, (n_images, 2))
@@ -161,7 +170,7 @@ class HostDetector:
         self.cfg, self._c = cfg, c_config(cfg)
         self.lib = capi.load_library()
 
-    def detect(self, pred, frames_hw, input_hw, n_out=None):
+    def detect(self, pred, frames_hw, input_hw=None, n_out=None):
         pred = _host_pred(self.cfg, pred)
         n, A = _pred_shape(self.cfg, pred.shape)
         n_out = n * self.cfg.max_det if n_out is None else int(n_out)
@@ -179,9 +188,10 @@ class DeviceDetector:
         capi.check(self.lib.vp_detector_create(engine._h, C.byref(self._c), C.byref(h)), engine._h)
         self._d = h
 
-    def detect(self, pred, frames_hw, input_hw, n_out=None):
+    def detect(self, pred, frames_hw, input_hw=None, n_out=None):
         """The head `pred` (a contiguous torch CUDA tensor of the configured dtype and layout, n images) on torch's current stream, no synchronisation.
-        `frames_hw`: (h, w) of the frames, one pair or one per image; `input_hw`: the detector's input size.  Returns (rows float32 [n_out, 6] =
+        `frames_hw`: (h, w) of the frames, one pair or one per image; `input_hw`: the detector's input size -- or `detect(pred, table)` with the undo table
+        `DeviceLetterbox.letterbox` returned (float32 [n, 5]).  Returns (rows float32 [n_out, 6] =
         (x1, y1, x2, y2, score, class) in frame pixels, image int32 [n_out], anchor int32 [n_out], count int32 [n + 1], flags int32 [n]) device tensors;
         n_out defaults to n * max_det, which cuts nothing."""
         import torch
@@ -205,7 +215,7 @@ class DeviceDetector:
                                              anchor.data_ptr(), n_out, count.data_ptr(), flags.data_ptr(), cs), self.engine._h)
         return rows, image, anchor, count, flags
 
-    def detect_host(self, pred, frames_hw, input_hw, n_out=None):
+    def detect_host(self, pred, frames_hw, input_hw=None, n_out=None):
         """`detect` on numpy arrays (vp_detect: upload, the same kernels, download, synchronous)."""
         pred = _host_pred(self.cfg, pred)
         n, A = _pred_shape(self.cfg, pred.shape)

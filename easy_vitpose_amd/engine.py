@@ -587,6 +587,12 @@ class VitPoseHip:
         from .devdetect import DetectCfg, DeviceDetector
         return DeviceDetector(self, DetectCfg() if cfg is None else cfg)
 
+    def letterbox(self, cfg=None):
+        """A letterbox stage on this handle's device (devletterbox.DeviceLetterbox over vp_letterbox_*): device frames to the detector's input tensor, the
+        stream-ordered stage in front of the detector network; its table goes to `detector().detect(pred, table)`."""
+        from .devletterbox import DeviceLetterbox, LetterboxCfg
+        return DeviceLetterbox(self, LetterboxCfg() if cfg is None else cfg)
+
     def smoother(self, cfg=None):
         """A keypoint smoother for this handle's K joints on its device (devsmooth.DeviceSmoother over vp_smooth_*): the stream-ordered One-Euro stage behind
         `infer_boxes` (and its NMS), keyed by the tracker's (stream, id), in front of `draw_poses`."""

@@ -16,7 +16,9 @@ Out of scope here (SURVEY.md section 2 / 8f): the YOLO detector is third-party;
 ``yolo`` may be a path (needs ``ultralytics``) or any callable
 ``img_rgb -> ndarray[n, 5] (x1, y1, x2, y2, conf)``.  With ``detect=`` (keyword, a ``devdetect.DetectCfg``) the
 callable returns ``(raw head [4 + nc, A], (in_h, in_w))`` instead and the detector stage (vp_detect: best class, threshold,
-class filter, box NMS, letterbox undone) makes the boxes on the device.  The SORT tracker is ``tracker.Sort``
+class filter, box NMS, letterbox undone) makes the boxes on the device.  With ``letterbox=`` (a ``devletterbox.LetterboxCfg``)
+on top of ``detect=`` the callable receives the letterboxed device tensor ``[1, 3, H, W]`` (vp_letterbox_stream) and returns the raw
+head alone; the detector stage is fed the letterbox stage's own table.  The SORT tracker is ``tracker.Sort``
 on the host by default, ``tracker='device'`` selects the device tracker
 (``devtracker.DeviceSort``, vp_tracker_update), and a factory of any object with the
 SORT ``update`` interface is taken as it is.
@@ -81,7 +83,7 @@ class VitInference:
                  single_pose: Optional[bool] = False,
                  yolo_step: Optional[int] = 1,
                  *, dtype: str = 'fp16', max_batch: int = 64, tracker=None, flip_test=None, shift_heatmap: bool = False,
-                 pose_nms: Optional[PoseNms] = None, crop: str = 'pad', box_scale: float = 1.25, skeleton=None, smooth=None, detect=None):
+                 pose_nms: Optional[PoseNms] = None, crop: str = 'pad', box_scale: float = 1.25, skeleton=None, smooth=None, detect=None, letterbox=None):
         # crop='affine': the training-protocol crop (cropprep.box_to_cs, VitPoseHip.infer_frames(crop='affine')) instead of the pad route; refused before anything is loaded
         if crop not in ('pad', 'affine'):
             raise ValueError(f"crop: 'pad' or 'affine' expected, got {crop!r}")
@@ -100,6 +102,14 @@ class VitInference:
         if not (detect is None or isinstance(detect, DetectCfg)):
             raise TypeError(f'detect: None or a DetectCfg expected, got {detect!r}')
         self._detect_cfg, self._detector = detect, None
+        # letterbox: the letterbox stage in front of the detector (devletterbox.LetterboxCfg, with detect=): `yolo(tensor)` then receives the letterboxed DEVICE tensor
+        # [1, 3, H, W] and returns the raw head (a device tensor or an ndarray); the geometry is the stage's own
+        from .devletterbox import LetterboxCfg
+        if not (letterbox is None or isinstance(letterbox, LetterboxCfg)):
+            raise TypeError(f'letterbox: None or a LetterboxCfg expected, got {letterbox!r}')
+        if letterbox is not None and detect is None:
+            raise ValueError('letterbox= feeds the detector stage: give detect= (a DetectCfg) with it')
+        self._letterbox_cfg, self._letterbox = letterbox, None
         if not (np.isfinite(box_scale) and box_scale > 0):
             raise ValueError(f'box_scale must be finite and > 0, got {box_scale!r}')
         self.crop, self.box_scale = crop, float(box_scale)
@@ -188,6 +198,8 @@ class VitInference:
             self._vit_pose.set_flip_test(flip_pairs, shift_heatmap)
         if self._detect_cfg is not None:
             self._detector = self._vit_pose.detector(dataclasses.replace(self._detect_cfg, max_images=1))
+        if self._letterbox_cfg is not None:
+            self._letterbox = self._vit_pose.letterbox(self._letterbox_cfg)
         if tracker == 'device' or self._smooth_cfg is not None:   # the device tracker and the smoother live on the engine's device: built now that there is one
             self.reset()
         self._inference = self._inference_hip
@@ -241,6 +253,20 @@ class VitInference:
         stage's synchronous twin (vp_detect): the [m, 5] rows (x1, y1, x2, y2, score) in frame pixels.  Every row is over DetectCfg.conf_thr already."""
         head = np.asarray(head)
         rows, _, _, count, _ = self._detector.detect_host(head.reshape((1,) + head.shape[-2:]), img.shape[:2], input_hw)
+        return rows[:int(count[-1]), :5]
+
+    def _letterbox_rows(self, img):
+        """VitInference(letterbox=, detect=): the frame goes to the device once, the letterbox stage writes the detector's input tensor there, `yolo(tensor)` returns
+        the raw head, and the detector stage undoes the letterbox with the table the letterbox stage returned: the [m, 5] rows in frame pixels.  A head left on the
+        device stays there (vp_detect_stream on torch's current stream); an ndarray head goes through the synchronous twin."""
+        tensor, table, _ = self._letterbox.letterbox([self._letterbox.upload(img)])
+        head = self.yolo(tensor)
+        if hasattr(head, 'data_ptr'):
+            rows, _, _, count, _ = self._detector.detect(head.reshape((1,) + tuple(head.shape[-2:])), table)
+            rows, count = rows.cpu().numpy(), count.cpu().numpy()
+        else:
+            head = np.asarray(head)
+            rows, _, _, count, _ = self._detector.detect_host(head.reshape((1,) + head.shape[-2:]), table)
         return rows[:int(count[-1]), :5]
 
     def _smooth_results(self, results):
@@ -302,7 +328,10 @@ class VitInference:
         for img in imgs:
             res_pd = np.empty((0, 5))
             if (self.tracker is None or (self.frame_counter % self.yolo_step == 0 or self.frame_counter < 3)):
-                det = self.yolo(img) if self._detector is None else self._detect_rows(img, *self.yolo(img))
+                if self._letterbox is not None:
+                    det = self._letterbox_rows(img)
+                else:
+                    det = self.yolo(img) if self._detector is None else self._detect_rows(img, *self.yolo(img))
                 det = np.asarray(det, dtype=np.float64).reshape((-1, 5))
                 res_pd = det[det[:, 4] > 0.35].reshape((-1, 5))
             self.frame_counter += 1

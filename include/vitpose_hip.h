@@ -601,8 +601,8 @@ VP_API int vp_tracker_update_counted_stream(vp_tracker_handle t, const float* d_
 
 /* The detector stage, IN FRONT of the tracker: a detector's raw head tensor, left in device memory by an engine on the same GPU, to the [n, 6] box rows every entry
  * above takes in place -- best-class pick, confidence threshold, class filter, greedy box NMS, letterbox undone (the reference's YOLOv8 post-processing behind
- * inference.py:240-241; csrc/detgeom.h states the arithmetic once for the kernels and the host tap).  The detector network itself and the letterboxing of the frame
- * into its input are not this library's: the stage takes the letterbox geometry as numbers.  Up to VP_DET_MAX_IMAGES images per call; the image index is the
+ * inference.py:240-241; csrc/detgeom.h states the arithmetic once for the kernels and the host tap).  The detector network itself is not this library's; the letterboxing of the frame
+ * into its input is the letterbox stage below, whose undo table this stage takes as `images`.  Up to VP_DET_MAX_IMAGES images per call; the image index is the
  * tracker's stream.  Everything is float32, nothing contracted, division correctly rounded.
  *   d_pred: the head, contiguous, float32 (VP_DET_F32) or float16 (VP_DET_F16, widened exactly); layout 0 = [n_images, 4 + nc, A] (YOLOv8's export), layout 1 =
  *   [n_images, A, 4 + nc].  Channels 0..3 = (cx, cy, w, h) in detector-input pixels, channels 4.. = class scores, already sigmoided.
@@ -658,6 +658,64 @@ VP_API int vp_detect(vp_detector_handle d, const void* pred, int32_t A, const vp
  * vp_detector_create and vp_detect_stream, the reason in vp_last_error(NULL). */
 VP_API int vp_dbg_detect_host(const vp_det_cfg* cfg, const void* pred, int32_t A, const vp_det_image* images, int32_t n_images, float* rows, int32_t* image,
                               int32_t* anchor, int32_t n_out, int32_t* count, int32_t* flags);
+
+/* The letterbox stage, IN FRONT of the detector network: frames in the layout their producer holds them (vp_image: NV12 decoder surfaces, BGR24 / RGB24 buffers,
+ * pitched) to the detector's input tensor in device memory -- resize, pad, colour conversion, normalisation and transpose in one kernel -- together with the
+ * vp_det_image table vp_detect_stream takes to undo it.  csrc/lbgeom.h states the arithmetic once for the kernel and the host tap; the detector network itself stays
+ * third-party.  Up to VP_LB_MAX_IMAGES frames per call, which may differ in size, format and matrix; image i fills slice i of the tensor.
+ *   Geometry (host, doubles; ultralytics' LetterBox(new_shape = (in_h, in_w), auto = False, scaleFill = False, center = True) on a frame of (h, w)):
+ *   r = min(in_h / h, in_w / w), with scaleup = 0 r = min(r, 1.0); new_w = round(w r), new_h = round(h r) (round half to even on the double: nearbyint);
+ *   left = round((in_w - new_w) / 2 - 0.1), top = round((in_h - new_h) / 2 - 0.1); the right and bottom pads are what remains.
+ *   Pixels, in this order: every source pixel is converted to RGB8 (the image entries' definition above: NV12 with its matrix, chroma replicated; BGR swapped).  The
+ *   h x w RGB8 image is resized to new_h x new_w as OpenCV's 8-bit cv2.resize(INTER_LINEAR) does (the crop kernel's restatement, easy_vitpose_amd/cropprep.py
+ *   resize_linear_u8; parity against the OpenCV and ultralytics binaries is unpinned): scale = 1.0 / ((double)new / (double)src) per axis; for output index d
+ *   f = (float)((d + 0.5) scale - 0.5) with product and difference in double, s = floor(f), f -= s, (f, s) = (0, 0) where s < 0 and (0, src - 1) where s >= src - 1,
+ *   taps s and min(s + 1, src - 1) with weights a1 = rint(f 2048), a0 = rint((1 - f) 2048) in float32; r = p(s) a0 + p(s + 1) a1 along x in int32, then
+ *   (((ay0 (r0 >> 4)) >> 16) + ((ay1 (r1 >> 4)) >> 16) + 2) >> 2 along y.  Where both scales are exactly 2.0 the result is the 2 x 2 box average (p00 + p01 + p10 +
+ *   p11 + 2) >> 2; where new_h x new_w equals h x w the frame is copied.  The result lies at rows [top, top + new_h), columns [left, left + new_w); every other
+ *   element is pad_value in all three channels.
+ *   Output: order 0 = R, G, B channels (ultralytics' model input), 1 = B, G, R; layout 0 = [n, 3, in_h, in_w] (NCHW), 1 = [n, in_h, in_w, 3] (NHWC); dtype
+ *   VP_LB_F32 = (float)v / 255.0f (division correctly rounded), VP_LB_F16 = that float rounded to nearest-even fp16 (what `im.half() / 255` gives), VP_LB_U8 = the
+ *   byte v itself, for engines that normalise inside the model.
+ *   det (host, may be NULL) [n_images]: the row of vp_detect_stream's `images` table per frame.  Where r was not clamped it is ultralytics' scale_boxes convention
+ *   (easy_vitpose_amd/devdetect.py letterbox_params): gain = (float)min(in_h / h, in_w / w), pad_x = round((in_w - w gain) / 2 - 0.1), pad_y likewise -- from
+ *   the UNROUNDED scaled size -- and frame_w = w, frame_h = h; where scaleup = 0 clamped r it is (1.0, left, top, w, h).  placement (host, may be NULL) int32
+ *   [n_images, 4] = (left, top, new_w, new_h): where the pixels really lie.  The two are ultralytics' own conventions and differ by one pixel of pad for some sizes
+ *   (5 x 7 into 640 x 640: top 91, pad_y 91; 1 x 6: top 266, pad_y 267): det is what undoes a detector's boxes the way ultralytics does, placement is the truth
+ *   about the tensor.
+ * vp_letterbox_stream only enqueues on caller_stream: one launch per 32 frames (the image records -- plane pointers, pitches, size, format, matrix, placement,
+ *   scales -- travel by kernel argument), a workgroup per output row: adjacent lanes fetch adjacent pixels into LDS, then a lane stores a run of 16 output bytes per
+ *   channel (8 fp16, 4 fp32, 16 u8 adjacent x); rows and pixels in the pad store the constant without a fetch; a d_out that is not 16-byte aligned or an in_w that is
+ *   no multiple of the run takes element stores with the same values.  No synchronisation, no copy from host memory, no allocation, none of the handle's workspaces: it works under graph capture and back to back.  The
+ *   planes are read in place; every plane is checked first to be device memory of the handle's device with (plane rows - 1) * pitch + row bytes inside one allocation.
+ *   n_images = 0 is legal and enqueues nothing.  The handle needs no weights.
+ * vp_letterbox: the synchronous twin, planes and tensor in host memory (upload at the caller's pitch, the same kernel, download).  vp_letterbox_plan: HOST ONLY, no
+ *   device needed: det, placement and every refusal below that needs no device; it reads sizes and layout only (plane[0] may be NULL there).
+ * VP_ERR_INVALID before anything is enqueued, the reason in vp_last_error (of the handle; vp_last_error(NULL) for the host-only entries): a NULL cfg, in_h / in_w
+ *   outside 1..8192, an unknown dtype / layout / order, pad_value outside 0..255, scaleup not 0 / 1, n_images outside 0..VP_LB_MAX_IMAGES, NULL images or NULL
+ *   output with n_images > 0, an output not aligned to its element, a frame with h or w < 1, the image refusals of vp_dbg_image_plan (an unknown format or matrix,
+ *   a negative pitch, a pitch below the row bytes, NV12 with a NULL plane[1]), a NULL plane[0], a frame whose new_w or new_h comes out 0 (1280 x 1 into 640 x 640),
+ *   a device plane that fails the allocation check.  A refused call leaves det and placement as they were.  Library builds that carry the stage define VP_HAS_LETTERBOX. */
+#define VP_HAS_LETTERBOX 1
+#define VP_LB_MAX_IMAGES 64
+#define VP_LB_F32 0
+#define VP_LB_F16 1
+#define VP_LB_U8  2
+typedef struct vp_letterbox_cfg {
+    int32_t in_h, in_w;     /* the detector's input size, 1..8192 each */
+    int32_t dtype;          /* VP_LB_* */
+    int32_t layout;         /* 0 NCHW, 1 NHWC */
+    int32_t order;          /* 0 RGB, 1 BGR */
+    int32_t pad_value;      /* 0..255; ultralytics pads with 114 */
+    int32_t scaleup;        /* 0: never enlarge a frame (r = min(r, 1)) */
+} vp_letterbox_cfg;   /* 28 bytes */
+VP_API int vp_letterbox_plan(const vp_letterbox_cfg* cfg, const vp_image* images, int32_t n_images, vp_det_image* det, int32_t* placement);
+VP_API int vp_letterbox_stream(vp_handle h, const vp_letterbox_cfg* cfg, const vp_image* images, int32_t n_images, void* d_out, vp_det_image* det,
+                               int32_t* placement, void* caller_stream);
+VP_API int vp_letterbox(vp_handle h, const vp_letterbox_cfg* cfg, const vp_image* images, int32_t n_images, void* out, vp_det_image* det, int32_t* placement);
+/* HOST ONLY, no device needed: csrc/lbgeom.h run serially on host planes, the model the device is tested against (a test tap, never a fallback); the refusals of
+ * vp_letterbox, the reason in vp_last_error(NULL). */
+VP_API int vp_dbg_letterbox_host(const vp_letterbox_cfg* cfg, const vp_image* images, int32_t n_images, void* out, vp_det_image* det, int32_t* placement);
 
 /* Keypoint smoothing on the device, the stage BEHIND a boxes entry (and its NMS) and in front of vp_draw_poses_stream: the One-Euro filter of the reference's
  * post_processing/one_euro_filter.py in its fixed-rate mode, one filter per (stream, track id) (csrc/eurogeom.h states the arithmetic once for the kernels and the
