@@ -43,6 +43,7 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_infer_images_affine', 'vp_infer_boxes_affine_stream', 'vp_dbg_box_cs', 'vp_dbg_affine_plan', 'vp_dbg_crop_affine', 'vp_dbg_decode_affine',
            'vp_dbg_decode_affine_flip',
            'vp_draw_poses_stream', 'vp_draw_poses', 'vp_dbg_draw_host',
+           'vp_draw_labels_stream', 'vp_draw_labels', 'vp_dbg_draw_labels_host', 'vp_dbg_label_text', 'vp_dbg_label_glyph',
            'vp_tracker_create', 'vp_tracker_destroy', 'vp_tracker_reset_stream', 'vp_tracker_update_stream', 'vp_tracker_update', 'vp_tracker_state_bytes',
            'vp_tracker_download_state', 'vp_dbg_track_host', 'vp_dbg_lsap', 'vp_tracker_update_counted_stream',
            'vp_detector_create', 'vp_detector_destroy', 'vp_detect_stream', 'vp_detect', 'vp_dbg_detect_host',
@@ -89,6 +90,10 @@ class vp_pose_nms_cfg(C.Structure):
 class vp_draw_cfg(C.Structure):
     _fields_ = [('conf_thr', C.c_float), ('radius', C.c_int32), ('thickness', C.c_int32), ('n_limbs', C.c_int32), ('limbs', C.c_void_p),
                 ('n_point_colors', C.c_int32), ('point_colors', C.c_void_p), ('n_limb_colors', C.c_int32), ('limb_colors', C.c_void_p)]
+
+
+class vp_label_cfg(C.Structure):
+    _fields_ = [('scale', C.c_int32), ('n_colors', C.c_int32), ('colors', C.c_void_p), ('auto_ink', C.c_int32), ('ink', C.c_uint8 * 3), ('show_score', C.c_int32)]
 
 
 class vp_track_cfg(C.Structure):
@@ -261,6 +266,13 @@ def load_library():
     lib.vp_draw_poses_stream.argtypes = [H] + draw_host + [C.c_void_p]
     lib.vp_draw_poses.argtypes = [H] + draw_host
     lib.vp_dbg_draw_host.argtypes = draw_host
+    label_host = [C.POINTER(vp_image), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                  C.POINTER(vp_label_cfg)]
+    lib.vp_draw_labels_stream.argtypes = [H] + label_host + [C.c_void_p]
+    lib.vp_draw_labels.argtypes = [H] + label_host
+    lib.vp_dbg_draw_labels_host.argtypes = label_host
+    lib.vp_dbg_label_text.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_char_p]
+    lib.vp_dbg_label_glyph.argtypes = [C.c_int32]
     trk_io = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.vp_tracker_create.argtypes = [H, C.POINTER(vp_track_cfg), C.POINTER(C.c_void_p)]
     lib.vp_tracker_destroy.argtypes = [C.c_void_p]
@@ -297,6 +309,7 @@ def load_library():
     for name in SYMBOLS:
         if name not in ('vp_stream', 'vp_last_error', 'vp_host_alloc', 'vp_host_free', 'vp_group_member', 'vp_group_last_error'):
             getattr(lib, name).restype = C.c_int
+    lib.vp_dbg_label_glyph.restype = C.c_uint64
     _lib = lib
     return lib
 

@@ -21,8 +21,9 @@ tensor or an ndarray.  The callable may carry ``nc`` (classes of its head, defau
 fp16).  It is refused together with ``--yolo`` / ``--boxes`` / ``--det-heads``.
 ``--det-heads`` (an ``.npz`` with the raw YOLOv8 head ``[4 + nc, A]`` of every frame, as an engine on the same GPU leaves it) replaces ``--yolo`` / ``--boxes``:
 the boxes then come from the detector stage (``devdetect``, ``VitInference(detect=)``); ``--det-input`` is the size the frames were letterboxed into.
-``--save-img`` writes ``<stem>_<frame>.png`` per frame (``VitInference.draw``: skeletons drawn on the device, csrc/drawgeom.h; no text labels) into the
-``--save-json`` directory; a dataset other than COCO-17 needs ``--skeleton FILE.json``.
+``--save-img`` writes ``<stem>_<frame>.png`` per frame (``VitInference.draw``: skeletons drawn on the device, csrc/drawgeom.h) into the
+``--save-json`` directory; a dataset other than COCO-17 needs ``--skeleton FILE.json``.  ``--labels`` adds the reference's ``#<id>: <score>`` tag at every
+tracked box of a video (csrc/labelgeom.h, this project's own bitmap font), ``--label-scale S`` sets its size (pixels per font bit, 1..8; implies ``--labels``).
 Not rebuilt (outside the hot path): preview windows (``--show``: OpenCV) and video
 decoding -- a video is accepted as a ``.npy`` stack ``[frames, H, W, 3]`` uint8 RGB, or as a directory of image files.
 ``--boxes`` (JSON: one ``[[x1, y1, x2, y2, conf], ...]`` list per frame, or a single list used for every frame) replaces the
@@ -172,6 +173,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--show', action='store_true')
     ap.add_argument('--save-img', action='store_true', help='write every frame with its skeletons drawn on it as <stem>_<frame>.png into the output directory')
     ap.add_argument('--skeleton', default=None, metavar='FILE.json', help='--save-img: the limb table [[a, b], ...] of the dataset (built in for COCO-17 only)')
+    ap.add_argument('--labels', action='store_true', help='--save-img on video input: write the tag `#<id>: <score>` at the top-left corner of every tracked box')
+    ap.add_argument('--label-scale', type=int, default=None, metavar='S', help='--labels: pixels per font bit, 1..8 (default: max(1, min(h, w) // 400) of the frame; '
+                    'implies --labels)')
     ap.add_argument('--max-batch', type=int, default=64)
     ap.add_argument('--dtype', default='fp16', choices=['fp16', 'bf16'])
     ap.add_argument('--frame-batch', type=int, default=1, help='frames per pose call: the crops of N frames run as one batch (VitInference.inference_frames)')
@@ -203,6 +207,7 @@ def main(argv=None) -> int:
     assert not args.show, 'preview windows (OpenCV) are outside the HIP hot path: use --save-img or --save-json'
     assert not (args.save_json or args.save_img) or args.output_path, 'Specify an output path if using save-img or save-json flags'
     assert args.skeleton is None or args.save_img, '--skeleton belongs to --save-img'
+    assert not (args.labels or args.label_scale is not None) or args.save_img, '--labels / --label-scale belong to --save-img'
     assert (args.model is None) != (args.synthetic is None), 'give exactly one of --model / --synthetic'
     assert args.frame_batch >= 1, '--frame-batch must be at least 1'
     # --det-engine: resolved (and refused together with the other detector options) before any file is read
@@ -244,6 +249,10 @@ def main(argv=None) -> int:
     if args.skeleton is not None:
         from easy_vitpose_amd.draw import load_skeleton
         skeleton = load_skeleton(args.skeleton)
+    labels = False
+    if args.labels or args.label_scale is not None:
+        from easy_vitpose_amd.draw import LabelStyle
+        labels = LabelStyle(scale=0 if args.label_scale is None else args.label_scale)   # a scale outside 0..8 is refused here, before anything is loaded
     state_dict = None
     if args.synthetic:
         from easy_vitpose_amd.synth import synthetic_state_dict
@@ -253,7 +262,7 @@ def main(argv=None) -> int:
                          yolo_step=args.yolo_step, dtype=args.dtype, max_batch=args.max_batch,
                          flip_test=flip_test_argument(args), shift_heatmap=args.shift_heatmap, pose_nms=pose_nms_argument(args),
                          crop=args.crop, box_scale=args.box_scale, skeleton=skeleton, tracker='device' if args.tracker == 'device' else None,
-                         smooth=smooth_argument(args), detect=detect, letterbox=letterbox)
+                         smooth=smooth_argument(args), detect=detect, letterbox=letterbox, labels=labels)
     print(f'>>> Model loaded: {args.model or "synthetic ViTPose-" + args.synthetic.upper()}')
     print(f'>>> Running inference on {args.input}')
     base = os.path.basename(args.input.rstrip('/'))

@@ -17,7 +17,7 @@ from .configs import HM_H, HM_W, IMG_H, IMG_W, ModelShape
 from .cropprep import PIX_FORMATS, YUV_MATRIX_IDS, Frame
 from .posenms import PoseNms, resolve_sigmas
 from .posenms import c_config as nms_c_config
-from .draw import DrawStyle, check_records, check_rows, resolve_skeleton
+from .draw import LABEL_MAX_ROWS, DrawStyle, LabelStyle, check_label_rows, check_records, check_rows, label_boxes, label_c_config, overlay_label_style, resolve_skeleton
 from .draw import c_config as draw_c_config
 from .draw import host_frame as host_draw_frame
 
@@ -607,13 +607,61 @@ class VitPoseHip:
             raise TypeError(f'a DrawStyle expected, got {type(style).__name__}')
         return resolve_skeleton(getattr(self, 'dataset', 'coco') if self._moe else 'coco', K, style.skeleton)
 
-    def draw_poses(self, frames, keypoints, frame_index, style: DrawStyle = DrawStyle(), rank=None, ids=None, boxes=None):
+    def draw_labels(self, frames, boxes, frame_index, style: LabelStyle = LabelStyle(), rank=None, ids=None, scores=None):
+        """Track-id / score tags written onto device frames IN PLACE (vp_draw_labels_stream, contract in include/vitpose_hip.h and csrc/labelgeom.h), stream-ordered
+        on torch's current stream without a host synchronisation: the stage in front of `draw_poses`.  `frames`: what `draw_poses` takes; `boxes`: float32 CUDA
+        [n, >= 4] with unit column stride -- the tracker's rows pass as they are; `frame_index`: int32 CUDA [n] with any positive element stride; `rank` / `ids`:
+        int32 CUDA [n] or None; `scores`: float32 CUDA [n] with any positive element stride, such as the column view `rows[:, 4]`, or None (the id alone).
+        Returns the frames as `Frame` objects."""
+        import torch
+        dev = torch.device('cuda', self.device_id)
+
+        def want(t, name, dtype, shape_ok, what):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype):
+                raise TypeError(f'{name}: a {dtype} torch CUDA tensor expected')
+            if t.device != dev or not shape_ok(t):
+                raise ValueError(f'{name}: {what} on {dev} expected, got {tuple(t.shape)} on {t.device}')
+        if boxes is None:
+            label_boxes(boxes)
+        want(boxes, 'boxes', torch.float32, lambda t: t.ndim == 2 and t.shape[1] >= 4 and (t.shape[0] == 0 or t.stride(1) == 1) and (t.shape[0] < 2 or t.stride(0) >= 1),
+             '[n, >= 4] with unit column stride')
+        n = boxes.shape[0]
+        if n > LABEL_MAX_ROWS:
+            raise ValueError(f'labels: {n} rows exceed the {LABEL_MAX_ROWS} records of one call')
+        want(frame_index, 'frame_index', torch.int32, lambda t: tuple(t.shape) == (n,) and (n < 2 or t.stride(0) >= 1), f'[{n}] with a positive stride')
+        for t, name in ((rank, 'rank'), (ids, 'ids')):
+            if t is not None:
+                want(t, name, torch.int32, lambda t: tuple(t.shape) == (n,) and t.is_contiguous(), f'contiguous [{n}]')
+        if scores is not None:
+            want(scores, 'scores', torch.float32, lambda t: tuple(t.shape) == (n,) and (n < 2 or t.stride(0) >= 1), f'[{n}] with a positive stride')
+        c, keep = label_c_config(style)
+        frames = [self._as_frame(f, i) for i, f in enumerate(frames)]
+        table = self._image_table(frames, device_only=True)
+        cs = torch.cuda.current_stream(dev).cuda_stream
+        capi.check(self.lib.vp_draw_labels_stream(self._h, table, len(frames), boxes.data_ptr(), 4 if n < 2 else boxes.stride(0), n, frame_index.data_ptr(),
+                                                  frame_index.stride(0) if n > 1 else 1, None if rank is None else rank.data_ptr(),
+                                                  None if ids is None else ids.data_ptr(), None if scores is None else scores.data_ptr(),
+                                                  1 if scores is None or n < 2 else scores.stride(0), C.byref(c), cs), self._h)
+        return frames
+
+    def draw_labels_host(self, frames, boxes, frame_index, style: LabelStyle = LabelStyle(), rank=None, ids=None, scores=None):
+        """`draw_labels` on numpy arrays and host frames, in place (vp_draw_labels: upload, the same kernels, download, synchronous).  Returns the frames as `Frame`s."""
+        c, keep = label_c_config(style)
+        frames = [host_draw_frame(f, i) for i, f in enumerate(frames)]
+        bx, fi, rk, pid, sc = check_label_rows(boxes, frame_index, rank, ids, scores)
+        capi.check(self.lib.vp_draw_labels(self._h, self._image_table(frames), len(frames), bx.ctypes.data, 4, bx.shape[0], fi.ctypes.data, 1,
+                                           None if rk is None else rk.ctypes.data, None if pid is None else pid.ctypes.data,
+                                           None if sc is None else sc.ctypes.data, 1, C.byref(c)), self._h)
+        return frames
+
+    def draw_poses(self, frames, keypoints, frame_index, style: DrawStyle = DrawStyle(), rank=None, ids=None, boxes=None, labels=None, scores=None):
         """Skeletons drawn onto device frames IN PLACE (vp_draw_poses_stream, contract in include/vitpose_hip.h), stream-ordered on torch's current stream without a
         host synchronisation: correct directly behind `infer_boxes` and `pose_nms`.  `frames`: what `infer_boxes` takes (uint8 CUDA tensors [H, W, 3] = RGB, or
         `Frame.rgb / bgr / nv12` over device planes, up to 8192 x 8192); `keypoints`: float32 CUDA [n, K, 3] in frame pixels; `frame_index`: int32 CUDA [n], or
         a column view such as `crop_params[:, 0]` (any positive element stride); `rank`: int32 CUDA [n] or None, rows with rank < 0 are not drawn; `ids`: int32
         CUDA [n] or None (the row index), the colour of a person's limbs; `boxes`: float32 CUDA [n, >= 4] with unit column stride or None, outlines drawn under the
-        skeletons.  Returns the frames as `Frame` objects."""
+        skeletons; `labels`: a `LabelStyle` enqueues `draw_labels` first (tags under the skeletons, in the limb palette of `style` unless it has colours of its
+        own; needs `boxes`), `scores` its scores; None (the default) draws no tag.  Returns the frames as `Frame` objects."""
         import torch
         dev = torch.device('cuda', self.device_id)
 
@@ -635,18 +683,23 @@ class VitPoseHip:
         check_records(n, K, keep[0].shape[0], boxes is not None)
         frames = [self._as_frame(f, i) for i, f in enumerate(frames)]
         table = self._image_table(frames, device_only=True)
+        if labels is not None:   # the tags first, the skeletons over them: the reference's order
+            self.draw_labels(frames, label_boxes(boxes), frame_index, overlay_label_style(labels, style), rank=rank, ids=ids, scores=scores)
         cs = torch.cuda.current_stream(dev).cuda_stream
         capi.check(self.lib.vp_draw_poses_stream(self._h, table, len(frames), keypoints.data_ptr(), n, K, frame_index.data_ptr(), frame_index.stride(0) if n > 1 else 1,
                                                  None if rank is None else rank.data_ptr(), None if ids is None else ids.data_ptr(),
                                                  None if boxes is None else boxes.data_ptr(), 4 if boxes is None or n < 2 else boxes.stride(0), C.byref(c), cs), self._h)
         return frames
 
-    def draw_poses_host(self, frames, keypoints, frame_index, style: DrawStyle = DrawStyle(), rank=None, ids=None, boxes=None):
-        """`draw_poses` on numpy arrays and host frames, in place (vp_draw_poses: upload, the same kernels, download, synchronous).  Returns the frames as `Frame`s."""
+    def draw_poses_host(self, frames, keypoints, frame_index, style: DrawStyle = DrawStyle(), rank=None, ids=None, boxes=None, labels=None, scores=None):
+        """`draw_poses` on numpy arrays and host frames, in place (vp_draw_poses: upload, the same kernels, download, synchronous).  Returns the frames as `Frame`s.
+        `labels`: a `LabelStyle` runs `draw_labels_host` first."""
         frames = [host_draw_frame(f, i) for i, f in enumerate(frames)]
         kp, fi, rk, pid, bx = check_rows(keypoints, frame_index, rank, ids, boxes)
         c, keep = draw_c_config(style, self._draw_skeleton(style, kp.shape[1]))
         check_records(kp.shape[0], kp.shape[1], keep[0].shape[0], bx is not None)
+        if labels is not None:
+            self.draw_labels_host(frames, label_boxes(bx), fi, overlay_label_style(labels, style), rank=rk, ids=pid, scores=scores)
         capi.check(self.lib.vp_draw_poses(self._h, self._image_table(frames), len(frames), kp.ctypes.data, kp.shape[0], kp.shape[1], fi.ctypes.data, 1,
                                           None if rk is None else rk.ctypes.data, None if pid is None else pid.ctypes.data,
                                           None if bx is None else bx.ctypes.data, 4, C.byref(c)), self._h)

@@ -36,7 +36,7 @@ from .configs import IMG_H, IMG_W, infer_dataset_by_path, infer_variant_from_sta
 from .cropprep import box_to_cs, frames_crop_params, resize_linear_u8
 from .engine import VitPoseHip, decode_heatmaps
 from .moe import DATASETS as MOE_DATASETS, is_vitpose_plus
-from .draw import DrawStyle, resolve_skeleton
+from .draw import DrawStyle, LabelStyle, resolve_skeleton
 from .posenms import PoseNms, resolve_sigmas
 
 __all__ = ['VitInference']
@@ -83,7 +83,7 @@ class VitInference:
                  single_pose: Optional[bool] = False,
                  yolo_step: Optional[int] = 1,
                  *, dtype: str = 'fp16', max_batch: int = 64, tracker=None, flip_test=None, shift_heatmap: bool = False,
-                 pose_nms: Optional[PoseNms] = None, crop: str = 'pad', box_scale: float = 1.25, skeleton=None, smooth=None, detect=None, letterbox=None):
+                 pose_nms: Optional[PoseNms] = None, crop: str = 'pad', box_scale: float = 1.25, skeleton=None, smooth=None, detect=None, letterbox=None, labels=False):
         # crop='affine': the training-protocol crop (cropprep.box_to_cs, VitPoseHip.infer_frames(crop='affine')) instead of the pad route; refused before anything is loaded
         if crop not in ('pad', 'affine'):
             raise ValueError(f"crop: 'pad' or 'affine' expected, got {crop!r}")
@@ -113,6 +113,10 @@ class VitInference:
         if not (np.isfinite(box_scale) and box_scale > 0):
             raise ValueError(f'box_scale must be finite and > 0, got {box_scale!r}')
         self.crop, self.box_scale = crop, float(box_scale)
+        # labels: draw() writes the `#<id>: <score>` tag of every tracked box (draw.LabelStyle; True = its defaults); off unless asked for
+        if not (labels is None or labels is True or labels is False or isinstance(labels, LabelStyle)):
+            raise TypeError(f'labels: False, True or a LabelStyle expected, got {labels!r}')
+        self._labels = LabelStyle() if labels is True else (labels or None)
         self._skeleton, self._limbs = skeleton, None   # draw(): the limb table is resolved, or refused, when draw is first called (draw.resolve_skeleton)
         state_dict = None
         dataset_given = dataset is not None
@@ -411,8 +415,9 @@ class VitInference:
         """inference.py:283-312: an RGB copy of the last frame with every kept pose drawn on it -- limbs in the person's colour (the tracker's id, or the
         pose's ordinal in the frame, as the reference's person_index), joints in the joint's colour, joints at or below `confidence_threshold` left out --
         on the device through `VitPoseHip.draw_poses_host` (csrc/drawgeom.h: this project's own integer rasterisation, parity against OpenCV unpinned).
-        `show_yolo` with a tracker on: the box outline of every kept pose, in the person's colour, each under its own skeleton.  NOT provided: text labels
-        (ids, scores) and `show_raw_yolo`'s detector plot -- the flag is accepted and ignored.  The skeleton is the COCO-17 one for that dataset; any other
+        `show_yolo` with a tracker on: the box outline of every kept pose, in the person's colour, each under its own skeleton; with `VitInference(labels=...)`
+        also the reference's `#<id>: <score>` tag at the box's top-left corner, from the tracker's result, under the skeletons (csrc/labelgeom.h: this
+        project's own bitmap font, parity against OpenCV's Hershey font unpinned).  NOT provided: `show_raw_yolo`'s detector plot -- the flag is accepted and ignored.  The skeleton is the COCO-17 one for that dataset; any other
         dataset needs `VitInference(skeleton=[[a, b], ...])`, refused here when it is missing."""
         if self._img is None or self._keypoints is None:
             raise RuntimeError('draw(): nothing to draw yet: call inference() first (with save_state on)')
@@ -422,10 +427,14 @@ class VitInference:
         img = np.array(self._img, dtype=np.uint8, order='C', copy=True)
         ids = list(self._keypoints.keys())
         kp = np.stack([self._keypoints[i] for i in ids]).astype(np.float32) if ids else np.zeros((0, K, 3), np.float32)
-        boxes = None
+        boxes = labels = scores = None
         if show_yolo and self.tracker is not None:
             box_of = {i: b for b, i in zip(self._tracker_res[0], self._tracker_res[1])}
             boxes = np.array([box_of[i] for i in ids], dtype=np.float32).reshape(-1, 4)
+            if getattr(self, '_labels', None) is not None:
+                score_of = dict(zip(self._tracker_res[1], self._tracker_res[2]))
+                labels, scores = self._labels, np.array([score_of[i] for i in ids], dtype=np.float32).reshape(-1)
         style = DrawStyle(conf_thr=confidence_threshold, skeleton=self._limbs)
-        self._vit_pose.draw_poses_host([img], kp, np.zeros(len(ids), np.int32), style, ids=np.array(ids, dtype=np.int32).reshape(-1), boxes=boxes)
+        self._vit_pose.draw_poses_host([img], kp, np.zeros(len(ids), np.int32), style, ids=np.array(ids, dtype=np.int32).reshape(-1), boxes=boxes, labels=labels,
+                                       scores=scores)
         return img

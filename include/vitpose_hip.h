@@ -535,6 +535,53 @@ VP_API int vp_draw_poses(vp_handle h, const vp_image* images, int32_t n_images, 
 VP_API int vp_dbg_draw_host(const vp_image* images, int32_t n_images, const float* kpts, int32_t n, int32_t k, const int32_t* frame_idx, int32_t frame_stride,
                             const int32_t* rank, const int32_t* ids, const float* boxes, int32_t box_stride, const vp_draw_cfg* cfg);
 
+/* Track-id and score tags on device frames, the stage IN FRONT of vp_draw_poses_stream (modelled on the reference's draw_bboxes, vit_utils/inference.py:19-38:
+ * `#<id>: <score>` on a filled tag at the top-left corner of every tracked box; csrc/labelgeom.h states the arithmetic once for the kernels and the host taps).
+ * The font is this library's own 5 x 7 bitmap font over 16 symbols (# 0-9 : . - space and one spare): parity against OpenCV's Hershey font is unpinned and not
+ * claimed.  Off unless called.
+ * A row is one person: d_boxes (REQUIRED) float32 (x1, y1, x2, y2) at d_boxes + i * box_stride, a frame index at d_frame_idx + i * frame_stride (a row whose index
+ * is outside [0, n_images) gets no tag), d_rank (may be NULL) int32 [n]: no tag for rank < 0, d_ids (may be NULL: the row's index) int32 [n], d_scores (may be NULL)
+ * float32 at d_scores + i * score_stride -- the rows of vp_tracker_update_stream pass in place: d_boxes = rows, box_stride = 6, d_scores = rows + 4, score_stride = 6.
+ *   Gates: the four box values usable (-16384 < v < 16384, never NaN: an absent tracker row draws nothing); corners truncated, then ordered.
+ *   Text: `#<id>` (int32 in decimal), and `: <score>` iff d_scores, cfg->show_score and -1000 < s < 1000; the score text equals printf-style "%.2f" of the exact
+ *   binary value, ties to even (0.125 -> 0.12, 0.375 -> 0.38), the sign from the sign bit (-0.0 -> -0.00); integer arithmetic only.  At most 22 characters.
+ *   Geometry (int32): scale s = cfg->scale in 1..8, 0 for max(1, min(h, w) / 400) of the row's frame capped at 8; with L characters the tag is the block
+ *   [x1, x1 + s (6 L + 1)) x [by, by + 9 s), by = y1 - 9 s when that is >= 0, else y1 (inside the box); glyph c at (x1 + s + 6 s c, by + s), every font bit an
+ *   s x s square; clipped to the frame, never shifted.
+ *   Colours: background colors[id mod n_colors] (mathematical mod); ink cfg->ink, or with auto_ink black when 77 R + 150 G + 29 B >= 32768 for the background and
+ *   white otherwise.  NV12 as vp_draw_poses_stream.  Order index of a primitive 2 * row + (ink ? 1 : 0): a pixel shows the covering primitive with the highest
+ *   one, a chroma sample the highest among its up-to-four pixels.  No byte outside a covered pixel or chroma sample is written; every written byte once per call.
+ * vp_draw_labels_stream only enqueues on caller_stream (two kernels per 32 frames of the table; font, palette and frame table travel by kernel argument): no
+ * synchronisation, no copy from host memory, no allocation.  The records live in a workspace of the handle (VP_LABEL_MAX_ROWS, allocated by vp_create): calls on one
+ * handle from different streams are the caller's to order.  `images` are DEVICE frames and this entry WRITES through their plane pointers.  cfg is HOST memory.
+ * VP_ERR_INVALID before anything is enqueued: NULL cfg; n < 0 or n > VP_LABEL_MAX_ROWS; a NULL images / d_boxes / d_frame_idx or n_images < 1 with n > 0; scale
+ * outside 0..8; n_colors outside 1..VP_DRAW_MAX_COLORS or a NULL table; a stride < 1 (score_stride with scores only); the per-image refusals of
+ * vp_draw_poses_stream; a plane that is not device memory of the handle's device inside one allocation.  n = 0: VP_OK, nothing enqueued.
+ * vp_draw_labels: the synchronous twin on host pointers and host planes (upload, the same kernels, download).
+ * vp_dbg_draw_labels_host: HOST ONLY, no device needed: csrc/labelgeom.h on host planes, rows in order (a test tap, never a fallback); the same refusals, the reason
+ * in vp_last_error(NULL).  vp_dbg_label_text: HOST ONLY, the text of a tag as characters (the spare symbol as '?'), NUL-terminated, out holds 25 bytes.
+ * vp_dbg_label_glyph: HOST ONLY, the 35 bits of glyph `code` (bit 5 * row + col; 0 for a code outside 0..15).  Library builds that carry the stage define
+ * VP_HAS_DRAW_LABELS. */
+#define VP_HAS_DRAW_LABELS 1
+#define VP_LABEL_MAX_ROWS 8192
+typedef struct vp_label_cfg {
+    int32_t scale;                          /* 1..8; 0: max(1, min(h, w) / 400) per frame, at most 8 */
+    int32_t n_colors; const uint8_t* colors; /* host [n, 3] RGB: the background of a tag is colors[id mod n] */
+    int32_t auto_ink;                       /* non-zero: black or white ink by the background's luma; 0: `ink` */
+    uint8_t ink[3];                         /* RGB */
+    int32_t show_score;                     /* 0: the id alone even when scores are given */
+} vp_label_cfg;
+VP_API int vp_draw_labels_stream(vp_handle h, const vp_image* images, int32_t n_images, const float* d_boxes, int32_t box_stride, int32_t n,
+                                 const int32_t* d_frame_idx, int32_t frame_stride, const int32_t* d_rank, const int32_t* d_ids, const float* d_scores,
+                                 int32_t score_stride, const vp_label_cfg* cfg, void* caller_stream);
+VP_API int vp_draw_labels(vp_handle h, const vp_image* images, int32_t n_images, const float* boxes, int32_t box_stride, int32_t n, const int32_t* frame_idx,
+                          int32_t frame_stride, const int32_t* rank, const int32_t* ids, const float* scores, int32_t score_stride, const vp_label_cfg* cfg);
+VP_API int vp_dbg_draw_labels_host(const vp_image* images, int32_t n_images, const float* boxes, int32_t box_stride, int32_t n, const int32_t* frame_idx,
+                                   int32_t frame_stride, const int32_t* rank, const int32_t* ids, const float* scores, int32_t score_stride,
+                                   const vp_label_cfg* cfg);
+VP_API int vp_dbg_label_text(int32_t id, int32_t has_score, float score, char* out);
+VP_API uint64_t vp_dbg_label_glyph(int32_t code);
+
 /* The box tracker on the device, the stage IN FRONT of a boxes entry: SORT as the reference's video path runs it (sort.py Sort.update behind inference.py:247-249;
  * csrc/sortgeom.h states the arithmetic once for the kernels and the host taps, easy_vitpose_amd/tracker.py is the Python twin).  A tracker object holds n_streams
  * independent SORT states (one per camera: the multi-frame shape of vp_infer_frames and of the NMS) in device memory of the handle's device; a stream holds at most
