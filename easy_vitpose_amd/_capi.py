@@ -44,6 +44,7 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_dbg_decode_affine_flip',
            'vp_draw_poses_stream', 'vp_draw_poses', 'vp_dbg_draw_host',
            'vp_draw_labels_stream', 'vp_draw_labels', 'vp_dbg_draw_labels_host', 'vp_dbg_label_text', 'vp_dbg_label_glyph',
+           'vp_collect_bytes', 'vp_collect_stream', 'vp_collect', 'vp_dbg_collect_host',
            'vp_tracker_create', 'vp_tracker_destroy', 'vp_tracker_reset_stream', 'vp_tracker_update_stream', 'vp_tracker_update', 'vp_tracker_state_bytes',
            'vp_tracker_download_state', 'vp_dbg_track_host', 'vp_dbg_lsap', 'vp_tracker_update_counted_stream',
            'vp_detector_create', 'vp_detector_destroy', 'vp_detect_stream', 'vp_detect', 'vp_dbg_detect_host',
@@ -273,6 +274,11 @@ def load_library():
     lib.vp_dbg_draw_labels_host.argtypes = label_host
     lib.vp_dbg_label_text.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_char_p]
     lib.vp_dbg_label_glyph.argtypes = [C.c_int32]
+    collect_host = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.vp_collect_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.vp_collect_stream.argtypes = [H] + collect_host + [C.c_void_p]
+    lib.vp_collect.argtypes = [H] + collect_host
+    lib.vp_dbg_collect_host.argtypes = collect_host
     trk_io = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.vp_tracker_create.argtypes = [H, C.POINTER(vp_track_cfg), C.POINTER(C.c_void_p)]
     lib.vp_tracker_destroy.argtypes = [C.c_void_p]
@@ -310,6 +316,7 @@ def load_library():
         if name not in ('vp_stream', 'vp_last_error', 'vp_host_alloc', 'vp_host_free', 'vp_group_member', 'vp_group_last_error'):
             getattr(lib, name).restype = C.c_int
     lib.vp_dbg_label_glyph.restype = C.c_uint64
+    lib.vp_collect_bytes.restype = C.c_int64
     _lib = lib
     return lib
 

@@ -203,7 +203,8 @@ struct vp_ctx {
     float* cs_stage = nullptr;        // ... and its (cx, cy, S_w, S_h) rows, what the affine decode reads [max_batch][4]
     void* draw_ws = nullptr;          // vp_draw_poses_stream: the primitive records of the current call, VP_DRAW_MAX_RECORDS keys then as many bodies (drawgeom.h), allocated by vp_create
     void* label_ws = nullptr;         // vp_draw_labels_stream: the tag records of the current call, VP_LABEL_MAX_ROWS of 40 bytes (labelgeom.h), allocated by vp_create
-    int32_t* box_aux = nullptr;       // vp_infer_boxes_stream: per box of the current chunk (y0 - top_pad, x0 - left_pad, status, 0) [max_batch][4]
+    void* collect_ws = nullptr;       // vp_collect_stream: record index and id of every row of the current call, kept rows per frame (collect.hip CollectWs), allocated by vp_create
+    int32_t* box_aux = nullptr;      // vp_infer_boxes_stream: per box of the current chunk (y0 - top_pad, x0 - left_pad, status, 0) [max_batch][4]
     // ViTPose+ (multi-dataset "mixture of experts") handle, vp_load_weights on a state dict with backbone.blocks.*.mlp.experts.*: mlp.fc2 of block l is one full
     // [D, 4D] matrix + [D] bias per expert (the split model's: shared rows then the expert's P rows), blocks[l].w_fc2 / b_fc2 point at expert 0 and expert e lies
     // e * fc2_w_stride / fc2_b_stride elements behind; one keypoint head per expert.  `expert` = the active one (vp_set_expert): its fc2 slice, its head and its

@@ -229,6 +229,7 @@ int vp_create(vp_handle* out, const vp_config* cfg) {
     if ((rc = dalloc(c, &c->zero, (size_t)256))) return bail(rc);
     if ((rc = dalloc(c, (char**)&c->draw_ws, (size_t)VP_DRAW_MAX_RECORDS * 48))) return bail(rc);   // 16-byte keys + 32-byte bodies: the stream entry allocates nothing
     if ((rc = dalloc(c, (char**)&c->label_ws, (size_t)VP_LABEL_MAX_ROWS * 40))) return bail(rc);   // 40-byte tag records: vp_draw_labels_stream allocates nothing
+    if ((rc = dalloc(c, (char**)&c->collect_ws, (size_t)(2 * VP_COLLECT_MAX_ROWS + VP_COLLECT_MAX_FRAMES) * 4))) return bail(rc);   // vp_collect_stream allocates nothing
     if (hipMemset(c->zero, 0, 512) != hipSuccess) { c->err = "hipMemset"; return bail(VP_ERR_HIP); }
     *out = c;
     return VP_OK;

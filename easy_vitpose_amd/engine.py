@@ -599,6 +599,21 @@ class VitPoseHip:
         from .devsmooth import DeviceSmoother, SmoothCfg
         return DeviceSmoother(self, self.K, SmoothCfg() if cfg is None else cfg)
 
+    # ------------------------------------------------------------ packed result
+    def collect(self, kpts, ids=None, frame=None, rank=None, status=None, score=None, crop_params=None, n_frames: int = 1, max_records=None, out=None):
+        """The kept persons of a call packed into one dense record table on the device (vp_collect_stream, contract in include/vitpose_hip.h and
+        csrc/collectgeom.h), stream-ordered on torch's current stream without a host synchronisation: the stage behind `infer_boxes`, `pose_nms` and
+        `smoother().update`.  `kpts`: float32 CUDA [n, K, 3]; `ids`, `frame`, `rank`, `status`: int32 CUDA [n] or None; `score`: float32 CUDA [n] with any
+        positive element stride, such as the column view `rows[:, 4]`, or None; `crop_params`: int32 CUDA [n, 9] or None; `max_records`: None = n.  Returns the
+        uint8 device table (`out`, or a new tensor): one copy to the host, then `devcollect.parse_records`."""
+        from .devcollect import collect_device
+        return collect_device(self, kpts, ids, frame, rank, status, score, crop_params, n_frames, max_records, out)
+
+    def collect_host(self, kpts, ids=None, frame=None, rank=None, status=None, score=None, crop_params=None, n_frames: int = 1, max_records=None, out=None):
+        """`collect` on numpy arrays (vp_collect: upload, the same kernels, download, synchronous).  Returns the uint8 table."""
+        from .devcollect import collect_host
+        return collect_host(self, kpts, ids, frame, rank, status, score, crop_params, n_frames, max_records, out)
+
     # ------------------------------------------------------------ skeleton overlay
     def _draw_skeleton(self, style: DrawStyle, K: int) -> np.ndarray:
         """the limb table of a call.  The handle of a plain checkpoint does not know its dataset: its 17 joints are taken as COCO's when `style.skeleton` is None

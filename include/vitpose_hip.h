@@ -582,6 +582,42 @@ VP_API int vp_dbg_draw_labels_host(const vp_image* images, int32_t n_images, con
 VP_API int vp_dbg_label_text(int32_t id, int32_t has_score, float score, char* out);
 VP_API uint64_t vp_dbg_label_glyph(int32_t code);
 
+/* The collect stage, BEHIND vp_infer_boxes_stream, its NMS and the smoother: the persons a call keeps packed into ONE dense record table, so that one device-to-host
+ * copy yields what the reference's inference() returns, `{id: keypoints}` per frame (csrc/collectgeom.h states the contract once for the kernels and the host tap,
+ * easy_vitpose_amd/devcollect.py restates it in numpy).  Off unless called.
+ * n rows, 0 <= n <= VP_COLLECT_MAX_ROWS, on n_frames in 1..VP_COLLECT_MAX_FRAMES frames; d_kpts float32 [n, k, 3], 1 <= k <= 133 (REQUIRED with n > 0).  Every
+ * other input may be NULL: d_ids int32 [n] (NULL: a row's id is its ordinal among the rows of its own frame in call order -- every row with a valid frame index
+ * counts, kept or not: the reference's range(len(bboxes))), d_frame int32 [n] (NULL: frame 0), d_rank int32 [n] (the NMS's rank), d_status int32 [n] (the boxes
+ * entry's status), d_score float32 at d_score + i * score_stride (the NMS's score, or column 4 of the tracker's rows in place; NULL: 0.0), d_crop_params int32
+ * [n, 9] (the boxes entry's rows {frame, x0, y0, cw, ch, ...}; NULL: a box of four zeros).
+ *   Kept: 0 <= frame < n_frames, id >= 0 when ids are given (an absent tracker row has id -1), rank >= 0 when ranks are given, status == 0 when a status is given.
+ *   Output, vp_collect_bytes(n_frames, k, max_records) bytes: a header int32 [n_frames + 1] = the kept rows of every frame and the TRUE total last, whatever
+ *   max_records is, zero-padded to a multiple of 16 bytes; then records of S = 4 ceil((8 + 3 k) / 4) 4-byte words: id, frame, the row's index in the call (int32),
+ *   score (float32), box int32 (x0, y0, x0 + cw, y0 + ch) -- the padded and clipped box the reference writes back into bboxes --, the row's 3 k keypoint words bit
+ *   for bit (a NaN keeps its payload), zeros.  Records by frame ascending, then in call order: the order of the reference's dict for one frame and of its list of
+ *   dicts for several.  The first min(total, max_records) records are written; no byte behind the last written record is touched; every written byte is written
+ *   once per call.  The order is decided without atomics: the table is a pure function of the inputs.
+ * vp_collect_stream only enqueues on caller_stream (two kernels; every input travels by kernel argument): no synchronisation, no copy from host memory, no
+ * allocation.  The record index and the id of every row live in a workspace of the handle (2 VP_COLLECT_MAX_ROWS + VP_COLLECT_MAX_FRAMES int32, allocated by
+ * vp_create): calls on one handle from different streams share it and are the caller's to order.
+ * VP_ERR_INVALID before anything is enqueued: n, n_frames or k outside their ranges; max_records < 0; NULL d_kpts with n > 0; NULL d_out; score_stride < 1; a
+ * d_out that is not 16-byte aligned.  n = 0 writes a zero header and nothing else.
+ * vp_collect_bytes: the size of the table, -1 for n_frames or k outside their ranges or max_records < 0.
+ * vp_collect: the synchronous twin on host pointers (upload, the same kernels, download of the header and of the written records only).
+ * vp_dbg_collect_host: HOST ONLY, no device needed: csrc/collectgeom.h on host memory, rows in order (a test tap, never a fallback); the same refusals, the reason in
+ * vp_last_error(NULL).  Library builds that carry the stage define VP_HAS_COLLECT. */
+#define VP_HAS_COLLECT 1
+#define VP_COLLECT_MAX_ROWS 8192
+#define VP_COLLECT_MAX_FRAMES 64
+VP_API int64_t vp_collect_bytes(int32_t n_frames, int32_t k, int32_t max_records);
+VP_API int vp_collect_stream(vp_handle h, const float* d_kpts, int32_t n, int32_t k, const int32_t* d_ids, const int32_t* d_frame, const int32_t* d_rank,
+                             const int32_t* d_status, const float* d_score, int32_t score_stride, const int32_t* d_crop_params, int32_t n_frames,
+                             int32_t max_records, void* d_out, void* caller_stream);
+VP_API int vp_collect(vp_handle h, const float* kpts, int32_t n, int32_t k, const int32_t* ids, const int32_t* frame, const int32_t* rank, const int32_t* status,
+                      const float* score, int32_t score_stride, const int32_t* crop_params, int32_t n_frames, int32_t max_records, void* out);
+VP_API int vp_dbg_collect_host(const float* kpts, int32_t n, int32_t k, const int32_t* ids, const int32_t* frame, const int32_t* rank, const int32_t* status,
+                               const float* score, int32_t score_stride, const int32_t* crop_params, int32_t n_frames, int32_t max_records, void* out);
+
 /* The box tracker on the device, the stage IN FRONT of a boxes entry: SORT as the reference's video path runs it (sort.py Sort.update behind inference.py:247-249;
  * csrc/sortgeom.h states the arithmetic once for the kernels and the host taps, easy_vitpose_amd/tracker.py is the Python twin).  A tracker object holds n_streams
  * independent SORT states (one per camera: the multi-frame shape of vp_infer_frames and of the NMS) in device memory of the handle's device; a stream holds at most
