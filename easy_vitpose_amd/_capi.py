@@ -51,7 +51,7 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_letterbox_plan', 'vp_letterbox_stream', 'vp_letterbox', 'vp_dbg_letterbox_host',
            'vp_smoother_create', 'vp_smoother_destroy', 'vp_smoother_reset_stream', 'vp_smooth_update_stream', 'vp_smooth_update', 'vp_smoother_state_bytes',
            'vp_smoother_download_state', 'vp_dbg_smooth_host',
-           'vp_dbg_head_case']
+           'vp_dbg_head_case', 'vp_dbg_im2col', 'vp_dbg_layernorm_planes']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -233,6 +233,8 @@ def load_library():
     lib.vp_dbg_gemm_case_lnpart.argtypes = [C.c_int32] * 9 + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 2
     lib.vp_dbg_ln_quant.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 4
     lib.vp_dbg_head_case.argtypes = [C.c_int32] * 9 + [C.c_void_p, C.POINTER(vp_tensor_desc), C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    lib.vp_dbg_im2col.argtypes = [C.c_int32] * 6 + [C.c_void_p] * 3
+    lib.vp_dbg_layernorm_planes.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 6
     lib.vp_set_flip_test.argtypes = [H, C.c_void_p, C.c_int32, C.c_int32]
     lib.vp_clear_flip_test.argtypes = [H]
     lib.vp_flip_test_enabled.argtypes = [H]

@@ -261,6 +261,62 @@ VP_API int vp_dbg_layernorm(int32_t device, int32_t dtype, int32_t M, int32_t D,
     return dbg_finish(c, download16(c, d16, out16, MD));
 }
 
+// The last_norm launch of the default path (tests/test_gpu_final_ln.py): layernorm_kernel<Ty, PLANES = true> on the two-plane residual stream.  hi_bits / lo_bits
+// [plane_rows, D] = the planes as 16-bit codes of `dtype`, uploaded as ONE buffer with plane = plane_rows * D between them (forward.hip lays the stream out for the
+// encoder's padded row count and normalises the caller's M <= plane_rows rows).  out16 [plane_rows, D] = the stored codes as exact fp32, out32 [plane_rows, D] = the
+// fp32 result; both device outputs are filled with 0xFF bytes before the launch: an unwritten row returns as NaN, a written row >= M shows.
+VP_API int vp_dbg_layernorm_planes(int32_t device, int32_t dtype, int32_t M, int32_t plane_rows, int32_t D, const uint16_t* hi_bits, const uint16_t* lo_bits,
+                                   const float* gamma, const float* beta, float* out16, float* out32) {
+    if (M <= 0 || plane_rows < M || plane_rows > (1 << 20) || D <= 0 || (D & 3) || D > 1280 || !hi_bits || !lo_bits || !gamma || !beta || !out16 || !out32 ||
+        (dtype != VP_DTYPE_F16 && dtype != VP_DTYPE_BF16))
+        return fail(nullptr, VP_ERR_INVALID, "bad layernorm planes case");
+    vp_ctx* c = dbg_ctx(device, dtype);
+    if (!c) return VP_ERR_HIP;
+    const size_t PD = (size_t)plane_rows * D;
+    uint16_t *dx, *d16;
+    float *dg, *db, *d32;
+    int rc;
+    if ((rc = upload_planes(c, &dx, nullptr, hi_bits, lo_bits, PD)) || (rc = upload_f32(c, &dg, gamma, D)) || (rc = upload_f32(c, &db, beta, D)) ||
+        (rc = dalloc(c, &d32, PD)) || (rc = dalloc(c, &d16, PD)))
+        return dbg_finish(c, rc);
+    hipError_t e = hipMemset(d32, 0xff, PD * 4);
+    if (e == hipSuccess) e = hipMemset(d16, 0xff, PD * 2);
+    if (e == hipSuccess) e = vp::layernorm_launch(c->dtype, (const float*)dx, dg, db, d16, d32, M, D, nullptr, PD);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out32, d32, PD * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, std::string("layernorm planes: ") + hipGetErrorString(e)));
+    return dbg_finish(c, download16(c, d16, out16, PD));
+}
+
+// The patch gather alone (tests/test_gpu_patch_gather.py): mode 0 = im2col_launch(flip = false), 1 = im2col_launch(flip = true), 2 = im2col_twin_launch.  crops = host
+// fp32 [n_src,3,256,192] (VP_INPUT_F32_NCHW) or uint8 [n_src,256,192,3] (VP_INPUT_U8_NHWC); modes 0 / 1: B output crops from n_src <= B source crops (the last one
+// repeated), mode 2: 2 n_src interleaved output crops (crop, mirror) + padding.  out_bits [B * 192 * 768] = the 16-bit codes exactly as the kernel stored them.  The device
+// output is filled with 0xFF bytes before the launch and followed by 192 * 768 guard elements (one output crop), which come back as bytes in guard [2 * 192 * 768].
+// What the launchers refuse (twin with 2 n_src > B, an unknown input format) comes back as an error, nothing is launched.
+VP_API int vp_dbg_im2col(int32_t device, int32_t dtype, int32_t input_format, int32_t mode, int32_t B, int32_t n_src, const void* crops, uint16_t* out_bits,
+                         uint8_t* guard) {
+    if (mode < 0 || mode > 2 || B <= 0 || B > 4096 || n_src <= 0 || n_src > B || !crops || !out_bits || !guard || (dtype != VP_DTYPE_F16 && dtype != VP_DTYPE_BF16))
+        return fail(nullptr, VP_ERR_INVALID, "bad im2col case");
+    vp_ctx* c = dbg_ctx(device, dtype);
+    if (!c) return VP_ERR_HIP;
+    const size_t crop_bytes = input_format == VP_INPUT_F32_NCHW ? (size_t)3 * 256 * 192 * 4 : input_format == VP_INPUT_U8_NHWC ? (size_t)256 * 192 * 3 : 0;
+    const size_t out_n = (size_t)B * 192 * 768, G = (size_t)192 * 768;
+    char* din;
+    uint16_t* dout;
+    int rc;
+    if ((rc = dalloc(c, &din, crop_bytes ? crop_bytes * n_src : (size_t)256)) || (rc = dalloc(c, &dout, out_n + G))) return dbg_finish(c, rc);
+    hipError_t e = crop_bytes ? hipMemcpy(din, crops, crop_bytes * n_src, hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess) e = hipMemset(dout, 0xff, (out_n + G) * 2);
+    if (e == hipSuccess)
+        e = mode == 2 ? vp::im2col_twin_launch(c->dtype, din, input_format, dout, B, n_src, nullptr)
+                      : vp::im2col_launch(c->dtype, din, input_format, dout, B, nullptr, mode == 1, n_src);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out_bits, dout, out_n * 2, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(guard, dout + out_n, G * 2, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = fail(c, VP_ERR_HIP, std::string("im2col: ") + hipGetErrorString(e));
+    return dbg_finish(c, rc);
+}
+
 // ConvTranspose2d(Cin,256,4,2,1,bias=False)+BN(eval)+ReLU on NHWC x [B,Hin,Win,Cin] fp32 -> NHWC [B,2Hin,2Win,256] fp32.
 // tensors = {"keypoint_head.deconv_layers.0.weight", ".1.weight", ".1.bias", ".1.running_mean", ".1.running_var"}
 VP_API int vp_dbg_deconv(int32_t device, int32_t dtype, int32_t B, int32_t Hin, int32_t Win, int32_t Cin, const float* x,

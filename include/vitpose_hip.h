@@ -937,6 +937,21 @@ VP_API int vp_dbg_qkvattn(int32_t device_id, int32_t dtype, int32_t npairs, int3
 /* LayerNorm(eps=1e-6) of x [M,D]: out16 = result rounded to dtype (returned as fp32), out32 = fp32 result */
 VP_API int vp_dbg_layernorm(int32_t device_id, int32_t dtype, int32_t M, int32_t D, const float* x,
                             const float* gamma, const float* beta, float* out16, float* out32);
+/* The last_norm launch of the default path (tests/test_gpu_final_ln.py): the same LayerNorm reading the two-plane residual stream.  hi_bits / lo_bits
+ * [plane_rows, D] = the planes as 16-bit codes of `dtype`, uploaded as one buffer with plane = plane_rows * D (the stream is laid out for the encoder's padded
+ * row count); the kernel is launched for M <= plane_rows rows.  out16 / out32 [plane_rows, D]: the stored codes as exact fp32 / the fp32 result; both device
+ * outputs are filled with 0xFF bytes first, so an unwritten row returns as NaN and a written row >= M shows.  D % 4 == 0, D <= 1280. */
+VP_API int vp_dbg_layernorm_planes(int32_t device_id, int32_t dtype, int32_t M, int32_t plane_rows, int32_t D, const uint16_t* hi_bits,
+                                   const uint16_t* lo_bits, const float* gamma, const float* beta, float* out16, float* out32);
+/* The patch gather alone (tests/test_gpu_patch_gather.py): crops -> the patch matrix [B * 192, 768] of PatchEmbed's conv (k 16, s 16, padding 2), row
+ * b * 192 + py * 12 + px, column c * 256 + ky * 16 + kx.  mode 0 = the straight gather, 1 = the crops mirrored left-right, 2 = the flip-test twin gather (output
+ * crop 2i = crop i, 2i + 1 = its mirror).  crops = host fp32 [n_src,3,256,192] (VP_INPUT_F32_NCHW) or uint8 [n_src,256,192,3] (VP_INPUT_U8_NHWC, normalised on
+ * the device); modes 0 / 1: output crops n_src .. B - 1 repeat source crop n_src - 1; mode 2: output crops 2 n_src .. B - 1 repeat output crop 2 n_src - 1.
+ * out_bits [B * 192 * 768] = the 16-bit codes as the kernel stored them.  The device output is filled with 0xFF bytes before the launch and followed by
+ * 192 * 768 guard elements, returned as bytes in guard [2 * 192 * 768].  What the launchers refuse (mode 2 with 2 n_src > B, an unknown input_format) comes
+ * back as an error, nothing is launched. */
+VP_API int vp_dbg_im2col(int32_t device_id, int32_t dtype, int32_t input_format, int32_t mode, int32_t B, int32_t n_src, const void* crops,
+                         uint16_t* out_bits, uint8_t* guard);
 /* ConvTranspose2d(Cin,256,4,2,1)+BN(eval)+ReLU (topdown_heatmap_simple_head.py:303-319) on NHWC
  * x [B,Hin,Win,Cin] -> NHWC [B,2Hin,2Win,256]; tensors named keypoint_head.deconv_layers.{0,1}.* */
 VP_API int vp_dbg_deconv(int32_t device_id, int32_t dtype, int32_t B, int32_t Hin, int32_t Win, int32_t Cin,
