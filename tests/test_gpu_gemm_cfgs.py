@@ -8,7 +8,8 @@ The dispatch of the tiles is generated from csrc/tiles.h, so every product tile 
 class here, and the two configuration matrices also run on bf16.
 The data here are Gaussians and the residual taps return hi + lo summed: the edge values of the residual producer row (the fp16 clamp, fp16 subnormals and signed zeros in the
 planes, rows with a large common offset, the association st + (hi + lo), the in-place update) and the planes and statistics bit for bit against a host model live in
-tests/test_gpu_residual_row.py."""
+tests/test_gpu_residual_row.py.  GELU over its whole domain (saturation, the negative tail, fp16-subnormal outputs, x off the 16-bit grid) at every site, fc1 and fc2
+per element at every model's widths (D = 384 / 1024 / 1280 beside the 768 of this file) and the blocked hand-over by position live in tests/test_gpu_mlp.py."""
 import ctypes as C
 
 import numpy as np
