@@ -49,6 +49,7 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_tracker_download_state', 'vp_dbg_track_host', 'vp_dbg_lsap', 'vp_tracker_update_counted_stream',
            'vp_detector_create', 'vp_detector_destroy', 'vp_detect_stream', 'vp_detect', 'vp_dbg_detect_host',
            'vp_letterbox_plan', 'vp_letterbox_stream', 'vp_letterbox', 'vp_dbg_letterbox_host',
+           'vp_orient_plan', 'vp_orient_stream', 'vp_orient', 'vp_dbg_orient_host',
            'vp_smoother_create', 'vp_smoother_destroy', 'vp_smoother_reset_stream', 'vp_smooth_update_stream', 'vp_smooth_update', 'vp_smoother_state_bytes',
            'vp_smoother_download_state', 'vp_dbg_smooth_host',
            'vp_dbg_head_case', 'vp_dbg_im2col', 'vp_dbg_layernorm_planes']
@@ -305,6 +306,11 @@ def load_library():
     lib.vp_letterbox_stream.argtypes = [H] + lb_io + [C.c_void_p] + lb_tabs + [C.c_void_p]
     lib.vp_letterbox.argtypes = [H] + lb_io + [C.c_void_p] + lb_tabs
     lib.vp_dbg_letterbox_host.argtypes = lb_io + [C.c_void_p] + lb_tabs
+    orient_io = [C.POINTER(vp_image), C.c_void_p, C.POINTER(vp_image), C.c_int32]
+    lib.vp_orient_plan.argtypes = [C.POINTER(vp_image), C.c_void_p, C.c_int32, C.POINTER(vp_image), C.c_void_p]
+    lib.vp_orient_stream.argtypes = [H] + orient_io + [C.c_void_p]
+    lib.vp_orient.argtypes = [H] + orient_io
+    lib.vp_dbg_orient_host.argtypes = orient_io
     smooth_io = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vp_smoother_create.argtypes = [H, C.POINTER(vp_smooth_cfg), C.POINTER(C.c_void_p)]
     lib.vp_smoother_destroy.argtypes = [C.c_void_p]

@@ -26,6 +26,9 @@ the boxes then come from the detector stage (``devdetect``, ``VitInference(detec
 tracked box of a video (csrc/labelgeom.h, this project's own bitmap font), ``--label-scale S`` sets its size (pixels per font bit, 1..8; implies ``--labels``).
 Not rebuilt (outside the hot path): preview windows (``--show``: OpenCV) and video
 decoding -- a video is accepted as a ``.npy`` stack ``[frames, H, W, 3]`` uint8 RGB, or as a directory of image files.
+``--rotate`` turns the input counter-clockwise as the reference's option does; ``--rotate-on device`` leaves the frames as read and turns them on the GPU
+(``VitInference(rotate=)``, the orient stage of ``devorient``).  For a single image file (and a directory of images) the host route inherits the reference's
+``Image.rotate(angle)``, which keeps the canvas and cuts the picture at 90 / 270; the device route is the true rotation the reference applies to video.
 ``--boxes`` (JSON: one ``[[x1, y1, x2, y2, conf], ...]`` list per frame, or a single list used for every frame) replaces the
 detector when ultralytics is not installed (there is no network in the build image to fetch it or its weights).
 """
@@ -55,6 +58,11 @@ def _read_frames(path: str, rotate: int):
     assert ext not in ('avi', 'mp4', 'mov'), 'video decoding needs OpenCV: convert the clip to a .npy frame stack or a directory of images'
     from PIL import Image
     return [np.array(Image.open(path).convert('RGB').rotate(rotate))], False
+
+
+def rotate_arguments(args):
+    """--rotate / --rotate-on -> (the angle `_read_frames` turns the frames by on the host, VitInference's rotate=): one of the two is 0"""
+    return (0, args.rotate) if args.rotate_on == 'device' else (args.rotate, 0)
 
 
 def flip_test_argument(args):
@@ -164,7 +172,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--model-name', default=None, choices=['s', 'b', 'l', 'h'])
     ap.add_argument('--yolo-size', type=int, default=320)
     ap.add_argument('--conf-threshold', type=float, default=0.5)
-    ap.add_argument('--rotate', type=int, default=0, choices=[0, 90, 180, 270])
+    ap.add_argument('--rotate', type=int, default=0, choices=[0, 90, 180, 270], help='turn the input by this many degrees counter-clockwise before anything else')
+    ap.add_argument('--rotate-on', default='host', choices=['host', 'device'], help='--rotate: host (the default) turns the frames as they are read; device hands them '
+                    'on as read and turns them on the GPU (the orient stage, devorient), one upload per frame.  For a single image FILE the host route inherits the '
+                    'reference\'s Image.rotate(angle), which keeps the canvas and cuts the picture at 90 / 270; the device route is the true rotation the reference '
+                    'applies to video')
     ap.add_argument('--yolo-step', type=int, default=1)
     ap.add_argument('--single-pose', action='store_true')
     ap.add_argument('--tracker', default='host', choices=['host', 'device'], help='video input: the SORT box tracker on the host (tracker.Sort, the default) or on '
@@ -217,7 +229,7 @@ def main(argv=None) -> int:
     from easy_vitpose_amd import VitInference
     from easy_vitpose_amd.configs import model_shape
     from easy_vitpose_amd.jsonio import COCO17_JOINTS, save_json
-    frames, is_video = _read_frames(args.input, args.rotate)
+    frames, is_video = _read_frames(args.input, rotate_arguments(args)[0])
     dataset = args.dataset or ('coco' if not args.model else None)   # --model: VitInference reads it from the file name (a ViTPose+ file needs --dataset)
 
     detector = args.yolo
@@ -262,7 +274,7 @@ def main(argv=None) -> int:
                          yolo_step=args.yolo_step, dtype=args.dtype, max_batch=args.max_batch,
                          flip_test=flip_test_argument(args), shift_heatmap=args.shift_heatmap, pose_nms=pose_nms_argument(args),
                          crop=args.crop, box_scale=args.box_scale, skeleton=skeleton, tracker='device' if args.tracker == 'device' else None,
-                         smooth=smooth_argument(args), detect=detect, letterbox=letterbox, labels=labels)
+                         smooth=smooth_argument(args), detect=detect, letterbox=letterbox, labels=labels, rotate=rotate_arguments(args)[1])
     print(f'>>> Model loaded: {args.model or "synthetic ViTPose-" + args.synthetic.upper()}')
     print(f'>>> Running inference on {args.input}')
     base = os.path.basename(args.input.rstrip('/'))

@@ -593,6 +593,12 @@ class VitPoseHip:
         from .devletterbox import DeviceLetterbox, LetterboxCfg
         return DeviceLetterbox(self, LetterboxCfg() if cfg is None else cfg)
 
+    def orient(self):
+        """An orient stage on this handle's device (devorient.DeviceOrient over vp_orient_*): device frames as captured -- rotated, mirrored -- to upright device
+        frames, the stream-ordered stage in front of `letterbox()` and of every entry that reads a frame."""
+        from .devorient import DeviceOrient
+        return DeviceOrient(self)
+
     def smoother(self, cfg=None):
         """A keypoint smoother for this handle's K joints on its device (devsmooth.DeviceSmoother over vp_smooth_*): the stream-ordered One-Euro stage behind
         `infer_boxes` (and its NMS), keyed by the tracker's (stream, id), in front of `draw_poses`."""

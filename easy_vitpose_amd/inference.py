@@ -8,7 +8,9 @@ types.  Added: ``flip_test=`` (keyword): the reference's test-time flip averagin
 of the engine handle (a pair list, or True for the COCO-17 table); ``pose_nms=`` (keyword, a ``PoseNms``): person scores
 (keypoint confidence x box score, the reference's open note at :272) and per-frame OKS pose NMS after the pose call; ``smooth=`` (keyword, True or a
 ``SmoothCfg``): with ``is_video``, One-Euro smoothing of every tracked person's keypoints on the device (``devsmooth``; the reference's
-``post_processing/one_euro_filter.py``), keyed by the tracker's ids, before the result dict and ``draw()``.  Changed on purpose: the per-box Python loop that ran the model once per
+``post_processing/one_euro_filter.py``), keyed by the tracker's ids, before the result dict and ``draw()``; ``rotate=`` (keyword, 0 / 90 / 180 / 270 degrees
+counter-clockwise, the reference's ``--rotate``): the frames arrive as captured and are made upright on the device (``devorient``), results and ``draw()`` in
+upright-frame pixels.  Changed on purpose: the per-box Python loop that ran the model once per
 crop (:259-272) becomes ONE batched call into the C ABI (``_inference_batch``);
 ``_inference`` (single crop, :207-219) is still there and returns ``[1, K, 3]``.
 
@@ -83,12 +85,17 @@ class VitInference:
                  single_pose: Optional[bool] = False,
                  yolo_step: Optional[int] = 1,
                  *, dtype: str = 'fp16', max_batch: int = 64, tracker=None, flip_test=None, shift_heatmap: bool = False,
-                 pose_nms: Optional[PoseNms] = None, crop: str = 'pad', box_scale: float = 1.25, skeleton=None, smooth=None, detect=None, letterbox=None, labels=False):
+                 pose_nms: Optional[PoseNms] = None, crop: str = 'pad', box_scale: float = 1.25, skeleton=None, smooth=None, detect=None, letterbox=None, labels=False,
+                 rotate: int = 0):
         # crop='affine': the training-protocol crop (cropprep.box_to_cs, VitPoseHip.infer_frames(crop='affine')) instead of the pad route; refused before anything is loaded
         if crop not in ('pad', 'affine'):
             raise ValueError(f"crop: 'pad' or 'affine' expected, got {crop!r}")
         if crop == 'affine' and pose_nms is not None:
             raise ValueError("pose_nms= does not run together with crop='affine' (the NMS area is defined on the pad route's crop)")
+        # rotate: the frames arrive as captured and are turned by this many degrees counter-clockwise (the reference's --rotate) on the device (devorient); 0, 90, 180
+        # or 270, refused before anything is loaded
+        from .devorient import rotate_code
+        self._rot_code, self._rot_k, self._orient = rotate_code(rotate), int(rotate) // 90, None
         if not (tracker is None or tracker == 'device' or callable(tracker)):
             raise ValueError(f"tracker: None (the host Sort), 'device' (devtracker.DeviceSort) or a factory expected, got {tracker!r}")
         # smooth: One-Euro keypoint smoothing per tracked person (devsmooth.SmoothCfg; True = the reference's defaults); refused before anything is loaded
@@ -204,6 +211,8 @@ class VitInference:
             self._detector = self._vit_pose.detector(dataclasses.replace(self._detect_cfg, max_images=1))
         if self._letterbox_cfg is not None:
             self._letterbox = self._vit_pose.letterbox(self._letterbox_cfg)
+        if self._rot_k:
+            self._orient = self._vit_pose.orient()
         if tracker == 'device' or self._smooth_cfg is not None:   # the device tracker and the smoother live on the engine's device: built now that there is one
             self.reset()
         self._inference = self._inference_hip
@@ -259,11 +268,12 @@ class VitInference:
         rows, _, _, count, _ = self._detector.detect_host(head.reshape((1,) + head.shape[-2:]), img.shape[:2], input_hw)
         return rows[:int(count[-1]), :5]
 
-    def _letterbox_rows(self, img):
+    def _letterbox_rows(self, img, upright=None):
         """VitInference(letterbox=, detect=): the frame goes to the device once, the letterbox stage writes the detector's input tensor there, `yolo(tensor)` returns
         the raw head, and the detector stage undoes the letterbox with the table the letterbox stage returned: the [m, 5] rows in frame pixels.  A head left on the
-        device stays there (vp_detect_stream on torch's current stream); an ndarray head goes through the synchronous twin."""
-        tensor, table, _ = self._letterbox.letterbox([self._letterbox.upload(img)])
+        device stays there (vp_detect_stream on torch's current stream); an ndarray head goes through the synchronous twin.  `upright` (rotate=): the frame is on
+        the device already, made upright by the orient stage, and is read there."""
+        tensor, table, _ = self._letterbox.letterbox([self._letterbox.upload(img) if upright is None else upright])
         head = self.yolo(tensor)
         if hasattr(head, 'data_ptr'):
             rows, _, _, count, _ = self._detector.detect(head.reshape((1,) + tuple(head.shape[-2:])), table)
@@ -329,11 +339,19 @@ class VitInference:
         offsets are added per crop.  `save_state` keeps the last frame's state."""
         pad_bbox = 10
         dets = []
-        for img in imgs:
+        upright = None
+        if getattr(self, '_orient', None) is not None and len(imgs):
+            # rotate=: every frame goes to the device once, as captured, and the orient stage makes it upright there: what the letterbox stage and the pose call read.
+            # Host-side consumers (a callable detector without letterbox=, draw()'s image) take np.rot90, by the stage's contract the same bytes
+            upright = []
+            for s in range(0, len(imgs), 64):
+                upright += self._orient.orient([self._orient.upload(img) for img in imgs[s:s + 64]], self._rot_code)
+            imgs = [np.ascontiguousarray(np.rot90(img, self._rot_k)) for img in imgs]
+        for f, img in enumerate(imgs):
             res_pd = np.empty((0, 5))
             if (self.tracker is None or (self.frame_counter % self.yolo_step == 0 or self.frame_counter < 3)):
                 if self._letterbox is not None:
-                    det = self._letterbox_rows(img)
+                    det = self._letterbox_rows(img, None if upright is None else upright[f])
                 else:
                     det = self.yolo(img) if self._detector is None else self._detect_rows(img, *self.yolo(img))
                 det = np.asarray(det, dtype=np.float64).reshape((-1, 5))
@@ -351,7 +369,7 @@ class VitInference:
             dets.append((bboxes, ids, scores))
 
         # crop + zero-pad to 3:4 + resize + normalise all happen on device, each frame uploaded once
-        frames = [np.ascontiguousarray(img) for img in imgs]
+        frames = [np.ascontiguousarray(img) for img in imgs] if upright is None else upright
         if self.crop == 'affine':
             return self._affine_frames(imgs, frames, dets)
         p9 = frames_crop_params([d[0] for d in dets], [f.shape for f in frames], pad_bbox)

@@ -800,6 +800,51 @@ VP_API int vp_letterbox(vp_handle h, const vp_letterbox_cfg* cfg, const vp_image
  * vp_letterbox, the reason in vp_last_error(NULL). */
 VP_API int vp_dbg_letterbox_host(const vp_letterbox_cfg* cfg, const vp_image* images, int32_t n_images, void* out, vp_det_image* det, int32_t* placement);
 
+/* The orient stage, IN FRONT of the letterbox stage: frames as a decoder or a capture device leaves them (a landscape surface plus a rotation tag, a mirrored
+ * webcam, a ceiling camera) made upright on the device, so that every later stage -- letterbox, the frames and boxes entries, the overlays -- sees an upright
+ * frame.  A pure permutation of bytes (csrc/orientgeom.h states it once for the kernel and the host tap): equal means equal bytes.  Up to VP_ORIENT_MAX_IMAGES
+ * frames per call, which may differ in size, format, matrix and code.
+ *   codes: HOST int32 [n], the EXIF orientation values: what the output is in terms of the source plane a of h x w elements
+ *     VP_ORIENT_IDENTITY 1  a (a copy; compacts a pitched view)      h x w      VP_ORIENT_TRANSPOSE  5  a.T                              w x h
+ *     VP_ORIENT_MIRROR   2  a[:, ::-1]                               h x w      VP_ORIENT_CW90       6  out[i, j] = a[h - 1 - j, i]      w x h  (90 degrees clockwise)
+ *     VP_ORIENT_ROT180   3  a[::-1, ::-1]                            h x w      VP_ORIENT_TRANSVERSE 7  out[i, j] = a[h - 1 - j, w - 1 - i]  w x h
+ *     VP_ORIENT_FLIP     4  a[::-1, :]                               h x w      VP_ORIENT_CCW90      8  out[i, j] = a[j, w - 1 - i]      w x h  (90 degrees counter-clockwise)
+ *   An element is one byte of the Y plane, the two-byte U,V pair of the NV12 chroma plane (pair order kept), the three-byte pixel of RGB24 / BGR24 (channel order
+ *   kept).  NV12: the Y plane is oriented with (h, w), the UV plane with the same code on (ceil(h / 2), ceil(w / 2)); that keeps the chroma rule (pixel (y, x)
+ *   reads pair (y >> 1, x >> 1)) exactly when every reversed axis has even length, so an NV12 frame with an odd extent along an axis the code reverses is refused
+ *   (codes 1 and 5 take any size).  Then to_rgb(orient(f)) == orient(to_rgb(f)), byte for byte.
+ *   src, dst: HOST tables of n vp_image; dst[i] is the layout vp_orient_plan gives (h, w swapped by codes 5..8; format and matrix the source's; any pitch >= the row
+ *   bytes, so a destination may be an ROI of a larger buffer).  vp_image's plane pointers are const, and the entries below WRITE through dst's.  No byte outside
+ *   [row start, row start + row bytes) of a destination row is written or read-modify-written: the gap bytes of a pitched destination stay as they were.
+ * vp_orient_plan: HOST ONLY, no device.  Fills dst[i].h, w, format, matrix; keeps a non-zero dst[i].pitch[p] after checking it, else writes the tight pitch (0 for
+ *   an absent plane); leaves the plane pointers alone; plane_bytes [n, 2] (may be NULL) = (rows - 1) pitch + row bytes of each plane, 0 for an absent one.
+ * vp_orient_stream only enqueues on caller_stream: one launch per 32 frames (the frame records travel by kernel argument), no atomics, no synchronisation, no host
+ *   copy, no allocation, none of the handle's workspaces, so it runs under graph capture, back to back, and beside any other entry of the handle.  The handle needs
+ *   no weights.  n = 0 is legal and enqueues nothing.
+ * vp_orient: the synchronous twin, planes of both tables in host memory (upload at the caller's pitch, the same kernel, download of the row bytes of each
+ *   destination row only).
+ * VP_ERR_INVALID, before anything is enqueued and with the reason, naming the frame, in vp_last_error: NULL tables with n > 0, n outside 0..VP_ORIENT_MAX_IMAGES, a
+ *   code outside 1..8, the image refusals of vp_dbg_image_plan, h or w < 1, a NULL plane, a dst entry whose h / w / format / matrix differ from the plan's, a dst pitch
+ *   below its row bytes, the NV12 odd-axis case above, any overlap between a destination plane's byte range (first byte to last) and any source plane's or any other
+ *   destination plane's of the call (there is no in-place orientation), a device plane, source or destination, that fails the handle's allocation check.  A refused
+ *   call writes nothing.  Library builds that carry the stage define VP_HAS_ORIENT. */
+#define VP_HAS_ORIENT 1
+#define VP_ORIENT_MAX_IMAGES 64
+#define VP_ORIENT_IDENTITY   1
+#define VP_ORIENT_MIRROR     2
+#define VP_ORIENT_ROT180     3
+#define VP_ORIENT_FLIP       4
+#define VP_ORIENT_TRANSPOSE  5
+#define VP_ORIENT_CW90       6
+#define VP_ORIENT_TRANSVERSE 7
+#define VP_ORIENT_CCW90      8
+VP_API int vp_orient_plan(const vp_image* src, const int32_t* codes, int32_t n, vp_image* dst, int64_t* plane_bytes);
+VP_API int vp_orient_stream(vp_handle h, const vp_image* src, const int32_t* codes, const vp_image* dst, int32_t n, void* caller_stream);
+VP_API int vp_orient(vp_handle h, const vp_image* src, const int32_t* codes, const vp_image* dst, int32_t n);
+/* HOST ONLY, no device needed: csrc/orientgeom.h run serially on host planes, the model the device is tested against (a test tap, never a fallback); the refusals of
+ * vp_orient, the reason in vp_last_error(NULL). */
+VP_API int vp_dbg_orient_host(const vp_image* src, const int32_t* codes, const vp_image* dst, int32_t n);
+
 /* Keypoint smoothing on the device, the stage BEHIND a boxes entry (and its NMS) and in front of vp_draw_poses_stream: the One-Euro filter of the reference's
  * post_processing/one_euro_filter.py in its fixed-rate mode, one filter per (stream, track id) (csrc/eurogeom.h states the arithmetic once for the kernels and the
  * host tap, easy_vitpose_amd/smooth.py is the numpy twin).  A smoother object holds n_streams tables of VP_SMOOTH_SLOTS slots for n_joints joints in device memory
