@@ -52,6 +52,8 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_orient_plan', 'vp_orient_stream', 'vp_orient', 'vp_dbg_orient_host',
            'vp_smoother_create', 'vp_smoother_destroy', 'vp_smoother_reset_stream', 'vp_smooth_update_stream', 'vp_smooth_update', 'vp_smoother_state_bytes',
            'vp_smoother_download_state', 'vp_dbg_smooth_host',
+           'vp_metrics_create', 'vp_metrics_destroy', 'vp_metrics_reset_stream', 'vp_metrics_update_stream', 'vp_metrics_update', 'vp_metrics_snapshot_stream',
+           'vp_metrics_state_bytes', 'vp_metrics_download_state', 'vp_dbg_metrics_host',
            'vp_dbg_head_case', 'vp_dbg_im2col', 'vp_dbg_layernorm_planes']
 
 
@@ -119,6 +121,11 @@ class vp_letterbox_cfg(C.Structure):
 class vp_smooth_cfg(C.Structure):
     _fields_ = [('min_cutoff', C.c_double), ('beta', C.c_double), ('d_cutoff', C.c_double), ('max_age', C.c_int32), ('n_streams', C.c_int32),
                 ('n_joints', C.c_int32), ('max_rows', C.c_int32), ('missing', C.c_int32)]
+
+
+class vp_metrics_cfg(C.Structure):
+    _fields_ = [('auc_norm', C.c_double), ('pck_thr', C.c_float * 8), ('vis_thr', C.c_float), ('n_joints', C.c_int32), ('n_pck', C.c_int32), ('auc_steps', C.c_int32),
+                ('use_oks', C.c_int32), ('reserved', C.c_int32)]
 
 
 class vp_profile(C.Structure):
@@ -320,6 +327,16 @@ def load_library():
     lib.vp_smoother_state_bytes.argtypes = [C.POINTER(vp_smooth_cfg), C.POINTER(C.c_int64)]
     lib.vp_smoother_download_state.argtypes = [C.c_void_p, C.c_void_p]
     lib.vp_dbg_smooth_host.argtypes = [C.c_void_p, C.POINTER(vp_smooth_cfg)] + smooth_io
+    metrics_io = [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.vp_metrics_create.argtypes = [H, C.POINTER(vp_metrics_cfg), C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.vp_metrics_destroy.argtypes = [C.c_void_p]
+    lib.vp_metrics_reset_stream.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vp_metrics_update_stream.argtypes = [C.c_void_p] + metrics_io + [C.c_void_p]
+    lib.vp_metrics_update.argtypes = [C.c_void_p] + metrics_io
+    lib.vp_metrics_snapshot_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vp_metrics_state_bytes.argtypes = [C.POINTER(vp_metrics_cfg), C.POINTER(C.c_int64)]
+    lib.vp_metrics_download_state.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vp_dbg_metrics_host.argtypes = [C.c_void_p, C.POINTER(vp_metrics_cfg), C.c_void_p] + metrics_io
     for name in SYMBOLS:
         if name not in ('vp_stream', 'vp_last_error', 'vp_host_alloc', 'vp_host_free', 'vp_group_member', 'vp_group_last_error'):
             getattr(lib, name).restype = C.c_int

@@ -6,6 +6,7 @@
 //   weights.hip      -- the weight packer (vp_load_weights: BN / LayerNorm folding, 16-bit / e4m3 conversion, deconv re-tiling)
 //   tile_rules.hip   -- which GEMM tile runs a shape (pure host functions + their host-only taps)
 //   debug_taps.hip   -- vp_dbg_*: one kernel on host data (parity tests), and the measurement build's timing taps
+//   metrics.hip      -- the accumulating accuracy-metrics stage (vp_metrics_*: an object of its own beside the handle, like the tracker and the smoother)
 // Everything here is library-internal (hidden visibility); nothing of it appears in the public headers.
 #pragma once
 #include <hip/hip_runtime.h>

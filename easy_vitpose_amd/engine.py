@@ -605,6 +605,12 @@ class VitPoseHip:
         from .devsmooth import DeviceSmoother, SmoothCfg
         return DeviceSmoother(self, self.K, SmoothCfg() if cfg is None else cfg)
 
+    def metrics(self, cfg=None):
+        """An accuracy evaluator on this handle's device (devmetrics.DeviceMetrics over vp_metrics_*): PCK / AUC / EPE / NME / OKS recall of predicted rows
+        against ground-truth rows that lie on the GPU, accumulated stream-ordered without a host synchronisation and read once at the end (`result()`)."""
+        from .devmetrics import DeviceMetrics, MetricsCfg
+        return DeviceMetrics(self, MetricsCfg(n_joints=self.K) if cfg is None else cfg)
+
     # ------------------------------------------------------------ packed result
     def collect(self, kpts, ids=None, frame=None, rank=None, status=None, score=None, crop_params=None, n_frames: int = 1, max_records=None, out=None):
         """The kept persons of a call packed into one dense record table on the device (vp_collect_stream, contract in include/vitpose_hip.h and

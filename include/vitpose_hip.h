@@ -901,6 +901,67 @@ VP_API int vp_smoother_download_state(vp_smoother_handle s, void* out);
 VP_API int vp_dbg_smooth_host(void* state, const vp_smooth_cfg* cfg, const float* kpts, const int32_t* ids, const int32_t* stream, const int32_t* rank, int32_t n,
                               uint64_t step_mask, const double* t_e, float* out, int32_t* flags);
 
+/* Accuracy metrics against ground truth on the device: an ACCUMULATING stage with the life cycle of the tracker and the smoother.  An evaluator object holds the
+ * counts and sums of PCK (up to 8 thresholds), AUC, EPE, NME and OKS recall in device memory of the handle's device; every update adds the rows of one call to
+ * them on the caller's stream and the state is read once at the end.  csrc/metricsgeom.h states the arithmetic (the reference's vit_utils/top_down_eval.py
+ * _calc_distances / keypoint_pck_accuracy / keypoint_auc / keypoint_nme / keypoint_epe and post_processing/nms.py oks_iou as "ground truth against detected") and
+ * the summation order once for the kernels and the host tap; easy_vitpose_amd/devmetrics.py holds the numpy twin and finish(), which turns a state into figures.
+ *   d_pred float32 [n, n_joints, 3] rows of (y, x, conf); d_gt float32 [n, n_joints, 3] rows of (y, x, v); 0 <= n <= VP_METRICS_MAX_ROWS, n_joints in
+ *   1..VP_NMS_MAX_K.  Optional, each may be NULL: d_norm float32 [n, 2] in (y, x) order (NULL: 1.0 both); d_area float32 [n] (NULL: no OKS for this call); d_rank
+ *   int32 [n] (the row counts iff rank >= 0: the NMS's rank or the tracker's ids as they are); d_set int32 [n] with set_value (the row counts iff equal: the
+ *   per-crop dataset index of a ViTPose+ call, one evaluator per dataset).  A COUNTED row passes both filters.
+ *   Per joint of a counted row (float32, every operation rounded on its own): visible = v > vis_thr; dy = py - gy, dx = px - gx; the normalised distance
+ *   qn = sqrtf((dy / n_y)^2 + (dx / n_x)^2) with a normaliser component <= 0 replaced by 1e6 and the whole row left out of this family when a component == 0; the
+ *   pixel distance q1 = sqrtf(dy^2 + dx^2); the AUC distance qa = (float)sqrt(((double)dy / auc_norm)^2 + ((double)dx / auc_norm)^2).  valid_norm / valid_px
+ *   count the visible joints (of rows not left out / of every counted row); pck_hits[t] += qn < pck_thr[t]; auc_hits[s] += qa < (float)((double)s / auc_steps)
+ *   (strict); sum_norm += qn, sum_px += q1 in fp64.  DEVIATION from the reference: a non-finite distance is valid and never hits, but is left out of its sum and
+ *   counted in `nonfinite`; the finisher then reports NaN for EPE / NME where the reference would report inf or NaN.
+ *   OKS of a counted row (use_oks, d_area given, the area finite and > 0, at least one visible joint): csrc/posenms.h's terms over the visible joints in joint order
+ *   with both areas = area; oks_rows += 1, oks_hits[t] += oks >= (float)(0.5 + 0.05 t) for t = 0..9, oks_sum += oks; a non-finite oks bumps `nonfinite` instead.
+ *   It is the share of instances recovered at OKS t with one candidate per instance, NOT COCO AP.
+ *   Summation order, part of the contract: rows form blocks of 64; a block's partial is the balanced binary tree over its 64 rows in row order (a row that does
+ *   not contribute gives +0.0); a call's sum is ((0.0 + P(0)) + P(1)) + ... in ascending block order; the state takes state + call_sum.  The state is therefore a
+ *   pure function of the inputs and the sequence of calls, bit for bit.
+ *   State blob (vp_metrics_state_bytes = 8 (24 + n_joints (4 + n_pck + auc_steps)); zeroed = new), 8-byte words: int64 calls, rows, counted, nonfinite, oks_rows,
+ *   0, 0, 0 | int64 oks_hits[10], double oks_sum, 0 x 5 | int64 valid_norm[K] | int64 valid_px[K] | double sum_norm[K] | double sum_px[K] | int64
+ *   pck_hits[n_pck][K] | int64 auc_hits[auc_steps][K].
+ *   Optional per-call outputs, every element written once per call: d_dist float32 [n, n_joints] = qn, or -1 where the joint is not in valid_norm; d_oks float32
+ *   [n] = oks, or -1 where none.
+ * vp_metrics_update_stream only enqueues on caller_stream (two kernels: one workgroup per 64 rows writes block partials into a workspace the evaluator owns, one
+ * workgroup adds them into the state; n = 0 is legal and counts a call): no synchronisation, no host copy, no allocation, no atomics.  Calls on one evaluator from
+ * different streams are the caller's to order.  vp_metrics_reset_stream zeroes the state on caller_stream; vp_metrics_snapshot_stream copies it to d_out (device,
+ * vp_metrics_state_bytes) on caller_stream, so that a pipeline reads it without stopping.  vp_metrics_update: the synchronous twin on host pointers (upload, the same
+ * kernels, download).  vp_metrics_create: on the device of h, state zeroed; sigmas = HOST float32 [n_joints] (required with use_oks, else may be NULL); the evaluator
+ * must be destroyed before h.  vp_metrics_download_state waits for the device first.
+ * VP_ERR_INVALID before anything is enqueued, the reason in vp_last_error: a NULL cfg, NULL d_pred / d_gt with n > 0, n outside 0..VP_METRICS_MAX_ROWS, n_joints
+ * outside 1..VP_NMS_MAX_K, n_pck outside 0..8, auc_steps outside 0..32, a pck_thr in use or vis_thr not finite, auc_norm not finite or <= 0 with auc_steps > 0,
+ * use_oks without sigmas or with a sigma not finite or <= 0, a NULL snapshot destination.  Library builds that carry the stage define VP_HAS_METRICS. */
+#define VP_HAS_METRICS 1
+#define VP_METRICS_MAX_ROWS 8192
+typedef struct vp_metrics_cfg {
+    double  auc_norm;
+    float   pck_thr[8];
+    float   vis_thr;
+    int32_t n_joints, n_pck, auc_steps, use_oks;
+    int32_t reserved;
+} vp_metrics_cfg;
+typedef struct vp_metrics* vp_metrics_handle;
+VP_API int vp_metrics_create(vp_handle h, const vp_metrics_cfg* cfg, const float* sigmas, vp_metrics_handle* out);
+VP_API int vp_metrics_destroy(vp_metrics_handle m);
+VP_API int vp_metrics_reset_stream(vp_metrics_handle m, void* caller_stream);
+VP_API int vp_metrics_update_stream(vp_metrics_handle m, const float* d_pred, const float* d_gt, const float* d_norm, const float* d_area, const int32_t* d_rank,
+                                    const int32_t* d_set, int32_t set_value, int32_t n, float* d_dist, float* d_oks, void* caller_stream);
+VP_API int vp_metrics_update(vp_metrics_handle m, const float* pred, const float* gt, const float* norm, const float* area, const int32_t* rank, const int32_t* set,
+                             int32_t set_value, int32_t n, float* dist, float* oks);
+VP_API int vp_metrics_snapshot_stream(vp_metrics_handle m, void* d_out, void* caller_stream);
+VP_API int vp_metrics_state_bytes(const vp_metrics_cfg* cfg, int64_t* bytes);
+VP_API int vp_metrics_download_state(vp_metrics_handle m, void* out);
+/* HOST ONLY, no device needed: csrc/metricsgeom.h run serially on a host state blob of vp_metrics_state_bytes (zeroed = a new evaluator), honouring the summation
+ * order: the model the device is tested against (a test tap, never a fallback); the refusals of vp_metrics_create and vp_metrics_update_stream, the reason in
+ * vp_last_error(NULL). */
+VP_API int vp_dbg_metrics_host(void* state, const vp_metrics_cfg* cfg, const float* sigmas, const float* pred, const float* gt, const float* norm, const float* area,
+                               const int32_t* rank, const int32_t* set, int32_t set_value, int32_t n, float* dist, float* oks);
+
 /* HOST ONLY, no device needed: the plan those entries run for expert_ids [n] on a handle of n_experts experts and max_batch crops per chunk -- the pure function
  * ids -> order, segments that shapes their launches.  Per chunk c (crops [c max_batch, ...)), with B = max_batch rounded up to a multiple of 4:
  *   order [n]: position j of chunk c holds the chunk-local caller row order[c max_batch + j] (stable expert order)
