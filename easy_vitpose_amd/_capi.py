@@ -54,6 +54,9 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_smoother_download_state', 'vp_dbg_smooth_host',
            'vp_metrics_create', 'vp_metrics_destroy', 'vp_metrics_reset_stream', 'vp_metrics_update_stream', 'vp_metrics_update', 'vp_metrics_snapshot_stream',
            'vp_metrics_state_bytes', 'vp_metrics_download_state', 'vp_dbg_metrics_host',
+           'vp_cocoeval_create', 'vp_cocoeval_destroy', 'vp_cocoeval_reset_stream', 'vp_cocoeval_update_stream', 'vp_cocoeval_update', 'vp_cocoeval_accumulate_stream',
+           'vp_cocoeval_accumulate', 'vp_cocoeval_state_bytes', 'vp_cocoeval_result_bytes', 'vp_cocoeval_download_state', 'vp_dbg_cocoeval_update_host',
+           'vp_dbg_cocoeval_accumulate_host',
            'vp_dbg_head_case', 'vp_dbg_im2col', 'vp_dbg_layernorm_planes']
 
 
@@ -126,6 +129,10 @@ class vp_smooth_cfg(C.Structure):
 class vp_metrics_cfg(C.Structure):
     _fields_ = [('auc_norm', C.c_double), ('pck_thr', C.c_float * 8), ('vis_thr', C.c_float), ('n_joints', C.c_int32), ('n_pck', C.c_int32), ('auc_steps', C.c_int32),
                 ('use_oks', C.c_int32), ('reserved', C.c_int32)]
+
+
+class vp_cocoeval_cfg(C.Structure):
+    _fields_ = [('n_joints', C.c_int32), ('max_records', C.c_int32), ('reserved', C.c_int32 * 2)]
 
 
 class vp_profile(C.Structure):
@@ -337,6 +344,19 @@ def load_library():
     lib.vp_metrics_state_bytes.argtypes = [C.POINTER(vp_metrics_cfg), C.POINTER(C.c_int64)]
     lib.vp_metrics_download_state.argtypes = [C.c_void_p, C.c_void_p]
     lib.vp_dbg_metrics_host.argtypes = [C.c_void_p, C.POINTER(vp_metrics_cfg), C.c_void_p] + metrics_io
+    coco_io = [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p]
+    lib.vp_cocoeval_create.argtypes = [H, C.POINTER(vp_cocoeval_cfg), C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.vp_cocoeval_destroy.argtypes = [C.c_void_p]
+    lib.vp_cocoeval_reset_stream.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vp_cocoeval_update_stream.argtypes = [C.c_void_p] + coco_io + [C.c_void_p]
+    lib.vp_cocoeval_update.argtypes = [C.c_void_p] + coco_io
+    lib.vp_cocoeval_accumulate_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vp_cocoeval_accumulate.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vp_cocoeval_state_bytes.argtypes = [C.POINTER(vp_cocoeval_cfg), C.POINTER(C.c_int64)]
+    lib.vp_cocoeval_result_bytes.argtypes = [C.POINTER(C.c_int64)]
+    lib.vp_cocoeval_download_state.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vp_dbg_cocoeval_update_host.argtypes = [C.c_void_p, C.POINTER(vp_cocoeval_cfg), C.c_void_p] + coco_io
+    lib.vp_dbg_cocoeval_accumulate_host.argtypes = [C.c_void_p, C.POINTER(vp_cocoeval_cfg), C.c_void_p]
     for name in SYMBOLS:
         if name not in ('vp_stream', 'vp_last_error', 'vp_host_alloc', 'vp_host_free', 'vp_group_member', 'vp_group_last_error'):
             getattr(lib, name).restype = C.c_int

@@ -7,6 +7,7 @@
 //   tile_rules.hip   -- which GEMM tile runs a shape (pure host functions + their host-only taps)
 //   debug_taps.hip   -- vp_dbg_*: one kernel on host data (parity tests), and the measurement build's timing taps
 //   metrics.hip      -- the accumulating accuracy-metrics stage (vp_metrics_*: an object of its own beside the handle, like the tracker and the smoother)
+//   cocoeval.hip     -- the accumulating COCO keypoint AP / AR stage (vp_cocoeval_*: an object of its own beside the handle, like the metrics stage)
 // Everything here is library-internal (hidden visibility); nothing of it appears in the public headers.
 #pragma once
 #include <hip/hip_runtime.h>

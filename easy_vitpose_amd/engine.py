@@ -611,6 +611,13 @@ class VitPoseHip:
         from .devmetrics import DeviceMetrics, MetricsCfg
         return DeviceMetrics(self, MetricsCfg(n_joints=self.K) if cfg is None else cfg)
 
+    def cocoeval(self, cfg=None):
+        """A COCO keypoint AP / AR evaluator on this handle's device (devcoco.DeviceCocoEval over vp_cocoeval_*): `update` matches the detections of a batch of
+        images against their ground truth where both lie on the GPU and appends one record per kept detection, `accumulate` sorts the records into the precision /
+        recall tables, `result()` reads them once and gives the ten figures of COCOeval's summarize."""
+        from .devcoco import CocoEvalCfg, DeviceCocoEval
+        return DeviceCocoEval(self, CocoEvalCfg(n_joints=self.K) if cfg is None else cfg)
+
     # ------------------------------------------------------------ packed result
     def collect(self, kpts, ids=None, frame=None, rank=None, status=None, score=None, crop_params=None, n_frames: int = 1, max_records=None, out=None):
         """The kept persons of a call packed into one dense record table on the device (vp_collect_stream, contract in include/vitpose_hip.h and

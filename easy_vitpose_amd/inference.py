@@ -403,6 +403,7 @@ class VitInference:
                         scores_bbox[id_] = float(score[start + i])
                 start += len(bboxes)
         self._smooth_results(results)
+        self._scores_frames = [r[1] for r in results]   # `_scores_bbox` of every frame of this call (tools/evaluation_on_coco.py reads a batch's scores here)
         if self.save_state and len(imgs):
             bboxes, ids, scores = dets[-1]
             self._img = imgs[-1]
@@ -423,6 +424,7 @@ class VitInference:
             start += len(bboxes)
             results.append(({id_: kps_f[i] for i, id_ in enumerate(ids)}, {id_: score for id_, score in zip(ids, scores)}))
         self._smooth_results(results)
+        self._scores_frames = [r[1] for r in results]
         if self.save_state and len(imgs):
             self._img = imgs[-1]
             self._tracker_res = dets[-1]

@@ -962,6 +962,69 @@ VP_API int vp_metrics_download_state(vp_metrics_handle m, void* out);
 VP_API int vp_dbg_metrics_host(void* state, const vp_metrics_cfg* cfg, const float* sigmas, const float* pred, const float* gt, const float* norm, const float* area,
                                const int32_t* rank, const int32_t* set, int32_t set_value, int32_t n, float* dist, float* oks);
 
+/* COCO keypoint AP / AR on the device: an ACCUMULATING evaluator with the life cycle of vp_metrics_*.  It is COCOeval for iouType = 'keypoints' (computeOks,
+ * evaluateImg, accumulate) with fixed parameters -- one category, maxDets = 20, the area ranges all [0, 1e10], medium [32^2, 96^2], large [96^2, 1e10], the OKS
+ * thresholds np.linspace(.5, .95, 10) and the recall thresholds np.linspace(0, 1, 101) -- restated operation by operation in csrc/cocogeom.h, once for the kernels
+ * and the host taps; easy_vitpose_amd/devcoco.py holds the numpy twin and finish(), which gives the ten figures of summarize.  UNPINNED: the pycocotools binary is
+ * not available to this project's tests, the contract is a restatement of its source.
+ *   One update, coordinates in (y, x, .) order: d_kpts float32 [n, n_joints, 3], d_score float32 [n], d_frame int32 [n] (NULL: 0), d_rank int32 [n] (optional: the
+ *   row counts iff rank >= 0); d_gt_kpts float32 [g, n_joints, 3] rows of (y, x, v), d_gt_box float32 [g, 4] rows of (x, y, w, h), d_gt_area float32 [g], d_gt_flags
+ *   int32 [g] (bit 0 = iscrowd; NULL: 0), d_gt_frame int32 [g] (NULL: 0); n_frames.  0 <= n, g <= VP_COCOEVAL_MAX_ROWS, 1 <= n_frames <= VP_COCOEVAL_MAX_FRAMES.  A
+ *   row or gt whose frame lies outside [0, n_frames) does not count; rows need not be grouped by frame.  At most 128 gts per image are used; later ones, in call
+ *   order, are left out and counted in gt_overflow.
+ *   Per image: the counted rows ordered by score descending, equal scores to the lower row, a NaN score as -infinity (the order of the pose NMS); the first 20 are
+ *   kept.  area_d = (max x - min x) (max y - min y) over all joints in fp64.  Per gt: k1 = the count of v > 0, ignore0 = iscrowd || k1 == 0.  OKS in fp64 on the
+ *   float32 inputs: e_j = (dx^2 + dy^2) / (2 sigma_j)^2 / (area_g + 2^-52) / 2, over the joints with v > 0 (dx = xd - xg), or with k1 == 0 the distance to the
+ *   doubled box over all joints (x0 = bx - bw, x1 = bx + 2 bw, dx = max(0, x0 - xd) + max(0, xd - x1)); oks = sum of exp(-e_j) / count, the sum in joint order
+ *   (DEVIATION: np.sum is pairwise, a few ulps).  DEVIATION: a non-finite oks never matches and is counted in `nonfinite`.  Matching per (range, threshold):
+ *   ignore_g = ignore0 || area_g outside the range; the gts ordered stably, not-ignored first; the detections in order, each starting at best = min(thr, 1 - 1e-10)
+ *   and walking the gts: skip a gt already matched unless it is a crowd, stop when the current match is not ignored and this gt is, skip when oks < best, else take
+ *   it.  A matched detection inherits its gt's ignore flag, an unmatched one is ignored iff area_d lies outside the range; npig[range] += the not-ignored gts.
+ *   Record, 16 bytes per kept detection: float32 score, uint32 matched (bit 10 range + threshold), uint32 ignored, uint32 image ordinal (state.images + frame),
+ *   appended in image order, inside an image in kept order; one that does not fit into max_records is not written and counted in `dropped`.
+ *   d_match int32 [n, 10], optional: the gt row matched under "all" at each threshold, -1 unmatched, -2 a row not among its image's kept 20 or not counted.
+ *   State blob (vp_cocoeval_state_bytes = 128 + 16 max_records; zeroed = new): int64 calls, images, rows, kept, records, dropped, gts, gt_overflow, nonfinite,
+ *   npig[3], 0 x 4 | the record table.  A pure function of the inputs and the sequence of calls, byte for byte.
+ *   Accumulate: records ordered by score descending (NaN as -infinity), equal scores by table position (COCOeval's stable argsort(-score) when images are fed in
+ *   ascending id order); per (range, threshold) integer cumulative tp / fp, rc = tp / npig, pr = tp / (fp + tp + 2^-52), the precision envelope from the back, the
+ *   first position with rc >= each recall threshold.  Result blob (vp_cocoeval_result_bytes = 128 + 8 * 3060): the header | double precision [3][10][101] | double
+ *   recall [3][10]; npig == 0 gives -1, no position gives precision 0, no record recall 0.
+ * vp_cocoeval_update_stream and vp_cocoeval_accumulate_stream only enqueue on caller_stream, a fixed launch sequence per evaluator (capturable as one linear chain):
+ * no synchronisation, no host copy, no allocation, no atomics.  d_out: device, 8-byte aligned.  vp_cocoeval_update / vp_cocoeval_accumulate: the synchronous twins on
+ * host pointers.  vp_cocoeval_create: on the device of h, state zeroed, sigmas = HOST double [n_joints]; destroy the evaluator before h.
+ * VP_ERR_INVALID before anything is enqueued, the reason in vp_last_error: a NULL cfg; NULL d_kpts / d_score with n > 0; NULL d_gt_kpts / d_gt_box / d_gt_area with
+ * g > 0; n, g, n_frames, n_joints (1..VP_NMS_MAX_K) or max_records (1..VP_COCOEVAL_MAX_RECORDS) outside its range; NULL sigmas, or a sigma not finite or <= 0; a NULL
+ * accumulate destination.  Library builds that carry the stage define VP_HAS_COCOEVAL. */
+#define VP_HAS_COCOEVAL 1
+#define VP_COCOEVAL_MAX_ROWS 8192
+#define VP_COCOEVAL_MAX_FRAMES 256
+#define VP_COCOEVAL_MAX_RECORDS (1 << 20)
+typedef struct vp_cocoeval_cfg {
+    int32_t n_joints, max_records;
+    int32_t reserved[2];
+} vp_cocoeval_cfg;
+typedef struct vp_cocoeval* vp_cocoeval_handle;
+VP_API int vp_cocoeval_create(vp_handle h, const vp_cocoeval_cfg* cfg, const double* sigmas, vp_cocoeval_handle* out);
+VP_API int vp_cocoeval_destroy(vp_cocoeval_handle e);
+VP_API int vp_cocoeval_reset_stream(vp_cocoeval_handle e, void* caller_stream);
+VP_API int vp_cocoeval_update_stream(vp_cocoeval_handle e, const float* d_kpts, const float* d_score, const int32_t* d_frame, const int32_t* d_rank, int32_t n,
+                                     const float* d_gt_kpts, const float* d_gt_box, const float* d_gt_area, const int32_t* d_gt_flags, const int32_t* d_gt_frame, int32_t g,
+                                     int32_t n_frames, int32_t* d_match, void* caller_stream);
+VP_API int vp_cocoeval_update(vp_cocoeval_handle e, const float* kpts, const float* score, const int32_t* frame, const int32_t* rank, int32_t n, const float* gt_kpts,
+                              const float* gt_box, const float* gt_area, const int32_t* gt_flags, const int32_t* gt_frame, int32_t g, int32_t n_frames, int32_t* match);
+VP_API int vp_cocoeval_accumulate_stream(vp_cocoeval_handle e, void* d_out, void* caller_stream);
+VP_API int vp_cocoeval_accumulate(vp_cocoeval_handle e, void* out);
+VP_API int vp_cocoeval_state_bytes(const vp_cocoeval_cfg* cfg, int64_t* bytes);
+VP_API int vp_cocoeval_result_bytes(int64_t* bytes);
+VP_API int vp_cocoeval_download_state(vp_cocoeval_handle e, void* out);
+/* HOST ONLY, no device needed: csrc/cocogeom.h run serially on a host state blob of vp_cocoeval_state_bytes (zeroed = a new evaluator), and the accumulation of
+ * such a blob into a result blob of vp_cocoeval_result_bytes: the model the device is tested against (test taps, never a fallback), with the refusals of
+ * vp_cocoeval_create, vp_cocoeval_update_stream and vp_cocoeval_accumulate_stream, the reason in vp_last_error(NULL). */
+VP_API int vp_dbg_cocoeval_update_host(void* state, const vp_cocoeval_cfg* cfg, const double* sigmas, const float* kpts, const float* score, const int32_t* frame,
+                                       const int32_t* rank, int32_t n, const float* gt_kpts, const float* gt_box, const float* gt_area, const int32_t* gt_flags,
+                                       const int32_t* gt_frame, int32_t g, int32_t n_frames, int32_t* match);
+VP_API int vp_dbg_cocoeval_accumulate_host(const void* state, const vp_cocoeval_cfg* cfg, void* out);
+
 /* HOST ONLY, no device needed: the plan those entries run for expert_ids [n] on a handle of n_experts experts and max_batch crops per chunk -- the pure function
  * ids -> order, segments that shapes their launches.  Per chunk c (crops [c max_batch, ...)), with B = max_batch rounded up to a multiple of 4:
  *   order [n]: position j of chunk c holds the chunk-local caller row order[c max_batch + j] (stable expert order)
