@@ -57,7 +57,9 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_cocoeval_create', 'vp_cocoeval_destroy', 'vp_cocoeval_reset_stream', 'vp_cocoeval_update_stream', 'vp_cocoeval_update', 'vp_cocoeval_accumulate_stream',
            'vp_cocoeval_accumulate', 'vp_cocoeval_state_bytes', 'vp_cocoeval_result_bytes', 'vp_cocoeval_download_state', 'vp_dbg_cocoeval_update_host',
            'vp_dbg_cocoeval_accumulate_host',
-           'vp_dbg_head_case', 'vp_dbg_im2col', 'vp_dbg_layernorm_planes']
+           'vp_dbg_head_case', 'vp_dbg_im2col', 'vp_dbg_layernorm_planes',
+           'vp_yolo_create', 'vp_yolo_destroy', 'vp_yolo_info', 'vp_yolo_forward_stream', 'vp_yolo_forward', 'vp_dbg_yolo_plan', 'vp_dbg_yolo_fold',
+           'vp_dbg_yolo_decode_host', 'vp_dbg_yolo_activation', 'vp_dbg_yolo_conv_case']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -133,6 +135,24 @@ class vp_metrics_cfg(C.Structure):
 
 class vp_cocoeval_cfg(C.Structure):
     _fields_ = [('n_joints', C.c_int32), ('max_records', C.c_int32), ('reserved', C.c_int32 * 2)]
+
+
+class vp_yolo_cfg(C.Structure):
+    _fields_ = [('in_h', C.c_int32), ('in_w', C.c_int32), ('max_images', C.c_int32), ('input_layout', C.c_int32), ('head_dtype', C.c_int32), ('head_layout', C.c_int32),
+                ('reserved', C.c_int32 * 2)]
+
+
+class vp_yolo_tensor(C.Structure):
+    _fields_ = [('name', C.c_char_p), ('data', C.POINTER(C.c_float)), ('numel', C.c_int64), ('ndim', C.c_int32), ('shape', C.c_int32 * 4), ('reserved', C.c_int32)]
+
+
+class vp_yolo_launch(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('kind', 'layer', 'conv', 'k', 's', 'act', 'f32_out', 'h_in', 'w_in', 'h_out', 'w_out', 'c_in', 'c_out', 'in_buf', 'in_off',
+                                         'in_stride', 'out_buf', 'out_off', 'out_stride', 'res_buf', 'res_off', 'res_stride')] + [('reserved', C.c_int32 * 2)]
+
+
+class vp_yolo_buffer(C.Structure):
+    _fields_ = [('h', C.c_int32), ('w', C.c_int32), ('c', C.c_int32), ('elem_bytes', C.c_int32)]
 
 
 class vp_profile(C.Structure):
@@ -357,6 +377,17 @@ def load_library():
     lib.vp_cocoeval_download_state.argtypes = [C.c_void_p, C.c_void_p]
     lib.vp_dbg_cocoeval_update_host.argtypes = [C.c_void_p, C.POINTER(vp_cocoeval_cfg), C.c_void_p] + coco_io
     lib.vp_dbg_cocoeval_accumulate_host.argtypes = [C.c_void_p, C.POINTER(vp_cocoeval_cfg), C.c_void_p]
+    yolo_ck = [C.POINTER(vp_yolo_cfg), C.POINTER(vp_yolo_tensor), C.c_int32]
+    lib.vp_yolo_create.argtypes = [H] + yolo_ck + [C.POINTER(C.c_void_p)]
+    lib.vp_yolo_destroy.argtypes = [C.c_void_p]
+    lib.vp_yolo_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    lib.vp_yolo_forward_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.vp_yolo_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.vp_dbg_yolo_plan.argtypes = yolo_ck + [C.POINTER(vp_yolo_launch), C.c_int32, C.POINTER(vp_yolo_buffer), C.c_int32, C.c_void_p]
+    lib.vp_dbg_yolo_fold.argtypes = yolo_ck + [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vp_dbg_yolo_decode_host.argtypes = [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.vp_dbg_yolo_activation.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.vp_dbg_yolo_conv_case.argtypes = [H, C.POINTER(vp_yolo_launch), C.c_int32] + [C.c_void_p] * 5
     for name in SYMBOLS:
         if name not in ('vp_stream', 'vp_last_error', 'vp_host_alloc', 'vp_host_free', 'vp_group_member', 'vp_group_last_error'):
             getattr(lib, name).restype = C.c_int

@@ -156,7 +156,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument('--output-path', default='', help='output directory (required by --save-json)')
     ap.add_argument('--model', default=None, help='ViTPose checkpoint (.pth)')
     ap.add_argument('--synthetic', default=None, choices=['s', 'b', 'l', 'h'], help='seeded peaked synthetic checkpoint of this size instead of --model')
-    ap.add_argument('--yolo', default=None, help='ultralytics detector weights')
+    ap.add_argument('--yolo', default=None, help='detector weights: a YOLOv8 state dict (.npz from tools/export_yolo_state.py, or a plain .pt) runs on the native '
+                    'detector network at --det-input; an ultralytics checkpoint needs ultralytics')
     ap.add_argument('--boxes', default=None, help='JSON file with detector boxes (replaces --yolo)')
     ap.add_argument('--det-heads', default=None, metavar='FILE.npz', help='the detector\'s RAW head of every frame ([4 + nc, A], YOLOv8\'s export) instead of --yolo / '
                     '--boxes: best class, confidence threshold, class filter (--det-class; heads of 80 classes) and box NMS run on the device (devdetect)')
@@ -255,6 +256,10 @@ def main(argv=None) -> int:
     letterbox = None
     if engine is not None:
         detector, detect, letterbox = engine
+    elif args.yolo is not None and args.boxes is None and VitInference._native_yolo(args.yolo):
+        # --yolo FILE.npz (or a plain state dict .pt): the native detector network (devyolo), letterbox -> DeviceYolo -> detect at --det-input
+        from easy_vitpose_amd.devletterbox import LetterboxCfg
+        letterbox = LetterboxCfg(tuple(args.det_input))
     assert detector is not None, 'give --yolo (ultralytics weights), --boxes, --det-heads or --det-engine'
 
     skeleton = None

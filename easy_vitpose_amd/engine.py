@@ -593,6 +593,12 @@ class VitPoseHip:
         from .devletterbox import DeviceLetterbox, LetterboxCfg
         return DeviceLetterbox(self, LetterboxCfg() if cfg is None else cfg)
 
+    def yolo(self, state, in_hw=(640, 640), **kw):
+        """The detector network on this handle's device (devyolo.DeviceYolo over vp_yolo_*): YOLOv8-detect from a state dict (or a path `load_yolo_state` reads),
+        the stream-ordered stage between `letterbox()` and `detector()`.  `kw`: max_images, input_layout, head_dtype, head_layout."""
+        from .devyolo import DeviceYolo
+        return DeviceYolo(self, state, in_hw, **kw)
+
     def orient(self):
         """An orient stage on this handle's device (devorient.DeviceOrient over vp_orient_*): device frames as captured -- rotated, mirrored -- to upright device
         frames, the stream-ordered stage in front of `letterbox()` and of every entry that reads a frame."""

@@ -114,7 +114,7 @@ class VitInference:
         from .devletterbox import LetterboxCfg
         if not (letterbox is None or isinstance(letterbox, LetterboxCfg)):
             raise TypeError(f'letterbox: None or a LetterboxCfg expected, got {letterbox!r}')
-        if letterbox is not None and detect is None:
+        if letterbox is not None and detect is None and not self._native_yolo(yolo):
             raise ValueError('letterbox= feeds the detector stage: give detect= (a DetectCfg) with it')
         self._letterbox_cfg, self._letterbox = letterbox, None
         if not (np.isfinite(box_scale) and box_scale > 0):
@@ -142,8 +142,14 @@ class VitInference:
         else:  # an in-memory state dict (extension; used by tests / benchmarks)
             state_dict = model
             assert dataset is not None, 'dataset must be given with an in-memory state dict'
+        self._yolo_state = None
         if callable(yolo):
             self.yolo = yolo
+        elif self._native_yolo(yolo):
+            # the native detector network (devyolo.DeviceYolo): built below, once the handle exists, and wired as letterbox -> DeviceYolo -> detect
+            from .devyolo import load_yolo_state
+            self._yolo_state = yolo if isinstance(yolo, dict) else load_yolo_state(yolo)
+            self.yolo = None
         else:
             assert os.path.isfile(yolo), f'The YOLOv8 model {yolo} does not exist'
             try:
@@ -203,10 +209,26 @@ class VitInference:
         if pose_nms is not None:
             sig = resolve_sigmas(dataset, shape.num_keypoints, pose_nms.sigmas)
             self._pose_nms = dataclasses.replace(pose_nms, sigmas=tuple(float(v) for v in sig))
+        if self._yolo_state is not None:
+            import torch   # the native detector runs on torch tensors: torch opens the device before the library does (the other order can leave torch without one)
+            torch.cuda.init()
         self._vit_pose = VitPoseHip(shape, state_dict,
                                     dtype=dtype, device_id=dev_id, max_batch=max_batch, dataset=dataset if plus else None)
         if flip_pairs is not None:   # a mode of the handle: every call below (inference, inference_frames, the boxes route) inherits it
             self._vit_pose.set_flip_test(flip_pairs, shift_heatmap)
+        if self._yolo_state is not None:
+            lb = self._letterbox_cfg or LetterboxCfg(((int(yolo_size) + 31) // 32 * 32,) * 2)
+            if lb.dtype != 'fp16' or lb.order != 'rgb':
+                raise ValueError(f"yolo=: the native detector network reads the letterbox stage's fp16 RGB tensor, got dtype {lb.dtype!r}, order {lb.order!r}")
+            dc = self._detect_cfg
+            self.yolo = self._vit_pose.yolo(self._yolo_state, lb.input_hw, input_layout=lb.layout, head_dtype='fp32' if dc is None else dc.dtype,
+                                            head_layout=0 if dc is None else dc.layout)
+            if dc is None:
+                cls = DETC_TO_YOLO_YOLOC[det_class]
+                dc = DetectCfg(nc=self.yolo.nc, dtype='fp32', classes=det_class if max(cls) < self.yolo.nc else None)
+            elif dc.nc != self.yolo.nc:
+                raise ValueError(f'detect=: nc = {dc.nc}, the checkpoint has {self.yolo.nc} classes')
+            self._letterbox_cfg, self._detect_cfg = lb, dc
         if self._detect_cfg is not None:
             self._detector = self._vit_pose.detector(dataclasses.replace(self._detect_cfg, max_images=1))
         if self._letterbox_cfg is not None:
@@ -216,6 +238,29 @@ class VitInference:
         if tracker == 'device' or self._smooth_cfg is not None:   # the device tracker and the smoother live on the engine's device: built now that there is one
             self.reset()
         self._inference = self._inference_hip
+
+    @staticmethod
+    def _native_yolo(yolo) -> bool:
+        """yolo= names the native detector network: a state dict, an .npz, or any other file that IS a plain state dict (the file decides, not the packages
+        installed).  A file that is not one -- an ultralytics pickle -- goes to ultralytics where that is installed and is otherwise refused with the exporter's
+        name.  A callable goes where it always went."""
+        if isinstance(yolo, dict):
+            return True
+        if callable(yolo) or not isinstance(yolo, (str, os.PathLike)):
+            return False
+        if str(yolo).endswith('.npz'):
+            return True
+        if not os.path.isfile(yolo):
+            return False
+        from .devyolo import load_yolo_state
+        try:
+            load_yolo_state(yolo)
+            return True
+        except ValueError:
+            import importlib.util
+            if importlib.util.find_spec('ultralytics') is None:
+                raise
+            return False
 
     @staticmethod
     def _load_pth(path):

@@ -1245,6 +1245,80 @@ VP_API int vp_dbg_gemm_fp8_case_planes(int32_t device_id, int32_t M, int32_t N, 
 /* HOST ONLY: fp32 -> OCP e4m3 codes with the converter the fp8 weight packer uses (round to nearest even, saturating at 448) */
 VP_API int vp_dbg_host_e4m3(const float* in, uint8_t* out, int64_t n);
 
+/* ---- The detector network: YOLOv8-detect on the device ------------------------------------------------------------------------------------------------------
+ * The stage between the letterbox stage and the detector stage: the tensor vp_letterbox_stream writes (fp16, [n, 3, H, W] or [n, H, W, 3], RGB, values / 255) to
+ * the head vp_detect_stream takes ([n, 4 + nc, A], layout 0, or [n, A, 4 + nc], layout 1; float32 or float16).  csrc/yologeom.h states the network once: the layer
+ * table and scaling rules of the scales n, s, m, l, x, the plan (every launch, every buffer), the load step and the Detect decode.  Eval mode, fp16 activations
+ * (NHWC), fp16 weights with BatchNorm folded in double precision and rounded once, float32 biases, float32 accumulation, float32 Detect outputs and decode.
+ *
+ *   vp_yolo_create reads the scale (the rows of model.0.conv.weight), the repeat counts (the highest model.{i}.m.{j} present) and nc (the rows of
+ *   model.22.cv3.0.2.weight) from the checkpoint's tensors (an ultralytics state dict of model.model: model.{i}.conv.weight, model.{i}.bn.*, ..., or a fused one
+ *   with conv.weight + conv.bias), plans, folds, uploads and allocates every buffer for max_images images.  Nothing is allocated, copied or synchronised later.
+ *   vp_yolo_forward_stream only enqueues on caller_stream: a pack pass, one implicit-GEMM MFMA kernel per convolution (bias, SiLU, the Bottleneck shortcut in its
+ *   epilogue; split and cat are channel offsets), three max-pool launches, two upsample copies, one decode.  A linear chain, no atomics: run-to-run bit-identical
+ *   and capturable in a graph.  d_input holds n_images images, d_head receives n_images heads; n_images 0 enqueues nothing.
+ *   vp_yolo_forward: the synchronous twin on host pointers.  vp_yolo_info: nc, A, the number of launches and the bytes of device memory.
+ *
+ * Refusals (VP_ERR_INVALID, the reason in vp_last_error(h), before anything is enqueued): in_h / in_w not multiples of 32 in 32..1280, max_images outside 1..64,
+ * an unknown input_layout, head_dtype or head_layout, nc outside 1..256, a missing tensor, a shape that contradicts the table, a repeat count of another scale,
+ * a model.22.dfl.conv.weight that is not 0..15, n_images outside 0..max_images, a NULL or misaligned pointer.  Library builds that carry the stage define
+ * VP_HAS_YOLO. */
+#define VP_HAS_YOLO 1
+typedef struct vp_yolo_cfg {
+    int32_t in_h, in_w;      /* multiples of 32, 32..1280 */
+    int32_t max_images;      /* 1..64 */
+    int32_t input_layout;    /* 0 [n, 3, H, W], 1 [n, H, W, 3] */
+    int32_t head_dtype;      /* VP_DET_F32 (0) or VP_DET_F16 */
+    int32_t head_layout;     /* 0 [n, 4 + nc, A], 1 [n, A, 4 + nc] */
+    int32_t reserved[2];     /* [0]: 1 keeps every internal buffer in a region of its own (vp_dbg_yolo_activation; more memory), 0 reuses regions; [1]: 0 */
+} vp_yolo_cfg;
+typedef struct vp_yolo_tensor {
+    const char* name;
+    const float* data;
+    int64_t numel;
+    int32_t ndim, shape[4];
+    int32_t reserved;
+} vp_yolo_tensor;
+/* One launch of the plan.  kind: 0 pack (the caller's tensor to 8-channel NHWC), 1 convolution, 2 5x5 max-pool, 3 nearest x2 copy, 4 Detect decode.  A launch
+ * reads channels [in_off, in_off + c_in) and writes channels [out_off, out_off + c_out) of every pixel of NHWC buffers with in_stride / out_stride channels per
+ * pixel; res_buf >= 0: the shortcut added in the epilogue, read at the output pixel.  conv: the index vp_dbg_yolo_fold takes.  The decode reads the three
+ * float32 level buffers in_buf, in_buf + 1, in_buf + 2 ([64 box logits | nc class logits] per anchor). */
+typedef struct vp_yolo_launch {
+    int32_t kind, layer, conv, k, s, act, f32_out;
+    int32_t h_in, w_in, h_out, w_out, c_in, c_out;
+    int32_t in_buf, in_off, in_stride, out_buf, out_off, out_stride, res_buf, res_off, res_stride;
+    int32_t reserved[2];
+} vp_yolo_launch;
+/* One buffer of the plan: h x w pixels of c channels of elem_bytes each, per image.  Buffer 0 is the caller's input, the last one the caller's head. */
+typedef struct vp_yolo_buffer { int32_t h, w, c, elem_bytes; } vp_yolo_buffer;
+typedef struct vp_yolo* vp_yolo_handle;
+VP_API int vp_yolo_create(vp_handle h, const vp_yolo_cfg* cfg, const vp_yolo_tensor* tensors, int32_t n_tensors, vp_yolo_handle* out);
+VP_API int vp_yolo_destroy(vp_yolo_handle y);
+VP_API int vp_yolo_info(vp_yolo_handle y, int32_t* nc, int32_t* A, int32_t* n_launches, int64_t* device_bytes);
+VP_API int vp_yolo_forward_stream(vp_yolo_handle y, const void* d_input, int32_t n_images, void* d_head, void* caller_stream);
+VP_API int vp_yolo_forward(vp_yolo_handle y, const void* input, int32_t n_images, void* head);
+/* HOST ONLY (no device): the plan of a checkpoint at cfg.  launches [max_launches], buffers [max_buffers] (either may be NULL to ask for the counts only);
+ * info int32 [16]: n_launches, n_buffers, n_convs, nc, A, the scale's letter, ch64, ch128, ch256, ch512, ch1024, d(3), d(6), Detect's c2, Detect's c3, 0.
+ * The refusals of vp_yolo_create, the reason in vp_last_error(NULL). */
+VP_API int vp_dbg_yolo_plan(const vp_yolo_cfg* cfg, const vp_yolo_tensor* tensors, int32_t n_tensors, vp_yolo_launch* launches, int32_t max_launches,
+                            vp_yolo_buffer* buffers, int32_t max_buffers, int32_t* info);
+/* HOST ONLY: the load step of convolution `conv` of the plan: w uint16 fp16 bits [rows][cols] with cols = k k c_in ((ky, kx, channel) order, channels padded to
+ * 8), b float32 [rows]; dims int32 [2] = (rows, cols).  w / b may be NULL to ask for dims only. */
+VP_API int vp_dbg_yolo_fold(const vp_yolo_cfg* cfg, const vp_yolo_tensor* tensors, int32_t n_tensors, int32_t conv, uint16_t* w, float* b, int32_t* dims);
+/* HOST ONLY: yologeom.h's Detect decode run serially.  levels: float32, P3 then P4 then P5, each [n_images][h_l w_l][64 + nc] with h_l = in_h / (8, 16, 32);
+ * head: [n_images, 4 + nc, A] (layout 0) or [n_images, A, 4 + nc] of head_dtype. */
+VP_API int vp_dbg_yolo_decode_host(int32_t nc, int32_t in_h, int32_t in_w, int32_t n_images, const float* levels, int32_t head_dtype, int32_t head_layout, void* head);
+/* After a forward of n_images: the whole buffer launch `launch` wrote into, [n_images][h][w][c] of its element type (the plan says which channels the launch
+ * wrote).  Needs a stage created with cfg.reserved[0] = 1: its buffers are then never reused inside a forward and, filled with 0xFF bytes by vp_yolo_create,
+ * show an element nothing wrote.  Synchronises. */
+VP_API int vp_dbg_yolo_activation(vp_yolo_handle y, int32_t launch, int32_t n_images, void* out);
+/* ONE launch of the convolution kernel on host data, on views the plan of a network never forms (a 1 x 1 reading at a channel offset): l gives k, s, act,
+ * f32_out, the sizes and the three views (kind, layer, conv, the buffer ids are ignored); in fp16 bits [n][h_in][w_in][in_stride]; w fp16 bits [c_out][k k c_in] in
+ * (ky, kx, channel) order; bias [c_out]; res (may be NULL) fp16 bits [n][h_out][w_out][res_stride]; out [n][h_out][w_out][out_stride] of the output's element
+ * type, filled with 0xFF bytes before the launch so that an element the kernel did not write shows. */
+VP_API int vp_dbg_yolo_conv_case(vp_handle h, const vp_yolo_launch* l, int32_t n_images, const uint16_t* in, const uint16_t* w, const float* bias, const uint16_t* res,
+                                 void* out);
+
 #ifdef __cplusplus
 }
 #endif
