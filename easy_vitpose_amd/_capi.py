@@ -59,7 +59,8 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_dbg_cocoeval_accumulate_host',
            'vp_dbg_head_case', 'vp_dbg_im2col', 'vp_dbg_layernorm_planes',
            'vp_yolo_create', 'vp_yolo_destroy', 'vp_yolo_info', 'vp_yolo_forward_stream', 'vp_yolo_forward', 'vp_dbg_yolo_plan', 'vp_dbg_yolo_fold',
-           'vp_dbg_yolo_decode_host', 'vp_dbg_yolo_activation', 'vp_dbg_yolo_conv_case']
+           'vp_dbg_yolo_decode_host', 'vp_dbg_yolo_activation', 'vp_dbg_yolo_conv_case',
+           'vp_head_kind', 'vp_dbg_simple_head_pack', 'vp_dbg_simple_head_case']
 
 
 class HipExtensionMissing(RuntimeError):
@@ -267,6 +268,9 @@ def load_library():
     lib.vp_dbg_ln_finalize.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 2
     lib.vp_dbg_gemm_case_lnpart.argtypes = [C.c_int32] * 9 + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 2
     lib.vp_dbg_ln_quant.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 4
+    lib.vp_head_kind.argtypes = [H]
+    lib.vp_dbg_simple_head_pack.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 3
+    lib.vp_dbg_simple_head_case.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p]
     lib.vp_dbg_head_case.argtypes = [C.c_int32] * 9 + [C.c_void_p, C.POINTER(vp_tensor_desc), C.c_int32, C.c_int32] + [C.c_void_p] * 6
     lib.vp_dbg_im2col.argtypes = [C.c_int32] * 6 + [C.c_void_p] * 3
     lib.vp_dbg_layernorm_planes.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 6

@@ -17,6 +17,8 @@ import os
 import re
 from dataclasses import dataclass
 
+import numpy as np
+
 # input crop (W, H) and heatmap (W, H): ViTPose_common.py:29-31
 IMAGE_SIZE = (192, 256)
 HEATMAP_SIZE = (48, 64)
@@ -25,7 +27,8 @@ HM_H, HM_W = 64, 48
 PATCH = 16
 TOKENS = 192  # 16 x 12 patches
 GRID_H, GRID_W = 16, 12
-DECONV_CH = 256  # num_deconv_filters=(256, 256)
+DECONV_CH = 256  # num_deconv_filters=(256, 256): the classic decoder only (the simple decoder has no deconv layers)
+HEADS = ('classic', 'simple')  # two deconvs + 1x1 conv | ReLU -> bilinear x 4 -> 3x3 conv (the model zoo's `-simple` files)
 
 MODEL_ABBR_MAP = {'s': 'small', 'b': 'base', 'l': 'large', 'h': 'huge'}
 
@@ -57,6 +60,7 @@ class ModelShape:
     depth: int
     num_heads: int
     num_keypoints: int
+    head: str = 'classic'
 
     @property
     def head_dim(self) -> int:
@@ -70,17 +74,20 @@ class ModelShape:
         """Algorithmic FLOPs (2*M*N*K of every matmul/conv incl. attention core),
         the formula of SURVEY.md section 8(d)."""
         D, L, K = self.embed_dim, self.depth, self.num_keypoints
-        return (L * (4608 * D * D + 147456 * D) + 294912 * D + 1572864 * D
-                + 1610612736 + 1572864 * K) / 1e9
+        encoder = L * (4608 * D * D + 147456 * D) + 294912 * D
+        if self.head == 'simple':   # the commuted form: the 9-tap GEMM at 16 x 12 (2 * 192 * 9 K * D) + the 36-term stencil at 64 x 48
+            return (encoder + 3456 * K * D + 221184 * K) / 1e9
+        return (encoder + 1572864 * D + 1610612736 + 1572864 * K) / 1e9
 
 
-def model_shape(variant: str, dataset: str | None = None, num_keypoints: int | None = None) -> ModelShape:
+def model_shape(variant: str, dataset: str | None = None, num_keypoints: int | None = None, head: str = 'classic') -> ModelShape:
     assert variant in VARIANTS, f'The model name {variant} is not valid'
     if num_keypoints is None:
         assert dataset in DATASET_KEYPOINTS, 'The specified dataset is not valid'
         num_keypoints = DATASET_KEYPOINTS[dataset]
     D, L, h = VARIANTS[variant]
-    return ModelShape(variant, D, L, h, int(num_keypoints))
+    assert head in HEADS, f'unknown decoder {head!r}'
+    return ModelShape(variant, D, L, h, int(num_keypoints), head)
 
 
 def infer_dataset_by_path(model_path: str) -> str:
@@ -100,6 +107,27 @@ def infer_variant_from_state_dict(sd) -> str:
         if d == D:
             return v
     raise ValueError(f'unknown embed_dim {D}')
+
+
+def infer_head_from_state_dict(sd) -> str:
+    """``'classic'`` (two deconvs + a 1x1 conv) or ``'simple'`` (ReLU -> bilinear x 4 -> 3x3 conv, the ``vitpose-*-simple`` files), by the
+    rule the loader applies: simple when no ``keypoint_head.deconv_layers.*`` is present and ``final_layer.weight`` is ``[K, D, 3, 3]``.
+    Raises ValueError for a dict that is neither (the loader refuses it too).
+
+    Note: ``infer_dataset_by_path('vitpose-b-simple.pth')`` returns ``'simple'`` exactly as the reference's function does, so such a file
+    needs ``dataset='coco'`` given or a name that ends in its dataset (``vitpose-b-simple-coco.pth``)."""
+    w = sd['keypoint_head.final_layer.weight']
+    shp = tuple(int(v) for v in w.shape)
+    D = int(sd['backbone.pos_embed'].shape[-1])
+    has_deconv = any(k.startswith('keypoint_head.deconv_layers.') for k in sd)
+    three = len(shp) == 4 and shp[1:] == (D, 3, 3)
+    if three and not has_deconv:
+        return 'simple'
+    if three:
+        raise ValueError('keypoint_head.final_layer.weight is a 3x3 conv (simple decoder) but keypoint_head.deconv_layers.* are present')
+    if int(np.prod(shp)) != shp[0] * DECONV_CH:
+        raise ValueError(f'keypoint_head.final_layer.weight {shp}: neither [K, {DECONV_CH}, 1, 1] (classic decoder) nor [K, {D}, 3, 3] (simple decoder)')
+    return 'classic'
 
 
 # mirror joint pairs of the 17-joint COCO layout (left / right eye, ear, shoulder, elbow, wrist, hip, knee, ankle): the one flip-pair table the

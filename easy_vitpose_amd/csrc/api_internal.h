@@ -7,6 +7,7 @@
 //   tile_rules.hip   -- which GEMM tile runs a shape (pure host functions + their host-only taps)
 //   debug_taps.hip   -- vp_dbg_*: one kernel on host data (parity tests), and the measurement build's timing taps
 //   metrics.hip      -- the accumulating accuracy-metrics stage (vp_metrics_*: an object of its own beside the handle, like the tracker and the smoother)
+//   simplehead.hip   -- the simple decoder's head (one kernel, simpleheadgeom.h), vp_head_kind and its two taps
 //   cocoeval.hip     -- the accumulating COCO keypoint AP / AR stage (vp_cocoeval_*: an object of its own beside the handle, like the metrics stage)
 // Everything here is library-internal (hidden visibility); nothing of it appears in the public headers.
 #pragma once
@@ -116,6 +117,8 @@ struct vp_ctx {
     float *lnf_g = nullptr, *lnf_b = nullptr;
     uint16_t *w_d1 = nullptr, *w_d2 = nullptr, *w_fin = nullptr;
     size_t fin_rows = 0;   // physical (hi/lo interleaved) rows of w_fin
+    int head_kind = 0;     // 0 = the classic decoder (two deconvs + 1x1 conv), 1 = the simple decoder (simpleheadgeom.h): w_fin = its 9-tap hi / lo weight image of
+                           // fin_rows rows per tap, b_fin its bias, w_d1 .. b_d2 unused (the d1 / d2 workspaces stay allocated)
     float *b_d1 = nullptr, *b_d2 = nullptr, *b_fin = nullptr, *b_zero = nullptr;
     uint16_t* zero = nullptr;
     // workspaces
@@ -277,6 +280,9 @@ size_t pad128(size_t n);
 int upload_f32(vp_ctx* c, float** dst, const float* src, size_t n, size_t npad = 0);
 int upload_mat(vp_ctx* c, uint16_t** dst, const float* src, size_t rows, size_t cols, size_t rows_pad);
 int upload_final(vp_ctx* c, uint16_t** dst, const float* src, size_t kp, size_t cols, size_t* rows_phys);
+// the simple decoder's final_layer.weight [K, D, 3, 3] as simpleheadgeom.h's weight image (HOST ONLY: img = 9 x sh_rows(K) x D codes), and its upload
+void pack_simple_final(const float* src, int K, int D, int dtype, std::vector<uint16_t>& img);
+int upload_simple_final(vp_ctx* c, uint16_t** dst, const float* src, int K, int D, size_t* rows_phys);
 int upload_ln_folded(vp_ctx* c, uint16_t** w_out, float** s_out, float** c_out, const float* W, const float* b,
                      const float* gamma, const float* beta, size_t N, size_t K);
 int upload_fp8_rows(vp_ctx* c, uint8_t** w_out, float** ws_out, float** c_out, const float* W, const float* b, const float* gamma,
@@ -384,6 +390,7 @@ GemmPick resolve_gemm(const Switches& s, int fam, int epi, int M, int N, int K, 
 GemmPick resolve_gemm_fp8(int fam, int epi, int Mp, int N);   // fp8 mode: qkv / fc1 / fc2 (and attn.proj at head dim 64) on the MXFP8 kernel
 enum QkvPath { QKV_GEMM = 0, QKV_ATTN64 = 1, QKV_ATTN80 = 2 };   // attn.qkv GEMM + attention kernel; fused: qkvattn.hip (head dim 64) / gemm8.hip EPI_QKV_ATTN (head dim 80)
 struct HeadPlan {
+    int kind = 0;                     // vp_ctx::head_kind: 1 = the simple decoder's one launch (simplehead.hip), nothing below applies
     bool fused = false;               // deconv2 + the final 1x1 conv in one kernel (EPI_DECONV_FINAL)
     GemmPick deconv1, deconv2, final;  // final: unused when fused
 };
@@ -396,9 +403,10 @@ struct ChunkPlan {
     GemmPick gemm[VP_PROF_COUNT];     // the encoder GEMMs by family: PATCH, QKV, PROJ, FC1, FC2
     HeadPlan head;                    // the head of the chunk's crops
 };
-// fin_rows = physical rows of the final conv's weights (final_rows); mix_bounds as in resolve_gemm
-ChunkPlan plan_chunk(const Switches& s, int D, int heads, int max_batch, bool fp8, int n_in, size_t fin_rows, const std::vector<int>* mix_bounds = nullptr);
-HeadPlan plan_head(const Switches& s, int D, int nh, size_t fin_rows);
+// fin_rows = physical rows of the final conv's weights (final_rows); mix_bounds as in resolve_gemm; head_kind = vp_ctx::head_kind
+ChunkPlan plan_chunk(const Switches& s, int D, int heads, int max_batch, bool fp8, int n_in, size_t fin_rows, const std::vector<int>* mix_bounds = nullptr,
+                     int head_kind = 0);
+HeadPlan plan_head(const Switches& s, int D, int nh, size_t fin_rows, int head_kind = 0);
 
 // ---- forward.hip: one GEMM of the path as `pk` resolved it (also what the vp_dbg_gemm* taps launch).  EPI_DECONV_FINAL: `out` = the fp32 heatmaps
 int gemm(vp_ctx* c, int fam, int epi, const GemmPick& pk, const uint16_t* A, const uint16_t* W, const float* bias, void* out,

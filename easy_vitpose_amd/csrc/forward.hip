@@ -1,6 +1,7 @@
 // The forward of one chunk behind the C ABI (include/vitpose_hip.h): the GEMM launchers, the encoder + head + decode of up to max_batch crops as the
 // chunk's plan (tile_rules.hip plan_chunk) picked them, and the hipGraph cache that replays small chunks (run_chunk).
 #include "api_internal.h"
+#include "simpleheadgeom.h"
 #include "tiles.h"
 
 using namespace vpi;
@@ -114,7 +115,7 @@ static const float* fc2_b(const vp_ctx* c, const vpi::Block& b) { return c->mix_
 // Under o.twin_src everything behind the patch gather is the plain forward of an n_in-crop batch.
 int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, const FwdOpts& o) {
     const int D = c->D;
-    const ChunkPlan pl = plan_chunk(c->sw, D, c->heads, c->maxb, c->fp8, n_in, c->fin_rows, c->mix_expert ? &c->mix_bounds : nullptr);
+    const ChunkPlan pl = plan_chunk(c->sw, D, c->heads, c->maxb, c->fp8, n_in, c->fin_rows, c->mix_expert ? &c->mix_bounds : nullptr, c->head_kind);
     const GemmPick* pk = pl.gemm;
     const int n = pl.n;   // rows n_in .. n - 1 of a padded encoder batch repeat the last crop and are never read by the head
     const int M = n * 192;
@@ -249,6 +250,12 @@ int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, const FwdOp
 int head_chunk(vp_ctx* c, const uint16_t* y, int nh, float* hm, const HeadPlan& hp) {
     const int D = c->D;
     int rc;
+    if (hp.kind == 1) {   // the simple decoder: relu -> bilinear x 4 -> 3x3 conv in one kernel, in the commuted form (simpleheadgeom.h)
+        vp::SimpleHeadArgs a{y, c->w_fin, c->b_fin, hm, nh, c->Kp, D, c->fin_rows};
+        LAUNCH(c, VP_PROF_GEMM_FINAL, vp::sh_flops(nh, c->Kp, D), vp::sh_bytes(nh, c->Kp, D), vp::simple_head_launch(c->dtype, a, c->stream));
+        note_kernel(c, VP_PROF_GEMM_FINAL, c->dtype == vp::DT_F16 ? "simple_head_kernel<F16>" : "simple_head_kernel<BF16>");
+        return VP_OK;
+    }
     // head: tokens [n,16,12,D] (NHWC view of [n*192, D]) -> [n,32,24,256] -> [n,64,48,256] -> heatmaps [n,Kp,64,48]
     if ((rc = gemm(c, VP_PROF_GEMM_DECONV, vp::EPI_DECONV, hp.deconv1, y, c->w_d1, c->b_d1, c->d1, nullptr, nh * 192, 256, 4 * D, 256, 16, 12, D))) return rc;
     if (hp.fused) {   // the final 1x1 conv rides in deconv2's epilogue: the [n,64,48,256] tensor is never written

@@ -314,4 +314,18 @@ hipError_t mix_tables_launch(const MixTable& t, int32_t* ids, int32_t* order, in
 // (recs[j] keeps {first, K, order} for box_offsets_launch, which reads K alone)
 hipError_t mix_tables_flip_launch(const MixTable& t, int32_t* ids, int32_t* order, int32_t* slot, MixRec* recs, MixRecFlip* recs_flip, hipStream_t s);
 
+// ---------------------------------------------------------------- simple decoder
+// simplehead.hip: ReLU -> bilinear x 4 -> Conv2d(D, K, 3, padding = 1) in the commuted form of simpleheadgeom.h, one launch of (ceil(K / 16), n) workgroups.
+// y = the last_norm tokens [n, 192, D] (16-bit), w = the tap-major hi / lo weight image (9 x rows x D, rows = sh_rows(K)), bias fp32 [K], hm fp32 [n, K, 64, 48].
+// D a multiple of 32; y, w and hm 16-byte aligned.  hipErrorInvalidValue for anything else, nothing launched.
+struct SimpleHeadArgs {
+    const uint16_t* y;
+    const uint16_t* w;
+    const float* bias;
+    float* hm;
+    int n, K, D;
+    size_t rows;
+};
+hipError_t simple_head_launch(int dtype, const SimpleHeadArgs& a, hipStream_t s);
+
 }  // namespace vp

@@ -285,8 +285,10 @@ GemmPick resolve_gemm_fp8(int fam, int epi, int Mp, int N) {
 
 // The head of nh crops: large batches run the final 1x1 conv in deconv2's epilogue (gemm.hip EPI_DECONV_FINAL, bit-identical heatmaps) and the [n,64,48,256] tensor is
 // never written; small batches keep the two launches on tiles that still fill 256 CUs
-HeadPlan plan_head(const Switches& s, int D, int nh, size_t fin_rows) {
+HeadPlan plan_head(const Switches& s, int D, int nh, size_t fin_rows, int head_kind) {
     HeadPlan h;
+    h.kind = head_kind;
+    if (head_kind == 1) return h;   // the simple decoder: one kernel, one shape (simplehead.hip)
     h.fused = s.fuse_head && s.gemm_variant[VP_PROF_GEMM_DECONV] < 0 && (long)nh * 12 >= 512;
     h.deconv1 = resolve_gemm(s, VP_PROF_GEMM_DECONV, vp::EPI_DECONV, nh * 192, 256, 4 * D);
     h.deconv2 = resolve_gemm(s, VP_PROF_GEMM_DECONV, h.fused ? vp::EPI_DECONV_FINAL : vp::EPI_DECONV, nh * 768, 256, 1024);
@@ -294,7 +296,7 @@ HeadPlan plan_head(const Switches& s, int D, int nh, size_t fin_rows) {
     return h;
 }
 
-ChunkPlan plan_chunk(const Switches& s, int D, int heads, int max_batch, bool fp8, int n_in, size_t fin_rows, const std::vector<int>* mix_bounds) {
+ChunkPlan plan_chunk(const Switches& s, int D, int heads, int max_batch, bool fp8, int n_in, size_t fin_rows, const std::vector<int>* mix_bounds, int head_kind) {
     ChunkPlan p;
     // the ENCODER's batch: n_in crops, or the next multiple of 4 where that buys the MLP GEMMs an 8-phase tile (pick_run_batch; rows n_in .. n - 1 repeat the last crop and
     // are never read by the head); the fp8 mode pads its rows itself
@@ -303,7 +305,7 @@ ChunkPlan plan_chunk(const Switches& s, int D, int heads, int max_batch, bool fp
     const size_t splitk_rows = (s.fuse_ln && !fp8 && s.splitk_on) ? (size_t)std::min(max_batch, SPLITK_MAX_CROPS) * 192 : 0;   // vp_create's workspace
     auto gemm = [&](int fam, int epi, int N, int K, bool ln_part) { return resolve_gemm(s, fam, epi, M, N, K, ln_part, splitk_rows, mix_bounds); };
     p.attn_qsplit = (long)n * heads <= s.attn_qsplit;
-    p.head = plan_head(s, D, n_in, fin_rows);
+    p.head = plan_head(s, D, n_in, fin_rows, head_kind);
     const int resid = s.fuse_ln ? vp::EPI_BIAS_RESID_LN : vp::EPI_BIAS_RESID;   // without the fused LayerNorm: standalone passes, fp32 residual stream
     p.gemm[VP_PROF_GEMM_PATCH] = gemm(VP_PROF_GEMM_PATCH, s.fuse_ln ? vp::EPI_POS_LN : vp::EPI_POS, D, 768, false);
     p.gemm[VP_PROF_GEMM_PROJ] = gemm(VP_PROF_GEMM_PROJ, resid, D, D, false);

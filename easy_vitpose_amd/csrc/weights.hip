@@ -3,6 +3,7 @@
 // LayerNorm's gamma / beta folded into qkv / fc1, pos + cls + conv bias pre-added, the deconvs re-tiled into four output-parity GEMM
 // operands, the final 1x1 conv as hi + lo pairs, e4m3 codes + scales in the fp8 mode.
 #include "api_internal.h"
+#include "simpleheadgeom.h"
 
 using namespace vpi;
 
@@ -101,6 +102,31 @@ int upload_final(vp_ctx* c, uint16_t** dst, const float* src, size_t kp, size_t 
     int rc = dalloc(c, dst, rows_pad * cols);
     if (rc) return rc;
     HIPCHK(c, hipMemcpy(*dst, tmp.data(), tmp.size() * 2, hipMemcpyHostToDevice));
+    return VP_OK;
+}
+
+// The simple decoder's 3x3 final conv as simpleheadgeom.h's weight image: tap-major, each tap a [sh_rows(K)][D] matrix in upload_final's hi / lo interleave
+// (hi = round16(w), lo = round16(w - hi)), rows of maps beyond K zero
+void pack_simple_final(const float* src, int K, int D, int dtype, std::vector<uint16_t>& img) {
+    const size_t rows = vp::sh_rows((size_t)K);
+    img.assign((size_t)vp::SH_TAPS * rows * D, 0);
+    for (int k = 0; k < K; ++k)
+        for (int d = 0; d < D; ++d)
+            for (int t = 0; t < vp::SH_TAPS; ++t) {
+                const float w = src[vp::sh_source_index(k, d, t / 3, t % 3, D)];
+                const uint16_t hi = host_to_bits(w, dtype);
+                img[vp::sh_weight_index(t, k, 0, d, rows, D)] = hi;
+                img[vp::sh_weight_index(t, k, 1, d, rows, D)] = host_to_bits(w - host_from_bits(hi, dtype), dtype);
+            }
+}
+
+int upload_simple_final(vp_ctx* c, uint16_t** dst, const float* src, int K, int D, size_t* rows_phys) {
+    std::vector<uint16_t> img;
+    pack_simple_final(src, K, D, c->dtype, img);
+    *rows_phys = vp::sh_rows((size_t)K);
+    int rc = dalloc(c, dst, img.size());
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpy(*dst, img.data(), img.size() * 2, hipMemcpyHostToDevice));
     return VP_OK;
 }
 
@@ -295,6 +321,27 @@ int vp_load_weights(vp_handle c, const vp_tensor_desc* tensors, int32_t n_tensor
     const float *p, *q;
     int E = 0, P = 0;   // ViTPose+: E experts of P features (DESIGN.md "ViTPose+")
     if ((rc = moe_layout(c, lk, &E, &P))) return rc;
+    // The decoder, read from the state dict (vp_config has no field for it): SIMPLE (relu -> bilinear x 4 -> 3x3 conv, simpleheadgeom.h) when no deconv layer is
+    // present and the final layer holds K D 9 elements; classic (two deconvs + 1x1 conv) as ever otherwise; anything in between is refused by name
+    bool simple = false;
+    {
+        const std::string fw = "keypoint_head.final_layer.weight", dc = "keypoint_head.deconv_layers.";
+        const int64_t nfw = lk.numel(fw), n1 = (int64_t)c->Kp * 256, n3 = (int64_t)c->Kp * D * 9;
+        std::string deconv_key;
+        for (const auto& kv : lk.map)
+            if (kv.first.compare(0, dc.size(), dc) == 0 && (deconv_key.empty() || kv.first < deconv_key)) deconv_key = kv.first;
+        if (nfw == n3 && E > 0)
+            return fail(c, VP_ERR_INVALID, "ViTPose+ state dict with a simple decoder (" + fw + " is [K, embed_dim, 3, 3]): no such checkpoints exist, the "
+                                           "multi-dataset models carry the classic decoder");
+        if (nfw == n3 && !deconv_key.empty())
+            return fail(c, VP_ERR_SHAPE, "size mismatch for " + fw + ": a 3x3 final layer (simple decoder) together with " + deconv_key +
+                                         " (classic decoder): the state dict is neither");
+        if (nfw >= 0 && nfw != n1 && nfw != n3 && E == 0)
+            return fail(c, VP_ERR_SHAPE, "size mismatch for " + fw + ": expected " + std::to_string(n1) + " elements (classic decoder, [K, 256, 1, 1]) or " +
+                                         std::to_string(n3) + " (simple decoder, [K, embed_dim, 3, 3]), got " + std::to_string(nfw));
+        simple = nfw == n3;
+        if (simple && D % 32) return fail(c, VP_ERR_INVALID, "simple decoder: embed_dim must be a multiple of 32");
+    }
     if (E > 0 && c->fp8) return fail(c, VP_ERR_INVALID, "ViTPose+ (expert) checkpoints are not supported in the fp8 mode: create the handle with VP_DTYPE_F16 or VP_DTYPE_BF16");
     if (E > 0 && c->Kp != kExpertK[0])
         return fail(c, VP_ERR_INVALID, "a ViTPose+ checkpoint loads on a handle created with num_keypoints = 17 (its coco head); got " + std::to_string(c->Kp));
@@ -372,6 +419,10 @@ int vp_load_weights(vp_handle c, const vp_tensor_desc* tensors, int32_t n_tensor
         if ((rc = dalloc(c, &c->expert_ids, 2 * B)) || (rc = dalloc(c, &c->mix_slot, B)) || (rc = dalloc(c, &c->mix_recs, B))) return rc;
         c->n_experts = E; c->part_features = P;
         use_expert(c, 0);
+    } else if (simple) {
+        if ((rc = lk.get("keypoint_head.final_layer.weight", (int64_t)c->Kp * D * 9, &p)) || (rc = upload_simple_final(c, &c->w_fin, p, c->Kp, D, &c->fin_rows))) return rc;
+        if ((rc = lk.get("keypoint_head.final_layer.bias", c->Kp, &p)) || (rc = upload_f32(c, &c->b_fin, p, c->Kp, pad128(c->Kp)))) return rc;
+        c->head_kind = 1;
     } else {
     if ((rc = pack_deconv(c, lk, 0, D, &c->w_d1, &c->b_d1))) return rc;
     if ((rc = pack_deconv(c, lk, 3, 256, &c->w_d2, &c->b_d2))) return rc;

@@ -13,7 +13,7 @@ import dataclasses
 
 from . import _capi as capi
 from . import moe
-from .configs import HM_H, HM_W, IMG_H, IMG_W, ModelShape
+from .configs import HEADS, HM_H, HM_W, IMG_H, IMG_W, ModelShape
 from .cropprep import PIX_FORMATS, YUV_MATRIX_IDS, Frame
 from .posenms import PoseNms, resolve_sigmas
 from .posenms import c_config as nms_c_config
@@ -102,6 +102,10 @@ class VitPoseHip:
         self._h = h
         try:
             self._load(state_dict)
+            # the decoder the loader recognised in the state dict: 'classic' (two deconvs + 1x1 conv) or 'simple' (ReLU -> bilinear x 4 -> 3x3 conv)
+            self.head = HEADS[int(self.lib.vp_head_kind(self._h))]
+            if self.shape.head != self.head:
+                self.shape = dataclasses.replace(self.shape, head=self.head)
             if self._moe:
                 n, p, ks = C.c_int32(), C.c_int32(), (C.c_int32 * 8)()
                 capi.check(self.lib.vp_expert_info(self._h, C.byref(n), C.byref(p), ks), self._h)

@@ -34,7 +34,7 @@ from typing import Optional
 
 import numpy as np
 
-from .configs import IMG_H, IMG_W, infer_dataset_by_path, infer_variant_from_state_dict, model_shape, resolve_flip_pairs
+from .configs import IMG_H, IMG_W, infer_dataset_by_path, infer_head_from_state_dict, infer_variant_from_state_dict, model_shape, resolve_flip_pairs
 from .cropprep import box_to_cs, frames_crop_params, resize_linear_u8
 from .engine import VitPoseHip, decode_heatmaps
 from .moe import DATASETS as MOE_DATASETS, is_vitpose_plus
@@ -199,7 +199,12 @@ class VitInference:
             nk = int(np.asarray(state_dict['keypoint_head.final_layer.bias']).shape[0])
         self.target_size = [IMG_W, IMG_H]  # data_cfg['image_size'], ViTPose_common.py:30
         dev_id = int(str(device).split(':')[1]) if ':' in str(device) else 0
-        shape = model_shape(model_name, None if nk else dataset, nk)
+        # the decoder comes from the file too: a `vitpose-*-simple` checkpoint (no deconv layers, a 3x3 final conv) loads with no switch
+        try:
+            head = infer_head_from_state_dict(state_dict)
+        except (KeyError, ValueError):   # a dict that is neither: the loader refuses it below, by tensor name, with the exception types it always raised
+            head = 'classic'
+        shape = model_shape(model_name, None if nk else dataset, nk, head=head)
         # flip_test (the reference's test configs: flip_test=True): a pair list, or True for the COCO-17 table; refused before anything is loaded
         flip_pairs = resolve_flip_pairs(flip_test, dataset, shape.num_keypoints)
         # pose_nms (data_cfg's oks_thr / vis_thr / soft_nms): off unless given; its sigma table is resolved, or refused, before anything is loaded

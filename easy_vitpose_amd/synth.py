@@ -19,6 +19,7 @@ attn.proj, mlp.fc1, mlp.fc2     N(0, 0.02) weight and bias
 deconv weights                  N(0, sqrt(2 / (4*Cin)))
 BN weight/bias/mean/var         1+N(0,.1) / N(0,.1) / N(0,.1) / U(.5,1.5)
 final_layer.weight / bias       N(0, 0.3/16) / N(0, 0.02)
+simple decoder: final_layer     N(0, 0.3 / sqrt(9 D)) / N(0, 0.02)
 =============================== =====================================
 """
 from __future__ import annotations
@@ -38,7 +39,7 @@ _CODE_NOMINAL = {(384, 12): 18.4, (768, 12): 23.6, (1024, 24): 24.7, (1280, 32):
 _CODE_NOMINAL_OUT = {(384, 12): 1.75, (768, 12): 1.866, (1024, 24): 3.474, (1280, 32): 4.898}
 
 
-def synthetic_state_dict(shape: ModelShape, seed: int = 0, peaked: bool = False, outliers: bool = False) -> "dict[str, np.ndarray]":
+def synthetic_state_dict(shape: ModelShape, seed: int = 0, peaked: bool = False, outliers: bool = False, head: str = 'classic') -> "dict[str, np.ndarray]":
     """Return ``{name: float32 ndarray}`` with the reference's key names/shapes.
 
     ``peaked=False``: every tensor random (table above) -- heatmaps are noise-like (std ~0.3): right for throughput
@@ -60,7 +61,13 @@ def synthetic_state_dict(shape: ModelShape, seed: int = 0, peaked: bool = False,
     All GEMMs, LayerNorms, the attention and the head still see full-scale random operands; only the read-out is designed.
 
     ``outliers=True`` (with or without ``peaked``): the activation statistics of TRAINED ViTs that seeded random tensors lack --
-    "massive activations" in a few residual channels and one attention head with large logits (``_make_outliers``)."""
+    "massive activations" in a few residual channels and one attention head with large logits (``_make_outliers``).
+
+    ``head='simple'``: the simple decoder's schema instead of the classic one's -- no ``deconv_layers``, ``final_layer.weight`` of shape
+    ``[K, D, 3, 3]`` (ReLU -> bilinear x 4 -> 3x3 conv).  The backbone tensors are the classic dict's of the same seed bit for bit (they are drawn
+    first).  ``peaked``: the read-out sits in the centre tap of the code channels (``_peak_simple_head``).  The default leaves every existing
+    caller's tensors unchanged."""
+    assert head in ('classic', 'simple'), head
     rng = np.random.Generator(np.random.PCG64(seed))
     D, L, K = shape.embed_dim, shape.depth, shape.num_keypoints
     sd: dict[str, np.ndarray] = {}
@@ -87,12 +94,21 @@ def synthetic_state_dict(shape: ModelShape, seed: int = 0, peaked: bool = False,
         sd[p + 'mlp.fc2.bias'] = normal((D,), 0.02)
     sd['backbone.last_norm.weight'] = normal((D,), 0.1, 1.0)
     sd['backbone.last_norm.bias'] = normal((D,), 0.05)
-    _random_head(sd, 'keypoint_head', rng, D, K)
+    if head == 'simple':
+        _random_simple_head(sd, 'keypoint_head', rng, D, K)
+    else:
+        _random_head(sd, 'keypoint_head', rng, D, K)
     if outliers:
         _make_outliers(sd, shape, seed)
     if peaked:
-        _make_peaked(sd, shape, seed, outliers)
+        _make_peaked(sd, shape, seed, outliers, head)
     return sd
+
+
+def _random_simple_head(sd, prefix: str, rng, D: int, K: int) -> None:
+    """The random simple decoder under `prefix`: a 3x3 conv on D channels, heatmaps of std ~0.3 on LayerNorm-scale tokens."""
+    sd[f'{prefix}.final_layer.weight'] = (rng.standard_normal((K, D, 3, 3), dtype=np.float32) * np.float32(0.3 / np.sqrt(9.0 * D))).astype(np.float32)
+    sd[f'{prefix}.final_layer.bias'] = (rng.standard_normal((K,), dtype=np.float32) * np.float32(0.02)).astype(np.float32)
 
 
 def _random_head(sd, prefix: str, rng, D: int, K: int) -> None:
@@ -160,14 +176,35 @@ def _make_outliers(sd, shape: ModelShape, seed: int) -> None:
             sd[p + 'attn.qkv.bias'][r] *= gain
 
 
-def _make_peaked(sd, shape: ModelShape, seed: int, outliers: bool = False) -> None:
+def _make_peaked(sd, shape: ModelShape, seed: int, outliers: bool = False, head: str = 'classic') -> None:
     D, L = shape.embed_dim, shape.depth
     code = (_CODE_NOMINAL_OUT if outliers else _CODE_NOMINAL).get((D, L), 0.8 * float(np.sqrt(D)))
     pos = sd['backbone.pos_embed']
     a = np.float32(2.5 * np.sqrt(D) * np.sqrt(L / 12.0))
     for t in range(192):
         pos[0, 1 + t, t] += a
-    _peak_head(sd, 'keypoint_head', np.random.Generator(np.random.PCG64(seed + 7777)), code, shape.num_keypoints)
+    rng = np.random.Generator(np.random.PCG64(seed + 7777))
+    if head == 'simple':
+        _peak_simple_head(sd, 'keypoint_head', rng, code, shape.num_keypoints)
+    else:
+        _peak_head(sd, 'keypoint_head', rng, code, shape.num_keypoints)
+
+
+def _peak_simple_head(sd, prefix: str, rng, code: float, K: int) -> None:
+    """The designed read-out on a simple decoder: token t carries its position code in channel t (> 0 there, ~0 elsewhere, so the ReLU keeps it), the
+    bilinear x 4 upsample turns channel t into the tent function of token t, and the CENTRE tap of the 3x3 conv reads
+    ``w[k, t, 1, 1] = amp_k G_k(token t) / code`` -- heatmap k = the bilinear interpolation of the Gaussian G_k sampled on the token grid, times the
+    content-dependent LayerNorm gain.  The random part of the dict is scaled by 0.15 and rides in all nine taps (the eight outer taps of the code
+    channels included, additionally divided by the code): low noise around one clear maximum per joint."""
+    w = sd[f'{prefix}.final_layer.weight'] * np.float32(0.15)
+    w[:, :192] /= np.float32(code)
+    ty, tx = np.mgrid[0:16, 0:12].astype(np.float64)
+    for k in range(K):
+        cy, cx = rng.uniform(1.0, 14.0), rng.uniform(1.0, 10.0)
+        sg, amp = rng.uniform(0.55, 0.8), rng.uniform(0.35, 0.95)
+        g = amp * np.exp(-((ty - cy) ** 2 + (tx - cx) ** 2) / (2.0 * sg * sg))
+        w[k, :192, 1, 1] += (g.reshape(-1) / (code * 0.67)).astype(np.float32)   # 0.67: peak of the interpolated blob / amp, as in _peak_head
+    sd[f'{prefix}.final_layer.weight'] = np.ascontiguousarray(w, dtype=np.float32)
 
 
 def _peak_head(sd, prefix: str, rng, code: float, K: int, rows: int = 0) -> None:

@@ -1319,6 +1319,27 @@ VP_API int vp_dbg_yolo_activation(vp_yolo_handle y, int32_t launch, int32_t n_im
 VP_API int vp_dbg_yolo_conv_case(vp_handle h, const vp_yolo_launch* l, int32_t n_images, const uint16_t* in, const uint16_t* w, const float* bias, const uint16_t* res,
                                  void* out);
 
+/* The simple decoder (upstream ViTPose's `vitpose-{s,b,l,h}-simple` files: TopdownHeatmapSimpleHead with num_deconv_layers = 0, upsample = 4 and
+ * final_conv_kernel = 3, i.e. ReLU -> bilinear x 4 (align_corners = False) -> Conv2d(D, K, 3, padding = 1)).  vp_load_weights recognises it from the state dict --
+ * vp_config is unchanged: the decoder is SIMPLE when no keypoint_head.deconv_layers.* tensor is present and keypoint_head.final_layer.weight holds K * D * 9
+ * elements, classic (two deconvs + 1 x 1 conv) as ever otherwise.  Refused: a 3 x 3 final layer together with deconv_layers.* (VP_ERR_SHAPE), a final layer of
+ * neither K * 256 nor K * D * 9 elements (VP_ERR_SHAPE), a ViTPose+ dict (mlp.experts.*) with a 3 x 3 final layer (VP_ERR_INVALID: no such checkpoints exist);
+ * the message names the tensor.  On a simple-decoder handle the head of every entry (vp_infer*, submit / wait, frames, boxes, affine crops, the flip-test mode, graph
+ * replay, groups, vp_infer_heatmaps) is one kernel in the commuted form of csrc/simpleheadgeom.h: fp32 from the tokens to the heatmaps, profiled under
+ * VP_PROF_GEMM_FINAL.  Unpinned: parity with upstream ViTPose's own binary and with a published -simple checkpoint (the reference cannot execute this decoder).
+ *   vp_head_kind: 0 = classic, 1 = simple; -1 without loaded weights.
+ *   vp_dbg_simple_head_pack (HOST ONLY, no device): final_layer.weight w [K, D, 3, 3] -> the weight image the kernel reads, uint16 [9][rows][D] with
+ *     rows = 32 ceil(K / 16): tap t = 3 ky + kx major, map k's hi row at (k / 16) 32 + k % 16 and its lo row 16 behind (hi = round16(w), lo = round16(w - hi)),
+ *     rows of maps beyond K zero.  *rows is always written; image may be NULL to ask for it only.
+ *   vp_dbg_simple_head_case: the launch the forward builds, on host data.  x = tokens float32 [B, 192, Cin] (rounded to dtype on upload: a no-op on values of that
+ *     type), w [Kp, Cin, 3, 3], b [Kp] -> out float32 [B, Kp, 64, 48].  The device output is filled with 0xFF bytes first and followed by 16 planes of 64 x 48
+ *     floats, which come back as bytes in guard [16 * 3072 * 4].  Cin a multiple of 32.  Library builds that carry the decoder define VP_HAS_SIMPLE_HEAD. */
+#define VP_HAS_SIMPLE_HEAD 1
+VP_API int vp_head_kind(vp_handle h);
+VP_API int vp_dbg_simple_head_pack(int32_t dtype, int32_t K, int32_t D, const float* w, uint16_t* image, int32_t* rows);
+VP_API int vp_dbg_simple_head_case(int32_t device_id, int32_t dtype, int32_t B, int32_t Cin, const float* x, const float* w, const float* b, int32_t Kp, float* out,
+                                   uint8_t* guard);
+
 #ifdef __cplusplus
 }
 #endif
