@@ -31,6 +31,8 @@ CONF_ERR = {'fp16': CONF_TOL, 'bf16': 1.5e-2}   # bf16 operands do NOT meet the 
 # ----------------------------------------------------------------------------- decode
 @pytest.mark.parametrize('tag', ['decode_k17', 'decode_k133'])
 def test_decode_matches_reference_golden(golden_dir, tag):
+    """The reference's own outputs under one flat tolerance.  The per-joint check -- a float64 model of the kernel, a derived bound and a conditioning class per
+    joint, ties, borders, the wrap and the clip bounds -- is tests/test_gpu_decode.py (tests/decode_model.py, tests/decode_cases.py)."""
     z = np.load(os.path.join(golden_dir, f'{tag}.npz'))
     n, k, seed = int(z['n']), int(z['k']), int(z['seed'])
     hm, wh = peaked_heatmaps(n, k, seed), org_sizes(n, seed)
