@@ -29,7 +29,7 @@ SYMBOLS = ['vp_abi_version', 'vp_create', 'vp_load_weights', 'vp_infer', 'vp_inf
            'vp_infer_tokens', 'vp_decode_only', 'vp_stream', 'vp_synchronize', 'vp_set_profiling',
            'vp_reset_profile', 'vp_get_profile', 'vp_profile_kernel', 'vp_group_peer_access_missing', 'vp_destroy', 'vp_last_error',
            'vp_dbg_gemm', 'vp_dbg_attention', 'vp_dbg_layernorm', 'vp_dbg_deconv', 'vp_dbg_gemm_case', 'vp_dbg_crop_prep',
-           'vp_dbg_group_plan', 'vp_dbg_group_trace', 'vp_dbg_gemm8_pick', 'vp_dbg_gemm2_pick', 'vp_dbg_splitk_pick', 'vp_dbg_run_batch', 'vp_dbg_fp8_gemm', 'vp_dbg_mx_gemm', 'vp_dbg_host_e4m3', 'vp_dbg_gemm_fp8_case', 'vp_dbg_qkvattn',
+           'vp_dbg_group_plan', 'vp_dbg_group_trace', 'vp_dbg_gemm8_pick', 'vp_dbg_gemm2_pick', 'vp_dbg_splitk_pick', 'vp_dbg_run_batch', 'vp_dbg_fp8_gemm', 'vp_dbg_mx_gemm', 'vp_dbg_host_e4m3', 'vp_dbg_gemm_fp8_case', 'vp_dbg_gemm_fp8_case_raw', 'vp_dbg_gemm_fp8_pick', 'vp_dbg_qkvattn',
            'vp_expert_info', 'vp_set_expert', 'vp_infer_experts', 'vp_dbg_expert_tile', 'vp_infer_frames', 'vp_dbg_frame_plan',
            'vp_dbg_chunk_plan', 'vp_infer_boxes_stream', 'vp_dbg_box_geometry',
            'vp_set_flip_test', 'vp_clear_flip_test', 'vp_flip_test_enabled', 'vp_group_set_flip_test', 'vp_group_clear_flip_test',
@@ -250,6 +250,8 @@ def load_library():
     lib.vp_dbg_mx_gemm.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 7
     lib.vp_dbg_host_e4m3.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     lib.vp_dbg_gemm_fp8_case.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 8
+    lib.vp_dbg_gemm_fp8_case_raw.argtypes = [C.c_int32] * 5 + [C.c_void_p] * 8 + [C.c_int32] + [C.c_void_p] * 3
+    lib.vp_dbg_gemm_fp8_pick.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 2
     lib.vp_dbg_gemm_case_planes.argtypes = [C.c_int32] * 9 + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3
     lib.vp_dbg_gemm_fp8_case_planes.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 5
     lib.vp_expert_info.argtypes = [H, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -656,10 +656,20 @@ VP_API int vp_dbg_mx_gemm(int32_t device, int32_t M, int32_t N, int32_t K, const
 // a_deq / w_deq return what the codes and scales stand for, so that the test can restate the product exactly.
 //   epi 0: out = a.w^T * w_scale + bias, rounded to fp16        epi 1: out = gelu(...) as MXFP8 (returned de-quantised)
 //   epi 6: out = ... + aux (two-plane residual, returned as hi + lo), stats [M, N/64, 2]
-// the body of vp_dbg_gemm_fp8_case and vp_dbg_gemm_fp8_case_planes (io != NULL: epi 6 on plane bits)
+// the tile of one case: the project's own rule, as forward.hip asks it (no way to force a tile)
+static GemmPick fp8_case_pick(int32_t epi, int32_t M, int32_t N) {
+    const int fam = epi == 0 ? VP_PROF_GEMM_QKV : epi == 1 ? VP_PROF_GEMM_FC1 : VP_PROF_GEMM_FC2;
+    return resolve_gemm_fp8(fam, epi, M, N);
+}
+// what vp_dbg_gemm_fp8_case_raw adds (tests/test_gpu_fp8_gemm.py): the buffers as the device holds them
+struct Fp8Raw {
+    bool out_blocked;                       // epi 0: LnFuse::out_blocked; `out` comes back in device order [M/64][N/64][64][64]
+    uint8_t *o_codes, *o_scales, *a_scales; // epi 1: output codes [M*N] / scale bytes [M*N/32]; any epi: operand scale bytes [M*K/32]; device order, may be NULL
+};
+// the body of vp_dbg_gemm_fp8_case, vp_dbg_gemm_fp8_case_raw and vp_dbg_gemm_fp8_case_planes (io != NULL: epi 6 on plane bits)
 static int gemm_fp8_case(int32_t device, int32_t epi, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias, const float* aux, float* out,
-                         float* stats, float* a_deq, float* w_deq, const PlaneIO* io) {
-    if (M <= 0 || N <= 0 || K <= 0 || M % 256 || K % 256 || N % 64 || !A || !W || !bias || (epi != 0 && epi != 1 && epi != 6))
+                         float* stats, float* a_deq, float* w_deq, const PlaneIO* io, const Fp8Raw* raw = nullptr) {
+    if (M <= 0 || N <= 0 || K <= 0 || M % 256 || K % 256 || N % 64 || !A || !W || !bias || (epi != 0 && epi != 1 && epi != 6) || (raw && raw->out_blocked && epi != 0))
         return fail(nullptr, VP_ERR_INVALID, "bad fp8 gemm case");
     vp_ctx* c = dbg_ctx(device, VP_DTYPE_F16);
     if (!c) return VP_ERR_HIP;
@@ -676,7 +686,11 @@ static int gemm_fp8_case(int32_t device, int32_t epi, int32_t M, int32_t N, int3
     if (e != hipSuccess) return dbg_finish(c, fail(c, VP_ERR_HIP, "mx quantize"));
     const size_t out_bytes = epi == 0 ? MN * 2 : epi == 1 ? MN : MN * 4;
     LnFuse ln;
-    if (epi == 1 && (r = dalloc(c, &dOs, MN / 32))) return dbg_finish(c, r);
+    if (epi == 1) {
+        if ((r = dalloc(c, &dOs, MN / 32))) return dbg_finish(c, r);
+        hipMemset(dOs, 0xff, MN / 32);   // as the codes below: an unwritten scale dword shows
+    }
+    if (raw) ln.out_blocked = raw->out_blocked;
     if (epi == 6) {
         if ((r = upload_planes(c, &dAux16, aux, io ? io->r_hi : nullptr, io ? io->r_lo : nullptr, MN)) || (r = dalloc(c, &dStats, (size_t)M * (N / 64) * 2)))
             return dbg_finish(c, r);
@@ -688,7 +702,7 @@ static int gemm_fp8_case(int32_t device, int32_t epi, int32_t M, int32_t N, int3
         hipMemset(dOut, 0xff, out_bytes);
     }
     const int fam = epi == 0 ? VP_PROF_GEMM_QKV : epi == 1 ? VP_PROF_GEMM_FC1 : VP_PROF_GEMM_FC2;
-    r = gemm_fp8(c, fam, epi, resolve_gemm_fp8(fam, epi, M, N), dA8, dAs, dW8, dWs, dB, dOut, dOs, (const float*)dAux16, M, N, K, &ln);
+    r = gemm_fp8(c, fam, epi, fp8_case_pick(epi, M, N), dA8, dAs, dW8, dWs, dB, dOut, dOs, (const float*)dAux16, M, N, K, &ln);
     if (!r && hipDeviceSynchronize() != hipSuccess) r = fail(c, VP_ERR_HIP, "fp8 gemm kernel failed");
     if (r) return dbg_finish(c, r);
     // what the operands stand for
@@ -696,6 +710,7 @@ static int gemm_fp8_case(int32_t device, int32_t epi, int32_t M, int32_t N, int3
         std::vector<uint8_t> ca(MK), sa(MK / 32);
         if (hipMemcpy(ca.data(), dA8, MK, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(sa.data(), dAs, MK / 32, hipMemcpyDeviceToHost) != hipSuccess)
             return dbg_finish(c, fail(c, VP_ERR_HIP, "D2H"));
+        if (raw && raw->a_scales) memcpy(raw->a_scales, sa.data(), sa.size());
         if (a_deq)
             for (size_t m = 0; m < (size_t)M; ++m)
                 for (size_t k = 0; k < (size_t)K; ++k)
@@ -715,6 +730,8 @@ static int gemm_fp8_case(int32_t device, int32_t epi, int32_t M, int32_t N, int3
         std::vector<uint8_t> co(MN), so(MN / 32);
         if (hipMemcpy(co.data(), dOut, MN, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(so.data(), dOs, MN / 32, hipMemcpyDeviceToHost) != hipSuccess)
             return dbg_finish(c, fail(c, VP_ERR_HIP, "D2H"));
+        if (raw && raw->o_codes) memcpy(raw->o_codes, co.data(), co.size());
+        if (raw && raw->o_scales) memcpy(raw->o_scales, so.data(), so.size());
         for (size_t m = 0; m < (size_t)M; ++m)
             for (size_t n = 0; n < (size_t)N; ++n)
                 out[m * N + n] = vp_host_e4m3_to_float(co[vp::mx_code_off(m, n, N)]) * std::ldexp(1.0f, (int)so[vp::mx_scale_off(m, n >> 5, N)] - 127);
@@ -729,6 +746,23 @@ VP_API int vp_dbg_gemm_fp8_case(int32_t device, int32_t epi, int32_t M, int32_t 
                                 const float* aux, float* out, float* stats, float* a_deq, float* w_deq) {
     if (!out) return fail(nullptr, VP_ERR_INVALID, "bad fp8 gemm case");
     return gemm_fp8_case(device, epi, M, N, K, A, W, bias, aux, out, stats, a_deq, w_deq, nullptr);
+}
+
+// ... with the buffers as the device holds them (tests/test_gpu_fp8_gemm.py).  flags: 1 = LnFuse::out_blocked (epi 0 only).  o_codes / o_scales (epi 1) and
+// a_scales may be NULL; the test de-blocks them itself
+VP_API int vp_dbg_gemm_fp8_case_raw(int32_t device, int32_t epi, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias, const float* aux,
+                                    float* out, float* stats, float* a_deq, float* w_deq, int32_t flags, uint8_t* o_codes, uint8_t* o_scales, uint8_t* a_scales) {
+    if (!out || (flags & ~1)) return fail(nullptr, VP_ERR_INVALID, "bad fp8 gemm case");
+    const Fp8Raw raw{(flags & 1) != 0, o_codes, o_scales, a_scales};
+    return gemm_fp8_case(device, epi, M, N, K, A, W, bias, aux, out, stats, a_deq, w_deq, nullptr, &raw);
+}
+
+// host only: the tile the taps above launch a case on -- resolve_gemm_fp8's variant (16 = 256 x 256, 17 = 256 x 192) and its group_m
+VP_API int vp_dbg_gemm_fp8_pick(int32_t epi, int32_t M, int32_t N, int32_t* variant, int32_t* group_m) {
+    if (M <= 0 || N <= 0 || (epi != 0 && epi != 1 && epi != 6) || !variant || !group_m) return VP_ERR_INVALID;
+    const GemmPick p = fp8_case_pick(epi, M, N);
+    *variant = p.variant; *group_m = p.group_m;
+    return VP_OK;
 }
 
 // ... and its producer-row sibling (epi 6), as vp_dbg_gemm_case_planes: residual and output as plane bits, in_place = out == aux; a_deq / w_deq as above

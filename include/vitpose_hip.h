@@ -1238,6 +1238,15 @@ VP_API int vp_dbg_mx_gemm(int32_t device_id, int32_t M, int32_t N, int32_t K, co
  * (hi + lo returned), stats [M, N/64, 2].  M % 256 == 0, K % 256 == 0, K >= 512, N % 256 == 0 (epi 6: N % 192 == 0 or N % 256 == 0). */
 VP_API int vp_dbg_gemm_fp8_case(int32_t device_id, int32_t epi, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias,
                                 const float* aux, float* out, float* stats, float* a_deq, float* w_deq);
+/* vp_dbg_gemm_fp8_case with the buffers as the device holds them (tests/test_gpu_fp8_gemm.py).  flags: 1 = the 64 x 64-blocked output of attn.qkv (epi 0
+ * only): out [M*N] then comes back in device order [M/64][N/64][64][64].  epi 1: o_codes [M*N] and o_scales [M*N/32] return the output's e4m3 codes and
+ * E8M0 scale bytes in device order (csrc/mx8.h; both buffers are filled with 0xff before the launch); a_scales [M*K/32]: the scale bytes of the quantised
+ * A operand in device order.  o_codes, o_scales, a_scales may be NULL. */
+VP_API int vp_dbg_gemm_fp8_case_raw(int32_t device_id, int32_t epi, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias,
+                                    const float* aux, float* out, float* stats, float* a_deq, float* w_deq, int32_t flags, uint8_t* o_codes,
+                                    uint8_t* o_scales, uint8_t* a_scales);
+/* HOST ONLY: the tile the vp_dbg_gemm_fp8_case* taps launch a case on, by the fp8 mode's own rule: variant 16 = 256 x 256, 17 = 256 x 192; group_m of the tile walk */
+VP_API int vp_dbg_gemm_fp8_pick(int32_t epi, int32_t M, int32_t N, int32_t* variant, int32_t* group_m);
 /* vp_dbg_gemm_fp8_case, epi 6, with the residual stream as plane bits (fp16 codes) on both sides, as vp_dbg_gemm_case_planes */
 VP_API int vp_dbg_gemm_fp8_case_planes(int32_t device_id, int32_t M, int32_t N, int32_t K, const float* A, const float* W, const float* bias,
                                        const uint16_t* r_hi, const uint16_t* r_lo, int32_t in_place, uint16_t* o_hi, uint16_t* o_lo, float* stats,

@@ -9,6 +9,9 @@ NORTH_STAR'S 1e-3 ON CONFIDENCES, it is never a default and never counts toward 
 * end to end on the peaked AP-10K checkpoint: coordinates within the north_star's +-0.5 px on EVERY joint, confidence error measured
   and asserted at its real bound (several 1e-3 -- printed);
 * mode properties at BASELINE configs[4]'s batch (512): finite, run-to-run identical, crop i of 512 == crop i alone.
+
+Launches of more than 256 tiles (a workgroup's second and third tile), mlp.fc1's GELU + MXFP8 epilogue per element on raw codes and scale bytes, and attn.qkv's
+64 x 64-blocked store by position live in tests/test_gpu_fp8_gemm.py.
 """
 import numpy as np
 import pytest
