@@ -8,6 +8,7 @@
 // No atomics, no flags between workgroups, no synchronisation, no allocation in a call; the launch sequence depends on the configuration only, so a call captures
 // as one linear chain.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "cocogeom.h"
 
 using namespace vpi;
@@ -470,8 +471,6 @@ struct vp_cocoeval {
 
 namespace {
 
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-
 struct UpdateArgs {
     const float *kpts, *score;
     const int32_t *frame, *rank;
@@ -699,10 +698,12 @@ int vp_cocoeval_create(vp_handle c, const vp_cocoeval_cfg* cfg, const double* si
     while (pcap < M) pcap <<= 1;
     const int chunks = (M + vp::CE_CHUNK - 1) / vp::CE_CHUNK;
     const size_t AT = vp::COCO_AT, RK = AT * vp::COCO_RECS;
-    const size_t sizes[] = {up256(e->state_bytes), up256((size_t)K * 8), up256(vp::COCO_MAX_FRAMES * 4), up256(vp::COCO_MAX_FRAMES * sizeof(vp::CocoImg)), up256((size_t)pcap * 8),
-                            up256((size_t)M * 8), up256((size_t)chunks * 2 * AT * 4), up256(AT * chunks * 8), up256(RK * 4), up256(RK * 8), up256(AT * 8)};
-    size_t bytes = 0, off[11];
-    for (int i = 0; i < 11; ++i) { off[i] = bytes; bytes += sizes[i]; }
+    const size_t sizes[] = {e->state_bytes, (size_t)K * 8, vp::COCO_MAX_FRAMES * 4, vp::COCO_MAX_FRAMES * sizeof(vp::CocoImg), (size_t)pcap * 8,
+                            (size_t)M * 8, (size_t)chunks * 2 * AT * 4, AT * chunks * 8, RK * 4, RK * 8, AT * 8};
+    StageLayout lay;
+    size_t off[11];
+    for (int i = 0; i < 11; ++i) off[i] = lay.part(sizes[i]);
+    const size_t bytes = lay.end;
     std::vector<double> vars;
     host_vars(sigmas, K, vars);
     hipError_t err = hipMalloc((void**)&e->mem, bytes);
@@ -764,33 +765,28 @@ int vp_cocoeval_update(vp_cocoeval_handle e, const float* kpts, const float* sco
     const UpdateArgs h{kpts, score, frame, rank, n, gt_kpts, gt_box, gt_area, gt_flags, gt_frame, g, n_frames, match};
     std::string why;
     if (update_check(h, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // one scratch allocation, every part 256-byte aligned: kpts | score | frame | rank | gt_kpts | gt_box | gt_area | gt_flags | gt_frame | match
+    // one scratch block: kpts | score | frame | rank | gt_kpts | gt_box | gt_area | gt_flags | gt_frame | match
+    HostStage st(c);
     const int K = e->K;
     const size_t raw[] = {(size_t)n * K * 12, (size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)g * K * 12, (size_t)g * 16, (size_t)g * 4, (size_t)g * 4, (size_t)g * 4, (size_t)n * 40};
     const void* src[] = {kpts, score, frame, rank, gt_kpts, gt_box, gt_area, gt_flags, gt_frame, nullptr};
-    size_t off[10], bytes = 0;
-    for (int i = 0; i < 10; ++i) { off[i] = bytes; bytes += up256(raw[i]); }
-    char* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, bytes + 256));
-    hipStream_t q = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t err, const char* what) { if (err != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(err)); };
-    const void* dev[10];
+    size_t off[10];
+    for (int i = 0; i < 10; ++i) off[i] = st.part(raw[i]);
+    if (st.alloc()) return st.rc;
+    void* dev[10];
     for (int i = 0; i < 10; ++i) {
         const bool given = raw[i] > 0 && (i == 9 ? match != nullptr : src[i] != nullptr);
-        dev[i] = given ? d + off[i] : nullptr;
-        if (given && i < 9) chk(hipMemcpyAsync(d + off[i], src[i], raw[i], hipMemcpyHostToDevice, q), "cocoeval upload");
+        dev[i] = given ? st.at(off[i]) : nullptr;
+        if (given && i < 9) st.up(dev[i], src[i], raw[i], "cocoeval upload");
     }
-    if (!rc) {
+    if (!st.rc) {
         const UpdateArgs u{(const float*)dev[0], (const float*)dev[1], (const int32_t*)dev[2], (const int32_t*)dev[3], n, (const float*)dev[4], (const float*)dev[5],
                            (const float*)dev[6], (const int32_t*)dev[7], (const int32_t*)dev[8], g, n_frames, (int32_t*)dev[9]};
-        rc = update_enqueue(e, u, q);
+        st.rc = update_enqueue(e, u, st.s);
     }
-    if (!rc && dev[9]) chk(hipMemcpyAsync(match, dev[9], raw[9], hipMemcpyDeviceToHost, q), "cocoeval download match");
-    chk(hipStreamSynchronize(q), "hipStreamSynchronize");
-    (void)hipFree(d);
-    return rc;
+    if (!st.rc && dev[9]) st.down(match, dev[9], raw[9], "cocoeval download match");
+    st.sync();
+    return st.rc;
 }
 
 int vp_cocoeval_accumulate_stream(vp_cocoeval_handle e, void* d_out, void* caller_stream) {
@@ -803,16 +799,14 @@ int vp_cocoeval_accumulate(vp_cocoeval_handle e, void* out) {
     if (!e) return VP_ERR_INVALID;
     vp_ctx* c = e->c;
     if (!out) return fail(c, VP_ERR_INVALID, "cocoeval: null accumulate destination");
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipDeviceSynchronize());
-    char* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, vp::coco_result_bytes()));
-    int rc = accumulate_enqueue(e, d, c->own_stream);
-    auto chk = [&](hipError_t err, const char* what) { if (err != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(err)); };
-    chk(hipStreamSynchronize(c->own_stream), "hipStreamSynchronize");
-    chk(hipMemcpy(out, d, vp::coco_result_bytes(), hipMemcpyDeviceToHost), "cocoeval download result");
-    (void)hipFree(d);
-    return rc;
+    HostStage st(c);   // the result; a blocking copy behind the synchronisation
+    st.chk(hipDeviceSynchronize(), "hipDeviceSynchronize()");
+    const size_t o_res = st.part(vp::coco_result_bytes());
+    if (st.alloc()) return st.rc;
+    st.rc = accumulate_enqueue(e, st.at(o_res), st.s);
+    st.sync();
+    st.chk(hipMemcpy(out, st.at(o_res), vp::coco_result_bytes(), hipMemcpyDeviceToHost), "cocoeval download result");
+    return st.rc;
 }
 
 int vp_cocoeval_state_bytes(const vp_cocoeval_cfg* cfg, int64_t* bytes) {

@@ -2,6 +2,7 @@
 // collectgeom.h), its synchronous host twin vp_collect and the host-only tap vp_dbg_collect_host.  Two kernels: a plan that gives every row its record index from
 // ballots and a prefix over waves, then a copy with one wave per row.  No atomics: the table is a pure function of the inputs whatever the launch shape.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "collectgeom.h"
 
 using namespace vpi;
@@ -174,44 +175,37 @@ int vp_collect(vp_handle c, const float* kpts, int32_t n, int32_t k, const int32
     if (!c) return VP_ERR_INVALID;
     std::string why;
     if (collect_args(kpts, n, k, score_stride, n_frames, max_records, out, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // one scratch allocation: the table | keypoints | ids | frame | rank | status | score | crop params (every part 256-byte aligned)
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b_out = up((size_t)vp::collect_bytes(n_frames, k, max_records)), b_kp = up((size_t)n * 3 * k * 4), b_n = up((size_t)n * 4),
-                 sc_bytes = score && n > 0 ? ((size_t)(n - 1) * score_stride + 1) * 4 : 0, b_sc = up(sc_bytes), b_cp = up((size_t)n * 9 * 4);
-    char* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, b_out + b_kp + 4 * b_n + b_sc + b_cp + 256));
-    hipStream_t s = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    char* q = d + b_out;
-    auto put = [&](const void* src, size_t bytes, size_t room, const char* what) -> const void* {
-        char* at = q;
-        if (src && bytes) chk(hipMemcpyAsync(at, src, bytes, hipMemcpyHostToDevice, s), what);
-        q += room;
-        return src ? at : nullptr;
-    };
-    const float* d_kp = (const float*)put(kpts, (size_t)n * 3 * k * 4, b_kp, "upload keypoints");
-    const int32_t* d_id = (const int32_t*)put(ids, (size_t)n * 4, b_n, "upload ids");
-    const int32_t* d_fr = (const int32_t*)put(frame, (size_t)n * 4, b_n, "upload frame");
-    const int32_t* d_rk = (const int32_t*)put(rank, (size_t)n * 4, b_n, "upload rank");
-    const int32_t* d_st = (const int32_t*)put(status, (size_t)n * 4, b_n, "upload status");
-    const float* d_sc = (const float*)put(score, sc_bytes, b_sc, "upload score");
-    const int32_t* d_cp = (const int32_t*)put(crop_params, (size_t)n * 9 * 4, b_cp, "upload crop params");
-    if (!rc) rc = collect_enqueue(c, collect_in(d_kp, n, k, d_id, d_fr, d_rk, d_st, d_sc, score_stride, d_cp, n_frames, max_records), d, s);
+    // one scratch block: the table | keypoints | ids | frame | rank | status | score | crop params
+    HostStage st(c);
+    const size_t nb = (size_t)n * 4, sc_bytes = score && n > 0 ? ((size_t)(n - 1) * score_stride + 1) * 4 : 0;
+    const size_t o_out = st.part((size_t)vp::collect_bytes(n_frames, k, max_records));
+    const void* src[7] = {kpts, ids, frame, rank, status, score, crop_params};
+    const size_t bytes[7] = {(size_t)n * 3 * k * 4, nb, nb, nb, nb, sc_bytes, (size_t)n * 9 * 4};
+    const char* what[7] = {"upload keypoints", "upload ids", "upload frame", "upload rank", "upload status", "upload score", "upload crop params"};
+    size_t off[7];
+    for (int i = 0; i < 7; ++i) off[i] = st.part(bytes[i]);
+    if (st.alloc()) return st.rc;
+    const void* dev[7];   // an absent input stays null; an empty one has an address and no copy
+    for (int i = 0; i < 7; ++i) {
+        dev[i] = src[i] ? st.at(off[i]) : nullptr;
+        if (src[i] && bytes[i]) st.up(st.at(off[i]), src[i], bytes[i], what[i]);
+    }
+    char* d = st.at(o_out);
+    if (!st.rc)
+        st.rc = collect_enqueue(c, collect_in((const float*)dev[0], n, k, (const int32_t*)dev[1], (const int32_t*)dev[2], (const int32_t*)dev[3], (const int32_t*)dev[4],
+                                              (const float*)dev[5], score_stride, (const int32_t*)dev[6], n_frames, max_records), d, st.s);
     // the header first: its total says how many records were written, and no byte behind them is touched on the host either
     const size_t hb = (size_t)vp::collect_header_words(n_frames) * 4;
-    if (!rc) chk(hipMemcpyAsync(out, d, hb, hipMemcpyDeviceToHost, s), "download header");
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-    if (!rc) {
+    if (!st.rc) st.down(out, d, hb, "download header");
+    st.sync();
+    if (!st.rc) {
         const int32_t total = ((const int32_t*)out)[n_frames], m = total < max_records ? total : max_records;
         if (m > 0) {
-            chk(hipMemcpyAsync((char*)out + hb, d + hb, (size_t)m * vp::collect_record_words(k) * 4, hipMemcpyDeviceToHost, s), "download records");
-            chk(hipStreamSynchronize(s), "hipStreamSynchronize");
+            st.down((char*)out + hb, d + hb, (size_t)m * vp::collect_record_words(k) * 4, "download records");
+            st.sync();
         }
     }
-    (void)hipFree(d);
-    return rc;
+    return st.rc;
 }
 
 int vp_dbg_collect_host(const float* kpts, int32_t n, int32_t k, const int32_t* ids, const int32_t* frame, const int32_t* rank, const int32_t* status,

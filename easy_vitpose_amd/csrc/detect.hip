@@ -3,6 +3,7 @@
 // workgroup reserves their slots, in arbitrary order), det_nms_kernel, one workgroup per image, ranks them on the 64-bit key -- which restores a fixed order -- runs
 // the greedy NMS and re-zeroes the image's counters, det_pack_kernel, one thread per output row, packs the images' rows.  Every output is a pure function of the inputs.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "detgeom.h"
 
 using namespace vpi;
@@ -460,36 +461,28 @@ int vp_detect(vp_detector_handle d, const void* pred, int32_t A, const vp_det_im
     vp_ctx* c = d->c;
     std::string why;
     if (call_args(d->p, d->max_anchors, d->max_images, pred, A, images, n_images, rows, image, anchor, n_out, count, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // one scratch allocation: pred | rows | image | anchor | count | flags (every part 256-byte aligned)
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    // one scratch block: pred | rows | image | anchor | count | flags
+    HostStage st(c);
     const size_t es = d->p.dtype == VP_DET_F16 ? 2 : 4;
-    const size_t pred_bytes = (size_t)n_images * (4 + d->p.nc) * (size_t)A * es;
-    const size_t b_pred = up(pred_bytes), b_rows = up((size_t)n_out * 24), b_n = up((size_t)n_out * 4), b_s = up((size_t)(n_images + 1) * 4);
-    char* m = nullptr;
-    HIPCHK(c, hipMalloc((void**)&m, b_pred + b_rows + 2 * b_n + 2 * b_s + 256));
-    float* d_rows = (float*)(m + b_pred);
-    int32_t* d_im = (int32_t*)(m + b_pred + b_rows);
-    int32_t* d_an = (int32_t*)(m + b_pred + b_rows + b_n);
-    int32_t* d_ct = (int32_t*)(m + b_pred + b_rows + 2 * b_n);
-    int32_t* d_fl = (int32_t*)(m + b_pred + b_rows + 2 * b_n + b_s);
-    hipStream_t s = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    if (pred_bytes) chk(hipMemcpyAsync(m, pred, pred_bytes, hipMemcpyHostToDevice, s), "upload pred");
-    if (!rc) rc = detect_enqueue(d, m, A, images, n_images, d_rows, d_im, d_an, n_out, d_ct, d_fl, s);
-    if (!rc) {
+    const size_t pred_bytes = (size_t)n_images * (4 + d->p.nc) * (size_t)A * es, ob = (size_t)n_out * 4, sb = (size_t)(n_images + 1) * 4;
+    const size_t o_pred = st.part(pred_bytes), o_rows = st.part((size_t)n_out * 24), o_im = st.part(ob), o_an = st.part(ob), o_ct = st.part(sb), o_fl = st.part(sb);
+    if (st.alloc()) return st.rc;
+    char* d_pred = st.at(o_pred);
+    float* d_rows = st.at<float>(o_rows);
+    int32_t *d_im = st.at<int32_t>(o_im), *d_an = st.at<int32_t>(o_an), *d_ct = st.at<int32_t>(o_ct), *d_fl = st.at<int32_t>(o_fl);
+    if (pred_bytes) st.up(d_pred, pred, pred_bytes, "upload pred");
+    if (!st.rc) st.rc = detect_enqueue(d, d_pred, A, images, n_images, d_rows, d_im, d_an, n_out, d_ct, d_fl, st.s);
+    if (!st.rc) {
         if (n_out) {
-            chk(hipMemcpyAsync(rows, d_rows, (size_t)n_out * 24, hipMemcpyDeviceToHost, s), "download rows");
-            chk(hipMemcpyAsync(image, d_im, (size_t)n_out * 4, hipMemcpyDeviceToHost, s), "download image");
-            chk(hipMemcpyAsync(anchor, d_an, (size_t)n_out * 4, hipMemcpyDeviceToHost, s), "download anchor");
+            st.down(rows, d_rows, (size_t)n_out * 24, "download rows");
+            st.down(image, d_im, ob, "download image");
+            st.down(anchor, d_an, ob, "download anchor");
         }
-        chk(hipMemcpyAsync(count, d_ct, (size_t)(n_images + 1) * 4, hipMemcpyDeviceToHost, s), "download count");
-        if (flags && n_images) chk(hipMemcpyAsync(flags, d_fl, (size_t)n_images * 4, hipMemcpyDeviceToHost, s), "download flags");
+        st.down(count, d_ct, sb, "download count");
+        if (flags && n_images) st.down(flags, d_fl, (size_t)n_images * 4, "download flags");
     }
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-    (void)hipFree(m);
-    return rc;
+    st.sync();
+    return st.rc;
 }
 
 int vp_dbg_detect_host(const vp_det_cfg* cfg, const void* pred, int32_t A, const vp_det_image* images, int32_t n_images, float* rows, int32_t* image, int32_t* anchor,

@@ -2,6 +2,7 @@
 // vp_dbg_draw_host.  A gather: every pixel looks up the last primitive in draw order that covers it.  No atomics and no scatter, so the picture is a pure function
 // of the inputs whatever the launch shape.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "drawgeom.h"
 
 using namespace vpi;
@@ -180,23 +181,10 @@ int draw_args(bool need_ptrs, const vp_image* images, int n_images, int n, int k
     return VP_OK;
 }
 
-size_t plane_bytes(const vp_image& im, int p) {   // of plane p, first byte to last: pitch padding between the rows, none behind the last
-    return (size_t)(vp::plane_rows(im.format, p, im.h) - 1) * (size_t)im.pitch[p] + (size_t)vp::plane_row_bytes(im.format, p, im.w);
-}
-int plane_count(const vp_image& im) { return im.format == vp::PIX_NV12 ? 2 : 1; }
-
 // frame f read and written in place: every plane device memory of the handle's device, inside one allocation (the check of the boxes entries)
 int check_device_image(vp_ctx* c, const vp_image& im, int f) {
     bool ok = true;
-    for (int p = 0; p < plane_count(im) && ok; ++p) {
-        hipPointerAttribute_t a;
-        std::memset(&a, 0, sizeof(a));
-        void* base = nullptr;
-        size_t size = 0;
-        const uint8_t* q = im.plane[p];
-        ok = q && hipPointerGetAttributes(&a, q) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->cfg.device_id;
-        ok = ok && hipMemGetAddressRange(&base, &size, (void*)q) == hipSuccess && q + plane_bytes(im, p) <= (const uint8_t*)base + size;
-    }
+    for (int p = 0; p < plane_count(im) && ok; ++p) ok = device_range_ok(c, im.plane[p], plane_bytes(im, p));
     if (ok) return VP_OK;
     (void)hipGetLastError();
     return fail(c, VP_ERR_INVALID, "draw: frame " + std::to_string(f) + " is not device memory of device " + std::to_string(c->cfg.device_id) +
@@ -279,37 +267,33 @@ int vp_draw_poses(vp_handle c, const vp_image* images, int32_t n_images, const f
     std::string why;
     if (draw_args(images && kpts && frame_idx, images, n_images, n, k, frame_stride, boxes != nullptr, box_stride, cfg, dc, &why)) return fail(c, VP_ERR_INVALID, why);
     if (n == 0) return VP_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // one scratch allocation: the planes of every frame | keypoints | frame index | rank | ids | boxes (every part 256-byte aligned)
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b_kp = up((size_t)n * k * 12), b_fi = up(((size_t)(n - 1) * frame_stride + 1) * 4), b_n = up((size_t)n * 4),
-                 b_bx = boxes ? up(((size_t)(n - 1) * box_stride + 4) * 4) : 0;
-    size_t total = b_kp + b_fi + 2 * b_n + b_bx;
+    // one scratch block: the planes of every frame | keypoints | frame index | rank | ids | boxes
+    HostStage st(c);
+    const size_t kp_bytes = (size_t)n * k * 12, fi_bytes = ((size_t)(n - 1) * frame_stride + 1) * 4, nb = (size_t)n * 4, bx_bytes = ((size_t)(n - 1) * box_stride + 4) * 4;
+    std::vector<size_t> o_pl;
     for (int f = 0; f < n_images; ++f)
-        for (int p = 0; p < plane_count(images[f]); ++p) total += up(plane_bytes(images[f], p));
-    char* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, total));
-    hipStream_t s = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    char* q = d;
-    auto put = [&](const void* src, size_t bytes, size_t room, const char* what) { char* at = q; if (src) chk(hipMemcpyAsync(at, src, bytes, hipMemcpyHostToDevice, s), what); q += room; return at; };
+        for (int p = 0; p < plane_count(images[f]); ++p) o_pl.push_back(st.part(plane_bytes(images[f], p)));
+    const size_t o_kp = st.part(kp_bytes), o_fi = st.part(fi_bytes), o_rk = st.part(nb), o_id = st.part(nb), o_bx = boxes ? st.part(bx_bytes) : 0;
+    if (st.alloc()) return st.rc;
     std::vector<vp_image> dev(images, images + n_images);
-    for (int f = 0; f < n_images; ++f)
+    for (int f = 0, i = 0; f < n_images; ++f)
+        for (int p = 0; p < plane_count(images[f]); ++p, ++i) {
+            dev[f].plane[p] = st.at<uint8_t>(o_pl[i]);
+            if (images[f].plane[p]) st.up(st.at(o_pl[i]), images[f].plane[p], plane_bytes(images[f], p), "upload frame");
+        }
+    const float *d_kp = st.at<float>(o_kp), *d_bx = boxes ? st.at<float>(o_bx) : nullptr;
+    const int32_t *d_fi = st.at<int32_t>(o_fi), *d_rk = st.at<int32_t>(o_rk), *d_id = st.at<int32_t>(o_id);
+    st.up(st.at(o_kp), kpts, kp_bytes, "upload keypoints");
+    st.up(st.at(o_fi), frame_idx, fi_bytes, "upload frame index");
+    if (rank) st.up(st.at(o_rk), rank, nb, "upload rank");
+    if (ids) st.up(st.at(o_id), ids, nb, "upload ids");
+    if (boxes) st.up(st.at(o_bx), boxes, bx_bytes, "upload boxes");
+    if (!st.rc) st.rc = draw_enqueue(c, dev.data(), n_images, d_kp, n, k, d_fi, frame_stride, rank ? d_rk : nullptr, ids ? d_id : nullptr, d_bx, box_stride, dc, st.s);
+    for (int f = 0; f < n_images && !st.rc; ++f)   // the frames are written back in place
         for (int p = 0; p < plane_count(images[f]); ++p)
-            dev[f].plane[p] = (const uint8_t*)put(images[f].plane[p], plane_bytes(images[f], p), up(plane_bytes(images[f], p)), "upload frame");
-    const float* d_kp = (const float*)put(kpts, (size_t)n * k * 12, b_kp, "upload keypoints");
-    const int32_t* d_fi = (const int32_t*)put(frame_idx, ((size_t)(n - 1) * frame_stride + 1) * 4, b_fi, "upload frame index");
-    const int32_t* d_rk = (const int32_t*)put(rank, (size_t)n * 4, b_n, "upload rank");
-    const int32_t* d_id = (const int32_t*)put(ids, (size_t)n * 4, b_n, "upload ids");
-    const float* d_bx = boxes ? (const float*)put(boxes, ((size_t)(n - 1) * box_stride + 4) * 4, b_bx, "upload boxes") : nullptr;
-    if (!rc) rc = draw_enqueue(c, dev.data(), n_images, d_kp, n, k, d_fi, frame_stride, rank ? d_rk : nullptr, ids ? d_id : nullptr, d_bx, box_stride, dc, s);
-    for (int f = 0; f < n_images && !rc; ++f)
-        for (int p = 0; p < plane_count(images[f]); ++p)
-            chk(hipMemcpyAsync(const_cast<uint8_t*>(images[f].plane[p]), dev[f].plane[p], plane_bytes(images[f], p), hipMemcpyDeviceToHost, s), "download frame");
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-    hipFree(d);
-    return rc;
+            st.down(const_cast<uint8_t*>(images[f].plane[p]), dev[f].plane[p], plane_bytes(images[f], p), "download frame");
+    st.sync();
+    return st.rc;
 }
 
 int vp_dbg_draw_host(const vp_image* images, int32_t n_images, const float* kpts, int32_t n, int32_t k, const int32_t* frame_idx, int32_t frame_stride, const int32_t* rank,

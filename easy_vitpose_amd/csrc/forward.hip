@@ -1,6 +1,7 @@
 // The forward of one chunk behind the C ABI (include/vitpose_hip.h): the GEMM launchers, the encoder + head + decode of up to max_batch crops as the
 // chunk's plan (tile_rules.hip plan_chunk) picked them, and the hipGraph cache that replays small chunks (run_chunk).
 #include "api_internal.h"
+#include "hoststage.h"
 #include "simpleheadgeom.h"
 #include "tiles.h"
 
@@ -134,7 +135,7 @@ int forward_chunk(vp_ctx* c, const void* d_crops, int fmt, int n_in, const FwdOp
         // fp8 mode.  The residual stream, the attention core, attn.proj, the head and the decode are the fp16 path's; qkv / fc1 / fc2 run
         // on MXFP8 operands.  Token rows are padded to Mp (multiple of the 256-row tile, >= 512): padding rows carry zeros into the
         // GEMMs and are never read by a kernel that works per crop.
-        const int Mp = (int)std::max<size_t>((size_t)(M + 255) / 256 * 256, 512);
+        const int Mp = (int)std::max<size_t>(up256((size_t)M), 512);
         plane = c->Mp * (size_t)D;                   // the planes are laid out for the handle's full padded row count
         uint16_t* xh = (uint16_t*)c->x;
         int tiles = 0;

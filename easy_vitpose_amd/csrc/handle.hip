@@ -2,6 +2,7 @@
 // the handle's modes (active expert, flip-test), profiling and synchronisation.  No CPU fallback anywhere: every compute entry point needs a
 // HIP device and fails with VP_ERR_HIP otherwise.
 #include "api_internal.h"
+#include "hoststage.h"
 
 using namespace vpi;
 
@@ -194,7 +195,7 @@ int vp_create(vp_handle* out, const vp_config* cfg) {
     c->own_stream = c->stream;
     const size_t B = (size_t)((c->maxb + 3) / 4 * 4);   // workspaces: the encoder may run the next multiple of 4 crops (forward_chunk)
     // fp8 mode: workspaces indexed by token row are sized for the padded row count the MXFP8 GEMM tiles need
-    c->Mp = std::max<size_t>((B * 192 + 255) / 256 * 256, 512);
+    c->Mp = std::max<size_t>(up256(B * 192), 512);
     const size_t M = c->fp8 ? c->Mp : B * 192;
     int rc = 0;
     void* stage = nullptr;

@@ -3,6 +3,7 @@
 // their host-side plan, mix_plan, and its doubled form under the per-expert flip-test mode, mix_records_flip), vp_infer_flip.  Each walks its crops in chunks (for_chunks) and hands a chunk to forward.hip.
 #include "affinegeom.h"
 #include "api_internal.h"
+#include "hoststage.h"
 #include "boxgeom.h"
 #include "pixfmt.h"
 
@@ -47,16 +48,7 @@ int device_chunks(vp_ctx* c, const void* d_crops, int fmt, int n, const int32_t*
 // image_plan, with the crop that names it).  The format and the pitches have passed image_check
 int check_device_frame(vp_ctx* c, const vp_image& im, int f) {
     bool ok = true;
-    for (int p = 0; p < (im.format == vp::PIX_NV12 ? 2 : 1) && ok; ++p) {
-        hipPointerAttribute_t a;
-        std::memset(&a, 0, sizeof(a));
-        void* base = nullptr;
-        size_t size = 0;
-        const uint8_t* q = im.plane[p];
-        const size_t bytes = (size_t)(vp::plane_rows(im.format, p, im.h) - 1) * (size_t)im.pitch[p] + (size_t)vp::plane_row_bytes(im.format, p, im.w);
-        ok = q && hipPointerGetAttributes(&a, q) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->cfg.device_id;
-        ok = ok && hipMemGetAddressRange(&base, &size, (void*)q) == hipSuccess && q + bytes <= (const uint8_t*)base + size;
-    }
+    for (int p = 0; p < plane_count(im) && ok; ++p) ok = device_range_ok(c, im.plane[p], plane_bytes(im, p));
     if (ok) return VP_OK;
     (void)hipGetLastError();
     return fail(c, VP_ERR_INVALID, "frame " + std::to_string(f) + " is not device memory of device " + std::to_string(c->cfg.device_id) +
@@ -251,7 +243,7 @@ int stage_bands(vp_ctx* c, const vp_image* frames, int n_frames, bool on_device,
         *r0 = p ? bands[2 * f] >> 1 : bands[2 * f];
         *r1 = p ? ((int64_t)bands[2 * f + 1] + 1) >> 1 : bands[2 * f + 1];
     };
-    auto planes = [&](int f) { return frames[f].format == vp::PIX_NV12 ? 2 : 1; };
+    auto planes = [&](int f) { return plane_count(frames[f]); };
     if (on_device) {
         for (int f = 0; f < n_frames; ++f) {
             if (bands[2 * f] == bands[2 * f + 1]) continue;

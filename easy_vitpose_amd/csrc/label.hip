@@ -2,6 +2,7 @@
 // vp_draw_labels and the host-only taps vp_dbg_draw_labels_host, vp_dbg_label_text and vp_dbg_label_glyph.  A gather: a pixel is written by the one workgroup whose
 // row is the last that covers it.  No atomics and no scatter, so the picture is a pure function of the inputs whatever the launch shape.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "labelgeom.h"
 
 using namespace vpi;
@@ -150,23 +151,10 @@ int label_args(bool need_ptrs, const vp_image* images, int n_images, int n, int 
     return VP_OK;
 }
 
-size_t plane_bytes(const vp_image& im, int p) {   // of plane p, first byte to last: pitch padding between the rows, none behind the last
-    return (size_t)(vp::plane_rows(im.format, p, im.h) - 1) * (size_t)im.pitch[p] + (size_t)vp::plane_row_bytes(im.format, p, im.w);
-}
-int plane_count(const vp_image& im) { return im.format == vp::PIX_NV12 ? 2 : 1; }
-
 // frame f read and written in place: every plane device memory of the handle's device, inside one allocation (the check of vp_draw_poses_stream)
 int check_device_image(vp_ctx* c, const vp_image& im, int f) {
     bool ok = true;
-    for (int p = 0; p < plane_count(im) && ok; ++p) {
-        hipPointerAttribute_t a;
-        std::memset(&a, 0, sizeof(a));
-        void* base = nullptr;
-        size_t size = 0;
-        const uint8_t* q = im.plane[p];
-        ok = q && hipPointerGetAttributes(&a, q) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->cfg.device_id;
-        ok = ok && hipMemGetAddressRange(&base, &size, (void*)q) == hipSuccess && q + plane_bytes(im, p) <= (const uint8_t*)base + size;
-    }
+    for (int p = 0; p < plane_count(im) && ok; ++p) ok = device_range_ok(c, im.plane[p], plane_bytes(im, p));
     if (ok) return VP_OK;
     (void)hipGetLastError();
     return fail(c, VP_ERR_INVALID, "labels: frame " + std::to_string(f) + " is not device memory of device " + std::to_string(c->cfg.device_id) +
@@ -256,37 +244,33 @@ int vp_draw_labels(vp_handle c, const vp_image* images, int32_t n_images, const 
     if (label_args(images && boxes && frame_idx, images, n_images, n, box_stride, frame_stride, scores != nullptr, score_stride, cfg, st, &why))
         return fail(c, VP_ERR_INVALID, why);
     if (n == 0) return VP_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // one scratch allocation: the planes of every frame | boxes | frame index | rank | ids | scores (every part 256-byte aligned)
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b_bx = up(((size_t)(n - 1) * box_stride + 4) * 4), b_fi = up(((size_t)(n - 1) * frame_stride + 1) * 4), b_n = up((size_t)n * 4),
-                 b_sc = scores ? up(((size_t)(n - 1) * score_stride + 1) * 4) : 0;
-    size_t total = b_bx + b_fi + 2 * b_n + b_sc;
+    // one scratch block: the planes of every frame | boxes | frame index | rank | ids | scores
+    HostStage hs(c);
+    const size_t bx_bytes = ((size_t)(n - 1) * box_stride + 4) * 4, fi_bytes = ((size_t)(n - 1) * frame_stride + 1) * 4, nb = (size_t)n * 4, sc_bytes = ((size_t)(n - 1) * score_stride + 1) * 4;
+    std::vector<size_t> o_pl;
     for (int f = 0; f < n_images; ++f)
-        for (int p = 0; p < plane_count(images[f]); ++p) total += up(plane_bytes(images[f], p));
-    char* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, total));
-    hipStream_t s = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    char* q = d;
-    auto put = [&](const void* src, size_t bytes, size_t room, const char* what) { char* at = q; if (src) chk(hipMemcpyAsync(at, src, bytes, hipMemcpyHostToDevice, s), what); q += room; return at; };
+        for (int p = 0; p < plane_count(images[f]); ++p) o_pl.push_back(hs.part(plane_bytes(images[f], p)));
+    const size_t o_bx = hs.part(bx_bytes), o_fi = hs.part(fi_bytes), o_rk = hs.part(nb), o_id = hs.part(nb), o_sc = scores ? hs.part(sc_bytes) : 0;
+    if (hs.alloc()) return hs.rc;
     std::vector<vp_image> dev(images, images + n_images);
-    for (int f = 0; f < n_images; ++f)
+    for (int f = 0, i = 0; f < n_images; ++f)
+        for (int p = 0; p < plane_count(images[f]); ++p, ++i) {
+            dev[f].plane[p] = hs.at<uint8_t>(o_pl[i]);
+            if (images[f].plane[p]) hs.up(hs.at(o_pl[i]), images[f].plane[p], plane_bytes(images[f], p), "upload frame");
+        }
+    const float *d_bx = hs.at<float>(o_bx), *d_sc = scores ? hs.at<float>(o_sc) : nullptr;
+    const int32_t *d_fi = hs.at<int32_t>(o_fi), *d_rk = hs.at<int32_t>(o_rk), *d_id = hs.at<int32_t>(o_id);
+    hs.up(hs.at(o_bx), boxes, bx_bytes, "upload boxes");
+    hs.up(hs.at(o_fi), frame_idx, fi_bytes, "upload frame index");
+    if (rank) hs.up(hs.at(o_rk), rank, nb, "upload rank");
+    if (ids) hs.up(hs.at(o_id), ids, nb, "upload ids");
+    if (scores) hs.up(hs.at(o_sc), scores, sc_bytes, "upload scores");
+    if (!hs.rc) hs.rc = label_enqueue(c, dev.data(), n_images, d_bx, box_stride, n, d_fi, frame_stride, rank ? d_rk : nullptr, ids ? d_id : nullptr, d_sc, score_stride, st, hs.s);
+    for (int f = 0; f < n_images && !hs.rc; ++f)   // the frames are written back in place
         for (int p = 0; p < plane_count(images[f]); ++p)
-            dev[f].plane[p] = (const uint8_t*)put(images[f].plane[p], plane_bytes(images[f], p), up(plane_bytes(images[f], p)), "upload frame");
-    const float* d_bx = (const float*)put(boxes, ((size_t)(n - 1) * box_stride + 4) * 4, b_bx, "upload boxes");
-    const int32_t* d_fi = (const int32_t*)put(frame_idx, ((size_t)(n - 1) * frame_stride + 1) * 4, b_fi, "upload frame index");
-    const int32_t* d_rk = (const int32_t*)put(rank, (size_t)n * 4, b_n, "upload rank");
-    const int32_t* d_id = (const int32_t*)put(ids, (size_t)n * 4, b_n, "upload ids");
-    const float* d_sc = scores ? (const float*)put(scores, ((size_t)(n - 1) * score_stride + 1) * 4, b_sc, "upload scores") : nullptr;
-    if (!rc) rc = label_enqueue(c, dev.data(), n_images, d_bx, box_stride, n, d_fi, frame_stride, rank ? d_rk : nullptr, ids ? d_id : nullptr, d_sc, score_stride, st, s);
-    for (int f = 0; f < n_images && !rc; ++f)
-        for (int p = 0; p < plane_count(images[f]); ++p)
-            chk(hipMemcpyAsync(const_cast<uint8_t*>(images[f].plane[p]), dev[f].plane[p], plane_bytes(images[f], p), hipMemcpyDeviceToHost, s), "download frame");
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-    (void)hipFree(d);
-    return rc;
+            hs.down(const_cast<uint8_t*>(images[f].plane[p]), dev[f].plane[p], plane_bytes(images[f], p), "download frame");
+    hs.sync();
+    return hs.rc;
 }
 
 int vp_dbg_draw_labels_host(const vp_image* images, int32_t n_images, const float* boxes, int32_t box_stride, int32_t n, const int32_t* frame_idx, int32_t frame_stride,

@@ -2,6 +2,7 @@
 // synchronous host twin vp_letterbox, the host-only plan vp_letterbox_plan and the host tap vp_dbg_letterbox_host.  One kernel, a workgroup per output row: adjacent lanes fetch
 // adjacent pixels into LDS, then a lane stores a run of adjacent x -- 16 bytes per channel plane -- so the stores are dwordx4 whatever the dtype; the image records travel by kernel argument, LB_PER_LAUNCH per launch.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "detgeom.h"
 #include "lbgeom.h"
 
@@ -188,22 +189,10 @@ int out_check(const LbParams& p, const vp_image* images, int n_images, const voi
     return VP_OK;
 }
 
-size_t plane_bytes(const vp_image& im, int pl) {   // of plane pl, first byte to last: pitch padding between the rows, none behind the last
-    return (size_t)(vp::plane_rows(im.format, pl, im.h) - 1) * (size_t)im.pitch[pl] + (size_t)vp::plane_row_bytes(im.format, pl, im.w);
-}
-
 // frame f is read in place: every plane device memory of the handle's device, inside one allocation (the check of the image entries)
 int check_device_image(vp_ctx* c, const vp_image& im, int f) {
     bool ok = true;
-    for (int pl = 0; pl < (im.format == vp::PIX_NV12 ? 2 : 1) && ok; ++pl) {
-        hipPointerAttribute_t a;
-        std::memset(&a, 0, sizeof(a));
-        void* base = nullptr;
-        size_t size = 0;
-        const uint8_t* q = im.plane[pl];
-        ok = q && hipPointerGetAttributes(&a, q) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->cfg.device_id;
-        ok = ok && hipMemGetAddressRange(&base, &size, (void*)q) == hipSuccess && q + plane_bytes(im, pl) <= (const uint8_t*)base + size;
-    }
+    for (int pl = 0; pl < plane_count(im) && ok; ++pl) ok = device_range_ok(c, im.plane[pl], plane_bytes(im, pl));
     if (ok) return VP_OK;
     (void)hipGetLastError();
     return fail(c, VP_ERR_INVALID, "letterbox: frame " + std::to_string(f) + " is not device memory of device " + std::to_string(c->cfg.device_id) +
@@ -295,32 +284,23 @@ int vp_letterbox(vp_handle c, const vp_letterbox_cfg* cfg, const vp_image* image
     if (plan(cfg, images, n_images, p, recs, t, &why) || out_check(p, images, n_images, out, &why)) return fail(c, VP_ERR_INVALID, why);
     t.publish(det, placement);
     if (n_images == 0) return VP_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // one scratch allocation: the tensor, then every plane at the caller's pitch (every part 256-byte aligned)
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    // one scratch block: the tensor, then every plane at the caller's pitch
+    HostStage st(c);
     const size_t out_bytes = (size_t)n_images * 3 * (size_t)p.in_h * (size_t)p.in_w * (size_t)vp::lb_elem_bytes(p.dtype);
-    size_t total = up(out_bytes);
+    const size_t o_out = st.part(out_bytes);
     std::vector<size_t> off((size_t)n_images * 2, 0);
     for (int f = 0; f < n_images; ++f)
-        for (int pl = 0; pl < (images[f].format == vp::PIX_NV12 ? 2 : 1); ++pl) {
-            off[2 * f + pl] = total;
-            total += up(plane_bytes(images[f], pl));
+        for (int pl = 0; pl < plane_count(images[f]); ++pl) off[2 * f + pl] = st.part(plane_bytes(images[f], pl));
+    if (st.alloc()) return st.rc;
+    for (int f = 0; f < n_images && !st.rc; ++f)
+        for (int pl = 0; pl < plane_count(images[f]); ++pl) {
+            st.up(st.at(off[2 * f + pl]), images[f].plane[pl], plane_bytes(images[f], pl), "upload plane");
+            recs[f].plane[pl] = st.at<const uint8_t>(off[2 * f + pl]);
         }
-    char* m = nullptr;
-    HIPCHK(c, hipMalloc((void**)&m, total));
-    hipStream_t s = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    for (int f = 0; f < n_images && !rc; ++f)
-        for (int pl = 0; pl < (images[f].format == vp::PIX_NV12 ? 2 : 1); ++pl) {
-            chk(hipMemcpyAsync(m + off[2 * f + pl], images[f].plane[pl], plane_bytes(images[f], pl), hipMemcpyHostToDevice, s), "upload plane");
-            recs[f].plane[pl] = (const uint8_t*)(m + off[2 * f + pl]);
-        }
-    if (!rc) rc = enqueue(c, p, recs, m, s);
-    if (!rc) chk(hipMemcpyAsync(out, m, out_bytes, hipMemcpyDeviceToHost, s), "download tensor");
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-    (void)hipFree(m);
-    return rc;
+    if (!st.rc) st.rc = enqueue(c, p, recs, st.at(o_out), st.s);
+    if (!st.rc) st.down(out, st.at(o_out), out_bytes, "download tensor");
+    st.sync();
+    return st.rc;
 }
 
 int vp_dbg_letterbox_host(const vp_letterbox_cfg* cfg, const vp_image* images, int32_t n_images, void* out, vp_det_image* det, int32_t* placement) {

@@ -4,6 +4,7 @@
 // evaluator, and metrics_finish_kernel, one workgroup that adds the block partials in ascending block order into the state.  No atomics, no flags between
 // workgroups: the state is a pure function of the inputs, bit for bit.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "metricsgeom.h"
 
 using namespace vpi;
@@ -174,8 +175,6 @@ struct vp_metrics {
 
 namespace {
 
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-
 // ---- the host model: metricsgeom.h run serially, block by block in the contract's summation order (HOST ONLY)
 void metrics_host(char* state, const vp::MetricsParams& m, const double* vars, const float* pred, const float* gt, const float* norm, const float* area, const int32_t* rank,
                   const int32_t* set, int32_t set_value, int n, float* dist, float* oks_out) {
@@ -323,25 +322,26 @@ int vp_metrics_create(vp_handle c, const vp_metrics_cfg* cfg, const float* sigma
     e->c = c;
     e->p = p;
     e->state_bytes = vp::metrics_state_words(K, p.n_pck, p.auc_steps) * 8;
-    const size_t b_state = up256(e->state_bytes), b_vars = up256((size_t)K * 8), b_sums = up256((size_t)B * 2 * K * 8), b_cnt = up256((size_t)B * C * K * 4),
-                 b_hdr = up256((size_t)B * sizeof(vp::MetricsBlockHdr));
-    const size_t bytes = b_state + b_vars + b_sums + b_cnt + b_hdr;
+    StageLayout lay;   // state | vars | sums | counts | block headers
+    const size_t o_state = lay.part(e->state_bytes), o_vars = lay.part((size_t)K * 8), o_sums = lay.part((size_t)B * 2 * K * 8), o_cnt = lay.part((size_t)B * C * K * 4),
+                 o_hdr = lay.part((size_t)B * sizeof(vp::MetricsBlockHdr));
+    const size_t bytes = lay.end;
     std::vector<double> vars((size_t)K, 1.0);
     if (p.use_oks)
         for (int j = 0; j < K; ++j) vars[j] = vp::nms_var(sigmas[j]);
     hipError_t err = hipMalloc((void**)&e->mem, bytes);
     if (err == hipSuccess) err = hipMemset(e->mem, 0, bytes);
-    if (err == hipSuccess) err = hipMemcpy(e->mem + b_state, vars.data(), (size_t)K * 8, hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(e->mem + o_vars, vars.data(), (size_t)K * 8, hipMemcpyHostToDevice);
     if (err != hipSuccess) {
         if (e->mem) (void)hipFree(e->mem);
         delete e;
         return fail(c, VP_ERR_HIP, std::string("metrics state: ") + hipGetErrorString(err));
     }
-    e->state = e->mem;
-    e->vars = (double*)(e->mem + b_state);
-    e->ws.sums = (double*)(e->mem + b_state + b_vars);
-    e->ws.cnt = (int32_t*)(e->mem + b_state + b_vars + b_sums);
-    e->ws.hdr = (vp::MetricsBlockHdr*)(e->mem + b_state + b_vars + b_sums + b_cnt);
+    e->state = e->mem + o_state;
+    e->vars = (double*)(e->mem + o_vars);
+    e->ws.sums = (double*)(e->mem + o_sums);
+    e->ws.cnt = (int32_t*)(e->mem + o_cnt);
+    e->ws.hdr = (vp::MetricsBlockHdr*)(e->mem + o_hdr);
     *out = e;
     return VP_OK;
 }
@@ -377,42 +377,33 @@ int vp_metrics_update(vp_metrics_handle e, const float* pred, const float* gt, c
     vp_ctx* c = e->c;
     std::string why;
     if (update_args(pred, gt, n, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // one scratch allocation: pred | gt | norm | area | rank | set | dist | oks (every part 256-byte aligned)
+    // one scratch block: pred | gt | norm | area | rank | set | oks | dist
+    HostStage st(c);
     const int K = e->p.n_joints;
-    const size_t kp_bytes = (size_t)n * K * 3 * sizeof(float), b_kp = up256(kp_bytes), b_n = up256((size_t)n * 4), b_n2 = up256((size_t)n * 8), dist_bytes = (size_t)n * K * 4,
-                 b_dist = up256(dist_bytes);
-    char* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, 2 * b_kp + b_n2 + 4 * b_n + b_dist + 256));
-    float* d_pred = (float*)d;
-    float* d_gt = (float*)(d + b_kp);
-    float* d_norm = (float*)(d + 2 * b_kp);
-    float* d_area = (float*)(d + 2 * b_kp + b_n2);
-    int32_t* d_rank = (int32_t*)(d + 2 * b_kp + b_n2 + b_n);
-    int32_t* d_set = (int32_t*)(d + 2 * b_kp + b_n2 + 2 * b_n);
-    float* d_oks = (float*)(d + 2 * b_kp + b_n2 + 3 * b_n);
-    float* d_dist = (float*)(d + 2 * b_kp + b_n2 + 4 * b_n);
-    hipStream_t q = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t err, const char* what) { if (err != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(err)); };
+    const size_t kp_bytes = (size_t)n * K * 3 * sizeof(float), nb = (size_t)n * 4, dist_bytes = (size_t)n * K * 4;
+    const size_t o_pred = st.part(kp_bytes), o_gt = st.part(kp_bytes), o_norm = st.part((size_t)n * 8), o_area = st.part(nb), o_rank = st.part(nb), o_set = st.part(nb), o_oks = st.part(nb),
+                 o_dist = st.part(dist_bytes);
+    if (st.alloc()) return st.rc;
+    float *d_pred = st.at<float>(o_pred), *d_gt = st.at<float>(o_gt), *d_norm = st.at<float>(o_norm), *d_area = st.at<float>(o_area), *d_oks = st.at<float>(o_oks),
+          *d_dist = st.at<float>(o_dist);
+    int32_t *d_rank = st.at<int32_t>(o_rank), *d_set = st.at<int32_t>(o_set);
     if (n) {
-        chk(hipMemcpyAsync(d_pred, pred, kp_bytes, hipMemcpyHostToDevice, q), "upload pred");
-        chk(hipMemcpyAsync(d_gt, gt, kp_bytes, hipMemcpyHostToDevice, q), "upload gt");
-        if (norm) chk(hipMemcpyAsync(d_norm, norm, (size_t)n * 8, hipMemcpyHostToDevice, q), "upload norm");
-        if (area) chk(hipMemcpyAsync(d_area, area, (size_t)n * 4, hipMemcpyHostToDevice, q), "upload area");
-        if (rank) chk(hipMemcpyAsync(d_rank, rank, (size_t)n * 4, hipMemcpyHostToDevice, q), "upload rank");
-        if (set) chk(hipMemcpyAsync(d_set, set, (size_t)n * 4, hipMemcpyHostToDevice, q), "upload set");
+        st.up(d_pred, pred, kp_bytes, "upload pred");
+        st.up(d_gt, gt, kp_bytes, "upload gt");
+        if (norm) st.up(d_norm, norm, (size_t)n * 8, "upload norm");
+        if (area) st.up(d_area, area, nb, "upload area");
+        if (rank) st.up(d_rank, rank, nb, "upload rank");
+        if (set) st.up(d_set, set, nb, "upload set");
     }
-    if (!rc)
-        rc = update_enqueue(e, d_pred, d_gt, n && norm ? d_norm : nullptr, n && area ? d_area : nullptr, n && rank ? d_rank : nullptr, n && set ? d_set : nullptr, set_value, n,
-                            n && dist ? d_dist : nullptr, n && oks ? d_oks : nullptr, q);
-    if (!rc && n) {
-        if (dist) chk(hipMemcpyAsync(dist, d_dist, dist_bytes, hipMemcpyDeviceToHost, q), "download dist");
-        if (oks) chk(hipMemcpyAsync(oks, d_oks, (size_t)n * 4, hipMemcpyDeviceToHost, q), "download oks");
+    if (!st.rc)
+        st.rc = update_enqueue(e, d_pred, d_gt, n && norm ? d_norm : nullptr, n && area ? d_area : nullptr, n && rank ? d_rank : nullptr, n && set ? d_set : nullptr, set_value, n,
+                               n && dist ? d_dist : nullptr, n && oks ? d_oks : nullptr, st.s);
+    if (!st.rc && n) {
+        if (dist) st.down(dist, d_dist, dist_bytes, "download dist");
+        if (oks) st.down(oks, d_oks, nb, "download oks");
     }
-    chk(hipStreamSynchronize(q), "hipStreamSynchronize");
-    (void)hipFree(d);
-    return rc;
+    st.sync();
+    return st.rc;
 }
 
 int vp_metrics_snapshot_stream(vp_metrics_handle e, void* d_out, void* caller_stream) {

@@ -6,6 +6,7 @@
 // registers.  Four-byte accesses where base and pitch allow (sixteen for a run that keeps its byte order), element accesses otherwise, the same values either way.  No byte outside the row bytes of a
 // destination row is written or read-modify-written: a row end takes byte stores.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "orientgeom.h"
 #include "pixfmt.h"
 
@@ -170,12 +171,6 @@ namespace {
 
 using vp::OrientRec;
 
-int plane_count(const vp_image& im) { return im.format == vp::PIX_NV12 ? 2 : 1; }
-
-size_t plane_bytes(const vp_image& im, int pl) {   // of plane pl, first byte to last: pitch padding between the rows, none behind the last
-    return (size_t)(vp::plane_rows(im.format, pl, im.h) - 1) * (size_t)im.pitch[pl] + (size_t)vp::plane_row_bytes(im.format, pl, im.w);
-}
-
 // the plan of a call (HOST ONLY): every refusal that reads no pixel and no pointer, and the destination layouts.  dst_in: the caller's table, whose non-zero
 // pitches are kept after the check (the plan entry) -- or, with strict, whose every field must be the plan's (the entries that move pixels)
 int plan(const vp_image* src, const int32_t* codes, int n, const vp_image* dst_in, bool strict, std::vector<vp_image>& out, std::string* why) {
@@ -262,13 +257,7 @@ int records(const vp_image* src, const int32_t* codes, const std::vector<vp_imag
 
 // plane pl of frame f, bytes [q, q + bytes): device memory of the handle's device, inside one allocation (the check of the image entries)
 int check_device_plane(vp_ctx* c, const uint8_t* q, size_t bytes, int f, const char* side) {
-    hipPointerAttribute_t a;
-    std::memset(&a, 0, sizeof(a));
-    void* base = nullptr;
-    size_t size = 0;
-    bool ok = q && hipPointerGetAttributes(&a, q) == hipSuccess && a.type == hipMemoryTypeDevice && a.device == c->cfg.device_id;
-    ok = ok && hipMemGetAddressRange(&base, &size, (void*)q) == hipSuccess && q + bytes <= (const uint8_t*)base + size;
-    if (ok) return VP_OK;
+    if (device_range_ok(c, q, bytes)) return VP_OK;
     (void)hipGetLastError();
     return fail(c, VP_ERR_INVALID, std::string("orient: ") + side + " frame " + std::to_string(f) + " is not device memory of device " + std::to_string(c->cfg.device_id) +
                                        " (or runs past the end of its allocation)");
@@ -343,37 +332,30 @@ int vp_orient(vp_handle c, const vp_image* src, const int32_t* codes, const vp_i
     std::string why;
     if (checked(src, codes, dst, n, full, recs, &why)) return fail(c, VP_ERR_INVALID, why);
     if (n == 0) return VP_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // one scratch allocation: every plane of either side at the caller's pitch, each part at its caller's address modulo 256 (the kernel then takes the access
+    // one scratch block: every plane of either side at the caller's pitch, each part at its caller's address modulo 256 (the kernel then takes the access
     // widths it would take on the caller's own layout)
-    size_t total = 0;
+    HostStage st(c);
     std::vector<size_t> off((size_t)n * 4, 0);
-    auto place = [&](const uint8_t* p, size_t bytes) { const size_t at = (total + 255) / 256 * 256 + (size_t)((uintptr_t)p % 256); total = at + bytes; return at; };
     for (int f = 0; f < n; ++f)
         for (int pl = 0; pl < plane_count(src[f]); ++pl) {
-            off[4 * f + pl] = place(src[f].plane[pl], plane_bytes(src[f], pl));
-            off[4 * f + 2 + pl] = place(full[f].plane[pl], plane_bytes(full[f], pl));
+            off[4 * f + pl] = st.part(plane_bytes(src[f], pl), (size_t)((uintptr_t)src[f].plane[pl] % 256));
+            off[4 * f + 2 + pl] = st.part(plane_bytes(full[f], pl), (size_t)((uintptr_t)full[f].plane[pl] % 256));
         }
-    uint8_t* m = nullptr;
-    HIPCHK(c, hipMalloc((void**)&m, total));
-    hipStream_t s = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    for (int f = 0; f < n && !rc; ++f)
+    if (st.alloc()) return st.rc;
+    for (int f = 0; f < n && !st.rc; ++f)
         for (int pl = 0; pl < plane_count(src[f]); ++pl) {
-            chk(hipMemcpyAsync(m + off[4 * f + pl], src[f].plane[pl], plane_bytes(src[f], pl), hipMemcpyHostToDevice, s), "upload plane");
-            recs[f].src[pl] = m + off[4 * f + pl];
-            recs[f].dst[pl] = m + off[4 * f + 2 + pl];
+            st.up(st.at(off[4 * f + pl]), src[f].plane[pl], plane_bytes(src[f], pl), "upload plane");
+            recs[f].src[pl] = st.at<uint8_t>(off[4 * f + pl]);
+            recs[f].dst[pl] = st.at<uint8_t>(off[4 * f + 2 + pl]);
         }
-    if (!rc) rc = enqueue(c, recs, s);
-    for (int f = 0; f < n && !rc; ++f)   // the row bytes of every destination row, never the gap between two rows
+    if (!st.rc) st.rc = enqueue(c, recs, st.s);
+    for (int f = 0; f < n && !st.rc; ++f)   // the row bytes of every destination row, never the gap between two rows
         for (int pl = 0; pl < plane_count(src[f]); ++pl)
-            chk(hipMemcpy2DAsync(const_cast<uint8_t*>(full[f].plane[pl]), (size_t)full[f].pitch[pl], m + off[4 * f + 2 + pl], (size_t)full[f].pitch[pl],
-                                 (size_t)vp::plane_row_bytes(full[f].format, pl, full[f].w), (size_t)vp::plane_rows(full[f].format, pl, full[f].h), hipMemcpyDeviceToHost, s),
-                "download plane");
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-    (void)hipFree(m);
-    return rc;
+            st.chk(hipMemcpy2DAsync(const_cast<uint8_t*>(full[f].plane[pl]), (size_t)full[f].pitch[pl], st.at(off[4 * f + 2 + pl]), (size_t)full[f].pitch[pl],
+                                    (size_t)vp::plane_row_bytes(full[f].format, pl, full[f].w), (size_t)vp::plane_rows(full[f].format, pl, full[f].h), hipMemcpyDeviceToHost, st.s),
+                   "download plane");
+    st.sync();
+    return st.rc;
 }
 
 int vp_dbg_orient_host(const vp_image* src, const int32_t* codes, const vp_image* dst, int32_t n) {

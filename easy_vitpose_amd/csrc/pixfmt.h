@@ -11,8 +11,14 @@
 // cvtColor(COLOR_YUV2RGB_NV12); BT709 (limited) and BT601_FULL are round(x 2^20) of the standard matrices.  Over all 2^24 (Y, U, V) the largest
 // intermediate magnitude is 5.7e8: int32 holds it.  Chroma is replicated: pixel (y, x) reads the UV pair (y >> 1, x >> 1).
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define PF_HD __host__ __device__ inline
+#else   // a plain host compiler (the layout part of hoststage.h in a stand-alone program): the same functions, host only
+#define PF_HD inline
+#endif
 
 namespace vp {
 
@@ -21,16 +27,16 @@ enum YuvMatrix { YUV_BT601 = 0, YUV_BT709 = 1, YUV_BT601_FULL = 2, YUV_MATRICES 
 
 struct YuvCoef { int32_t yoff, cy, crv, cgu, cgv, cbu; };
 
-__host__ __device__ inline YuvCoef yuv_coef(int matrix) {
+PF_HD YuvCoef yuv_coef(int matrix) {
     if (matrix == YUV_BT709) return YuvCoef{16, 1220945, 1879825, -223607, -558796, 2215014};
     if (matrix == YUV_BT601_FULL) return YuvCoef{0, 1048576, 1470104, -360853, -748826, 1858077};
     return YuvCoef{16, 1220542, 1673527, -409993, -852492, 2116026};
 }
 
-__host__ __device__ inline int clip255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+PF_HD int clip255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // one (Y, U, V) sample -> rgb[3]
-__host__ __device__ inline void yuv_to_rgb(const YuvCoef& k, int Y, int U, int V, int* rgb) {
+PF_HD void yuv_to_rgb(const YuvCoef& k, int Y, int U, int V, int* rgb) {
     const int32_t yy = Y - k.yoff, y = (yy < 0 ? 0 : yy) * k.cy + (1 << 19), u = U - 128, v = V - 128;
     rgb[0] = clip255((y + k.crv * v) >> 20);
     rgb[1] = clip255((y + k.cgu * u + k.cgv * v) >> 20);
@@ -38,11 +44,11 @@ __host__ __device__ inline void yuv_to_rgb(const YuvCoef& k, int Y, int U, int V
 }
 
 // bytes of one row of plane p (0 / 1) of a w-pixel-wide frame, and that plane's row count for h frame rows
-__host__ __device__ inline int64_t plane_row_bytes(int format, int plane, int64_t w) {
+PF_HD int64_t plane_row_bytes(int format, int plane, int64_t w) {
     if (format == PIX_NV12) return plane == 0 ? w : 2 * ((w + 1) / 2);
     return plane == 0 ? 3 * w : 0;
 }
-__host__ __device__ inline int64_t plane_rows(int format, int plane, int64_t h) {
+PF_HD int64_t plane_rows(int format, int plane, int64_t h) {
     if (plane == 0) return h;
     return format == PIX_NV12 ? (h + 1) / 2 : 0;
 }

@@ -2,6 +2,7 @@
 // the two taps vp_dbg_pose_nms_host / vp_dbg_pose_oks.  No atomics and every sum in joint order: a call is bit-identical from run to run and
 // independent of the launch shape.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "posenms.h"
 
 using namespace vpi;
@@ -219,35 +220,26 @@ int vp_pose_nms(vp_handle c, const float* kpts, int32_t n, int32_t k, const floa
         if (count && n_frames > 0) std::memset(count, 0, (size_t)n_frames * 4);
         return VP_OK;
     }
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // one scratch allocation: kpts | box scores | crop params | status | score | rank | count (every part 256-byte aligned)
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b_kp = up((size_t)n * k * 12), b_bs = up(((size_t)(n - 1) * score_stride + 1) * 4), b_p9 = up((size_t)n * 36), b_n = up((size_t)n * 4), b_f = up((size_t)n_frames * 4);
-    char* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, b_kp + b_bs + b_p9 + 3 * b_n + b_f));
-    float* d_kp = (float*)d;
-    float* d_bs = (float*)(d + b_kp);
-    int32_t* d_p9 = (int32_t*)(d + b_kp + b_bs);
-    int32_t* d_st = (int32_t*)(d + b_kp + b_bs + b_p9);
-    float* d_sc = (float*)(d + b_kp + b_bs + b_p9 + b_n);
-    int32_t* d_rk = (int32_t*)(d + b_kp + b_bs + b_p9 + 2 * b_n);
-    int32_t* d_ct = (int32_t*)(d + b_kp + b_bs + b_p9 + 3 * b_n);
-    hipStream_t s = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    chk(hipMemcpyAsync(d_kp, kpts, (size_t)n * k * 12, hipMemcpyHostToDevice, s), "upload keypoints");
-    chk(hipMemcpyAsync(d_bs, box_score, ((size_t)(n - 1) * score_stride + 1) * 4, hipMemcpyHostToDevice, s), "upload box scores");
-    chk(hipMemcpyAsync(d_p9, crop_params, (size_t)n * 36, hipMemcpyHostToDevice, s), "upload crop params");
-    if (status) chk(hipMemcpyAsync(d_st, status, (size_t)n * 4, hipMemcpyHostToDevice, s), "upload status");
-    if (!rc) rc = nms_enqueue(c, d_kp, n, k, d_bs, score_stride, d_p9, status ? d_st : nullptr, n_frames, p, vars, d_sc, d_rk, d_ct, s);
-    if (!rc) {
-        chk(hipMemcpyAsync(score, d_sc, (size_t)n * 4, hipMemcpyDeviceToHost, s), "download score");
-        chk(hipMemcpyAsync(rank, d_rk, (size_t)n * 4, hipMemcpyDeviceToHost, s), "download rank");
-        if (count) chk(hipMemcpyAsync(count, d_ct, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s), "download count");
+    // one scratch block: kpts | box scores | crop params | status | score | rank | count
+    HostStage st(c);
+    const size_t kp_bytes = (size_t)n * k * 12, bs_bytes = ((size_t)(n - 1) * score_stride + 1) * 4, nb = (size_t)n * 4;
+    const size_t o_kp = st.part(kp_bytes), o_bs = st.part(bs_bytes), o_p9 = st.part((size_t)n * 36), o_st = st.part(nb), o_sc = st.part(nb), o_rk = st.part(nb),
+                 o_ct = st.part((size_t)n_frames * 4);
+    if (st.alloc()) return st.rc;
+    float *d_kp = st.at<float>(o_kp), *d_bs = st.at<float>(o_bs), *d_sc = st.at<float>(o_sc);
+    int32_t *d_p9 = st.at<int32_t>(o_p9), *d_st = st.at<int32_t>(o_st), *d_rk = st.at<int32_t>(o_rk), *d_ct = st.at<int32_t>(o_ct);
+    st.up(d_kp, kpts, kp_bytes, "upload keypoints");
+    st.up(d_bs, box_score, bs_bytes, "upload box scores");
+    st.up(d_p9, crop_params, (size_t)n * 36, "upload crop params");
+    if (status) st.up(d_st, status, nb, "upload status");
+    if (!st.rc) st.rc = nms_enqueue(c, d_kp, n, k, d_bs, score_stride, d_p9, status ? d_st : nullptr, n_frames, p, vars, d_sc, d_rk, d_ct, st.s);
+    if (!st.rc) {
+        st.down(score, d_sc, nb, "download score");
+        st.down(rank, d_rk, nb, "download rank");
+        if (count) st.down(count, d_ct, (size_t)n_frames * 4, "download count");
     }
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-    hipFree(d);
-    return rc;
+    st.sync();
+    return st.rc;
 }
 
 // the semantics of posenms.h run row by row on the host: what pose_nms_kernel computes, in the same order
@@ -321,26 +313,21 @@ int vp_dbg_pose_oks(int32_t device_id, const float* kpts, int32_t n, int32_t k, 
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(c, VP_ERR_HIP, "no HIP device available (no CPU fallback)");
     if (device_id >= ndev) return fail(c, VP_ERR_INVALID, "device_id out of range");
     HIPCHK(c, hipSetDevice(device_id));
-    float *d_kp = nullptr, *d_out = nullptr;
-    int32_t* d_p9 = nullptr;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    chk(hipMalloc((void**)&d_kp, (size_t)n * row * 4), "hipMalloc");
-    chk(hipMalloc((void**)&d_p9, (size_t)n * 36), "hipMalloc");
-    chk(hipMalloc((void**)&d_out, (size_t)n * n * 4), "hipMalloc");
-    if (!rc) {
-        chk(hipMemcpy(d_kp, kpts, (size_t)n * row * 4, hipMemcpyHostToDevice), "upload keypoints");
-        chk(hipMemcpy(d_p9, crop_params, (size_t)n * 36, hipMemcpyHostToDevice), "upload crop params");
-    }
-    if (!rc) {
+    HostStage st(c);   // kpts | crop params | oks; blocking copies around a launch on the default stream
+    const size_t o_kp = st.part((size_t)n * row * 4), o_p9 = st.part((size_t)n * 36), o_out = st.part((size_t)n * n * 4);
+    if (st.alloc()) return st.rc;
+    float *d_kp = st.at<float>(o_kp), *d_out = st.at<float>(o_out);
+    int32_t* d_p9 = st.at<int32_t>(o_p9);
+    st.chk(hipMemcpy(d_kp, kpts, (size_t)n * row * 4, hipMemcpyHostToDevice), "upload keypoints");
+    st.chk(hipMemcpy(d_p9, crop_params, (size_t)n * 36, hipMemcpyHostToDevice), "upload crop params");
+    if (!st.rc) {
         const int L = vp::nms_lanes(n);
         hipLaunchKernelGGL(vp::pose_oks_kernel, dim3((unsigned)(((size_t)n * n * L + vp::NMS_THREADS - 1) / vp::NMS_THREADS)), dim3(vp::NMS_THREADS), 0, 0, d_kp, n, k, d_p9,
                            p, vars, L, d_out);
-        chk(hipGetLastError(), "pose_oks_kernel");
-        chk(hipMemcpy(oks, d_out, (size_t)n * n * 4, hipMemcpyDeviceToHost), "download oks");
+        st.chk(hipGetLastError(), "pose_oks_kernel");
+        st.chk(hipMemcpy(oks, d_out, (size_t)n * n * 4, hipMemcpyDeviceToHost), "download oks");
     }
-    hipFree(d_kp); hipFree(d_p9); hipFree(d_out);
-    return rc;
+    return st.rc;
 }
 
 }  // extern "C"

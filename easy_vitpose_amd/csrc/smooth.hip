@@ -3,6 +3,7 @@
 // per stepped stream (ageing, id matching, births), and smooth_filter_kernel, one thread per (row, joint).  No atomics, no flags between workgroups: every row maps
 // to at most one slot and every slot to at most one row of a call, so a call is bit-identical from run to run.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "eurogeom.h"
 
 using namespace vpi;
@@ -394,35 +395,27 @@ int vp_smooth_update(vp_smoother_handle s, const float* kpts, const int32_t* ids
     std::string why;
     vp::EuroTe te;
     if (update_args(s->p, kpts, ids, n, step_mask, t_e, out, te, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // one scratch allocation: keypoints | ids | stream | rank | flags (every part 256-byte aligned); the filter runs in place on the keypoints
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    // one scratch block: keypoints | ids | stream | rank | flags; the filter runs in place on the keypoints
+    HostStage st(c);
     const int ns = s->p.n_streams;
-    const size_t kp_bytes = (size_t)n * s->p.n_joints * 3 * sizeof(float), b_kp = up(kp_bytes), b_n = up((size_t)n * 4), b_f = up((size_t)ns * 4);
-    char* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, b_kp + 3 * b_n + b_f + 256));
-    float* d_kp = (float*)d;
-    int32_t* d_ids = (int32_t*)(d + b_kp);
-    int32_t* d_st = (int32_t*)(d + b_kp + b_n);
-    int32_t* d_rk = (int32_t*)(d + b_kp + 2 * b_n);
-    int32_t* d_fl = (int32_t*)(d + b_kp + 3 * b_n);
-    hipStream_t q = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
+    const size_t kp_bytes = (size_t)n * s->p.n_joints * 3 * sizeof(float), nb = (size_t)n * 4;
+    const size_t o_kp = st.part(kp_bytes), o_ids = st.part(nb), o_st = st.part(nb), o_rk = st.part(nb), o_fl = st.part((size_t)ns * 4);
+    if (st.alloc()) return st.rc;
+    float* d_kp = st.at<float>(o_kp);
+    int32_t *d_ids = st.at<int32_t>(o_ids), *d_st = st.at<int32_t>(o_st), *d_rk = st.at<int32_t>(o_rk), *d_fl = st.at<int32_t>(o_fl);
     if (n) {
-        chk(hipMemcpyAsync(d_kp, kpts, kp_bytes, hipMemcpyHostToDevice, q), "upload keypoints");
-        chk(hipMemcpyAsync(d_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, q), "upload ids");
-        if (stream) chk(hipMemcpyAsync(d_st, stream, (size_t)n * 4, hipMemcpyHostToDevice, q), "upload stream");
-        if (rank) chk(hipMemcpyAsync(d_rk, rank, (size_t)n * 4, hipMemcpyHostToDevice, q), "upload rank");
+        st.up(d_kp, kpts, kp_bytes, "upload keypoints");
+        st.up(d_ids, ids, nb, "upload ids");
+        if (stream) st.up(d_st, stream, nb, "upload stream");
+        if (rank) st.up(d_rk, rank, nb, "upload rank");
     }
-    if (!rc) rc = update_enqueue(s, te, d_kp, d_ids, n && stream ? d_st : nullptr, n && rank ? d_rk : nullptr, n, step_mask, d_kp, d_fl, q);
-    if (!rc) {
-        if (n) chk(hipMemcpyAsync(out, d_kp, kp_bytes, hipMemcpyDeviceToHost, q), "download keypoints");
-        if (flags) chk(hipMemcpyAsync(flags, d_fl, (size_t)ns * 4, hipMemcpyDeviceToHost, q), "download flags");
+    if (!st.rc) st.rc = update_enqueue(s, te, d_kp, d_ids, n && stream ? d_st : nullptr, n && rank ? d_rk : nullptr, n, step_mask, d_kp, d_fl, st.s);
+    if (!st.rc) {
+        if (n) st.down(out, d_kp, kp_bytes, "download keypoints");
+        if (flags) st.down(flags, d_fl, (size_t)ns * 4, "download flags");
     }
-    chk(hipStreamSynchronize(q), "hipStreamSynchronize");
-    (void)hipFree(d);
-    return rc;
+    st.sync();
+    return st.rc;
 }
 
 int vp_smoother_state_bytes(const vp_smooth_cfg* cfg, int64_t* bytes) {

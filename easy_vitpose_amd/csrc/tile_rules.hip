@@ -2,6 +2,7 @@
 // (pick_*) feed one resolver per GEMM (resolve_gemm) and one plan per chunk (plan_chunk), which the orchestration (forward.hip) only executes.
 // tests/test_host_logic.py walks the rules and the plan over every batch size of every model through the host-only taps at the end of this file.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "tiles.h"
 
 using namespace vpi;
@@ -44,7 +45,7 @@ G8Pick pick_gemm8_tile(int M, int N, bool wide, int bm192_mask, long min_tiles, 
         if (ext) q = q || (rounds == 1 && t >= 192) || cost < 0.95 * cost2;
         if (!q) continue;
         if (cd.BM == 256) have256 = true;
-        if (!pk.variant || (ext ? cost < 0.98 * best : f > (double)pk.tiles / (double)((pk.tiles + 255) / 256 * 256) + 1e-9)) {
+        if (!pk.variant || (ext ? cost < 0.98 * best : f > (double)pk.tiles / (double)up256((size_t)pk.tiles) + 1e-9)) {
             pk = {cd.id, cd.BM, cd.BN, t};
             best = cost;
         }
@@ -273,7 +274,7 @@ GemmPick resolve_gemm_fp8(int fam, int epi, int Mp, int N) {
             if (N % cand) continue;
             const long t = (long)(Mp / 256) * (N / cand);
             if (t < 8) continue;
-            const double f = (double)t / (double)((t + 255) / 256 * 256);
+            const double f = (double)t / (double)up256((size_t)t);
             if (f > fill + 1e-9) { bn = cand; fill = f; }
         }
     }
@@ -310,7 +311,7 @@ ChunkPlan plan_chunk(const Switches& s, int D, int heads, int max_batch, bool fp
     p.gemm[VP_PROF_GEMM_PATCH] = gemm(VP_PROF_GEMM_PATCH, s.fuse_ln ? vp::EPI_POS_LN : vp::EPI_POS, D, 768, false);
     p.gemm[VP_PROF_GEMM_PROJ] = gemm(VP_PROF_GEMM_PROJ, resid, D, D, false);
     if (fp8) {   // qkv / fc1 / fc2 (and attn.proj at head dim 64) on MXFP8 operands, token rows padded to a multiple of 256 (>= 512)
-        const int Mp = std::max((M + 255) / 256 * 256, 512);
+        const int Mp = std::max((int)up256((size_t)M), 512);
         p.proj_fp8 = hd == 64 && !s.fp8_proj16;
         p.gemm[VP_PROF_GEMM_QKV] = resolve_gemm_fp8(VP_PROF_GEMM_QKV, vp::EPI_BIAS, Mp, 3 * D);
         if (p.proj_fp8) p.gemm[VP_PROF_GEMM_PROJ] = resolve_gemm_fp8(VP_PROF_GEMM_PROJ, vp::EPI_BIAS_RESID_LN, Mp, D);

@@ -2,6 +2,7 @@
 // vp_tracker_update and the two taps vp_dbg_track_host / vp_dbg_lsap.  Two launches per call: track_update_kernel, one workgroup per stepped stream, and
 // track_gather_kernel, one workgroup.  vp_tracker_update_counted_stream is the same call with the detection count read from device memory.  No atomics, no flags between workgroups, every reduction in a fixed order: a call is bit-identical from run to run.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "sortgeom.h"
 
 using namespace vpi;
@@ -636,39 +637,30 @@ int vp_tracker_update(vp_tracker_handle t, const float* dets, int32_t row_stride
     vp_ctx* c = t->c;
     std::string why;
     if (update_args(t->p, dets, row_stride, n_dets, step_mask, rows, ids, stream, n_out, count, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    // one scratch allocation: dets | frame index | rows | ids | stream | count | flags (every part 256-byte aligned)
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    // one scratch block: dets | frame index | rows | ids | stream | count | flags
+    HostStage st(c);
     const int ns = t->p.n_streams;
-    const size_t b_det = up(n_dets ? ((size_t)(n_dets - 1) * row_stride + 5) * 4 : 0), b_fi = up((size_t)n_dets * 4), b_rows = up((size_t)n_out * 24), b_n = up((size_t)n_out * 4),
-                 b_s = up((size_t)(ns + 1) * 4);
-    char* d = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d, b_det + b_fi + b_rows + 2 * b_n + 2 * b_s + 256));
-    float* d_det = (float*)d;
-    int32_t* d_fi = (int32_t*)(d + b_det);
-    float* d_rows = (float*)(d + b_det + b_fi);
-    int32_t* d_ids = (int32_t*)(d + b_det + b_fi + b_rows);
-    int32_t* d_st = (int32_t*)(d + b_det + b_fi + b_rows + b_n);
-    int32_t* d_ct = (int32_t*)(d + b_det + b_fi + b_rows + 2 * b_n);
-    int32_t* d_fl = (int32_t*)(d + b_det + b_fi + b_rows + 2 * b_n + b_s);
-    hipStream_t s = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    if (n_dets) chk(hipMemcpyAsync(d_det, dets, ((size_t)(n_dets - 1) * row_stride + 5) * 4, hipMemcpyHostToDevice, s), "upload detections");
-    if (n_dets && frame_idx) chk(hipMemcpyAsync(d_fi, frame_idx, (size_t)n_dets * 4, hipMemcpyHostToDevice, s), "upload frame index");
-    if (!rc) rc = update_enqueue(t, n_dets ? d_det : nullptr, row_stride, n_dets && frame_idx ? d_fi : nullptr, n_dets, nullptr, step_mask, d_rows, d_ids, d_st, n_out, d_ct, d_fl, s);
-    if (!rc) {
+    const size_t det_bytes = n_dets ? ((size_t)(n_dets - 1) * row_stride + 5) * 4 : 0, ob = (size_t)n_out * 4, sb = (size_t)(ns + 1) * 4;
+    const size_t o_det = st.part(det_bytes), o_fi = st.part((size_t)n_dets * 4), o_rows = st.part((size_t)n_out * 24), o_ids = st.part(ob), o_st = st.part(ob), o_ct = st.part(sb),
+                 o_fl = st.part(sb);
+    if (st.alloc()) return st.rc;
+    float *d_det = st.at<float>(o_det), *d_rows = st.at<float>(o_rows);
+    int32_t *d_fi = st.at<int32_t>(o_fi), *d_ids = st.at<int32_t>(o_ids), *d_st = st.at<int32_t>(o_st), *d_ct = st.at<int32_t>(o_ct), *d_fl = st.at<int32_t>(o_fl);
+    if (n_dets) st.up(d_det, dets, det_bytes, "upload detections");
+    if (n_dets && frame_idx) st.up(d_fi, frame_idx, (size_t)n_dets * 4, "upload frame index");
+    if (!st.rc)
+        st.rc = update_enqueue(t, n_dets ? d_det : nullptr, row_stride, n_dets && frame_idx ? d_fi : nullptr, n_dets, nullptr, step_mask, d_rows, d_ids, d_st, n_out, d_ct, d_fl, st.s);
+    if (!st.rc) {
         if (n_out) {
-            chk(hipMemcpyAsync(rows, d_rows, (size_t)n_out * 24, hipMemcpyDeviceToHost, s), "download rows");
-            chk(hipMemcpyAsync(ids, d_ids, (size_t)n_out * 4, hipMemcpyDeviceToHost, s), "download ids");
-            chk(hipMemcpyAsync(stream, d_st, (size_t)n_out * 4, hipMemcpyDeviceToHost, s), "download stream");
+            st.down(rows, d_rows, (size_t)n_out * 24, "download rows");
+            st.down(ids, d_ids, ob, "download ids");
+            st.down(stream, d_st, ob, "download stream");
         }
-        chk(hipMemcpyAsync(count, d_ct, (size_t)(ns + 1) * 4, hipMemcpyDeviceToHost, s), "download count");
-        if (flags) chk(hipMemcpyAsync(flags, d_fl, (size_t)ns * 4, hipMemcpyDeviceToHost, s), "download flags");
+        st.down(count, d_ct, sb, "download count");
+        if (flags) st.down(flags, d_fl, (size_t)ns * 4, "download flags");
     }
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-    (void)hipFree(d);
-    return rc;
+    st.sync();
+    return st.rc;
 }
 
 int vp_tracker_state_bytes(int32_t n_streams, int64_t* bytes) {
@@ -725,20 +717,18 @@ int vp_dbg_lsap(int32_t device_id, const double* iou, int32_t nd, int32_t nt, fl
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(c, VP_ERR_HIP, "no HIP device available (no CPU fallback)");
     if (device_id >= ndev) return fail(c, VP_ERR_INVALID, "device_id out of range");
     HIPCHK(c, hipSetDevice(device_id));
-    double* d_iou = nullptr;
-    int32_t* d_out = nullptr;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    chk(hipMalloc((void**)&d_iou, (size_t)nd * nt * 8), "hipMalloc");
-    chk(hipMalloc((void**)&d_out, (size_t)nd * 4), "hipMalloc");
-    if (!rc) chk(hipMemcpy(d_iou, iou, (size_t)nd * nt * 8, hipMemcpyHostToDevice), "upload iou");
-    if (!rc) {
+    HostStage st(c);   // iou | pairs; blocking copies around a launch on the default stream
+    const size_t o_iou = st.part((size_t)nd * nt * 8), o_out = st.part((size_t)nd * 4);
+    if (st.alloc()) return st.rc;
+    double* d_iou = st.at<double>(o_iou);
+    int32_t* d_out = st.at<int32_t>(o_out);
+    st.chk(hipMemcpy(d_iou, iou, (size_t)nd * nt * 8, hipMemcpyHostToDevice), "upload iou");
+    if (!st.rc) {
         hipLaunchKernelGGL(vp::track_lsap_kernel, dim3(1), dim3(vp::TRK_THREADS), 0, 0, d_iou, nd, nt, thr, d_out);
-        chk(hipGetLastError(), "track_lsap_kernel");
-        chk(hipMemcpy(trk_of_det, d_out, (size_t)nd * 4, hipMemcpyDeviceToHost), "download pairs");
+        st.chk(hipGetLastError(), "track_lsap_kernel");
+        st.chk(hipMemcpy(trk_of_det, d_out, (size_t)nd * 4, hipMemcpyDeviceToHost), "download pairs");
     }
-    (void)hipFree(d_iou); (void)hipFree(d_out);
-    return rc;
+    return st.rc;
 }
 
 }  // extern "C"

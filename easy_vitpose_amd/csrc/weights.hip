@@ -3,6 +3,7 @@
 // LayerNorm's gamma / beta folded into qkv / fc1, pos + cls + conv bias pre-added, the deconvs re-tiled into four output-parity GEMM
 // operands, the final 1x1 conv as hi + lo pairs, e4m3 codes + scales in the fp8 mode.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "simpleheadgeom.h"
 
 using namespace vpi;
@@ -77,7 +78,7 @@ float host_from_bits(uint16_t h, int dtype) {
     return f;
 }
 
-size_t pad128(size_t n) { return (n + 255) / 256 * 256; }
+size_t pad128(size_t n) { return up256(n); }
 
 // final 1x1 conv weights as a hi + lo pair of 16-bit values (W = hi + lo to ~22 bits): 16-row groups interleaved
 // [16 hi rows][16 lo rows] so that the two MFMA accumulator fragments a lane sums in the EPI_HEATMAP epilogue are

@@ -3,6 +3,7 @@
 // (every convolution: implicit GEMM on mfma_f32_16x16x32_f16, operands straight from global memory, no LDS), yolo_pool_kernel, yolo_up_kernel, yolo_decode_kernel.
 // A forward is the plan's launches in order on the caller's stream: no atomics, no allocation, no copy, no synchronisation.
 #include "api_internal.h"
+#include "hoststage.h"
 #include "common.h"
 #include "yologeom.h"
 
@@ -202,8 +203,6 @@ template <typename T> __global__ __launch_bounds__(EW_THREADS) void yolo_decode_
 namespace {
 
 using vp::YoloPlan;
-
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 
 int cfg_check(const vp_yolo_cfg* cfg, std::string* why) {
     auto bad = [&](const std::string& m) { *why = "yolo: " + m; return (int)VP_ERR_INVALID; };
@@ -439,19 +438,15 @@ int vp_yolo_forward(vp_yolo_handle y, const void* input, int32_t n_images, void*
     std::string why;
     if (call_args(y, input, n_images, head, &why)) return fail(c, VP_ERR_INVALID, why);
     if (n_images == 0) return VP_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
+    HostStage st(c);   // one scratch block: input | head
     const size_t in_bytes = (size_t)n_images * 3 * y->cfg.in_h * y->cfg.in_w * 2, hb = head_bytes(y, n_images);
-    char* m = nullptr;
-    HIPCHK(c, hipMalloc((void**)&m, up256(in_bytes) + hb + 256));
-    hipStream_t s = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    chk(hipMemcpyAsync(m, input, in_bytes, hipMemcpyHostToDevice, s), "upload input");
-    if (!rc) rc = forward_enqueue(y, m, n_images, m + up256(in_bytes), s);
-    if (!rc) chk(hipMemcpyAsync(head, m + up256(in_bytes), hb, hipMemcpyDeviceToHost, s), "download head");
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-    (void)hipFree(m);
-    return rc;
+    const size_t o_in = st.part(in_bytes), o_head = st.part(hb);
+    if (st.alloc()) return st.rc;
+    st.up(st.at(o_in), input, in_bytes, "upload input");
+    if (!st.rc) st.rc = forward_enqueue(y, st.at(o_in), n_images, st.at(o_head), st.s);
+    if (!st.rc) st.down(head, st.at(o_head), hb, "download head");
+    st.sync();
+    return st.rc;
 }
 
 int vp_dbg_yolo_plan(const vp_yolo_cfg* cfg, const vp_yolo_tensor* tensors, int32_t n_tensors, vp_yolo_launch* launches, int32_t max_launches, vp_yolo_buffer* buffers,
@@ -556,21 +551,18 @@ int vp_dbg_yolo_conv_case(vp_handle c, const vp_yolo_launch* l, int32_t n_images
         bi[(size_t)o] = bias[o];
     }
     const size_t pin = (size_t)n_images * l->h_in * l->w_in, pout = (size_t)n_images * l->h_out * l->w_out;
-    const size_t b_in = up256(pin * l->in_stride * 2), b_out = up256(pout * l->out_stride * (l->f32_out ? 4 : 2)), b_res = res ? up256(pout * l->res_stride * 2) : 0;
-    const size_t b_w = up256(wi.size() * 2), b_b = up256(bi.size() * 4);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    char* m = nullptr;
-    HIPCHK(c, hipMalloc((void**)&m, b_in + b_out + b_res + b_w + b_b));
-    char *d_in = m, *d_out = d_in + b_in, *d_res = d_out + b_out, *d_w = d_res + b_res, *d_b = d_w + b_w;
-    hipStream_t s = c->own_stream;
-    int rc = VP_OK;
-    auto chk = [&](hipError_t e, const char* what) { if (e != hipSuccess && !rc) rc = fail(c, VP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
-    chk(hipMemcpyAsync(d_in, in, pin * l->in_stride * 2, hipMemcpyHostToDevice, s), "upload in");
-    chk(hipMemcpyAsync(d_w, wi.data(), wi.size() * 2, hipMemcpyHostToDevice, s), "upload w");
-    chk(hipMemcpyAsync(d_b, bi.data(), bi.size() * 4, hipMemcpyHostToDevice, s), "upload bias");
-    if (res) chk(hipMemcpyAsync(d_res, res, pout * l->res_stride * 2, hipMemcpyHostToDevice, s), "upload res");
-    chk(hipMemsetAsync(d_out, 0xFF, b_out, s), "fill out");
-    if (!rc) {
+    HostStage st(c);   // one scratch block: in | out | res | w | bias
+    const size_t in_bytes = pin * l->in_stride * 2, out_bytes = pout * l->out_stride * (l->f32_out ? 4 : 2), res_bytes = pout * l->res_stride * 2;
+    const size_t o_in = st.part(in_bytes), o_out = st.part(out_bytes), o_res = res ? st.part(res_bytes) : 0, o_w = st.part(wi.size() * 2), o_b = st.part(bi.size() * 4);
+    if (st.alloc()) return st.rc;
+    char *d_in = st.at(o_in), *d_out = st.at(o_out), *d_res = st.at(o_res), *d_w = st.at(o_w), *d_b = st.at(o_b);
+    hipStream_t s = st.s;
+    st.up(d_in, in, in_bytes, "upload in");
+    st.up(d_w, wi.data(), wi.size() * 2, "upload w");
+    st.up(d_b, bi.data(), bi.size() * 4, "upload bias");
+    if (res) st.up(d_res, res, res_bytes, "upload res");
+    st.chk(hipMemsetAsync(d_out, 0xFF, up256(out_bytes), s), "fill out");   // the part's whole room: what the kernel must not write stays 0xFF
+    if (!st.rc) {
         ConvArgs a;
         a.in = (const _Float16*)d_in; a.w = (const _Float16*)d_w; a.bias = (const float*)d_b; a.out = d_out; a.res = res ? (const _Float16*)d_res : nullptr;
         a.M = (int)pout; a.H = l->h_in; a.W = l->w_in; a.Ho = l->h_out; a.Wo = l->w_out;
@@ -578,12 +570,11 @@ int vp_dbg_yolo_conv_case(vp_handle c, const vp_yolo_launch* l, int32_t n_images
         a.c_out = l->c_out; a.s = l->s; a.act = l->act;
         a.in_off = l->in_off; a.in_stride = l->in_stride; a.out_off = l->out_off; a.out_stride = l->out_stride; a.res_off = l->res_off; a.res_stride = l->res_stride;
         conv_run(a, l->k, l->f32_out != 0, rows_pad, s);
-        chk(hipGetLastError(), "launch");
-        chk(hipMemcpyAsync(out, d_out, pout * l->out_stride * (l->f32_out ? 4 : 2), hipMemcpyDeviceToHost, s), "download out");
+        st.chk(hipGetLastError(), "launch");
+        st.down(out, d_out, out_bytes, "download out");
     }
-    chk(hipStreamSynchronize(s), "hipStreamSynchronize");
-    (void)hipFree(m);
-    return rc;
+    st.sync();
+    return st.rc;
 }
 
 }  // extern "C"

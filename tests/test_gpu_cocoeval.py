@@ -54,6 +54,27 @@ def test_device_equals_the_host_model_on_the_cpu_cases(eng, name):
     ev.close()
 
 
+@pytest.mark.parametrize('rank,rows,gts', [(r, n, g) for r in (True, False) for n in (True, False) for g in (True, False)],
+                         ids=lambda v: 'given' if v else 'absent')
+def test_host_arrays_with_every_combination_of_rank_rows_and_gts(eng, rank, rows, gts):
+    """vp_cocoeval_update on host arrays with rank given or null, with and without rows, with and without ground truths (7 rows, 3 gts: the margin-checked
+    `null_optionals` call), twice: match, the state and the result equal the host tap byte for byte"""
+    call = dict(cc.inputs(CASES['null_optionals']['calls'][0]))
+    if rank:
+        call['rank'] = np.array([0, -1, 2, 1, -1, 0, 3], I32)
+    if not rows:
+        call.update(kpts=None, score=None, frame=None, rank=np.zeros(0, I32) if rank else None)
+    if not gts:
+        call.update(gt_kpts=None, gt_box=None, gt_area=None, gt_flags=None, gt_frame=None)
+    cfg = CocoEvalCfg(17, 64)
+    ev, want = eng.cocoeval(cfg), new_state(cfg)
+    for i in range(2):
+        assert ev.update_host(**call).tobytes() == cocoeval_tap(want, cfg, **call).tobytes(), i
+    same(ev.state(), want)
+    same(ev.accumulate_host(), cocoeval_tap_accumulate(want, cfg))
+    ev.close()
+
+
 def test_stream_entries_with_reset_and_calls_without_rows_or_gts(eng):
     import torch
     cs = CASES['frames_256']

@@ -35,6 +35,21 @@ def test_device_equals_the_host_model_on_the_cpu_cases(eng, name):
         assert np.array_equal(g, w), f'{name}: buffer {p} differs in {int((g != w).sum())} bytes'
 
 
+OPTIONAL = ('rank', 'ids', 'boxes')
+
+
+@pytest.mark.parametrize('absent', [tuple(k for k, bit in zip(OPTIONAL, (1, 2, 4)) if m & bit) for m in range(8)], ids=lambda a: 'no_' + '_'.join(a) if a else 'all_given')
+def test_host_arrays_with_every_combination_of_optional_inputs_absent(eng, absent):
+    """vp_draw_poses on host arrays with every subset of rank, ids and boxes null: 8 rows of 17 joints on one pitched 32 x 48 frame per format, the whole buffers
+    equal the host tap's byte for byte"""
+    rng = np.random.default_rng(11)
+    kp = dc.people(rng, 8, 17, 32, 48, spread=12.0)
+    given = dict(rank=[0, -1, 2, 1, 3, -1, 4, 5], ids=[7, 3, 3, 250, 0, 12, 1, 99], boxes=dc.boxes_of(kp, rng))
+    cs = dc.case([(32, 48, 'rgb', 'bt601', 5), (32, 48, 'nv12', 'bt709', 6)], kp, np.arange(8) % 2, seed=3, **{k: None if k in absent else v for k, v in given.items()})
+    got, want = dc.run_device(cs, eng), dc.run_tap(cs)
+    assert dc.same(got, want) and not dc.same(want, dc.build_frames(cs['specs'], cs['seed'])[1]), 'equal, and something was drawn'
+
+
 @pytest.mark.parametrize('fmt', ['rgb', 'nv12'])
 def test_more_hits_on_one_tile_than_the_lds_list_holds(eng, fmt):
     """300 rows x 36 primitives on one 20 x 20 region: chunks of 256 records in which every record hits the same tiles, so the list fills and is resolved many times"""

@@ -37,6 +37,21 @@ def test_device_equals_the_host_model_on_the_cpu_cases(eng, name):
         assert np.array_equal(g, w), f'{name}: buffer {p} differs in {int((g != w).sum())} bytes'
 
 
+OPTIONAL = ('rank', 'ids', 'scores')
+
+
+@pytest.mark.parametrize('absent', [tuple(k for k, bit in zip(OPTIONAL, (1, 2, 4)) if m & bit) for m in range(8)], ids=lambda a: 'no_' + '_'.join(a) if a else 'all_given')
+def test_host_arrays_with_every_combination_of_optional_inputs_absent(eng, absent):
+    """vp_draw_labels on host arrays with every subset of rank, ids and scores null: 8 rows on one pitched 32 x 48 frame per format, the whole buffers equal the
+    host tap's byte for byte"""
+    rng = np.random.default_rng(12)
+    given = dict(rank=[0, -1, 2, 1, 3, -1, 4, 5], ids=[7, 3, -3, 250, 0, 12, 1, 99], scores=rng.uniform(0, 1, 8))
+    cs = lc.case([(32, 48, 'rgb', 'bt601', 5), (32, 48, 'nv12', 'bt709', 6)], lc.crowd(rng, 8, 24, 40), np.arange(8) % 2, LabelStyle(scale=1), seed=4,
+                 **{k: None if k in absent else v for k, v in given.items()})
+    got, want = lc.run_device(cs, eng), lc.run_tap(cs)
+    assert lc.same(got, want) and not lc.same(want, lc.build_frames(cs['specs'], cs['seed'])[1]), 'equal, and something was drawn'
+
+
 def test_three_runs_are_bit_identical(eng):
     for name in ('overlap3', 'edges_nv12'):
         runs = [lc.run_device(CASES[name], eng) for _ in range(3)]

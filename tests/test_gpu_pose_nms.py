@@ -64,6 +64,16 @@ def test_device_equals_the_host_model_on_goldens_and_edge_cases(eng):
     assert c.cpu().tolist() == [0, 0] and s.shape == (0,) and r.shape == (0,)
 
 
+@pytest.mark.parametrize('n', [8, 1, 0])
+@pytest.mark.parametrize('status', [True, False], ids=['status', 'no_status'])
+def test_host_arrays_with_status_absent_and_with_zero_rows(eng, status, n):
+    """vp_pose_nms on host arrays with status given or null, on 8 rows of 17 joints over two frames, on one row and on none: scores, ranks and counts
+    against the host tap (hard scores bit for bit)"""
+    kp, bs, p9 = people(8, n_frames=2, seed=7)
+    st = np.array([0, 3, 0, 0, 1, 0, 0, 0], np.int32)[:n] if status else None
+    check_against_host(eng, kp[:n], bs[:n], p9[:n], 2, PoseNms(oks_thr=0.5), sigmas17(), status=st, tag=f'n={n}')
+
+
 @pytest.mark.parametrize('n', [65, 257, NMS_MAX_PER_FRAME])
 def test_sizes_across_a_wave_a_workgroup_and_the_cap(eng, n):
     kp, bs, p9 = people(n, seed=100 + n)

@@ -71,6 +71,24 @@ def test_in_place_equals_out_of_place(eng, case):
     both(eng, case[1], cfg_kw, calls, in_place=True)   # against the tap, which `both` without in_place equals too: in place == out of place
 
 
+OPTIONAL = ('stream', 'rank', 't_e')
+
+
+@pytest.mark.parametrize('absent', [tuple(k for k, bit in zip(OPTIONAL, (1, 2, 4)) if m & bit) for m in range(8)], ids=lambda a: 'no_' + '_'.join(a) if a else 'all_given')
+def test_host_arrays_with_every_combination_of_optional_inputs_absent(eng, absent):
+    """vp_smooth_update on host arrays with every subset of stream, rank and t_e null, on calls of at most 8 rows of 17 joints and on one without rows:
+    keypoints, flags and the state after every call equal the host tap bit for bit"""
+    cfg_kw, seq = sequence(SEQUENCES[0])   # one stream: a null stream argument means the same table
+    calls = []
+    for c in [c for c in seq if 'reset' not in c and len(c['ids'])][:3]:
+        n = min(len(c['ids']), 8)
+        given = dict(kpts=c['kpts'][:n], ids=c['ids'][:n], stream=np.zeros(n, np.int32), rank=(np.arange(n, dtype=np.int32) % 3) - 1, t_e=2.0, step_mask=None)
+        calls.append({k: None if k in absent else v for k, v in given.items()})
+    calls.append({**calls[-1], 'kpts': np.zeros((0, 17, 3), np.float32), 'ids': np.zeros(0, np.int32), 'stream': None if 'stream' in absent else np.zeros(0, np.int32),
+                  'rank': None if 'rank' in absent else np.zeros(0, np.int32)})
+    both(eng, 17, cfg_kw, calls)
+
+
 def test_table_full_on_the_device(eng):
     cfg_kw, calls = table_full()
     outs = both(eng, 17, cfg_kw, calls)

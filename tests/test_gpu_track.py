@@ -53,6 +53,16 @@ def test_device_equals_the_host_tap_on_the_sequences(eng, tag):
     assert sum(int(o[3][-1]) for o in outs) > 50 and all(o[4][0] == 0 for o in outs)
 
 
+@pytest.mark.parametrize('n_dets', [8, 0], ids=['dets_8', 'dets_0'])
+@pytest.mark.parametrize('frame_index', [True, False], ids=['frame_index', 'no_frame_index'])
+def test_host_arrays_with_frame_index_absent_and_with_zero_rows(eng, frame_index, n_dets):
+    """vp_tracker_update on host arrays with frame_index given or null, with at most 8 detections or none, with and without room for output rows: every output
+    and the final state equal the host tap bit for bit"""
+    frames, age, hits = SEQUENCES[next(iter(SEQUENCES))]
+    calls = [dict(dets=d[:n_dets], frame_index=np.zeros(len(d[:n_dets]), np.int32) if frame_index else None, n_out=n_out) for d, n_out in zip(frames[:4], (8, 8, 0, 8))]
+    both(eng, TrackCfg(age, hits, IOU_THRESHOLD, 1), calls)
+
+
 def lsap(device_id, iou, thr):
     out = np.full(iou.shape[0], -7, np.int32)
     capi.check(capi.load_library().vp_dbg_lsap(device_id, iou.ctypes.data, iou.shape[0], iou.shape[1], thr, out.ctypes.data))
