@@ -30,7 +30,7 @@ TOOLS_LIB = os.path.join(LIBDIR, 'libvitpose_hip_tools.so')
 SOURCES = ['gemm.hip', 'gemm8.hip', 'gemm8f.hip', 'qkvattn.hip', 'quant8.hip', 'attention.hip', 'elementwise.hip', 'decode.hip', 'boxes.hip', 'affine.hip', 'posenms.hip', 'draw.hip', 'label.hip', 'collect.hip', 'track.hip', 'smooth.hip', 'metrics.hip', 'cocoeval.hip', 'detect.hip', 'letterbox.hip', 'orient.hip', 'yolo.hip', 'simplehead.hip', 'fp8_probe.hip',
            'handle.hip', 'forward.hip', 'infer.hip', 'group.hip', 'weights.hip', 'tile_rules.hip', 'debug_taps.hip']
 TOOLS_SOURCES = SOURCES + ['probes.hip', 'tools_taps.hip']   # measurement code no plan can launch: probes, timing taps
-HEADERS = ['common.h', 'attn_core.h', 'kernels.h', 'tiles.h', 'dbg_util.h', 'gemm8_common.h', 'gemm8_epilogue.h', 'mx8.h', 'api_internal.h', 'boxgeom.h', 'posenms.h', 'pixfmt.h', 'drawgeom.h', 'labelgeom.h', 'collectgeom.h', 'sortgeom.h', 'eurogeom.h', 'metricsgeom.h', 'cocogeom.h', 'detgeom.h', 'lbgeom.h', 'orientgeom.h', 'yologeom.h', 'simpleheadgeom.h', 'hoststage.h', os.path.join('..', '..', 'include', 'vitpose_hip.h'),
+HEADERS = ['common.h', 'attn_core.h', 'kernels.h', 'tiles.h', 'dbg_util.h', 'gemm8_common.h', 'gemm8_epilogue.h', 'mx8.h', 'api_internal.h', 'boxgeom.h', 'posenms.h', 'pixfmt.h', 'drawgeom.h', 'labelgeom.h', 'collectgeom.h', 'sortgeom.h', 'eurogeom.h', 'metricsgeom.h', 'cocogeom.h', 'detgeom.h', 'lbgeom.h', 'orientgeom.h', 'yologeom.h', 'simpleheadgeom.h', 'hoststage.h', 'stageobj.h', os.path.join('..', '..', 'include', 'vitpose_hip.h'),
            os.path.join('..', '..', 'include', 'vitpose_hip_tools.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden',
          '-ffp-contract=fast', '-Wno-unused-result']

@@ -9,6 +9,8 @@
 //   metrics.hip      -- the accumulating accuracy-metrics stage (vp_metrics_*: an object of its own beside the handle, like the tracker and the smoother)
 //   simplehead.hip   -- the simple decoder's head (one kernel, simpleheadgeom.h), vp_head_kind and its two taps
 //   cocoeval.hip     -- the accumulating COCO keypoint AP / AR stage (vp_cocoeval_*: an object of its own beside the handle, like the metrics stage)
+//   hoststage.h      -- what the synchronous twins of every stage share: the scratch-block layout and HostStage (includes this header in its hipcc part)
+//   stageobj.h       -- what the six stage objects share: StageObj, stage_create / _destroy / _download / _reset, mask_check (includes this header in its hipcc part)
 // Everything here is library-internal (hidden visibility); nothing of it appears in the public headers.
 #pragma once
 #include <hip/hip_runtime.h>

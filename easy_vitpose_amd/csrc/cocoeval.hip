@@ -9,6 +9,7 @@
 // as one linear chain.
 #include "api_internal.h"
 #include "hoststage.h"
+#include "stageobj.h"
 #include "cocogeom.h"
 
 using namespace vpi;
@@ -459,11 +460,9 @@ __global__ __launch_bounds__(CE_THREADS) void coco_final_kernel(const char* __re
 
 }  // namespace vp
 
-struct vp_cocoeval {
-    vp_ctx* c = nullptr;
+struct vp_cocoeval : StageObj {
     int K = 0, max_records = 0;
-    char* mem = nullptr;     // device: state | vars double [K] | the workspace (CocoWs)
-    char* state = nullptr;
+    char* state = nullptr;   // device, one allocation: state | vars double [K] | the workspace (CocoWs)
     double* vars = nullptr;
     vp::CocoWs ws{};
     size_t state_bytes = 0;
@@ -683,69 +682,45 @@ int accumulate_enqueue(vp_cocoeval* e, char* d_out, hipStream_t q) {
 extern "C" {
 
 int vp_cocoeval_create(vp_handle c, const vp_cocoeval_cfg* cfg, const double* sigmas, vp_cocoeval_handle* out) {
-    if (!c || !out) return VP_ERR_INVALID;
-    *out = nullptr;
-    std::string why;
-    if (cfg_check(cfg, sigmas, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const int K = cfg->n_joints, M = cfg->max_records;
-    vp_cocoeval* e = new vp_cocoeval;
-    e->c = c;
-    e->K = K;
-    e->max_records = M;
-    e->state_bytes = vp::coco_state_bytes(M);
-    int pcap = vp::CE_SORT_LOCAL;
-    while (pcap < M) pcap <<= 1;
-    const int chunks = (M + vp::CE_CHUNK - 1) / vp::CE_CHUNK;
-    const size_t AT = vp::COCO_AT, RK = AT * vp::COCO_RECS;
-    const size_t sizes[] = {e->state_bytes, (size_t)K * 8, vp::COCO_MAX_FRAMES * 4, vp::COCO_MAX_FRAMES * sizeof(vp::CocoImg), (size_t)pcap * 8,
-                            (size_t)M * 8, (size_t)chunks * 2 * AT * 4, AT * chunks * 8, RK * 4, RK * 8, AT * 8};
-    StageLayout lay;
-    size_t off[11];
-    for (int i = 0; i < 11; ++i) off[i] = lay.part(sizes[i]);
-    const size_t bytes = lay.end;
-    std::vector<double> vars;
-    host_vars(sigmas, K, vars);
-    hipError_t err = hipMalloc((void**)&e->mem, bytes);
-    if (err == hipSuccess) err = hipMemset(e->mem, 0, bytes);
-    if (err == hipSuccess) err = hipMemcpy(e->mem + off[1], vars.data(), (size_t)K * 8, hipMemcpyHostToDevice);
-    if (err != hipSuccess) {
-        if (e->mem) (void)hipFree(e->mem);
-        delete e;
-        return fail(c, VP_ERR_HIP, std::string("cocoeval state: ") + hipGetErrorString(err));
-    }
-    e->state = e->mem;
-    e->vars = (double*)(e->mem + off[1]);
-    e->ws.kept = (int32_t*)(e->mem + off[2]);
-    e->ws.img = (vp::CocoImg*)(e->mem + off[3]);
-    e->ws.keys = (uint64_t*)(e->mem + off[4]);
-    e->ws.flags = (uint2*)(e->mem + off[5]);
-    e->ws.partial = (int32_t*)(e->mem + off[6]);
-    e->ws.chunkmax = (double*)(e->mem + off[7]);
-    e->ws.idx = (int32_t*)(e->mem + off[8]);
-    e->ws.pin = (double*)(e->mem + off[9]);
-    e->ws.lastrc = (double*)(e->mem + off[10]);
-    e->ws.chunks = chunks;
-    e->ws.pcap = pcap;
-    *out = e;
-    return VP_OK;
+    return stage_create(c, out, [&](vp_cocoeval*, std::string* why) { return cfg_check(cfg, sigmas, why); },
+                        [&](vp_cocoeval* e) {
+                            const int K = e->K = cfg->n_joints, M = e->max_records = cfg->max_records;
+                            e->state_bytes = vp::coco_state_bytes(M);
+                            int pcap = vp::CE_SORT_LOCAL;
+                            while (pcap < M) pcap <<= 1;
+                            const int chunks = (M + vp::CE_CHUNK - 1) / vp::CE_CHUNK;
+                            const size_t AT = vp::COCO_AT, RK = AT * vp::COCO_RECS;
+                            const size_t sizes[] = {e->state_bytes, (size_t)K * 8, vp::COCO_MAX_FRAMES * 4, vp::COCO_MAX_FRAMES * sizeof(vp::CocoImg), (size_t)pcap * 8,
+                                                    (size_t)M * 8, (size_t)chunks * 2 * AT * 4, AT * chunks * 8, RK * 4, RK * 8, AT * 8};
+                            StageLayout lay;
+                            size_t off[11];
+                            for (int i = 0; i < 11; ++i) off[i] = lay.part(sizes[i]);
+                            std::vector<double> vars;
+                            host_vars(sigmas, K, vars);
+                            char* mem = e->alloc(lay.end, 0);
+                            e->up(mem + off[1], vars.data(), (size_t)K * 8);
+                            e->state = mem;
+                            e->vars = (double*)(mem + off[1]);
+                            e->ws.kept = (int32_t*)(mem + off[2]);
+                            e->ws.img = (vp::CocoImg*)(mem + off[3]);
+                            e->ws.keys = (uint64_t*)(mem + off[4]);
+                            e->ws.flags = (uint2*)(mem + off[5]);
+                            e->ws.partial = (int32_t*)(mem + off[6]);
+                            e->ws.chunkmax = (double*)(mem + off[7]);
+                            e->ws.idx = (int32_t*)(mem + off[8]);
+                            e->ws.pin = (double*)(mem + off[9]);
+                            e->ws.lastrc = (double*)(mem + off[10]);
+                            e->ws.chunks = chunks;
+                            e->ws.pcap = pcap;
+                            return "cocoeval state: ";
+                        });
 }
 
-int vp_cocoeval_destroy(vp_cocoeval_handle e) {
-    if (!e) return VP_ERR_INVALID;
-    (void)hipSetDevice(e->c->cfg.device_id);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(e->mem);
-    delete e;
-    return VP_OK;
-}
+int vp_cocoeval_destroy(vp_cocoeval_handle e) { return stage_destroy(e); }
 
 int vp_cocoeval_reset_stream(vp_cocoeval_handle e, void* caller_stream) {
     if (!e) return VP_ERR_INVALID;
-    vp_ctx* c = e->c;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipMemsetAsync(e->state, 0, e->state_bytes, (hipStream_t)caller_stream));
-    return VP_OK;
+    return stage_reset(e, e->state, e->state_bytes, caller_stream);
 }
 
 int vp_cocoeval_update_stream(vp_cocoeval_handle e, const float* d_kpts, const float* d_score, const int32_t* d_frame, const int32_t* d_rank, int32_t n, const float* d_gt_kpts,
@@ -825,11 +800,7 @@ int vp_cocoeval_result_bytes(int64_t* bytes) {
 
 int vp_cocoeval_download_state(vp_cocoeval_handle e, void* out) {
     if (!e || !out) return VP_ERR_INVALID;
-    vp_ctx* c = e->c;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(out, e->state, e->state_bytes, hipMemcpyDeviceToHost));
-    return VP_OK;
+    return stage_download(e, out, e->state, e->state_bytes);
 }
 
 int vp_dbg_cocoeval_update_host(void* state, const vp_cocoeval_cfg* cfg, const double* sigmas, const float* kpts, const float* score, const int32_t* frame, const int32_t* rank,

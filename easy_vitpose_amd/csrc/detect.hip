@@ -4,12 +4,12 @@
 // the greedy NMS and re-zeroes the image's counters, det_pack_kernel, one thread per output row, packs the images' rows.  Every output is a pure function of the inputs.
 #include "api_internal.h"
 #include "hoststage.h"
+#include "stageobj.h"
 #include "detgeom.h"
 
 using namespace vpi;
 
-struct vp_detector {
-    vp_ctx* c = nullptr;
+struct vp_detector : StageObj {
     vp::DetParams p{};
     int max_anchors = 0, max_images = 0;
     vp::DetCand* cand = nullptr;    // device [max_images][DET_MAX_CAND]
@@ -411,41 +411,21 @@ int detect_enqueue(vp_detector* d, const void* d_pred, int A, const vp_det_image
 extern "C" {
 
 int vp_detector_create(vp_handle c, const vp_det_cfg* cfg, vp_detector_handle* out) {
-    if (!c || !out) return VP_ERR_INVALID;
-    *out = nullptr;
-    vp::DetParams p;
-    std::string why;
-    if (cfg_check(cfg, p, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    vp_detector* d = new vp_detector;
-    d->c = c;
-    d->p = p;
-    d->max_anchors = cfg->max_anchors;
-    d->max_images = cfg->max_images;
-    const size_t ni = (size_t)cfg->max_images, nd = (size_t)p.max_det;
-    hipError_t e = hipMalloc((void**)&d->cand, sizeof(vp::DetCand) * ni * vp::DET_MAX_CAND);
-    if (e == hipSuccess) e = hipMalloc((void**)&d->counters, ni * 8);
-    if (e == hipSuccess) e = hipMemset(d->counters, 0, ni * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&d->st_rows, ni * nd * 24);
-    if (e == hipSuccess) e = hipMalloc((void**)&d->st_anchor, ni * nd * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&d->st_n, ni * 8);
-    if (e != hipSuccess) {
-        (void)hipFree(d->cand); (void)hipFree(d->counters); (void)hipFree(d->st_rows); (void)hipFree(d->st_anchor); (void)hipFree(d->st_n);
-        delete d;
-        return fail(c, VP_ERR_HIP, std::string("detector workspace: ") + hipGetErrorString(e));
-    }
-    *out = d;
-    return VP_OK;
+    return stage_create(c, out, [&](vp_detector* d, std::string* why) { return cfg_check(cfg, d->p, why); },
+                        [&](vp_detector* d) {
+                            d->max_anchors = cfg->max_anchors;
+                            d->max_images = cfg->max_images;
+                            const size_t ni = (size_t)cfg->max_images, nd = (size_t)d->p.max_det;
+                            d->cand = d->alloc<vp::DetCand>(sizeof(vp::DetCand) * ni * vp::DET_MAX_CAND);
+                            d->counters = d->alloc<int32_t>(ni * 8, 0);
+                            d->st_rows = d->alloc<float>(ni * nd * 24);
+                            d->st_anchor = d->alloc<int32_t>(ni * nd * 4);
+                            d->st_n = d->alloc<int32_t>(ni * 8);
+                            return "detector workspace: ";
+                        });
 }
 
-int vp_detector_destroy(vp_detector_handle d) {
-    if (!d) return VP_ERR_INVALID;
-    (void)hipSetDevice(d->c->cfg.device_id);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(d->cand); (void)hipFree(d->counters); (void)hipFree(d->st_rows); (void)hipFree(d->st_anchor); (void)hipFree(d->st_n);
-    delete d;
-    return VP_OK;
-}
+int vp_detector_destroy(vp_detector_handle d) { return stage_destroy(d); }
 
 int vp_detect_stream(vp_detector_handle d, const void* d_pred, int32_t A, const vp_det_image* images, int32_t n_images, float* d_rows, int32_t* d_image, int32_t* d_anchor,
                      int32_t n_out, int32_t* d_count, int32_t* d_flags, void* caller_stream) {

@@ -5,6 +5,7 @@
 // workgroups: the state is a pure function of the inputs, bit for bit.
 #include "api_internal.h"
 #include "hoststage.h"
+#include "stageobj.h"
 #include "metricsgeom.h"
 
 using namespace vpi;
@@ -163,11 +164,9 @@ __global__ __launch_bounds__(MET_FIN_THREADS) void metrics_finish_kernel(Metrics
 
 }  // namespace vp
 
-struct vp_metrics {
-    vp_ctx* c = nullptr;
+struct vp_metrics : StageObj {
     vp::MetricsParams p{};
-    char* mem = nullptr;       // device: state | vars double [K] | the workspace of a call (MetricsWs) for METRICS_MAX_BLOCKS blocks
-    char* state = nullptr;
+    char* state = nullptr;     // device, one allocation: state | vars double [K] | the workspace of a call (MetricsWs) for METRICS_MAX_BLOCKS blocks
     double* vars = nullptr;
     vp::MetricsWs ws{};
     size_t state_bytes = 0;
@@ -311,56 +310,33 @@ int update_enqueue(vp_metrics* e, const float* d_pred, const float* d_gt, const 
 extern "C" {
 
 int vp_metrics_create(vp_handle c, const vp_metrics_cfg* cfg, const float* sigmas, vp_metrics_handle* out) {
-    if (!c || !out) return VP_ERR_INVALID;
-    *out = nullptr;
-    vp::MetricsParams p;
-    std::string why;
-    if (cfg_check(cfg, sigmas, p, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const int K = p.n_joints, C = vp::metrics_count_kinds(p), B = vp::METRICS_MAX_BLOCKS;
-    vp_metrics* e = new vp_metrics;
-    e->c = c;
-    e->p = p;
-    e->state_bytes = vp::metrics_state_words(K, p.n_pck, p.auc_steps) * 8;
-    StageLayout lay;   // state | vars | sums | counts | block headers
-    const size_t o_state = lay.part(e->state_bytes), o_vars = lay.part((size_t)K * 8), o_sums = lay.part((size_t)B * 2 * K * 8), o_cnt = lay.part((size_t)B * C * K * 4),
-                 o_hdr = lay.part((size_t)B * sizeof(vp::MetricsBlockHdr));
-    const size_t bytes = lay.end;
-    std::vector<double> vars((size_t)K, 1.0);
-    if (p.use_oks)
-        for (int j = 0; j < K; ++j) vars[j] = vp::nms_var(sigmas[j]);
-    hipError_t err = hipMalloc((void**)&e->mem, bytes);
-    if (err == hipSuccess) err = hipMemset(e->mem, 0, bytes);
-    if (err == hipSuccess) err = hipMemcpy(e->mem + o_vars, vars.data(), (size_t)K * 8, hipMemcpyHostToDevice);
-    if (err != hipSuccess) {
-        if (e->mem) (void)hipFree(e->mem);
-        delete e;
-        return fail(c, VP_ERR_HIP, std::string("metrics state: ") + hipGetErrorString(err));
-    }
-    e->state = e->mem + o_state;
-    e->vars = (double*)(e->mem + o_vars);
-    e->ws.sums = (double*)(e->mem + o_sums);
-    e->ws.cnt = (int32_t*)(e->mem + o_cnt);
-    e->ws.hdr = (vp::MetricsBlockHdr*)(e->mem + o_hdr);
-    *out = e;
-    return VP_OK;
+    return stage_create(c, out, [&](vp_metrics* e, std::string* why) { return cfg_check(cfg, sigmas, e->p, why); },
+                        [&](vp_metrics* e) {
+                            const vp::MetricsParams& p = e->p;
+                            const int K = p.n_joints, C = vp::metrics_count_kinds(p), B = vp::METRICS_MAX_BLOCKS;
+                            e->state_bytes = vp::metrics_state_words(K, p.n_pck, p.auc_steps) * 8;
+                            StageLayout lay;   // state | vars | sums | counts | block headers
+                            const size_t o_state = lay.part(e->state_bytes), o_vars = lay.part((size_t)K * 8), o_sums = lay.part((size_t)B * 2 * K * 8),
+                                         o_cnt = lay.part((size_t)B * C * K * 4), o_hdr = lay.part((size_t)B * sizeof(vp::MetricsBlockHdr));
+                            std::vector<double> vars((size_t)K, 1.0);
+                            if (p.use_oks)
+                                for (int j = 0; j < K; ++j) vars[j] = vp::nms_var(sigmas[j]);
+                            char* mem = e->alloc(lay.end, 0);
+                            e->up(mem + o_vars, vars.data(), (size_t)K * 8);
+                            e->state = mem + o_state;
+                            e->vars = (double*)(mem + o_vars);
+                            e->ws.sums = (double*)(mem + o_sums);
+                            e->ws.cnt = (int32_t*)(mem + o_cnt);
+                            e->ws.hdr = (vp::MetricsBlockHdr*)(mem + o_hdr);
+                            return "metrics state: ";
+                        });
 }
 
-int vp_metrics_destroy(vp_metrics_handle e) {
-    if (!e) return VP_ERR_INVALID;
-    (void)hipSetDevice(e->c->cfg.device_id);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(e->mem);
-    delete e;
-    return VP_OK;
-}
+int vp_metrics_destroy(vp_metrics_handle e) { return stage_destroy(e); }
 
 int vp_metrics_reset_stream(vp_metrics_handle e, void* caller_stream) {
     if (!e) return VP_ERR_INVALID;
-    vp_ctx* c = e->c;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipMemsetAsync(e->state, 0, e->state_bytes, (hipStream_t)caller_stream));
-    return VP_OK;
+    return stage_reset(e, e->state, e->state_bytes, caller_stream);
 }
 
 int vp_metrics_update_stream(vp_metrics_handle e, const float* d_pred, const float* d_gt, const float* d_norm, const float* d_area, const int32_t* d_rank, const int32_t* d_set,
@@ -426,11 +402,7 @@ int vp_metrics_state_bytes(const vp_metrics_cfg* cfg, int64_t* bytes) {
 
 int vp_metrics_download_state(vp_metrics_handle e, void* out) {
     if (!e || !out) return VP_ERR_INVALID;
-    vp_ctx* c = e->c;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(out, e->state, e->state_bytes, hipMemcpyDeviceToHost));
-    return VP_OK;
+    return stage_download(e, out, e->state, e->state_bytes);
 }
 
 int vp_dbg_metrics_host(void* state, const vp_metrics_cfg* cfg, const float* sigmas, const float* pred, const float* gt, const float* norm, const float* area, const int32_t* rank,

@@ -4,12 +4,12 @@
 // to at most one slot and every slot to at most one row of a call, so a call is bit-identical from run to run.
 #include "api_internal.h"
 #include "hoststage.h"
+#include "stageobj.h"
 #include "eurogeom.h"
 
 using namespace vpi;
 
-struct vp_smoother {
-    vp_ctx* c = nullptr;
+struct vp_smoother : StageObj {
     vp::EuroParams p{};
     char* state = nullptr;           // device: n_streams blobs (eurogeom.h) | slot_of_row int32 [max_rows] | gap_of_row int32 [max_rows]
     int32_t* slot_of_row = nullptr;
@@ -289,11 +289,6 @@ int cfg_check(const vp_smooth_cfg* cfg, vp::EuroParams& p, std::string* why) {
     return VP_OK;
 }
 
-int mask_check(uint64_t mask, int n_streams, std::string* why) {
-    if (n_streams < 64 && (mask >> n_streams)) { *why = "smoother: a mask bit beyond n_streams = " + std::to_string(n_streams); return VP_ERR_INVALID; }
-    return VP_OK;
-}
-
 int update_args(const vp::EuroParams& p, const void* kpts, const void* ids, int n, uint64_t step_mask, const double* t_e, const void* out, vp::EuroTe& te, std::string* why) {
     auto bad = [&](const std::string& m) { *why = "smoother: " + m; return (int)VP_ERR_INVALID; };
     if (n < 0) return bad("negative n");
@@ -305,10 +300,8 @@ int update_args(const vp::EuroParams& p, const void* kpts, const void* ids, int 
             if (!(t_e[s] - t_e[s] == 0.0 && t_e[s] > 0.0)) return bad("t_e[" + std::to_string(s) + "] not finite or <= 0");
             te.v[s] = t_e[s];
         }
-    return mask_check(step_mask, p.n_streams, why);
+    return mask_check(step_mask, p.n_streams, "smoother: ", why);
 }
-
-int popcount64(uint64_t m) { int n = 0; for (; m; m &= m - 1) ++n; return n; }
 
 // the checked call on stream q: two launches
 int update_enqueue(vp_smoother* s, const vp::EuroTe& te, const float* d_kpts, const int32_t* d_ids, const int32_t* d_stream, const int32_t* d_rank, int n, uint64_t step_mask,
@@ -334,49 +327,21 @@ int update_enqueue(vp_smoother* s, const vp::EuroTe& te, const float* d_kpts, co
 extern "C" {
 
 int vp_smoother_create(vp_handle c, const vp_smooth_cfg* cfg, vp_smoother_handle* out) {
-    if (!c || !out) return VP_ERR_INVALID;
-    *out = nullptr;
-    vp::EuroParams p;
-    std::string why;
-    if (cfg_check(cfg, p, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    vp_smoother* s = new vp_smoother;
-    s->c = c;
-    s->p = p;
-    s->state_bytes = vp::euro_stream_bytes(p.n_joints) * (size_t)p.n_streams;   // a multiple of 16
-    const size_t bytes = s->state_bytes + 2 * (size_t)p.max_rows * sizeof(int32_t);
-    hipError_t e = hipMalloc((void**)&s->state, bytes);
-    if (e == hipSuccess) e = hipMemset(s->state, 0, bytes);
-    if (e != hipSuccess) {
-        if (s->state) (void)hipFree(s->state);
-        delete s;
-        return fail(c, VP_ERR_HIP, std::string("smoother state: ") + hipGetErrorString(e));
-    }
-    s->slot_of_row = (int32_t*)(s->state + s->state_bytes);
-    s->gap_of_row = s->slot_of_row + p.max_rows;
-    *out = s;
-    return VP_OK;
+    return stage_create(c, out, [&](vp_smoother* s, std::string* why) { return cfg_check(cfg, s->p, why); },
+                        [](vp_smoother* s) {
+                            s->state_bytes = vp::euro_stream_bytes(s->p.n_joints) * (size_t)s->p.n_streams;   // a multiple of 16
+                            s->state = s->alloc(s->state_bytes + 2 * (size_t)s->p.max_rows * sizeof(int32_t), 0);
+                            s->slot_of_row = (int32_t*)(s->state + s->state_bytes);
+                            s->gap_of_row = s->slot_of_row + s->p.max_rows;
+                            return "smoother state: ";
+                        });
 }
 
-int vp_smoother_destroy(vp_smoother_handle s) {
-    if (!s) return VP_ERR_INVALID;
-    (void)hipSetDevice(s->c->cfg.device_id);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(s->state);
-    delete s;
-    return VP_OK;
-}
+int vp_smoother_destroy(vp_smoother_handle s) { return stage_destroy(s); }
 
 int vp_smoother_reset_stream(vp_smoother_handle s, uint64_t stream_mask, void* caller_stream) {
     if (!s) return VP_ERR_INVALID;
-    vp_ctx* c = s->c;
-    std::string why;
-    if (mask_check(stream_mask, s->p.n_streams, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    const size_t one = vp::euro_stream_bytes(s->p.n_joints);
-    for (int k = 0; k < s->p.n_streams; ++k)
-        if ((stream_mask >> k) & 1ull) HIPCHK(c, hipMemsetAsync(s->state + (size_t)k * one, 0, one, (hipStream_t)caller_stream));
-    return VP_OK;
+    return stage_reset_masked(s, s->state, vp::euro_stream_bytes(s->p.n_joints), s->p.n_streams, stream_mask, "smoother: ", caller_stream);
 }
 
 int vp_smooth_update_stream(vp_smoother_handle s, const float* d_kpts, const int32_t* d_ids, const int32_t* d_stream, const int32_t* d_rank, int32_t n, uint64_t step_mask,
@@ -429,11 +394,7 @@ int vp_smoother_state_bytes(const vp_smooth_cfg* cfg, int64_t* bytes) {
 
 int vp_smoother_download_state(vp_smoother_handle s, void* out) {
     if (!s || !out) return VP_ERR_INVALID;
-    vp_ctx* c = s->c;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(out, s->state, s->state_bytes, hipMemcpyDeviceToHost));
-    return VP_OK;
+    return stage_download(s, out, s->state, s->state_bytes);
 }
 
 int vp_dbg_smooth_host(void* state, const vp_smooth_cfg* cfg, const float* kpts, const int32_t* ids, const int32_t* stream, const int32_t* rank, int32_t n,

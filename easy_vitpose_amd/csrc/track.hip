@@ -3,12 +3,12 @@
 // track_gather_kernel, one workgroup.  vp_tracker_update_counted_stream is the same call with the detection count read from device memory.  No atomics, no flags between workgroups, every reduction in a fixed order: a call is bit-identical from run to run.
 #include "api_internal.h"
 #include "hoststage.h"
+#include "stageobj.h"
 #include "sortgeom.h"
 
 using namespace vpi;
 
-struct vp_tracker {
-    vp_ctx* c = nullptr;
+struct vp_tracker : StageObj {
     vp::TrkParams p{};
     vp::TrkStream* state = nullptr;   // device [n_streams]
 };
@@ -531,11 +531,6 @@ int cfg_check(const vp_track_cfg* cfg, vp::TrkParams& p, std::string* why) {
     return VP_OK;
 }
 
-int mask_check(uint64_t mask, int n_streams, std::string* why) {
-    if (n_streams < 64 && (mask >> n_streams)) { *why = "tracker: a mask bit beyond n_streams = " + std::to_string(n_streams); return VP_ERR_INVALID; }
-    return VP_OK;
-}
-
 int update_args(const vp::TrkParams& p, const void* dets, int row_stride, int n_dets, uint64_t step_mask, const void* rows, const void* ids, const void* stream, int n_out,
                 const void* count, std::string* why) {
     auto bad = [&](const std::string& m) { *why = "tracker: " + m; return (int)VP_ERR_INVALID; };
@@ -545,10 +540,8 @@ int update_args(const vp::TrkParams& p, const void* dets, int row_stride, int n_
     if (n_dets > 0 && !dets) return bad("null detections with n_dets > 0");
     if (!count) return bad("null count");
     if (n_out > 0 && !(rows && ids && stream)) return bad("null rows, ids or stream with n_out > 0");
-    return mask_check(step_mask, p.n_streams, why);
+    return mask_check(step_mask, p.n_streams, "tracker: ", why);
 }
-
-int popcount64(uint64_t m) { int n = 0; for (; m; m &= m - 1) ++n; return n; }
 
 // the checked call on stream s: two launches
 int update_enqueue(vp_tracker* t, const float* d_dets, int row_stride, const int32_t* d_fidx, int n_dets, const int32_t* d_n_dets, uint64_t step_mask, float* d_rows,
@@ -572,45 +565,18 @@ int update_enqueue(vp_tracker* t, const float* d_dets, int row_stride, const int
 extern "C" {
 
 int vp_tracker_create(vp_handle c, const vp_track_cfg* cfg, vp_tracker_handle* out) {
-    if (!c || !out) return VP_ERR_INVALID;
-    *out = nullptr;
-    vp::TrkParams p;
-    std::string why;
-    if (cfg_check(cfg, p, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    vp_tracker* t = new vp_tracker;
-    t->c = c;
-    t->p = p;
-    const size_t bytes = sizeof(vp::TrkStream) * (size_t)p.n_streams;
-    hipError_t e = hipMalloc((void**)&t->state, bytes);
-    if (e == hipSuccess) e = hipMemset(t->state, 0, bytes);
-    if (e != hipSuccess) {
-        if (t->state) (void)hipFree(t->state);
-        delete t;
-        return fail(c, VP_ERR_HIP, std::string("tracker state: ") + hipGetErrorString(e));
-    }
-    *out = t;
-    return VP_OK;
+    return stage_create(c, out, [&](vp_tracker* t, std::string* why) { return cfg_check(cfg, t->p, why); },
+                        [](vp_tracker* t) {
+                            t->state = t->alloc<vp::TrkStream>(sizeof(vp::TrkStream) * (size_t)t->p.n_streams, 0);
+                            return "tracker state: ";
+                        });
 }
 
-int vp_tracker_destroy(vp_tracker_handle t) {
-    if (!t) return VP_ERR_INVALID;
-    (void)hipSetDevice(t->c->cfg.device_id);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(t->state);
-    delete t;
-    return VP_OK;
-}
+int vp_tracker_destroy(vp_tracker_handle t) { return stage_destroy(t); }
 
 int vp_tracker_reset_stream(vp_tracker_handle t, uint64_t stream_mask, void* caller_stream) {
     if (!t) return VP_ERR_INVALID;
-    vp_ctx* c = t->c;
-    std::string why;
-    if (mask_check(stream_mask, t->p.n_streams, &why)) return fail(c, VP_ERR_INVALID, why);
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    for (int s = 0; s < t->p.n_streams; ++s)
-        if ((stream_mask >> s) & 1ull) HIPCHK(c, hipMemsetAsync(t->state + s, 0, sizeof(vp::TrkStream), (hipStream_t)caller_stream));
-    return VP_OK;
+    return stage_reset_masked(t, t->state, sizeof(vp::TrkStream), t->p.n_streams, stream_mask, "tracker: ", caller_stream);
 }
 
 int vp_tracker_update_stream(vp_tracker_handle t, const float* d_dets, int32_t row_stride, const int32_t* d_frame_idx, int32_t n_dets, uint64_t step_mask, float* d_rows,
@@ -671,11 +637,7 @@ int vp_tracker_state_bytes(int32_t n_streams, int64_t* bytes) {
 
 int vp_tracker_download_state(vp_tracker_handle t, void* out) {
     if (!t || !out) return VP_ERR_INVALID;
-    vp_ctx* c = t->c;
-    HIPCHK(c, hipSetDevice(c->cfg.device_id));
-    HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(out, t->state, sizeof(vp::TrkStream) * (size_t)t->p.n_streams, hipMemcpyDeviceToHost));
-    return VP_OK;
+    return stage_download(t, out, t->state, sizeof(vp::TrkStream) * (size_t)t->p.n_streams);
 }
 
 int vp_dbg_track_host(void* state, const vp_track_cfg* cfg, const float* dets, int32_t row_stride, const int32_t* frame_idx, int32_t n_dets, uint64_t step_mask,

@@ -4,13 +4,13 @@
 // A forward is the plan's launches in order on the caller's stream: no atomics, no allocation, no copy, no synchronisation.
 #include "api_internal.h"
 #include "hoststage.h"
+#include "stageobj.h"
 #include "common.h"
 #include "yologeom.h"
 
 using namespace vpi;
 
-struct vp_yolo {
-    vp_ctx* c = nullptr;
+struct vp_yolo : StageObj {
     vp_yolo_cfg cfg{};
     vp::YoloPlan plan;
     char* arena = nullptr;               // every internal buffer for max_images images, 256-byte aligned parts
@@ -375,46 +375,30 @@ size_t head_bytes(const vp_yolo* y, int n) { return (size_t)n * (4 + y->plan.d.n
 extern "C" {
 
 int vp_yolo_create(vp_handle c, const vp_yolo_cfg* cfg, const vp_yolo_tensor* tensors, int32_t n_tensors, vp_yolo_handle* out) {
-    if (!c || !out) return VP_ERR_INVALID;
-    *out = nullptr;
-    std::string why;
-    vp::YoloTensors tab;
-    vp_yolo* y = new vp_yolo;
     std::vector<uint16_t> w;
     std::vector<float> b;
-    int rc = make_plan(cfg, tensors, n_tensors, &tab, &y->plan, &why);
-    if (!rc) rc = fold_all(tab, y->plan, &w, &b, &why);
-    if (rc) { delete y; return fail(c, rc, why); }
-    y->c = c;
-    y->cfg = *cfg;
-    const YoloPlan& p = y->plan;
-    const size_t total = place_buffers(p, cfg->max_images, cfg->reserved[0] != 0, &y->buf_off);
-    hipError_t e = hipSetDevice(c->cfg.device_id);
-    if (e == hipSuccess) e = hipMalloc((void**)&y->arena, total);
-    if (e == hipSuccess) e = hipMemset(y->arena, 0xFF, total);
-    if (e == hipSuccess) e = hipMalloc((void**)&y->w, w.size() * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&y->b, b.size() * 4);
-    if (e == hipSuccess) e = hipMemcpy(y->w, w.data(), w.size() * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(y->b, b.data(), b.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void)hipFree(y->arena); (void)hipFree(y->w); (void)hipFree(y->b);
-        delete y;
-        return fail(c, VP_ERR_HIP, std::string("yolo: device memory (") + std::to_string(total) + " bytes of activations): " + hipGetErrorString(e));
-    }
-    y->device_bytes = total + w.size() * 2 + b.size() * 4;
-    *out = y;
-    return VP_OK;
+    return stage_create(c, out,
+                        [&](vp_yolo* y, std::string* why) {   // a bad plan or a failed fold: its own code and text
+                            vp::YoloTensors tab;
+                            int rc = make_plan(cfg, tensors, n_tensors, &tab, &y->plan, why);
+                            if (!rc) rc = fold_all(tab, y->plan, &w, &b, why);
+                            return rc;
+                        },
+                        [&](vp_yolo* y) {
+                            y->cfg = *cfg;
+                            const size_t total = place_buffers(y->plan, cfg->max_images, cfg->reserved[0] != 0, &y->buf_off);
+                            y->arena = y->alloc(total, 0xFF);
+                            y->w = y->alloc<_Float16>(w.size() * 2);
+                            y->b = y->alloc<float>(b.size() * 4);
+                            y->up(y->w, w.data(), w.size() * 2);
+                            y->up(y->b, b.data(), b.size() * 4);
+                            if (y->err == hipSuccess) y->err = hipDeviceSynchronize();
+                            y->device_bytes = total + w.size() * 2 + b.size() * 4;
+                            return std::string("yolo: device memory (") + std::to_string(total) + " bytes of activations): ";
+                        });
 }
 
-int vp_yolo_destroy(vp_yolo_handle y) {
-    if (!y) return VP_ERR_INVALID;
-    (void)hipSetDevice(y->c->cfg.device_id);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(y->arena); (void)hipFree(y->w); (void)hipFree(y->b);
-    delete y;
-    return VP_OK;
-}
+int vp_yolo_destroy(vp_yolo_handle y) { return stage_destroy(y); }
 
 int vp_yolo_info(vp_yolo_handle y, int32_t* nc, int32_t* A, int32_t* n_launches, int64_t* device_bytes) {
     if (!y) return VP_ERR_INVALID;

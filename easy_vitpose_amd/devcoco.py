@@ -19,6 +19,7 @@ import numbers
 import numpy as np
 
 from . import _capi as capi
+from ._stage import DeviceStage, check_tensor, handle_alias, ptr
 from .posenms import NMS_MAX_K
 
 MAX_ROWS, MAX_GTS, MAX_FRAMES, MAX_RECORDS = 8192, 8192, 256, 1 << 20
@@ -124,10 +125,6 @@ def _host_args(K, kpts, score, frame, rank, gt_kpts, gt_box, gt_area, gt_flags, 
         out.append(a)
     score, frame, rank, gt_box, gt_area, gt_flags, gt_frame = out
     return kpts, score, frame, rank, gt_kpts, gt_box, gt_area, gt_flags, gt_frame
-
-
-def _ptr(a):
-    return None if a is None or a.size == 0 else a.ctypes.data
 
 
 def _c_exp(v):
@@ -312,9 +309,9 @@ def cocoeval_tap(state: np.ndarray, cfg: CocoEvalCfg, kpts, score, frame=None, r
     c, sig = c_config(cfg)
     assert state.dtype == state_dtype(cfg) and state.flags.c_contiguous
     match = np.empty((len(kpts), 10), I32)
-    capi.check(capi.load_library().vp_dbg_cocoeval_update_host(state.ctypes.data, C.byref(c), sig.ctypes.data, _ptr(kpts), _ptr(score), _ptr(frame), _ptr(rank), len(kpts),
-                                                               _ptr(gt_kpts), _ptr(gt_box), _ptr(gt_area), _ptr(gt_flags), _ptr(gt_frame), len(gt_kpts), int(n_frames),
-                                                               _ptr(match)))
+    capi.check(capi.load_library().vp_dbg_cocoeval_update_host(state.ctypes.data, C.byref(c), sig.ctypes.data, ptr(kpts), ptr(score), ptr(frame), ptr(rank), len(kpts),
+                                                               ptr(gt_kpts), ptr(gt_box), ptr(gt_area), ptr(gt_flags), ptr(gt_frame), len(gt_kpts), int(n_frames),
+                                                               ptr(match)))
     return match
 
 
@@ -371,102 +368,78 @@ def finish(result: np.ndarray) -> CocoResult:
                       int(r['nonfinite']), tuple(int(v) for v in r['npig']))
 
 
-class DeviceCocoEval:
+class DeviceCocoEval(DeviceStage):
+    _destroy, _e = 'vp_cocoeval_destroy', handle_alias
+
     def __init__(self, engine, cfg: CocoEvalCfg):
+        super().__init__(engine)
         self.cfg = cfg
         self._c, self._sig = c_config(cfg)
-        self.engine, self.lib = engine, engine.lib
-        h = C.c_void_p()
-        capi.check(self.lib.vp_cocoeval_create(engine._h, C.byref(self._c), self._sig.ctypes.data, C.byref(h)), engine._h)
-        self._e = h
-
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(torch.device('cuda', self.engine.device_id)).cuda_stream
+        self._create(self.lib.vp_cocoeval_create, C.byref(self._c), self._sig.ctypes.data)
 
     def update(self, kpts, score, frame=None, rank=None, gt_kpts=None, gt_box=None, gt_area=None, gt_flags=None, gt_frame=None, n_frames: int = 1, match=None):
         """Adds one call on torch's current stream, no synchronisation.  Contiguous CUDA tensors: `kpts` float32 [n, K, 3], `score` float32 [n], `frame`, `rank` int32
         [n] or None; `gt_kpts` float32 [g, K, 3], `gt_box` float32 [g, 4], `gt_area` float32 [g], `gt_flags`, `gt_frame` int32 [g] or None (all None: no gt);
         `match` int32 [n, 10]: optional output."""
         import torch
-        dev = torch.device('cuda', self.engine.device_id)
-        K = self.cfg.n_joints
-
-        def chk(name, a, dtype, shape, needed=False):
-            if a is None and not needed:
-                return
-            if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == dtype):
-                raise TypeError(f'{name}: a {dtype} torch CUDA tensor expected')
-            if a.device != dev or tuple(a.shape) != shape or not a.is_contiguous():
-                raise ValueError(f'{name}: contiguous {list(shape)} on {dev} expected, got {tuple(a.shape)} on {a.device}')
+        dev, K = self._dev, self.cfg.n_joints
         if not (isinstance(kpts, torch.Tensor) and kpts.ndim == 3):
             raise TypeError('kpts: a float32 torch CUDA tensor [n, K, 3] expected')
         n = kpts.shape[0]
         g = 0 if gt_kpts is None else gt_kpts.shape[0]
-        chk('kpts', kpts, torch.float32, (n, K, 3), True)
-        chk('score', score, torch.float32, (n,), True)
-        chk('frame', frame, torch.int32, (n,))
-        chk('rank', rank, torch.int32, (n,))
-        chk('gt_kpts', gt_kpts, torch.float32, (g, K, 3), g > 0)
-        chk('gt_box', gt_box, torch.float32, (g, 4), g > 0)
-        chk('gt_area', gt_area, torch.float32, (g,), g > 0)
-        chk('gt_flags', gt_flags, torch.int32, (g,))
-        chk('gt_frame', gt_frame, torch.int32, (g,))
-        chk('match', match, torch.int32, (n, 10))
-        p = (lambda a, cnt: None if a is None or cnt == 0 else a.data_ptr())
-        capi.check(self.lib.vp_cocoeval_update_stream(self._e, p(kpts, n), p(score, n), p(frame, n), p(rank, n), n, p(gt_kpts, g), p(gt_box, g), p(gt_area, g),
-                                                      p(gt_flags, g), p(gt_frame, g), g, int(n_frames), p(match, n), self._stream()), self.engine._h)
+        check_tensor('kpts', kpts, torch.float32, (n, K, 3), dev, True)
+        check_tensor('score', score, torch.float32, (n,), dev, True)
+        check_tensor('frame', frame, torch.int32, (n,), dev)
+        check_tensor('rank', rank, torch.int32, (n,), dev)
+        check_tensor('gt_kpts', gt_kpts, torch.float32, (g, K, 3), dev, g > 0)
+        check_tensor('gt_box', gt_box, torch.float32, (g, 4), dev, g > 0)
+        check_tensor('gt_area', gt_area, torch.float32, (g,), dev, g > 0)
+        check_tensor('gt_flags', gt_flags, torch.int32, (g,), dev)
+        check_tensor('gt_frame', gt_frame, torch.int32, (g,), dev)
+        check_tensor('match', match, torch.int32, (n, 10), dev)
+        p = ptr
+        self._check(self.lib.vp_cocoeval_update_stream(self._obj, p(kpts, n), p(score, n), p(frame, n), p(rank, n), n, p(gt_kpts, g), p(gt_box, g), p(gt_area, g),
+                                                       p(gt_flags, g), p(gt_frame, g), g, int(n_frames), p(match, n), self._stream()))
 
     def update_host(self, kpts, score, frame=None, rank=None, gt_kpts=None, gt_box=None, gt_area=None, gt_flags=None, gt_frame=None, n_frames: int = 1) -> np.ndarray:
         """`update` on numpy arrays (vp_cocoeval_update: upload, the same kernels, download, synchronous) -> match [n, 10]"""
         kpts, score, frame, rank, gt_kpts, gt_box, gt_area, gt_flags, gt_frame = _host_args(self.cfg.n_joints, kpts, score, frame, rank, gt_kpts, gt_box, gt_area, gt_flags,
                                                                                             gt_frame)
         match = np.empty((len(kpts), 10), I32)
-        capi.check(self.lib.vp_cocoeval_update(self._e, _ptr(kpts), _ptr(score), _ptr(frame), _ptr(rank), len(kpts), _ptr(gt_kpts), _ptr(gt_box), _ptr(gt_area),
-                                               _ptr(gt_flags), _ptr(gt_frame), len(gt_kpts), int(n_frames), _ptr(match)), self.engine._h)
+        self._check(self.lib.vp_cocoeval_update(self._obj, ptr(kpts), ptr(score), ptr(frame), ptr(rank), len(kpts), ptr(gt_kpts), ptr(gt_box), ptr(gt_area),
+                                                ptr(gt_flags), ptr(gt_frame), len(gt_kpts), int(n_frames), ptr(match)))
         return match
 
     def accumulate(self, out=None):
         """the precision / recall tables of the state so far, on torch's current stream: a uint8 CUDA tensor of RESULT.itemsize bytes (`parse_result` reads it)"""
         import torch
-        dev = torch.device('cuda', self.engine.device_id)
+        dev = self._dev
         if out is None:
             out = torch.empty((RESULT.itemsize,), dtype=torch.uint8, device=dev)
         elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and out.numel() == RESULT.itemsize and out.is_contiguous()):
             raise ValueError(f'out: a contiguous uint8 tensor of {RESULT.itemsize} bytes on {dev} expected')
-        capi.check(self.lib.vp_cocoeval_accumulate_stream(self._e, out.data_ptr(), self._stream()), self.engine._h)
+        self._check(self.lib.vp_cocoeval_accumulate_stream(self._obj, out.data_ptr(), self._stream()))
         return out
 
     def accumulate_host(self) -> np.ndarray:
         """vp_cocoeval_accumulate: synchronous -> a RESULT scalar array"""
         res = np.zeros((), RESULT)
-        capi.check(self.lib.vp_cocoeval_accumulate(self._e, res.ctypes.data), self.engine._h)
+        self._check(self.lib.vp_cocoeval_accumulate(self._obj, res.ctypes.data))
         return res
 
     def reset(self):
         """zero the state on torch's current stream"""
-        capi.check(self.lib.vp_cocoeval_reset_stream(self._e, self._stream()), self.engine._h)
+        self._check(self.lib.vp_cocoeval_reset_stream(self._obj, self._stream()))
 
     def state(self) -> np.ndarray:
         """the device state as a state_dtype(cfg) scalar array (synchronous)"""
         out = new_state(self.cfg)
-        capi.check(self.lib.vp_cocoeval_download_state(self._e, out.ctypes.data), self.engine._h)
+        self._check(self.lib.vp_cocoeval_download_state(self._obj, out.ctypes.data))
         return out
 
     def result(self) -> CocoResult:
         """accumulate, one small download, the ten figures"""
         return finish(self.accumulate_host())
-
-    def close(self):
-        if getattr(self, '_e', None) and self.engine._h:
-            self.lib.vp_cocoeval_destroy(self._e)
-        self._e = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def parse_result(raw) -> np.ndarray:

@@ -13,6 +13,7 @@ import numbers
 import numpy as np
 
 from . import _capi as capi
+from ._stage import check_tensor, ptr, stream_of
 
 MAX_ROWS = 8192      # VP_COLLECT_MAX_ROWS
 MAX_FRAMES = 64      # VP_COLLECT_MAX_FRAMES
@@ -174,10 +175,6 @@ def frame_dicts(rec: Records, n_frames: int) -> "list[dict]":
     return out
 
 
-def _ptr(a):
-    return None if a is None or a.size == 0 else a.ctypes.data
-
-
 def _call_host(fn, handle, kpts, ids, frame, rank, status, score, crop_params, n_frames, max_records, out):
     kpts, ids, frame, rank, status, score, crop_params = _host_rows(kpts, ids, frame, rank, status, score, crop_params)
     n, K = kpts.shape[0], kpts.shape[1]
@@ -190,8 +187,8 @@ def _call_host(fn, handle, kpts, ids, frame, rank, status, score, crop_params, n
     if fresh:
         out[:] = 0
     stride = 1 if score is None or n < 2 else score.strides[0] // 4
-    args = (_ptr(kpts), n, K, _ptr(ids), _ptr(frame), _ptr(rank), _ptr(status), None if score is None or n == 0 else score.ctypes.data,
-            stride, _ptr(crop_params), int(n_frames), int(max_records), out.ctypes.data)
+    args = (ptr(kpts), n, K, ptr(ids), ptr(frame), ptr(rank), ptr(status), None if score is None or n == 0 else score.ctypes.data,
+            stride, ptr(crop_params), int(n_frames), int(max_records), out.ctypes.data)
     capi.check(fn(*args) if handle is None else fn(handle, *args), handle)
     return out if nbytes is None else out[:nbytes]
 
@@ -213,31 +210,23 @@ def collect_device(engine, kpts, ids=None, frame=None, rank=None, status=None, s
     """`VitPoseHip.collect`: vp_collect_stream on torch CUDA tensors on torch's current stream, no synchronisation.  Returns the uint8 device table."""
     import torch
     dev = torch.device('cuda', engine.device_id)
-
-    def want(t, name, dtype, shape_ok, what):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype):
-            raise TypeError(f'{name}: a {dtype} torch CUDA tensor expected')
-        if t.device != dev or not shape_ok(t):
-            raise ValueError(f'{name}: {what} on {dev} expected, got {tuple(t.shape)} on {t.device}')
-    want(kpts, 'kpts', torch.float32, lambda t: t.ndim == 3 and t.shape[2] == 3 and t.is_contiguous(), 'contiguous [n, K, 3]')
+    check_tensor('kpts', kpts, torch.float32, ('n', 'K', 3), dev, True)
     n, K = kpts.shape[0], kpts.shape[1]
     for t, name in ((ids, 'ids'), (frame, 'frame'), (rank, 'rank'), (status, 'status')):
-        if t is not None:
-            want(t, name, torch.int32, lambda t: tuple(t.shape) == (n,) and t.is_contiguous(), f'contiguous [{n}]')
-    if score is not None:
-        want(score, 'score', torch.float32, lambda t: tuple(t.shape) == (n,) and (n < 2 or t.stride(0) >= 1), f'[{n}] with a positive stride')
-    if crop_params is not None:
-        want(crop_params, 'crop_params', torch.int32, lambda t: tuple(t.shape) == (n, 9) and t.is_contiguous(), f'contiguous [{n}, 9]')
+        check_tensor(name, t, torch.int32, (n,), dev)
+    check_tensor('score', score, torch.float32, (n,), dev, contiguous=False)
+    check_tensor('crop_params', crop_params, torch.int32, (n, 9), dev)
     max_records = n if max_records is None else max_records
     _check_sizes(n, K, n_frames, max_records)
     nbytes = 4 * (header_words(n_frames) + max_records * record_words(K))
     if out is None:
         out = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     else:
-        want(out, 'out', torch.uint8, lambda t: t.ndim == 1 and t.is_contiguous() and t.numel() >= nbytes and t.data_ptr() % 16 == 0,
-             f'contiguous, 16-byte aligned, at least {nbytes} bytes')
-    p = (lambda a: None if a is None or n == 0 else a.data_ptr())
-    cs = torch.cuda.current_stream(dev).cuda_stream
+        check_tensor('out', out, torch.uint8, ('bytes',), dev, True)
+        if out.numel() < nbytes or out.data_ptr() % 16:
+            raise ValueError(f'out: contiguous, 16-byte aligned, at least {nbytes} bytes on {dev} expected, got {tuple(out.shape)} on {out.device}')
+    p = (lambda a: ptr(a, n))
+    cs = stream_of(dev)
     capi.check(engine.lib.vp_collect_stream(engine._h, p(kpts), n, K, p(ids), p(frame), p(rank), p(status), p(score), 1 if score is None or n < 2 else score.stride(0),
                                             p(crop_params), int(n_frames), int(max_records), out.data_ptr(), cs), engine._h)
     return out

@@ -18,6 +18,7 @@ import numbers
 import numpy as np
 
 from . import _capi as capi
+from ._stage import DeviceStage, check_tensor, handle_alias
 
 MAX_IMAGES = 64
 MAX_CLASSES = 256
@@ -180,13 +181,13 @@ class HostDetector:
         return out
 
 
-class DeviceDetector:
+class DeviceDetector(DeviceStage):
+    _destroy, _d = 'vp_detector_destroy', handle_alias
+
     def __init__(self, engine, cfg: DetectCfg = DetectCfg()):
+        super().__init__(engine)
         self.cfg, self._c = cfg, c_config(cfg)
-        self.engine, self.lib = engine, engine.lib
-        h = C.c_void_p()
-        capi.check(self.lib.vp_detector_create(engine._h, C.byref(self._c), C.byref(h)), engine._h)
-        self._d = h
+        self._create(self.lib.vp_detector_create, C.byref(self._c))
 
     def detect(self, pred, frames_hw, input_hw=None, n_out=None):
         """The head `pred` (a contiguous torch CUDA tensor of the configured dtype and layout, n images) on torch's current stream, no synchronisation.
@@ -195,12 +196,8 @@ class DeviceDetector:
         (x1, y1, x2, y2, score, class) in frame pixels, image int32 [n_out], anchor int32 [n_out], count int32 [n + 1], flags int32 [n]) device tensors;
         n_out defaults to n * max_det, which cuts nothing."""
         import torch
-        dev = torch.device('cuda', self.engine.device_id)
-        want = torch.float16 if self.cfg.dtype == 'fp16' else torch.float32
-        if not (isinstance(pred, torch.Tensor) and pred.is_cuda and pred.dtype == want):
-            raise TypeError(f'pred: a {self.cfg.dtype} torch CUDA tensor expected')
-        if pred.device != dev or not pred.is_contiguous():
-            raise ValueError(f'pred: a contiguous tensor on {dev} expected')
+        dev = self._dev
+        check_tensor('pred', pred, torch.float16 if self.cfg.dtype == 'fp16' else torch.float32, None, dev, True)
         n, A = _pred_shape(self.cfg, pred.shape)
         n_out = n * self.cfg.max_det if n_out is None else int(n_out)
         if n_out < 0:
@@ -210,9 +207,8 @@ class DeviceDetector:
         anchor = torch.empty((n_out,), dtype=torch.int32, device=dev)
         count = torch.empty((n + 1,), dtype=torch.int32, device=dev)
         flags = torch.empty((n,), dtype=torch.int32, device=dev)
-        cs = torch.cuda.current_stream(dev).cuda_stream
-        capi.check(self.lib.vp_detect_stream(self._d, pred.data_ptr() if n else None, A, image_table(frames_hw, input_hw, n), n, rows.data_ptr(), image.data_ptr(),
-                                             anchor.data_ptr(), n_out, count.data_ptr(), flags.data_ptr(), cs), self.engine._h)
+        self._check(self.lib.vp_detect_stream(self._obj, pred.data_ptr() if n else None, A, image_table(frames_hw, input_hw, n), n, rows.data_ptr(), image.data_ptr(),
+                                              anchor.data_ptr(), n_out, count.data_ptr(), flags.data_ptr(), self._stream()))
         return rows, image, anchor, count, flags
 
     def detect_host(self, pred, frames_hw, input_hw=None, n_out=None):
@@ -221,17 +217,6 @@ class DeviceDetector:
         n, A = _pred_shape(self.cfg, pred.shape)
         n_out = n * self.cfg.max_det if n_out is None else int(n_out)
         out = _host_out(max(n_out, 0), n)
-        capi.check(self.lib.vp_detect(self._d, pred.ctypes.data if n else None, A, image_table(frames_hw, input_hw, n), n, *[a.ctypes.data for a in out[:3]], n_out,
-                                      out[3].ctypes.data, out[4].ctypes.data), self.engine._h)
+        self._check(self.lib.vp_detect(self._obj, pred.ctypes.data if n else None, A, image_table(frames_hw, input_hw, n), n, *[a.ctypes.data for a in out[:3]], n_out,
+                                       out[3].ctypes.data, out[4].ctypes.data))
         return out
-
-    def close(self):
-        if getattr(self, '_d', None) and self.engine._h:
-            self.lib.vp_detector_destroy(self._d)
-        self._d = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

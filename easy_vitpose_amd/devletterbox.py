@@ -16,16 +16,15 @@ import dataclasses
 import numpy as np
 
 from . import _capi as capi
-from .cropprep import PIX_FORMATS, YUV_MATRIX_IDS, Frame, resize_linear_u8, to_rgb
+from ._stage import IMAGE_DTYPE, MAX_FRAMES as MAX_IMAGES, HandleStage, _images_ptr, device_frames, host_frames, image_table   # noqa: F401  (re-exported)
+from .cropprep import resize_linear_u8, to_rgb
 from .devdetect import _integer, letterbox_params
 
-MAX_IMAGES = 64
 MAX_SIDE = 8192
 DTYPES = {'fp32': 0, 'fp16': 1, 'u8': 2}                      # VP_LB_*
 NP_DTYPES = {'fp32': np.float32, 'fp16': np.float16, 'u8': np.uint8}
 LAYOUTS = {'nchw': 0, 'nhwc': 1}
 ORDERS = {'rgb': 0, 'bgr': 1}
-IMAGE_DTYPE = np.dtype([('plane', np.uint64, 2), ('pitch', np.int64, 2), ('h', np.int32), ('w', np.int32), ('format', np.int32), ('matrix', np.int32)])   # vp_image
 
 
 @dataclasses.dataclass(frozen=True)
@@ -74,26 +73,6 @@ def c_config(cfg: LetterboxCfg):
     if not isinstance(cfg, LetterboxCfg):
         raise TypeError(f'a LetterboxCfg expected, got {type(cfg).__name__}')
     return capi.vp_letterbox_cfg(cfg.input_hw[0], cfg.input_hw[1], DTYPES[cfg.dtype], LAYOUTS[cfg.layout], ORDERS[cfg.order], cfg.pad_value, int(cfg.scaleup))
-
-
-def _images_ptr(images: np.ndarray):
-    return C.cast(images.ctypes.data, C.POINTER(capi.vp_image)) if len(images) else None
-
-
-def image_table(frames) -> np.ndarray:
-    """the vp_image table of `Frame`s as a numpy record array (the frames keep the planes alive)"""
-    tab = np.zeros(len(frames), IMAGE_DTYPE)
-    for i, f in enumerate(frames):
-        if not isinstance(f, Frame):
-            raise TypeError(f'frame {i}: a Frame (Frame.nv12 / Frame.bgr / Frame.rgb) expected, got {type(f).__name__}')
-        p0, p1 = f.pointers()
-        tab[i] = ((p0, p1 or 0), f.pitch, f.h, f.w, PIX_FORMATS[f.format], YUV_MATRIX_IDS[f.matrix])
-    return tab
-
-
-def _check_count(n: int):
-    if n > MAX_IMAGES:
-        raise ValueError(f'letterbox: {n} frames, a call takes {MAX_IMAGES}')
 
 
 def letterbox_plan(frames_hw, cfg: LetterboxCfg):
@@ -152,15 +131,6 @@ def letterbox_host_numpy(frame, cfg: LetterboxCfg):
     return np.ascontiguousarray(out), np.array(undo + (w, h), np.float32), np.array((left, top, new_w, new_h), np.int32)
 
 
-def _host_frames(frames):
-    frames = [f if isinstance(f, Frame) else Frame.rgb(np.asarray(f)) for f in frames]
-    for i, f in enumerate(frames):
-        if f.on_device:
-            raise TypeError(f'frame {i}: host planes (numpy arrays) expected')
-    _check_count(len(frames))
-    return frames
-
-
 class HostLetterbox:
     """csrc/lbgeom.h run serially through the tap vp_dbg_letterbox_host: the model the device is tested against, never a fallback."""
 
@@ -170,7 +140,7 @@ class HostLetterbox:
 
     def letterbox(self, frames):
         """host `Frame`s -> (tensor ndarray, undo table float32 [n, 5], placement int32 [n, 4])"""
-        frames = _host_frames(frames)
+        frames = host_frames(frames, 'letterbox')
         n = len(frames)
         images = image_table(frames)
         out = np.empty(self.cfg.shape(n), NP_DTYPES[self.cfg.dtype])
@@ -180,19 +150,14 @@ class HostLetterbox:
         return out, det, placement
 
 
-class DeviceLetterbox:
+class DeviceLetterbox(HandleStage):
     def __init__(self, engine, cfg: LetterboxCfg = LetterboxCfg()):
+        super().__init__(engine)
         self.cfg, self._c = cfg, c_config(cfg)
-        self.engine, self.lib = engine, engine.lib
 
     def _torch_dtype(self):
         import torch
         return {'fp32': torch.float32, 'fp16': torch.float16, 'u8': torch.uint8}[self.cfg.dtype]
-
-    def upload(self, img):
-        """a host uint8 [H, W, 3] RGB array as a device `Frame`"""
-        import torch
-        return Frame.rgb(torch.from_numpy(np.ascontiguousarray(img)).to(torch.device('cuda', self.engine.device_id)))
 
     def letterbox(self, frames, out=None, stream=None):
         """`frames`: `Frame.nv12 / Frame.bgr / Frame.rgb` over torch CUDA planes of the handle's device (a bare uint8 CUDA tensor [H, W, 3] is RGB), read in place.
@@ -200,16 +165,9 @@ class DeviceLetterbox:
         shape to write into (it may be a view whose start is aligned to its element only); None allocates one.  Returns (tensor, undo table float32 [n, 5] -- what
         `DeviceDetector.detect(pred, table)` takes --, placement int32 [n, 4]); the two tables are host arrays, known when the call returns."""
         import torch
-        dev = torch.device('cuda', self.engine.device_id)
-        frames = [f if isinstance(f, Frame) else Frame.rgb(f) for f in frames]
+        dev = self._dev
+        frames = device_frames(frames, dev, 'letterbox')
         n = len(frames)
-        _check_count(n)
-        for i, f in enumerate(frames):
-            if not f.on_device:
-                raise TypeError(f'frame {i}: torch uint8 CUDA tensors expected')
-            for p in f.planes:
-                if p.device != dev:
-                    raise ValueError(f'frame {i} lives on {p.device}, the handle on {dev}')
         shape = self.cfg.shape(n)
         if out is None:
             out = torch.empty(shape, dtype=self._torch_dtype(), device=dev)
@@ -217,20 +175,19 @@ class DeviceLetterbox:
             raise TypeError(f'out: a {self.cfg.dtype} torch CUDA tensor expected')
         elif out.device != dev or not out.is_contiguous() or tuple(out.shape) != shape:
             raise ValueError(f'out: a contiguous tensor of shape {shape} on {dev} expected, got {tuple(out.shape)} on {out.device}')
-        cs = (torch.cuda.current_stream(dev) if stream is None else stream).cuda_stream
         images = image_table(frames)
         det, placement = np.empty((n, 5), np.float32), np.empty((n, 4), np.int32)
-        capi.check(self.lib.vp_letterbox_stream(self.engine._h, C.byref(self._c), _images_ptr(images), n, out.data_ptr() if n else None,
-                                                C.cast(det.ctypes.data, C.POINTER(capi.vp_det_image)), placement.ctypes.data, cs), self.engine._h)
+        self._check(self.lib.vp_letterbox_stream(self.engine._h, C.byref(self._c), _images_ptr(images), n, out.data_ptr() if n else None,
+                                                 C.cast(det.ctypes.data, C.POINTER(capi.vp_det_image)), placement.ctypes.data, self._stream(stream)))
         return out, det, placement
 
     def letterbox_host(self, frames):
         """`letterbox` on host `Frame`s (vp_letterbox: upload, the same kernel, download, synchronous) -> (ndarray, table, placement)"""
-        frames = _host_frames(frames)
+        frames = host_frames(frames, 'letterbox')
         n = len(frames)
         images = image_table(frames)
         out = np.empty(self.cfg.shape(n), NP_DTYPES[self.cfg.dtype])
         det, placement = np.empty((n, 5), np.float32), np.empty((n, 4), np.int32)
-        capi.check(self.lib.vp_letterbox(self.engine._h, C.byref(self._c), _images_ptr(images), n, out.ctypes.data if n else None,
-                                         C.cast(det.ctypes.data, C.POINTER(capi.vp_det_image)), placement.ctypes.data), self.engine._h)
+        self._check(self.lib.vp_letterbox(self.engine._h, C.byref(self._c), _images_ptr(images), n, out.ctypes.data if n else None,
+                                          C.cast(det.ctypes.data, C.POINTER(capi.vp_det_image)), placement.ctypes.data))
         return out, det, placement

@@ -16,6 +16,7 @@ import numbers
 import numpy as np
 
 from . import _capi as capi
+from ._stage import DeviceStage, check_tensor, handle_alias, ptr
 from .posenms import COCO17_SIGMAS, NMS_MAX_K
 
 MAX_ROWS = 8192
@@ -126,10 +127,6 @@ def _host_args(K, pred, gt, norm, area, rank, set_):
     return (pred, gt, *out)
 
 
-def _ptr(a):
-    return None if a is None or a.size == 0 else a.ctypes.data
-
-
 _exp = np.frompyfunc(math.exp, 1, 1)   # the C library's exp, element by element: what the host tap calls (numpy's own exp is another implementation)
 
 
@@ -234,8 +231,8 @@ def metrics_tap(state: np.ndarray, cfg: MetricsCfg, pred, gt, norm=None, area=No
     assert state.dtype == state_dtype(cfg) and state.flags.c_contiguous
     dist = np.empty((n, K), F32) if dist is None else dist
     oks = np.empty(n, F32) if oks is None else oks
-    capi.check(capi.load_library().vp_dbg_metrics_host(state.ctypes.data, C.byref(c), _ptr(sig), _ptr(pred), _ptr(gt), _ptr(norm), _ptr(area), _ptr(rank), _ptr(set_),
-                                                       int(set_value), n, _ptr(dist), _ptr(oks)))
+    capi.check(capi.load_library().vp_dbg_metrics_host(state.ctypes.data, C.byref(c), ptr(sig), ptr(pred), ptr(gt), ptr(norm), ptr(area), ptr(rank), ptr(set_),
+                                                       int(set_value), n, ptr(dist), ptr(oks)))
     return dist, oks
 
 
@@ -290,89 +287,63 @@ def parse_state(raw, cfg: MetricsCfg) -> np.ndarray:
     return np.frombuffer(np.ascontiguousarray(raw, dtype=np.uint8).tobytes(), dtype=state_dtype(cfg))[0].copy().reshape(())
 
 
-class DeviceMetrics:
+class DeviceMetrics(DeviceStage):
+    _destroy, _m = 'vp_metrics_destroy', handle_alias
+
     def __init__(self, engine, cfg: MetricsCfg):
+        super().__init__(engine)
         self.cfg = cfg
         self._c, self._sig = c_config(cfg)
-        self.engine, self.lib = engine, engine.lib
         self.nbytes = state_dtype(cfg).itemsize
-        h = C.c_void_p()
-        capi.check(self.lib.vp_metrics_create(engine._h, C.byref(self._c), _ptr(self._sig), C.byref(h)), engine._h)
-        self._m = h
-
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(torch.device('cuda', self.engine.device_id)).cuda_stream
+        self._create(self.lib.vp_metrics_create, C.byref(self._c), ptr(self._sig))
 
     def update(self, pred, gt, norm=None, area=None, rank=None, set=None, set_value=0, dist=None, oks=None):
         """Adds one call on torch's current stream, no synchronisation.  `pred`, `gt`: float32 CUDA [n, K, 3], contiguous; `norm` float32 CUDA [n, 2], `area`
         float32 CUDA [n], `rank`, `set` int32 CUDA [n], each or None; `dist` float32 CUDA [n, K] and `oks` float32 CUDA [n]: optional outputs."""
         import torch
-        dev = torch.device('cuda', self.engine.device_id)
-        K = self.cfg.n_joints
-
-        def chk(name, a, dtype, shape, needed=False):
-            if a is None and not needed:
-                return
-            if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == dtype):
-                raise TypeError(f'{name}: a {dtype} torch CUDA tensor expected')
-            if a.device != dev or tuple(a.shape) != shape or not a.is_contiguous():
-                raise ValueError(f'{name}: contiguous {list(shape)} on {dev} expected, got {tuple(a.shape)} on {a.device}')
+        dev, K = self._dev, self.cfg.n_joints
         if not (isinstance(pred, torch.Tensor) and pred.ndim == 3):
             raise TypeError('pred: a float32 torch CUDA tensor [n, K, 3] expected')
         n = pred.shape[0]
-        chk('pred', pred, torch.float32, (n, K, 3), True)
-        chk('gt', gt, torch.float32, (n, K, 3), True)
-        chk('norm', norm, torch.float32, (n, 2))
-        chk('area', area, torch.float32, (n,))
-        chk('rank', rank, torch.int32, (n,))
-        chk('set', set, torch.int32, (n,))
-        chk('dist', dist, torch.float32, (n, K))
-        chk('oks', oks, torch.float32, (n,))
-        p = (lambda a: None if a is None or n == 0 else a.data_ptr())
-        capi.check(self.lib.vp_metrics_update_stream(self._m, p(pred), p(gt), p(norm), p(area), p(rank), p(set), int(set_value), n, p(dist), p(oks), self._stream()),
-                   self.engine._h)
+        check_tensor('pred', pred, torch.float32, (n, K, 3), dev, True)
+        check_tensor('gt', gt, torch.float32, (n, K, 3), dev, True)
+        check_tensor('norm', norm, torch.float32, (n, 2), dev)
+        check_tensor('area', area, torch.float32, (n,), dev)
+        check_tensor('rank', rank, torch.int32, (n,), dev)
+        check_tensor('set', set, torch.int32, (n,), dev)
+        check_tensor('dist', dist, torch.float32, (n, K), dev)
+        check_tensor('oks', oks, torch.float32, (n,), dev)
+        p = (lambda a: ptr(a, n))
+        self._check(self.lib.vp_metrics_update_stream(self._obj, p(pred), p(gt), p(norm), p(area), p(rank), p(set), int(set_value), n, p(dist), p(oks), self._stream()))
 
     def update_host(self, pred, gt, norm=None, area=None, rank=None, set=None, set_value=0):
         """`update` on numpy arrays (vp_metrics_update: upload, the same kernels, download, synchronous) -> (dist, oks)"""
         pred, gt, norm, area, rank, set_ = _host_args(self.cfg.n_joints, pred, gt, norm, area, rank, set)
         n = len(pred)
         dist, oks = np.empty((n, self.cfg.n_joints), F32), np.empty(n, F32)
-        capi.check(self.lib.vp_metrics_update(self._m, _ptr(pred), _ptr(gt), _ptr(norm), _ptr(area), _ptr(rank), _ptr(set_), int(set_value), n, _ptr(dist), _ptr(oks)),
-                   self.engine._h)
+        self._check(self.lib.vp_metrics_update(self._obj, ptr(pred), ptr(gt), ptr(norm), ptr(area), ptr(rank), ptr(set_), int(set_value), n, ptr(dist), ptr(oks)))
         return dist, oks
 
     def reset(self):
         """zero the state on torch's current stream"""
-        capi.check(self.lib.vp_metrics_reset_stream(self._m, self._stream()), self.engine._h)
+        self._check(self.lib.vp_metrics_reset_stream(self._obj, self._stream()))
 
     def snapshot(self, out=None):
         """a stream-ordered device copy of the state on torch's current stream: a uint8 CUDA tensor of the state's size (`parse_state` reads it on the host)"""
         import torch
-        dev = torch.device('cuda', self.engine.device_id)
+        dev = self._dev
         if out is None:
             out = torch.empty((self.nbytes,), dtype=torch.uint8, device=dev)
         elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.device == dev and out.numel() == self.nbytes and out.is_contiguous()):
             raise ValueError(f'out: a contiguous uint8 tensor of {self.nbytes} bytes on {dev} expected')
-        capi.check(self.lib.vp_metrics_snapshot_stream(self._m, out.data_ptr(), self._stream()), self.engine._h)
+        self._check(self.lib.vp_metrics_snapshot_stream(self._obj, out.data_ptr(), self._stream()))
         return out
 
     def state(self) -> np.ndarray:
         """the device state as a state_dtype(cfg) scalar array (synchronous)"""
         out = new_state(self.cfg)
-        capi.check(self.lib.vp_metrics_download_state(self._m, out.ctypes.data), self.engine._h)
+        self._check(self.lib.vp_metrics_download_state(self._obj, out.ctypes.data))
         return out
 
     def result(self) -> MetricsResult:
         return finish(self.state(), self.cfg)
-
-    def close(self):
-        if getattr(self, '_m', None) and self.engine._h:
-            self.lib.vp_metrics_destroy(self._m)
-        self._m = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

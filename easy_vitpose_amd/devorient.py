@@ -21,10 +21,9 @@ import ctypes as C
 import numpy as np
 
 from . import _capi as capi
-from .cropprep import Frame
-from .devletterbox import _images_ptr, image_table
+from ._stage import IMAGE_DTYPE, MAX_FRAMES as MAX_IMAGES, HandleStage, check_count, _images_ptr, device_frames, frame_on, host_frames, image_table
+from .cropprep import PIX_FORMATS, Frame
 
-MAX_IMAGES = 64
 ORIENT_CODES = {'identity': 1, 'mirror': 2, 'rot180': 3, 'flip': 4, 'transpose': 5, 'cw90': 6, 'transverse': 7, 'ccw90': 8}   # VP_ORIENT_*: the EXIF values
 _ROTATE = {0: 1, 90: 8, 180: 3, 270: 6}
 INVERSE = {1: 1, 2: 2, 3: 3, 4: 4, 5: 5, 6: 8, 7: 7, 8: 6}   # orient(orient(f, c), INVERSE[c]) == f
@@ -101,20 +100,6 @@ def _codes(codes, n: int) -> np.ndarray:
     return np.array([check_code(c, i) for i, c in enumerate(codes)], dtype=np.int32).reshape(n)
 
 
-def _check_count(n: int):
-    if n > MAX_IMAGES:
-        raise ValueError(f'orient: {n} frames, a call takes {MAX_IMAGES}')
-
-
-def _frames(frames, on_device: bool):
-    frames = [f if isinstance(f, Frame) else Frame.rgb(f if on_device else np.asarray(f)) for f in frames]
-    _check_count(len(frames))
-    for i, f in enumerate(frames):
-        if f.on_device != on_device:
-            raise TypeError(f'frame {i}: ' + ('torch uint8 CUDA tensors expected' if on_device else 'host planes (numpy arrays) expected'))
-    return frames
-
-
 def _plane_shapes(fmt: str, h: int, w: int):
     return ((h, w), ((h + 1) // 2, (w + 1) // 2, 2)) if fmt == 'nv12' else ((h, w, 3),)
 
@@ -142,11 +127,9 @@ def _out_frames(frames, codes, out, on_device: bool, alloc):
 def orient_plan(frames_hw, codes, fmt: str = 'rgb', pitch=None):
     """vp_orient_plan (host only) for frames of `frames_hw` = (h, w) or [n, 2] of one format: (sizes int32 [n, 2] = (h, w), pitches int64 [n, 2], plane bytes
     int64 [n, 2]) of the destination frames.  `pitch` [n, 2] (or None): the destination pitches to keep where non-zero."""
-    from .cropprep import PIX_FORMATS
-    from .devletterbox import IMAGE_DTYPE
     hw = np.asarray(frames_hw, dtype=np.int64).reshape(-1, 2)
     n = len(hw)
-    _check_count(n)
+    check_count(n, 'orient')
     codes = _codes(codes, n)
     src, dst = np.zeros(n, IMAGE_DTYPE), np.zeros(n, IMAGE_DTYPE)
     src['h'], src['w'], src['format'] = hw[:, 0], hw[:, 1], PIX_FORMATS[fmt]
@@ -168,7 +151,7 @@ class HostOrient:
 
     def orient(self, frames, codes, out=None):
         """host `Frame`s and one code each (or one for all) -> the oriented host `Frame`s (`out`, possibly pitched views, or tight new ones)"""
-        frames = _frames(frames, False)
+        frames = host_frames(frames, 'orient')
         n = len(frames)
         codes = _codes(codes, n)
         out = _out_frames(frames, codes, out, False, lambda s: np.empty(s, np.uint8))
@@ -177,42 +160,30 @@ class HostOrient:
         return out
 
 
-class DeviceOrient:
-    def __init__(self, engine):
-        self.engine, self.lib = engine, engine.lib
-
-    def upload(self, img):
-        """a host uint8 [H, W, 3] RGB array as a device `Frame`"""
-        import torch
-        return Frame.rgb(torch.from_numpy(np.ascontiguousarray(img)).to(torch.device('cuda', self.engine.device_id)))
-
+class DeviceOrient(HandleStage):
     def orient(self, frames, codes, out=None, stream=None):
         """`frames`: `Frame.nv12 / Frame.bgr / Frame.rgb` over torch CUDA planes of the handle's device (a bare uint8 CUDA tensor [H, W, 3] is RGB), read in place;
         `codes`: one orientation code per frame, or one for all.  Enqueues on `stream` (a torch stream; None: torch's current stream) and never synchronises.
         `out`: the destination `Frame`s (possibly pitched views into larger buffers: no byte outside their rows is touched); None allocates tight planes.  Returns
         the upright `Frame`s, which `letterbox`, `infer_boxes`, `infer_frames`, `draw_poses` and `draw_labels` take as they are."""
         import torch
-        dev = torch.device('cuda', self.engine.device_id)
-        frames = _frames(frames, True)
+        dev = self._dev
+        frames = device_frames(frames, dev, 'orient')
         n = len(frames)
         codes = _codes(codes, n)
         out = _out_frames(frames, codes, out, True, lambda s: torch.empty(s, dtype=torch.uint8, device=dev))
-        for what, fs in (('frame', frames), ('out', out)):
-            for i, f in enumerate(fs):
-                for p in f.planes:
-                    if p.device != dev:
-                        raise ValueError(f'{what} {i} lives on {p.device}, the handle on {dev}')
-        cs = (torch.cuda.current_stream(dev) if stream is None else stream).cuda_stream
+        for i, f in enumerate(out):
+            frame_on(f, i, dev, 'out')
         src, dst = image_table(frames), image_table(out)
-        capi.check(self.lib.vp_orient_stream(self.engine._h, _images_ptr(src), codes.ctypes.data if n else None, _images_ptr(dst), n, cs), self.engine._h)
+        self._check(self.lib.vp_orient_stream(self.engine._h, _images_ptr(src), codes.ctypes.data if n else None, _images_ptr(dst), n, self._stream(stream)))
         return out
 
     def orient_host(self, frames, codes, out=None):
         """`orient` on host `Frame`s (vp_orient: upload, the same kernel, download of the destination rows, synchronous) -> host `Frame`s"""
-        frames = _frames(frames, False)
+        frames = host_frames(frames, 'orient')
         n = len(frames)
         codes = _codes(codes, n)
         out = _out_frames(frames, codes, out, False, lambda s: np.empty(s, np.uint8))
         src, dst = image_table(frames), image_table(out)
-        capi.check(self.lib.vp_orient(self.engine._h, _images_ptr(src), codes.ctypes.data if n else None, _images_ptr(dst), n), self.engine._h)
+        self._check(self.lib.vp_orient(self.engine._h, _images_ptr(src), codes.ctypes.data if n else None, _images_ptr(dst), n))
         return out

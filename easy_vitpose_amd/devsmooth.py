@@ -15,6 +15,7 @@ import numbers
 import numpy as np
 
 from . import _capi as capi
+from ._stage import DeviceStage, check_tensor, handle_alias, ptr
 from .devtracker import TRACK_MAX_STREAMS, mask_of
 from .smooth import FLAG_BAD_ROW, FLAG_DUP, FLAG_FULL, MISSING, SLOTS   # noqa: F401  (re-exported)
 
@@ -117,10 +118,6 @@ def _te(t_e, n_streams):
     return np.ascontiguousarray(np.broadcast_to(np.asarray(t_e, dtype=np.float64), (n_streams,)))
 
 
-def _ptr(a):
-    return None if a is None or a.size == 0 else a.ctypes.data
-
-
 class HostSmoother:
     """csrc/eurogeom.h on a host state blob through the tap vp_dbg_smooth_host: the model the device is tested against, never a fallback."""
 
@@ -141,77 +138,55 @@ class HostSmoother:
     def update(self, kpts, ids, stream=None, rank=None, t_e=None, step_mask=None):
         kpts, ids, stream, rank, te = _host_args(self.K, self.cfg.n_streams, kpts, ids, stream, rank, t_e)
         out, flags = np.empty_like(kpts), np.empty(self.cfg.n_streams, np.int32)
-        capi.check(self.lib.vp_dbg_smooth_host(self.blob.ctypes.data, C.byref(self._c), _ptr(kpts), _ptr(ids), _ptr(stream), _ptr(rank), len(ids),
-                                               mask_of(step_mask, self.cfg.n_streams), _ptr(te), _ptr(out), flags.ctypes.data))
+        capi.check(self.lib.vp_dbg_smooth_host(self.blob.ctypes.data, C.byref(self._c), ptr(kpts), ptr(ids), ptr(stream), ptr(rank), len(ids),
+                                               mask_of(step_mask, self.cfg.n_streams), ptr(te), ptr(out), flags.ctypes.data))
         return out, flags
 
 
-class DeviceSmoother:
+class DeviceSmoother(DeviceStage):
+    _destroy, _s = 'vp_smoother_destroy', handle_alias
+
     def __init__(self, engine, n_joints: "int | None" = None, cfg: SmoothCfg = SmoothCfg()):
+        super().__init__(engine)
         self.K = int(engine.K if n_joints is None else n_joints)
         self.cfg, self._c = cfg, c_config(cfg, self.K)
-        self.engine, self.lib = engine, engine.lib
-        h = C.c_void_p()
-        capi.check(self.lib.vp_smoother_create(engine._h, C.byref(self._c), C.byref(h)), engine._h)
-        self._s = h
+        self._create(self.lib.vp_smoother_create, C.byref(self._c))
 
     def update(self, kpts, ids, stream=None, rank=None, t_e=None, step_mask=None, out=None):
         """One step of the streams in `step_mask` (None: all) on torch's current stream, no synchronisation.  `kpts`: float32 CUDA [n, K, 3] rows of
         (y, x, conf), contiguous; `ids`, `stream` (None: stream 0), `rank` (None: none): int32 CUDA [n]; `t_e`: None (1.0), a number or one per stream (host);
         `out`: None (a new tensor), or a tensor like `kpts` -- `kpts` itself filters in place.  Returns (out, flags int32 [n_streams]) device tensors."""
         import torch
-        dev = torch.device('cuda', self.engine.device_id)
-        if not (isinstance(kpts, torch.Tensor) and kpts.is_cuda and kpts.dtype == torch.float32):
-            raise TypeError('kpts: a float32 torch CUDA tensor expected')
-        if kpts.device != dev or kpts.ndim != 3 or tuple(kpts.shape[1:]) != (self.K, 3) or not kpts.is_contiguous():
-            raise ValueError(f'kpts: contiguous [n, {self.K}, 3] on {dev} expected, got {tuple(kpts.shape)} on {kpts.device}')
+        dev = self._dev
+        check_tensor('kpts', kpts, torch.float32, ('n', self.K, 3), dev, True)
         n = kpts.shape[0]
-        for name, a, needed in (('ids', ids, True), ('stream', stream, False), ('rank', rank, False)):
-            if a is None and not needed:
-                continue
-            if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.int32):
-                raise TypeError(f'{name}: an int32 torch CUDA tensor expected')
-            if a.device != dev or tuple(a.shape) != (n,) or not a.is_contiguous():
-                raise ValueError(f'{name}: contiguous [{n}] on {dev} expected')
+        check_tensor('ids', ids, torch.int32, (n,), dev, True)
+        check_tensor('stream', stream, torch.int32, (n,), dev)
+        check_tensor('rank', rank, torch.int32, (n,), dev)
         if out is None:
             out = torch.empty_like(kpts)
         elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == dev and out.shape == kpts.shape and out.is_contiguous()):
             raise ValueError(f'out: a contiguous float32 tensor like kpts on {dev} expected')
         te = _te(t_e, self.cfg.n_streams)
         flags = torch.empty((self.cfg.n_streams,), dtype=torch.int32, device=dev)
-        cs = torch.cuda.current_stream(dev).cuda_stream
-        p = (lambda a: None if a is None or n == 0 else a.data_ptr())
-        capi.check(self.lib.vp_smooth_update_stream(self._s, p(kpts), p(ids), p(stream), p(rank), n, mask_of(step_mask, self.cfg.n_streams), _ptr(te), p(out),
-                                                    flags.data_ptr(), cs), self.engine._h)
+        self._check(self.lib.vp_smooth_update_stream(self._obj, ptr(kpts, n), ptr(ids, n), ptr(stream, n), ptr(rank, n), n, mask_of(step_mask, self.cfg.n_streams), ptr(te),
+                                                     ptr(out, n), flags.data_ptr(), self._stream()))
         return out, flags
 
     def update_host(self, kpts, ids, stream=None, rank=None, t_e=None, step_mask=None):
         """`update` on numpy arrays (vp_smooth_update: upload, the same kernels, download, synchronous) -> (out, flags)"""
         kpts, ids, stream, rank, te = _host_args(self.K, self.cfg.n_streams, kpts, ids, stream, rank, t_e)
         out, flags = np.empty_like(kpts), np.empty(self.cfg.n_streams, np.int32)
-        capi.check(self.lib.vp_smooth_update(self._s, _ptr(kpts), _ptr(ids), _ptr(stream), _ptr(rank), len(ids), mask_of(step_mask, self.cfg.n_streams), _ptr(te),
-                                             _ptr(out), flags.ctypes.data), self.engine._h)
+        self._check(self.lib.vp_smooth_update(self._obj, ptr(kpts), ptr(ids), ptr(stream), ptr(rank), len(ids), mask_of(step_mask, self.cfg.n_streams), ptr(te),
+                                              ptr(out), flags.ctypes.data))
         return out, flags
 
     def reset(self, streams=None):
         """zero the tables of `streams` (None: all) on torch's current stream"""
-        import torch
-        cs = torch.cuda.current_stream(torch.device('cuda', self.engine.device_id)).cuda_stream
-        capi.check(self.lib.vp_smoother_reset_stream(self._s, mask_of(streams, self.cfg.n_streams), cs), self.engine._h)
+        self._check(self.lib.vp_smoother_reset_stream(self._obj, mask_of(streams, self.cfg.n_streams), self._stream()))
 
     def state(self) -> np.ndarray:
         """the device state as a state_dtype(K) array [n_streams] (synchronous; for tests)"""
         out = np.zeros(self.cfg.n_streams, state_dtype(self.K))
-        capi.check(self.lib.vp_smoother_download_state(self._s, out.ctypes.data), self.engine._h)
+        self._check(self.lib.vp_smoother_download_state(self._obj, out.ctypes.data))
         return out
-
-    def close(self):
-        if getattr(self, '_s', None) and self.engine._h:
-            self.lib.vp_smoother_destroy(self._s)
-        self._s = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -17,6 +17,7 @@ import numbers
 import numpy as np
 
 from . import _capi as capi
+from ._stage import DeviceStage, check_tensor, handle_alias
 
 TRACK_MAX = 128
 TRACK_MAX_STREAMS = 64
@@ -160,13 +161,13 @@ def _host_out(n_out: int, n_streams: int):
     return (np.empty((n_out, 6), np.float32), np.empty(n_out, np.int32), np.empty(n_out, np.int32), np.empty(n_streams + 1, np.int32), np.empty(n_streams, np.int32))
 
 
-class DeviceTracker:
+class DeviceTracker(DeviceStage):
+    _destroy, _t = 'vp_tracker_destroy', handle_alias
+
     def __init__(self, engine, cfg: TrackCfg = TrackCfg()):
+        super().__init__(engine)
         self.cfg, self._c = cfg, c_config(cfg)
-        self.engine, self.lib = engine, engine.lib
-        h = C.c_void_p()
-        capi.check(self.lib.vp_tracker_create(engine._h, C.byref(self._c), C.byref(h)), engine._h)
-        self._t = h
+        self._create(self.lib.vp_tracker_create, C.byref(self._c))
         self._bound = RowBound(cfg.max_age, cfg.n_streams)
 
     def row_bound(self, n_dets: int, step=None) -> int:
@@ -184,17 +185,13 @@ class DeviceTracker:
         `n_dets`: an int32 CUDA tensor of one element, the detection count decided on the device (vp_tracker_update_counted_stream): only the first
         min(n_dets, n) rows are read -- the detector stage's rows, image and count[-1:] pass in place; the bound is recorded with n."""
         import torch
-        dev = torch.device('cuda', self.engine.device_id)
+        dev = self._dev
         if not (isinstance(dets, torch.Tensor) and dets.is_cuda and dets.dtype == torch.float32):
             raise TypeError('dets: a float32 torch CUDA tensor expected')
         if dets.device != dev or dets.ndim != 2 or dets.shape[1] < 5 or (dets.shape[0] > 0 and dets.stride(1) != 1):
             raise ValueError(f'dets: [n, >= 5] with contiguous rows on {dev} expected, got {tuple(dets.shape)} on {dets.device}')
         n = dets.shape[0]
-        if frame_index is not None:
-            if not (isinstance(frame_index, torch.Tensor) and frame_index.is_cuda and frame_index.dtype == torch.int32):
-                raise TypeError('frame_index: an int32 torch CUDA tensor expected')
-            if frame_index.device != dev or tuple(frame_index.shape) != (n,) or not frame_index.is_contiguous():
-                raise ValueError(f'frame_index: contiguous [{n}] on {dev} expected')
+        check_tensor('frame_index', frame_index, torch.int32, (n,), dev)
         mask = mask_of(step, self.cfg.n_streams)
         n_out = self.row_bound(n, mask) if n_out is None else int(n_out)
         if n_out < 0:
@@ -205,17 +202,16 @@ class DeviceTracker:
         stream = torch.empty((n_out,), dtype=torch.int32, device=dev)
         count = torch.empty((ns + 1,), dtype=torch.int32, device=dev)
         flags = torch.empty((ns,), dtype=torch.int32, device=dev)
-        cs = torch.cuda.current_stream(dev).cuda_stream
         io = (dets.data_ptr() if n else None, dets.stride(0) if n > 1 else max(dets.shape[1], 5), None if frame_index is None or n == 0 else frame_index.data_ptr(), n)
-        out = (mask, rows.data_ptr(), ids.data_ptr(), stream.data_ptr(), n_out, count.data_ptr(), flags.data_ptr(), cs)
+        out = (mask, rows.data_ptr(), ids.data_ptr(), stream.data_ptr(), n_out, count.data_ptr(), flags.data_ptr(), self._stream())
         if n_dets is None:
-            capi.check(self.lib.vp_tracker_update_stream(self._t, *io, *out), self.engine._h)
+            self._check(self.lib.vp_tracker_update_stream(self._obj, *io, *out))
         else:
             if not (isinstance(n_dets, torch.Tensor) and n_dets.is_cuda and n_dets.dtype == torch.int32):
                 raise TypeError('n_dets: an int32 torch CUDA tensor expected')
             if n_dets.device != dev or n_dets.numel() != 1:
                 raise ValueError(f'n_dets: one element on {dev} expected')
-            capi.check(self.lib.vp_tracker_update_counted_stream(self._t, *io, n_dets.data_ptr(), *out), self.engine._h)
+            self._check(self.lib.vp_tracker_update_counted_stream(self._obj, *io, n_dets.data_ptr(), *out))
         self._bound.push(n, bin(mask).count('1'))
         return rows, ids, stream, count, flags
 
@@ -225,35 +221,22 @@ class DeviceTracker:
         mask = mask_of(step, self.cfg.n_streams)
         n_out = self.row_bound(len(dets), mask) if n_out is None else int(n_out)
         out = _host_out(max(n_out, 0), self.cfg.n_streams)
-        capi.check(self.lib.vp_tracker_update(self._t, dets.ctypes.data if dets.size else None, dets.shape[1], None if fi is None else fi.ctypes.data, len(dets),
-                                              mask, *[a.ctypes.data for a in out[:3]], n_out, out[3].ctypes.data, out[4].ctypes.data), self.engine._h)
+        self._check(self.lib.vp_tracker_update(self._obj, dets.ctypes.data if dets.size else None, dets.shape[1], None if fi is None else fi.ctypes.data, len(dets),
+                                               mask, *[a.ctypes.data for a in out[:3]], n_out, out[3].ctypes.data, out[4].ctypes.data))
         self._bound.push(len(dets), bin(mask).count('1'))
         return out
 
     def reset(self, streams=None):
         """zero the state of `streams` (None: all) on torch's current stream: their ids restart at 1"""
-        import torch
-        cs = torch.cuda.current_stream(torch.device('cuda', self.engine.device_id)).cuda_stream
         mask = mask_of(streams, self.cfg.n_streams)
-        capi.check(self.lib.vp_tracker_reset_stream(self._t, mask, cs), self.engine._h)
+        self._check(self.lib.vp_tracker_reset_stream(self._obj, mask, self._stream()))
         self._bound.reset(bin(mask).count('1'))
 
     def state(self) -> np.ndarray:
         """the device state as a STATE_DTYPE array [n_streams] (synchronous; for tests)"""
         out = np.zeros(self.cfg.n_streams, STATE_DTYPE)
-        capi.check(self.lib.vp_tracker_download_state(self._t, out.ctypes.data), self.engine._h)
+        self._check(self.lib.vp_tracker_download_state(self._obj, out.ctypes.data))
         return out
-
-    def close(self):
-        if getattr(self, '_t', None) and self.engine._h:
-            self.lib.vp_tracker_destroy(self._t)
-        self._t = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class DeviceSort:

@@ -18,6 +18,7 @@ import os
 import numpy as np
 
 from . import _capi as capi
+from ._stage import DeviceStage, handle_alias
 
 MAX_IMAGES = 64
 MAX_SIDE = 1280
@@ -194,28 +195,27 @@ def yolo_decode_host(levels, nc: int, in_hw, head_dtype='fp32', head_layout=0):
     return head
 
 
-class DeviceYolo:
+class DeviceYolo(DeviceStage):
     """YOLOv8-detect on the engine's device.  ``state``: a state dict, or a path `load_yolo_state` reads.  ``in_hw``: the input size, multiples of 32.
     Callable on the letterboxed device tensor (fp16, [n, 3, H, W] under input_layout 'nchw', [n, H, W, 3] under 'nhwc', RGB, values / 255; n <= max_images):
     returns the head [n, 4 + nc, A] (head_layout 0) or [n, A, 4 + nc] of ``head_dtype``, a view of a device tensor this object owns.  ``keep_activations``
     (tests): every internal buffer in a region of its own, which `activation` needs; otherwise the regions are reused along the forward."""
 
+    _destroy, _y = 'vp_yolo_destroy', handle_alias
+
     def __init__(self, engine, state, in_hw=(640, 640), max_images: int = 1, input_layout: str = 'nchw', head_dtype: str = 'fp32', head_layout: int = 0,
                  keep_activations: bool = False):
         import torch
+        super().__init__(engine)
         if isinstance(state, (str, os.PathLike)):
             state = load_yolo_state(state)
-        self.engine, self.lib = engine, engine.lib
         self._c = _c_cfg(in_hw, max_images, input_layout, head_dtype, head_layout, keep_activations)
         self.in_hw, self.max_images, self.input_layout, self.head_dtype, self.head_layout = (self._c.in_h, self._c.in_w), int(max_images), input_layout, head_dtype, int(head_layout)
         tab, n, keep = _tensor_table(state)
-        h = C.c_void_p()
-        capi.check(self.lib.vp_yolo_create(engine._h, C.byref(self._c), tab, n, C.byref(h)), engine._h)
-        self._y = h
+        self._create(self.lib.vp_yolo_create, C.byref(self._c), tab, n)
         nc, A, nl, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
-        capi.check(self.lib.vp_yolo_info(h, C.byref(nc), C.byref(A), C.byref(nl), C.byref(nb)), engine._h)
+        self._check(self.lib.vp_yolo_info(self._obj, C.byref(nc), C.byref(A), C.byref(nl), C.byref(nb)))
         self.nc, self.A, self.n_launches, self.device_bytes = nc.value, A.value, nl.value, nb.value
-        self._dev = torch.device('cuda', engine.device_id)
         shape = (self.max_images, 4 + self.nc, self.A) if self.head_layout == 0 else (self.max_images, self.A, 4 + self.nc)
         self._head = torch.zeros(shape, dtype=torch.float16 if head_dtype == 'fp16' else torch.float32, device=self._dev)
 
@@ -232,8 +232,7 @@ class DeviceYolo:
         n = int(x.shape[0]) if x.dim() == 4 else -1
         if n < 0 or n > self.max_images or tuple(x.shape) != self.input_shape(n):
             raise ValueError(f'DeviceYolo: {self.input_shape("n")} with n <= {self.max_images} expected, got {tuple(x.shape)}')
-        cs = torch.cuda.current_stream(self._dev).cuda_stream
-        capi.check(self.lib.vp_yolo_forward_stream(self._y, x.data_ptr() if n else None, n, self._head.data_ptr() if n else None, cs), self.engine._h)
+        self._check(self.lib.vp_yolo_forward_stream(self._obj, x.data_ptr() if n else None, n, self._head.data_ptr() if n else None, self._stream()))
         return self._head[:n]
 
     def forward_host(self, x: np.ndarray) -> np.ndarray:
@@ -244,22 +243,11 @@ class DeviceYolo:
             raise ValueError(f'DeviceYolo: float16 {self.input_shape("n")} expected, got {x.dtype} {x.shape}')
         shape = (n, 4 + self.nc, self.A) if self.head_layout == 0 else (n, self.A, 4 + self.nc)
         head = np.empty(shape, NP_HEAD[self.head_dtype])
-        capi.check(self.lib.vp_yolo_forward(self._y, x.ctypes.data if n else None, n, head.ctypes.data if n else None), self.engine._h)
+        self._check(self.lib.vp_yolo_forward(self._obj, x.ctypes.data if n else None, n, head.ctypes.data if n else None))
         return head
 
     def activation(self, launch: int, n_images: int, buffer: dict) -> np.ndarray:
         """After a forward of n_images: the whole buffer launch `launch` of the plan wrote into ([n, h, w, c]; `buffer` = its row of `yolo_plan`)."""
         out = np.empty((n_images, buffer['h'], buffer['w'], buffer['c']), np.float16 if buffer['elem_bytes'] == 2 else np.float32)
-        capi.check(self.lib.vp_dbg_yolo_activation(self._y, int(launch), int(n_images), out.ctypes.data), self.engine._h)
+        self._check(self.lib.vp_dbg_yolo_activation(self._obj, int(launch), int(n_images), out.ctypes.data))
         return out
-
-    def close(self):
-        if getattr(self, '_y', None) and self.engine._h:
-            self.lib.vp_yolo_destroy(self._y)
-        self._y = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -14,6 +14,7 @@ import dataclasses
 from . import _capi as capi
 from . import moe
 from .configs import HEADS, HM_H, HM_W, IMG_H, IMG_W, ModelShape
+from ._stage import check_tensor, frame_on, stream_of
 from .cropprep import PIX_FORMATS, YUV_MATRIX_IDS, Frame
 from .posenms import PoseNms, resolve_sigmas
 from .posenms import c_config as nms_c_config
@@ -71,6 +72,16 @@ class PinnedArray:
             self.free()
         except Exception:
             pass
+
+
+def _check_boxes(t, dev, n):
+    """the box rows of the two draw entries: float32 CUDA [n, >= 4] on `dev`, unit column stride, any positive row stride (n = 'n': any count)"""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+        raise TypeError('boxes: a float32 torch CUDA tensor expected')
+    if (t.device != dev or t.ndim != 2 or n not in ('n', t.shape[0]) or t.shape[1] < 4 or (t.shape[0] > 0 and t.stride(1) != 1)
+            or (t.shape[0] > 1 and t.stride(0) < 1)):
+        raise ValueError(f'boxes: [{n}, >= 4] with unit column stride on {dev} expected, got {tuple(t.shape)} on {t.device}')
 
 
 class VitPoseHip:
@@ -433,9 +444,8 @@ class VitPoseHip:
             if device_only and not f.on_device:
                 raise TypeError(f'frame {i}: torch uint8 CUDA tensors expected')
             if f.on_device:
-                for p in f.planes:
-                    if p.device.index != self.device_id:
-                        raise ValueError(f'frame {i} lives on {p.device}, the handle on cuda:{self.device_id}')
+                import torch
+                frame_on(f, i, torch.device('cuda', self.device_id))
             p0, p1 = f.pointers()
             table[i] = capi.vp_image((C.c_void_p * 2)(p0, p1), (C.c_int64 * 2)(*f.pitch), f.h, f.w, PIX_FORMATS[f.format], YUV_MATRIX_IDS[f.matrix])
         return table
@@ -493,10 +503,7 @@ class VitPoseHip:
         row_stride = boxes.stride(0) if n > 1 else max(boxes.stride(0), 4)   # one row: its stride is never used
         fip = None
         if frame_index is not None:
-            if not (isinstance(frame_index, torch.Tensor) and frame_index.is_cuda and frame_index.dtype == torch.int32):
-                raise TypeError('frame_index: an int32 torch CUDA tensor expected')
-            if frame_index.device != dev or tuple(frame_index.shape) != (n,) or not frame_index.is_contiguous():
-                raise ValueError(f'frame_index: contiguous [{n}] on {dev} expected, got {tuple(frame_index.shape)} on {frame_index.device}')
+            check_tensor('frame_index', frame_index, torch.int32, (n,), dev)
             fip = frame_index.data_ptr()
         ids = None if datasets is None else self._dataset_ids(datasets, n)
         K = self.K if ids is None else self.Kmax
@@ -508,7 +515,7 @@ class VitPoseHip:
         cp = torch.empty((n, 9), dtype=torch.int32, device=dev) if crop_params or nms is not None else None
         st = torch.empty((n,), dtype=torch.int32, device=dev) if status or nms is not None else None
         bsc = None if nms is None else (box_scores if box_scores is not None else boxes[:, 4])
-        want_cs, cs = cs, torch.cuda.current_stream(dev).cuda_stream
+        want_cs, cs = cs, stream_of(dev)
         if affine:
             d_cs = torch.empty((n, 4), dtype=torch.float32, device=dev) if want_cs else None
             capi.check(self.lib.vp_infer_boxes_affine_stream(self._h, table, len(frames), boxes.data_ptr(), row_stride, fip, n, float(box_scale), out.data_ptr(),
@@ -541,23 +548,16 @@ class VitPoseHip:
         Returns (score float32 [n], rank int32 [n], count int32 [n_frames]): keep the rows with `rank >= 0`."""
         import torch
         dev = torch.device('cuda', self.device_id)
-
-        def want(t, name, dtype, shape_ok, what):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype):
-                raise TypeError(f'{name}: a {dtype} torch CUDA tensor expected')
-            if t.device != dev or not shape_ok(t):
-                raise ValueError(f'{name}: {what} on {dev} expected, got {tuple(t.shape)} on {t.device}')
-        want(keypoints, 'keypoints', torch.float32, lambda t: t.ndim == 3 and t.shape[2] == 3 and t.is_contiguous(), 'contiguous [n, K, 3]')
+        check_tensor('keypoints', keypoints, torch.float32, ('n', 'K', 3), dev, True)
         n, K = keypoints.shape[0], keypoints.shape[1]
-        want(box_scores, 'box_scores', torch.float32, lambda t: tuple(t.shape) == (n,) and (n < 2 or t.stride(0) >= 1), f'[{n}] with a positive stride')
-        want(crop_params, 'crop_params', torch.int32, lambda t: tuple(t.shape) == (n, 9) and t.is_contiguous(), f'contiguous [{n}, 9]')
-        if status is not None:
-            want(status, 'status', torch.int32, lambda t: tuple(t.shape) == (n,) and t.is_contiguous(), f'contiguous [{n}]')
+        check_tensor('box_scores', box_scores, torch.float32, (n,), dev, True, contiguous=False)
+        check_tensor('crop_params', crop_params, torch.int32, (n, 9), dev, True)
+        check_tensor('status', status, torch.int32, (n,), dev)
         c, keep = nms_c_config(cfg, self._nms_sigmas(cfg, K))
         score = torch.empty((n,), dtype=torch.float32, device=dev)
         rank = torch.empty((n,), dtype=torch.int32, device=dev)
         count = torch.empty((max(int(n_frames), 0),), dtype=torch.int32, device=dev)
-        cs = torch.cuda.current_stream(dev).cuda_stream
+        cs = stream_of(dev)
         capi.check(self.lib.vp_pose_nms_stream(self._h, keypoints.data_ptr(), n, K, box_scores.data_ptr(), box_scores.stride(0) if n > 1 else 1,
                                                crop_params.data_ptr(), None if status is None else status.data_ptr(), int(n_frames), C.byref(c),
                                                score.data_ptr(), rank.data_ptr(), count.data_ptr(), cs), self._h)
@@ -659,29 +659,20 @@ class VitPoseHip:
         Returns the frames as `Frame` objects."""
         import torch
         dev = torch.device('cuda', self.device_id)
-
-        def want(t, name, dtype, shape_ok, what):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype):
-                raise TypeError(f'{name}: a {dtype} torch CUDA tensor expected')
-            if t.device != dev or not shape_ok(t):
-                raise ValueError(f'{name}: {what} on {dev} expected, got {tuple(t.shape)} on {t.device}')
         if boxes is None:
             label_boxes(boxes)
-        want(boxes, 'boxes', torch.float32, lambda t: t.ndim == 2 and t.shape[1] >= 4 and (t.shape[0] == 0 or t.stride(1) == 1) and (t.shape[0] < 2 or t.stride(0) >= 1),
-             '[n, >= 4] with unit column stride')
+        _check_boxes(boxes, dev, 'n')
         n = boxes.shape[0]
         if n > LABEL_MAX_ROWS:
             raise ValueError(f'labels: {n} rows exceed the {LABEL_MAX_ROWS} records of one call')
-        want(frame_index, 'frame_index', torch.int32, lambda t: tuple(t.shape) == (n,) and (n < 2 or t.stride(0) >= 1), f'[{n}] with a positive stride')
-        for t, name in ((rank, 'rank'), (ids, 'ids')):
-            if t is not None:
-                want(t, name, torch.int32, lambda t: tuple(t.shape) == (n,) and t.is_contiguous(), f'contiguous [{n}]')
-        if scores is not None:
-            want(scores, 'scores', torch.float32, lambda t: tuple(t.shape) == (n,) and (n < 2 or t.stride(0) >= 1), f'[{n}] with a positive stride')
+        check_tensor('frame_index', frame_index, torch.int32, (n,), dev, True, contiguous=False)
+        check_tensor('rank', rank, torch.int32, (n,), dev)
+        check_tensor('ids', ids, torch.int32, (n,), dev)
+        check_tensor('scores', scores, torch.float32, (n,), dev, contiguous=False)
         c, keep = label_c_config(style)
         frames = [self._as_frame(f, i) for i, f in enumerate(frames)]
         table = self._image_table(frames, device_only=True)
-        cs = torch.cuda.current_stream(dev).cuda_stream
+        cs = stream_of(dev)
         capi.check(self.lib.vp_draw_labels_stream(self._h, table, len(frames), boxes.data_ptr(), 4 if n < 2 else boxes.stride(0), n, frame_index.data_ptr(),
                                                   frame_index.stride(0) if n > 1 else 1, None if rank is None else rank.data_ptr(),
                                                   None if ids is None else ids.data_ptr(), None if scores is None else scores.data_ptr(),
@@ -708,28 +699,20 @@ class VitPoseHip:
         own; needs `boxes`), `scores` its scores; None (the default) draws no tag.  Returns the frames as `Frame` objects."""
         import torch
         dev = torch.device('cuda', self.device_id)
-
-        def want(t, name, dtype, shape_ok, what):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype):
-                raise TypeError(f'{name}: a {dtype} torch CUDA tensor expected')
-            if t.device != dev or not shape_ok(t):
-                raise ValueError(f'{name}: {what} on {dev} expected, got {tuple(t.shape)} on {t.device}')
-        want(keypoints, 'keypoints', torch.float32, lambda t: t.ndim == 3 and t.shape[2] == 3 and t.is_contiguous(), 'contiguous [n, K, 3]')
+        check_tensor('keypoints', keypoints, torch.float32, ('n', 'K', 3), dev, True)
         n, K = keypoints.shape[0], keypoints.shape[1]
-        want(frame_index, 'frame_index', torch.int32, lambda t: tuple(t.shape) == (n,) and (n < 2 or t.stride(0) >= 1), f'[{n}] with a positive stride')
-        for t, name in ((rank, 'rank'), (ids, 'ids')):
-            if t is not None:
-                want(t, name, torch.int32, lambda t: tuple(t.shape) == (n,) and t.is_contiguous(), f'contiguous [{n}]')
+        check_tensor('frame_index', frame_index, torch.int32, (n,), dev, True, contiguous=False)
+        check_tensor('rank', rank, torch.int32, (n,), dev)
+        check_tensor('ids', ids, torch.int32, (n,), dev)
         if boxes is not None:
-            want(boxes, 'boxes', torch.float32, lambda t: t.ndim == 2 and t.shape[0] == n and t.shape[1] >= 4 and (n == 0 or t.stride(1) == 1) and (n < 2 or t.stride(0) >= 1),
-                 f'[{n}, >= 4] with unit column stride')
+            _check_boxes(boxes, dev, n)
         c, keep = draw_c_config(style, self._draw_skeleton(style, K))
         check_records(n, K, keep[0].shape[0], boxes is not None)
         frames = [self._as_frame(f, i) for i, f in enumerate(frames)]
         table = self._image_table(frames, device_only=True)
         if labels is not None:   # the tags first, the skeletons over them: the reference's order
             self.draw_labels(frames, label_boxes(boxes), frame_index, overlay_label_style(labels, style), rank=rank, ids=ids, scores=scores)
-        cs = torch.cuda.current_stream(dev).cuda_stream
+        cs = stream_of(dev)
         capi.check(self.lib.vp_draw_poses_stream(self._h, table, len(frames), keypoints.data_ptr(), n, K, frame_index.data_ptr(), frame_index.stride(0) if n > 1 else 1,
                                                  None if rank is None else rank.data_ptr(), None if ids is None else ids.data_ptr(),
                                                  None if boxes is None else boxes.data_ptr(), 4 if boxes is None or n < 2 else boxes.stride(0), C.byref(c), cs), self._h)

@@ -8,7 +8,8 @@
 // 256, and asserts: every offset = skew (mod 256); parts in order, disjoint, each with room for up256(bytes); total >= the end of the last part + 256.  The block is
 // a heap block of exactly total() bytes and the room of every part is written and read back, so a part past the block or over another part is a heap overflow or a
 // wrong byte.  A plane is a heap block of exactly plane_bytes() and every row of it is written.  At the largest counts the entries accept the arithmetic is compared
-// with 128-bit integers (nothing is allocated).  Exit status 0, "stage layout ok" and no sanitizer report is the pass (tests/test_stage_layout_host.py).
+// with 128-bit integers (nothing is allocated).  Then the mask part of csrc/stageobj.h (popcount64, mask_check) on the masks at the edges of n_streams = 1 and 64.
+// Exit status 0, "stage layout ok" and no sanitizer report is the pass (tests/test_stage_layout_host.py).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "../easy_vitpose_amd/csrc/hoststage.h"
+#include "../easy_vitpose_amd/csrc/stageobj.h"
 
 using vpi::plane_bytes;
 using vpi::plane_count;
@@ -226,6 +228,26 @@ int main() {
     check(site = "vp_yolo_forward", yolo_forward(64, 1280, 1280, 256, (size_t)1 << 20, 4));
     check(site = "vp_dbg_pose_oks", pose_oks(32768, 1024));
 
-    std::printf("stage layout ok (%ld layouts)\n", n_layouts);
+    // the mask part of csrc/stageobj.h: no mask, the last stream, the first bit beyond it, all 64 bits, at n_streams 1 and 64 (a shift by 64 would be undefined)
+    site = "mask_check";
+    int n_masks = 0;
+    for (int ns : {1, 64}) {
+        const uint64_t last = 1ull << (ns - 1), all = ~0ull;
+        std::string why;
+        REQUIRE(vpi::mask_check(0, ns, "tracker: ", &why) == VP_OK && vpi::mask_check(last, ns, "tracker: ", &why) == VP_OK && why.empty());
+        REQUIRE(vpi::popcount64(0) == 0 && vpi::popcount64(last) == 1 && vpi::popcount64(all) == 64);
+        n_masks += 2;
+        if (ns < 64) {   // bit n_streams exists
+            REQUIRE(vpi::mask_check(1ull << ns, ns, "tracker: ", &why) == VP_ERR_INVALID && why == "tracker: a mask bit beyond n_streams = 1");
+            REQUIRE(vpi::mask_check(all, ns, "smoother: ", &why) == VP_ERR_INVALID && why == "smoother: a mask bit beyond n_streams = 1");
+            REQUIRE(vpi::popcount64(1ull << ns) == 1);
+            n_masks += 2;
+        } else {
+            REQUIRE(vpi::mask_check(all, ns, "smoother: ", &why) == VP_OK && why.empty());
+            ++n_masks;
+        }
+    }
+
+    std::printf("stage layout ok (%ld layouts, %d masks)\n", n_layouts, n_masks);
     return 0;
 }
